@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""bench.py -- MFCC frames/sec (512-pt, 32 mel, 13 coeff) on N MI355X; % of HBM roofline.
+"""bench.py -- MFCC frames/sec (512-pt, 32 mel, 13 coeff) on N MI355X; with --full also % of HBM roofline.
 
     python bench.py --gpus N --steps K --warmup W        # N > 1: spawns one child process per GPU itself
+    python bench.py --gpus N --steps K --warmup W --full # + roofline, ceilings, CPU baseline, configs 3 / 4 / 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W     # the same ranks under torchrun
 
@@ -12,8 +13,13 @@ A "step" = one pass of the hot path over the rank's batch, input and output resi
 Each rank owns its own batch (weak scaling, frames shard with no data-path collective --
 SURVEY.md 8e); value = frames of all ranks / max-over-ranks time.
 
-The default line also carries, as sub-objects measured the same way (barrier + synchronize around K steps, HIP events
-for the kernel, skip each with --no-configN):
+A plain run sets up, warms up, times the K steps and prints the headline: `value`, `ms_per_step` and the workload.
+`--dump-outputs DIR` then writes what the last timed step computed as DIR/mfcc.npy (float32; all rows of rank 0's output
+when they fit in DUMP_BYTES, else a fixed sample of whole frames drawn with seed 0, in order).  Inputs are seeded, so
+two builds given the same arguments compute on the same data.
+
+`--full` adds everything else, each in runs of its own after the timed steps.  Its line carries, as sub-objects
+measured the same way (barrier + synchronize around K steps, HIP events for the kernel, skip each with --no-configN):
   `config3`  BASELINE.json configs[2]: the fixed-point kernel (RTL arithmetic, STREAM framing, 366 B/frame) on the same batch;
   `config4`  configs[3]: 64 channels x 1 h, nfft 1024 / hop 341 / 40 mel / 13 coeff (10.8 M frames, 734 B/frame);
   `config5`  configs[4]: ONE fixed corpus of 10 000 utterances x 10 s (seed = utterance id), sharded by utterance over the
@@ -22,9 +28,10 @@ for the kernel, skip each with --no-configN):
              as its own field, never inside `value`.
 `--config 3|4|5` runs one of them as the headline instead.
 
-Prints ONE JSON line (rank 0) with `roofline` (algorithmic bytes per frame over the kernel's HIP-event duration,
-against the 8 TB/s HBM peak) and `cpu_baseline` (the oracle's restatement of the reference notebook's NumPy path
-timed on this host, on a bounded sample of the same workload and on the reference's own wav, config 1's input).
+Prints ONE JSON line (rank 0); with `--full` it also holds `roofline` (algorithmic bytes per frame over the kernel's
+HIP-event duration, against the 8 TB/s HBM peak), `valu_roofline` / `alu_roofline` and `cpu_baseline` (the oracle's
+restatement of the reference notebook's NumPy path timed on this host, on a bounded sample of the same workload and on
+the reference's own wav, config 1's input).
 """
 import argparse
 import json
@@ -44,6 +51,7 @@ SPEC_CLOCK_GHZ = 2.4           # MI355X_MICROARCH.md: max clock; the clock held 
 C5_UTTS, C5_SAMPLES = 10_000, 160_000     # config 5: 10 000 utterances of 10 s
 PREWARM_S = 0.4                # launches before anything is timed, whatever --warmup says: the clocks of an idle
                                # MI355X ramp over the first ~100 ms of work (round 1: 5 warm-up steps read 5 % slow)
+DUMP_BYTES = 32 << 20          # --dump-outputs: at most this many bytes of coefficients
 
 # the batched configurations (BASELINE.json configs[1..3]); bytes per frame = hop x 2 B in + n_cep x 4 | 2 B out
 BATCH = {
@@ -73,12 +81,18 @@ def parse_args(argv=None):
     ap.add_argument("--channels", type=int, default=64, help="configs 2-4: channels per GPU per step")
     ap.add_argument("--utterances", type=int, default=C5_UTTS, help="config 5: corpus size")
     ap.add_argument("--impl", default="auto", choices=["auto", "generic", "fused512"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-config3", action="store_true", help="default run: leave out the config3 sub-object")
-    ap.add_argument("--no-config4", action="store_true", help="default run: leave out the config4 sub-object")
-    ap.add_argument("--no-config5", action="store_true", help="default run: leave out the config5 sub-object")
-    ap.add_argument("--only", action="store_true", help="default run: no sub-objects at all (profiling passes)")
-    ap.add_argument("--no-gather", action="store_true", help="config 5: do not time the result gather")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check the rest: kernel time by HIP events, roofline and "
+                         "ceilings, finite output, CPU baseline, the config3 / config4 / config5 sub-objects (config 2), "
+                         "host enqueue and result gather (config 5)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the coefficients of the last timed step (rank 0) as DIR/mfcc.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
+    ap.add_argument("--no-config3", action="store_true", help="--full, config 2: leave out the config3 sub-object")
+    ap.add_argument("--no-config4", action="store_true", help="--full, config 2: leave out the config4 sub-object")
+    ap.add_argument("--no-config5", action="store_true", help="--full, config 2: leave out the config5 sub-object")
+    ap.add_argument("--only", action="store_true", help="--full, config 2: no sub-objects at all (profiling passes)")
+    ap.add_argument("--no-gather", action="store_true", help="--full, config 5: do not time the result gather")
     ap.add_argument("--fixed", action="store_true", help="same as --config 3 (config 5: the fixed-point kernel)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse the "
@@ -399,6 +413,21 @@ def noise_batch(cx, nch, n, seed):
     return pcm
 
 
+def dump_outputs(dump_dir, out):
+    """--dump-outputs: the coefficients `out` holds (what the caller of the timed path receives) as dump_dir/mfcc.npy,
+    float32 rows of n_cep values.  An output larger than DUMP_BYTES is sampled: a fixed set of whole frames (rows of the
+    flattened output, drawn with seed 0 and kept in order), the same set for the same arguments."""
+    import numpy as np
+    import torch
+    rows = out.reshape(-1, out.shape[-1])
+    keep = DUMP_BYTES // (rows.shape[1] * 4)
+    if rows.shape[0] > keep:
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))
+        rows = rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "mfcc.npy"), rows.float().cpu().numpy())
+
+
 # ------------------------------------------------------------------------------------------------ configs 2, 3, 4
 
 def bench_batch(cx, args, cid, steps, warmup, pcm=None, with_cpu=False, headline=False):
@@ -420,10 +449,13 @@ def bench_batch(cx, args, cid, steps, warmup, pcm=None, with_cpu=False, headline
 
     cx.prewarm(run)
     dt = cx.timed(run, steps, warmup)
-    # dominant kernel's launch duration, HIP events on the launch stream (rank-local)
-    kernel_ms = m.time_launches(pcm, out, fixed=fixed, warmup=1, iters=max(3, min(steps, 10)))
+    if headline and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     bpf = bytes_per_frame(c)
-    assert bool(torch.isfinite(out.float()).all()), "non-finite coefficients in bench output"
+    if args.full:
+        # dominant kernel's launch duration, HIP events on the launch stream (rank-local)
+        kernel_ms = m.time_launches(pcm, out, fixed=fixed, warmup=1, iters=max(3, min(steps, 10)))
+        assert bool(torch.isfinite(out.float()).all()), "non-finite coefficients in bench output"
 
     pcie = None
     if rank == 0 and args.host_io and headline:
@@ -446,7 +478,6 @@ def bench_batch(cx, args, cid, steps, warmup, pcm=None, with_cpu=False, headline
     line = None
     if rank == 0:
         kname = m.kernel_name(fixed=fixed)
-        roof, fig = roofline(frames, bpf, kernel_ms, kname)
         line = {
             "metric": "MFCC frames/sec (%d-pt, %d mel, %d coeff)" % (c["nfft"], c["nmel"], c["ncep"]),
             "value": round(frames * world * steps / dt, 1),
@@ -471,10 +502,11 @@ def bench_batch(cx, args, cid, steps, warmup, pcm=None, with_cpu=False, headline
                 "fallback": m.is_fallback(fixed=fixed),      # a generic kernel runs: 3-6 x slower
                 "prewarm_s": PREWARM_S,
             },
-            "roofline": roof,
             "cpu_baseline": None,
         }
-        line.update(compute_ceilings(torch, dev, frames, kernel_ms, kname, fig, fixed))
+        if args.full:
+            line["roofline"], fig = roofline(frames, bpf, kernel_ms, kname)
+            line.update(compute_ceilings(torch, dev, frames, kernel_ms, kname, fig, fixed))
         if pcie:
             line["pcie_inclusive"] = pcie
         if with_cpu:
@@ -503,7 +535,7 @@ def bench_batch(cx, args, cid, steps, warmup, pcm=None, with_cpu=False, headline
 
 # ------------------------------------------------------------------------------------------------ config 5
 
-def bench_config5(cx, args, steps, warmup, with_cpu):
+def bench_config5(cx, args, steps, warmup, with_cpu, headline=False):
     """ONE fixed corpus (seed = utterance id), sharded by utterance; one launch per rank per step."""
     import numpy as np
     import mfcc_amd
@@ -529,48 +561,50 @@ def bench_config5(cx, args, steps, warmup, with_cpu):
 
     cx.prewarm(run)
     dt = cx.timed(run, steps, warmup)
-    kernel_ms = m.time_launches(flat[:len(mine) * n].view(len(mine), n), out.view(len(mine), per, NCEP),
-                                fixed=fixed, warmup=1, iters=max(3, min(steps, 10)))
-    assert bool(torch.isfinite(out.float()).all()), "non-finite coefficients in bench output"
+    if headline and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    enq = gather = None
+    if args.full:
+        kernel_ms = m.time_launches(flat[:len(mine) * n].view(len(mine), n), out.view(len(mine), per, NCEP),
+                                    fixed=fixed, warmup=1, iters=max(3, min(steps, 10)))
+        assert bool(torch.isfinite(out.float()).all()), "non-finite coefficients in bench output"
 
-    # what the host needs per step, against the kernel it feeds: this rank's shard, and -- on one GPU -- the shard an
-    # 8-GPU run would give every rank (n_utt / 8 utterances: a kernel of ~0.3 ms), so that a host-bound step shows
-    # before there is an 8-GPU node to show it on
-    enq = {"this_rank": {"utterances": len(mine), "enqueue_us_per_step": round(cx.enqueue_us(run, 40), 1),
-                         "kernel_us": round(kernel_ms * 1e3, 1)}}
-    if world == 1 and n_utt >= 8:
-        k8 = n_utt // 8
-        c8, o8, out8 = flat[:k8 * n], offsets[:k8 + 1], out[:k8 * per]
-        run8 = lambda: m.process_packed(c8, o8, fixed=fixed, out=out8)
-        t8 = cx.timed(run8, 40, 5)
-        ms8 = m.time_launches(c8.view(k8, n), out8.view(k8, per, NCEP), fixed=fixed, warmup=1, iters=10)
-        enq["shard_of_8"] = {"utterances": k8, "enqueue_us_per_step": round(cx.enqueue_us(run8, 40), 1),
-                             "kernel_us": round(ms8 * 1e3, 1), "step_us": round(t8 / 40 * 1e6, 1)}
-    for v in enq.values():
-        v["host_bound"] = v["enqueue_us_per_step"] > v["kernel_us"]
+        # what the host needs per step, against the kernel it feeds: this rank's shard, and -- on one GPU -- the shard an
+        # 8-GPU run would give every rank (n_utt / 8 utterances: a kernel of ~0.3 ms), so that a host-bound step shows
+        # before there is an 8-GPU node to show it on
+        enq = {"this_rank": {"utterances": len(mine), "enqueue_us_per_step": round(cx.enqueue_us(run, 40), 1),
+                             "kernel_us": round(kernel_ms * 1e3, 1)}}
+        if world == 1 and n_utt >= 8:
+            k8 = n_utt // 8
+            c8, o8, out8 = flat[:k8 * n], offsets[:k8 + 1], out[:k8 * per]
+            run8 = lambda: m.process_packed(c8, o8, fixed=fixed, out=out8)
+            t8 = cx.timed(run8, 40, 5)
+            ms8 = m.time_launches(c8.view(k8, n), out8.view(k8, per, NCEP), fixed=fixed, warmup=1, iters=10)
+            enq["shard_of_8"] = {"utterances": k8, "enqueue_us_per_step": round(cx.enqueue_us(run8, 40), 1),
+                                 "kernel_us": round(ms8 * 1e3, 1), "step_us": round(t8 / 40 * 1e6, 1)}
+        for v in enq.values():
+            v["host_bound"] = v["enqueue_us_per_step"] > v["kernel_us"]
 
-    # the one collective of the path, outside `value`: every rank's rows to rank 0 (RCCL over xGMI with nccl)
-    gather = None
-    if cx.grouped and not args.no_gather:
-        loc = out.float() if args.backend == "nccl" else out.float().cpu()
-        md.gather_frames(loc, NCEP, dst=0)                         # warm-up (communicator setup)
-        torch.cuda.synchronize()
-        cx.barrier()
-        t0 = time.perf_counter()
-        full = md.gather_frames(loc, NCEP, dst=0)
-        torch.cuda.synchronize()
-        cx.barrier()
-        tg = cx.max_over_ranks(time.perf_counter() - t0)
-        if rank == 0:
-            assert full.shape[0] == frames_total
-            gather = {"ms": round(tg * 1e3, 3), "bytes": frames_total * NCEP * 4, "backend": args.backend,
-                      "what": "gather_frames(dst=0): all ranks' [frames, 13] fp32 rows to rank 0, once, outside value"}
+        # the one collective of the path, outside `value`: every rank's rows to rank 0 (RCCL over xGMI with nccl)
+        if cx.grouped and not args.no_gather:
+            loc = out.float() if args.backend == "nccl" else out.float().cpu()
+            md.gather_frames(loc, NCEP, dst=0)                         # warm-up (communicator setup)
+            torch.cuda.synchronize()
+            cx.barrier()
+            t0 = time.perf_counter()
+            full = md.gather_frames(loc, NCEP, dst=0)
+            torch.cuda.synchronize()
+            cx.barrier()
+            tg = cx.max_over_ranks(time.perf_counter() - t0)
+            if rank == 0:
+                assert full.shape[0] == frames_total
+                gather = {"ms": round(tg * 1e3, 3), "bytes": frames_total * NCEP * 4, "backend": args.backend,
+                          "what": "gather_frames(dst=0): all ranks' [frames, 13] fp32 rows to rank 0, once, outside value"}
 
     res = None
     if rank == 0:
         bpf = HOP * 2 + NCEP * (2 if fixed else 4)
         kname = m.kernel_name(fixed=fixed)
-        roof, fig = roofline(frames_local, bpf, kernel_ms, kname)
         res = {
             "metric": "MFCC frames/sec (512-pt, 32 mel, 13 coeff)",
             "value": round(frames_total * steps / dt, 1),
@@ -595,12 +629,12 @@ def bench_config5(cx, args, steps, warmup, with_cpu):
                 "kernel": kname,
                 "fallback": m.is_fallback(fixed=fixed),
             },
-            "roofline": roof,
-            "host_enqueue": enq,
-            "gather": gather,
             "cpu_baseline": None,
         }
-        res.update(compute_ceilings(torch, dev, frames_local, kernel_ms, kname, fig, fixed))
+        if args.full:
+            res["roofline"], fig = roofline(frames_local, bpf, kernel_ms, kname)
+            res.update(host_enqueue=enq, gather=gather)
+            res.update(compute_ceilings(torch, dev, frames_local, kernel_ms, kname, fig, fixed))
         if with_cpu:
             k = min(len(mine), 256)
             rows = out.view(len(mine), per, NCEP)
@@ -622,9 +656,9 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
     cx = Ctx(args)
-    with_cpu = not args.no_cpu_baseline
+    with_cpu = args.full and not args.no_cpu_baseline
     if args.config == 5:
-        line = bench_config5(cx, args, args.steps, args.warmup, with_cpu=with_cpu)
+        line = bench_config5(cx, args, args.steps, args.warmup, with_cpu=with_cpu, headline=True)
     elif args.config in (3, 4):
         line = bench_batch(cx, args, args.config, args.steps, args.warmup, with_cpu=with_cpu, headline=True)
     else:
@@ -632,7 +666,7 @@ def main():
         pcm = noise_batch(cx, args.channels, BATCH[2]["samples"], 1234 + cx.rank)
         line = bench_batch(cx, args, 2, args.steps, args.warmup, pcm=pcm, with_cpu=with_cpu, headline=True)
         subs = {}
-        if not (args.only or args.host_io):
+        if args.full and not (args.only or args.host_io):
             if not args.no_config3:                   # the same batch through the fixed-point kernel
                 subs["config3"] = bench_batch(cx, args, 3, sub_steps, 2, pcm=pcm)
             del pcm

@@ -50,10 +50,10 @@ def test_bench_only_uses_the_oracle_for_the_cpu_baseline():
     i = src.index("from oracle import")
     j = src.rindex("\ndef ", 0, i)
     assert src[j:].startswith("\ndef cpu_baseline("), "the oracle import must sit inside the cpu_baseline leg"
-    # and that leg only runs when asked for, on rank 0, outside the timed regions
+    # and that leg only runs when asked for (--full), on rank 0, outside the timed regions
     # the definition, two guarded call sites on the batch (the sample and config 1's wav) and one on the corpus
     assert src.count("cpu_baseline(") == 4
-    assert "with_cpu = not args.no_cpu_baseline" in src and src.count("if with_cpu:") == 2
+    assert "with_cpu = args.full and not args.no_cpu_baseline" in src and src.count("if with_cpu:") == 2
     for call in re.finditer(r"= cpu_baseline\(", src):
         head = src.rfind("if with_cpu:", 0, call.start())
         assert head >= 0 and src.count("\ndef ", head, call.start()) == 0, "unguarded cpu_baseline call"

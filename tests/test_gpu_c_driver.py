@@ -28,9 +28,7 @@ def c_driver():
 
 
 def _run(*args):
-    env = dict(os.environ)
-    env.pop("LD_PRELOAD", None)
-    r = subprocess.run(list(args), capture_output=True, text=True, timeout=300, env=env)
+    r = subprocess.run(list(args), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
     return r.stdout
 

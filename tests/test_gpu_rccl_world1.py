@@ -1,5 +1,5 @@
 """The multi-GPU path's one collective on RCCL itself.  One GPU allows a world of one rank: `init_process_group("nccl")`,
-`dist.gather_frames` both ways (all_gather / gather to rank 0), and one `bench.py --config 5` run inside the group
+`dist.gather_frames` both ways (all_gather / gather to rank 0), and one `bench.py --config 5 --full` run inside the group
 (barrier, max-over-ranks all_reduce and the timed result gather all go through RCCL).  Child processes, so a wedged
 communicator cannot take the test session with it.  The N > 1 logic is covered by tests/test_dist_gloo.py."""
 import json
@@ -60,7 +60,7 @@ def test_gather_frames_over_rccl_world_of_one():
 def test_bench_config5_step_inside_an_rccl_group():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "5", "--gpus", "1", "--group",
                         "--backend", "nccl", "--utterances", "1250", "--steps", "5", "--warmup", "2",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=_env())
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=_env())
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     b = json.loads(r.stdout.strip().splitlines()[-1])
     assert b["n_gpus"] == 1 and b["scaling"] == "strong" and b["config"]["frames_per_step"] == 1250 * 939

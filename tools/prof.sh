@@ -6,7 +6,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
-timeout -k 10 400 python3 bench.py $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err || exit 1
+timeout -k 10 400 python3 bench.py --full $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err || exit 1
 tail -c 600 $OUT/bench.json; echo
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 bench.py --steps 30 --warmup 3 --no-cpu-baseline --only $BENCH_ARGS > $OUT/kt.log 2>&1 || exit 2
 echo kt done

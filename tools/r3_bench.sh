@@ -4,7 +4,7 @@
 set -o pipefail
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r3b
 mkdir -p $OUT; cd $GRAFT_REPO_ROOT
-run() { name=$1; shift; timeout -k 10 500 python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "$name FAILED"; tail -5 $OUT/$name.err; }; }
+run() { name=$1; shift; timeout -k 10 500 python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "$name FAILED"; tail -5 $OUT/$name.err; }; }
 run bench_driver --steps 20 --warmup 5
 run bench_default
 run bench_c3 --config 3
