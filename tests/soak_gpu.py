@@ -8,25 +8,22 @@ kernel against oracle/mfcc_fixed.py, bit for bit, EVERY signal kind.  Float cont
 rates, 16-filter banks) and 1024 (its per-rate schedules) kernels AND the generic kernel, each against the float64
 oracle on every channel, and against each other.
 
-How the float comparison is made (round 3; round 2 set aside whole FRAMES, 0.17 % of them).  Every handle also runs
-with all n_mel coefficients, so the DCT (orthonormal) can be undone: log-mel = coefficients @ B.  The error is taken
-band by band in the log-mel domain, the bands that are beyond fp32's reach are zeroed, and what is left is carried
-back through the DCT and held to the contract: 1e-4 of the largest coefficient.  A band is beyond reach when its
-energy is below 1e-7 of the frame's MEAN BIN POWER: a band that is a single complex FFT bin (44.1 / 48 kHz have
-several) cancels that far about once in 1e7 band-frames, and an fp32 FFT's error there -- 1e-7 of the frame's rms --
-is then as large as the band itself (tools/replay_band.py on case 10050240: bin 2 at 2.9e-12 next to 4e-4; both
-kernels off by 0.04..0.06 in log2).  DC-only bands are NEVER set aside: that bin is summed exactly.
-The summary counts the bands set aside and prints the largest log-mel error inside that set.  The kernel with the
-drawn n_cep is compared with the first n_cep columns of the all-coefficient run (1e-6: the same log-mel values
-through more DCT rows).  Frames with a silent band (-inf log-mel) are compared by their -inf / NaN pattern, exactly.
-DC / square / sine inputs have mel bands at the fp32 noise floor where fp32 FFTs legitimately differ from float64
-after the log: for the float contract their error is collected and its distribution printed,
-not counted, unless FUZZ_STRICT is set.  No sample rate is masked.
+How the float comparison is made: every float result -- the drawn n_cep, and all n_mel coefficients on the same
+kernel and on the generic kernel -- is held to the per-coefficient error bound of the kernel's declared arithmetic
+(oracle/error_bound.py, check()): each coefficient of each frame within the bound carried from the float64 oracle's
+stages, frames with a silent band (-inf log-mel) to the oracle's exact -inf / NaN pattern.  Nothing is set aside:
+DC, square and sine channels count under the float contract like the noise-like ones, at every sample rate, and the
+fused 1024 kernel is compared on every frame.  The only frames the bound leaves free are those where the model
+itself cannot tell a band from 0 (a constant input's bands away from DC: float64 roundoff of an exact zero); the
+summary counts them.  The drawn n_cep is also compared with the first n_cep columns of the
+all-coefficient run (1e-6: the same log-mel values through more DCT rows).  The summary prints the worst ratio
+|error| / bound per kernel and signal kind.
 Every case has its own seed, printed with the failure: `python tests/soak_gpu.py --case SEED` replays it.
 FUZZ_FIXED=1 restricts the run to the fixed contract."""
 import os, sys, time, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # repo root
 import torch, mfcc_amd
+from oracle import error_bound as eb
 from oracle import mfcc_fixed as mx
 from oracle import mfcc_float as mf
 
@@ -43,11 +40,9 @@ def signal(rng, n, kind):
     return np.clip(x, -32768, 32767).astype(np.int16)
 
 
-ILL = [0, 0]       # bands of noise-like channels set aside / compared (see the docstring)
-EXCL_MAX = [0.0]   # largest |log-mel error| inside the set-aside bands (noise-like channels)
-HARD = []          # DC / square / sine channels, float contract: max coefficient error / max |coefficient|, per channel
-FRAMES_1K = [0, 0]  # fused 1024 kernel (n_cep <= 32 < n_mel): frames with a band set aside / frames compared
-REACH = 1e-7       # a band below this fraction of the frame's mean bin power is beyond fp32's reach
+WORST = {}         # (kernel, signal kind) -> largest |error| / bound seen (see the docstring)
+FREE = [0, 0]      # float frames the model leaves unconstrained (a band's bound reaches its energy) / frames checked
+KIND_NAMES = ["gauss", "uniform", "silence", "dc", "square", "sine"]
 
 
 def pattern_ok(a, b):
@@ -57,28 +52,17 @@ def pattern_ok(a, b):
     return True, ""
 
 
-def band_compare(g_full, ref_full, st, B, noise_like):
-    """g_full / ref_full: (frames, n_mel) coefficients; st: the oracle's stages.  Returns (ok, why, rel err, frames
-    that have a band set aside)."""
-    g = g_full.astype(np.float64)
-    ok, why = pattern_ok(g, ref_full)
-    if not ok: return False, why, np.inf, None
-    rows = np.isfinite(ref_full).all(axis=1)
-    if not rows.any(): return True, "", 0.0, np.zeros(len(ref_full), bool)
-    mel, lm = st["mel"][rows], st["logmel"][rows]
-    dl = g[rows] @ B - lm                                        # per-band log-mel error
-    w = st["filters"]
-    dc_only = (w[:, 0] > 0) & (np.count_nonzero(w[:, 1:], axis=1) == 0)
-    out = (mel < REACH * st["power"][rows].mean(axis=1, keepdims=True)) & ~dc_only[None, :]
-    if noise_like:
-        ILL[0] += int(out.sum()); ILL[1] += out.size
-        if out.any(): EXCL_MAX[0] = max(EXCL_MAX[0], float(np.abs(dl[out]).max()))
-    dl = np.where(out, 0.0, dl)
-    dc = dl @ B.T                                                # back through the DCT: the coefficient error of the kept bands
-    rel = float(np.abs(dc).max() / max(np.abs(ref_full[rows]).max(), 1.0))
-    aside = np.zeros(len(ref_full), bool)
-    aside[np.flatnonzero(rows)[out.any(axis=1)]] = True
-    return rel <= 1e-4, "err %.3g of the largest coefficient" % rel, rel, aside
+def bound_check(name, kind, g, ref, bound):
+    """check() of one channel; returns a failure string or None, and records the ratio in WORST."""
+    try:
+        r = eb.check(g, ref, bound, name)
+    except AssertionError as e:
+        return str(e)[:600]
+    free = eb.unbounded_frames(bound)
+    FREE[0] += int(free.sum()); FREE[1] += len(free)
+    key = (name, KIND_NAMES[kind])
+    WORST[key] = max(WORST.get(key, 0.0), r)
+    return None
 
 
 def one_case(seed):
@@ -140,7 +124,6 @@ def one_case(seed):
         name_a = a.kernel_name()
     if ga.shape[1] == 0:
         return fails                               # no frame: nothing to compare
-    B = mf.dct_basis(nmel, nmel)
     for c in range(nch):
         x = flat[off + c * stride: off + c * stride + n + halo]
         xs = np.concatenate([np.zeros(hop - 1, np.int16), x]) if halo else x
@@ -154,24 +137,17 @@ def one_case(seed):
             st = {k: (v[1:] if k in ("power", "mel", "logmel") else v) for k, v in st.items()}
         if halo and len(ref) == gaf.shape[1] - 1 and n < nfft:
             continue      # a shard shorter than a frame: the oracle's stream, one hop longer, has no frame of its own here
-        noise_like = kinds[c] < 3
-        worst, aside = 0.0, None
-        for name, g in zip(names, (gaf[c], gbf[c])):
+        runs = [(names[0], gaf[c], nmel), (names[1], gbf[c], nmel), (name_a, ga[c], ncep)]
+        for name, g, k in runs:
             if len(g) != len(ref):
                 fails.append("FLOAT %s %s ch %d: %d frames, oracle %d" % (name, tag, c, len(g), len(ref)))
                 continue
-            ok, why, rel, asd = band_compare(g, ref, st, B, noise_like)
-            worst = max(worst, rel)
-            aside = asd if aside is None else aside
-            if not ok and (noise_like or os.environ.get("FUZZ_STRICT")):
-                fails.append("FLOAT %s vs float64 oracle %s ch %d: %s" % (name, tag, c, why))
-        if not noise_like:
-            HARD.append(worst)
-        a64 = ga[c].astype(np.float64)
-        if len(a64) != len(ref):
-            continue
-        if name_a == names[0]:
+            why = bound_check(name, kinds[c], g, ref[:, :k], eb.bound_from_stages(st, eb.model_of(name), k))
+            if why:
+                fails.append("FLOAT %s n_cep %d vs float64 oracle %s ch %d: %s" % (name, k, tag, c, why))
+        if name_a == names[0] and len(ga[c]) == len(ref):
             # the drawn n_cep against the first columns of the all-coefficient run: the same log-mel values, fewer DCT rows
+            a64 = ga[c].astype(np.float64)
             f64 = gaf[c][:, :ncep].astype(np.float64)
             ok, why = pattern_ok(a64, f64)
             fin = np.isfinite(f64)
@@ -179,34 +155,15 @@ def one_case(seed):
                 ok, why = False, "err %.3g of %.3g" % (np.abs(a64[fin] - f64[fin]).max(), np.abs(f64[fin]).max())
             if not ok:
                 fails.append("FLOAT n_cep %d vs n_cep %d of %s %s ch %d: %s" % (ncep, nmel, names[0], tag, c, why))
-        elif aside is not None:
-            # the fused 1024 kernel keeps at most 32 of its 40 coefficients, so its DCT cannot be undone: it is held to
-            # the contract in the coefficient domain on the frames that have no band set aside (counted in FRAMES_1K)
-            r64 = ref[:, :ncep]
-            ok, why = pattern_ok(a64, r64)
-            keep = ~aside & np.isfinite(r64).all(axis=1)
-            if noise_like:
-                FRAMES_1K[0] += int(aside.sum()); FRAMES_1K[1] += len(aside)
-            if ok and keep.any():
-                rel = np.abs(a64[keep] - r64[keep]).max() / max(np.abs(r64[keep]).max(), 1.0)
-                if rel > 1e-4: ok, why = False, "err %.3g of the largest coefficient" % rel
-            if not ok and (noise_like or os.environ.get("FUZZ_STRICT")):
-                fails.append("FLOAT %s vs float64 oracle %s ch %d: %s" % (name_a, tag, c, why))
     return fails
 
 
 def summary():
-    s = "bands beyond fp32's reach set aside %d of %d (%.4f %%) on noise-like channels, largest log-mel error inside " \
-        "that set %.3g" % (ILL[0], ILL[1], 100.0 * ILL[0] / max(ILL[1], 1), EXCL_MAX[0])
-    if FRAMES_1K[1]:
-        s += "; fused 1024 kernel, coefficient domain: %d of %d frames not compared (a band set aside)" % tuple(FRAMES_1K)
-    if HARD:
-        h = np.sort(np.array(HARD)[np.isfinite(HARD)])
-        if len(h):
-            s += "; DC / square / sine channels (float contract, reported): %d, kept-band coefficient error / largest " \
-                 "coefficient: median %.2g, p90 %.2g, p99 %.2g, max %.2g, above 1e-4: %d" % (
-                     len(h), h[len(h) // 2], h[int(len(h) * 0.9)], h[int(len(h) * 0.99)], h[-1], int((h > 1e-4).sum()))
-    return s
+    if not WORST:
+        return "no float channel compared"
+    return "worst |error| / bound per float kernel and signal kind: " + ", ".join(
+        "%s %s %.3f" % (k[0], k[1], v) for k, v in sorted(WORST.items())) + \
+        "; frames left unconstrained (a band at the roundoff of an exact zero): %d of %d" % tuple(FREE)
 
 
 if __name__ == "__main__":

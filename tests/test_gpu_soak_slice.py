@@ -1,6 +1,6 @@
 """A fixed slice of the randomized soak (tests/soak_gpu.py) in front of the driver: 300 seeded cases -- ragged
-batches, the fixed-point kernel bit for bit on every signal kind, both float kernels band by band against the
-float64 oracle at random shapes, alignments, sample rates and filter counts.  `python tests/soak_gpu.py --case SEED`
+batches, the fixed-point kernel bit for bit on every signal kind, both float kernels against the per-coefficient
+error bound of the float64 oracle (oracle/error_bound.py) at random shapes, alignments, sample rates and filter counts.  `python tests/soak_gpu.py --case SEED`
 replays a failing case."""
 import importlib.util
 import os
@@ -28,5 +28,8 @@ def test_soak_slice(seed0):
         seed = seed0 * 10_000_000 + k
         fails += ["[--case %d] %s" % (seed, f) for f in soak.one_case(seed)]
     assert not fails, fails
-    # the exclusion stays what the docstring says it is: rare, and band-wise
-    assert soak.ILL[0] <= 1e-4 * max(soak.ILL[1], 1) + 8, soak.summary()
+    # nothing is set aside: the DC / square / sine channels were held to the bound like the noise-like ones
+    counted = {kind for _, kind in soak.WORST}
+    assert {"dc", "square", "sine", "gauss"} <= counted, soak.summary()
+    assert max(soak.WORST.values()) <= 1.0, soak.summary()
+    print(soak.summary())
