@@ -13,7 +13,10 @@
  * Conventions kept from the reference:
  *   - 0 = success, negative error codes in the ft601_error range      software/ft601.h:25-32
  *   - caller owns every in/out buffer; the handle owns device tables/streams   main.c:109,40
- *   - output layout [frame][n_cep] row-major, i.e. the `.mfcc` file layout     main.c:162-165
+ *   - output layout [frame][n_cep] row-major, i.e. the `.mfcc` file layout     main.c:162-165;
+ *     with output = MFCC_HIP_OUTPUT_LOGMEL the rows are [frame][n_mel] log2 mel energies instead
+ *     (the stage before the DCT, notebook/MFCC.ipynb `audio_log`); every "n_cep" below that
+ *     sizes an output row then reads "n_mel"
  *   - nothing is printed by the library (the reference printf's; a log hook exists there,
  *     ft601.h:43-51 -- here errors are returned and described by mfcc_hip_strerror)
  *   - a handle is not thread-safe; distinct handles are independent            ft601.c:185,197
@@ -63,6 +66,16 @@ enum mfcc_hip_float_impl {
     MFCC_HIP_IMPL_FUSED512 = 2  /* 512/170/32 specialised kernel                        */
 };
 
+/* what a float output row holds */
+enum mfcc_hip_output {
+    MFCC_HIP_OUTPUT_CEPSTRA = 0,  /* [n_cep] DCT-II cepstra (x lifter): the `.mfcc` coefficients      */
+    MFCC_HIP_OUTPUT_LOGMEL = 1    /* [n_mel] log2 of the mel band energies (MFCC.ipynb `audio_log.T`),
+                                     -inf for a silent band.  Float path only: the fixed-point entry
+                                     points, fixed streaming sessions and the .mfcc file writers
+                                     return MFCC_HIP_ERROR_UNSUPPORTED; lifter must be 0; n_cep is
+                                     validated but not used                                       */
+};
+
 /*
  * Parameters = the constructor arguments of `MFCC(width=16, nfft, samplerate, nfilters,
  * nceptrums)` (mfcc/core/mfcc.py:20-21) plus the host driver's constants
@@ -82,7 +95,8 @@ typedef struct mfcc_hip_params {
                               software/lift.py:12); 0 = off                               */
     int32_t  device;       /* HIP device ordinal; -1 = the current device                 */
     int32_t  float_impl;   /* enum mfcc_hip_float_impl                                    */
-    int32_t  reserved[5];  /* must be zero                                                */
+    int32_t  output;       /* enum mfcc_hip_output; 0 = cepstra                           */
+    int32_t  reserved[4];  /* must be zero                                                */
 } mfcc_hip_params;
 
 typedef struct mfcc_hip_handle mfcc_hip_handle;
@@ -200,7 +214,9 @@ int  mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t 
                        size_t ch_stride_samples, size_t n_channels, void *d_out,
                        int warmup, int iters, float *avg_ms);
 
-/* name of the kernel symbol process_*_dev launches for this handle (to match rocprofv3 rows) */
+/* name of the kernel symbol process_*_dev launches for this handle (to match rocprofv3 rows).  A log-mel handle runs
+ * the log-mel instantiation of the kernel named (the default form: MFCC_HIP_FUSED512 / MFCC_HIP_FUSED1024 do not
+ * apply to it) */
 const char *mfcc_hip_kernel_name(const mfcc_hip_handle *h, int fixed);
 
 /* ---- file-level convenience: mfcc_convert(sess, wav_in, mfcc_out)  software/main.c:100 --- */

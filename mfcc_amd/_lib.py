@@ -32,6 +32,9 @@ IMPL_AUTO = 0
 IMPL_GENERIC = 1
 IMPL_FUSED512 = 2
 
+OUTPUT_CEPSTRA = 0
+OUTPUT_LOGMEL = 1
+
 TABLE_WINDOW_F32 = 0
 TABLE_MEL_POINTS_I32 = 1
 TABLE_MEL_DENSE_F32 = 2
@@ -55,7 +58,8 @@ class Params(C.Structure):
         ("lifter", C.c_float),
         ("device", C.c_int32),
         ("float_impl", C.c_int32),
-        ("reserved", C.c_int32 * 5),
+        ("output", C.c_int32),
+        ("reserved", C.c_int32 * 4),
     ]
 
 

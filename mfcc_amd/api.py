@@ -27,10 +27,13 @@ PAD_NOTEBOOK = _lib.PAD_NOTEBOOK
 PAD_STREAM = _lib.PAD_STREAM
 _PAD = {"notebook": PAD_NOTEBOOK, "stream": PAD_STREAM, PAD_NOTEBOOK: PAD_NOTEBOOK, PAD_STREAM: PAD_STREAM}
 _IMPL = {"auto": _lib.IMPL_AUTO, "generic": _lib.IMPL_GENERIC, "fused512": _lib.IMPL_FUSED512}
+_OUTPUT = {"cepstra": _lib.OUTPUT_CEPSTRA, "logmel": _lib.OUTPUT_LOGMEL}
 
 
 def make_params(nfft=512, hop=None, nfilters=32, nceptrums=13, samplerate=16000, pad_mode="notebook",
-                power_scale=512.0, lifter=0.0, device=-1, impl="auto") -> Params:
+                power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra") -> Params:
+    """``output``: ``"cepstra"`` (rows of ``nceptrums`` DCT-II coefficients) or ``"logmel"`` (rows of ``nfilters``
+    log2 mel band energies, the stage before the DCT; float path only, no lifter)."""
     lib = _lib.load()
     p = Params()
     _lib.check(lib.mfcc_hip_default_params(C.byref(p)))
@@ -44,6 +47,7 @@ def make_params(nfft=512, hop=None, nfilters=32, nceptrums=13, samplerate=16000,
     p.lifter = float(lifter)
     p.device = int(device)
     p.float_impl = _IMPL[impl] if isinstance(impl, str) else int(impl)
+    p.output = _OUTPUT[output] if isinstance(output, str) else int(output)
     return p
 
 
@@ -86,10 +90,14 @@ class MFCC:
 
     ``hop`` defaults to ``nfft // 3`` like the core (``mfcc.py:43``); the notebook and the host
     driver hard-code 170 for nfft 512, which is the same number.
+
+    ``output="logmel"`` makes every float entry point return rows of ``nfilters`` log2 mel band energies
+    (the notebook's ``audio_log.T``, -inf for a silent band) instead of ``nceptrums`` cepstra; the width of a
+    row is :attr:`num_features` either way.  The fixed-point path and ``convert`` refuse such a handle.
     """
 
     def __init__(self, width=16, nfft=512, samplerate=16e3, nfilters=16, nceptrums=16, *, hop=None,
-                 pad_mode="notebook", power_scale=512.0, lifter=0.0, device=-1, impl="auto"):
+                 pad_mode="notebook", power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra"):
         if width != 16:
             raise ValueError("only width=16 (int16 PCM) is supported, like every reference target")
         self.width = width
@@ -100,8 +108,9 @@ class MFCC:
         self._lib = _lib.load()
         self._params = make_params(nfft=nfft, hop=hop, nfilters=nfilters, nceptrums=nceptrums,
                                    samplerate=int(samplerate), pad_mode=pad_mode, power_scale=power_scale,
-                                   lifter=lifter, device=device, impl=impl)
+                                   lifter=lifter, device=device, impl=impl, output=output)
         self.hop = self._params.hop or self.nfft // 3
+        self.output = "logmel" if self._params.output == _lib.OUTPUT_LOGMEL else "cepstra"
         h = C.c_void_p()
         self._device_index = None
         if int(device) < 0:
@@ -132,6 +141,14 @@ class MFCC:
 
     def __exit__(self, *a):
         self.close()
+
+    @property
+    def num_features(self) -> int:
+        """Width of an output row of the float path: ``nfilters`` for ``output="logmel"``, else ``nceptrums``."""
+        return self.nfilters if self.output == "logmel" else self.nceptrums
+
+    def _row(self, fixed):
+        return self.nceptrums if fixed else self.num_features
 
     def num_frames(self, n_samples) -> int:
         out = C.c_size_t(0)
@@ -170,7 +187,7 @@ class MFCC:
             raise ValueError("pcm must be (n,) or (channels, n)")
         nch, n = pcm.shape
         nf = self.num_frames(n)
-        out = np.empty((nch, nf, self.nceptrums), dtype=np.int16 if fixed else np.float32)
+        out = np.empty((nch, nf, self._row(fixed)), dtype=np.int16 if fixed else np.float32)
         got = C.c_size_t(0)
         fn = self._lib.mfcc_hip_process_fixed_i16 if fixed else self._lib.mfcc_hip_process_i16
         _lib.check(fn(self._h, pcm.ctypes.data, n, nch, out.ctypes.data, out.size, C.byref(got)),
@@ -194,11 +211,12 @@ class MFCC:
         nf = self.num_frames(n)
         self._check_device(pcm)
         odt = torch.int16 if fixed else torch.float32
+        row = self._row(fixed)
         if out is None:
-            out = torch.empty((nch, nf, self.nceptrums), device=pcm.device, dtype=odt)
+            out = torch.empty((nch, nf, row), device=pcm.device, dtype=odt)
         else:
             # the kernel gets raw pointers: a wrong shape / dtype / layout / device would be an out-of-bounds write
-            want = (nf, self.nceptrums) if squeeze and out.dim() == 2 else (nch, nf, self.nceptrums)
+            want = (nf, row) if squeeze and out.dim() == 2 else (nch, nf, row)
             if tuple(out.shape) != want or out.dtype != odt or not out.is_contiguous() or out.device != pcm.device:
                 raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (odt, want, pcm.device))
         fn = self._lib.mfcc_hip_process_fixed_i16_dev if fixed else self._lib.mfcc_hip_process_i16_dev
@@ -234,7 +252,7 @@ class MFCC:
         return ctx()
 
     def process(self, pcm, halo=0, out=None):
-        """Float contract: int16 PCM ``(n,)`` / ``(channels, n)`` -> float32 ``(.., frames, nceptrums)``.
+        """Float contract: int16 PCM ``(n,)`` / ``(channels, n)`` -> float32 ``(.., frames, num_features)``.
         NumPy in -> NumPy out (H2D, kernel, D2H); torch CUDA tensor in -> torch tensor out, asynchronous
         on the current stream.  ``halo=1`` (device path): sample 0 of every channel is history only."""
         if _is_torch(pcm):
@@ -254,7 +272,7 @@ class MFCC:
     def process_batch(self, utterances, fixed=False):
         """Many utterances of different lengths in ONE launch (the batched form of the driver's directory
         walk, main.c:206-247).  ``utterances``: sequence of 1-D int16 arrays.  Returns a list of
-        ``(frames_u, nceptrums)`` arrays (views of one result buffer), bit-identical to calling
+        ``(frames_u, num_features)`` arrays (views of one result buffer), bit-identical to calling
         ``process`` / ``process_fixed`` on each utterance."""
         if len(utterances) and _is_torch(utterances[0]):
             return self._batch_dev(utterances, fixed)
@@ -266,7 +284,7 @@ class MFCC:
         flat = np.concatenate(utts) if n and int(offsets[-1]) else np.zeros(0, dtype=np.int16)
         fo = np.zeros(n + 1, dtype=np.uint64)
         nf = sum(self.num_frames(u.size) for u in utts)
-        out = np.empty((nf, self.nceptrums), dtype=np.int16 if fixed else np.float32)
+        out = np.empty((nf, self._row(fixed)), dtype=np.int16 if fixed else np.float32)
         fn = self._lib.mfcc_hip_process_ragged_fixed_i16 if fixed else self._lib.mfcc_hip_process_ragged_i16
         _lib.check(fn(self._h, flat.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), n,
                       out.ctypes.data_as(C.c_void_p), out.size, fo.ctypes.data_as(C.c_void_p)), "process_ragged")
@@ -297,7 +315,7 @@ class MFCC:
     def process_packed(self, flat, offsets, fixed=False, out=None):
         """A corpus that already lies in HBM: ``flat`` = all utterances back to back (1-D CUDA int16 tensor),
         utterance ``u`` = ``flat[offsets[u]:offsets[u + 1]]``.  ONE launch (``mfcc_hip_process_ragged_*_dev``),
-        asynchronous on the current stream.  Returns ``(out, frame_offsets)``: the dense ``(sum frames, nceptrums)``
+        asynchronous on the current stream.  Returns ``(out, frame_offsets)``: the dense ``(sum frames, num_features)``
         result tensor and the row range of every utterance (``out[fo[u]:fo[u + 1]]``).  Equal-length utterances run
         as channels of one multi-channel launch (no packing copy); the bits are the same."""
         import torch
@@ -320,11 +338,11 @@ class MFCC:
             uniq, counts = np.unique(lens, return_counts=True)
             nf = int(sum(self.num_frames(int(v)) * int(c) for v, c in zip(uniq, counts)))
         odt = torch.int16 if fixed else torch.float32
+        row = self._row(fixed)
         if out is None:
-            out = torch.empty((nf, self.nceptrums), device=flat.device, dtype=odt)
-        elif tuple(out.shape) != (nf, self.nceptrums) or out.dtype != odt or not out.is_contiguous() or \
-                out.device != flat.device:
-            raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (odt, (nf, self.nceptrums), flat.device))
+            out = torch.empty((nf, row), device=flat.device, dtype=odt)
+        elif tuple(out.shape) != (nf, row) or out.dtype != odt or not out.is_contiguous() or out.device != flat.device:
+            raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (odt, (nf, row), flat.device))
         fn = self._lib.mfcc_hip_process_ragged_fixed_i16_dev if fixed else self._lib.mfcc_hip_process_ragged_i16_dev
         with self._on_torch_stream(flat.device):
             _lib.check(fn(self._h, C.c_void_p(flat.data_ptr()), offsets.ctypes.data_as(C.c_void_p), n,
@@ -403,10 +421,10 @@ class MfccStream:
         return int(self._lib.mfcc_hip_stream_pending(self._s))
 
     def _out(self, nf):
-        return np.empty((nf, self._m.nceptrums), dtype=np.int16 if self.fixed else np.float32)
+        return np.empty((nf, self._m._row(self.fixed)), dtype=np.int16 if self.fixed else np.float32)
 
     def push(self, samples) -> np.ndarray:
-        """``sink``: int16 samples in; returns the ``(frames, nceptrums)`` they complete (possibly 0 rows)."""
+        """``sink``: int16 samples in; returns the ``(frames, num_features)`` they complete (possibly 0 rows)."""
         samples = np.ascontiguousarray(samples)
         if samples.dtype != np.int16 or samples.ndim != 1:
             raise TypeError("samples must be a 1-D int16 array (the core's sink is signed 16 bit, mfcc.py:29)")

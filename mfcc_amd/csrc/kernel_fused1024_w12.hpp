@@ -37,6 +37,8 @@
 // Two kernels in this file: mfcc_fused1024_w12_kernel<R> (this namespace: the fp32 lists of kernel_fused1024_f32.hpp, five
 // sample rates, an A/B form: MFCC_HIP_FUSED1024=w12) and, at the end, mfcc_fused1024_w12bf_kernel<VAR> (the bf16-split set
 // lists of kernel_fused1024.hpp, every sample rate): the one a handle runs, 1.5 % ahead of the other at 16 kHz.
+// mfcc_fused1024_w12bf_kernel<VAR, true> is its log-mel form (output = log-mel): wave 11 stores the 40 log2 band energies
+// of a frame instead of running the DCT.
 #pragma once
 
 #include "kernel_fused1024.hpp"
@@ -562,7 +564,7 @@ __device__ __forceinline__ void wait_bf_burst(u32x4 (&ah)[NS], u32x4 (&al)[NS]) 
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(ah[0]), "+v"(ah[1]), "+v"(ah[2]), "+v"(ah[3]), "+v"(ah[4]), "+v"(al[0]), "+v"(al[1]), "+v"(al[2]), "+v"(al[3]), "+v"(al[4]));
 }
 
-template <int VAR>
+template <int VAR, bool LOGMEL>
 __global__ __launch_bounds__(64 * kW12Waves) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void mfcc_fused1024_w12bf_kernel(mfcc_k::StreamDesc s, Tables t, LaunchGeom g, float *__restrict__ out) {
     using S = Sets<VAR>;
@@ -842,7 +844,8 @@ void mfcc_fused1024_w12bf_kernel(mfcc_k::StreamDesc s, Tables t, LaunchGeom g, f
         float ax[12];
 #pragma unroll
         for (int i = 0; i < 12; ++i) ax[i] = t.a_extra[(0 * kAextra + i) * 64 + lane];
-        const int lane_off = lo * t.n_cep + 4 * q;
+        const int row = LOGMEL ? mfcc_fused1024::kMel : t.n_cep;     // floats per output row
+        const int lane_off = lo * row + 4 * q;
         Cursor ta = cursor_of(s, g, va), tb = cursor_of(s, g, vb);
         lds_barrier();
         for (int h = 0; h <= last_h; ++h) {
@@ -858,18 +861,39 @@ void mfcc_fused1024_w12bf_kernel(mfcc_k::StreamDesc s, Tables t, LaunchGeom g, f
 #pragma unroll
                     for (int r = 0; r < 4; ++r) lm[b][r] = __builtin_amdgcn_logf(m[r]);
                 }
-                if (q >= 2) lm[2] = zero;
-                f32x4 d[kBlocks] = {zero, zero, zero};
+                if constexpr (LOGMEL) {
+                    // log-mel output: lane lo + 16 q holds bands 16 b + 4 q .. 16 b + 4 q + 3 of frame lo -- a 16-byte
+                    // store per block, none for bands 40..47 (block 2, q >= 2), which do not exist.  No DCT
+                    auto store = [&](const Cursor &c) {
+                        const long long fr0 = (long long)c.t_in * kTile;
+                        float *o = out + ((long long)c.ch * s.frames_per_ch + fr0) * row + lane_off;
+                        if (lo < s.frames_per_ch - fr0) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int b = 0; b < kBlocks; ++b) d[b] = MFCC1K_MFMA(ax[4 * b + r], lm[b][r], d[b]);
-                if (gi) {
-                    dct_store(s, t, d, lm, tb, lo, q, lane, lane_off, out);
-                    advance(tb, g);
+                            for (int b = 0; b < kBlocks; ++b)
+                                if (b < 2 || q < 2) *reinterpret_cast<f32x4 *>(o + 16 * b) = lm[b];
+                        }
+                    };
+                    if (gi) {
+                        store(tb);
+                        advance(tb, g);
+                    } else {
+                        store(ta);
+                        advance(ta, g);
+                    }
                 } else {
-                    dct_store(s, t, d, lm, ta, lo, q, lane, lane_off, out);
-                    advance(ta, g);
+                    if (q >= 2) lm[2] = zero;
+                    f32x4 d[kBlocks] = {zero, zero, zero};
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int b = 0; b < kBlocks; ++b) d[b] = MFCC1K_MFMA(ax[4 * b + r], lm[b][r], d[b]);
+                    if (gi) {
+                        dct_store(s, t, d, lm, tb, lo, q, lane, lane_off, out);
+                        advance(tb, g);
+                    } else {
+                        dct_store(s, t, d, lm, ta, lo, q, lane, lane_off, out);
+                        advance(ta, g);
+                    }
                 }
             }
             lds_barrier();
@@ -879,6 +903,7 @@ void mfcc_fused1024_w12bf_kernel(mfcc_k::StreamDesc s, Tables t, LaunchGeom g, f
 
 inline const char *kernel_name() { return "mfcc_fused1024_w12bf_kernel"; }
 
+template <bool LOGMEL = false>
 inline bool launch(const mfcc_k::StreamDesc &s, const Tables &t, float *out, int n_cu, hipStream_t stream) {
     const long long tiles_per_ch = (s.frames_per_ch + kTile - 1) / kTile;
     const long long n_ch = s.total_frames / s.frames_per_ch;
@@ -901,9 +926,9 @@ inline bool launch(const mfcc_k::StreamDesc &s, const Tables &t, float *out, int
     g.t_hi = s.n_samples < kSUsed ? -1 : (int)(hi < tiles_per_ch ? hi : tiles_per_ch);
     const dim3 grid3((unsigned)wgs), block3(64 * kW12Waves);
     switch (t.variant) {
-    case 1: hipLaunchKernelGGL(mfcc_fused1024_w12bf_kernel<1>, grid3, block3, 0, stream, s, t, g, out); break;
-    case 2: hipLaunchKernelGGL(mfcc_fused1024_w12bf_kernel<2>, grid3, block3, 0, stream, s, t, g, out); break;
-    default: hipLaunchKernelGGL(mfcc_fused1024_w12bf_kernel<0>, grid3, block3, 0, stream, s, t, g, out); break;
+    case 1: hipLaunchKernelGGL((mfcc_fused1024_w12bf_kernel<1, LOGMEL>), grid3, block3, 0, stream, s, t, g, out); break;
+    case 2: hipLaunchKernelGGL((mfcc_fused1024_w12bf_kernel<2, LOGMEL>), grid3, block3, 0, stream, s, t, g, out); break;
+    default: hipLaunchKernelGGL((mfcc_fused1024_w12bf_kernel<0, LOGMEL>), grid3, block3, 0, stream, s, t, g, out); break;
     }
     return true;
 }

@@ -14,7 +14,8 @@
 //   wave  10     column 16 of the group that is in pass 2: 16 x 16 DFT + its mel contribution (fp32 MFMAs)
 //   wave  11     the tail of the tile that finished pass 2 in the previous half-step: log2, DCT-II (on bf16-split matrix
 //                instructions since round 3: three independent v_mfma_f32_16x16x32_bf16 per 16 coefficients instead of
-//                eight fp32 ones that block the SIMD; frames with a -inf band take the fp32 chain), store
+//                eight fp32 ones that block the SIMD; frames with a -inf band take the fp32 chain), store.
+//                LOGMEL (output = log-mel): log2, store -- no DCT, no matrix instruction at all
 //
 // Waves i, i + 4 and i + 8 share SIMD i's slot (cyclic placement): one worker in pass 1, one in pass 2, one helper.
 // Registers: a worker without the helpers' state needs 156 VGPRs (164 with the dense mel sets).
@@ -182,14 +183,14 @@ struct TileStream {
     unsigned v;
     int gv;
     RaggedTile nx;           // record of tile v + gv
-    __device__ __forceinline__ void adopt(const mfcc_k::StreamDesc &s, const RaggedTile &r, int n_cep, float *out) {
+    __device__ __forceinline__ void adopt(const mfcc_k::StreamDesc &s, const RaggedTile &r, int row, float *out) {
         c.ch = 0;
         c.t_in = r.t_in;
         c.ptr = s.pcm + r.pcm_off + (long long)r.t_in * kTileHop;
         sl.n_samples = r.n_samples;
         sl.frames_per_ch = r.frames;
         gl.t_hi = r.t_hi;
-        outp = out + r.out_row * n_cep;
+        outp = out + r.out_row * row;
     }
     // called right before a barrier: the wait that the next LDS access brings (lgkmcnt counts scalar loads too) then
     // falls into the barrier wait instead of into the work
@@ -200,7 +201,7 @@ struct TileStream {
         }
     }
     __device__ __forceinline__ void start(const mfcc_k::StreamDesc &s, const LaunchGeom &g, const RaggedTables &r,
-                                          unsigned v0, int stride, int n_cep, float *out) {
+                                          unsigned v0, int stride, int row, float *out) {
         sl = s;
         gl = g;
         outp = out;
@@ -213,16 +214,16 @@ struct TileStream {
             c.t_in = 0;
             c.ptr = s.pcm;
             nx = RaggedTile{0, 0, 0, 0, -1, 0};
-            if ((int)v < r.n_tiles) adopt(s, load_tile_record(r.tiles, v), n_cep, out);
+            if ((int)v < r.n_tiles) adopt(s, load_tile_record(r.tiles, v), row, out);
             prefetch(r);
         } else {
             c = cursor_of(s, g, v0);
         }
     }
-    __device__ __forceinline__ void next(const mfcc_k::StreamDesc &s, const RaggedTables &r, int n_cep, float *out) {
+    __device__ __forceinline__ void next(const mfcc_k::StreamDesc &s, const RaggedTables &r, int row, float *out) {
         if constexpr (RAGGED) {
             v += (unsigned)gv;
-            if ((int)v < r.n_tiles) adopt(s, nx, n_cep, out);      // the caller prefetches the one after it (see prefetch)
+            if ((int)v < r.n_tiles) adopt(s, nx, row, out);      // the caller prefetches the one after it (see prefetch)
         } else {
             advance(c, gl);
         }
@@ -256,10 +257,11 @@ __device__ unsigned long long g_stamps12[kW12Waves * 4];      // [wave]: work ev
 #define W12_LOOP_END
 #endif
 
-template <bool DENSE, bool RAGGED, bool DCX>
+template <bool DENSE, bool RAGGED, bool DCX, bool LOGMEL>
 __global__ __launch_bounds__(64 * kW12Waves) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, RaggedTables rag, float *__restrict__ out) {
     constexpr int kSets = SetsBf<DENSE>::N;
+    const int row = LOGMEL ? t.n_mel : t.n_cep;        // floats per output row
     __shared__ __attribute__((aligned(16))) float lds[kW12LdsWords + (DCX ? kDcLdsWords : 0) + (RAGGED ? 4 : 0)];
     // RAGGED: the shift of the window that lies in S_A / S_B, published by the parkers next to the window itself -- the
     // eight worker waves then need no per-tile record at all (they used to fetch one each: an L2 round trip per tile)
@@ -317,7 +319,7 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
         const int lane_slot = fr_id * kHop + lo;
         const int n_mine = gi ? nB : nA;
         TileStream<false> cur;                         // the plain call's arithmetic cursor (RAGGED: unused, see Shw)
-        if constexpr (!RAGGED) cur.start(s, g, rag, gi ? vb : va, gv, t.n_cep, out);
+        if constexpr (!RAGGED) cur.start(s, g, rag, gi ? vb : va, gv, row, out);
 
         lds_barrier();                                 // the parkers' prologue: S_A(0) and S_B(0) are in LDS
         // The pass-1 operands of a tile are read out of its window ONE half-step early, in the middle of the same
@@ -364,7 +366,7 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
             }
             PowerBf pb;
             split_power(pw, pb);
-            if constexpr (!RAGGED) cur.next(s, rag, t.n_cep, out);
+            if constexpr (!RAGGED) cur.next(s, rag, row, out);
             load_ep();           // the next tile's operands fly during the MFMAs (after the last tile they are never used)
             f32x4 acc[kSets];
 #pragma unroll
@@ -404,8 +406,8 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
         // although they have the least to do and everybody waits for them at the barrier
         __builtin_amdgcn_s_setprio(3);
         TileStream<RAGGED> pa, pb;
-        pa.start(s, g, rag, va, gv, t.n_cep, out);
-        pb.start(s, g, rag, vb, gv, t.n_cep, out);
+        pa.start(s, g, rag, va, gv, row, out);
+        pb.start(s, g, rag, vb, gv, row, out);
         int ka = 0, kb = 0;                            // next tile of each stream to fetch
         // one register set per stream: a window is fetched TWO half-steps before it is parked (HBM latency under
         // load is longer than a half-step), i.e. right after the same stream's previous window has been parked
@@ -414,27 +416,27 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
         if (nA > 0) {                                  // prologue: S_A(0) and S_B(0) directly
             fetch_window3(pa.sl, pa.window(), u, fa);
             park_window3<DCX>(Sf(0), Rw, u, fa, RAGGED ? Shw + 0 : nullptr);
-            pa.next(s, rag, t.n_cep, out);
+            pa.next(s, rag, row, out);
             pa.prefetch(rag);
             ++ka;
         }
         if (nB > 0) {
             fetch_window3(pb.sl, pb.window(), u, fb);
             park_window3<DCX>(Sf(1), Rw + kRawWords, u, fb, RAGGED ? Shw + 1 : nullptr);
-            pb.next(s, rag, t.n_cep, out);
+            pb.next(s, rag, row, out);
             pb.prefetch(rag);
             ++kb;
         }
         if (ka < nA) {                                 // S_A(1): parked at h = 0
             fetch_window3(pa.sl, pa.window(), u, fa);
-            pa.next(s, rag, t.n_cep, out);
+            pa.next(s, rag, row, out);
             pa.prefetch(rag);
             ++ka;
             have_a = true;
         }
         if (kb < nB) {                                 // S_B(1): parked at h = 1
             fetch_window3(pb.sl, pb.window(), u, fb);
-            pb.next(s, rag, t.n_cep, out);
+            pb.next(s, rag, row, out);
             pb.prefetch(rag);
             ++kb;
             have_b = true;
@@ -453,7 +455,7 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                 have_a = false;
                 if (ka < nA) {
                     fetch_window3(pa.sl, pa.window(), u, fa);
-                    pa.next(s, rag, t.n_cep, out);
+                    pa.next(s, rag, row, out);
                     ++ka;
                     have_a = true;
                 }
@@ -462,7 +464,7 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                 have_b = false;
                 if (kb < nB) {
                     fetch_window3(pb.sl, pb.window(), u, fb);
-                    pb.next(s, rag, t.n_cep, out);
+                    pb.next(s, rag, row, out);
                     ++kb;
                     have_b = true;
                 }
@@ -488,8 +490,8 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
         if constexpr (DCX) {
 #pragma unroll
             for (int b = 0; b < kDcBlocks; ++b) adc[b] = reinterpret_cast<const v4i *>(t.a_dc_i8)[b * 64 + lane];
-            da.start(s, g, rag, va, gv, t.n_cep, out);
-            db.start(s, g, rag, vb, gv, t.n_cep, out);
+            da.start(s, g, rag, va, gv, row, out);
+            db.start(s, g, rag, vb, gv, row, out);
         }
         auto dc_tile = [&](int gi, int k, TileStream<RAGGED> &dts) {
             // lane (frame lo, k-group q): 16 bytes = 4 dwords per k-block, 16 dwords apart
@@ -522,7 +524,7 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
             int *d = DcI + (gi * 2 + (k & 1)) * 256 + lo;
 #pragma unroll
             for (int r = 0; r < 4; ++r) d[(4 * q + r) * 16] = acc[r];
-            dts.next(s, rag, t.n_cep, out);
+            dts.next(s, rag, row, out);
         };
         lds_barrier();                                 // the parkers' two prologue barriers
         if constexpr (DCX) {
@@ -582,10 +584,10 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                 dct_l[tile][d] = t.a_dct_bf[((size_t)tile * 2 + 1) * 256 + d * 64 + lane];
             }
 #endif
-        const int lane_off = lo * t.n_cep + 4 * q;
+        const int lane_off = lo * row + 4 * q;
         TileStream<RAGGED> ta, tb;
-        ta.start(s, g, rag, va, gv, t.n_cep, out);
-        tb.start(s, g, rag, vb, gv, t.n_cep, out);
+        ta.start(s, g, rag, va, gv, row, out);
+        tb.start(s, g, rag, vb, gv, row, out);
         // bin 0's weight in this lane's eight filters (4 q + r of block 0, 16 + 4 q + r of block 1)
         f32x4 wdc0 = zero, wdc1 = zero;
         double dc_scale = 0.0, dc_bias_lo = 0.0, dc_bias_hi = 0.0;
@@ -641,6 +643,23 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                     l0[r] = __builtin_amdgcn_logf(m0[r]);
                     l1[r] = __builtin_amdgcn_logf(m1[r]);
                 }
+                if constexpr (LOGMEL) {
+                    // log-mel output: this lane holds bands 4 q .. 4 q + 3 (l0) and 16 + 4 q .. 16 + 4 q + 3 (l1) of frame
+                    // lo, so a row is two 16-byte stores and a tile's 16 rows are one contiguous block.  No DCT: no matrix
+                    // instruction, no accumulator chain, no -inf special case (a silent band is stored as the -inf it is)
+                    auto finish = [&](TileStream<RAGGED> &c) {
+                        const long long fr0 = (long long)c.c.t_in * kTile;
+                        const long long rows_left = c.sl.frames_per_ch - fr0;
+                        float *o = c.outp + ((long long)c.c.ch * c.sl.frames_per_ch + fr0) * row + lane_off;
+                        if (lo < rows_left) {
+                            *reinterpret_cast<f32x4 *>(o) = l0;
+                            if (t.n_mel > 16) *reinterpret_cast<f32x4 *>(o + 16) = l1;   // a 16-wide row ends at o + 4
+                        }
+                        c.next(s, rag, row, out);
+                    };
+                    if (gi) finish(tb);
+                    else finish(ta);
+                } else {
                 if (t.n_mel <= 16) l1 = zero;          // no filters 16..31 (uniform)
 #if MFCC_W12_DCT_BF16
                 // The DCT on bf16-split matrix instructions: K = 32 is the 32 log-mel values of a frame, so an M tile of 16
@@ -698,7 +717,7 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                 auto finish = [&](TileStream<RAGGED> &c) {
                     const long long fr0 = (long long)c.c.t_in * kTile;
                     const long long rows_left = c.sl.frames_per_ch - fr0;
-                    float *o = c.outp + ((long long)c.c.ch * c.sl.frames_per_ch + fr0) * t.n_cep + lane_off;
+                    float *o = c.outp + ((long long)c.c.ch * c.sl.frames_per_ch + fr0) * row + lane_off;
                     if (lo < rows_left) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
@@ -706,7 +725,7 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                             if (16 + 4 * q + r < t.n_cep) o[16 + r] = e[r];
                         }
                     }
-                    c.next(s, rag, t.n_cep, out);
+                    c.next(s, rag, row, out);
                 };
                 if (gi) finish(tb);
                 else finish(ta);
@@ -720,11 +739,12 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                 // (not `TileStream &c = gi ? tb : ta`: a reference picked at run time puts both walks into scratch)
                 auto finish = [&](TileStream<RAGGED> &c) {
                     dct_store(c.sl, t, l0, l1, d0, d1, ax, c.c, lo, q, lane_off, c.outp);
-                    c.next(s, rag, t.n_cep, out);
+                    c.next(s, rag, row, out);
                 };
                 if (gi) finish(tb);
                 else finish(ta);
 #endif
+                }   // !LOGMEL
             }
             ta.prefetch(rag);
             tb.prefetch(rag);
@@ -737,7 +757,8 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
 
 inline const char *kernel_name() { return "mfcc_fused512_w12_kernel"; }
 
-// returns false when the problem does not fit (then the 4-wave kernel runs)
+// returns false when the problem does not fit (then the 4-wave kernel runs).  LOGMEL: the log-mel form
+template <bool LOGMEL = false>
 inline bool launch(const mfcc_k::StreamDesc &s, const FusedTables &t, bool dense, float *out, int n_cu,
                    hipStream_t stream) {
     const bool dcx = t.win_dc != nullptr;                // a filter has weight on bin 0: that bin in double (dense sets)
@@ -762,11 +783,11 @@ inline bool launch(const mfcc_k::StreamDesc &s, const FusedTables &t, bool dense
     g.t_hi = s.n_samples < kSUsed ? -1 : (int)(hi < tiles_per_ch ? hi : tiles_per_ch);
     const RaggedTables none = {nullptr, 0};
     if (dcx)
-        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<true, false, true>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, none, out);
+        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<true, false, true, LOGMEL>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, none, out);
     else if (dense)
-        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<true, false, false>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, none, out);
+        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<true, false, false, LOGMEL>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, none, out);
     else
-        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<false, false, false>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, none, out);
+        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<false, false, false, LOGMEL>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, none, out);
     return true;
 }
 
@@ -787,6 +808,7 @@ __global__ void ragged_tile_map_kernel(const RaggedChan *__restrict__ chans, int
     }
 }
 
+template <bool LOGMEL = false>
 inline bool launch_ragged(const int16_t *d_pcm, const RaggedChan *d_chans, int n_chan, RaggedTile *d_map, int n_tiles,
                           const FusedTables &t, bool dense, float *out, int n_cu, hipStream_t stream) {
     if (n_tiles <= 0) return false;
@@ -810,11 +832,11 @@ inline bool launch_ragged(const int16_t *d_pcm, const RaggedChan *d_chans, int n
     g.t_hi = -1;
     const RaggedTables r = {d_map, n_tiles};
     if (dcx)
-        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<true, true, true>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, r, out);
+        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<true, true, true, LOGMEL>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, r, out);
     else if (dense)
-        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<true, true, false>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, r, out);
+        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<true, true, false, LOGMEL>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, r, out);
     else
-        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<false, true, false>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, r, out);
+        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<false, true, false, LOGMEL>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, r, out);
     return true;
 }
 

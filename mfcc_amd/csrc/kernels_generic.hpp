@@ -1,7 +1,7 @@
 // Generic (correctness-first) gfx950 kernels: one frame per 64-lane wave, four waves per
 // workgroup, the frame staged in LDS.
 //
-//   mfcc_float_generic_kernel<NFFT> : float contract (notebook/MFCC.ipynb), any n_mel <= 64
+//   mfcc_float_generic_kernel<NFFT, LOGMEL> : float contract (notebook/MFCC.ipynb), any n_mel <= 64; LOGMEL: log-mel rows
 //   mfcc_fixed_kernel               : fixed contract (the RTL arithmetic), bit-exact int16
 //
 // The specialised 512/170/32 kernel lives in kernel_fused512.hpp; these are the reference
@@ -70,7 +70,8 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int NFFT>
+// LOGMEL: the log-mel form -- rows of n_mel log2 band energies instead of n_cep DCT-II coefficients
+template <int NFFT, bool LOGMEL>
 __global__ __launch_bounds__(kBlock) void mfcc_float_generic_kernel(StreamDesc s, FloatTables t,
                                                                   float *__restrict__ out) {
     constexpr int M = NFFT / 2;                 // complex FFT length (real-FFT packing)
@@ -200,12 +201,16 @@ __global__ __launch_bounds__(kBlock) void mfcc_float_generic_kernel(StreamDesc s
             float acc = 0.0f;
 #pragma unroll 4
             for (int j = 0; j < cnt; ++j) acc = fmaf(P[st + j], w[j], acc);
-            melv[wave][lane] = log2f(acc);
+            if constexpr (LOGMEL) {
+                if (valid) out[fid * t.n_mel + lane] = log2f(acc);
+            } else {
+                melv[wave][lane] = log2f(acc);
+            }
         }
         wave_sync();
 
         // DCT-II, first n_cep rows (cells 38-39)
-        if (valid && lane < t.n_cep) {
+        if (!LOGMEL && valid && lane < t.n_cep) {
             float acc = 0.0f;
             if (dct_in_lds) {
                 const float *d = dctl + lane * t.n_mel;

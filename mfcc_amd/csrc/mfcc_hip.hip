@@ -33,7 +33,12 @@ struct Resolved {
     int nfft, hop, n_mel, n_cep, sample_rate, pad_mode;
     double power_scale, lifter;
     int device, float_impl;
+    int output;                // enum mfcc_hip_output
 };
+
+// width of an output row: n_mel log-mel values or n_cep coefficients
+inline size_t row_width(const Resolved &r) { return size_t(r.output == MFCC_HIP_OUTPUT_LOGMEL ? r.n_mel : r.n_cep); }
+inline bool is_logmel(const Resolved &r) { return r.output == MFCC_HIP_OUTPUT_LOGMEL; }
 
 int resolve(const mfcc_hip_params *p, Resolved &r) {
     if (!p) return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -50,6 +55,7 @@ int resolve(const mfcc_hip_params *p, Resolved &r) {
     r.lifter = double(p->lifter);
     r.device = p->device;
     r.float_impl = p->float_impl;
+    r.output = p->output;
     if (!is_pow2(r.nfft) || r.nfft < 64 || r.nfft > 1024) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (r.hop < 1 || r.hop > r.nfft) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (r.n_mel < 1 || r.n_mel > mfcc_k::kMaxMel) return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -60,6 +66,8 @@ int resolve(const mfcc_hip_params *p, Resolved &r) {
     if (!(r.power_scale > 0.0) || r.lifter < 0.0) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (r.float_impl < MFCC_HIP_IMPL_AUTO || r.float_impl > MFCC_HIP_IMPL_FUSED512)
         return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (r.output != MFCC_HIP_OUTPUT_CEPSTRA && r.output != MFCC_HIP_OUTPUT_LOGMEL) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (r.output == MFCC_HIP_OUTPUT_LOGMEL && r.lifter != 0.0) return MFCC_HIP_ERROR_INVALID_PARAM;   // weights cepstra
     return MFCC_HIP_SUCCESS;
 }
 
@@ -275,7 +283,7 @@ int build_tables(mfcc_hip_handle *h) {
     std::vector<int> x5_lanes;
     std::vector<uint32_t> x5_wl;
     FxMel fm;
-    h->fixed_ok = fixed_supported(r);
+    h->fixed_ok = fixed_supported(r) && !is_logmel(r);     // log-mel output is float only: every fixed entry point refuses
     if (h->fixed_ok) {
         std::vector<int> cv = fx_window_curve(r.nfft);
         std::vector<int> re, im;
@@ -333,7 +341,8 @@ int build_tables(mfcc_hip_handle *h) {
         // Default: the twelve-wave staging with the bf16-split contraction (kernel_fused1024_w12.hpp), every rate.
         // MFCC_HIP_FUSED1024 is a diagnostic override for A/B runs -- f32 / bf16: the eight-wave lockstep staging of
         // either contraction; w12 / w12bf: the twelve-wave staging of either (fp32: the five rates it has lists for)
-        const char *e = std::getenv("MFCC_HIP_FUSED1024");
+        // a log-mel handle ignores it: only the default form has a log-mel tail
+        const char *e = is_logmel(r) ? nullptr : std::getenv("MFCC_HIP_FUSED1024");
         auto is = [&](const char *v) { return e && !std::strcmp(e, v); };
         const bool no_f32 = !(is("f32") || is("w12")), no_bf16 = is("f32") || is("w12");
         h->f1k_w12 = !(is("f32") || is("bf16"));
@@ -378,8 +387,9 @@ int build_tables(mfcc_hip_handle *h) {
     }
     if (h->fused_ok) mfcc_fused::bind_tables(b + o_fu, r.n_cep, r.n_mel, h->fused_dense, fused_dcx, h->fu);
     {
-        // diagnostic override for A/B runs: MFCC_HIP_FUSED512=w4 keeps the four-wave form
-        const char *e = std::getenv("MFCC_HIP_FUSED512");
+        // diagnostic override for A/B runs: MFCC_HIP_FUSED512=w4 keeps the four-wave form (not on a log-mel handle:
+        // the four-wave form has no log-mel tail)
+        const char *e = is_logmel(r) ? nullptr : std::getenv("MFCC_HIP_FUSED512");
         h->fused_w12 = h->fused_ok && !(e && std::strcmp(e, "w4") == 0);
     }
     if (h->fused1k_ok) {
@@ -403,6 +413,27 @@ int build_tables(mfcc_hip_handle *h) {
 bool use_fused(const mfcc_hip_handle *h) {
     if (h->r.float_impl == MFCC_HIP_IMPL_GENERIC) return false;
     return h->fused_ok;
+}
+
+// the generic float kernel for every nfft; LOGMEL: its log-mel form
+template <bool LOGMEL>
+int launch_generic(mfcc_hip_handle *h, const mfcc_k::StreamDesc &s, unsigned blocks, float *o) {
+    switch (h->r.nfft) {
+#define MFCC_GEN_CASE(N)                                                                                           \
+    case N:                                                                                                        \
+        hipLaunchKernelGGL((mfcc_k::mfcc_float_generic_kernel<N, LOGMEL>), dim3(blocks), dim3(mfcc_k::kBlock), 0,  \
+                           h->stream, s, h->ft, o);                                                                \
+        break;
+        MFCC_GEN_CASE(64)
+        MFCC_GEN_CASE(128)
+        MFCC_GEN_CASE(256)
+        MFCC_GEN_CASE(512)
+        MFCC_GEN_CASE(1024)
+#undef MFCC_GEN_CASE
+        default:
+            return MFCC_HIP_ERROR_UNSUPPORTED;
+    }
+    return MFCC_HIP_SUCCESS;
 }
 
 int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t stride, size_t nch,
@@ -429,6 +460,7 @@ int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t s
 
     DeviceGuard guard(h->device);
     const long long total = s.total_frames;
+    const bool logmel = is_logmel(h->r);
     if (fixed && h->fixed512_ok) {
         mfcc_fixed512::launch(s, h->x5, static_cast<int16_t *>(d_out), h->n_cu, h->stream);
     } else if (fixed) {
@@ -455,6 +487,14 @@ int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t s
             default:
                 return MFCC_HIP_ERROR_UNSUPPORTED;
         }
+    } else if (logmel && use_fused(h)) {
+        // log-mel output: the twelve-wave form only (the four-wave one has no log-mel tail)
+        if (!mfcc_fused12::launch<true>(s, h->fu, h->fused_dense, static_cast<float *>(d_out), h->n_cu, h->stream))
+            return MFCC_HIP_ERROR_UNSUPPORTED;
+    } else if (logmel && h->fused1k_ok && h->r.float_impl == MFCC_HIP_IMPL_AUTO) {
+        // the bf16-split twelve-wave form (build_tables leaves the diagnostic overrides aside for a log-mel handle)
+        if (!mfcc_fused1024_w12bf::launch<true>(s, h->f1k, static_cast<float *>(d_out), h->n_cu, h->stream))
+            return MFCC_HIP_ERROR_UNSUPPORTED;
     } else if (use_fused(h)) {
         const bool done = h->fused_w12 &&
                           mfcc_fused12::launch(s, h->fu, h->fused_dense, static_cast<float *>(d_out), h->n_cu, h->stream);
@@ -471,30 +511,8 @@ int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t s
         long long cap = (long long)h->n_cu * 128;    // measured: 8 per CU 3.55 ms, 32 3.24, 128 3.06 (nfft 256)
         if (blocks > cap) blocks = cap;
         float *o = static_cast<float *>(d_out);
-        switch (h->r.nfft) {
-            case 64:
-                hipLaunchKernelGGL(mfcc_k::mfcc_float_generic_kernel<64>, dim3((unsigned)blocks),
-                                   dim3(mfcc_k::kBlock), 0, h->stream, s, h->ft, o);
-                break;
-            case 128:
-                hipLaunchKernelGGL(mfcc_k::mfcc_float_generic_kernel<128>, dim3((unsigned)blocks),
-                                   dim3(mfcc_k::kBlock), 0, h->stream, s, h->ft, o);
-                break;
-            case 256:
-                hipLaunchKernelGGL(mfcc_k::mfcc_float_generic_kernel<256>, dim3((unsigned)blocks),
-                                   dim3(mfcc_k::kBlock), 0, h->stream, s, h->ft, o);
-                break;
-            case 512:
-                hipLaunchKernelGGL(mfcc_k::mfcc_float_generic_kernel<512>, dim3((unsigned)blocks),
-                                   dim3(mfcc_k::kBlock), 0, h->stream, s, h->ft, o);
-                break;
-            case 1024:
-                hipLaunchKernelGGL(mfcc_k::mfcc_float_generic_kernel<1024>, dim3((unsigned)blocks),
-                                   dim3(mfcc_k::kBlock), 0, h->stream, s, h->ft, o);
-                break;
-            default:
-                return MFCC_HIP_ERROR_UNSUPPORTED;
-        }
+        const int rc = logmel ? launch_generic<true>(h, s, (unsigned)blocks, o) : launch_generic<false>(h, s, (unsigned)blocks, o);
+        if (rc) return rc;
     }
     HIP_TRY(h, hipGetLastError());
     return MFCC_HIP_SUCCESS;
@@ -711,7 +729,7 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     const size_t nf = count_frames(h->r, n);
     if (n_frames) *n_frames = nf;
     if (nf == 0 || nch == 0) return MFCC_HIP_SUCCESS;
-    const size_t ncep = size_t(h->r.n_cep), hop = size_t(h->r.hop), nfft = size_t(h->r.nfft);
+    const size_t ncep = row_width(h->r), hop = size_t(h->r.hop), nfft = size_t(h->r.nfft);   // elements per row
     const size_t n_out = nf * nch * ncep;
     if (!out || cap < n_out) return MFCC_HIP_ERROR_BUFFER_SMALL;
     DeviceGuard guard(h->device);
@@ -799,7 +817,7 @@ int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, con
                        OutT *d_out, size_t cap, size_t *frame_offsets) {
     if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
-    const size_t hop = size_t(h->r.hop), nfft = size_t(h->r.nfft), ncep = size_t(h->r.n_cep);
+    const size_t hop = size_t(h->r.hop), nfft = size_t(h->r.nfft), ncep = row_width(h->r);   // elements per row
     DeviceGuard guard(h->device);
     // A corpus of equal-length utterances lying back to back (BASELINE config 5: 10 000 x 10 s) IS a multi-channel
     // stream, channel stride = utterance length: no packing copy, no row gather, no descriptors, the same bits (every
@@ -885,8 +903,12 @@ int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, con
             pd->in_flight = true;
             auto *d_chans = static_cast<const mfcc_fused12::RaggedChan *>(h->d_in);
             auto *d_map = reinterpret_cast<mfcc_fused12::RaggedTile *>(static_cast<char *>(h->d_in) + map_off);
-            if (mfcc_fused12::launch_ragged(d_pcm, d_chans, (int)n_utt, d_map, (int)n_tiles, h->fu, h->fused_dense,
-                                            reinterpret_cast<float *>(d_out), h->n_cu, h->stream)) {
+            const bool launched =
+                is_logmel(h->r) ? mfcc_fused12::launch_ragged<true>(d_pcm, d_chans, (int)n_utt, d_map, (int)n_tiles, h->fu,
+                                                                    h->fused_dense, reinterpret_cast<float *>(d_out), h->n_cu, h->stream)
+                                : mfcc_fused12::launch_ragged(d_pcm, d_chans, (int)n_utt, d_map, (int)n_tiles, h->fu,
+                                                              h->fused_dense, reinterpret_cast<float *>(d_out), h->n_cu, h->stream);
+            if (launched) {
                 HIP_TRY(h, hipGetLastError());
                 return scratch_release(h);
             }
@@ -961,7 +983,7 @@ int process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const siz
                    OutT *out, size_t cap, size_t *frame_offsets) {
     if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
-    const size_t ncep = size_t(h->r.n_cep);
+    const size_t ncep = row_width(h->r);               // elements per row
     size_t total = 0;
     std::vector<size_t> rel(n_utt + 1, 0);
     for (size_t u = 0; u < n_utt; ++u) {
@@ -1340,6 +1362,8 @@ int mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n
 const char *mfcc_hip_kernel_name(const mfcc_hip_handle *h, int fixed) {
     if (!h) return "";
     if (fixed) return h->fixed512_ok ? mfcc_fixed512::kernel_name() : "mfcc_fixed_kernel";
+    // a log-mel handle runs the twelve-wave forms only (build_tables ignores the diagnostic overrides for it): the
+    // names below follow from that
     if (use_fused(h)) return h->fused_w12 ? mfcc_fused12::kernel_name() : mfcc_fused::kernel_name();
     if (h->fused1k_ok && h->r.float_impl == MFCC_HIP_IMPL_AUTO)
         return !h->f1k_w12 ? mfcc_fused1024::kernel_name()
@@ -1350,6 +1374,7 @@ const char *mfcc_hip_kernel_name(const mfcc_hip_handle *h, int fixed) {
 int mfcc_hip_convert_wav(mfcc_hip_handle *h, const char *wav_in, const char *mfcc_out, int fixed,
                          size_t *n_frames_out) {
     if (!h || !wav_in || !mfcc_out) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
     std::vector<int16_t> pcm;
     int rc = read_wav_i16(wav_in, h->r.sample_rate, pcm);
     if (rc) return rc;
@@ -1390,6 +1415,7 @@ static inline int16_t to_mfcc_i16(float v) {
 int mfcc_hip_convert_wavs(mfcc_hip_handle *h, const char *const *wav_in, const char *const *mfcc_out, size_t n_files,
                           int fixed, size_t *n_frames_each) {
     if (!h || (n_files && (!wav_in || !mfcc_out))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
     std::vector<int16_t> pcm;
     std::vector<size_t> off(n_files + 1, 0), fo(n_files + 1, 0);
     for (size_t i = 0; i < n_files; ++i) {
@@ -1480,7 +1506,7 @@ int stream_reserve(mfcc_hip_stream *s, size_t samples, size_t out_bytes) {
 int stream_emit(mfcc_hip_stream *s, size_t total, size_t nf, void *out) {
     mfcc_hip_handle *h = s->h;
     const size_t esz = s->fixed ? sizeof(int16_t) : sizeof(float);
-    const size_t bytes = nf * size_t(h->r.n_cep) * esz;
+    const size_t bytes = nf * row_width(h->r) * esz;
     int rc = launch(h, s->fixed, s->buf[s->cur], total, total + 1, 1, /*halo=*/1, s->d_out, nullptr, nf);
     if (rc) return rc;
     HIP_TRY(h, hipMemcpyAsync(out, s->d_out, bytes, hipMemcpyDeviceToHost, h->stream));
@@ -1502,7 +1528,7 @@ int mfcc_hip_stream_create(mfcc_hip_handle *h, int fixed, mfcc_hip_stream **out)
     s->fixed = fixed != 0;
     ++h->n_sessions;
     DeviceGuard guard(h->device);
-    int rc = stream_reserve(s, size_t(h->r.nfft) * 8, size_t(64) * size_t(h->r.n_cep) * sizeof(float));
+    int rc = stream_reserve(s, size_t(h->r.nfft) * 8, size_t(64) * row_width(h->r) * sizeof(float));
     if (rc) {
         mfcc_hip_stream_destroy(s);
         return rc;
@@ -1544,7 +1570,7 @@ int mfcc_hip_stream_push(mfcc_hip_stream *s, const int16_t *samples, size_t n, v
                          size_t *n_frames_out) {
     if (!s || (n && !samples)) return MFCC_HIP_ERROR_INVALID_PARAM;
     mfcc_hip_handle *h = s->h;
-    const size_t nfft = size_t(h->r.nfft), hop = size_t(h->r.hop), ncep = size_t(h->r.n_cep);
+    const size_t nfft = size_t(h->r.nfft), hop = size_t(h->r.hop), ncep = row_width(h->r);
     const size_t total = s->pending + n;
     const size_t nf = total >= nfft ? (total - nfft) / hop + 1 : 0;          // frames this push completes
     if (n_frames_out) *n_frames_out = nf;
@@ -1577,7 +1603,7 @@ int mfcc_hip_stream_flush(mfcc_hip_stream *s, void *out, size_t cap, size_t *n_f
     mfcc_hip_handle *h = s->h;
     const size_t nf = h->r.pad_mode == MFCC_HIP_PAD_STREAM ? 1 : 0;
     if (n_frames_out) *n_frames_out = nf;
-    if (nf && (!out || cap < size_t(h->r.n_cep))) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    if (nf && (!out || cap < row_width(h->r))) return MFCC_HIP_ERROR_BUFFER_SMALL;
     DeviceGuard guard(h->device);
     if (nf) {
         // the zero-padded tail frame of main.c:134-144: the pending samples, then zeros (the kernels read
