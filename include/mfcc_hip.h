@@ -13,7 +13,8 @@
  * Conventions kept from the reference:
  *   - 0 = success, negative error codes in the ft601_error range      software/ft601.h:25-32
  *   - caller owns every in/out buffer; the handle owns device tables/streams   main.c:109,40
- *   - output layout [frame][n_cep] row-major, i.e. the `.mfcc` file layout     main.c:162-165;
+ *   - output layout [frame][n_cep] row-major, i.e. the `.mfcc` file layout     main.c:162-165
+ *     (raw, or standardized per channel / utterance: mfcc_hip_set_normalize);
  *     with output = MFCC_HIP_OUTPUT_LOGMEL the rows are [frame][n_mel] log2 mel energies instead
  *     (the stage before the DCT, notebook/MFCC.ipynb `audio_log`); every "n_cep" below that
  *     sizes an output row then reads "n_mel"
@@ -74,6 +75,19 @@ enum mfcc_hip_output {
                                      points, fixed streaming sessions and the .mfcc file writers
                                      return MFCC_HIP_ERROR_UNSUPPORTED; lifter must be 0; n_cep is
                                      validated but not used                                       */
+};
+
+/* per-segment normalization of float output rows (mfcc_hip_set_normalize / mfcc_hip_normalize_dev below).  A segment is
+ * one channel of a dense call or one utterance of a ragged one; per column j of its rows, over the FINITE values F
+ * (a silent frame's -inf / NaN are left out):  mu = mean(F),  sigma = sqrt(mean((F - mu)^2)) (population std, the
+ * `sklearn.preprocessing.scale` of the reference's software/genlibrosa.py), both in float64, sigma' = 1 where
+ * sigma < 10 * 2^-52 (a constant column gives 0).  y = (x - mu32) * r32 with mu and 1 / sigma' rounded once to fp32
+ * (MEAN: r32 = 1); non-finite x are written back unchanged.  The result of a segment depends on its rows alone: it
+ * is the same bits from every entry point, any chunking, any run.                                              */
+enum mfcc_hip_normalize {
+    MFCC_HIP_NORMALIZE_NONE = 0,      /* raw rows (the state after mfcc_hip_create)   */
+    MFCC_HIP_NORMALIZE_MEAN = 1,      /* y = x - mu                                     */
+    MFCC_HIP_NORMALIZE_MEAN_VAR = 2   /* y = (x - mu) / sigma'  (CMVN)                  */
 };
 
 /*
@@ -213,6 +227,22 @@ int  mfcc_hip_process_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm,
 int  mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n_samples_per_ch,
                        size_t ch_stride_samples, size_t n_channels, void *d_out,
                        int warmup, int iters, float *avg_ms);
+
+/* ---- per-segment normalization (enum mfcc_hip_normalize) -------------------------------------------------------
+ * The handle's mode applies to every float call enqueued after it: mfcc_hip_process_i16, mfcc_hip_process_i16_dev,
+ * both float mfcc_hip_process_ragged_* entry points and mfcc_hip_time_dev (which then times the launch AND the
+ * normalization passes, what mfcc_hip_process_i16_dev enqueues) return normalized rows.  With a mode other than NONE
+ * the fixed-point entry points, mfcc_hip_stream_create, mfcc_hip_convert_wav(s) and mfcc_hip_process_i16_dev with
+ * halo = 1 (a shard of a longer stream: its statistics would not be the stream's) return MFCC_HIP_ERROR_UNSUPPORTED.
+ * NULL handle or an unknown mode: MFCC_HIP_ERROR_INVALID_PARAM; a handle with live streaming sessions:
+ * MFCC_HIP_ERROR_BUSY.  The parameter block and the ABI version are unchanged.                                  */
+int  mfcc_hip_set_normalize(mfcc_hip_handle *h, int mode);
+/* The kernels' direct entry: normalizes float32 rows [seg_offsets[n_segs]][row_width] in HBM in place, segment k =
+ * rows seg_offsets[k] .. seg_offsets[k + 1] (host array, n_segs + 1 entries, must not decrease; rows before
+ * seg_offsets[0] are not touched).  row_width 1..64, d_rows 4-byte aligned.  Asynchronous on the handle's stream;
+ * mode NONE or n_segs = 0 is a no-op.  E.g. the rows of a frame-range-sharded stream after their gather. */
+int  mfcc_hip_normalize_dev(mfcc_hip_handle *h, void *d_rows, int row_width, const size_t *seg_offsets, size_t n_segs,
+                            int mode);
 
 /* name of the kernel symbol process_*_dev launches for this handle (to match rocprofv3 rows).  A log-mel handle runs
  * the log-mel instantiation of the kernel named (the default form: MFCC_HIP_FUSED512 / MFCC_HIP_FUSED1024 do not

@@ -28,6 +28,16 @@ PAD_STREAM = _lib.PAD_STREAM
 _PAD = {"notebook": PAD_NOTEBOOK, "stream": PAD_STREAM, PAD_NOTEBOOK: PAD_NOTEBOOK, PAD_STREAM: PAD_STREAM}
 _IMPL = {"auto": _lib.IMPL_AUTO, "generic": _lib.IMPL_GENERIC, "fused512": _lib.IMPL_FUSED512}
 _OUTPUT = {"cepstra": _lib.OUTPUT_CEPSTRA, "logmel": _lib.OUTPUT_LOGMEL}
+_NORMALIZE = {None: _lib.NORMALIZE_NONE, "none": _lib.NORMALIZE_NONE, "mean": _lib.NORMALIZE_MEAN,
+              "meanvar": _lib.NORMALIZE_MEAN_VAR}
+
+
+def normalize_mode(mode) -> int:
+    """``None`` / ``"none"``, ``"mean"`` or ``"meanvar"`` -> ``enum mfcc_hip_normalize``."""
+    try:
+        return _NORMALIZE[mode]
+    except (KeyError, TypeError):
+        raise ValueError("normalize must be None, 'mean' or 'meanvar', not %r" % (mode,)) from None
 
 
 def make_params(nfft=512, hop=None, nfilters=32, nceptrums=13, samplerate=16000, pad_mode="notebook",
@@ -94,12 +104,19 @@ class MFCC:
     ``output="logmel"`` makes every float entry point return rows of ``nfilters`` log2 mel band energies
     (the notebook's ``audio_log.T``, -inf for a silent band) instead of ``nceptrums`` cepstra; the width of a
     row is :attr:`num_features` either way.  The fixed-point path and ``convert`` refuse such a handle.
+
+    ``normalize="mean"`` / ``"meanvar"`` standardizes every channel / utterance of every float result over its own
+    frames, column by column (CMVN: ``sklearn.preprocessing.scale`` of the reference's ``software/genlibrosa.py``;
+    -inf / NaN of silent frames are left out and left as they are) -- ``process``, ``process_batch`` and
+    ``process_packed``.  ``process_fixed``, :meth:`stream`, ``convert*`` and ``halo=1`` then raise ``UNSUPPORTED``.
     """
 
     def __init__(self, width=16, nfft=512, samplerate=16e3, nfilters=16, nceptrums=16, *, hop=None,
-                 pad_mode="notebook", power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra"):
+                 pad_mode="notebook", power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra",
+                 normalize=None):
         if width != 16:
             raise ValueError("only width=16 (int16 PCM) is supported, like every reference target")
+        norm = normalize_mode(normalize)
         self.width = width
         self.nfft = int(nfft)
         self.samplerate = samplerate
@@ -123,6 +140,40 @@ class MFCC:
                 pass
         _lib.check(self._lib.mfcc_hip_create(C.byref(self._params), C.byref(h)), "mfcc_hip_create")
         self._h = h
+        self.normalize = None
+        if norm != _lib.NORMALIZE_NONE:
+            self.set_normalize(normalize)
+
+    def set_normalize(self, mode):
+        """The handle's normalization for every float call after this one (None, ``"mean"``, ``"meanvar"``)."""
+        _lib.check(self._lib.mfcc_hip_set_normalize(self._h, normalize_mode(mode)), "set_normalize")
+        self.normalize = None if normalize_mode(mode) == _lib.NORMALIZE_NONE else mode
+
+    def normalize_rows(self, rows, frame_offsets=None, mode="meanvar"):
+        """Normalize a CUDA float32 tensor of rows in place, on the current torch stream, and return it.  ``rows``:
+        ``(frames, width)`` with ``frame_offsets`` (segment ``u`` = rows ``fo[u]:fo[u + 1]``, e.g. what
+        :meth:`process_packed` returns) or, without them, one segment; ``(channels, frames, width)``: one segment per
+        channel.  ``width`` 1..64, independent of this handle's own rows."""
+        import torch
+        if rows.dtype != torch.float32 or not rows.is_cuda or not rows.is_contiguous() or rows.dim() not in (2, 3):
+            raise TypeError("rows must be a contiguous 2-D or 3-D CUDA(HIP) float32 tensor")
+        width = int(rows.shape[-1])
+        if frame_offsets is None:
+            nseg = int(rows.shape[0]) if rows.dim() == 3 else 1
+            per = int(rows.shape[1]) if rows.dim() == 3 else int(rows.shape[0])
+            fo = np.arange(nseg + 1, dtype=np.uint64) * np.uint64(per)
+        else:
+            fo = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
+            if fo.ndim != 1 or len(fo) < 1:
+                raise ValueError("frame_offsets must be 1-D with n_segments + 1 entries")
+            if len(fo) > 1 and int(fo[-1]) * width > rows.numel():
+                raise ValueError("frame_offsets run past the end of rows")
+        self._check_device(rows)
+        with self._on_torch_stream(rows.device):
+            _lib.check(self._lib.mfcc_hip_normalize_dev(self._h, C.c_void_p(rows.data_ptr()), width,
+                                                        fo.ctypes.data_as(C.c_void_p), len(fo) - 1,
+                                                        normalize_mode(mode)), "normalize_dev")
+        return rows
 
     # -- lifetime (``reset`` of the core clears all state: every call here starts from reset)
     def close(self):

@@ -1,0 +1,250 @@
+// Per-segment mean / variance normalization of float rows already in HBM (include/mfcc_hip.h:
+// mfcc_hip_normalize_dev).  A pass after the MFCC kernels, not a change to them.
+//
+// rows: float32 [R][W], W = 1..64; a segment is a range of whole rows (one channel of a dense call, one utterance of
+// a ragged one).  Three launches:
+//   stats     one read of the rows: every workgroup takes a tile of kTileFloats / W rows of ONE segment (tiles
+//             counted from the segment's own first row), stages it in LDS and writes the tile's per-column
+//             (n, mean, M2) of the finite values in float64 (two passes over the LDS copy: sum, then squares of the
+//             deviations from the tile mean)
+//   finalize  one workgroup per segment combines its tiles' partials with Chan's formula in a fixed order and
+//             stores (mu, 1/sigma') per column, each rounded once to fp32
+//   apply     one read and one write: y = (x - mu) * r for finite x, x unchanged otherwise
+// Every order of summation is a function of W and of the segment's rows alone (the 16-byte-aligned float4 body of
+// a tile only decides how the bytes reach LDS or registers): a segment gives the same bits wherever it lies, in
+// whatever call.  No atomics.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace mfcc_norm {
+
+constexpr int kThreads = 256;
+constexpr int kTileFloats = 8192;      // 32 KB of LDS per stats workgroup
+constexpr int kMaxWidth = 64;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// rows per tile: a function of the row width only
+__host__ __device__ inline int tile_rows(int width) { return kTileFloats / width; }
+
+// one tile of a segment (table form of Segs)
+struct BlockRec {
+    long long row0;
+    int rows;
+    int seg;
+};
+
+// per-column partial of one tile: count, mean and sum of squared deviations of the finite values
+struct Part {
+    double n, mean, m2;
+};
+
+// The tiles of a call.  Uniform form (blk == nullptr): n_segs segments of seg_rows rows each, back to back from row
+// base_row, blocks_per_seg tiles each (a dense multi-channel call, equal-length utterances).  Table form: one record
+// per tile and the first tile of every segment (seg_blk0, n_segs + 1 entries), built on the host.
+struct Segs {
+    long long base_row, seg_rows, blocks_per_seg;
+    const BlockRec *blk;
+    const long long *seg_blk0;
+    long long n_blocks, n_segs;
+    int width, tile_rows;
+};
+
+__device__ __forceinline__ void tile_of(const Segs &s, long long b, long long &row0, int &rows, long long &seg) {
+    if (!s.blk) {
+        seg = b / s.blocks_per_seg;
+        const long long k = b - seg * s.blocks_per_seg;
+        row0 = s.base_row + seg * s.seg_rows + k * s.tile_rows;
+        const long long left = s.seg_rows - k * s.tile_rows;
+        rows = int(left < s.tile_rows ? left : s.tile_rows);
+    } else {
+        const BlockRec r = s.blk[b];
+        row0 = r.row0;
+        rows = r.rows;
+        seg = r.seg;
+    }
+}
+
+__device__ __forceinline__ bool finite(float v) { return __builtin_isfinite(v); }
+
+// Elements [e0, e0 + n) of x: the first one at which x + e is 16-byte aligned (x itself is 4-byte aligned; mis =
+// its offset from 16 bytes in floats), clamped to n.  Everything before is the scalar head, then float4s, then the
+// scalar tail; nothing outside [e0, e0 + n) is read.
+__device__ __forceinline__ int head_of(long long e0, int n, unsigned mis) {
+    const int head = int((4u - unsigned((e0 + mis) & 3)) & 3u);
+    return head < n ? head : n;
+}
+
+__global__ __launch_bounds__(kThreads) void normalize_stats_kernel(const float *__restrict__ x, Segs s,
+                                                                   Part *__restrict__ part) {
+    __shared__ float tile[kTileFloats];
+    __shared__ double red[kThreads];
+    __shared__ double cnt[kThreads];
+    __shared__ double mean_s[kMaxWidth];
+    const int W = s.width, G = kThreads / W, t = threadIdx.x, c = t % W, g = t / W;
+    const unsigned mis = unsigned(reinterpret_cast<uintptr_t>(x) >> 2) & 3u;
+    for (long long b = blockIdx.x; b < s.n_blocks; b += gridDim.x) {
+        long long row0, seg;
+        int rows;
+        tile_of(s, b, row0, rows, seg);
+        const long long e0 = row0 * W;
+        const int n = rows * W, head = head_of(e0, n, mis), nv = (n - head) >> 2;
+        const f32x4 *xv = reinterpret_cast<const f32x4 *>(x + e0 + head);
+        for (int i = t; i < nv; i += kThreads) {
+            const f32x4 v = xv[i];
+            float *d = tile + head + 4 * i;
+            d[0] = v.x;
+            d[1] = v.y;
+            d[2] = v.z;
+            d[3] = v.w;
+        }
+        if (t < head) tile[t] = x[e0 + t];
+        for (int i = head + 4 * nv + t; i < n; i += kThreads) tile[i] = x[e0 + i];
+        __syncthreads();
+        // pass 1: thread (c, g) takes rows g, g + G, ... of column c; the G stripes are then added in order
+        double sum = 0.0, k = 0.0;
+        if (g < G)
+            for (int r = g; r < rows; r += G) {
+                const float v = tile[r * W + c];
+                if (finite(v)) {
+                    sum += double(v);
+                    k += 1.0;
+                }
+            }
+        red[t] = sum;
+        cnt[t] = k;
+        __syncthreads();
+        if (t < W) {
+            double S = 0.0, K = 0.0;
+            for (int j = 0; j < G; ++j) {
+                S += red[j * W + t];
+                K += cnt[j * W + t];
+            }
+            mean_s[t] = K > 0.0 ? S / K : 0.0;
+        }
+        __syncthreads();
+        // pass 2: squared deviations from the tile's mean
+        const double m = mean_s[c];
+        double q = 0.0;
+        if (g < G)
+            for (int r = g; r < rows; r += G) {
+                const float v = tile[r * W + c];
+                if (finite(v)) {
+                    const double d = double(v) - m;
+                    q += d * d;
+                }
+            }
+        red[t] = q;
+        __syncthreads();
+        if (t < W) {
+            double Q = 0.0, K = 0.0;
+            for (int j = 0; j < G; ++j) {
+                Q += red[j * W + t];
+                K += cnt[j * W + t];
+            }
+            part[b * W + t] = Part{K, mean_s[t], Q};
+        }
+        __syncthreads();           // the next tile overwrites tile, red and cnt
+    }
+}
+
+// Chan et al.: (n, m, q) <- (n, m, q) combined with (nb, mb, qb)
+__device__ __forceinline__ void chan(double &n, double &m, double &q, double nb, double mb, double qb) {
+    if (nb == 0.0) return;
+    if (n == 0.0) {
+        n = nb;
+        m = mb;
+        q = qb;
+        return;
+    }
+    const double N = n + nb, d = mb - m;
+    m += d * (nb / N);
+    q += qb + d * d * (n * nb / N);
+    n = N;
+}
+
+// mode: 1 = mean only (r = 1), 2 = mean and variance.  coef[seg][col] = (mu, r), fp32
+__global__ __launch_bounds__(kThreads) void normalize_finalize_kernel(Segs s, const Part *__restrict__ part,
+                                                                      float2 *__restrict__ coef, int mode) {
+    __shared__ double sn[kThreads], sm[kThreads], sq[kThreads];
+    const int W = s.width, G = kThreads / W, t = threadIdx.x, c = t % W, g = t / W;
+    for (long long seg = blockIdx.x; seg < s.n_segs; seg += gridDim.x) {
+        long long b0, b1;
+        if (!s.blk) {
+            b0 = seg * s.blocks_per_seg;
+            b1 = b0 + s.blocks_per_seg;
+        } else {
+            b0 = s.seg_blk0[seg];
+            b1 = s.seg_blk0[seg + 1];
+        }
+        // stripe g combines tiles b0 + g, b0 + g + G, ... in order; then the stripes are combined in order
+        double n = 0.0, m = 0.0, q = 0.0;
+        if (g < G)
+            for (long long b = b0 + g; b < b1; b += G) {
+                const Part p = part[b * W + c];
+                chan(n, m, q, p.n, p.mean, p.m2);
+            }
+        sn[t] = n;
+        sm[t] = m;
+        sq[t] = q;
+        __syncthreads();
+        if (t < W) {
+            n = m = q = 0.0;
+            for (int j = 0; j < G; ++j) chan(n, m, q, sn[j * W + t], sm[j * W + t], sq[j * W + t]);
+            float mu = 0.0f, r = 1.0f;          // no finite value: y = (x - 0) * 1 = x
+            if (n > 0.0) {
+                mu = float(m);
+                if (mode == 2) {
+                    double sd = sqrt(q / n);
+                    if (sd < 10.0 * 2.220446049250313e-16) sd = 1.0;      // sklearn's _handle_zeros_in_scale
+                    r = float(1.0 / sd);
+                }
+            }
+            coef[seg * W + t] = make_float2(mu, r);
+        }
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ float apply1(float v, float2 cf) { return finite(v) ? (v - cf.x) * cf.y : v; }
+
+__global__ __launch_bounds__(kThreads) void normalize_apply_kernel(float *__restrict__ x, Segs s,
+                                                                   const float2 *__restrict__ coef) {
+    __shared__ float2 cf[kMaxWidth];
+    const int W = s.width, t = threadIdx.x;
+    const int step = (4 * kThreads) % W;          // column advance of a lane per float4 stride
+    const unsigned mis = unsigned(reinterpret_cast<uintptr_t>(x) >> 2) & 3u;
+    for (long long b = blockIdx.x; b < s.n_blocks; b += gridDim.x) {
+        long long row0, seg;
+        int rows;
+        tile_of(s, b, row0, rows, seg);
+        if (t < W) cf[t] = coef[seg * W + t];
+        __syncthreads();
+        // a tile starts on a row: the column of element e0 + i is i % W
+        const long long e0 = row0 * W;
+        const int n = rows * W, head = head_of(e0, n, mis), nv = (n - head) >> 2;
+        f32x4 *xv = reinterpret_cast<f32x4 *>(x + e0 + head);
+        int col = (head + 4 * t) % W;
+        for (int i = t; i < nv; i += kThreads) {
+            f32x4 v = xv[i];
+            int k = col;
+            v.x = apply1(v.x, cf[k]);
+            if (++k == W) k = 0;
+            v.y = apply1(v.y, cf[k]);
+            if (++k == W) k = 0;
+            v.z = apply1(v.z, cf[k]);
+            if (++k == W) k = 0;
+            v.w = apply1(v.w, cf[k]);
+            xv[i] = v;
+            col += step;
+            if (col >= W) col -= W;
+        }
+        if (t < head) x[e0 + t] = apply1(x[e0 + t], cf[t % W]);
+        for (int i = head + 4 * nv + t; i < n; i += kThreads) x[e0 + i] = apply1(x[e0 + i], cf[i % W]);
+        __syncthreads();           // the next tile overwrites cf
+    }
+}
+
+}  // namespace mfcc_norm

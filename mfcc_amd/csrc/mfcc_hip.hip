@@ -23,6 +23,7 @@
 #include "kernel_fused1024_w12.hpp"
 #include "kernel_fused512.hpp"
 #include "kernel_fused512_w12.hpp"
+#include "kernel_normalize.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -169,6 +170,13 @@ struct mfcc_hip_handle {
     // the handle; the last mfcc_hip_stream_destroy then tears it down (include/mfcc_hip.h: lifetime)
     int n_sessions = 0;
     bool destroy_pending = false;
+    // per-segment normalization (mfcc_hip_set_normalize): the mode, the stats / coefficient / tile-table scratch and,
+    // for host-buffer calls whose chunks cut a channel, the whole result on the device (run_host_pipeline)
+    int norm = MFCC_HIP_NORMALIZE_NONE;
+    void *d_norm = nullptr;
+    size_t d_norm_bytes = 0;
+    void *d_full = nullptr;
+    size_t d_full_bytes = 0;
 };
 
 namespace {
@@ -531,6 +539,101 @@ int ensure(mfcc_hip_handle *h, void **p, size_t *have, size_t want) {
     return MFCC_HIP_SUCCESS;
 }
 
+// ---- per-segment mean / variance normalization (kernel_normalize.hpp): every float entry point
+// of a handle with a mode other than NONE runs this after its kernels, on the handle's stream, over the rows it wrote.
+// Scratch (h->d_norm): [tile partials: n_blocks * W * 24 B][coefficients: n_segs * W * 8 B][table form: the first tile
+// of every segment (n_segs + 1) and one record per tile].  The table is built in pinned memory (desc_acquire).
+int normalize_enqueue(mfcc_hip_handle *h, float *d_rows, mfcc_norm::Segs s, const long long *host_table,
+                      size_t table_ll, int mode) {
+    const size_t W = size_t(s.width);
+    const size_t part_bytes = (size_t(s.n_blocks) * W * sizeof(mfcc_norm::Part) + 255) & ~size_t(255);
+    const size_t coef_bytes = (size_t(s.n_segs) * W * sizeof(float2) + 255) & ~size_t(255);
+    int rc = ensure(h, &h->d_norm, &h->d_norm_bytes, part_bytes + coef_bytes + table_ll * sizeof(long long) + 64);
+    if (rc) return rc;
+    if ((rc = scratch_acquire(h))) return rc;
+    char *base = static_cast<char *>(h->d_norm);
+    auto *part = reinterpret_cast<mfcc_norm::Part *>(base);
+    auto *coef = reinterpret_cast<float2 *>(base + part_bytes);
+    if (host_table) {
+        long long *d_table = reinterpret_cast<long long *>(base + part_bytes + coef_bytes);
+        HIP_TRY(h, hipMemcpyAsync(d_table, host_table, table_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+        s.seg_blk0 = d_table;
+        s.blk = reinterpret_cast<const mfcc_norm::BlockRec *>(d_table + s.n_segs + 1);
+    }
+    const unsigned grid = unsigned(std::min<long long>(s.n_blocks, 1 << 20));
+    const unsigned grid_f = unsigned(std::min<long long>(s.n_segs, 1 << 20));
+    hipLaunchKernelGGL(mfcc_norm::normalize_stats_kernel, dim3(grid), dim3(mfcc_norm::kThreads), 0, h->stream,
+                       static_cast<const float *>(d_rows), s, part);
+    hipLaunchKernelGGL(mfcc_norm::normalize_finalize_kernel, dim3(grid_f), dim3(mfcc_norm::kThreads), 0, h->stream, s,
+                       static_cast<const mfcc_norm::Part *>(part), coef, mode);
+    hipLaunchKernelGGL(mfcc_norm::normalize_apply_kernel, dim3(grid), dim3(mfcc_norm::kThreads), 0, h->stream, d_rows, s,
+                       static_cast<const float2 *>(coef));
+    HIP_TRY(h, hipGetLastError());
+    return scratch_release(h);
+}
+
+// n_segs segments of seg_rows rows each, back to back from row base_row
+int normalize_uniform(mfcc_hip_handle *h, float *d_rows, int width, size_t base_row, size_t n_segs, size_t seg_rows,
+                      int mode) {
+    if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0 || seg_rows == 0) return MFCC_HIP_SUCCESS;
+    mfcc_norm::Segs s{};
+    s.width = width;
+    s.tile_rows = mfcc_norm::tile_rows(width);
+    s.base_row = (long long)base_row;
+    s.seg_rows = (long long)seg_rows;
+    s.blocks_per_seg = (long long)((seg_rows + size_t(s.tile_rows) - 1) / size_t(s.tile_rows));
+    s.n_segs = (long long)n_segs;
+    s.n_blocks = s.blocks_per_seg * s.n_segs;
+    return normalize_enqueue(h, d_rows, s, nullptr, 0, mode);
+}
+
+// segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
+int normalize_segments(mfcc_hip_handle *h, float *d_rows, int width, const size_t *off, size_t n_segs, int mode) {
+    if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0 || off[n_segs] == off[0]) return MFCC_HIP_SUCCESS;
+    const size_t len0 = off[1] - off[0];
+    bool uniform = true;
+    for (size_t k = 1; k < n_segs && uniform; ++k) uniform = off[k + 1] - off[k] == len0;
+    if (uniform) return normalize_uniform(h, d_rows, width, off[0], n_segs, len0, mode);
+    const size_t tr = size_t(mfcc_norm::tile_rows(width));
+    size_t n_blocks = 0;
+    for (size_t k = 0; k < n_segs; ++k) n_blocks += (off[k + 1] - off[k] + tr - 1) / tr;
+    if (n_segs >= (size_t(1) << 31)) return MFCC_HIP_ERROR_INVALID_PARAM;       // BlockRec::seg is an int
+    static_assert(sizeof(mfcc_norm::BlockRec) == 2 * sizeof(long long), "record layout");
+    const size_t table_ll = n_segs + 1 + 2 * n_blocks;
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    int rc = desc_acquire(h, table_ll, &pd);
+    if (rc) return rc;
+    long long *blk0 = pd->p;
+    auto *rec = reinterpret_cast<mfcc_norm::BlockRec *>(pd->p + n_segs + 1);
+    size_t b = 0;
+    for (size_t k = 0; k < n_segs; ++k) {
+        blk0[k] = (long long)b;
+        for (size_t r = off[k]; r < off[k + 1]; r += tr)
+            rec[b++] = mfcc_norm::BlockRec{(long long)r, int(std::min(tr, off[k + 1] - r)), int(k)};
+    }
+    blk0[n_segs] = (long long)b;
+    mfcc_norm::Segs s{};
+    s.width = width;
+    s.tile_rows = int(tr);
+    s.n_segs = (long long)n_segs;
+    s.n_blocks = (long long)n_blocks;
+    rc = normalize_enqueue(h, d_rows, s, pd->p, table_ll, mode);
+    if (rc) return rc;
+    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
+    pd->in_flight = true;
+    return MFCC_HIP_SUCCESS;
+}
+
+// the dense float device path with the handle's normalization: the launch, then one segment per channel
+int launch_float_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo, void *d_out,
+                     size_t *n_frames) {
+    if (h && h->norm != MFCC_HIP_NORMALIZE_NONE && halo) return MFCC_HIP_ERROR_UNSUPPORTED;   // a shard of a longer stream
+    int rc = launch(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
+    if (rc || h->norm == MFCC_HIP_NORMALIZE_NONE) return rc;
+    DeviceGuard guard(h->device);
+    return normalize_uniform(h, static_cast<float *>(d_out), int(row_width(h->r)), 0, nch, count_frames(h->r, n), h->norm);
+}
+
 // ---- host buffers in, host buffers out: the shape of the reference's own caller (software/main.c:100-177: file in,
 // file out).  The input crosses PCIe at 340 B per frame, which is 25 times what the kernel needs per frame in time, so this
 // path is a COPY pipeline: the batch is cut into chunks of ~64 MB (whole channels, or frame ranges of a long channel with
@@ -759,14 +862,33 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
                                   (f1 - f0) * ncep, (c * nf + f0) * ncep});
             }
     }
+    // normalization: no row may leave the device before its channel's statistics exist.  Chunks of whole channels
+    // normalize their own rows before the copy back; frame-range chunks of long channels write into one device buffer of
+    // the whole result, which is normalized and copied back after the pipeline
+    const int norm = fixed ? MFCC_HIP_NORMALIZE_NONE : h->norm;
+    const bool whole = norm != MFCC_HIP_NORMALIZE_NONE && ch_bytes > kChunkBytes;
+    OutT *d_full = nullptr;
+    if (whole) {
+        const int rc = ensure(h, &h->d_full, &h->d_full_bytes, n_out * sizeof(OutT) + 64);
+        if (rc) return rc;
+        d_full = static_cast<OutT *>(h->d_full);
+    }
     std::vector<PipeChunk> pc;
     pc.reserve(chunks.size());
     for (const HostChunk &c : chunks)
-        pc.push_back({c.in, c.in_samples * sizeof(int16_t), out + c.out_off, c.out_elems * sizeof(OutT)});
-    return run_host_pipeline(h, pc, pcm, nch * ch_bytes, out, n_out * sizeof(OutT), [&](size_t i, void *d_in, void *d_out) {
+        pc.push_back({c.in, c.in_samples * sizeof(int16_t), out + c.out_off, whole ? 0 : c.out_elems * sizeof(OutT)});
+    int rc = run_host_pipeline(h, pc, pcm, nch * ch_bytes, out, whole ? 0 : n_out * sizeof(OutT), [&](size_t i, void *d_in, void *d_out) {
         const HostChunk &c = chunks[i];
-        return launch(h, fixed, d_in, c.n, c.stride, c.nch, c.halo, d_out, nullptr, c.halo || c.frames != nf ? c.frames : 0);
+        if (whole) d_out = d_full + c.out_off;
+        const int lrc = launch(h, fixed, d_in, c.n, c.stride, c.nch, c.halo, d_out, nullptr, c.halo || c.frames != nf ? c.frames : 0);
+        if (lrc || whole || norm == MFCC_HIP_NORMALIZE_NONE) return lrc;
+        return normalize_uniform(h, reinterpret_cast<float *>(d_out), int(ncep), 0, c.nch, nf, norm);
     });
+    if (rc || !whole) return rc;
+    if ((rc = normalize_uniform(h, reinterpret_cast<float *>(d_full), int(ncep), 0, nch, nf, norm))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(out, d_full, n_out * sizeof(OutT), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MFCC_HIP_SUCCESS;
 }
 
 // ---- ragged batch: many utterances of different lengths, one launch.
@@ -813,8 +935,8 @@ __global__ void pack_utterances_kernel(const int16_t *__restrict__ src, int16_t 
 }
 
 template <typename OutT>
-int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
-                       OutT *d_out, size_t cap, size_t *frame_offsets) {
+int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
+                           OutT *d_out, size_t cap, size_t *frame_offsets) {
     if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
     const size_t hop = size_t(h->r.hop), nfft = size_t(h->r.nfft), ncep = row_width(h->r);   // elements per row
@@ -972,6 +1094,17 @@ int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, con
                        d_desc + 4 * n_utt, (long long)n_utt, (int)ncep);
     HIP_TRY(h, hipGetLastError());
     return scratch_release(h);
+}
+
+// ... and the handle's normalization over the dense result, one segment per utterance (float contract only: the
+// public fixed-point entry points refuse a normalizing handle)
+template <typename OutT>
+int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
+                       OutT *d_out, size_t cap, size_t *frame_offsets) {
+    const int rc = process_ragged_dev_raw<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
+    if (rc || fixed || h->norm == MFCC_HIP_NORMALIZE_NONE || n_utt == 0) return rc;
+    DeviceGuard guard(h->device);
+    return normalize_segments(h, reinterpret_cast<float *>(d_out), int(row_width(h->r)), frame_offsets, n_utt, h->norm);
 }
 
 // Host buffers: the corpus goes to the device in ONE copy (the span offsets[0] .. offsets[n_utt] as it lies), runs through
@@ -1266,6 +1399,8 @@ void mfcc_hip_destroy(mfcc_hip_handle *h) {
     if (h->arena) (void)hipFree(h->arena);
     if (h->d_in) (void)hipFree(h->d_in);
     if (h->d_out) (void)hipFree(h->d_out);
+    if (h->d_norm) (void)hipFree(h->d_norm);
+    if (h->d_full) (void)hipFree(h->d_full);
     delete h;
 }
 
@@ -1294,6 +1429,7 @@ int mfcc_hip_process_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_
 
 int mfcc_hip_process_fixed_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_t nch,
                                int16_t *out, size_t cap, size_t *n_frames) {
+    if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
     return process_host<int16_t>(h, true, pcm, n, nch, out, cap, n_frames);
 }
 
@@ -1304,6 +1440,7 @@ int mfcc_hip_process_ragged_i16(mfcc_hip_handle *h, const int16_t *pcm, const si
 
 int mfcc_hip_process_ragged_fixed_i16(mfcc_hip_handle *h, const int16_t *pcm, const size_t *offsets, size_t n_utt,
                                       int16_t *out, size_t cap, size_t *frame_offsets) {
+    if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
     return process_ragged<int16_t>(h, true, pcm, offsets, n_utt, out, cap, frame_offsets);
 }
 
@@ -1315,26 +1452,34 @@ int mfcc_hip_process_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const
 
 int mfcc_hip_process_ragged_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const size_t *offsets, size_t n_utt,
                                           void *d_out, size_t cap, size_t *frame_offsets) {
+    if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
     return process_ragged_dev<int16_t>(h, true, static_cast<const int16_t *>(d_pcm), offsets, n_utt,
                                        static_cast<int16_t *>(d_out), cap, frame_offsets);
 }
 
 int mfcc_hip_process_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch,
                              int halo, void *d_out, size_t *n_frames) {
-    return launch(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
+    return launch_float_dev(h, d_pcm, n, stride, nch, halo, d_out, n_frames);
 }
 
 int mfcc_hip_process_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride,
                                    size_t nch, int halo, void *d_out, size_t *n_frames) {
+    if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
     return launch(h, true, d_pcm, n, stride, nch, halo, d_out, n_frames);
 }
 
 int mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n, size_t stride,
                       size_t nch, void *d_out, int warmup, int iters, float *avg_ms) {
     if (!h || iters < 1 || warmup < 0 || !avg_ms) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (fixed && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;
     DeviceGuard guard(h->device);
+    // what process_*_dev enqueues: with normalization on, the float launch and the normalization passes
+    auto once = [&]() {
+        return fixed ? launch(h, true, d_pcm, n, stride, nch, 0, d_out, nullptr)
+                     : launch_float_dev(h, d_pcm, n, stride, nch, 0, d_out, nullptr);
+    };
     for (int i = 0; i < warmup; ++i) {
-        int rc = launch(h, fixed != 0, d_pcm, n, stride, nch, 0, d_out, nullptr);
+        int rc = once();
         if (rc) return rc;
     }
     struct Events {                                // destroyed on every return path
@@ -1348,7 +1493,7 @@ int mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n
     HIP_TRY(h, hipEventCreate(&ev.e1));
     HIP_TRY(h, hipEventRecord(ev.e0, h->stream));
     for (int i = 0; i < iters; ++i) {
-        int rc = launch(h, fixed != 0, d_pcm, n, stride, nch, 0, d_out, nullptr);
+        int rc = once();
         if (rc) return rc;
     }
     HIP_TRY(h, hipEventRecord(ev.e1, h->stream));
@@ -1357,6 +1502,27 @@ int mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n
     HIP_TRY(h, hipEventElapsedTime(&ms, ev.e0, ev.e1));
     *avg_ms = ms / float(iters);
     return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_set_normalize(mfcc_hip_handle *h, int mode) {
+    if (!h || mode < MFCC_HIP_NORMALIZE_NONE || mode > MFCC_HIP_NORMALIZE_MEAN_VAR) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
+    h->norm = mode;
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_normalize_dev(mfcc_hip_handle *h, void *d_rows, int row_width, const size_t *seg_offsets, size_t n_segs,
+                           int mode) {
+    if (!h || mode < MFCC_HIP_NORMALIZE_NONE || mode > MFCC_HIP_NORMALIZE_MEAN_VAR) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (row_width < 1 || row_width > mfcc_norm::kMaxWidth || (n_segs && !seg_offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    for (size_t k = 0; k < n_segs; ++k)
+        if (seg_offsets[k + 1] < seg_offsets[k]) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (n_segs && seg_offsets[n_segs] > seg_offsets[0] &&
+        (!d_rows || (reinterpret_cast<uintptr_t>(d_rows) & 3)))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0) return MFCC_HIP_SUCCESS;
+    DeviceGuard guard(h->device);
+    return normalize_segments(h, static_cast<float *>(d_rows), row_width, seg_offsets, n_segs, mode);
 }
 
 const char *mfcc_hip_kernel_name(const mfcc_hip_handle *h, int fixed) {
@@ -1375,6 +1541,7 @@ int mfcc_hip_convert_wav(mfcc_hip_handle *h, const char *wav_in, const char *mfc
                          size_t *n_frames_out) {
     if (!h || !wav_in || !mfcc_out) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
+    if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;     // ... raw ones
     std::vector<int16_t> pcm;
     int rc = read_wav_i16(wav_in, h->r.sample_rate, pcm);
     if (rc) return rc;
@@ -1416,6 +1583,7 @@ int mfcc_hip_convert_wavs(mfcc_hip_handle *h, const char *const *wav_in, const c
                           int fixed, size_t *n_frames_each) {
     if (!h || (n_files && (!wav_in || !mfcc_out))) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
+    if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;     // ... raw ones
     std::vector<int16_t> pcm;
     std::vector<size_t> off(n_files + 1, 0), fo(n_files + 1, 0);
     for (size_t i = 0; i < n_files; ++i) {
@@ -1521,6 +1689,7 @@ int mfcc_hip_stream_create(mfcc_hip_handle *h, int fixed, mfcc_hip_stream **out)
     if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
     *out = nullptr;
     if (h->destroy_pending) return MFCC_HIP_ERROR_INVALID_PARAM;        // the handle was already given back
+    if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // per-call statistics of a stream
     if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
     mfcc_hip_stream *s = new (std::nothrow) mfcc_hip_stream();
     if (!s) return MFCC_HIP_ERROR_NO_MEM;

@@ -14,6 +14,11 @@ all_gather / gather, which is RCCL over xGMI with the ``nccl`` backend on the GP
 in the CPU test-suite.  The compute itself is injected (``compute``): in production it is
 ``MFCC.process`` / ``MFCC.process_fixed`` (HIP); the CPU tests inject the oracle, so the N > 1
 logic is covered without a GPU.
+
+Per-utterance normalization (``MFCC(normalize=...)``) needs the statistics of a whole segment.  Item plans keep every
+utterance / channel on one rank, so a normalizing handle there gives the right rows as it is.  A frame-range shard is
+only part of a stream: the device path refuses ``halo=1`` on a normalizing handle.  Compute the shards raw, gather
+them, then normalize the whole stream once with ``MFCC.normalize_rows`` (``mfcc_hip_normalize_dev``).
 """
 from __future__ import annotations
 
