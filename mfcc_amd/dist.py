@@ -80,17 +80,32 @@ def plan_frames(n_samples: int, world: int, nfft: int = 512, hop: int = 170,
 
 
 def process_frames_sharded(compute: Callable, pcm: np.ndarray, rank: int, world: int, n_cep: int,
-                           nfft: int = 512, hop: int = 170, n_frames: Optional[int] = None):
+                           nfft: Optional[int] = None, hop: Optional[int] = None, n_frames: Optional[int] = None):
     """This rank's part of one stream: returns (shard, coefficients[shard.n_frames, n_cep]).
 
     ``compute(samples, halo, n_frames)`` must return ``n_frames`` rows for frames that start at
     ``samples[halo]``, treating ``samples[0]`` as history when ``halo == 1`` and zero-padding
-    past the end -- :func:`mfcc_compute` wraps a real :class:`mfcc_amd.MFCC` handle into that shape."""
+    past the end -- :func:`mfcc_compute` wraps a real :class:`mfcc_amd.MFCC` handle into that shape.
+
+    ``nfft`` / ``hop`` default to the geometry ``compute`` carries (its ``nfft`` / ``hop`` attributes, which
+    :func:`mfcc_compute` sets from the handle), else to 512 / 170; a value that disagrees with the one ``compute``
+    carries is a ``ValueError`` -- spans planned for another hop would give wrong rows without any other sign."""
+    nfft = _geometry(compute, "nfft", nfft, 512)
+    hop = _geometry(compute, "hop", hop, 170)
     shard = plan_frames(len(pcm), world, nfft, hop, n_frames)[rank]
     if shard.n_frames == 0:
         return shard, np.zeros((0, n_cep), dtype=np.float32)
     out = compute(pcm[shard.sample_lo:shard.sample_hi], shard.halo, shard.n_frames)
     return shard, np.asarray(out)
+
+
+def _geometry(compute: Callable, name: str, given: Optional[int], default: int) -> int:
+    own = getattr(compute, name, None)
+    if given is None:
+        return int(own) if own is not None else default
+    if own is not None and int(given) != int(own):
+        raise ValueError("%s=%d, but compute runs a handle with %s=%d" % (name, int(given), name, int(own)))
+    return int(given)
 
 
 def mfcc_compute(m, fixed: bool = False, device=None) -> Callable:
@@ -114,6 +129,7 @@ def mfcc_compute(m, fixed: bool = False, device=None) -> Callable:
         assert out.shape[0] >= n_frames, (out.shape, n_frames)
         return out[:n_frames].cpu().numpy()
 
+    compute.nfft, compute.hop = int(m.nfft), int(m.hop)        # process_frames_sharded plans its spans with these
     return compute
 
 

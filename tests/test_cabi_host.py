@@ -86,21 +86,63 @@ def test_lifter_is_folded_into_the_dct_rows():
     np.testing.assert_allclose(d, ref, rtol=0, atol=1e-6)
 
 
-@pytest.mark.parametrize("nfft,nmel", [(512, 32), (256, 16), (1024, 64)])
+# The RTL's parameter space (tests/test_gpu_fixed_generic.py runs the same grid on the GPU): every power-of-two nfft
+# the library takes, every n_mel whose (4 n_mel)-point DCT FFT fits, every rate the float tests use
+FX_NFFTS = (64, 128, 256, 512, 1024)
+FX_NMELS = (4, 8, 16, 32, 64)
+RATES = (8000, 11025, 16000, 22050, 32000, 44100, 48000)
+FX_PAIRS = [(nfft, nmel) for nfft in FX_NFFTS for nmel in FX_NMELS if 4 * nmel <= nfft]
+
+
+def _oracle_streams(nfft, nmel, sr):
+    """Whether the oracle's filterbank emits n_mel values per frame (it asserts otherwise)."""
+    try:
+        mx.mfcc_fixed_ref(np.zeros(nfft * 2, np.int16), nfft=nfft, nfilters=nmel, nceptrums=1, sample_rate=float(sr))
+        return True
+    except AssertionError:
+        return False
+
+
+@pytest.mark.parametrize("nfft,nmel", FX_PAIRS)
 def test_fixed_tables_match_oracle(nfft, nmel):
-    kw = dict(nfft=nfft, nfilters=nmel, nceptrums=nmel // 2)
-    assert np.array_equal(mfcc_amd.get_table(L.TABLE_FX_CURVE_I32, **kw), mx.window_curve(nfft))
-    re, im = mx.twiddle_rom(nfft)
-    tw = mfcc_amd.get_table(L.TABLE_FX_TWIDDLE_I32, **kw).reshape(-1, 2)
-    assert np.array_equal(tw[:, 0], re) and np.array_equal(tw[:, 1], im)
-    # the closed-form filterbank weights reproduce the RTL's streaming accumulators bit for bit
-    fm = mfcc_amd.get_table(L.TABLE_FX_MEL_DENSE_U32, **kw)
-    shift, W = int(fm[0]), fm[1:].reshape(nmel, nfft // 2).astype(np.uint64)
-    P = np.random.default_rng(nfft).integers(0, 1 << 29, size=(40, nfft // 2)).astype(np.uint64)
-    with np.errstate(over="ignore"):
-        acc = (P[:, None, :] * W[None]).sum(-1)
-    got = ((acc >> np.uint64(shift)) & np.uint64(0xFFFF)).astype(np.int64)
-    assert np.array_equal(got, mx.filterbank(P.astype(np.int64), nfft, nmel))
+    """At every rate where the oracle streams: the closed-form filterbank weights reproduce the RTL's streaming
+    accumulators bit for bit; where it asserts, the table is UNSUPPORTED.  The window curve and twiddle ROM depend on
+    nfft only and are checked at every rate all the same (the builder must not read the rate)."""
+    ran = 0
+    for sr in RATES:
+        kw = dict(nfft=nfft, nfilters=nmel, nceptrums=max(1, nmel // 2), samplerate=sr)
+        assert np.array_equal(mfcc_amd.get_table(L.TABLE_FX_CURVE_I32, **kw), mx.window_curve(nfft))
+        re, im = mx.twiddle_rom(nfft)
+        tw = mfcc_amd.get_table(L.TABLE_FX_TWIDDLE_I32, **kw).reshape(-1, 2)
+        assert np.array_equal(tw[:, 0], re) and np.array_equal(tw[:, 1], im)
+        if not _oracle_streams(nfft, nmel, sr):
+            with pytest.raises(mfcc_amd.MfccHipError) as e:
+                mfcc_amd.get_table(L.TABLE_FX_MEL_DENSE_U32, **kw)
+            assert e.value.code == L.ERROR_UNSUPPORTED, sr
+            continue
+        fm = mfcc_amd.get_table(L.TABLE_FX_MEL_DENSE_U32, **kw)
+        shift, W = int(fm[0]), fm[1:].reshape(nmel, nfft // 2).astype(np.uint64)
+        P = np.random.default_rng(nfft + sr).integers(0, 1 << 30, size=(40, nfft // 2)).astype(np.uint64)
+        P[0] = (1 << 30) - 1                                  # a full-scale frame: every register bit the RTL keeps
+        with np.errstate(over="ignore"):
+            acc = (P[:, None, :] * W[None]).sum(-1)
+        got = ((acc >> np.uint64(shift)) & np.uint64(0xFFFF)).astype(np.int64)
+        assert np.array_equal(got, mx.filterbank(P.astype(np.int64), nfft, nmel, float(sr))), sr
+        ran += 1
+    assert ran or nfft == 4 * nmel           # a DCT as long as the FFT: too dense at every rate
+
+
+@pytest.mark.parametrize("nmel", [8, 16, 20, 32, 40, 64])
+@pytest.mark.parametrize("nfft", [64, 128, 256, 512, 1024])
+def test_float_mel_tables_match_oracle_at_every_rate(nfft, nmel):
+    """The float filter points and dense filterbank at every rate (the notebook's cells 24-31 with fmax = rate / 2)."""
+    for sr in RATES:
+        kw = dict(nfft=nfft, nfilters=nmel, nceptrums=1, samplerate=sr)
+        pts = mfcc_amd.get_table(L.TABLE_MEL_POINTS_I32, **kw)
+        ref_pts, _ = mf.get_filter_points(0, sr / 2, nmel, nfft, sample_rate=sr)
+        assert np.array_equal(pts, ref_pts), sr
+        md = mfcc_amd.get_table(L.TABLE_MEL_DENSE_F32, **kw).reshape(nmel, nfft // 2 + 1)
+        np.testing.assert_allclose(md, mf.mel_filterbank(nfft, nmel, sr), rtol=0, atol=6e-8, err_msg=str(sr))
 
 
 def test_fixed_table_unsupported_parameters():
@@ -224,19 +266,27 @@ def test_stream_entry_points_check_their_arguments_without_a_gpu():
 
 def test_fixed_support_follows_the_rtl_filterbank():
     """The fixed path exists where the RTL's streaming filterbank emits n_mel values per frame (the oracle asserts
-    on exactly the other sets)."""
+    on exactly the other sets) -- at every point of the grid, so also where that depends on the rate: (256, 32) streams
+    only up to 22.05 kHz, (512, 64) only at 8 and 11.025 kHz."""
     from mfcc_amd import _lib
+    checked = {}
+    for nfft, nmel in FX_PAIRS:
+        for sr in RATES:
+            try:
+                mfcc_amd.get_table(_lib.TABLE_FX_MEL_DENSE_U32, nfft=nfft, nfilters=nmel, nceptrums=4 if nmel >= 4 else 1,
+                                   samplerate=sr)
+                got = True
+            except mfcc_amd.MfccHipError as e:
+                assert e.code == -105
+                got = False
+            ok = _oracle_streams(nfft, nmel, sr)
+            assert got == ok, (nfft, nmel, sr)
+            checked[(nfft, nmel, sr)] = ok
+    assert len(checked) == 22 * 7
+    # the points the issue of rate dependence is about, spelled out
+    assert [checked[(256, 32, r)] for r in RATES] == [True, True, True, True, False, False, False]
+    assert [checked[(512, 64, r)] for r in RATES] == [True, True, False, False, False, False, False]
+    assert all(checked[(nfft, 4, r)] for nfft in FX_NFFTS for r in RATES)
     for nfft, nmel, ok in ((512, 32, True), (256, 16, True), (1024, 64, True), (128, 16, True), (64, 8, True),
                            (256, 64, False), (512, 64, False), (128, 32, False), (64, 16, False)):
-        try:
-            mfcc_amd.get_table(_lib.TABLE_FX_MEL_DENSE_U32, nfft=nfft, nfilters=nmel, nceptrums=4)
-            got = True
-        except mfcc_amd.MfccHipError as e:
-            assert e.code == -105
-            got = False
-        assert got == ok, (nfft, nmel)
-        if ok:
-            mx.mfcc_fixed_ref(np.zeros(nfft * 2, np.int16), nfft=nfft, nfilters=nmel, nceptrums=4)
-        else:
-            with pytest.raises(AssertionError):
-                mx.mfcc_fixed_ref(np.zeros(nfft * 2, np.int16), nfft=nfft, nfilters=nmel, nceptrums=4)
+        assert checked[(nfft, nmel, 16000)] == ok, (nfft, nmel)

@@ -155,3 +155,47 @@ def test_plans():
     assert sh[0].sample_hi - sh[1].sample_lo == 343
     tiny = md.plan_frames(600, 4)
     assert [s.n_frames for s in tiny] == [1, 0, 0, 0]
+
+
+class _StubHandle:
+    """Stands in for an ``MFCC`` handle in ``mfcc_compute`` (no GPU): 1024 / 341 geometry, notebook framing; row k is
+    (history sample, first sample, last sample) of frame k, so a span planned for another hop gives other rows."""
+    nfft, hop = 1024, 341
+
+    def num_frames(self, n):
+        return 0 if n < self.nfft else (n - self.nfft) // self.hop + 1
+
+    def process(self, x, halo=0):
+        x = x.to(torch.int64)
+        hist = int(x[0]) if halo else 0
+        x = x[halo:]
+        rows = [[hist if k == 0 else int(x[k * self.hop - 1]), int(x[k * self.hop]), int(x[k * self.hop + self.nfft - 1])]
+                for k in range(self.num_frames(x.numel()))]
+        return torch.tensor(rows, dtype=torch.int64).reshape(-1, 3)
+
+    process_fixed = process
+
+
+def test_frame_sharding_takes_the_geometry_of_the_handle():
+    """`process_frames_sharded` plans with the nfft / hop that `mfcc_compute` attaches from the handle: a 1024 / 341
+    handle sharded without explicit arguments gives the unsharded rows; an explicit value that disagrees is refused; a
+    plain callable keeps the 512 / 170 defaults."""
+    m = _StubHandle()
+    compute = md.mfcc_compute(m, device="cpu")
+    assert (compute.nfft, compute.hop) == (1024, 341)
+    pcm = np.random.default_rng(3).integers(-32768, 32768, 341 * 60 + 1024 + 100).astype(np.int16)
+    whole = m.process(torch.from_numpy(pcm)).numpy()
+    assert whole.shape == (61, 3)
+    for world in (2, 3, 8):
+        for kw in ({}, dict(nfft=1024), dict(hop=341), dict(nfft=1024, hop=341)):
+            parts = [md.process_frames_sharded(compute, pcm, r, world, 3, **kw)[1] for r in range(world)]
+            assert np.array_equal(np.concatenate(parts), whole), (world, kw)
+    for kw in (dict(nfft=512), dict(hop=170), dict(nfft=512, hop=170)):
+        with pytest.raises(ValueError):
+            md.process_frames_sharded(compute, pcm, 1, 2, 3, **kw)
+    # a plain callable carries no geometry: 512 / 170, as before
+    seen = []
+    md.process_frames_sharded(lambda s, h, n: seen.append((len(s), h, n)) or np.zeros((n, 3)), pcm, 1, 2, 3)
+    shard = md.plan_frames(len(pcm), 2)[1]
+    assert seen == [(shard.sample_hi - shard.sample_lo, 1, shard.n_frames)]
+    assert shard.sample_lo == 170 * shard.frame_lo - 1
