@@ -97,8 +97,10 @@ enum mfcc_hip_normalize {
  */
 typedef struct mfcc_hip_params {
     uint32_t struct_size;  /* = sizeof(mfcc_hip_params); set by mfcc_hip_default_params   */
-    int32_t  nfft;         /* 512.  float: 256/512/1024; fixed: power of two 64..1024     */
-    int32_t  hop;          /* 170.  0 -> nfft / 3 (mfcc/core/mfcc.py:43)                  */
+    int32_t  nfft;         /* 512.  float and fixed: power of two 64..1024                */
+    int32_t  hop;          /* 170.  1..nfft; 0 -> nfft / 3 (mfcc/core/mfcc.py:43).  At any
+                              other hop than nfft / 3 the float path runs the generic kernel
+                              and the fixed path refuses (MFCC_HIP_ERROR_UNSUPPORTED)     */
     int32_t  n_mel;        /* 32.   float: 1..64; fixed: 4*n_mel must be a power of two   */
     int32_t  n_cep;        /* 13.   1..n_mel; `Discard(first=0, count)` misc/discard.py   */
     int32_t  sample_rate;  /* 16000                                                       */

@@ -28,14 +28,15 @@ class Family:
     samplerate: int = 16000
     extra: dict = field(default_factory=dict)      # further MFCC() arguments (power_scale)
     why: str = ""
+    hop: int = 0                                   # 0: nfft // 3, the library's default
 
-    @property
-    def hop(self) -> int:
-        return self.nfft // 3
+    def __post_init__(self):
+        if not self.hop:
+            object.__setattr__(self, "hop", self.nfft // 3)
 
     def kwargs(self, pad_mode="notebook", **over):
-        kw = dict(nfft=self.nfft, nfilters=self.nfilters, nceptrums=self.nceptrums, samplerate=self.samplerate,
-                  pad_mode=pad_mode, **self.extra)
+        kw = dict(nfft=self.nfft, hop=self.hop, nfilters=self.nfilters, nceptrums=self.nceptrums,
+                  samplerate=self.samplerate, pad_mode=pad_mode, **self.extra)
         kw.update(over)
         return kw
 
@@ -57,6 +58,18 @@ FLOAT = [
     Family("g256", False, "mfcc_float_generic_kernel", 256, 20, 13, extra=dict(power_scale=0),
            why="n_mel not a power of two"),
     Family("g1024_64", False, "mfcc_float_generic_kernel", 1024, 64, 32, extra=dict(power_scale=0)),
+    # other hops: every one runs on the generic kernel, whatever its shape (the fused kernels hard-code theirs)
+    Family("f512_h160", False, "mfcc_float_generic_kernel", 512, 32, 13, hop=160,
+           why="10 ms at 16 kHz; the fused 512 kernel's shape"),
+    Family("f512_h171", False, "mfcc_float_generic_kernel", 512, 32, 13, hop=171, why="one off the fused hop"),
+    Family("f1024_h256", False, "mfcc_float_generic_kernel", 1024, 40, 13, extra=dict(power_scale=0), hop=256,
+           why="75 % overlap; the fused 1024 kernel's shape"),
+    Family("g512_h257", False, "mfcc_float_generic_kernel", 512, 32, 32, 48000, hop=257,
+           why="hop above nfft / 2; the exact-DC branch"),
+    Family("g256_h256", False, "mfcc_float_generic_kernel", 256, 20, 13, extra=dict(power_scale=0), hop=256,
+           why="hop = nfft: frames share only the pre-emphasis history"),
+    Family("g128_h1", False, "mfcc_float_generic_kernel", 128, 16, 13, extra=dict(power_scale=0), hop=1,
+           why="every sample starts a frame"),
 ]
 FIXED = [
     Family("x512", True, "mfcc_fixed512_kernel", 512, 32, 13, why="the control"),

@@ -49,6 +49,26 @@ def test_frame_counts_match_reference_conventions():
     assert mfcc_amd.num_frames(57_600_000, nfft=1024, nfilters=40) == 168912       # config 4, hop 341
 
 
+@pytest.mark.parametrize("nfft", [64, 256, 512, 1024])
+def test_frame_counts_at_every_hop_of_the_grid(nfft):
+    """Both framings count frames from the hop; hop 0 is nfft // 3, 1 and nfft are valid, nfft + 1 and -1 are not."""
+    t = nfft // 3
+    for h in sorted({1, 2, 3, nfft // 4, t - 1, t, t + 1, nfft // 2, nfft - 1, nfft}):
+        for n in (0, 1, nfft - 1, nfft, nfft + 1, nfft + h - 1, nfft + h, nfft + 7 * h + 3):
+            assert mfcc_amd.num_frames(n, nfft=nfft, hop=h) == mf.num_frames_notebook(n, nfft, h), (nfft, h, n)
+            assert mfcc_amd.num_frames(n, nfft=nfft, hop=h, pad_mode="stream") == mf.num_frames_stream(n, nfft, h), \
+                (nfft, h, n)
+    n = nfft + 7 * t + 3
+    assert mfcc_amd.num_frames(n, nfft=nfft, hop=0) == mfcc_amd.num_frames(n, nfft=nfft) == \
+        mf.num_frames_notebook(n, nfft, t)
+    lib = L.load()
+    out = C.c_size_t(0)
+    for h, rc in ((0, L.SUCCESS), (1, L.SUCCESS), (nfft, L.SUCCESS), (nfft + 1, L.ERROR_INVALID_PARAM),
+                  (-1, L.ERROR_INVALID_PARAM)):
+        p = mfcc_amd.make_params(nfft=nfft, nfilters=8, nceptrums=8, hop=h)
+        assert lib.mfcc_hip_num_frames(C.byref(p), 5000, C.byref(out)) == rc, (nfft, h)
+
+
 def test_invalid_parameters_are_rejected():
     lib = L.load()
     out = C.c_size_t(0)

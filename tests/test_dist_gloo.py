@@ -24,18 +24,28 @@ def _free_port():
     return p
 
 
-def _float_compute(samples, halo, n_frames):
+def _float_compute(samples, halo, n_frames, nfft=512, hop=170):
     """Oracle stand-in for MFCC.process(..., halo): samples[0] is history when halo == 1."""
     x = np.asarray(samples).astype(np.float64)
+    need = halo + (n_frames - 1) * hop + nfft
+    if len(x) < need:                              # zeros past the end, before pre-emphasis (as the kernels read them)
+        x = np.concatenate([x, np.zeros(need - len(x))])
     y = mf.pre_emphasis(x)                         # y[j] uses x[j-1]; y[0] is wrong only if halo == 0 is false
-    need = halo + (n_frames - 1) * 170 + 512
-    if len(y) < need:
-        y = np.concatenate([y, np.zeros(need - len(y))])
-    fr = np.stack([y[halo + 170 * k: halo + 170 * k + 512] for k in range(n_frames)])
-    win = fr * mf.hamming_window(512)
+    fr = np.stack([y[halo + hop * k: halo + hop * k + nfft] for k in range(n_frames)])
+    win = fr * mf.hamming_window(nfft)
     p = np.abs(np.fft.rfft(win, axis=1) / 512.0) ** 2
-    mel = p @ mf.mel_filterbank().T
+    mel = p @ mf.mel_filterbank(nfft).T
     return (np.log2(mel) @ mf.dct_basis(32, 32).T)[:, :13]
+
+
+class _FloatComputeAt:
+    """``_float_compute`` at another hop, carrying ``.nfft`` / ``.hop`` the way ``md.mfcc_compute`` does."""
+
+    def __init__(self, hop, nfft=512):
+        self.nfft, self.hop = nfft, hop
+
+    def __call__(self, samples, halo, n_frames):
+        return _float_compute(samples, halo, n_frames, self.nfft, self.hop)
 
 
 def _fixed_compute(samples, halo, n_frames):
@@ -114,6 +124,26 @@ def test_frame_sharding_with_halo_float():
         assert full.shape == ref.shape
         np.testing.assert_allclose(full, ref, rtol=0, atol=1e-9)
     assert res[0][2] == (0, 51, 0) and res[1][2] == (51, 102, 1)
+
+
+@pytest.mark.parametrize("pad", ["notebook", "stream"])
+@pytest.mark.parametrize("hop", [1, 160, 512])
+def test_frame_sharding_with_halo_at_other_hops(hop, pad):
+    """The frame plans of 2-, 3- and 8-way shards at hops 1, 160 and nfft, planned from the geometry that ``compute``
+    carries, concatenate to the whole-stream oracle rows (both frame counts: STREAM's padded tail frame on the last
+    rank)."""
+    compute = _FloatComputeAt(hop)
+    pcm = mf.synth_pcm(512 + hop * (900 // hop + 40) + hop // 2 + 1, seed=hop)
+    ref = mf.mfcc_float_ref(pcm, pad_mode=pad, nfft=512, hop=hop)
+    nf = len(ref)
+    assert nf == (mf.num_frames_stream if pad == "stream" else mf.num_frames_notebook)(len(pcm), 512, hop)
+    for world in (2, 3, 8):
+        parts = []
+        for rank in range(world):
+            shard, loc = md.process_frames_sharded(compute, pcm, rank, world, 13, n_frames=nf)
+            assert shard.halo == int(shard.frame_lo > 0) and shard.sample_lo == hop * shard.frame_lo - shard.halo
+            parts.append(loc)
+        np.testing.assert_allclose(np.concatenate(parts), ref, rtol=0, atol=1e-9, err_msg="%d-way" % world)
 
 
 def test_frame_sharding_fixed_stream_padding_is_bit_exact():

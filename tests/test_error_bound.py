@@ -111,7 +111,10 @@ KINDS = ["wav", "noise3000", "noise30", "uniform", "square", "sine", "dc_dither"
 SHAPES = {"512/16k": dict(nfft=512, hop=170, n_mel=32, sample_rate=16000, power_scale=512.0),
           "512/44.1k": dict(nfft=512, hop=170, n_mel=32, sample_rate=44100, power_scale=512.0),
           "512/48k": dict(nfft=512, hop=170, n_mel=32, sample_rate=48000, power_scale=512.0),
-          "1024/40": dict(nfft=1024, hop=341, n_mel=40, sample_rate=16000, power_scale=1024.0)}
+          "1024/40": dict(nfft=1024, hop=341, n_mel=40, sample_rate=16000, power_scale=1024.0),
+          # other hops: the generic kernel's (fp32 / fp32) shapes
+          "256/20 hop 1": dict(nfft=256, hop=1, n_mel=20, sample_rate=16000, power_scale=256.0),
+          "512/32 hop 160": dict(nfft=512, hop=160, n_mel=32, sample_rate=16000, power_scale=512.0)}
 
 
 def _pcm(kind, kw, wav_pcm):
@@ -180,6 +183,26 @@ def test_lifter_and_halo_and_stream_framing(wav_pcm):
     rs, bs = eb.reference_and_bound(np.stack([pcm, pcm[::-1].copy()]), "fp32/fp32", n_cep=13, pad_mode="stream")
     assert rs.shape == bs.shape == (2, mf.num_frames_stream(len(pcm)), 13)
     np.testing.assert_array_equal(rs[1], mf.mfcc_float_ref(pcm[::-1].copy(), pad_mode="stream"))
+
+
+@pytest.mark.parametrize("hop", [1, 2, 160, 511, 512])
+def test_halo_and_stream_framing_at_other_hops(wav_pcm, hop):
+    """halo=1 puts sample 0 hop - 1 zeros into a longer stream (none at hop 1) and drops that stream's frame 0; STREAM
+    framing zero-pads to the end of its last frame: both against the oracle run directly on that stream."""
+    kw = dict(nfft=512, hop=hop, n_mel=32, sample_rate=16000, power_scale=512.0)
+    pcm = wav_pcm[5000:5000 + 512 + hop * (1500 // hop + 3) + hop // 2 + 1]
+    n = len(pcm)
+    r1, b1 = eb.reference_and_bound(pcm, "fp32/fp32", n_cep=13, halo=1, **kw)
+    assert r1.shape == b1.shape == (mf.num_frames_notebook(n - 1, 512, hop), 13)
+    longer = np.concatenate([np.zeros(hop - 1, np.int16), pcm])
+    np.testing.assert_array_equal(r1, mf.mfcc_notebook(longer, **kw)[1:, :13])
+    rs, bs = eb.reference_and_bound(pcm, "fp32/fp32", n_cep=13, pad_mode="stream", **kw)
+    nf = mf.num_frames_stream(n, 512, hop)
+    assert rs.shape == bs.shape == (nf, 13) and (nf - 1) * hop + 512 >= n
+    padded = np.concatenate([pcm, np.zeros((nf - 1) * hop + 512 - n, np.int16)])
+    np.testing.assert_array_equal(rs, mf.mfcc_notebook(padded, **kw)[:, :13])
+    np.testing.assert_array_equal(rs, mf.mfcc_float_ref(pcm, pad_mode="stream", **kw))
+    eb.check(emulate(padded, "fp32/fp32", n_cep=13, **kw), rs, bs)
 
 
 # ----------------------------------------------------------------------------- sharpness

@@ -157,7 +157,7 @@ def _pushes(n, kind, fam, rng):
         if kind == "driver":                                  # the host driver's pattern: nfft, then hop per round
             c = fam.nfft if pos == 0 else fam.hop
         elif kind == "hop-1":
-            c = fam.hop - 1
+            c = max(1, fam.hop - 1)                           # hop 1: one sample per push, not none
         elif kind == "hop+1":
             c = fam.hop + 1
         elif kind == "random":

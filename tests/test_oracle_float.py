@@ -115,3 +115,28 @@ def test_synth_is_deterministic():
     a = mf.synth_pcm(4096, seed=3)
     b = mf.synth_pcm(4096, seed=3)
     assert a.dtype == np.int16 and np.array_equal(a, b) and a.std() > 2500
+
+
+@pytest.mark.parametrize("nfft,n_mel,rate", [(64, 8, 16000), (256, 20, 16000), (512, 32, 48000), (1024, 40, 16000)])
+def test_a_frame_does_not_depend_on_the_hop(wav_pcm, nfft, n_mel, rate):
+    """Frame f at hop h is the frame at sample f h: the framed, windowed and power stages of hop h are those of hop 1
+    at every h-th sample, exactly.  The mel and DCT stages are matrix products whose summation order BLAS may choose
+    by the number of frames, so the log-mel values and the cepstra are held to 1e-12 relative, their -inf / NaN
+    pattern (a silent stretch) exactly.  Hops: the grid of the GPU tests."""
+    n = nfft + 1500
+    x = np.resize(wav_pcm[3000:], n).astype(np.int16)
+    x[700:700 + nfft + 40] = 0
+    kw = dict(nfft=nfft, n_mel=n_mel, sample_rate=rate, power_scale=float(nfft))
+    r1, s1 = mf.mfcc_notebook(x, hop=1, return_stages=True, **kw)
+    assert r1.shape == (n - nfft + 1, n_mel) and np.isneginf(r1[:, 0]).any()
+    t = nfft // 3
+    for h in sorted({1, 2, 3, nfft // 4, t - 1, t, t + 1, nfft // 2, nfft - 1, nfft}):
+        rh, sh = mf.mfcc_notebook(x, hop=h, return_stages=True, **kw)
+        assert len(rh) == mf.num_frames_notebook(n, nfft, h)
+        at = np.arange(len(rh)) * h
+        for stage in ("framed", "windowed", "power"):
+            np.testing.assert_array_equal(np.asarray(sh[stage]), np.asarray(s1[stage])[at],
+                                          err_msg="%s, hop %d" % (stage, h))
+        for a, b, what in ((sh["logmel"], s1["logmel"][at], "logmel"), (rh, r1[at], "cepstra")):
+            np.testing.assert_array_equal(np.isfinite(a), np.isfinite(b), err_msg="%s, hop %d" % (what, h))
+            np.testing.assert_allclose(a, b, rtol=1e-12, atol=1e-12, err_msg="%s, hop %d" % (what, h))
