@@ -246,6 +246,38 @@ int  mfcc_hip_set_normalize(mfcc_hip_handle *h, int mode);
 int  mfcc_hip_normalize_dev(mfcc_hip_handle *h, void *d_rows, int row_width, const size_t *seg_offsets, size_t n_segs,
                             int mode);
 
+/* ---- delta and delta-delta coefficients -------------------------------------------------
+ * With delta order K (1 or 2) and window N (1..MFCC_HIP_MAX_DELTA_WINDOW), the float row of frame t of a segment (one
+ * channel of a dense call, one utterance of a ragged one) becomes W * (1 + K) wide, W = n_cep or n_mel:
+ *     [ s_t (W) | D_t (W) | DD_t (W, order 2 only) ]
+ * s_t is the static row the handle returns with deltas off (lifter, log-mel and normalization as set), bit for bit.
+ *     D_t = r * sum_{n=1..N} n (s_{t+n} - s_{t-n}),  r = 1 / (2 sum_{n=1..N} n^2)
+ * with indices clamped to the segment (s before its first row = its first row, after its last = its last: HTK's rule);
+ * DD_t is the same formula on the D rows, clamped the same way.  In fp32, for every element: acc = 0; for n = 1..N
+ * ascending: acc = fmaf((float)n, a_n - b_n, acc); then D = acc * (float)r, nothing else contracted -- every entry
+ * point and every cut of the rows gives the same bits.  A non-finite static value (a silent band) makes every D
+ * element that reads it non-finite, and DD follows from D the same way.  A segment of one row gives D = DD = 0 where
+ * its statics are finite.
+ *
+ * The handle's order applies to every float call enqueued after it, as normalization does: mfcc_hip_process_i16,
+ * mfcc_hip_process_i16_dev, both float mfcc_hip_process_ragged_* entry points and mfcc_hip_time_dev (which then times
+ * the delta pass too).  Output capacities, BUFFER_SMALL and frame_offsets count rows of W * (1 + K).  With an order
+ * other than 0 the fixed-point entry points, mfcc_hip_stream_create (a session would need 2 K N frames of lookahead),
+ * mfcc_hip_convert_wav(s) (a .mfcc row is n_cep wide) and mfcc_hip_process_i16_dev with halo = 1 (a shard's edges
+ * are not the stream's) return MFCC_HIP_ERROR_UNSUPPORTED.  NULL handle or a bad order / window:
+ * MFCC_HIP_ERROR_INVALID_PARAM; a handle with live streaming sessions: MFCC_HIP_ERROR_BUSY.                      */
+#define MFCC_HIP_MAX_DELTA_WINDOW 8
+/* order 0 (off, the state after create), 1 (D) or 2 (D, DD); window 1..MFCC_HIP_MAX_DELTA_WINDOW */
+int  mfcc_hip_set_deltas(mfcc_hip_handle *h, int order, int window);
+/* The kernel's direct entry: d_in rows [seg_offsets[n_segs]][width] (rows before seg_offsets[0] not read), d_out rows
+ * [..][width * (1 + order)] at the same row indices; rows of d_out outside the segments untouched.  Segment k = rows
+ * seg_offsets[k] .. seg_offsets[k + 1] (host array, n_segs + 1 entries, must not decrease).  width 1..64, order 1..2,
+ * window 1..MFCC_HIP_MAX_DELTA_WINDOW, both pointers 4-byte aligned, the two byte ranges must not overlap.
+ * Asynchronous on the handle's stream; n_segs = 0 is a no-op.  E.g. the gathered rows of a frame-range-sharded
+ * stream, after mfcc_hip_normalize_dev.                                                                        */
+int  mfcc_hip_deltas_dev(mfcc_hip_handle *h, const void *d_in, int width, void *d_out,
+                         const size_t *seg_offsets, size_t n_segs, int order, int window);
+
 /* name of the kernel symbol process_*_dev launches for this handle (to match rocprofv3 rows).  A log-mel handle runs
  * the log-mel instantiation of the kernel named (the default form: MFCC_HIP_FUSED512 / MFCC_HIP_FUSED1024 do not
  * apply to it) */

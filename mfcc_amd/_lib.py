@@ -39,6 +39,8 @@ NORMALIZE_NONE = 0
 NORMALIZE_MEAN = 1
 NORMALIZE_MEAN_VAR = 2
 
+MAX_DELTA_WINDOW = 8
+
 TABLE_WINDOW_F32 = 0
 TABLE_MEL_POINTS_I32 = 1
 TABLE_MEL_DENSE_F32 = 2
@@ -107,6 +109,8 @@ SYMBOLS = {
     "mfcc_hip_kernel_name": (C.c_char_p, [_H, C.c_int]),
     "mfcc_hip_set_normalize": (C.c_int, [_H, C.c_int]),
     "mfcc_hip_normalize_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, _SZ, C.c_int]),
+    "mfcc_hip_set_deltas": (C.c_int, [_H, C.c_int, C.c_int]),
+    "mfcc_hip_deltas_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _SZ, C.c_int, C.c_int]),
     "mfcc_hip_convert_wav": (C.c_int, [_H, C.c_char_p, C.c_char_p, C.c_int, _PSZ]),
     "mfcc_hip_stream_create": (C.c_int, [_H, C.c_int, C.POINTER(_H)]),
     "mfcc_hip_stream_destroy": (None, [_H]),

@@ -40,6 +40,16 @@ def normalize_mode(mode) -> int:
         raise ValueError("normalize must be None, 'mean' or 'meanvar', not %r" % (mode,)) from None
 
 
+def _delta_args(order, window, orders=(0, 1, 2)):
+    """(order, window) as ints, or ValueError: order in ``orders``, window 1..8 (MFCC_HIP_MAX_DELTA_WINDOW)."""
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or int(order) not in orders:
+        raise ValueError("deltas must be one of %s, not %r" % (orders, order))
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or \
+            not 1 <= int(window) <= _lib.MAX_DELTA_WINDOW:
+        raise ValueError("delta_window must be 1..%d, not %r" % (_lib.MAX_DELTA_WINDOW, window))
+    return int(order), int(window)
+
+
 def make_params(nfft=512, hop=None, nfilters=32, nceptrums=13, samplerate=16000, pad_mode="notebook",
                 power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra") -> Params:
     """``output``: ``"cepstra"`` (rows of ``nceptrums`` DCT-II coefficients) or ``"logmel"`` (rows of ``nfilters``
@@ -109,14 +119,22 @@ class MFCC:
     frames, column by column (CMVN: ``sklearn.preprocessing.scale`` of the reference's ``software/genlibrosa.py``;
     -inf / NaN of silent frames are left out and left as they are) -- ``process``, ``process_batch`` and
     ``process_packed``.  ``process_fixed``, :meth:`stream`, ``convert*`` and ``halo=1`` then raise ``UNSUPPORTED``.
+
+    ``deltas=1`` / ``2`` appends the first (and second) time derivatives to every float row, ``[s | D | DD]``, over
+    ``delta_window`` frames on each side (1..8, default 2; HTK's regression formula, indices clamped to the channel /
+    utterance).  The static part is what the handle returns with deltas off, normalization included, and
+    :attr:`num_features` counts the expanded width.  The same entry points as normalization refuse such a handle.
     """
+
+    deltas, delta_window = 0, 2                 # the state after mfcc_hip_create
 
     def __init__(self, width=16, nfft=512, samplerate=16e3, nfilters=16, nceptrums=16, *, hop=None,
                  pad_mode="notebook", power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra",
-                 normalize=None):
+                 normalize=None, deltas=0, delta_window=2):
         if width != 16:
             raise ValueError("only width=16 (int16 PCM) is supported, like every reference target")
         norm = normalize_mode(normalize)
+        order, window = _delta_args(deltas, delta_window)
         self.width = width
         self.nfft = int(nfft)
         self.samplerate = samplerate
@@ -143,6 +161,48 @@ class MFCC:
         self.normalize = None
         if norm != _lib.NORMALIZE_NONE:
             self.set_normalize(normalize)
+        self.deltas, self.delta_window = 0, window
+        if order:
+            self.set_deltas(order, window)
+
+    def set_deltas(self, order, window=2):
+        """The handle's delta order (0 = off, 1 = D, 2 = D and DD) and window for every float call after this one."""
+        order, window = _delta_args(order, window)
+        _lib.check(self._lib.mfcc_hip_set_deltas(self._h, order, window), "set_deltas")
+        self.deltas, self.delta_window = order, window
+
+    def deltas_rows(self, rows, frame_offsets=None, order=2, window=2, out=None):
+        """Delta coefficients of a CUDA float32 tensor of static rows, on the current torch stream: returns ``out``,
+        the rows expanded to ``width * (1 + order)`` ([s | D | DD]).  ``rows`` and the segments as in
+        :meth:`normalize_rows`; ``width`` 1..64, independent of this handle's own rows.  Rows of ``out`` outside the
+        segments are left as they are."""
+        import torch
+        order, window = _delta_args(order, window, orders=(1, 2))
+        if rows.dtype != torch.float32 or not rows.is_cuda or not rows.is_contiguous() or rows.dim() not in (2, 3):
+            raise TypeError("rows must be a contiguous 2-D or 3-D CUDA(HIP) float32 tensor")
+        width = int(rows.shape[-1])
+        if frame_offsets is None:
+            nseg = int(rows.shape[0]) if rows.dim() == 3 else 1
+            per = int(rows.shape[1]) if rows.dim() == 3 else int(rows.shape[0])
+            fo = np.arange(nseg + 1, dtype=np.uint64) * np.uint64(per)
+        else:
+            fo = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
+            if fo.ndim != 1 or len(fo) < 1:
+                raise ValueError("frame_offsets must be 1-D with n_segments + 1 entries")
+            if len(fo) > 1 and int(fo[-1]) * width > rows.numel():
+                raise ValueError("frame_offsets run past the end of rows")
+        want = tuple(rows.shape[:-1]) + (width * (1 + order),)
+        if out is None:
+            out = torch.empty(want, device=rows.device, dtype=torch.float32)
+        elif tuple(out.shape) != want or out.dtype != torch.float32 or not out.is_contiguous() or \
+                out.device != rows.device:
+            raise ValueError("out must be a contiguous float32 tensor of shape %s on %s" % (want, rows.device))
+        self._check_device(rows)
+        with self._on_torch_stream(rows.device):
+            _lib.check(self._lib.mfcc_hip_deltas_dev(self._h, C.c_void_p(rows.data_ptr()), width,
+                                                     C.c_void_p(out.data_ptr()), fo.ctypes.data_as(C.c_void_p),
+                                                     len(fo) - 1, order, window), "deltas_dev")
+        return out
 
     def set_normalize(self, mode):
         """The handle's normalization for every float call after this one (None, ``"mean"``, ``"meanvar"``)."""
@@ -195,8 +255,9 @@ class MFCC:
 
     @property
     def num_features(self) -> int:
-        """Width of an output row of the float path: ``nfilters`` for ``output="logmel"``, else ``nceptrums``."""
-        return self.nfilters if self.output == "logmel" else self.nceptrums
+        """Width of an output row of the float path: ``nfilters`` for ``output="logmel"``, else ``nceptrums``; times
+        ``1 + deltas``."""
+        return (self.nfilters if self.output == "logmel" else self.nceptrums) * (1 + self.deltas)
 
     def _row(self, fixed):
         return self.nceptrums if fixed else self.num_features

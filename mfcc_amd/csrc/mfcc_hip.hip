@@ -24,6 +24,7 @@
 #include "kernel_fused512.hpp"
 #include "kernel_fused512_w12.hpp"
 #include "kernel_normalize.hpp"
+#include "kernel_deltas.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -177,6 +178,14 @@ struct mfcc_hip_handle {
     size_t d_norm_bytes = 0;
     void *d_full = nullptr;
     size_t d_full_bytes = 0;
+    // delta coefficients (mfcc_hip_set_deltas): order 0 (off), 1 or 2 and the window; the static rows the delta pass
+    // reads (d_stat) and its tile table (d_dtab)
+    int delta_order = 0;
+    int delta_window = 2;
+    void *d_stat = nullptr;
+    size_t d_stat_bytes = 0;
+    void *d_dtab = nullptr;
+    size_t d_dtab_bytes = 0;
 };
 
 namespace {
@@ -624,10 +633,107 @@ int normalize_segments(mfcc_hip_handle *h, float *d_rows, int width, const size_
     return MFCC_HIP_SUCCESS;
 }
 
+// ---- delta coefficients (kernel_deltas.hpp): a handle with a delta order runs its kernels and
+// its normalization into h->d_stat, then this pass writes the expanded rows to the caller's buffer.  The tile table of
+// a ragged call goes to h->d_dtab ([first tile of every segment (n_segs + 1)][one record per tile], as normalization's)
+int deltas_enqueue(mfcc_hip_handle *h, const float *d_in, float *d_out, mfcc_norm::Segs s, const long long *host_table,
+                   size_t table_ll, int order, int window) {
+    int rc = scratch_acquire(h);
+    if (rc) return rc;
+    if (host_table) {
+        if ((rc = ensure(h, &h->d_dtab, &h->d_dtab_bytes, table_ll * sizeof(long long) + 64))) return rc;
+        long long *d_table = static_cast<long long *>(h->d_dtab);
+        HIP_TRY(h, hipMemcpyAsync(d_table, host_table, table_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+        s.seg_blk0 = d_table;
+        s.blk = reinterpret_cast<const mfcc_norm::BlockRec *>(d_table + s.n_segs + 1);
+    }
+    const unsigned grid = unsigned(std::min<long long>(s.n_blocks, 1 << 20));
+    const mfcc_delta::DeltasKernel kernel = mfcc_delta::deltas_kernel_of(order, window);
+    if (!kernel) return MFCC_HIP_ERROR_INVALID_PARAM;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(mfcc_delta::kThreads), 0, h->stream, d_in, d_out, s,
+                       mfcc_delta::delta_scale(window));
+    HIP_TRY(h, hipGetLastError());
+    return scratch_release(h);
+}
+
+// n_segs segments of seg_rows rows each, back to back from row base_row
+int deltas_uniform(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, size_t base_row, size_t n_segs,
+                   size_t seg_rows, int order, int window) {
+    if (n_segs == 0 || seg_rows == 0) return MFCC_HIP_SUCCESS;
+    mfcc_norm::Segs s{};
+    s.width = width;
+    s.tile_rows = mfcc_delta::tile_rows(width, order, window);
+    s.base_row = (long long)base_row;
+    s.seg_rows = (long long)seg_rows;
+    s.blocks_per_seg = (long long)((seg_rows + size_t(s.tile_rows) - 1) / size_t(s.tile_rows));
+    s.n_segs = (long long)n_segs;
+    s.n_blocks = s.blocks_per_seg * s.n_segs;
+    return deltas_enqueue(h, d_in, d_out, s, nullptr, 0, order, window);
+}
+
+// segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
+int deltas_segments(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, const size_t *off, size_t n_segs,
+                    int order, int window) {
+    if (n_segs == 0 || off[n_segs] == off[0]) return MFCC_HIP_SUCCESS;
+    const size_t len0 = off[1] - off[0];
+    bool uniform = true;
+    for (size_t k = 1; k < n_segs && uniform; ++k) uniform = off[k + 1] - off[k] == len0;
+    if (uniform) return deltas_uniform(h, d_in, d_out, width, off[0], n_segs, len0, order, window);
+    const size_t tr = size_t(mfcc_delta::tile_rows(width, order, window));
+    size_t n_blocks = 0;
+    for (size_t k = 0; k < n_segs; ++k) n_blocks += (off[k + 1] - off[k] + tr - 1) / tr;
+    if (n_segs >= (size_t(1) << 31)) return MFCC_HIP_ERROR_INVALID_PARAM;       // BlockRec::seg is an int
+    const size_t table_ll = n_segs + 1 + 2 * n_blocks;
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    int rc = desc_acquire(h, table_ll, &pd);
+    if (rc) return rc;
+    long long *blk0 = pd->p;
+    auto *rec = reinterpret_cast<mfcc_norm::BlockRec *>(pd->p + n_segs + 1);
+    size_t b = 0;
+    for (size_t k = 0; k < n_segs; ++k) {
+        blk0[k] = (long long)b;
+        for (size_t r = off[k]; r < off[k + 1]; r += tr)
+            rec[b++] = mfcc_norm::BlockRec{(long long)r, int(std::min(tr, off[k + 1] - r)), int(k)};
+    }
+    blk0[n_segs] = (long long)b;
+    mfcc_norm::Segs s{};
+    s.width = width;
+    s.tile_rows = int(tr);
+    s.n_segs = (long long)n_segs;
+    s.n_blocks = (long long)n_blocks;
+    rc = deltas_enqueue(h, d_in, d_out, s, pd->p, table_ll, order, window);
+    if (rc) return rc;
+    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
+    pd->in_flight = true;
+    return MFCC_HIP_SUCCESS;
+}
+
+// width of a float output row of this handle: the static row, times 1 + the delta order
+inline size_t out_width(const mfcc_hip_handle *h) { return row_width(h->r) * size_t(1 + h->delta_order); }
+
+// the dense float device path of a handle with deltas: the launch and the normalization into h->d_stat, then the
+// expanded rows into d_out, one segment per channel
+int launch_expanded(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch, void *d_out,
+                    size_t *n_frames) {
+    const size_t nf = count_frames(h->r, n), W = row_width(h->r);
+    if (nf == 0 || nch == 0 || !d_out) return launch(h, false, d_pcm, n, stride, nch, 0, d_out, n_frames);
+    DeviceGuard guard(h->device);
+    int rc = ensure(h, &h->d_stat, &h->d_stat_bytes, nf * nch * W * sizeof(float) + 64);
+    if (rc || (rc = scratch_acquire(h))) return rc;
+    float *stat = static_cast<float *>(h->d_stat);
+    if ((rc = launch(h, false, d_pcm, n, stride, nch, 0, stat, n_frames))) return rc;
+    if ((rc = normalize_uniform(h, stat, int(W), 0, nch, nf, h->norm))) return rc;
+    if ((rc = deltas_uniform(h, stat, static_cast<float *>(d_out), int(W), 0, nch, nf, h->delta_order, h->delta_window)))
+        return rc;
+    return scratch_release(h);
+}
+
 // the dense float device path with the handle's normalization: the launch, then one segment per channel
 int launch_float_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo, void *d_out,
                      size_t *n_frames) {
-    if (h && h->norm != MFCC_HIP_NORMALIZE_NONE && halo) return MFCC_HIP_ERROR_UNSUPPORTED;   // a shard of a longer stream
+    if (h && (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order) && halo)
+        return MFCC_HIP_ERROR_UNSUPPORTED;                                       // a shard of a longer stream
+    if (h && h->delta_order) return launch_expanded(h, d_pcm, n, stride, nch, d_out, n_frames);
     int rc = launch(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
     if (rc || h->norm == MFCC_HIP_NORMALIZE_NONE) return rc;
     DeviceGuard guard(h->device);
@@ -832,11 +938,14 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     const size_t nf = count_frames(h->r, n);
     if (n_frames) *n_frames = nf;
     if (nf == 0 || nch == 0) return MFCC_HIP_SUCCESS;
-    const size_t ncep = row_width(h->r), hop = size_t(h->r.hop), nfft = size_t(h->r.nfft);   // elements per row
+    const size_t ncep = fixed ? row_width(h->r) : out_width(h), hop = size_t(h->r.hop), nfft = size_t(h->r.nfft);   // elements per row
     const size_t n_out = nf * nch * ncep;
     if (!out || cap < n_out) return MFCC_HIP_ERROR_BUFFER_SMALL;
     DeviceGuard guard(h->device);
     const size_t kChunkBytes = host_chunk_bytes();
+    // deltas: the static rows (W wide, 1 + K times narrower than the output rows) go to h->d_stat first
+    const int K = fixed ? 0 : h->delta_order;
+    const size_t W = row_width(h->r);
 
     // ---- the chunks
     std::vector<HostChunk> chunks;
@@ -865,13 +974,23 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     // normalization: no row may leave the device before its channel's statistics exist.  Chunks of whole channels
     // normalize their own rows before the copy back; frame-range chunks of long channels write into one device buffer of
     // the whole result, which is normalized and copied back after the pipeline
+    // The same holds for deltas, which need the neighbouring frames of the channel: a chunk edge is not a channel edge.
+    // With deltas, chunks of whole channels write their static rows to h->d_stat and expand them into the chunk's
+    // output; frame-range chunks write every channel's static rows to h->d_stat, which is normalized and expanded into
+    // the whole result after the pipeline
     const int norm = fixed ? MFCC_HIP_NORMALIZE_NONE : h->norm;
-    const bool whole = norm != MFCC_HIP_NORMALIZE_NONE && ch_bytes > kChunkBytes;
+    const bool whole = (norm != MFCC_HIP_NORMALIZE_NONE || K) && ch_bytes > kChunkBytes;
     OutT *d_full = nullptr;
+    float *d_stat = nullptr;
     if (whole) {
         const int rc = ensure(h, &h->d_full, &h->d_full_bytes, n_out * sizeof(OutT) + 64);
         if (rc) return rc;
         d_full = static_cast<OutT *>(h->d_full);
+    }
+    if (K) {
+        int rc = ensure(h, &h->d_stat, &h->d_stat_bytes, (whole ? nch : std::min(nch, kChunkBytes / (ch_bytes ? ch_bytes : 1) + 1)) * nf * W * sizeof(float) + 64);
+        if (rc || (rc = scratch_acquire(h))) return rc;
+        d_stat = static_cast<float *>(h->d_stat);
     }
     std::vector<PipeChunk> pc;
     pc.reserve(chunks.size());
@@ -879,13 +998,20 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
         pc.push_back({c.in, c.in_samples * sizeof(int16_t), out + c.out_off, whole ? 0 : c.out_elems * sizeof(OutT)});
     int rc = run_host_pipeline(h, pc, pcm, nch * ch_bytes, out, whole ? 0 : n_out * sizeof(OutT), [&](size_t i, void *d_in, void *d_out) {
         const HostChunk &c = chunks[i];
-        if (whole) d_out = d_full + c.out_off;
-        const int lrc = launch(h, fixed, d_in, c.n, c.stride, c.nch, c.halo, d_out, nullptr, c.halo || c.frames != nf ? c.frames : 0);
-        if (lrc || whole || norm == MFCC_HIP_NORMALIZE_NONE) return lrc;
-        return normalize_uniform(h, reinterpret_cast<float *>(d_out), int(ncep), 0, c.nch, nf, norm);
+        void *rows = whole ? static_cast<void *>(d_full + c.out_off) : d_out;
+        if (K) rows = whole ? d_stat + c.out_off / size_t(1 + K) : d_stat;
+        const int lrc = launch(h, fixed, d_in, c.n, c.stride, c.nch, c.halo, rows, nullptr, c.halo || c.frames != nf ? c.frames : 0);
+        if (lrc || whole) return lrc;
+        const int nrc = normalize_uniform(h, reinterpret_cast<float *>(rows), int(W), 0, c.nch, nf, norm);
+        if (nrc || !K) return nrc;
+        return deltas_uniform(h, d_stat, reinterpret_cast<float *>(d_out), int(W), 0, c.nch, nf, K, h->delta_window);
     });
-    if (rc || !whole) return rc;
-    if ((rc = normalize_uniform(h, reinterpret_cast<float *>(d_full), int(ncep), 0, nch, nf, norm))) return rc;
+    if (rc || !whole) return rc ? rc : (K ? scratch_release(h) : MFCC_HIP_SUCCESS);
+    float *stat = K ? d_stat : reinterpret_cast<float *>(d_full);
+    if ((rc = normalize_uniform(h, stat, int(W), 0, nch, nf, norm))) return rc;
+    if (K && (rc = deltas_uniform(h, stat, reinterpret_cast<float *>(d_full), int(W), 0, nch, nf, K, h->delta_window)))
+        return rc;
+    if (K && (rc = scratch_release(h))) return rc;
     HIP_TRY(h, hipMemcpyAsync(out, d_full, n_out * sizeof(OutT), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MFCC_HIP_SUCCESS;
@@ -1099,12 +1225,39 @@ int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm,
 // ... and the handle's normalization over the dense result, one segment per utterance (float contract only: the
 // public fixed-point entry points refuse a normalizing handle)
 template <typename OutT>
-int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
-                       OutT *d_out, size_t cap, size_t *frame_offsets) {
+int process_ragged_dev_static(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
+                              OutT *d_out, size_t cap, size_t *frame_offsets) {
     const int rc = process_ragged_dev_raw<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
     if (rc || fixed || h->norm == MFCC_HIP_NORMALIZE_NONE || n_utt == 0) return rc;
     DeviceGuard guard(h->device);
     return normalize_segments(h, reinterpret_cast<float *>(d_out), int(row_width(h->r)), frame_offsets, n_utt, h->norm);
+}
+
+// ... and with deltas: the static rows go to h->d_stat, then the expanded rows to d_out, one segment per utterance
+template <typename OutT>
+int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
+                       OutT *d_out, size_t cap, size_t *frame_offsets) {
+    if (!h || fixed || !h->delta_order || !offsets || !frame_offsets)
+        return process_ragged_dev_static<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
+    size_t total = 0;
+    for (size_t u = 0; u < n_utt; ++u) {
+        if (offsets[u + 1] < offsets[u])            // refused by the call below
+            return process_ragged_dev_static<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
+        total += count_frames(h->r, offsets[u + 1] - offsets[u]);
+    }
+    const size_t W = row_width(h->r);
+    // nothing to write, or a buffer too small: the static call fills frame_offsets and gives the answer
+    if (total == 0 || !d_out || cap < total * out_width(h))
+        return process_ragged_dev_static<OutT>(h, fixed, d_pcm, offsets, n_utt, total ? nullptr : d_out, 0, frame_offsets);
+    DeviceGuard guard(h->device);
+    int rc = ensure(h, &h->d_stat, &h->d_stat_bytes, total * W * sizeof(float) + 64);
+    if (rc || (rc = scratch_acquire(h))) return rc;
+    float *stat = static_cast<float *>(h->d_stat);
+    if ((rc = process_ragged_dev_static<float>(h, false, d_pcm, offsets, n_utt, stat, total * W, frame_offsets))) return rc;
+    if ((rc = deltas_segments(h, stat, reinterpret_cast<float *>(d_out), int(W), frame_offsets, n_utt, h->delta_order,
+                              h->delta_window)))
+        return rc;
+    return scratch_release(h);
 }
 
 // Host buffers: the corpus goes to the device in ONE copy (the span offsets[0] .. offsets[n_utt] as it lies), runs through
@@ -1116,7 +1269,7 @@ int process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const siz
                    OutT *out, size_t cap, size_t *frame_offsets) {
     if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
-    const size_t ncep = row_width(h->r);               // elements per row
+    const size_t ncep = fixed ? row_width(h->r) : out_width(h);          // elements per row
     size_t total = 0;
     std::vector<size_t> rel(n_utt + 1, 0);
     for (size_t u = 0; u < n_utt; ++u) {
@@ -1401,6 +1554,8 @@ void mfcc_hip_destroy(mfcc_hip_handle *h) {
     if (h->d_out) (void)hipFree(h->d_out);
     if (h->d_norm) (void)hipFree(h->d_norm);
     if (h->d_full) (void)hipFree(h->d_full);
+    if (h->d_stat) (void)hipFree(h->d_stat);
+    if (h->d_dtab) (void)hipFree(h->d_dtab);
     delete h;
 }
 
@@ -1430,6 +1585,7 @@ int mfcc_hip_process_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_
 int mfcc_hip_process_fixed_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_t nch,
                                int16_t *out, size_t cap, size_t *n_frames) {
     if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
+    if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
     return process_host<int16_t>(h, true, pcm, n, nch, out, cap, n_frames);
 }
 
@@ -1441,6 +1597,7 @@ int mfcc_hip_process_ragged_i16(mfcc_hip_handle *h, const int16_t *pcm, const si
 int mfcc_hip_process_ragged_fixed_i16(mfcc_hip_handle *h, const int16_t *pcm, const size_t *offsets, size_t n_utt,
                                       int16_t *out, size_t cap, size_t *frame_offsets) {
     if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
+    if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
     return process_ragged<int16_t>(h, true, pcm, offsets, n_utt, out, cap, frame_offsets);
 }
 
@@ -1453,6 +1610,7 @@ int mfcc_hip_process_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const
 int mfcc_hip_process_ragged_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const size_t *offsets, size_t n_utt,
                                           void *d_out, size_t cap, size_t *frame_offsets) {
     if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
+    if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
     return process_ragged_dev<int16_t>(h, true, static_cast<const int16_t *>(d_pcm), offsets, n_utt,
                                        static_cast<int16_t *>(d_out), cap, frame_offsets);
 }
@@ -1465,15 +1623,16 @@ int mfcc_hip_process_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, si
 int mfcc_hip_process_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride,
                                    size_t nch, int halo, void *d_out, size_t *n_frames) {
     if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
+    if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
     return launch(h, true, d_pcm, n, stride, nch, halo, d_out, n_frames);
 }
 
 int mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n, size_t stride,
                       size_t nch, void *d_out, int warmup, int iters, float *avg_ms) {
     if (!h || iters < 1 || warmup < 0 || !avg_ms) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (fixed && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (fixed && (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order)) return MFCC_HIP_ERROR_UNSUPPORTED;
     DeviceGuard guard(h->device);
-    // what process_*_dev enqueues: with normalization on, the float launch and the normalization passes
+    // what process_*_dev enqueues: with normalization or deltas on, the float launch and the passes behind it
     auto once = [&]() {
         return fixed ? launch(h, true, d_pcm, n, stride, nch, 0, d_out, nullptr)
                      : launch_float_dev(h, d_pcm, n, stride, nch, 0, d_out, nullptr);
@@ -1525,6 +1684,37 @@ int mfcc_hip_normalize_dev(mfcc_hip_handle *h, void *d_rows, int row_width, cons
     return normalize_segments(h, static_cast<float *>(d_rows), row_width, seg_offsets, n_segs, mode);
 }
 
+int mfcc_hip_set_deltas(mfcc_hip_handle *h, int order, int window) {
+    if (!h || order < 0 || order > 2 || window < 1 || window > MFCC_HIP_MAX_DELTA_WINDOW)
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
+    h->delta_order = order;
+    h->delta_window = window;
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_deltas_dev(mfcc_hip_handle *h, const void *d_in, int width, void *d_out, const size_t *seg_offsets,
+                        size_t n_segs, int order, int window) {
+    if (!h || width < 1 || width > mfcc_delta::kMaxWidth || order < 1 || order > 2 || window < 1 ||
+        window > MFCC_HIP_MAX_DELTA_WINDOW || (n_segs && !seg_offsets))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    for (size_t k = 0; k < n_segs; ++k)
+        if (seg_offsets[k + 1] < seg_offsets[k]) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (n_segs == 0 || seg_offsets[n_segs] == seg_offsets[0]) return MFCC_HIP_SUCCESS;
+    if (!d_in || !d_out || (reinterpret_cast<uintptr_t>(d_in) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    // the byte ranges the pass reads and writes must not overlap
+    const size_t r0 = seg_offsets[0], r1 = seg_offsets[n_segs], W = size_t(width), WO = W * size_t(1 + order);
+    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(d_in) + r0 * W * sizeof(float);
+    const uintptr_t in_hi = reinterpret_cast<uintptr_t>(d_in) + r1 * W * sizeof(float);
+    const uintptr_t out_lo = reinterpret_cast<uintptr_t>(d_out) + r0 * WO * sizeof(float);
+    const uintptr_t out_hi = reinterpret_cast<uintptr_t>(d_out) + r1 * WO * sizeof(float);
+    if (in_lo < out_hi && out_lo < in_hi) return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    return deltas_segments(h, static_cast<const float *>(d_in), static_cast<float *>(d_out), width, seg_offsets, n_segs,
+                           order, window);
+}
+
 const char *mfcc_hip_kernel_name(const mfcc_hip_handle *h, int fixed) {
     if (!h) return "";
     if (fixed) return h->fixed512_ok ? mfcc_fixed512::kernel_name() : "mfcc_fixed_kernel";
@@ -1542,6 +1732,7 @@ int mfcc_hip_convert_wav(mfcc_hip_handle *h, const char *wav_in, const char *mfc
     if (!h || !wav_in || !mfcc_out) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
     if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;     // ... raw ones
+    if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... n_cep wide
     std::vector<int16_t> pcm;
     int rc = read_wav_i16(wav_in, h->r.sample_rate, pcm);
     if (rc) return rc;
@@ -1584,6 +1775,7 @@ int mfcc_hip_convert_wavs(mfcc_hip_handle *h, const char *const *wav_in, const c
     if (!h || (n_files && (!wav_in || !mfcc_out))) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
     if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;     // ... raw ones
+    if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... n_cep wide
     std::vector<int16_t> pcm;
     std::vector<size_t> off(n_files + 1, 0), fo(n_files + 1, 0);
     for (size_t i = 0; i < n_files; ++i) {
@@ -1690,6 +1882,7 @@ int mfcc_hip_stream_create(mfcc_hip_handle *h, int fixed, mfcc_hip_stream **out)
     *out = nullptr;
     if (h->destroy_pending) return MFCC_HIP_ERROR_INVALID_PARAM;        // the handle was already given back
     if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // per-call statistics of a stream
+    if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;     // deltas need 2 K N frames of lookahead
     if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
     mfcc_hip_stream *s = new (std::nothrow) mfcc_hip_stream();
     if (!s) return MFCC_HIP_ERROR_NO_MEM;

@@ -19,6 +19,11 @@ Per-utterance normalization (``MFCC(normalize=...)``) needs the statistics of a 
 utterance / channel on one rank, so a normalizing handle there gives the right rows as it is.  A frame-range shard is
 only part of a stream: the device path refuses ``halo=1`` on a normalizing handle.  Compute the shards raw, gather
 them, then normalize the whole stream once with ``MFCC.normalize_rows`` (``mfcc_hip_normalize_dev``).
+
+Deltas (``MFCC(deltas=...)``) read the neighbouring frames, so a shard's first and last frames are not its stream's
+edges: the device path refuses ``halo=1`` on a handle with deltas too.  For frame-range shards compute the raw rows,
+gather them, ``MFCC.normalize_rows`` if wanted, then ``MFCC.deltas_rows`` (``mfcc_hip_deltas_dev``) over the whole
+stream.
 """
 from __future__ import annotations
 
