@@ -246,6 +246,39 @@ int  mfcc_hip_set_normalize(mfcc_hip_handle *h, int mode);
 int  mfcc_hip_normalize_dev(mfcc_hip_handle *h, void *d_rows, int row_width, const size_t *seg_offsets, size_t n_segs,
                             int mode);
 
+/* ---- sliding-window normalization -------------------------------------------------------
+ * For long channels: with a window on and mode MEAN or MEAN_VAR, the row of frame t of a segment of T rows (one channel
+ * of a dense call, one utterance of a ragged one) is standardized with the statistics of rows [a, b) of the SAME
+ * segment instead of the whole segment.  With window N, minimum window M and center (Kaldi's SlidingWindowCmn rule):
+ *     if center:  a = t - N / 2;  b = a + N
+ *     else:       a = t - N;      b = t + 1            (the causal window holds N + 1 frames)
+ *     if a < 0:   b -= a;  a = 0
+ *     if not center and b > t:  b = max(t + 1, M)      (M only acts on the first frames of the causal form)
+ *     if b > T:   a -= b - T;  b = T;  a = max(a, 0)
+ * Everything else is the contract of enum mfcc_hip_normalize applied to rows [a, b): per column over the FINITE values
+ * of those rows, mu and the population sigma in float64, sigma' = 1 where sigma < 10 * 2^-52 (a window with one finite
+ * value, or a constant one, gives exactly 0; Kaldi floors the variance at 1e-10 instead: a documented difference),
+ * y = (x - mu32) * r32, non-finite x written back unchanged and left out of every window that covers them.  The rows
+ * read are the rows the handle returns with normalization off.  The result of a segment depends on its rows, the row
+ * width, N, M, center and the mode alone: the same bits from every entry point, any chunking of a host call, any
+ * 4-byte alignment, any run.  Deltas (mfcc_hip_set_deltas) run on the sliding-normalized statics.
+ * window = 0: off (the state after mfcc_hip_create: per-segment statistics, bit for bit).  Otherwise
+ * 1 <= min_window <= window <= MFCC_HIP_MAX_NORMALIZE_WINDOW, center 0 or 1; anything else, or a NULL handle:
+ * MFCC_HIP_ERROR_INVALID_PARAM; live streaming sessions: MFCC_HIP_ERROR_BUSY.  A window with mode NONE is stored and has
+ * no effect.  The refusals of a normalizing handle are those of mfcc_hip_set_normalize.  mfcc_hip_time_dev times this
+ * pass too.  The parameter block and the ABI version are unchanged.                                             */
+#define MFCC_HIP_MAX_NORMALIZE_WINDOW 16384
+int  mfcc_hip_set_normalize_window(mfcc_hip_handle *h, int window, int min_window, int center);
+/* The kernel's direct entry, OUT OF PLACE (the window of a row reaches into rows already rewritten): d_in rows
+ * [seg_offsets[n_segs]][row_width] (rows before seg_offsets[0] not read), d_out rows at the same row indices; rows of
+ * d_out outside the segments untouched.  Segment k = rows seg_offsets[k] .. seg_offsets[k + 1] (host array, n_segs + 1
+ * entries, must not decrease).  row_width 1..64, window / min_window / center as above (window >= 1), both pointers
+ * 4-byte aligned, the two byte ranges must not overlap: otherwise MFCC_HIP_ERROR_INVALID_PARAM.  Asynchronous on the
+ * handle's stream; mode NONE or n_segs = 0 is a no-op.                                                         */
+int  mfcc_hip_normalize_sliding_dev(mfcc_hip_handle *h, const void *d_in, int row_width, void *d_out,
+                                    const size_t *seg_offsets, size_t n_segs, int mode, int window, int min_window,
+                                    int center);
+
 /* ---- delta and delta-delta coefficients -------------------------------------------------
  * With delta order K (1 or 2) and window N (1..MFCC_HIP_MAX_DELTA_WINDOW), the float row of frame t of a segment (one
  * channel of a dense call, one utterance of a ragged one) becomes W * (1 + K) wide, W = n_cep or n_mel:

@@ -40,6 +40,7 @@ NORMALIZE_MEAN = 1
 NORMALIZE_MEAN_VAR = 2
 
 MAX_DELTA_WINDOW = 8
+MAX_NORMALIZE_WINDOW = 16384
 
 TABLE_WINDOW_F32 = 0
 TABLE_MEL_POINTS_I32 = 1
@@ -109,6 +110,9 @@ SYMBOLS = {
     "mfcc_hip_kernel_name": (C.c_char_p, [_H, C.c_int]),
     "mfcc_hip_set_normalize": (C.c_int, [_H, C.c_int]),
     "mfcc_hip_normalize_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, _SZ, C.c_int]),
+    "mfcc_hip_set_normalize_window": (C.c_int, [_H, C.c_int, C.c_int, C.c_int]),
+    "mfcc_hip_normalize_sliding_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _SZ, C.c_int, C.c_int,
+                                                 C.c_int, C.c_int]),
     "mfcc_hip_set_deltas": (C.c_int, [_H, C.c_int, C.c_int]),
     "mfcc_hip_deltas_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _SZ, C.c_int, C.c_int]),
     "mfcc_hip_convert_wav": (C.c_int, [_H, C.c_char_p, C.c_char_p, C.c_int, _PSZ]),

@@ -50,6 +50,33 @@ def _delta_args(order, window, orders=(0, 1, 2)):
     return int(order), int(window)
 
 
+_MIN_WINDOW = 100                  # default minimum window of the causal form (Kaldi's --min-cmn-window)
+
+
+def _window_args(window, min_window=_MIN_WINDOW, center=True):
+    """(window, min_window, center) as ints for mfcc_hip_set_normalize_window, or ValueError.  ``window`` None: off,
+    (0, 1, 1).  Otherwise 1 <= min_window <= window <= 16 384 (MFCC_HIP_MAX_NORMALIZE_WINDOW); a ``min_window`` left
+    at its default is clamped to ``window``."""
+    def is_int(v):
+        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+    if isinstance(center, bool) or (is_int(center) and int(center) in (0, 1)):
+        center = int(center)
+    else:
+        raise ValueError("normalize_center must be True or False, not %r" % (center,))
+    if window is None:
+        return 0, 1, center
+    if not is_int(window) or not 1 <= int(window) <= _lib.MAX_NORMALIZE_WINDOW:
+        raise ValueError("normalize_window must be None or 1..%d, not %r" % (_lib.MAX_NORMALIZE_WINDOW, window))
+    if not is_int(min_window):
+        raise ValueError("normalize_min_window must be an int, not %r" % (min_window,))
+    window, min_window = int(window), int(min_window)
+    if min_window == _MIN_WINDOW:
+        min_window = min(min_window, window)
+    if not 1 <= min_window <= window:
+        raise ValueError("normalize_min_window must be 1..normalize_window (%d), not %r" % (window, min_window))
+    return window, min_window, center
+
+
 def make_params(nfft=512, hop=None, nfilters=32, nceptrums=13, samplerate=16000, pad_mode="notebook",
                 power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra") -> Params:
     """``output``: ``"cepstra"`` (rows of ``nceptrums`` DCT-II coefficients) or ``"logmel"`` (rows of ``nfilters``
@@ -130,10 +157,12 @@ class MFCC:
 
     def __init__(self, width=16, nfft=512, samplerate=16e3, nfilters=16, nceptrums=16, *, hop=None,
                  pad_mode="notebook", power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra",
-                 normalize=None, deltas=0, delta_window=2):
+                 normalize=None, deltas=0, delta_window=2, normalize_window=None, normalize_min_window=_MIN_WINDOW,
+                 normalize_center=True):
         if width != 16:
             raise ValueError("only width=16 (int16 PCM) is supported, like every reference target")
         norm = normalize_mode(normalize)
+        _window_args(normalize_window, normalize_min_window, normalize_center)
         order, window = _delta_args(deltas, delta_window)
         self.width = width
         self.nfft = int(nfft)
@@ -164,6 +193,17 @@ class MFCC:
         self.deltas, self.delta_window = 0, window
         if order:
             self.set_deltas(order, window)
+        self.normalize_window, self.normalize_min_window, self.normalize_center = None, _MIN_WINDOW, True
+        if normalize_window is not None:
+            self.set_normalize_window(normalize_window, normalize_min_window, normalize_center)
+
+    def set_normalize_window(self, window, min_window=_MIN_WINDOW, center=True):
+        """The window of the handle's normalization for every float call after this one: ``None`` (statistics over
+        the whole channel / utterance) or ``window`` frames around each frame (``center``) or before it (causal, with
+        at least ``min_window`` frames at the start): Kaldi's sliding-window CMVN, for long channels."""
+        w, m, c = _window_args(window, min_window, center)
+        _lib.check(self._lib.mfcc_hip_set_normalize_window(self._h, w, m, c), "set_normalize_window")
+        self.normalize_window, self.normalize_min_window, self.normalize_center = (w or None), m, bool(c)
 
     def set_deltas(self, order, window=2):
         """The handle's delta order (0 = off, 1 = D, 2 = D and DD) and window for every float call after this one."""
@@ -209,12 +249,18 @@ class MFCC:
         _lib.check(self._lib.mfcc_hip_set_normalize(self._h, normalize_mode(mode)), "set_normalize")
         self.normalize = None if normalize_mode(mode) == _lib.NORMALIZE_NONE else mode
 
-    def normalize_rows(self, rows, frame_offsets=None, mode="meanvar"):
+    def normalize_rows(self, rows, frame_offsets=None, mode="meanvar", window=None, min_window=_MIN_WINDOW, center=True,
+                       out=None):
         """Normalize a CUDA float32 tensor of rows in place, on the current torch stream, and return it.  ``rows``:
         ``(frames, width)`` with ``frame_offsets`` (segment ``u`` = rows ``fo[u]:fo[u + 1]``, e.g. what
         :meth:`process_packed` returns) or, without them, one segment; ``(channels, frames, width)``: one segment per
-        channel.  ``width`` 1..64, independent of this handle's own rows."""
+        channel.  ``width`` 1..64, independent of this handle's own rows.  With a ``window`` (sliding statistics, see
+        :meth:`set_normalize_window`) the pass is out of place: ``rows`` is left alone and a new tensor (or ``out``,
+        same shape, not overlapping ``rows``) is returned; rows of it outside the segments are left as they are."""
         import torch
+        w, m, c = _window_args(window, min_window, center)
+        if not w and out is not None:
+            raise ValueError("out is for the sliding form (window=...); without a window rows are normalized in place")
         if rows.dtype != torch.float32 or not rows.is_cuda or not rows.is_contiguous() or rows.dim() not in (2, 3):
             raise TypeError("rows must be a contiguous 2-D or 3-D CUDA(HIP) float32 tensor")
         width = int(rows.shape[-1])
@@ -229,6 +275,20 @@ class MFCC:
             if len(fo) > 1 and int(fo[-1]) * width > rows.numel():
                 raise ValueError("frame_offsets run past the end of rows")
         self._check_device(rows)
+        if w:
+            if out is None:
+                # a new tensor: rows the segments do not cover (and every row, for mode None) are copies of the input
+                whole = frame_offsets is None and normalize_mode(mode) != _lib.NORMALIZE_NONE
+                out = torch.empty_like(rows) if whole else rows.clone()
+            elif tuple(out.shape) != tuple(rows.shape) or out.dtype != torch.float32 or not out.is_contiguous() or \
+                    out.device != rows.device:
+                raise ValueError("out must be a contiguous float32 tensor of shape %s on %s"
+                                 % (tuple(rows.shape), rows.device))
+            with self._on_torch_stream(rows.device):
+                _lib.check(self._lib.mfcc_hip_normalize_sliding_dev(
+                    self._h, C.c_void_p(rows.data_ptr()), width, C.c_void_p(out.data_ptr()),
+                    fo.ctypes.data_as(C.c_void_p), len(fo) - 1, normalize_mode(mode), w, m, c), "normalize_sliding_dev")
+            return out
         with self._on_torch_stream(rows.device):
             _lib.check(self._lib.mfcc_hip_normalize_dev(self._h, C.c_void_p(rows.data_ptr()), width,
                                                         fo.ctypes.data_as(C.c_void_p), len(fo) - 1,

@@ -25,6 +25,7 @@
 #include "kernel_fused512_w12.hpp"
 #include "kernel_normalize.hpp"
 #include "kernel_deltas.hpp"
+#include "kernel_normalize_sliding.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -186,6 +187,16 @@ struct mfcc_hip_handle {
     size_t d_stat_bytes = 0;
     void *d_dtab = nullptr;
     size_t d_dtab_bytes = 0;
+    // sliding-window normalization (mfcc_hip_set_normalize_window): window 0 (off: the per-segment form), the minimum
+    // window of the causal form and centered / causal; the raw rows the sliding pass reads (d_slide: it cannot run
+    // in place) and its tile table (d_stab)
+    int norm_window = 0;
+    int norm_min_window = 1;
+    int norm_center = 1;
+    void *d_slide = nullptr;
+    size_t d_slide_bytes = 0;
+    void *d_stab = nullptr;
+    size_t d_stab_bytes = 0;
 };
 
 namespace {
@@ -708,6 +719,88 @@ int deltas_segments(mfcc_hip_handle *h, const float *d_in, float *d_out, int wid
     return MFCC_HIP_SUCCESS;
 }
 
+// ---- sliding-window normalization (kernel_normalize_sliding.hpp): out of place.  A handle with
+// a window runs its kernels into h->d_slide, then this pass writes the normalized rows to the caller's buffer (or to
+// h->d_stat, when deltas follow).  The tile table of a ragged call goes to h->d_stab (layout as normalization's)
+struct SlideArgs {
+    int mode, window, min_window, center;
+};
+
+inline bool sliding(const mfcc_hip_handle *h) { return h->norm != MFCC_HIP_NORMALIZE_NONE && h->norm_window > 0; }
+inline SlideArgs slide_args(const mfcc_hip_handle *h) {
+    return SlideArgs{h->norm, h->norm_window, h->norm_min_window, h->norm_center};
+}
+
+int sliding_enqueue(mfcc_hip_handle *h, const float *d_in, float *d_out, mfcc_norm::Segs s, const long long *host_table,
+                    size_t table_ll, SlideArgs a) {
+    int rc = scratch_acquire(h);
+    if (rc) return rc;
+    if (host_table) {
+        if ((rc = ensure(h, &h->d_stab, &h->d_stab_bytes, table_ll * sizeof(long long) + 64))) return rc;
+        long long *d_table = static_cast<long long *>(h->d_stab);
+        HIP_TRY(h, hipMemcpyAsync(d_table, host_table, table_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+        s.seg_blk0 = d_table;
+        s.blk = reinterpret_cast<const mfcc_norm::BlockRec *>(d_table + s.n_segs + 1);
+    }
+    const unsigned grid = unsigned(std::min<long long>(s.n_blocks, 1 << 20));
+    hipLaunchKernelGGL(mfcc_slide::normalize_sliding_kernel, dim3(grid), dim3(mfcc_slide::kThreads), 0, h->stream, d_in,
+                       d_out, s, mfcc_slide::run_rows(a.window), a.window, a.min_window, a.center, a.mode);
+    HIP_TRY(h, hipGetLastError());
+    return scratch_release(h);
+}
+
+// n_segs segments of seg_rows rows each, back to back from row base_row
+int sliding_uniform(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, size_t base_row, size_t n_segs,
+                    size_t seg_rows, SlideArgs a) {
+    if (n_segs == 0 || seg_rows == 0) return MFCC_HIP_SUCCESS;
+    mfcc_norm::Segs s{};
+    s.width = width;
+    s.tile_rows = mfcc_slide::tile_rows(width, a.window);
+    s.base_row = (long long)base_row;
+    s.seg_rows = (long long)seg_rows;
+    s.blocks_per_seg = (long long)((seg_rows + size_t(s.tile_rows) - 1) / size_t(s.tile_rows));
+    s.n_segs = (long long)n_segs;
+    s.n_blocks = s.blocks_per_seg * s.n_segs;
+    return sliding_enqueue(h, d_in, d_out, s, nullptr, 0, a);
+}
+
+// segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
+int sliding_segments(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, const size_t *off, size_t n_segs,
+                     SlideArgs a) {
+    if (n_segs == 0 || off[n_segs] == off[0]) return MFCC_HIP_SUCCESS;
+    const size_t len0 = off[1] - off[0];
+    bool uniform = true;
+    for (size_t k = 1; k < n_segs && uniform; ++k) uniform = off[k + 1] - off[k] == len0;
+    if (uniform) return sliding_uniform(h, d_in, d_out, width, off[0], n_segs, len0, a);
+    const size_t tr = size_t(mfcc_slide::tile_rows(width, a.window));
+    size_t n_blocks = 0;
+    for (size_t k = 0; k < n_segs; ++k) n_blocks += (off[k + 1] - off[k] + tr - 1) / tr;
+    if (n_segs >= (size_t(1) << 31)) return MFCC_HIP_ERROR_INVALID_PARAM;       // BlockRec::seg is an int
+    const size_t table_ll = n_segs + 1 + 2 * n_blocks;
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    int rc = desc_acquire(h, table_ll, &pd);
+    if (rc) return rc;
+    long long *blk0 = pd->p;
+    auto *rec = reinterpret_cast<mfcc_norm::BlockRec *>(pd->p + n_segs + 1);
+    size_t b = 0;
+    for (size_t k = 0; k < n_segs; ++k) {
+        blk0[k] = (long long)b;
+        for (size_t r = off[k]; r < off[k + 1]; r += tr)
+            rec[b++] = mfcc_norm::BlockRec{(long long)r, int(std::min(tr, off[k + 1] - r)), int(k)};
+    }
+    blk0[n_segs] = (long long)b;
+    mfcc_norm::Segs s{};
+    s.width = width;
+    s.tile_rows = int(tr);
+    s.n_segs = (long long)n_segs;
+    s.n_blocks = (long long)n_blocks;
+    rc = sliding_enqueue(h, d_in, d_out, s, pd->p, table_ll, a);
+    if (rc) return rc;
+    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
+    pd->in_flight = true;
+    return MFCC_HIP_SUCCESS;
+}
+
 // width of a float output row of this handle: the static row, times 1 + the delta order
 inline size_t out_width(const mfcc_hip_handle *h) { return row_width(h->r) * size_t(1 + h->delta_order); }
 
@@ -718,12 +811,19 @@ int launch_expanded(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stri
     const size_t nf = count_frames(h->r, n), W = row_width(h->r);
     if (nf == 0 || nch == 0 || !d_out) return launch(h, false, d_pcm, n, stride, nch, 0, d_out, n_frames);
     DeviceGuard guard(h->device);
-    int rc = ensure(h, &h->d_stat, &h->d_stat_bytes, nf * nch * W * sizeof(float) + 64);
+    // with a normalization window the kernels' raw rows go to h->d_slide and the sliding pass writes the statics
+    const bool sl = sliding(h);
+    const int K = h->delta_order;
+    int rc = K ? ensure(h, &h->d_stat, &h->d_stat_bytes, nf * nch * W * sizeof(float) + 64) : MFCC_HIP_SUCCESS;
+    if (!rc && sl) rc = ensure(h, &h->d_slide, &h->d_slide_bytes, nf * nch * W * sizeof(float) + 64);
     if (rc || (rc = scratch_acquire(h))) return rc;
-    float *stat = static_cast<float *>(h->d_stat);
-    if ((rc = launch(h, false, d_pcm, n, stride, nch, 0, stat, n_frames))) return rc;
-    if ((rc = normalize_uniform(h, stat, int(W), 0, nch, nf, h->norm))) return rc;
-    if ((rc = deltas_uniform(h, stat, static_cast<float *>(d_out), int(W), 0, nch, nf, h->delta_order, h->delta_window)))
+    float *stat = K ? static_cast<float *>(h->d_stat) : static_cast<float *>(d_out);
+    float *raw = sl ? static_cast<float *>(h->d_slide) : stat;
+    if ((rc = launch(h, false, d_pcm, n, stride, nch, 0, raw, n_frames))) return rc;
+    rc = sl ? sliding_uniform(h, raw, stat, int(W), 0, nch, nf, slide_args(h))
+            : normalize_uniform(h, stat, int(W), 0, nch, nf, h->norm);
+    if (rc) return rc;
+    if (K && (rc = deltas_uniform(h, stat, static_cast<float *>(d_out), int(W), 0, nch, nf, K, h->delta_window)))
         return rc;
     return scratch_release(h);
 }
@@ -733,7 +833,7 @@ int launch_float_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t str
                      size_t *n_frames) {
     if (h && (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order) && halo)
         return MFCC_HIP_ERROR_UNSUPPORTED;                                       // a shard of a longer stream
-    if (h && h->delta_order) return launch_expanded(h, d_pcm, n, stride, nch, d_out, n_frames);
+    if (h && (h->delta_order || sliding(h))) return launch_expanded(h, d_pcm, n, stride, nch, d_out, n_frames);
     int rc = launch(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
     if (rc || h->norm == MFCC_HIP_NORMALIZE_NONE) return rc;
     DeviceGuard guard(h->device);
@@ -987,10 +1087,16 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
         if (rc) return rc;
         d_full = static_cast<OutT *>(h->d_full);
     }
-    if (K) {
-        int rc = ensure(h, &h->d_stat, &h->d_stat_bytes, (whole ? nch : std::min(nch, kChunkBytes / (ch_bytes ? ch_bytes : 1) + 1)) * nf * W * sizeof(float) + 64);
+    // a normalization window: the kernels' raw rows go to h->d_slide (sized like d_stat), the sliding pass reads them
+    const bool sl = !fixed && sliding(h);
+    float *d_slide = nullptr;
+    if (K || sl) {
+        const size_t stage = (whole ? nch : std::min(nch, kChunkBytes / (ch_bytes ? ch_bytes : 1) + 1)) * nf * W * sizeof(float) + 64;
+        int rc = K ? ensure(h, &h->d_stat, &h->d_stat_bytes, stage) : MFCC_HIP_SUCCESS;
+        if (!rc && sl) rc = ensure(h, &h->d_slide, &h->d_slide_bytes, stage);
         if (rc || (rc = scratch_acquire(h))) return rc;
         d_stat = static_cast<float *>(h->d_stat);
+        d_slide = static_cast<float *>(h->d_slide);
     }
     std::vector<PipeChunk> pc;
     pc.reserve(chunks.size());
@@ -1000,18 +1106,23 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
         const HostChunk &c = chunks[i];
         void *rows = whole ? static_cast<void *>(d_full + c.out_off) : d_out;
         if (K) rows = whole ? d_stat + c.out_off / size_t(1 + K) : d_stat;
+        void *stat_c = rows;                             // where this chunk's normalized statics go
+        if (sl) rows = whole ? d_slide + c.out_off / size_t(1 + K) : d_slide;
         const int lrc = launch(h, fixed, d_in, c.n, c.stride, c.nch, c.halo, rows, nullptr, c.halo || c.frames != nf ? c.frames : 0);
         if (lrc || whole) return lrc;
-        const int nrc = normalize_uniform(h, reinterpret_cast<float *>(rows), int(W), 0, c.nch, nf, norm);
+        const int nrc = sl ? sliding_uniform(h, d_slide, reinterpret_cast<float *>(stat_c), int(W), 0, c.nch, nf, slide_args(h))
+                           : normalize_uniform(h, reinterpret_cast<float *>(rows), int(W), 0, c.nch, nf, norm);
         if (nrc || !K) return nrc;
         return deltas_uniform(h, d_stat, reinterpret_cast<float *>(d_out), int(W), 0, c.nch, nf, K, h->delta_window);
     });
-    if (rc || !whole) return rc ? rc : (K ? scratch_release(h) : MFCC_HIP_SUCCESS);
+    if (rc || !whole) return rc ? rc : (K || sl ? scratch_release(h) : MFCC_HIP_SUCCESS);
     float *stat = K ? d_stat : reinterpret_cast<float *>(d_full);
-    if ((rc = normalize_uniform(h, stat, int(W), 0, nch, nf, norm))) return rc;
+    rc = sl ? sliding_uniform(h, d_slide, stat, int(W), 0, nch, nf, slide_args(h))
+            : normalize_uniform(h, stat, int(W), 0, nch, nf, norm);
+    if (rc) return rc;
     if (K && (rc = deltas_uniform(h, stat, reinterpret_cast<float *>(d_full), int(W), 0, nch, nf, K, h->delta_window)))
         return rc;
-    if (K && (rc = scratch_release(h))) return rc;
+    if ((K || sl) && (rc = scratch_release(h))) return rc;
     HIP_TRY(h, hipMemcpyAsync(out, d_full, n_out * sizeof(OutT), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MFCC_HIP_SUCCESS;
@@ -1237,7 +1348,7 @@ int process_ragged_dev_static(mfcc_hip_handle *h, bool fixed, const int16_t *d_p
 template <typename OutT>
 int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
                        OutT *d_out, size_t cap, size_t *frame_offsets) {
-    if (!h || fixed || !h->delta_order || !offsets || !frame_offsets)
+    if (!h || fixed || !(h->delta_order || sliding(h)) || !offsets || !frame_offsets)
         return process_ragged_dev_static<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
     size_t total = 0;
     for (size_t u = 0; u < n_utt; ++u) {
@@ -1250,12 +1361,22 @@ int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, con
     if (total == 0 || !d_out || cap < total * out_width(h))
         return process_ragged_dev_static<OutT>(h, fixed, d_pcm, offsets, n_utt, total ? nullptr : d_out, 0, frame_offsets);
     DeviceGuard guard(h->device);
-    int rc = ensure(h, &h->d_stat, &h->d_stat_bytes, total * W * sizeof(float) + 64);
+    // with a normalization window the raw rows go to h->d_slide and the sliding pass writes the statics
+    const bool sl = sliding(h);
+    const int K = h->delta_order;
+    int rc = K ? ensure(h, &h->d_stat, &h->d_stat_bytes, total * W * sizeof(float) + 64) : MFCC_HIP_SUCCESS;
+    if (!rc && sl) rc = ensure(h, &h->d_slide, &h->d_slide_bytes, total * W * sizeof(float) + 64);
     if (rc || (rc = scratch_acquire(h))) return rc;
-    float *stat = static_cast<float *>(h->d_stat);
-    if ((rc = process_ragged_dev_static<float>(h, false, d_pcm, offsets, n_utt, stat, total * W, frame_offsets))) return rc;
-    if ((rc = deltas_segments(h, stat, reinterpret_cast<float *>(d_out), int(W), frame_offsets, n_utt, h->delta_order,
-                              h->delta_window)))
+    float *stat = K ? static_cast<float *>(h->d_stat) : reinterpret_cast<float *>(d_out);
+    if (sl) {
+        float *raw = static_cast<float *>(h->d_slide);
+        if ((rc = process_ragged_dev_raw<float>(h, false, d_pcm, offsets, n_utt, raw, total * W, frame_offsets))) return rc;
+        if ((rc = sliding_segments(h, raw, stat, int(W), frame_offsets, n_utt, slide_args(h)))) return rc;
+    } else if ((rc = process_ragged_dev_static<float>(h, false, d_pcm, offsets, n_utt, stat, total * W, frame_offsets))) {
+        return rc;
+    }
+    if (K && (rc = deltas_segments(h, stat, reinterpret_cast<float *>(d_out), int(W), frame_offsets, n_utt, K,
+                                   h->delta_window)))
         return rc;
     return scratch_release(h);
 }
@@ -1556,6 +1677,8 @@ void mfcc_hip_destroy(mfcc_hip_handle *h) {
     if (h->d_full) (void)hipFree(h->d_full);
     if (h->d_stat) (void)hipFree(h->d_stat);
     if (h->d_dtab) (void)hipFree(h->d_dtab);
+    if (h->d_slide) (void)hipFree(h->d_slide);
+    if (h->d_stab) (void)hipFree(h->d_stab);
     delete h;
 }
 
@@ -1682,6 +1805,43 @@ int mfcc_hip_normalize_dev(mfcc_hip_handle *h, void *d_rows, int row_width, cons
     if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0) return MFCC_HIP_SUCCESS;
     DeviceGuard guard(h->device);
     return normalize_segments(h, static_cast<float *>(d_rows), row_width, seg_offsets, n_segs, mode);
+}
+
+int mfcc_hip_set_normalize_window(mfcc_hip_handle *h, int window, int min_window, int center) {
+    if (!h || center < 0 || center > 1 || window < 0 || window > MFCC_HIP_MAX_NORMALIZE_WINDOW)
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (window && (min_window < 1 || min_window > window)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
+    h->norm_window = window;
+    h->norm_min_window = window ? min_window : 1;
+    h->norm_center = center;
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_normalize_sliding_dev(mfcc_hip_handle *h, const void *d_in, int row_width, void *d_out,
+                                   const size_t *seg_offsets, size_t n_segs, int mode, int window, int min_window,
+                                   int center) {
+    static_assert(MFCC_HIP_MAX_NORMALIZE_WINDOW == mfcc_slide::kMaxWindow, "window limit");
+    if (!h || mode < MFCC_HIP_NORMALIZE_NONE || mode > MFCC_HIP_NORMALIZE_MEAN_VAR) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (row_width < 1 || row_width > mfcc_slide::kMaxWidth || (n_segs && !seg_offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (window < 1 || window > MFCC_HIP_MAX_NORMALIZE_WINDOW || min_window < 1 || min_window > window || center < 0 ||
+        center > 1)
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    for (size_t k = 0; k < n_segs; ++k)
+        if (seg_offsets[k + 1] < seg_offsets[k]) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0 || seg_offsets[n_segs] == seg_offsets[0]) return MFCC_HIP_SUCCESS;
+    if (!d_in || !d_out || (reinterpret_cast<uintptr_t>(d_in) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    // the byte ranges the pass reads and writes must not overlap: a window reaches into rows already written
+    const size_t r0 = seg_offsets[0], r1 = seg_offsets[n_segs], row_bytes = size_t(row_width) * sizeof(float);
+    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(d_in) + r0 * row_bytes;
+    const uintptr_t in_hi = reinterpret_cast<uintptr_t>(d_in) + r1 * row_bytes;
+    const uintptr_t out_lo = reinterpret_cast<uintptr_t>(d_out) + r0 * row_bytes;
+    const uintptr_t out_hi = reinterpret_cast<uintptr_t>(d_out) + r1 * row_bytes;
+    if (in_lo < out_hi && out_lo < in_hi) return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    return sliding_segments(h, static_cast<const float *>(d_in), static_cast<float *>(d_out), row_width, seg_offsets,
+                            n_segs, SlideArgs{mode, window, min_window, center});
 }
 
 int mfcc_hip_set_deltas(mfcc_hip_handle *h, int order, int window) {
