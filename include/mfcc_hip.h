@@ -311,6 +311,62 @@ int  mfcc_hip_set_deltas(mfcc_hip_handle *h, int order, int window);
 int  mfcc_hip_deltas_dev(mfcc_hip_handle *h, const void *d_in, int width, void *d_out,
                          const size_t *seg_offsets, size_t n_segs, int order, int window);
 
+/* ---- energy VAD and voiced-frame selection -----------------------------------------------
+ * Kaldi's compute-vad-energy and select-voiced-frames on float rows in HBM.  A segment is one channel or one utterance
+ * of T rows; e_t is column `column` of the RAW static row of frame t -- the row the handle returns with normalization,
+ * deltas and VAD all off.  With energy_threshold (fp32, finite), energy_mean_scale (fp32, >= 0), frames_context
+ * (0..MFCC_HIP_MAX_VAD_CONTEXT) and proportion_threshold (fp32, 0 < p < 1), Kaldi's ComputeVadEnergy:
+ *     F       = the finite e_t of the segment
+ *     theta   = (double)energy_threshold + (double)energy_mean_scale * mean(F)      mean in float64; with scale 0 no mean
+ *               is taken; with scale != 0 and F empty every frame is unvoiced
+ *     above_t = isfinite(e_t) && (double)e_t > theta       a silent frame's -inf / NaN is never above and is left out of
+ *                                                          the mean, as normalization leaves it out
+ *     num     = the count of above frames over [t - ctx, t + ctx] n [0, T),  den = the size of that intersection
+ *     voiced_t = ((float)num >= (float)den * p)            one fp32 multiply
+ * The order of the mean's summation is a function of the segment's own rows and of the row width alone: the same bits
+ * from every entry point, any chunking of a host call, any run.  No atomics are used anywhere.
+ * The defaults are Kaldi's: 5.0, 0.5, 0, 0.6 -- applied in the column's OWN units.  This library's C0 is log2-based:
+ * it is Kaldi's natural-log C0 divided by ln 2 (up to the constant that power_scale adds), so a threshold taken from a
+ * Kaldi recipe converts by 1 / ln 2.  Column 0 is C0 on a cepstra handle; on a log-mel handle the caller names the band.
+ *
+ * mfcc_hip_set_vad: mode MFCC_HIP_VAD_OFF (the state after mfcc_hip_create; every entry point gives the bits it gave
+ * before this call existed) or MFCC_HIP_VAD_SELECT: the four float ragged entry points (mfcc_hip_process_ragged_i16,
+ * mfcc_hip_process_ragged_i16_dev; one utterance is a ragged call of one) return ONLY the voiced rows, packed back to
+ * back in order, and frame_offsets describes them.  out_capacity is checked against the count of ALL frames, so a caller
+ * sizes `out` as before; the device entry synchronizes the stream before it returns (frame_offsets depends on the data).
+ * The order of the passes is fixed:  MFCC kernels -> decision on the raw rows -> normalization (per segment or sliding,
+ * statistics over ALL frames of the segment: Kaldi's order) -> deltas over all frames -> selection of the final rows.
+ * A SELECT handle answers MFCC_HIP_ERROR_UNSUPPORTED to the fixed-point entry points, mfcc_hip_stream_create,
+ * mfcc_hip_convert_wav(s), the dense mfcc_hip_process_i16 / mfcc_hip_process_i16_dev and mfcc_hip_time_dev: a dense
+ * [channel][frame][W] result cannot hold rows of different counts.  NULL handle, an unknown mode, a column outside the
+ * handle's static row or a parameter outside its range (checked with either mode): MFCC_HIP_ERROR_INVALID_PARAM; live
+ * streaming sessions: MFCC_HIP_ERROR_BUSY.  The parameter block and the ABI version are unchanged.                  */
+#define MFCC_HIP_MAX_VAD_CONTEXT 64
+enum mfcc_hip_vad_mode {
+    MFCC_HIP_VAD_OFF = 0,       /* every frame is returned (the state after mfcc_hip_create) */
+    MFCC_HIP_VAD_SELECT = 1     /* the float ragged entry points return the voiced frames only */
+};
+int  mfcc_hip_set_vad(mfcc_hip_handle *h, int mode, int column, float energy_threshold, float energy_mean_scale,
+                      int frames_context, float proportion_threshold);
+/* The decision's direct entry: d_rows float32 [seg_offsets[n_segs]][row_width] (rows before seg_offsets[0] not read),
+ * d_voiced one uint8 0 / 1 per row at the same row indices; bytes outside the segments are left untouched.  Segment k =
+ * rows seg_offsets[k] .. seg_offsets[k + 1] (host array, n_segs + 1 entries, must not decrease).  row_width 1..64,
+ * column 0..row_width - 1, d_rows 4-byte aligned, the rows and the bytes must not overlap, the four parameters in the
+ * ranges above: otherwise MFCC_HIP_ERROR_INVALID_PARAM.  Asynchronous on the handle's stream; n_segs = 0 is a no-op. */
+int  mfcc_hip_vad_dev(mfcc_hip_handle *h, const void *d_rows, int row_width, int column, const size_t *seg_offsets,
+                      size_t n_segs, float energy_threshold, float energy_mean_scale, int frames_context,
+                      float proportion_threshold, void *d_voiced);
+/* The selection's direct entry: copies the rows of d_in ([seg_offsets[n_segs]][row_width] float32) whose d_voiced byte
+ * is not 0 to d_out, packed back to back from row 0 of d_out, in order; rows of d_out beyond out_offsets[n_segs] are
+ * untouched.  out_offsets (HOST array, n_segs + 1 entries) receives the row range of every segment in the packed result:
+ * this call therefore SYNCHRONIZES the handle's stream before it returns.  row_width 1..192 (three times the widest static
+ * row), both row pointers 4-byte aligned, d_out must not overlap the rows or the bytes read: otherwise
+ * MFCC_HIP_ERROR_INVALID_PARAM.  out_capacity_rows below the count of ALL rows of the segments
+ * (seg_offsets[n_segs] - seg_offsets[0]): MFCC_HIP_ERROR_BUFFER_SMALL before anything runs.  n_segs = 0 is a no-op. */
+int  mfcc_hip_select_dev(mfcc_hip_handle *h, const void *d_in, int row_width, const void *d_voiced,
+                         const size_t *seg_offsets, size_t n_segs, void *d_out, size_t out_capacity_rows,
+                         size_t *out_offsets);
+
 /* name of the kernel symbol process_*_dev launches for this handle (to match rocprofv3 rows).  A log-mel handle runs
  * the log-mel instantiation of the kernel named (the default form: MFCC_HIP_FUSED512 / MFCC_HIP_FUSED1024 do not
  * apply to it) */

@@ -39,7 +39,11 @@ NORMALIZE_NONE = 0
 NORMALIZE_MEAN = 1
 NORMALIZE_MEAN_VAR = 2
 
+VAD_OFF = 0
+VAD_SELECT = 1
+
 MAX_DELTA_WINDOW = 8
+MAX_VAD_CONTEXT = 64
 MAX_NORMALIZE_WINDOW = 16384
 
 TABLE_WINDOW_F32 = 0
@@ -115,6 +119,11 @@ SYMBOLS = {
                                                  C.c_int, C.c_int]),
     "mfcc_hip_set_deltas": (C.c_int, [_H, C.c_int, C.c_int]),
     "mfcc_hip_deltas_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _SZ, C.c_int, C.c_int]),
+    "mfcc_hip_set_vad": (C.c_int, [_H, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float]),
+    "mfcc_hip_vad_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, _SZ, C.c_float, C.c_float, C.c_int,
+                                   C.c_float, C.c_void_p]),
+    "mfcc_hip_select_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _SZ, C.c_void_p, _SZ,
+                                      C.c_void_p]),
     "mfcc_hip_convert_wav": (C.c_int, [_H, C.c_char_p, C.c_char_p, C.c_int, _PSZ]),
     "mfcc_hip_stream_create": (C.c_int, [_H, C.c_int, C.POINTER(_H)]),
     "mfcc_hip_stream_destroy": (None, [_H]),

@@ -50,6 +50,40 @@ def _delta_args(order, window, orders=(0, 1, 2)):
     return int(order), int(window)
 
 
+_VAD = {None: _lib.VAD_OFF, "off": _lib.VAD_OFF, "select": _lib.VAD_SELECT}
+
+
+def _vad_args(mode=None, column=0, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0,
+              proportion_threshold=0.6, width=None):
+    """(mode, column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold) for
+    mfcc_hip_set_vad / mfcc_hip_vad_dev, or ValueError: mode ``None`` or ``"select"``, column an int >= 0 (below
+    ``width`` when given), a finite threshold, a finite scale >= 0, context 0..64 (MFCC_HIP_MAX_VAD_CONTEXT),
+    0 < proportion < 1.  The defaults are Kaldi's compute-vad-energy."""
+    def is_int(v):
+        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+    def is_f32(v):                                  # a real number that is still finite as the float the ABI takes
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and \
+            abs(float(v)) <= float(np.finfo(np.float32).max)
+    try:
+        m = _VAD[mode]
+    except (KeyError, TypeError):
+        raise ValueError("vad must be None or 'select', not %r" % (mode,)) from None
+    if not is_int(column) or int(column) < 0 or (width is not None and int(column) >= int(width)):
+        raise ValueError("vad_column must be an int in 0..%s, not %r" % ("width - 1" if width is None else width - 1,
+                                                                         column))
+    if not is_f32(energy_threshold):
+        raise ValueError("vad_energy_threshold must be a finite number, not %r" % (energy_threshold,))
+    if not is_f32(energy_mean_scale) or energy_mean_scale < 0:
+        raise ValueError("vad_energy_mean_scale must be a finite number >= 0, not %r" % (energy_mean_scale,))
+    if not is_int(frames_context) or not 0 <= int(frames_context) <= _lib.MAX_VAD_CONTEXT:
+        raise ValueError("vad_frames_context must be 0..%d, not %r" % (_lib.MAX_VAD_CONTEXT, frames_context))
+    if not is_f32(proportion_threshold) or not 0.0 < float(np.float32(proportion_threshold)) < 1.0:
+        raise ValueError("vad_proportion_threshold must lie strictly between 0 and 1, not %r" % (proportion_threshold,))
+    return (m, int(column), float(energy_threshold), float(energy_mean_scale), int(frames_context),
+            float(proportion_threshold))
+
+
 _MIN_WINDOW = 100                  # default minimum window of the causal form (Kaldi's --min-cmn-window)
 
 
@@ -151,19 +185,31 @@ class MFCC:
     ``delta_window`` frames on each side (1..8, default 2; HTK's regression formula, indices clamped to the channel /
     utterance).  The static part is what the handle returns with deltas off, normalization included, and
     :attr:`num_features` counts the expanded width.  The same entry points as normalization refuse such a handle.
+
+    ``vad="select"`` drops the frames an energy VAD calls unvoiced (Kaldi's compute-vad-energy and select-voiced-frames:
+    ``vad_energy_threshold + vad_energy_mean_scale * mean`` of column ``vad_column`` of the raw rows, then at least
+    ``vad_proportion_threshold`` of the frames within ``vad_frames_context`` above it; the thresholds are in this
+    library's log2 units, a Kaldi value times ``1 / ln 2``).  Normalization and deltas still see every frame; the rows
+    that come back are the voiced ones.  ``process`` then takes ONE utterance and returns ``(voiced, num_features)``;
+    ``process_batch`` / ``process_packed`` return the shorter utterances; everything that returns a dense
+    ``(channels, frames, ...)`` result, ``process_fixed``, :meth:`stream` and ``convert*`` raise ``UNSUPPORTED``.
     """
 
     deltas, delta_window = 0, 2                 # the state after mfcc_hip_create
+    vad = None
 
     def __init__(self, width=16, nfft=512, samplerate=16e3, nfilters=16, nceptrums=16, *, hop=None,
                  pad_mode="notebook", power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra",
                  normalize=None, deltas=0, delta_window=2, normalize_window=None, normalize_min_window=_MIN_WINDOW,
-                 normalize_center=True):
+                 normalize_center=True, vad=None, vad_column=0, vad_energy_threshold=5.0, vad_energy_mean_scale=0.5,
+                 vad_frames_context=0, vad_proportion_threshold=0.6):
         if width != 16:
             raise ValueError("only width=16 (int16 PCM) is supported, like every reference target")
         norm = normalize_mode(normalize)
         _window_args(normalize_window, normalize_min_window, normalize_center)
         order, window = _delta_args(deltas, delta_window)
+        vad_args = _vad_args(vad, vad_column, vad_energy_threshold, vad_energy_mean_scale, vad_frames_context,
+                             vad_proportion_threshold)
         self.width = width
         self.nfft = int(nfft)
         self.samplerate = samplerate
@@ -196,6 +242,91 @@ class MFCC:
         self.normalize_window, self.normalize_min_window, self.normalize_center = None, _MIN_WINDOW, True
         if normalize_window is not None:
             self.set_normalize_window(normalize_window, normalize_min_window, normalize_center)
+        self.vad = None
+        (self.vad_column, self.vad_energy_threshold, self.vad_energy_mean_scale, self.vad_frames_context,
+         self.vad_proportion_threshold) = _vad_args()[1:]
+        if vad_args[0] != _lib.VAD_OFF:
+            self.set_vad(vad, vad_column, vad_energy_threshold, vad_energy_mean_scale, vad_frames_context,
+                         vad_proportion_threshold)
+
+    def set_vad(self, mode, column=0, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0,
+                proportion_threshold=0.6):
+        """The handle's frame selection for every float call after this one: ``None`` (every frame) or ``"select"``
+        (the voiced frames only, by Kaldi's energy rule on column ``column`` of the raw rows)."""
+        a = _vad_args(mode, column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold)
+        _lib.check(self._lib.mfcc_hip_set_vad(self._h, *a), "set_vad")
+        self.vad = "select" if a[0] == _lib.VAD_SELECT else None
+        (self.vad_column, self.vad_energy_threshold, self.vad_energy_mean_scale, self.vad_frames_context,
+         self.vad_proportion_threshold) = a[1:]
+
+    def _segments(self, rows, frame_offsets):
+        """The checks :meth:`normalize_rows` makes on ``rows`` and the segment offsets as a uint64 array."""
+        import torch
+        if rows.dtype != torch.float32 or not rows.is_cuda or not rows.is_contiguous() or rows.dim() not in (2, 3):
+            raise TypeError("rows must be a contiguous 2-D or 3-D CUDA(HIP) float32 tensor")
+        width = int(rows.shape[-1])
+        if frame_offsets is None:
+            nseg = int(rows.shape[0]) if rows.dim() == 3 else 1
+            per = int(rows.shape[1]) if rows.dim() == 3 else int(rows.shape[0])
+            return np.arange(nseg + 1, dtype=np.uint64) * np.uint64(per)
+        fo = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
+        if fo.ndim != 1 or len(fo) < 1:
+            raise ValueError("frame_offsets must be 1-D with n_segments + 1 entries")
+        if len(fo) > 1 and int(fo[-1]) * width > rows.numel():
+            raise ValueError("frame_offsets run past the end of rows")
+        return fo
+
+    def vad_rows(self, rows, frame_offsets=None, column=0, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0,
+                 proportion_threshold=0.6, out=None):
+        """The energy VAD decision on a CUDA float32 tensor of RAW static rows, on the current torch stream: a uint8
+        tensor of ``rows.shape[:-1]``, 1 where the frame is voiced.  ``rows`` and the segments as in
+        :meth:`normalize_rows`; ``width`` 1..64, independent of this handle's own rows.  Entries of ``out`` outside the
+        segments are left as they are (0 in a tensor made here)."""
+        import torch
+        fo = self._segments(rows, frame_offsets)
+        width = int(rows.shape[-1])
+        a = _vad_args("select", column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold,
+                      width=width)
+        want = tuple(rows.shape[:-1])
+        if out is None:
+            out = torch.zeros(want, device=rows.device, dtype=torch.uint8) if frame_offsets is not None else \
+                torch.empty(want, device=rows.device, dtype=torch.uint8)
+        elif tuple(out.shape) != want or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != rows.device:
+            raise ValueError("out must be a contiguous uint8 tensor of shape %s on %s" % (want, rows.device))
+        self._check_device(rows)
+        with self._on_torch_stream(rows.device):
+            _lib.check(self._lib.mfcc_hip_vad_dev(self._h, C.c_void_p(rows.data_ptr()), width, a[1],
+                                                  fo.ctypes.data_as(C.c_void_p), len(fo) - 1, a[2], a[3], a[4], a[5],
+                                                  C.c_void_p(out.data_ptr())), "vad_dev")
+        return out
+
+    def select_rows(self, rows, voiced, frame_offsets=None, out=None):
+        """The rows of a CUDA float32 tensor whose ``voiced`` byte (uint8 tensor of ``rows.shape[:-1]``, e.g. from
+        :meth:`vad_rows`) is not 0, packed in order: returns ``(out[:total], offsets)`` with segment ``u`` of the result
+        in rows ``offsets[u]:offsets[u + 1]``.  ``rows`` and the segments as in :meth:`normalize_rows`, ``width``
+        1..192.  ``out``: a ``(capacity, width)`` tensor with room for EVERY row of the segments; its rows beyond the
+        total are left as they are.  Waits for the stream: the offsets depend on the data."""
+        import torch
+        fo = self._segments(rows, frame_offsets)
+        width = int(rows.shape[-1])
+        if voiced.dtype != torch.uint8 or not voiced.is_contiguous() or voiced.device != rows.device or \
+                tuple(voiced.shape) != tuple(rows.shape[:-1]):
+            raise ValueError("voiced must be a contiguous uint8 tensor of shape %s on %s"
+                             % (tuple(rows.shape[:-1]), rows.device))
+        need = int(fo[-1]) - int(fo[0])
+        if out is None:
+            out = torch.empty((need, width), device=rows.device, dtype=torch.float32)
+        elif out.dim() != 2 or int(out.shape[1]) != width or out.dtype != torch.float32 or not out.is_contiguous() or \
+                out.device != rows.device:
+            raise ValueError("out must be a contiguous float32 tensor of shape (capacity, %d) on %s" % (width, rows.device))
+        self._check_device(rows)
+        oo = np.zeros(len(fo), dtype=np.uint64)
+        with self._on_torch_stream(rows.device):
+            _lib.check(self._lib.mfcc_hip_select_dev(self._h, C.c_void_p(rows.data_ptr()), width,
+                                                     C.c_void_p(voiced.data_ptr()), fo.ctypes.data_as(C.c_void_p),
+                                                     len(fo) - 1, C.c_void_p(out.data_ptr()), int(out.shape[0]),
+                                                     oo.ctypes.data_as(C.c_void_p)), "select_dev")
+        return out[:int(oo[-1])], oo
 
     def set_normalize_window(self, window, min_window=_MIN_WINDOW, center=True):
         """The window of the handle's normalization for every float call after this one: ``None`` (statistics over
@@ -363,7 +494,7 @@ class MFCC:
         got = C.c_size_t(0)
         fn = self._lib.mfcc_hip_process_fixed_i16 if fixed else self._lib.mfcc_hip_process_i16
         _lib.check(fn(self._h, pcm.ctypes.data, n, nch, out.ctypes.data, out.size, C.byref(got)),
-                   "process")
+                   "process" if not self.vad else self._DENSE_VAD)
         assert got.value == nf
         return out[0] if squeeze else out
 
@@ -395,10 +526,13 @@ class MFCC:
         got = C.c_size_t(0)
         with self._on_torch_stream(pcm.device):
             _lib.check(fn(self._h, C.c_void_p(pcm.data_ptr()), n, pcm.stride(0), nch, int(halo),
-                          C.c_void_p(out.data_ptr()), C.byref(got)), "process_dev")
+                          C.c_void_p(out.data_ptr()), C.byref(got)), "process_dev" if not self.vad else self._DENSE_VAD)
         if squeeze and out.dim() == 3:
             return out[0]
         return out
+
+    _DENSE_VAD = ("process: a vad='select' handle returns a different number of rows per channel; pass one 1-D "
+                  "utterance, or use process_batch / process_packed")
 
     def _check_device(self, t):
         """The handle's tables, stream and scratch live on ONE GPU: refuse tensors of another one."""
@@ -426,7 +560,11 @@ class MFCC:
     def process(self, pcm, halo=0, out=None):
         """Float contract: int16 PCM ``(n,)`` / ``(channels, n)`` -> float32 ``(.., frames, num_features)``.
         NumPy in -> NumPy out (H2D, kernel, D2H); torch CUDA tensor in -> torch tensor out, asynchronous
-        on the current stream.  ``halo=1`` (device path): sample 0 of every channel is history only."""
+        on the current stream.  ``halo=1`` (device path): sample 0 of every channel is history only.
+        On a ``vad="select"`` handle a 1-D input goes through the ragged entry as one utterance and comes back as
+        ``(voiced, num_features)``; a 2-D one raises ``UNSUPPORTED``."""
+        if self.vad and (pcm.dim() if _is_torch(pcm) else np.ndim(pcm)) == 1 and not halo and out is None:
+            return self.process_batch([pcm])[0]
         if _is_torch(pcm):
             return self._dev(pcm, False, halo, out)
         if halo:
@@ -460,7 +598,7 @@ class MFCC:
         fn = self._lib.mfcc_hip_process_ragged_fixed_i16 if fixed else self._lib.mfcc_hip_process_ragged_i16
         _lib.check(fn(self._h, flat.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), n,
                       out.ctypes.data_as(C.c_void_p), out.size, fo.ctypes.data_as(C.c_void_p)), "process_ragged")
-        assert int(fo[-1]) == nf
+        assert int(fo[-1]) == nf or (self.vad and not fixed and int(fo[-1]) <= nf)
         return [out[int(fo[i]):int(fo[i + 1])] for i in range(n)]
 
     def _batch_dev(self, utterances, fixed):
@@ -489,7 +627,8 @@ class MFCC:
         utterance ``u`` = ``flat[offsets[u]:offsets[u + 1]]``.  ONE launch (``mfcc_hip_process_ragged_*_dev``),
         asynchronous on the current stream.  Returns ``(out, frame_offsets)``: the dense ``(sum frames, num_features)``
         result tensor and the row range of every utterance (``out[fo[u]:fo[u + 1]]``).  Equal-length utterances run
-        as channels of one multi-channel launch (no packing copy); the bits are the same."""
+        as channels of one multi-channel launch (no packing copy); the bits are the same.  On a ``vad="select"`` handle
+        ``out`` still needs room for every frame; what is returned is ``(out[:fo[-1]], fo)``, the voiced rows."""
         import torch
         if flat.dtype != torch.int16 or not flat.is_cuda or flat.dim() != 1 or not flat.is_contiguous():
             raise TypeError("flat must be a contiguous 1-D CUDA(HIP) int16 tensor")
@@ -519,6 +658,8 @@ class MFCC:
         with self._on_torch_stream(flat.device):
             _lib.check(fn(self._h, C.c_void_p(flat.data_ptr()), offsets.ctypes.data_as(C.c_void_p), n,
                           C.c_void_p(out.data_ptr()), out.numel(), fo.ctypes.data_as(C.c_void_p)), "process_ragged_dev")
+        if self.vad and not fixed:
+            return out[:int(fo[-1])], fo                 # the voiced rows; the entry point has waited for the stream
         assert int(fo[-1]) == nf
         return out, fo
 

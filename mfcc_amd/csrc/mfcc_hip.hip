@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <string>
@@ -26,6 +27,7 @@
 #include "kernel_normalize.hpp"
 #include "kernel_deltas.hpp"
 #include "kernel_normalize_sliding.hpp"
+#include "kernel_vad.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -197,6 +199,21 @@ struct mfcc_hip_handle {
     size_t d_slide_bytes = 0;
     void *d_stab = nullptr;
     size_t d_stab_bytes = 0;
+    // energy VAD (mfcc_hip_set_vad): the mode and the rule's parameters; the decision's scratch (d_vad: tile partials,
+    // thresholds, tile table), the mask (d_voiced), the selection's scratch (d_sel: tile counts, prefixes, segment
+    // offsets, tile table) and the final rows of a SELECT call before the gather moves them to the caller (d_final)
+    int vad_mode = MFCC_HIP_VAD_OFF;
+    int vad_column = 0;
+    int vad_context = 0;
+    float vad_threshold = 5.0f, vad_scale = 0.5f, vad_proportion = 0.6f;
+    void *d_vad = nullptr;
+    size_t d_vad_bytes = 0;
+    void *d_voiced = nullptr;
+    size_t d_voiced_bytes = 0;
+    void *d_sel = nullptr;
+    size_t d_sel_bytes = 0;
+    void *d_final = nullptr;
+    size_t d_final_bytes = 0;
 };
 
 namespace {
@@ -801,6 +818,183 @@ int sliding_segments(mfcc_hip_handle *h, const float *d_in, float *d_out, int wi
     return MFCC_HIP_SUCCESS;
 }
 
+// ---- energy VAD and voiced-row selection (kernel_vad.hpp).  The decision reads one column of
+// the raw rows and writes a byte per row; the selection packs the rows whose byte is set.  Both work on tiles of the
+// SAME plan when a handle with MFCC_HIP_VAD_SELECT runs them (the decision's tile counts feed the selection's prefix sum);
+// the direct entries each make their own.
+struct VadArgs {
+    int column;
+    float threshold, scale;
+    int context;
+    float proportion;
+};
+
+inline VadArgs vad_args(const mfcc_hip_handle *h) {
+    return VadArgs{h->vad_column, h->vad_threshold, h->vad_scale, h->vad_context, h->vad_proportion};
+}
+
+inline bool vad_args_ok(int width, int column, float threshold, float scale, int context, float proportion) {
+    return column >= 0 && column < width && std::isfinite(threshold) && std::isfinite(scale) && scale >= 0.0f &&
+           context >= 0 && context <= MFCC_HIP_MAX_VAD_CONTEXT && proportion > 0.0f && proportion < 1.0f;
+}
+
+inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
+
+// The tiles of tr rows of segments off[0 .. n_segs] (off does not decrease, off[n_segs] > off[0]): the uniform form of Segs
+// when every segment has one length, else the table form, built in pinned memory (pd; table_ll long longs) and not yet on
+// the device (vad_table_upload)
+int vad_segs(mfcc_hip_handle *h, const size_t *off, size_t n_segs, int width, size_t tr, mfcc_norm::Segs &s,
+             size_t &table_ll, mfcc_hip_handle::PinnedDesc *&pd) {
+    s = mfcc_norm::Segs{};
+    s.width = width;
+    s.tile_rows = int(tr);
+    s.n_segs = (long long)n_segs;
+    table_ll = 0;
+    pd = nullptr;
+    const size_t len0 = off[1] - off[0];
+    bool uniform = true;
+    for (size_t k = 1; k < n_segs && uniform; ++k) uniform = off[k + 1] - off[k] == len0;
+    if (uniform) {
+        s.base_row = (long long)off[0];
+        s.seg_rows = (long long)len0;
+        s.blocks_per_seg = (long long)((len0 + tr - 1) / tr);
+        s.n_blocks = s.blocks_per_seg * s.n_segs;
+        return MFCC_HIP_SUCCESS;
+    }
+    size_t n_blocks = 0;
+    for (size_t k = 0; k < n_segs; ++k) n_blocks += (off[k + 1] - off[k] + tr - 1) / tr;
+    if (n_segs >= (size_t(1) << 31)) return MFCC_HIP_ERROR_INVALID_PARAM;       // BlockRec::seg is an int
+    table_ll = n_segs + 1 + 2 * n_blocks;
+    const int rc = desc_acquire(h, table_ll, &pd);
+    if (rc) return rc;
+    long long *blk0 = pd->p;
+    auto *rec = reinterpret_cast<mfcc_norm::BlockRec *>(pd->p + n_segs + 1);
+    size_t b = 0;
+    for (size_t k = 0; k < n_segs; ++k) {
+        blk0[k] = (long long)b;
+        for (size_t r = off[k]; r < off[k + 1]; r += tr)
+            rec[b++] = mfcc_norm::BlockRec{(long long)r, int(std::min(tr, off[k + 1] - r)), int(k)};
+    }
+    blk0[n_segs] = (long long)b;
+    s.n_blocks = (long long)n_blocks;
+    return MFCC_HIP_SUCCESS;
+}
+
+int vad_table_upload(mfcc_hip_handle *h, mfcc_norm::Segs &s, size_t table_ll, mfcc_hip_handle::PinnedDesc *pd,
+                     long long *d_table) {
+    if (!pd) return MFCC_HIP_SUCCESS;
+    HIP_TRY(h, hipMemcpyAsync(d_table, pd->p, table_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    s.seg_blk0 = d_table;
+    s.blk = reinterpret_cast<const mfcc_norm::BlockRec *>(d_table + s.n_segs + 1);
+    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
+    pd->in_flight = true;
+    return MFCC_HIP_SUCCESS;
+}
+
+// the tiles of a selection and its scratch in h->d_sel: [tile counts][tile prefixes (n_blocks + 1)][segment offsets
+// (n_segs + 1)][tile table]
+struct SelPlan {
+    mfcc_norm::Segs s;
+    unsigned *counts;
+    long long *tile_off, *seg_off;
+};
+
+int select_plan(mfcc_hip_handle *h, const size_t *off, size_t n_segs, int tile_width, SelPlan &pl) {
+    size_t table_ll = 0;
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    int rc = vad_segs(h, off, n_segs, tile_width, size_t(mfcc_vad::select_tile_rows(tile_width)), pl.s, table_ll, pd);
+    if (rc) return rc;
+    const size_t nb = size_t(pl.s.n_blocks);
+    const size_t cnt_b = up256(nb * sizeof(unsigned)), toff_b = up256((nb + 1) * sizeof(long long));
+    const size_t soff_b = up256((n_segs + 1) * sizeof(long long));
+    if ((rc = ensure(h, &h->d_sel, &h->d_sel_bytes, cnt_b + toff_b + soff_b + table_ll * sizeof(long long) + 64))) return rc;
+    if ((rc = scratch_acquire(h))) return rc;
+    char *base = static_cast<char *>(h->d_sel);
+    pl.counts = reinterpret_cast<unsigned *>(base);
+    pl.tile_off = reinterpret_cast<long long *>(base + cnt_b);
+    pl.seg_off = reinterpret_cast<long long *>(base + cnt_b + toff_b);
+    return vad_table_upload(h, pl.s, table_ll, pd, reinterpret_cast<long long *>(base + cnt_b + toff_b + soff_b));
+}
+
+// the decision on column a.column of rows [..][W], on the tiles of pl (whose counts it fills).  Scratch (h->d_vad):
+// [tile partials of the mean][theta per segment][tile table of the mean]
+int vad_decide(mfcc_hip_handle *h, const float *d_rows, int W, const size_t *off, size_t n_segs, VadArgs a,
+               unsigned char *d_voiced, const SelPlan &pl) {
+    const double *theta = nullptr;
+    int rc;
+    if (a.scale != 0.0f) {
+        mfcc_norm::Segs sm;
+        size_t table_ll = 0;
+        mfcc_hip_handle::PinnedDesc *pd = nullptr;
+        if ((rc = vad_segs(h, off, n_segs, W, size_t(mfcc_vad::kMeanTileRows), sm, table_ll, pd))) return rc;
+        const size_t part_b = up256(size_t(sm.n_blocks) * sizeof(mfcc_vad::MeanPart)), theta_b = up256(n_segs * sizeof(double));
+        if ((rc = ensure(h, &h->d_vad, &h->d_vad_bytes, part_b + theta_b + table_ll * sizeof(long long) + 64))) return rc;
+        char *base = static_cast<char *>(h->d_vad);
+        auto *part = reinterpret_cast<mfcc_vad::MeanPart *>(base);
+        double *th = reinterpret_cast<double *>(base + part_b);
+        if ((rc = vad_table_upload(h, sm, table_ll, pd, reinterpret_cast<long long *>(base + part_b + theta_b)))) return rc;
+        hipLaunchKernelGGL(mfcc_vad::vad_mean_kernel, dim3(unsigned(std::min<long long>(sm.n_blocks, 1 << 20))),
+                           dim3(mfcc_vad::kThreads), 0, h->stream, d_rows, sm, a.column, part);
+        hipLaunchKernelGGL(mfcc_vad::vad_theta_kernel, dim3(unsigned(std::min<long long>(sm.n_segs, 1 << 20))),
+                           dim3(mfcc_vad::kThreads), 0, h->stream, sm, static_cast<const mfcc_vad::MeanPart *>(part),
+                           double(a.threshold), double(a.scale), th);
+        theta = th;
+    }
+    mfcc_norm::Segs sd = pl.s;
+    sd.width = W;
+    hipLaunchKernelGGL(mfcc_vad::vad_decide_kernel, dim3(unsigned(std::min<long long>(sd.n_blocks, 1 << 20))),
+                       dim3(mfcc_vad::kThreads), 0, h->stream, d_rows, sd, a.column, theta, double(a.threshold), a.context,
+                       a.proportion, d_voiced, pl.counts);
+    HIP_TRY(h, hipGetLastError());
+    return MFCC_HIP_SUCCESS;
+}
+
+// the selection on the tiles of pl (made for rows of Wp floats): [count,] scan, gather, then the segment offsets to the
+// host -- which is why this synchronizes the stream
+int select_run(mfcc_hip_handle *h, const float *d_in, int Wp, const unsigned char *d_voiced, const SelPlan &pl, bool counted,
+               float *d_out, size_t *out_offsets) {
+    mfcc_norm::Segs s = pl.s;
+    s.width = Wp;
+    const unsigned grid = unsigned(std::min<long long>(s.n_blocks, 1 << 20));
+    if (!counted)
+        hipLaunchKernelGGL(mfcc_vad::vad_count_kernel, dim3(grid), dim3(mfcc_vad::kThreads), 0, h->stream, d_voiced, s,
+                           pl.counts);
+    hipLaunchKernelGGL(mfcc_vad::vad_scan_kernel, dim3(1), dim3(mfcc_vad::kScanThreads), 0, h->stream, s,
+                       static_cast<const unsigned *>(pl.counts), pl.tile_off, pl.seg_off);
+    hipLaunchKernelGGL(mfcc_vad::vad_gather_kernel, dim3(grid), dim3(mfcc_vad::kThreads), 0, h->stream, d_in, d_voiced, s,
+                       static_cast<const long long *>(pl.tile_off), d_out);
+    HIP_TRY(h, hipGetLastError());
+    static_assert(sizeof(size_t) == sizeof(long long), "segment offsets are copied as they are");
+    HIP_TRY(h, hipMemcpyAsync(out_offsets, pl.seg_off, size_t(s.n_segs + 1) * sizeof(long long), hipMemcpyDeviceToHost,
+                              h->stream));
+    const int rc = scratch_release(h);
+    if (rc) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MFCC_HIP_SUCCESS;
+}
+
+// segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
+int vad_segments(mfcc_hip_handle *h, const float *d_rows, int W, const size_t *off, size_t n_segs, VadArgs a,
+                 unsigned char *d_voiced) {
+    if (n_segs == 0 || off[n_segs] == off[0]) return MFCC_HIP_SUCCESS;
+    SelPlan pl;
+    int rc = select_plan(h, off, n_segs, 1, pl);           // tiles of kMaxTileRows rows
+    if (rc || (rc = vad_decide(h, d_rows, W, off, n_segs, a, d_voiced, pl))) return rc;
+    return scratch_release(h);
+}
+
+int select_segments(mfcc_hip_handle *h, const float *d_in, int Wp, const unsigned char *d_voiced, const size_t *off,
+                    size_t n_segs, float *d_out, size_t *out_offsets) {
+    if (n_segs == 0 || off[n_segs] == off[0]) {
+        for (size_t k = 0; k <= n_segs && out_offsets; ++k) out_offsets[k] = 0;
+        return MFCC_HIP_SUCCESS;
+    }
+    SelPlan pl;
+    const int rc = select_plan(h, off, n_segs, Wp, pl);
+    if (rc) return rc;
+    return select_run(h, d_in, Wp, d_voiced, pl, false, d_out, out_offsets);
+}
+
 // width of a float output row of this handle: the static row, times 1 + the delta order
 inline size_t out_width(const mfcc_hip_handle *h) { return row_width(h->r) * size_t(1 + h->delta_order); }
 
@@ -1344,10 +1538,49 @@ int process_ragged_dev_static(mfcc_hip_handle *h, bool fixed, const int16_t *d_p
     return normalize_segments(h, reinterpret_cast<float *>(d_out), int(row_width(h->r)), frame_offsets, n_utt, h->norm);
 }
 
+// ... and with MFCC_HIP_VAD_SELECT: the kernels, the decision on the raw rows, normalization and deltas over ALL frames
+// into h->d_final, then only the voiced rows to d_out; frame_offsets describes those.  Synchronizes (select_run)
+int process_ragged_dev_select(mfcc_hip_handle *h, const int16_t *d_pcm, const size_t *offsets, size_t n_utt, float *d_out,
+                              size_t cap, size_t *frame_offsets) {
+    size_t total = 0;
+    for (size_t u = 0; u < n_utt; ++u) {
+        if (offsets[u + 1] < offsets[u])            // refused by the call below
+            return process_ragged_dev_static<float>(h, false, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
+        total += count_frames(h->r, offsets[u + 1] - offsets[u]);
+    }
+    const size_t W = row_width(h->r), WO = out_width(h);
+    // nothing to write, or a buffer too small for every frame: the static call fills frame_offsets and gives the answer
+    if (total == 0 || !d_out || cap < total * WO)
+        return process_ragged_dev_static<float>(h, false, d_pcm, offsets, n_utt, total ? nullptr : d_out, 0, frame_offsets);
+    DeviceGuard guard(h->device);
+    const bool sl = sliding(h);
+    const int K = h->delta_order;
+    int rc = ensure(h, &h->d_final, &h->d_final_bytes, total * WO * sizeof(float) + 64);
+    if (!rc) rc = ensure(h, &h->d_voiced, &h->d_voiced_bytes, total + 64);
+    if (!rc && K) rc = ensure(h, &h->d_stat, &h->d_stat_bytes, total * W * sizeof(float) + 64);
+    if (!rc && sl) rc = ensure(h, &h->d_slide, &h->d_slide_bytes, total * W * sizeof(float) + 64);
+    if (rc || (rc = scratch_acquire(h))) return rc;
+    float *fin = static_cast<float *>(h->d_final);
+    float *stat = K ? static_cast<float *>(h->d_stat) : fin;
+    float *raw = sl ? static_cast<float *>(h->d_slide) : stat;
+    unsigned char *voiced = static_cast<unsigned char *>(h->d_voiced);
+    if ((rc = process_ragged_dev_raw<float>(h, false, d_pcm, offsets, n_utt, raw, total * W, frame_offsets))) return rc;
+    SelPlan pl;
+    if ((rc = select_plan(h, frame_offsets, n_utt, int(WO), pl))) return rc;
+    if ((rc = vad_decide(h, raw, int(W), frame_offsets, n_utt, vad_args(h), voiced, pl))) return rc;
+    rc = sl ? sliding_segments(h, raw, stat, int(W), frame_offsets, n_utt, slide_args(h))
+            : normalize_segments(h, stat, int(W), frame_offsets, n_utt, h->norm);
+    if (rc) return rc;
+    if (K && (rc = deltas_segments(h, stat, fin, int(W), frame_offsets, n_utt, K, h->delta_window))) return rc;
+    return select_run(h, fin, int(WO), voiced, pl, true, d_out, frame_offsets);
+}
+
 // ... and with deltas: the static rows go to h->d_stat, then the expanded rows to d_out, one segment per utterance
 template <typename OutT>
 int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
                        OutT *d_out, size_t cap, size_t *frame_offsets) {
+    if (h && !fixed && h->vad_mode && offsets && frame_offsets && std::is_same<OutT, float>::value)
+        return process_ragged_dev_select(h, d_pcm, offsets, n_utt, reinterpret_cast<float *>(d_out), cap, frame_offsets);
     if (!h || fixed || !(h->delta_order || sliding(h)) || !offsets || !frame_offsets)
         return process_ragged_dev_static<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
     size_t total = 0;
@@ -1432,6 +1665,10 @@ int process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const siz
     }
     frame_offsets[0] = 0;
     std::vector<size_t> loc, fo;
+    // MFCC_HIP_VAD_SELECT: every chunk returns its voiced rows only (the call below synchronizes and reports them), so its
+    // copy back shrinks and lands behind the voiced rows of the chunks before it
+    const bool sel_mode = !fixed && h->vad_mode;
+    size_t sel_rows = 0;
     return run_host_pipeline(h, pc, pcm + offsets[0], rel[n_utt] * sizeof(int16_t), out, total * ncep * sizeof(OutT),
                              [&](size_t i, void *d_in, void *d_out) {
         const Range &r = ranges[i];
@@ -1441,7 +1678,13 @@ int process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const siz
         for (size_t j = 0; j <= k; ++j) loc[j] = rel[r.u0 + j] - rel[r.u0];
         const int rc = process_ragged_dev<OutT>(h, fixed, static_cast<const int16_t *>(d_in), loc.data(), k,
                                                 static_cast<OutT *>(d_out), pc[i].out_bytes / sizeof(OutT), fo.data());
-        for (size_t j = 1; j <= k; ++j) frame_offsets[r.u0 + j] = r.rows0 + fo[j];
+        const size_t rows0 = sel_mode ? sel_rows : r.rows0;
+        for (size_t j = 1; j <= k; ++j) frame_offsets[r.u0 + j] = rows0 + fo[j];
+        if (sel_mode && !rc) {
+            pc[i].out = out + rows0 * ncep;
+            pc[i].out_bytes = fo[k] * ncep * sizeof(OutT);
+            sel_rows += fo[k];
+        }
         return rc;
     });
 }
@@ -1679,6 +1922,10 @@ void mfcc_hip_destroy(mfcc_hip_handle *h) {
     if (h->d_dtab) (void)hipFree(h->d_dtab);
     if (h->d_slide) (void)hipFree(h->d_slide);
     if (h->d_stab) (void)hipFree(h->d_stab);
+    if (h->d_vad) (void)hipFree(h->d_vad);
+    if (h->d_voiced) (void)hipFree(h->d_voiced);
+    if (h->d_sel) (void)hipFree(h->d_sel);
+    if (h->d_final) (void)hipFree(h->d_final);
     delete h;
 }
 
@@ -1702,6 +1949,7 @@ int mfcc_hip_synchronize(mfcc_hip_handle *h) {
 
 int mfcc_hip_process_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_t nch, float *out,
                          size_t cap, size_t *n_frames) {
+    if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;   // a dense result cannot hold rows of different counts
     return process_host<float>(h, false, pcm, n, nch, out, cap, n_frames);
 }
 
@@ -1709,6 +1957,7 @@ int mfcc_hip_process_fixed_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n,
                                int16_t *out, size_t cap, size_t *n_frames) {
     if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
     if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
+    if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... nor frame selection
     return process_host<int16_t>(h, true, pcm, n, nch, out, cap, n_frames);
 }
 
@@ -1721,6 +1970,7 @@ int mfcc_hip_process_ragged_fixed_i16(mfcc_hip_handle *h, const int16_t *pcm, co
                                       int16_t *out, size_t cap, size_t *frame_offsets) {
     if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
     if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
+    if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... nor frame selection
     return process_ragged<int16_t>(h, true, pcm, offsets, n_utt, out, cap, frame_offsets);
 }
 
@@ -1734,12 +1984,14 @@ int mfcc_hip_process_ragged_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm,
                                           void *d_out, size_t cap, size_t *frame_offsets) {
     if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
     if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
+    if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... nor frame selection
     return process_ragged_dev<int16_t>(h, true, static_cast<const int16_t *>(d_pcm), offsets, n_utt,
                                        static_cast<int16_t *>(d_out), cap, frame_offsets);
 }
 
 int mfcc_hip_process_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch,
                              int halo, void *d_out, size_t *n_frames) {
+    if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;   // a dense result cannot hold rows of different counts
     return launch_float_dev(h, d_pcm, n, stride, nch, halo, d_out, n_frames);
 }
 
@@ -1747,6 +1999,7 @@ int mfcc_hip_process_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t
                                    size_t nch, int halo, void *d_out, size_t *n_frames) {
     if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
     if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
+    if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... nor frame selection
     return launch(h, true, d_pcm, n, stride, nch, halo, d_out, n_frames);
 }
 
@@ -1754,6 +2007,7 @@ int mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n
                       size_t nch, void *d_out, int warmup, int iters, float *avg_ms) {
     if (!h || iters < 1 || warmup < 0 || !avg_ms) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (fixed && (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;        // a dense result cannot hold rows of different counts
     DeviceGuard guard(h->device);
     // what process_*_dev enqueues: with normalization or deltas on, the float launch and the passes behind it
     auto once = [&]() {
@@ -1875,6 +2129,67 @@ int mfcc_hip_deltas_dev(mfcc_hip_handle *h, const void *d_in, int width, void *d
                            order, window);
 }
 
+int mfcc_hip_set_vad(mfcc_hip_handle *h, int mode, int column, float energy_threshold, float energy_mean_scale,
+                     int frames_context, float proportion_threshold) {
+    static_assert(MFCC_HIP_MAX_VAD_CONTEXT == mfcc_vad::kMaxContext, "context limit");
+    if (!h || mode < MFCC_HIP_VAD_OFF || mode > MFCC_HIP_VAD_SELECT) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!vad_args_ok(int(row_width(h->r)), column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
+    h->vad_mode = mode;
+    h->vad_column = column;
+    h->vad_threshold = energy_threshold;
+    h->vad_scale = energy_mean_scale;
+    h->vad_context = frames_context;
+    h->vad_proportion = proportion_threshold;
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_vad_dev(mfcc_hip_handle *h, const void *d_rows, int row_width, int column, const size_t *seg_offsets,
+                     size_t n_segs, float energy_threshold, float energy_mean_scale, int frames_context,
+                     float proportion_threshold, void *d_voiced) {
+    if (!h || row_width < 1 || row_width > mfcc_vad::kMaxWidth || (n_segs && !seg_offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!vad_args_ok(row_width, column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    for (size_t k = 0; k < n_segs; ++k)
+        if (seg_offsets[k + 1] < seg_offsets[k]) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (n_segs == 0 || seg_offsets[n_segs] == seg_offsets[0]) return MFCC_HIP_SUCCESS;
+    if (!d_rows || !d_voiced || (reinterpret_cast<uintptr_t>(d_rows) & 3)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    // the rows read and the bytes written must not overlap
+    const size_t r0 = seg_offsets[0], r1 = seg_offsets[n_segs], row_bytes = size_t(row_width) * sizeof(float);
+    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(d_rows) + r0 * row_bytes;
+    const uintptr_t in_hi = reinterpret_cast<uintptr_t>(d_rows) + r1 * row_bytes;
+    const uintptr_t out_lo = reinterpret_cast<uintptr_t>(d_voiced) + r0, out_hi = reinterpret_cast<uintptr_t>(d_voiced) + r1;
+    if (in_lo < out_hi && out_lo < in_hi) return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    return vad_segments(h, static_cast<const float *>(d_rows), row_width, seg_offsets, n_segs,
+                        VadArgs{column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold},
+                        static_cast<unsigned char *>(d_voiced));
+}
+
+int mfcc_hip_select_dev(mfcc_hip_handle *h, const void *d_in, int row_width, const void *d_voiced, const size_t *seg_offsets,
+                        size_t n_segs, void *d_out, size_t out_capacity_rows, size_t *out_offsets) {
+    if (!h || row_width < 1 || row_width > mfcc_vad::kMaxSelectWidth || (n_segs && (!seg_offsets || !out_offsets)))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    for (size_t k = 0; k < n_segs; ++k)
+        if (seg_offsets[k + 1] < seg_offsets[k]) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (n_segs == 0 || seg_offsets[n_segs] == seg_offsets[0])
+        return select_segments(h, nullptr, row_width, nullptr, seg_offsets, n_segs, nullptr, out_offsets);
+    if (!d_in || !d_voiced || !d_out || (reinterpret_cast<uintptr_t>(d_in) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    // the rows and the mask read must not overlap the rows that may be written (every row may be voiced)
+    const size_t r0 = seg_offsets[0], r1 = seg_offsets[n_segs], row_bytes = size_t(row_width) * sizeof(float);
+    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(d_in) + r0 * row_bytes;
+    const uintptr_t in_hi = reinterpret_cast<uintptr_t>(d_in) + r1 * row_bytes;
+    const uintptr_t v_lo = reinterpret_cast<uintptr_t>(d_voiced) + r0, v_hi = reinterpret_cast<uintptr_t>(d_voiced) + r1;
+    const uintptr_t out_lo = reinterpret_cast<uintptr_t>(d_out), out_hi = out_lo + (r1 - r0) * row_bytes;
+    if ((in_lo < out_hi && out_lo < in_hi) || (v_lo < out_hi && out_lo < v_hi)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (out_capacity_rows < r1 - r0) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    DeviceGuard guard(h->device);
+    return select_segments(h, static_cast<const float *>(d_in), row_width, static_cast<const unsigned char *>(d_voiced),
+                           seg_offsets, n_segs, static_cast<float *>(d_out), out_offsets);
+}
+
 const char *mfcc_hip_kernel_name(const mfcc_hip_handle *h, int fixed) {
     if (!h) return "";
     if (fixed) return h->fixed512_ok ? mfcc_fixed512::kernel_name() : "mfcc_fixed_kernel";
@@ -1893,6 +2208,7 @@ int mfcc_hip_convert_wav(mfcc_hip_handle *h, const char *wav_in, const char *mfc
     if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
     if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;     // ... raw ones
     if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... n_cep wide
+    if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                            // ... of every frame
     std::vector<int16_t> pcm;
     int rc = read_wav_i16(wav_in, h->r.sample_rate, pcm);
     if (rc) return rc;
@@ -1936,6 +2252,7 @@ int mfcc_hip_convert_wavs(mfcc_hip_handle *h, const char *const *wav_in, const c
     if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
     if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;     // ... raw ones
     if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... n_cep wide
+    if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                            // ... of every frame
     std::vector<int16_t> pcm;
     std::vector<size_t> off(n_files + 1, 0), fo(n_files + 1, 0);
     for (size_t i = 0; i < n_files; ++i) {
@@ -2043,6 +2360,7 @@ int mfcc_hip_stream_create(mfcc_hip_handle *h, int fixed, mfcc_hip_stream **out)
     if (h->destroy_pending) return MFCC_HIP_ERROR_INVALID_PARAM;        // the handle was already given back
     if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // per-call statistics of a stream
     if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;     // deltas need 2 K N frames of lookahead
+    if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;        // the threshold's mean is a whole-segment statistic
     if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
     mfcc_hip_stream *s = new (std::nothrow) mfcc_hip_stream();
     if (!s) return MFCC_HIP_ERROR_NO_MEM;

@@ -24,6 +24,12 @@ Deltas (``MFCC(deltas=...)``) read the neighbouring frames, so a shard's first a
 edges: the device path refuses ``halo=1`` on a handle with deltas too.  For frame-range shards compute the raw rows,
 gather them, ``MFCC.normalize_rows`` if wanted, then ``MFCC.deltas_rows`` (``mfcc_hip_deltas_dev``) over the whole
 stream.
+
+Frame selection (``MFCC(vad="select")``) takes its threshold from the mean of a whole segment and returns a different
+number of rows per segment, so a selecting handle has no dense entry point at all (``halo=1`` included).  Item plans use
+``process_batch`` on such a handle as they are.  For frame-range shards compute the raw rows, gather them, then, in this
+order: ``MFCC.vad_rows`` (``mfcc_hip_vad_dev``) on the RAW rows, ``MFCC.normalize_rows`` and ``MFCC.deltas_rows`` if wanted
+(both over every frame), and last ``MFCC.select_rows`` (``mfcc_hip_select_dev``) with the mask of the first step.
 """
 from __future__ import annotations
 
