@@ -425,6 +425,73 @@ int  mfcc_hip_stream_push(mfcc_hip_stream *s, const int16_t *samples, size_t n, 
  */
 int  mfcc_hip_stream_flush(mfcc_hip_stream *s, void *out, size_t out_capacity, size_t *n_frames_out);
 
+/* ---- stream bank: many online sessions advanced by one launch ---------------------------------
+ * A bank is n_streams independent sessions (N live lines: a microphone array, telephony) whose state
+ * lives on the device in one allocation: per stream the pre-emphasis history sample and the samples of
+ * the frame in progress.  One push takes a ragged batch of chunks, one per stream, and advances all of
+ * them with one launch of the frame kernels; every stream gets exactly the rows a session of its own
+ * would have returned for the same chunks, bit for bit.  The samples may already lie in device memory
+ * (mfcc_hip_bank_push_dev).  The number of samples each stream holds back (0 <= pending < nfft) depends
+ * on lengths only and is mirrored on the host: planning a push needs no device traffic.
+ * Cost of a push: the streams that complete frames run as channels of ONE launch of nfmax frames each,
+ * nfmax = the most frames any of them completes.  Equal chunks (lines in lockstep) compute exactly the
+ * frames returned and write them straight into `out`; a mixed push computes active x nfmax frames and
+ * gathers the ones that count; a straggler pushed alone costs only its own frames.
+ * A bank counts as a streaming session of its handle: the lifetime rule at mfcc_hip_destroy and the
+ * MFCC_HIP_ERROR_BUSY of the mfcc_hip_set_* calls hold for it, and mfcc_hip_bank_create refuses what
+ * mfcc_hip_stream_create refuses (MFCC_HIP_ERROR_UNSUPPORTED: a handle with normalization, deltas or VAD;
+ * fixed = 1 where the fixed-point path does not cover the parameters, a log-mel handle included).
+ * Banks, sessions and one-shot calls may share a handle; like the handle a bank is not thread-safe.  */
+typedef struct mfcc_hip_bank mfcc_hip_bank;
+
+/* fixed as for mfcc_hip_stream_create; n_streams >= 1.  Every stream starts in the reset state. */
+int    mfcc_hip_bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, mfcc_hip_bank **out);
+/* frees the bank's device buffers (waits for its work first); frees the handle too if that was already
+ * given to mfcc_hip_destroy and this was its last session or bank */
+void   mfcc_hip_bank_destroy(mfcc_hip_bank *b);
+/* n_streams (0 for NULL) */
+size_t mfcc_hip_bank_size(const mfcc_hip_bank *b);
+/* pending[n_streams]: the samples every stream holds back for its frame in progress */
+int    mfcc_hip_bank_pending(const mfcc_hip_bank *b, size_t *pending);
+/*
+ * The plan of a push, host only (no GPU, no handle).  Stream u has pending[u] < nfft samples and receives
+ * offsets[u + 1] - offsets[u] more; with total = pending + new it completes
+ *   nf = total >= nfft ? (total - nfft) / hop + 1 : 0   frames and keeps   total - nf * hop  (< nfft).
+ * frame_offsets[n_streams + 1]: running sum of nf, the row range of every stream in the result of the
+ * push; pending_after[n_streams] may be NULL.  Decreasing offsets or pending[u] >= nfft:
+ * MFCC_HIP_ERROR_INVALID_PARAM (frame_offsets is filled up to that stream).
+ */
+int    mfcc_hip_bank_plan(const mfcc_hip_params *p, const size_t *pending, const size_t *offsets,
+                          size_t n_streams, size_t *frame_offsets, size_t *pending_after);
+/*
+ * Feed every stream a chunk: stream u gets samples[offsets[u] .. offsets[u + 1]) (n_streams + 1 offsets,
+ * not decreasing; a range may be empty).  out: [sum frames][n_cep], float or int16_t by the bank's
+ * contract, out_capacity in elements; stream u's rows are rows frame_offsets[u] .. frame_offsets[u + 1].
+ * MFCC_HIP_ERROR_BUFFER_SMALL and MFCC_HIP_ERROR_INVALID_PARAM (decreasing offsets): frame_offsets is
+ * filled where it can be, NOTHING is consumed and the bank is as before.
+ * mfcc_hip_bank_push: host buffers, synchronous (one copy in, the device push, one copy out).
+ * mfcc_hip_bank_push_dev: device buffers, asynchronous on the handle's stream (mfcc_hip_set_stream); no
+ * synchronize and no device-to-host copy anywhere in it, no per-stream copy or launch.  d_samples and
+ * d_out must stay valid until the stream has run it; offsets is read before the call returns.
+ */
+int    mfcc_hip_bank_push(mfcc_hip_bank *b, const int16_t *samples, const size_t *offsets, void *out,
+                          size_t out_capacity, size_t *frame_offsets);
+int    mfcc_hip_bank_push_dev(mfcc_hip_bank *b, const void *d_samples, const size_t *offsets, void *d_out,
+                              size_t out_capacity, size_t *frame_offsets);
+/*
+ * End of some streams.  streams == NULL: all of them (n is not read); otherwise n distinct indices below
+ * the bank's size -- one repeated or out of range is MFCC_HIP_ERROR_INVALID_PARAM and nothing is done.
+ * Per listed stream, in the order listed, what mfcc_hip_stream_flush gives, [n_frames][n_cep] to HOST
+ * memory: MFCC_HIP_PAD_STREAM one zero-padded tail frame each, MFCC_HIP_PAD_NOTEBOOK nothing.
+ * *n_frames_out (may be NULL) = frames written; MFCC_HIP_ERROR_BUFFER_SMALL leaves the bank untouched.
+ * The listed streams are in the reset state afterwards, the others are not touched.  Synchronous.
+ */
+int    mfcc_hip_bank_flush(mfcc_hip_bank *b, const size_t *streams, size_t n, void *out, size_t out_capacity,
+                           size_t *n_frames_out);
+/* `mfcc_softreset` for the listed streams (as for flush): pending samples dropped, history back to 0.
+ * Ordered on the handle's stream behind the pushes before it; does not wait for them. */
+int    mfcc_hip_bank_reset(mfcc_hip_bank *b, const size_t *streams, size_t n);
+
 /* ---- `.mfcc` -> `.lift` (software/lift.py:28-40): host only, no GPU --------------------------
  * reads raw int16 [frame][n_cep], multiplies column n by 1 + (L/2) sin(pi n / L) in double
  * (lift.py:12-26; L <= 0: unchanged) and writes `astype(np.int16)` of it: truncation toward zero,

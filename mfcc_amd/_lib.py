@@ -132,6 +132,15 @@ SYMBOLS = {
     "mfcc_hip_stream_max_frames": (C.c_size_t, [_H, _SZ]),
     "mfcc_hip_stream_push": (C.c_int, [_H, C.c_void_p, _SZ, C.c_void_p, _SZ, _PSZ]),
     "mfcc_hip_stream_flush": (C.c_int, [_H, C.c_void_p, _SZ, _PSZ]),
+    "mfcc_hip_bank_create": (C.c_int, [_H, C.c_int, _SZ, C.POINTER(_H)]),
+    "mfcc_hip_bank_destroy": (None, [_H]),
+    "mfcc_hip_bank_size": (C.c_size_t, [_H]),
+    "mfcc_hip_bank_pending": (C.c_int, [_H, C.c_void_p]),
+    "mfcc_hip_bank_plan": (C.c_int, [C.POINTER(Params), C.c_void_p, C.c_void_p, _SZ, C.c_void_p, C.c_void_p]),
+    "mfcc_hip_bank_push": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, _SZ, C.c_void_p]),
+    "mfcc_hip_bank_push_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, _SZ, C.c_void_p]),
+    "mfcc_hip_bank_flush": (C.c_int, [_H, C.c_void_p, _SZ, C.c_void_p, _SZ, _PSZ]),
+    "mfcc_hip_bank_reset": (C.c_int, [_H, C.c_void_p, _SZ]),
     "mfcc_hip_lift_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_double, _PSZ]),
 }
 

@@ -682,6 +682,10 @@ class MFCC:
         """A streaming session on this handle: feed chunks, get the frames they complete."""
         return MfccStream(self, fixed)
 
+    def stream_bank(self, n_streams, fixed=False) -> "MfccStreamBank":
+        """``n_streams`` streaming sessions on this handle that advance together: one launch per push."""
+        return MfccStreamBank(self, n_streams, fixed)
+
     # -- file level: mfcc_convert(sess, path_in, path_out), software/main.c:100-177 -----
     def convert_many(self, paths_in, paths_out, fixed=True):
         """``mfcc_convert`` for many files in one ragged launch; returns the frame count of each file."""
@@ -758,6 +762,150 @@ class MfccStream:
     def reset(self):
         """``MFCC.reset`` / ``mfcc_softreset`` (main.c:21-34): drop pending samples, history back to 0."""
         _lib.check(self._lib.mfcc_hip_stream_reset(self._s), "stream_reset")
+
+
+class MfccStreamBank:
+    """``n_streams`` independent :class:`MfccStream` sessions (N live lines) whose state lives on the device and which
+    advance together: one push takes one chunk per stream and runs ONE launch of the frame kernels.  Every stream gets
+    the rows a session of its own would have returned for the same chunks, bit for bit.  Equal chunks (lines in
+    lockstep) compute exactly the frames returned; a mixed push computes ``active streams x most frames of any``."""
+
+    def __init__(self, mfcc: MFCC, n_streams, fixed=False):
+        self._m = mfcc
+        self._lib = mfcc._lib
+        self.fixed = bool(fixed)
+        self.n_streams = int(n_streams)
+        if self.n_streams < 1:
+            raise ValueError("a bank needs at least one stream")
+        b = C.c_void_p()
+        _lib.check(self._lib.mfcc_hip_bank_create(mfcc._h, int(self.fixed), self.n_streams, C.byref(b)), "bank_create")
+        self._b = b
+
+    def close(self):
+        # either order is safe: a handle closed first is kept alive by the library until its last bank / session goes
+        if getattr(self, "_b", None):
+            self._lib.mfcc_hip_bank_destroy(self._b)
+        self._b = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __len__(self):
+        return self.n_streams
+
+    @property
+    def pending(self) -> np.ndarray:
+        """Samples every stream holds back for its frame in progress: uint64 ``(n_streams,)``, each below ``nfft``."""
+        p = np.zeros(self.n_streams, dtype=np.uint64)
+        _lib.check(self._lib.mfcc_hip_bank_pending(self._b, p.ctypes.data_as(C.c_void_p)), "bank_pending")
+        return p
+
+    def _offsets(self, offsets):
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offsets.ndim != 1 or len(offsets) != self.n_streams + 1:
+            raise ValueError("offsets must be 1-D with n_streams + 1 = %d entries" % (self.n_streams + 1))
+        if int(np.diff(offsets.astype(np.int64)).min()) < 0:
+            raise ValueError("offsets must not decrease")
+        return offsets
+
+    def _plan(self, offsets):
+        fo = np.zeros(self.n_streams + 1, dtype=np.uint64)
+        pending = self.pending
+        _lib.check(self._lib.mfcc_hip_bank_plan(C.byref(self._m._params), pending.ctypes.data_as(C.c_void_p),
+                                                offsets.ctypes.data_as(C.c_void_p), self.n_streams,
+                                                fo.ctypes.data_as(C.c_void_p), None), "bank_plan")
+        return fo
+
+    def num_frames(self, lengths) -> np.ndarray:
+        """``frame_offsets`` a push of chunks of these lengths would give now (host only: ``mfcc_hip_bank_plan``)."""
+        lengths = np.asarray(lengths, dtype=np.uint64).reshape(-1)
+        if len(lengths) != self.n_streams:
+            raise ValueError("one length per stream: %d, not %d" % (self.n_streams, len(lengths)))
+        offsets = np.zeros(self.n_streams + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum(lengths, dtype=np.uint64)
+        return self._plan(offsets)
+
+    def _row(self):
+        return self._m._row(self.fixed)
+
+    def push(self, chunks) -> list:
+        """``sink`` of every stream: ``n_streams`` 1-D int16 arrays (any may be empty).  Returns a list of
+        ``(frames_u, num_features)`` arrays, the frames each stream completed (views of one buffer).  Synchronous."""
+        if len(chunks) != self.n_streams:
+            raise ValueError("one chunk per stream: %d, not %d" % (self.n_streams, len(chunks)))
+        cs = [np.ascontiguousarray(c) for c in chunks]
+        if any(c.dtype != np.int16 or c.ndim != 1 for c in cs):
+            raise TypeError("chunks must be 1-D int16 arrays (the core's sink is signed 16 bit, mfcc.py:29)")
+        n = self.n_streams
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([c.size for c in cs], dtype=np.uint64)
+        flat = np.concatenate(cs) if int(offsets[-1]) else np.zeros(0, dtype=np.int16)
+        nf = int(self._plan(offsets)[-1])
+        out = np.empty((nf, self._row()), dtype=np.int16 if self.fixed else np.float32)
+        fo = np.zeros(n + 1, dtype=np.uint64)
+        _lib.check(self._lib.mfcc_hip_bank_push(self._b, flat.ctypes.data_as(C.c_void_p),
+                                                offsets.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
+                                                out.size, fo.ctypes.data_as(C.c_void_p)), "bank_push")
+        assert int(fo[-1]) == nf
+        return [out[int(fo[u]):int(fo[u + 1])] for u in range(n)]
+
+    def push_packed(self, flat, offsets, out=None):
+        """Chunks that already lie in HBM: ``flat`` is a 1-D CUDA int16 tensor, stream ``u`` gets
+        ``flat[offsets[u]:offsets[u + 1]]``.  Asynchronous on the current torch stream, nothing is copied to the host.
+        Returns ``(out, frame_offsets)``: the ``(sum frames, num_features)`` tensor and, as a uint64 array, the row range
+        of every stream.  Lines in lockstep pass ``x.reshape(-1)`` with ``arange`` offsets and view the result as
+        ``(n_streams, frames, num_features)``."""
+        import torch
+        if flat.dtype != torch.int16 or not flat.is_cuda or flat.dim() != 1 or not flat.is_contiguous():
+            raise TypeError("flat must be a contiguous 1-D CUDA(HIP) int16 tensor")
+        offsets = self._offsets(offsets)
+        if int(offsets[-1]) > flat.numel():
+            raise ValueError("offsets run past the end of flat")
+        m = self._m
+        m._check_device(flat)
+        nf = int(self._plan(offsets)[-1])
+        odt = torch.int16 if self.fixed else torch.float32
+        row = self._row()
+        if out is None:
+            out = torch.empty((nf, row), device=flat.device, dtype=odt)
+        elif tuple(out.shape) != (nf, row) or out.dtype != odt or not out.is_contiguous() or out.device != flat.device:
+            raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (odt, (nf, row), flat.device))
+        fo = np.zeros(self.n_streams + 1, dtype=np.uint64)
+        with m._on_torch_stream(flat.device):
+            _lib.check(self._lib.mfcc_hip_bank_push_dev(self._b, C.c_void_p(flat.data_ptr()),
+                                                        offsets.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()),
+                                                        out.numel(), fo.ctypes.data_as(C.c_void_p)), "bank_push_dev")
+        assert int(fo[-1]) == nf
+        return out, fo
+
+    def _streams(self, streams):
+        if streams is None:
+            return None, self.n_streams
+        s = np.ascontiguousarray(streams, dtype=np.uint64).reshape(-1)
+        return s, len(s)
+
+    def flush(self, streams=None) -> list:
+        """End of the listed streams (``None``: all): per stream, in the order listed, what :meth:`MfccStream.flush`
+        returns -- one zero-padded tail frame with ``pad_mode="stream"``, no row with ``"notebook"``.  They are reset
+        afterwards; the other streams are not touched."""
+        s, n = self._streams(streams)
+        out = np.empty((n, self._row()), dtype=np.int16 if self.fixed else np.float32)
+        nf = C.c_size_t(0)
+        _lib.check(self._lib.mfcc_hip_bank_flush(self._b, None if s is None else s.ctypes.data_as(C.c_void_p), n,
+                                                 out.ctypes.data_as(C.c_void_p), out.size, C.byref(nf)), "bank_flush")
+        per = int(nf.value) // n if n else 0
+        return [out[i * per:(i + 1) * per] for i in range(n)]
+
+    def reset(self, streams=None):
+        """``MFCC.reset`` for the listed streams (``None``: all): drop pending samples, history back to 0."""
+        s, n = self._streams(streams)
+        _lib.check(self._lib.mfcc_hip_bank_reset(self._b, None if s is None else s.ctypes.data_as(C.c_void_p), n),
+                   "bank_reset")
 
 
 def lift_file(mfcc_in, lift_out, nceptrums=32, L=22) -> int:

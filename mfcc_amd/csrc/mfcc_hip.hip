@@ -28,6 +28,7 @@
 #include "kernel_deltas.hpp"
 #include "kernel_normalize_sliding.hpp"
 #include "kernel_vad.hpp"
+#include "kernel_stream_bank.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -2452,6 +2453,293 @@ int mfcc_hip_stream_flush(mfcc_hip_stream *s, void *out, size_t cap, size_t *n_f
         if (rc) return rc;
     }
     return mfcc_hip_stream_reset(s);
+}
+
+// ---- stream bank (include/mfcc_hip.h: mfcc_hip_bank_*; kernel_stream_bank.hpp) -------------
+// N sessions whose state rows ([history | pending], nfft int16 each) lie in one device allocation.  A push is planned on
+// the host from lengths alone, described by one record per stream in the pinned descriptor pool and carried out by ONE
+// launch of bank_advance_kernel, ONE launch of the frame kernels over the active streams' rows of the work buffer W
+// (h->d_in) and, when the streams complete different numbers of frames, ONE row gather out of h->d_out.
+
+}  // extern "C"
+
+struct mfcc_hip_bank {
+    mfcc_hip_handle *h = nullptr;
+    bool fixed = false;
+    size_t n = 0;                        // streams
+    int16_t *d_state = nullptr;          // [n][nfft]
+    std::vector<size_t> pending, after;  // the host mirror and the plan of the push in progress
+    // staging of the host-buffer entries (mfcc_hip_bank_push, mfcc_hip_bank_flush): the flat samples and the rows
+    void *st_in = nullptr, *st_out = nullptr;
+    size_t st_in_bytes = 0, st_out_bytes = 0;
+};
+
+namespace {
+
+// frame_offsets (n + 1) and, where given, pending_after (n) of a push of chunks offsets[u] .. offsets[u + 1]; on
+// INVALID_PARAM frame_offsets is filled up to the offending stream
+int bank_plan_raw(size_t nfft, size_t hop, const size_t *pending, const size_t *offsets, size_t n, size_t *frame_offsets,
+                  size_t *pending_after) {
+    frame_offsets[0] = 0;
+    for (size_t u = 0; u < n; ++u) {
+        if (offsets[u + 1] < offsets[u] || pending[u] >= nfft) return MFCC_HIP_ERROR_INVALID_PARAM;
+        size_t nf, pa;
+        mfcc_bank::plan(pending[u], offsets[u + 1] - offsets[u], nfft, hop, nf, pa);
+        frame_offsets[u + 1] = frame_offsets[u] + nf;
+        if (pending_after) pending_after[u] = pa;
+    }
+    return MFCC_HIP_SUCCESS;
+}
+
+// descriptors at the front of h->d_out (what follows them there is the row scratch of a mixed push)
+int bank_desc_upload(mfcc_hip_handle *h, mfcc_hip_handle::PinnedDesc *pd, size_t n_ll) {
+    HIP_TRY(h, hipMemcpyAsync(h->d_out, pd->p, n_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
+    pd->in_flight = true;
+    return MFCC_HIP_SUCCESS;
+}
+
+// The push proper: device buffers, asynchronous on the handle's stream.  Stream u's chunk is d_samples[offsets[u] - shift ..
+// offsets[u + 1] - shift).  Nothing is consumed unless MFCC_HIP_SUCCESS is returned.
+template <typename OutT>
+int bank_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const size_t *offsets, OutT *d_out, size_t cap,
+                 size_t *frame_offsets) {
+    mfcc_hip_handle *h = b->h;
+    const size_t nfft = size_t(h->r.nfft), hop = size_t(h->r.hop), W = row_width(h->r), n = b->n;
+    int rc = bank_plan_raw(nfft, hop, b->pending.data(), offsets, n, frame_offsets, b->after.data());
+    if (rc) return rc;
+    const size_t total_frames = frame_offsets[n];
+    if (total_frames && (!d_out || cap < total_frames * W)) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    size_t n_rec = 0, n_active = 0, nfmax = 0, nfmin = ~size_t(0), max_total = 0;
+    for (size_t u = 0; u < n; ++u) {
+        const size_t n_new = offsets[u + 1] - offsets[u], nf = frame_offsets[u + 1] - frame_offsets[u];
+        if (!n_new) continue;                          // nothing of this stream changes (nf > 0 needs new samples)
+        ++n_rec;
+        if (!nf) continue;
+        ++n_active;
+        nfmax = std::max(nfmax, nf);
+        nfmin = std::min(nfmin, nf);
+        max_total = std::max(max_total, b->pending[u] + n_new);
+    }
+    if (!n_rec) return MFCC_HIP_SUCCESS;
+    if (!d_samples) return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    const bool lockstep = n_active && nfmin == nfmax;    // the frame kernels' [active][nf][row] IS the result
+    const size_t S = 1 + max_total;
+    // [0, 5 n_rec): the records, active streams first; [5 n_rec, 5 n_rec + 3 n_active): the row gather of a mixed push
+    const size_t rec_ll = mfcc_bank::kRecLL * n_rec, desc_ll = rec_ll + 3 * n_active;
+    static_assert(sizeof(mfcc_bank::Rec) == mfcc_bank::kRecLL * sizeof(long long), "record layout");
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    if ((rc = desc_acquire(h, desc_ll, &pd))) return rc;
+    auto *rec = reinterpret_cast<mfcc_bank::Rec *>(pd->p);
+    long long *gat = pd->p + rec_ll;
+    size_t a = 0, q = n_active;
+    for (size_t u = 0; u < n; ++u) {
+        const size_t n_new = offsets[u + 1] - offsets[u], nf = frame_offsets[u + 1] - frame_offsets[u];
+        if (!n_new) continue;
+        const mfcc_bank::Rec c{(long long)u, (long long)(offsets[u] - shift), (long long)n_new, (long long)b->pending[u],
+                               (long long)nf};
+        if (!nf) {
+            rec[q++] = c;
+            continue;
+        }
+        gat[3 * a] = (long long)(a * nfmax);
+        gat[3 * a + 1] = (long long)frame_offsets[u];
+        gat[3 * a + 2] = (long long)nf;
+        rec[a++] = c;
+    }
+    const size_t desc_bytes = up256(desc_ll * sizeof(long long));
+    const size_t rows_bytes = lockstep ? 0 : n_active * nfmax * W * sizeof(OutT);
+    if (n_active && (rc = ensure(h, &h->d_in, &h->d_in_bytes, n_active * S * sizeof(int16_t) + 256))) return rc;
+    if ((rc = ensure(h, &h->d_out, &h->d_out_bytes, desc_bytes + rows_bytes + 64))) return rc;
+    if ((rc = scratch_acquire(h))) return rc;
+    if ((rc = bank_desc_upload(h, pd, desc_ll))) return rc;
+    auto *d_rec = static_cast<const mfcc_bank::Rec *>(h->d_out);
+    int16_t *d_w = static_cast<int16_t *>(h->d_in);
+    const unsigned blocks = (unsigned)std::min<size_t>(n_rec, size_t(h->n_cu) * 8);
+    hipLaunchKernelGGL(mfcc_bank::bank_advance_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, d_samples,
+                       b->d_state, d_w, d_rec, (long long)n_rec, (long long)n_active, (long long)S, h->r.nfft, h->r.hop);
+    if (n_active) {
+        OutT *d_rows = lockstep ? d_out : reinterpret_cast<OutT *>(static_cast<char *>(h->d_out) + desc_bytes);
+        if ((rc = launch(h, b->fixed, d_w, S - 1, S, n_active, /*halo=*/1, d_rows, nullptr, nfmax))) return rc;
+        if (!lockstep) {
+            const unsigned gblocks = (unsigned)std::min<size_t>(n_active, size_t(h->n_cu) * 8);
+            hipLaunchKernelGGL(gather_rows_kernel<OutT>, dim3(gblocks), dim3(256), 0, h->stream, d_rows, d_out,
+                               reinterpret_cast<const long long *>(d_rec) + rec_ll, (long long)n_active, (int)W);
+        }
+    }
+    HIP_TRY(h, hipGetLastError());
+    if ((rc = scratch_release(h))) return rc;
+    b->pending.swap(b->after);
+    return MFCC_HIP_SUCCESS;
+}
+
+// `streams` of a flush / reset as a list: NULL = every stream, else n distinct indices below the bank's size
+int bank_list(const mfcc_hip_bank *b, const size_t *streams, size_t n, std::vector<size_t> &list) {
+    list.clear();
+    if (!streams) {
+        for (size_t u = 0; u < b->n; ++u) list.push_back(u);
+        return MFCC_HIP_SUCCESS;
+    }
+    std::vector<char> seen(b->n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (streams[i] >= b->n || seen[streams[i]]) return MFCC_HIP_ERROR_INVALID_PARAM;
+        seen[streams[i]] = 1;
+        list.push_back(streams[i]);
+    }
+    return MFCC_HIP_SUCCESS;
+}
+
+// The listed streams back to the reset state; emit: their zero-padded tail frames first, to host memory (synchronous)
+int bank_tail(mfcc_hip_bank *b, const std::vector<size_t> &list, bool emit, void *out) {
+    mfcc_hip_handle *h = b->h;
+    const size_t k = list.size(), nfft = size_t(h->r.nfft), W = row_width(h->r), S = nfft + 1;
+    if (!k) return MFCC_HIP_SUCCESS;
+    const size_t esz = b->fixed ? sizeof(int16_t) : sizeof(float);
+    DeviceGuard guard(h->device);
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    int rc = desc_acquire(h, mfcc_bank::kRecLL * k, &pd);
+    if (rc) return rc;
+    auto *rec = reinterpret_cast<mfcc_bank::Rec *>(pd->p);
+    for (size_t i = 0; i < k; ++i) rec[i] = mfcc_bank::Rec{(long long)list[i], 0, 0, (long long)b->pending[list[i]], 1};
+    if (emit && (rc = ensure(h, &h->d_in, &h->d_in_bytes, k * S * sizeof(int16_t) + 256))) return rc;
+    if (emit && (rc = ensure(h, &b->st_out, &b->st_out_bytes, k * W * esz + 64))) return rc;
+    if ((rc = ensure(h, &h->d_out, &h->d_out_bytes, mfcc_bank::kRecLL * k * sizeof(long long) + 64))) return rc;
+    if ((rc = scratch_acquire(h))) return rc;
+    if ((rc = bank_desc_upload(h, pd, mfcc_bank::kRecLL * k))) return rc;
+    int16_t *d_w = emit ? static_cast<int16_t *>(h->d_in) : nullptr;
+    const unsigned blocks = (unsigned)std::min<size_t>(k, size_t(h->n_cu) * 8);
+    hipLaunchKernelGGL(mfcc_bank::bank_flush_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, b->d_state, d_w,
+                       static_cast<const mfcc_bank::Rec *>(h->d_out), (long long)k, (long long)S, h->r.nfft);
+    if (emit) {
+        // one frame per stream over history | pending | zeros: the tail frame of main.c:134-144
+        if ((rc = launch(h, b->fixed, d_w, nfft, S, k, /*halo=*/1, b->st_out, nullptr, 1))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(out, b->st_out, k * W * esz, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(h, hipGetLastError());
+    if ((rc = scratch_release(h))) return rc;
+    for (size_t u : list) b->pending[u] = 0;
+    if (emit) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MFCC_HIP_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfcc_hip_bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, mfcc_hip_bank **out) {
+    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
+    *out = nullptr;
+    if (h->destroy_pending || !n_streams) return MFCC_HIP_ERROR_INVALID_PARAM;
+    // what mfcc_hip_stream_create refuses: per-call statistics, lookahead and whole-segment thresholds of a stream
+    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
+    mfcc_hip_bank *b = new (std::nothrow) mfcc_hip_bank();
+    if (!b) return MFCC_HIP_ERROR_NO_MEM;
+    b->h = h;
+    b->fixed = fixed != 0;
+    b->n = n_streams;
+    b->pending.assign(n_streams, 0);
+    b->after.assign(n_streams, 0);
+    ++h->n_sessions;
+    DeviceGuard guard(h->device);
+    const size_t bytes = n_streams * size_t(h->r.nfft) * sizeof(int16_t);
+    auto fail = [&](hipError_t e) {
+        h->last_hip = int(e);
+        mfcc_hip_bank_destroy(b);
+        return e == hipErrorOutOfMemory ? MFCC_HIP_ERROR_NO_MEM : MFCC_HIP_ERROR_OTHER;
+    };
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_state), bytes + 64);
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_state, 0, bytes, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(e);
+    *out = b;
+    return MFCC_HIP_SUCCESS;
+}
+
+void mfcc_hip_bank_destroy(mfcc_hip_bank *b) {
+    if (!b) return;
+    mfcc_hip_handle *h = b->h;
+    {
+        DeviceGuard guard(h->device);
+        if (h->scratch_used) (void)hipEventSynchronize(h->scratch_done);    // a push may be in flight on a caller's stream
+        (void)hipStreamSynchronize(h->stream);
+        if (b->d_state) (void)hipFree(b->d_state);
+        if (b->st_in) (void)hipFree(b->st_in);
+        if (b->st_out) (void)hipFree(b->st_out);
+        delete b;
+    }
+    if (--h->n_sessions == 0 && h->destroy_pending) mfcc_hip_destroy(h);
+}
+
+size_t mfcc_hip_bank_size(const mfcc_hip_bank *b) { return b ? b->n : 0; }
+
+int mfcc_hip_bank_pending(const mfcc_hip_bank *b, size_t *pending) {
+    if (!b || !pending) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::copy(b->pending.begin(), b->pending.end(), pending);
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_bank_plan(const mfcc_hip_params *p, const size_t *pending, const size_t *offsets, size_t n_streams,
+                       size_t *frame_offsets, size_t *pending_after) {
+    if (!p || !pending || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    Resolved r;
+    const int rc = resolve(p, r);
+    if (rc) return rc;
+    return bank_plan_raw(size_t(r.nfft), size_t(r.hop), pending, offsets, n_streams, frame_offsets, pending_after);
+}
+
+int mfcc_hip_bank_push_dev(mfcc_hip_bank *b, const void *d_samples, const size_t *offsets, void *d_out, size_t out_capacity,
+                           size_t *frame_offsets) {
+    if (!b || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const int16_t *d = static_cast<const int16_t *>(d_samples);
+    return b->fixed ? bank_advance<int16_t>(b, d, 0, offsets, static_cast<int16_t *>(d_out), out_capacity, frame_offsets)
+                    : bank_advance<float>(b, d, 0, offsets, static_cast<float *>(d_out), out_capacity, frame_offsets);
+}
+
+int mfcc_hip_bank_push(mfcc_hip_bank *b, const int16_t *samples, const size_t *offsets, void *out, size_t out_capacity,
+                       size_t *frame_offsets) {
+    if (!b || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    mfcc_hip_handle *h = b->h;
+    const size_t W = row_width(h->r), esz = b->fixed ? sizeof(int16_t) : sizeof(float);
+    // the plan first: a refused push must not have copied anything
+    int rc = bank_plan_raw(size_t(h->r.nfft), size_t(h->r.hop), b->pending.data(), offsets, b->n, frame_offsets, nullptr);
+    if (rc) return rc;
+    const size_t total = frame_offsets[b->n], span = offsets[b->n] - offsets[0];
+    if (total && (!out || out_capacity < total * W)) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    if (!span) return MFCC_HIP_SUCCESS;
+    if (!samples) return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    if ((rc = ensure(h, &b->st_in, &b->st_in_bytes, span * sizeof(int16_t) + 64))) return rc;
+    if ((rc = ensure(h, &b->st_out, &b->st_out_bytes, total * W * esz + 64))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(b->st_in, samples + offsets[0], span * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+    const int16_t *d = static_cast<const int16_t *>(b->st_in);
+    rc = b->fixed ? bank_advance<int16_t>(b, d, offsets[0], offsets, static_cast<int16_t *>(b->st_out), total * W, frame_offsets)
+                  : bank_advance<float>(b, d, offsets[0], offsets, static_cast<float *>(b->st_out), total * W, frame_offsets);
+    if (!rc && total) HIP_TRY(h, hipMemcpyAsync(out, b->st_out, total * W * esz, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));        // `samples` and `out` belong to the caller again
+    return rc;
+}
+
+int mfcc_hip_bank_flush(mfcc_hip_bank *b, const size_t *streams, size_t n, void *out, size_t out_capacity,
+                        size_t *n_frames_out) {
+    if (!b) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::vector<size_t> list;
+    const int rc = bank_list(b, streams, n, list);
+    if (rc) return rc;
+    const bool emit = b->h->r.pad_mode == MFCC_HIP_PAD_STREAM;
+    const size_t nf = emit ? list.size() : 0;
+    if (n_frames_out) *n_frames_out = nf;
+    if (nf && (!out || out_capacity < nf * row_width(b->h->r))) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    return bank_tail(b, list, emit, out);
+}
+
+int mfcc_hip_bank_reset(mfcc_hip_bank *b, const size_t *streams, size_t n) {
+    if (!b) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::vector<size_t> list;
+    const int rc = bank_list(b, streams, n, list);
+    if (rc) return rc;
+    return bank_tail(b, list, false, nullptr);
 }
 
 int mfcc_hip_lift_file(const char *mfcc_in, const char *lift_out, int n_cep, double L, size_t *n_frames_out) {
