@@ -492,6 +492,63 @@ int    mfcc_hip_bank_flush(mfcc_hip_bank *b, const size_t *streams, size_t n, vo
  * Ordered on the handle's stream behind the pushes before it; does not wait for them. */
 int    mfcc_hip_bank_reset(mfcc_hip_bank *b, const size_t *streams, size_t n);
 
+/* ---- online bank: causal CMVN and delta coefficients as state of the bank --------------------------------
+ * A float bank on a RAW handle (no normalization, deltas or VAD set on it: MFCC_HIP_ERROR_UNSUPPORTED otherwise, as
+ * for a handle that cannot run the float path) with settings of its own, fixed at creation:
+ *   normalize         MFCC_HIP_NORMALIZE_MEAN / _MEAN_VAR over the purely causal window of mfcc_hip_set_normalize_window:
+ *                     row t of a stream is standardized with rows [max(0, t - normalize_window), t + 1) of that stream.
+ *                     In one-shot terms window = normalize_window, min_window = 1, center = 0.
+ *                     1 <= normalize_window <= MFCC_HIP_MAX_NORMALIZE_WINDOW, else MFCC_HIP_ERROR_INVALID_PARAM; with
+ *                     MFCC_HIP_NORMALIZE_NONE the window is ignored.  NOT offered, because they need the stream's end
+ *                     or frames of its future: per-utterance statistics (window 0), the centred window, min_window > 1
+ *                     and VAD.
+ *   delta_order       0, 1 or 2 with delta_window 1..8 (anything else: MFCC_HIP_ERROR_INVALID_PARAM): the formula of
+ *                     mfcc_hip_set_deltas on the normalized rows.  A stream's edges are its own: indices clamp at frame 0
+ *                     after create / reset and at the last frame only when the stream is flushed.  Row t is therefore
+ *                     returned once row t + lag is known, lag = delta_order * delta_window: every stream holds back up
+ *                     to lag finished rows (mfcc_hip_bank_held), which a flush returns.
+ * Rows are [s | D | DD], W (1 + delta_order) floats, W = n_cep or n_mel.  Contract: any pushes followed by a flush give,
+ * per stream and bit for bit, the rows of the one-shot call on the stream's whole signal by a handle with
+ * normalize, normalize_window, min_window 1, center 0, delta_order, delta_window.
+ * Device memory besides mfcc_hip_bank_create's: n_streams * (normalize_window + S) * W * 4 bytes of raw rows with
+ * normalization (S = normalize_window / 4 clamped to 32..256) and n_streams * 2 * lag * W * 4 bytes of static rows with
+ * deltas; MFCC_HIP_ERROR_NO_MEM if that cannot be had.
+ * With MFCC_HIP_NORMALIZE_NONE and order 0 the bank is mfcc_hip_bank_create(h, 0, n_streams) bit for bit.
+ * It counts as a session of the handle like any bank.  mfcc_hip_bank_push / _push_dev / _reset / _pending / _destroy
+ * take it; capacities and MFCC_HIP_ERROR_BUFFER_SMALL count expanded floats, frame_offsets the rows RETURNED; a refused
+ * push consumes nothing.  mfcc_hip_bank_push_dev stays asynchronous: held depends on chunk lengths only. */
+int    mfcc_hip_bank_create_online(mfcc_hip_handle *h, size_t n_streams, int normalize, int normalize_window,
+                                   int delta_order, int delta_window, mfcc_hip_bank **out);
+/* floats per row: W (1 + delta_order); W for a plain bank (int16 elements for a fixed one); 0 for NULL */
+size_t mfcc_hip_bank_row_width(const mfcc_hip_bank *b);
+/* delta_order * delta_window; 0 for a plain bank or NULL */
+int    mfcc_hip_bank_lag(const mfcc_hip_bank *b);
+/* held[n_streams]: finished rows every stream has not returned yet (0 <= held <= lag) */
+int    mfcc_hip_bank_held(const mfcc_hip_bank *b, size_t *held);
+/*
+ * mfcc_hip_bank_plan for sessions with a lag, host only (no GPU, no handle).  nf_raw and pending_after as there; then
+ *   emitted = max(0, held + nf_raw - lag)   rows are returned and   held_after = held + nf_raw - emitted.
+ * frame_offsets[n_streams + 1]: running sum of emitted; pending_after, held_after may be NULL.  With lag = 0 (held all
+ * 0) it is mfcc_hip_bank_plan.  lag < 0, held[u] > lag, decreasing offsets or pending[u] >= nfft:
+ * MFCC_HIP_ERROR_INVALID_PARAM.
+ */
+int    mfcc_hip_bank_plan_online(const mfcc_hip_params *p, int lag, const size_t *pending, const size_t *held,
+                                 const size_t *offsets, size_t n_streams, size_t *frame_offsets,
+                                 size_t *pending_after, size_t *held_after);
+/*
+ * mfcc_hip_bank_flush with a row count per stream; works on every bank.  streams / n as there.  Per listed stream, in
+ * the order listed: with MFCC_HIP_PAD_STREAM the zero-padded tail frame is computed and joins the stream as its last
+ * row; then the held rows (and that one) are written with the delta indices clamped at the stream's end, rows
+ * frame_offsets[i] .. frame_offsets[i + 1] of out (HOST memory, out_capacity in elements), held + (STREAM ? 1 : 0) of
+ * them -- fewer than lag for a short stream.  frame_offsets has n + 1 entries (bank size + 1 with streams == NULL) and
+ * is filled also on MFCC_HIP_ERROR_BUFFER_SMALL, which leaves the bank untouched.  The listed streams are in the reset
+ * state afterwards.  Synchronous.  mfcc_hip_bank_flush itself answers MFCC_HIP_ERROR_UNSUPPORTED on a bank with
+ * lag > 0 (its rows per stream are not uniform) and works on every other.  mfcc_hip_bank_reset also forgets a stream's
+ * window, its held rows and its frame count.
+ */
+int    mfcc_hip_bank_flush_ragged(mfcc_hip_bank *b, const size_t *streams, size_t n, void *out,
+                                  size_t out_capacity, size_t *frame_offsets);
+
 /* ---- `.mfcc` -> `.lift` (software/lift.py:28-40): host only, no GPU --------------------------
  * reads raw int16 [frame][n_cep], multiplies column n by 1 + (L/2) sin(pi n / L) in double
  * (lift.py:12-26; L <= 0: unchanged) and writes `astype(np.int16)` of it: truncation toward zero,

@@ -141,6 +141,13 @@ SYMBOLS = {
     "mfcc_hip_bank_push_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, _SZ, C.c_void_p]),
     "mfcc_hip_bank_flush": (C.c_int, [_H, C.c_void_p, _SZ, C.c_void_p, _SZ, _PSZ]),
     "mfcc_hip_bank_reset": (C.c_int, [_H, C.c_void_p, _SZ]),
+    "mfcc_hip_bank_create_online": (C.c_int, [_H, _SZ, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
+    "mfcc_hip_bank_row_width": (C.c_size_t, [_H]),
+    "mfcc_hip_bank_lag": (C.c_int, [_H]),
+    "mfcc_hip_bank_held": (C.c_int, [_H, C.c_void_p]),
+    "mfcc_hip_bank_plan_online": (C.c_int, [C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _SZ,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mfcc_hip_bank_flush_ragged": (C.c_int, [_H, C.c_void_p, _SZ, C.c_void_p, _SZ, C.c_void_p]),
     "mfcc_hip_lift_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_double, _PSZ]),
 }
 

@@ -682,9 +682,18 @@ class MFCC:
         """A streaming session on this handle: feed chunks, get the frames they complete."""
         return MfccStream(self, fixed)
 
-    def stream_bank(self, n_streams, fixed=False) -> "MfccStreamBank":
-        """``n_streams`` streaming sessions on this handle that advance together: one launch per push."""
-        return MfccStreamBank(self, n_streams, fixed)
+    def stream_bank(self, n_streams, fixed=False, *, normalize=None, normalize_window=None, deltas=0,
+                    delta_window=2) -> "MfccStreamBank":
+        """``n_streams`` streaming sessions on this handle that advance together: one launch per push.
+
+        ``normalize`` (``"mean"`` / ``"meanvar"``, with ``normalize_window=N``) and ``deltas`` (1 or 2, with
+        ``delta_window``) make it an ONLINE bank on a raw float handle: rows are standardized over the causal window
+        ``[max(0, t - N), t + 1)`` of their own stream and expanded to ``[s | D | DD]``; row ``t`` is returned once
+        row ``t + deltas * delta_window`` is known, :meth:`MfccStreamBank.flush` returns the rest.  Pushes followed
+        by a flush equal ``MFCC(..., normalize=..., normalize_window=N, normalize_min_window=1,
+        normalize_center=False, deltas=..., delta_window=...).process`` of the whole signal, bit for bit."""
+        return MfccStreamBank(self, n_streams, fixed, normalize=normalize, normalize_window=normalize_window,
+                              deltas=deltas, delta_window=delta_window)
 
     # -- file level: mfcc_convert(sess, path_in, path_out), software/main.c:100-177 -----
     def convert_many(self, paths_in, paths_out, fixed=True):
@@ -770,15 +779,36 @@ class MfccStreamBank:
     the rows a session of its own would have returned for the same chunks, bit for bit.  Equal chunks (lines in
     lockstep) compute exactly the frames returned; a mixed push computes ``active streams x most frames of any``."""
 
-    def __init__(self, mfcc: MFCC, n_streams, fixed=False):
+    def __init__(self, mfcc: MFCC, n_streams, fixed=False, *, normalize=None, normalize_window=None, deltas=0,
+                 delta_window=2):
         self._m = mfcc
         self._lib = mfcc._lib
         self.fixed = bool(fixed)
         self.n_streams = int(n_streams)
         if self.n_streams < 1:
             raise ValueError("a bank needs at least one stream")
+        mode = normalize_mode(normalize)
+        order, dwin = _delta_args(deltas, delta_window)
+        if mode != _lib.NORMALIZE_NONE:
+            if normalize_window is None:
+                raise ValueError("a stream bank normalizes over the causal window [max(0, t - N), t + 1) of each "
+                                 "stream only: normalize needs normalize_window=N (per-utterance statistics need the "
+                                 "stream's end)")
+            window = _window_args(normalize_window, 1, False)[0]
+        else:
+            window = 0
+        self.online = mode != _lib.NORMALIZE_NONE or order != 0 or normalize_window is not None
+        if self.online and self.fixed:
+            raise ValueError("normalize / deltas of a stream bank are float only: fixed=True takes neither")
+        self.normalize, self.normalize_window = (normalize if mode != _lib.NORMALIZE_NONE else None), (window or None)
+        self.deltas, self.delta_window = order, dwin
         b = C.c_void_p()
-        _lib.check(self._lib.mfcc_hip_bank_create(mfcc._h, int(self.fixed), self.n_streams, C.byref(b)), "bank_create")
+        if self.online:
+            _lib.check(self._lib.mfcc_hip_bank_create_online(mfcc._h, self.n_streams, mode, window, order, dwin,
+                                                             C.byref(b)), "bank_create_online")
+        else:
+            _lib.check(self._lib.mfcc_hip_bank_create(mfcc._h, int(self.fixed), self.n_streams, C.byref(b)),
+                       "bank_create")
         self._b = b
 
     def close(self):
@@ -805,6 +835,23 @@ class MfccStreamBank:
         _lib.check(self._lib.mfcc_hip_bank_pending(self._b, p.ctypes.data_as(C.c_void_p)), "bank_pending")
         return p
 
+    @property
+    def num_features(self) -> int:
+        """Elements per row: the handle's row width times ``1 + deltas``."""
+        return int(self._lib.mfcc_hip_bank_row_width(self._b))
+
+    @property
+    def lag(self) -> int:
+        """Rows a stream is behind: row ``t`` is returned once row ``t + lag`` is known (``deltas * delta_window``)."""
+        return int(self._lib.mfcc_hip_bank_lag(self._b))
+
+    @property
+    def held(self) -> np.ndarray:
+        """Finished rows every stream has not returned yet: uint64 ``(n_streams,)``, each at most ``lag``."""
+        p = np.zeros(self.n_streams, dtype=np.uint64)
+        _lib.check(self._lib.mfcc_hip_bank_held(self._b, p.ctypes.data_as(C.c_void_p)), "bank_held")
+        return p
+
     def _offsets(self, offsets):
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         if offsets.ndim != 1 or len(offsets) != self.n_streams + 1:
@@ -815,14 +862,17 @@ class MfccStreamBank:
 
     def _plan(self, offsets):
         fo = np.zeros(self.n_streams + 1, dtype=np.uint64)
-        pending = self.pending
-        _lib.check(self._lib.mfcc_hip_bank_plan(C.byref(self._m._params), pending.ctypes.data_as(C.c_void_p),
-                                                offsets.ctypes.data_as(C.c_void_p), self.n_streams,
-                                                fo.ctypes.data_as(C.c_void_p), None), "bank_plan")
+        pending, held = self.pending, self.held
+        _lib.check(self._lib.mfcc_hip_bank_plan_online(C.byref(self._m._params), self.lag,
+                                                       pending.ctypes.data_as(C.c_void_p),
+                                                       held.ctypes.data_as(C.c_void_p),
+                                                       offsets.ctypes.data_as(C.c_void_p), self.n_streams,
+                                                       fo.ctypes.data_as(C.c_void_p), None, None), "bank_plan_online")
         return fo
 
     def num_frames(self, lengths) -> np.ndarray:
-        """``frame_offsets`` a push of chunks of these lengths would give now (host only: ``mfcc_hip_bank_plan``)."""
+        """``frame_offsets`` (rows RETURNED, the lag counted) a push of chunks of these lengths would give now (host
+        only: ``mfcc_hip_bank_plan_online``, which is ``mfcc_hip_bank_plan`` on a plain bank)."""
         lengths = np.asarray(lengths, dtype=np.uint64).reshape(-1)
         if len(lengths) != self.n_streams:
             raise ValueError("one length per stream: %d, not %d" % (self.n_streams, len(lengths)))
@@ -831,7 +881,7 @@ class MfccStreamBank:
         return self._plan(offsets)
 
     def _row(self):
-        return self._m._row(self.fixed)
+        return self.num_features
 
     def push(self, chunks) -> list:
         """``sink`` of every stream: ``n_streams`` 1-D int16 arrays (any may be empty).  Returns a list of
@@ -891,15 +941,17 @@ class MfccStreamBank:
 
     def flush(self, streams=None) -> list:
         """End of the listed streams (``None``: all): per stream, in the order listed, what :meth:`MfccStream.flush`
-        returns -- one zero-padded tail frame with ``pad_mode="stream"``, no row with ``"notebook"``.  They are reset
+        returns -- one zero-padded tail frame with ``pad_mode="stream"``, no row with ``"notebook"``.  An online bank
+        returns the rows the stream still holds (:attr:`held`) first, with the tail frame as the stream's last row and
+        the delta indices clamped there: arrays of different lengths (``mfcc_hip_bank_flush_ragged``).  They are reset
         afterwards; the other streams are not touched."""
         s, n = self._streams(streams)
-        out = np.empty((n, self._row()), dtype=np.int16 if self.fixed else np.float32)
-        nf = C.c_size_t(0)
-        _lib.check(self._lib.mfcc_hip_bank_flush(self._b, None if s is None else s.ctypes.data_as(C.c_void_p), n,
-                                                 out.ctypes.data_as(C.c_void_p), out.size, C.byref(nf)), "bank_flush")
-        per = int(nf.value) // n if n else 0
-        return [out[i * per:(i + 1) * per] for i in range(n)]
+        out = np.empty((n * (self.lag + 1), self._row()), dtype=np.int16 if self.fixed else np.float32)
+        fo = np.zeros(n + 1, dtype=np.uint64)
+        _lib.check(self._lib.mfcc_hip_bank_flush_ragged(self._b, None if s is None else s.ctypes.data_as(C.c_void_p), n,
+                                                        out.ctypes.data_as(C.c_void_p), out.size,
+                                                        fo.ctypes.data_as(C.c_void_p)), "bank_flush_ragged")
+        return [out[int(fo[i]):int(fo[i + 1])] for i in range(n)]
 
     def reset(self, streams=None):
         """``MFCC.reset`` for the listed streams (``None``: all): drop pending samples, history back to 0."""

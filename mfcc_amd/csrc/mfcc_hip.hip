@@ -29,6 +29,7 @@
 #include "kernel_normalize_sliding.hpp"
 #include "kernel_vad.hpp"
 #include "kernel_stream_bank.hpp"
+#include "kernel_stream_bank_online.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -2460,6 +2461,9 @@ int mfcc_hip_stream_flush(mfcc_hip_stream *s, void *out, size_t cap, size_t *n_f
 // the host from lengths alone, described by one record per stream in the pinned descriptor pool and carried out by ONE
 // launch of bank_advance_kernel, ONE launch of the frame kernels over the active streams' rows of the work buffer W
 // (h->d_in) and, when the streams complete different numbers of frames, ONE row gather out of h->d_out.
+// An online bank (mfcc_hip_bank_create_online) keeps raw rows and static rows per stream as
+// well: its frame launch always goes to h->d_out, and the CMVN, delta and carry kernels of
+// kernel_stream_bank_online.hpp follow on the same stream; there is no gather, the delta kernel writes packed rows.
 
 }  // extern "C"
 
@@ -2472,6 +2476,14 @@ struct mfcc_hip_bank {
     // staging of the host-buffer entries (mfcc_hip_bank_push, mfcc_hip_bank_flush): the flat samples and the rows
     void *st_in = nullptr, *st_out = nullptr;
     size_t st_in_bytes = 0, st_out_bytes = 0;
+    // online bank (mfcc_hip_bank_create_online; kernel_stream_bank_online.hpp): causal CMVN
+    // over `window` rows and deltas of `order` x `dwin`, lag = order * dwin.  seen[u] = frames computed since reset,
+    // held[u] <= lag = finished rows not yet returned; both depend on chunk lengths only
+    bool online = false;
+    int norm = MFCC_HIP_NORMALIZE_NONE, window = 0, run = 0, depth = 0, order = 0, dwin = 0, lag = 0;
+    float *d_ring = nullptr;             // [n][depth][W] raw rows (norm != NONE)
+    float *d_tail = nullptr;             // [n][2 lag][W] static rows (lag > 0)
+    std::vector<size_t> seen, held, held_after, raw_fo;
 };
 
 namespace {
@@ -2490,6 +2502,28 @@ int bank_plan_raw(size_t nfft, size_t hop, const size_t *pending, const size_t *
     }
     return MFCC_HIP_SUCCESS;
 }
+
+// The same for sessions that return row t once row t + lag is known: frame_offsets counts the rows RETURNED.  held may
+// be NULL with lag = 0; raw_offsets (n + 1, may be NULL) gets the running sum of the frames computed
+int bank_plan_lagged(size_t nfft, size_t hop, size_t lag, const size_t *pending, const size_t *held, const size_t *offsets,
+                     size_t n, size_t *frame_offsets, size_t *pending_after, size_t *held_after, size_t *raw_offsets) {
+    frame_offsets[0] = 0;
+    if (raw_offsets) raw_offsets[0] = 0;
+    for (size_t u = 0; u < n; ++u) {
+        const size_t hu = held ? held[u] : 0;
+        if (offsets[u + 1] < offsets[u] || pending[u] >= nfft || hu > lag) return MFCC_HIP_ERROR_INVALID_PARAM;
+        size_t nf, pa;
+        mfcc_bank::plan(pending[u], offsets[u + 1] - offsets[u], nfft, hop, nf, pa);
+        const size_t emitted = hu + nf > lag ? hu + nf - lag : 0;
+        frame_offsets[u + 1] = frame_offsets[u] + emitted;
+        if (raw_offsets) raw_offsets[u + 1] = raw_offsets[u] + nf;
+        if (pending_after) pending_after[u] = pa;
+        if (held_after) held_after[u] = hu + nf - emitted;
+    }
+    return MFCC_HIP_SUCCESS;
+}
+
+inline size_t bank_row_width(const mfcc_hip_bank *b) { return row_width(b->h->r) * size_t(1 + b->order); }
 
 // descriptors at the front of h->d_out (what follows them there is the row scratch of a mixed push)
 int bank_desc_upload(mfcc_hip_handle *h, mfcc_hip_handle::PinnedDesc *pd, size_t n_ll) {
@@ -2574,6 +2608,136 @@ int bank_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const
     return MFCC_HIP_SUCCESS;
 }
 
+
+// The runs of the causal CMVN that cover the fresh rows [seen, seen + nf) of a stream: S rows each, counted from frame 0
+inline size_t online_runs(size_t seen, size_t nf, size_t S) { return nf ? (seen + nf - 1) / S - seen / S + 1 : 0; }
+
+// records of the CMVN pass for one stream (rec may be NULL: count only)
+size_t online_cmvn_recs(mfcc_online::Rec *rec, size_t u, size_t row0, size_t seen, size_t nf, size_t S, size_t out_row) {
+    const size_t k = online_runs(seen, nf, S);
+    if (rec)
+        for (size_t i = 0, t0 = seen / S * S; i < k; ++i, t0 += S)
+            rec[i] = mfcc_online::Rec{(long long)u, (long long)row0, (long long)seen, (long long)nf, (long long)t0,
+                                      (long long)std::min(t0 + S, seen + nf), (long long)out_row, 0};
+    return k;
+}
+
+// records of the delta pass: rows [e, e + emitted) of stream u to rows out_row .. of the result, g rows per tile
+size_t online_delta_recs(mfcc_online::Rec *rec, size_t u, size_t row0, size_t seen, size_t nf, size_t e, size_t emitted,
+                         size_t g, size_t out_row, long long last) {
+    const size_t k = (emitted + g - 1) / g;
+    if (rec)
+        for (size_t i = 0; i < k; ++i)
+            rec[i] = mfcc_online::Rec{(long long)u, (long long)row0, (long long)seen, (long long)nf, (long long)(e + i * g),
+                                      (long long)std::min(g, emitted - i * g), (long long)(out_row + i * g), last};
+    return k;
+}
+
+// the passes of an online bank over fresh raw rows, on the handle's stream; d_rec: the three record tables one behind
+// the other on the device.  y: the caller's rows.  carry: also append to ring and tail (a push; a flush resets instead)
+void online_passes(mfcc_hip_bank *b, const mfcc_online::Rec *d_rec, size_t n_cmvn, size_t n_delta, size_t n_carry,
+                   const float *d_raw, float *d_stat, float *y) {
+    mfcc_hip_handle *h = b->h;
+    const int W = int(row_width(h->r));
+    const size_t cap = size_t(h->n_cu) * 8;
+    const bool norm = b->norm != MFCC_HIP_NORMALIZE_NONE;
+    if (norm && n_cmvn) {
+        const size_t G = size_t(mfcc_online::kThreads / W), blocks = std::min((n_cmvn + G - 1) / G, cap);
+        hipLaunchKernelGGL(mfcc_online::online_cmvn_kernel, dim3((unsigned)blocks), dim3(mfcc_online::kThreads), 0, h->stream,
+                           b->d_ring, d_raw, b->order ? d_stat : y, d_rec, (long long)n_cmvn, W, b->window, b->depth, b->norm);
+    }
+    const float *stat = norm ? d_stat : d_raw;
+    if (b->order && n_delta)
+        hipLaunchKernelGGL(mfcc_online::online_deltas_kernel, dim3((unsigned)std::min(n_delta, cap)),
+                           dim3(mfcc_online::kThreads), 0, h->stream, b->d_tail, stat, y, d_rec + n_cmvn, (long long)n_delta, W,
+                           b->order, b->dwin, mfcc_delta::delta_scale(b->dwin));
+    if (n_carry)
+        hipLaunchKernelGGL(mfcc_online::online_carry_kernel, dim3((unsigned)std::min(n_carry, cap)),
+                           dim3(mfcc_online::kThreads), 0, h->stream, b->d_ring, b->d_tail, d_raw, stat,
+                           d_rec + n_cmvn + n_delta, (long long)n_carry, W, b->depth, 2 * b->lag);
+}
+
+// bank_advance of an online bank (float): the frame launch always writes raw rows [active][nfmax][W] into the handle's
+// scratch; CMVN, deltas and the carry follow on the same stream.  cap counts expanded floats
+int online_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const size_t *offsets, float *d_out, size_t cap,
+                   size_t *frame_offsets) {
+    mfcc_hip_handle *h = b->h;
+    const size_t nfft = size_t(h->r.nfft), hop = size_t(h->r.hop), W = row_width(h->r), WO = bank_row_width(b), n = b->n;
+    const size_t S = size_t(b->run), L = size_t(b->lag);
+    const bool norm = b->norm != MFCC_HIP_NORMALIZE_NONE;
+    size_t *rfo = b->raw_fo.data();
+    int rc = bank_plan_lagged(nfft, hop, L, b->pending.data(), b->held.data(), offsets, n, frame_offsets, b->after.data(),
+                              b->held_after.data(), rfo);
+    if (rc) return rc;
+    const size_t total_rows = frame_offsets[n];
+    if (total_rows && (!d_out || cap < total_rows * WO)) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    const size_t g = b->order ? size_t(mfcc_online::tile_rows(int(W), b->order, b->dwin)) : 1;
+    size_t n_rec = 0, n_active = 0, nfmax = 0, max_total = 0, n_cmvn = 0, n_delta = 0;
+    for (size_t u = 0; u < n; ++u) {
+        const size_t n_new = offsets[u + 1] - offsets[u], nf = rfo[u + 1] - rfo[u];
+        if (!n_new) continue;
+        ++n_rec;
+        if (!nf) continue;
+        ++n_active;
+        nfmax = std::max(nfmax, nf);
+        max_total = std::max(max_total, b->pending[u] + n_new);
+        if (norm) n_cmvn += online_runs(b->seen[u], nf, S);
+        if (b->order) n_delta += (frame_offsets[u + 1] - frame_offsets[u] + g - 1) / g;
+    }
+    if (!n_rec) return MFCC_HIP_SUCCESS;
+    if (!d_samples) return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    const size_t SW = 1 + max_total;
+    // [0, 5 n_rec): the bank's records, active streams first; then the CMVN, delta and carry records
+    const size_t rec_ll = mfcc_bank::kRecLL * n_rec, desc_ll = rec_ll + mfcc_online::kRecLL * (n_cmvn + n_delta + n_active);
+    static_assert(sizeof(mfcc_online::Rec) == mfcc_online::kRecLL * sizeof(long long), "record layout");
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    if ((rc = desc_acquire(h, desc_ll, &pd))) return rc;
+    auto *rec = reinterpret_cast<mfcc_bank::Rec *>(pd->p);
+    auto *cm = reinterpret_cast<mfcc_online::Rec *>(pd->p + rec_ll), *de = cm + n_cmvn, *ca = de + n_delta;
+    size_t a = 0, q = n_active;
+    for (size_t u = 0; u < n; ++u) {
+        const size_t n_new = offsets[u + 1] - offsets[u], nf = rfo[u + 1] - rfo[u];
+        if (!n_new) continue;
+        const mfcc_bank::Rec c{(long long)u, (long long)(offsets[u] - shift), (long long)n_new, (long long)b->pending[u],
+                               (long long)nf};
+        if (!nf) {
+            rec[q++] = c;
+            continue;
+        }
+        const size_t row0 = a * nfmax, seen = b->seen[u], emitted = frame_offsets[u + 1] - frame_offsets[u];
+        if (norm) cm += online_cmvn_recs(cm, u, row0, seen, nf, S, b->order ? row0 : frame_offsets[u]);
+        if (b->order)
+            de += online_delta_recs(de, u, row0, seen, nf, seen - b->held[u], emitted, g, frame_offsets[u], mfcc_online::kNoEdge);
+        ca[a] = mfcc_online::Rec{(long long)u, (long long)row0, (long long)seen, (long long)nf, 0, 0, 0, 0};
+        rec[a++] = c;
+    }
+    const size_t desc_bytes = up256(desc_ll * sizeof(long long));
+    const size_t rows_bytes = up256(n_active * nfmax * W * sizeof(float));
+    if (n_active && (rc = ensure(h, &h->d_in, &h->d_in_bytes, n_active * SW * sizeof(int16_t) + 256))) return rc;
+    if ((rc = ensure(h, &h->d_out, &h->d_out_bytes, desc_bytes + 2 * rows_bytes + 64))) return rc;
+    if ((rc = scratch_acquire(h))) return rc;
+    if ((rc = bank_desc_upload(h, pd, desc_ll))) return rc;
+    auto *d_rec = static_cast<const mfcc_bank::Rec *>(h->d_out);
+    int16_t *d_w = static_cast<int16_t *>(h->d_in);
+    const unsigned blocks = (unsigned)std::min<size_t>(n_rec, size_t(h->n_cu) * 8);
+    hipLaunchKernelGGL(mfcc_bank::bank_advance_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, d_samples,
+                       b->d_state, d_w, d_rec, (long long)n_rec, (long long)n_active, (long long)SW, h->r.nfft, h->r.hop);
+    if (n_active) {
+        float *d_raw = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes);
+        float *d_stat = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes + rows_bytes);
+        if ((rc = launch(h, false, d_w, SW - 1, SW, n_active, /*halo=*/1, d_raw, nullptr, nfmax))) return rc;
+        online_passes(b, reinterpret_cast<const mfcc_online::Rec *>(reinterpret_cast<const long long *>(d_rec) + rec_ll),
+                      n_cmvn, n_delta, n_active, d_raw, d_stat, d_out);
+    }
+    HIP_TRY(h, hipGetLastError());
+    if ((rc = scratch_release(h))) return rc;
+    for (size_t u = 0; u < n; ++u) b->seen[u] += rfo[u + 1] - rfo[u];
+    b->pending.swap(b->after);
+    b->held.swap(b->held_after);
+    return MFCC_HIP_SUCCESS;
+}
+
 // `streams` of a flush / reset as a list: NULL = every stream, else n distinct indices below the bank's size
 int bank_list(const mfcc_hip_bank *b, const size_t *streams, size_t n, std::vector<size_t> &list) {
     list.clear();
@@ -2618,8 +2782,117 @@ int bank_tail(mfcc_hip_bank *b, const std::vector<size_t> &list, bool emit, void
     }
     HIP_TRY(h, hipGetLastError());
     if ((rc = scratch_release(h))) return rc;
-    for (size_t u : list) b->pending[u] = 0;
+    for (size_t u : list) b->pending[u] = b->seen[u] = b->held[u] = 0;
     if (emit) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MFCC_HIP_SUCCESS;
+}
+
+// The end of the listed streams of an online bank, to host memory (synchronous): the zero-padded tail frame (emit) joins
+// each stream as its last row, the held rows and that one are returned with the end clamped -- fo[i + 1] - fo[i] =
+// held + emit rows of stream list[i] -- and the streams are back in the reset state.  The ring and the tail are not
+// cleared: with seen = 0 nothing of them is read
+int online_tail(mfcc_hip_bank *b, const std::vector<size_t> &list, bool emit, void *out, const size_t *fo) {
+    mfcc_hip_handle *h = b->h;
+    const size_t k = list.size(), nfft = size_t(h->r.nfft), W = row_width(h->r), WO = bank_row_width(b), SW = nfft + 1;
+    if (!k) return MFCC_HIP_SUCCESS;
+    const bool norm = b->norm != MFCC_HIP_NORMALIZE_NONE;
+    const size_t nf = emit ? 1 : 0, total = fo[k], S = size_t(b->run);
+    const size_t g = b->order ? size_t(mfcc_online::tile_rows(int(W), b->order, b->dwin)) : 1;
+    size_t n_cmvn = 0, n_delta = 0;
+    for (size_t i = 0; i < k; ++i) {
+        if (norm) n_cmvn += online_runs(b->seen[list[i]], nf, S);
+        if (b->order) n_delta += (fo[i + 1] - fo[i] + g - 1) / g;
+    }
+    DeviceGuard guard(h->device);
+    const size_t rec_ll = mfcc_bank::kRecLL * k, desc_ll = rec_ll + mfcc_online::kRecLL * (n_cmvn + n_delta);
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    int rc = desc_acquire(h, desc_ll, &pd);
+    if (rc) return rc;
+    auto *rec = reinterpret_cast<mfcc_bank::Rec *>(pd->p);
+    auto *cm = reinterpret_cast<mfcc_online::Rec *>(pd->p + rec_ll), *de = cm + n_cmvn;
+    for (size_t i = 0; i < k; ++i) {
+        const size_t u = list[i], seen = b->seen[u];
+        rec[i] = mfcc_bank::Rec{(long long)u, 0, 0, (long long)b->pending[u], 1};
+        if (norm) cm += online_cmvn_recs(cm, u, i, seen, nf, S, b->order ? i : fo[i]);
+        if (b->order)
+            de += online_delta_recs(de, u, i, seen, nf, seen - b->held[u], fo[i + 1] - fo[i], g, fo[i],
+                                    (long long)(seen + nf) - 1);
+    }
+    const size_t desc_bytes = up256(desc_ll * sizeof(long long)), rows_bytes = up256(k * W * sizeof(float));
+    if (emit && (rc = ensure(h, &h->d_in, &h->d_in_bytes, k * SW * sizeof(int16_t) + 256))) return rc;
+    if (total && (rc = ensure(h, &b->st_out, &b->st_out_bytes, total * WO * sizeof(float) + 64))) return rc;
+    if ((rc = ensure(h, &h->d_out, &h->d_out_bytes, desc_bytes + 2 * rows_bytes + 64))) return rc;
+    if ((rc = scratch_acquire(h))) return rc;
+    if ((rc = bank_desc_upload(h, pd, desc_ll))) return rc;
+    int16_t *d_w = emit ? static_cast<int16_t *>(h->d_in) : nullptr;
+    const unsigned blocks = (unsigned)std::min<size_t>(k, size_t(h->n_cu) * 8);
+    hipLaunchKernelGGL(mfcc_bank::bank_flush_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, b->d_state, d_w,
+                       static_cast<const mfcc_bank::Rec *>(h->d_out), (long long)k, (long long)SW, h->r.nfft);
+    float *d_raw = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes);
+    float *d_stat = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes + rows_bytes);
+    if (emit && (rc = launch(h, false, d_w, nfft, SW, k, /*halo=*/1, d_raw, nullptr, 1))) return rc;
+    if (total) {
+        online_passes(b, reinterpret_cast<const mfcc_online::Rec *>(static_cast<const long long *>(h->d_out) + rec_ll), n_cmvn,
+                      n_delta, 0, d_raw, d_stat, static_cast<float *>(b->st_out));
+        HIP_TRY(h, hipMemcpyAsync(out, b->st_out, total * WO * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(h, hipGetLastError());
+    if ((rc = scratch_release(h))) return rc;
+    for (size_t u : list) b->pending[u] = b->seen[u] = b->held[u] = 0;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MFCC_HIP_SUCCESS;
+}
+
+// rows a flush returns per listed stream, as running sums fo[k + 1]
+void bank_flush_offsets(const mfcc_hip_bank *b, const std::vector<size_t> &list, size_t *fo) {
+    const size_t emit = b->h->r.pad_mode == MFCC_HIP_PAD_STREAM ? 1 : 0;
+    fo[0] = 0;
+    for (size_t i = 0; i < list.size(); ++i) fo[i + 1] = fo[i] + b->held[list[i]] + emit;
+}
+
+// a bank on a checked handle; norm / order as validated by the caller (NONE and 0: a plain bank)
+int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int window, int order, int dwin,
+                mfcc_hip_bank **out) {
+    mfcc_hip_bank *b = new (std::nothrow) mfcc_hip_bank();
+    if (!b) return MFCC_HIP_ERROR_NO_MEM;
+    b->h = h;
+    b->fixed = fixed != 0;
+    b->n = n_streams;
+    b->pending.assign(n_streams, 0);
+    b->after.assign(n_streams, 0);
+    b->seen.assign(n_streams, 0);
+    b->held.assign(n_streams, 0);
+    b->held_after.assign(n_streams, 0);
+    b->raw_fo.assign(n_streams + 1, 0);
+    b->online = norm != MFCC_HIP_NORMALIZE_NONE || order != 0;
+    if (norm != MFCC_HIP_NORMALIZE_NONE) {
+        b->norm = norm;
+        b->window = window;
+        b->run = mfcc_slide::run_rows(window);
+        b->depth = b->window + b->run;
+    }
+    if (order) {
+        b->order = order;
+        b->dwin = dwin;
+        b->lag = order * dwin;
+    }
+    ++h->n_sessions;
+    DeviceGuard guard(h->device);
+    const size_t bytes = n_streams * size_t(h->r.nfft) * sizeof(int16_t), W = row_width(h->r);
+    const size_t ring_bytes = n_streams * size_t(b->depth) * W * sizeof(float);
+    const size_t tail_bytes = n_streams * size_t(2 * b->lag) * W * sizeof(float);
+    auto fail = [&](hipError_t e) {
+        h->last_hip = int(e);
+        mfcc_hip_bank_destroy(b);
+        return e == hipErrorOutOfMemory ? MFCC_HIP_ERROR_NO_MEM : MFCC_HIP_ERROR_OTHER;
+    };
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_state), bytes + 64);
+    if (e == hipSuccess && ring_bytes) e = hipMalloc(reinterpret_cast<void **>(&b->d_ring), ring_bytes + 64);
+    if (e == hipSuccess && tail_bytes) e = hipMalloc(reinterpret_cast<void **>(&b->d_tail), tail_bytes + 64);
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_state, 0, bytes, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(e);
+    *out = b;
     return MFCC_HIP_SUCCESS;
 }
 
@@ -2634,27 +2907,58 @@ int mfcc_hip_bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, mfcc_h
     // what mfcc_hip_stream_create refuses: per-call statistics, lookahead and whole-segment thresholds of a stream
     if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
-    mfcc_hip_bank *b = new (std::nothrow) mfcc_hip_bank();
-    if (!b) return MFCC_HIP_ERROR_NO_MEM;
-    b->h = h;
-    b->fixed = fixed != 0;
-    b->n = n_streams;
-    b->pending.assign(n_streams, 0);
-    b->after.assign(n_streams, 0);
-    ++h->n_sessions;
-    DeviceGuard guard(h->device);
-    const size_t bytes = n_streams * size_t(h->r.nfft) * sizeof(int16_t);
-    auto fail = [&](hipError_t e) {
-        h->last_hip = int(e);
-        mfcc_hip_bank_destroy(b);
-        return e == hipErrorOutOfMemory ? MFCC_HIP_ERROR_NO_MEM : MFCC_HIP_ERROR_OTHER;
-    };
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_state), bytes + 64);
-    if (e == hipSuccess) e = hipMemsetAsync(b->d_state, 0, bytes, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(e);
-    *out = b;
+    return bank_create(h, fixed, n_streams, MFCC_HIP_NORMALIZE_NONE, 0, 0, 0, out);
+}
+
+int mfcc_hip_bank_create_online(mfcc_hip_handle *h, size_t n_streams, int normalize, int normalize_window, int delta_order,
+                                int delta_window, mfcc_hip_bank **out) {
+    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
+    *out = nullptr;
+    if (h->destroy_pending || !n_streams) return MFCC_HIP_ERROR_INVALID_PARAM;
+    // the bank's settings are its own: the handle must be a raw one, and able to run the float path
+    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !h->fused_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (normalize != MFCC_HIP_NORMALIZE_NONE && normalize != MFCC_HIP_NORMALIZE_MEAN && normalize != MFCC_HIP_NORMALIZE_MEAN_VAR)
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (normalize != MFCC_HIP_NORMALIZE_NONE && (normalize_window < 1 || normalize_window > MFCC_HIP_MAX_NORMALIZE_WINDOW))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (delta_order < 0 || delta_order > 2 || delta_window < 1 || delta_window > mfcc_delta::kMaxWindow)
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    return bank_create(h, 0, n_streams, normalize, normalize_window, delta_order, delta_window, out);
+}
+
+size_t mfcc_hip_bank_row_width(const mfcc_hip_bank *b) { return b ? bank_row_width(b) : 0; }
+
+int mfcc_hip_bank_lag(const mfcc_hip_bank *b) { return b ? b->lag : 0; }
+
+int mfcc_hip_bank_held(const mfcc_hip_bank *b, size_t *held) {
+    if (!b || !held) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::copy(b->held.begin(), b->held.end(), held);
     return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_bank_plan_online(const mfcc_hip_params *p, int lag, const size_t *pending, const size_t *held,
+                              const size_t *offsets, size_t n_streams, size_t *frame_offsets, size_t *pending_after,
+                              size_t *held_after) {
+    if (!p || lag < 0 || !pending || !held || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    Resolved r;
+    const int rc = resolve(p, r);
+    if (rc) return rc;
+    return bank_plan_lagged(size_t(r.nfft), size_t(r.hop), size_t(lag), pending, held, offsets, n_streams, frame_offsets,
+                            pending_after, held_after, nullptr);
+}
+
+int mfcc_hip_bank_flush_ragged(mfcc_hip_bank *b, const size_t *streams, size_t n, void *out, size_t out_capacity,
+                               size_t *frame_offsets) {
+    if (!b || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::vector<size_t> list;
+    const int rc = bank_list(b, streams, n, list);
+    if (rc) return rc;
+    bank_flush_offsets(b, list, frame_offsets);
+    const size_t total = frame_offsets[list.size()];
+    if (total && (!out || out_capacity < total * bank_row_width(b))) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    const bool emit = b->h->r.pad_mode == MFCC_HIP_PAD_STREAM;
+    return b->online ? online_tail(b, list, emit, out, frame_offsets) : bank_tail(b, list, emit, out);
 }
 
 void mfcc_hip_bank_destroy(mfcc_hip_bank *b) {
@@ -2665,6 +2969,8 @@ void mfcc_hip_bank_destroy(mfcc_hip_bank *b) {
         if (h->scratch_used) (void)hipEventSynchronize(h->scratch_done);    // a push may be in flight on a caller's stream
         (void)hipStreamSynchronize(h->stream);
         if (b->d_state) (void)hipFree(b->d_state);
+        if (b->d_ring) (void)hipFree(b->d_ring);
+        if (b->d_tail) (void)hipFree(b->d_tail);
         if (b->st_in) (void)hipFree(b->st_in);
         if (b->st_out) (void)hipFree(b->st_out);
         delete b;
@@ -2693,6 +2999,7 @@ int mfcc_hip_bank_push_dev(mfcc_hip_bank *b, const void *d_samples, const size_t
                            size_t *frame_offsets) {
     if (!b || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
     const int16_t *d = static_cast<const int16_t *>(d_samples);
+    if (b->online) return online_advance(b, d, 0, offsets, static_cast<float *>(d_out), out_capacity, frame_offsets);
     return b->fixed ? bank_advance<int16_t>(b, d, 0, offsets, static_cast<int16_t *>(d_out), out_capacity, frame_offsets)
                     : bank_advance<float>(b, d, 0, offsets, static_cast<float *>(d_out), out_capacity, frame_offsets);
 }
@@ -2701,9 +3008,10 @@ int mfcc_hip_bank_push(mfcc_hip_bank *b, const int16_t *samples, const size_t *o
                        size_t *frame_offsets) {
     if (!b || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
     mfcc_hip_handle *h = b->h;
-    const size_t W = row_width(h->r), esz = b->fixed ? sizeof(int16_t) : sizeof(float);
+    const size_t W = bank_row_width(b), esz = b->fixed ? sizeof(int16_t) : sizeof(float);
     // the plan first: a refused push must not have copied anything
-    int rc = bank_plan_raw(size_t(h->r.nfft), size_t(h->r.hop), b->pending.data(), offsets, b->n, frame_offsets, nullptr);
+    int rc = bank_plan_lagged(size_t(h->r.nfft), size_t(h->r.hop), size_t(b->lag), b->pending.data(), b->held.data(), offsets,
+                              b->n, frame_offsets, nullptr, nullptr, nullptr);
     if (rc) return rc;
     const size_t total = frame_offsets[b->n], span = offsets[b->n] - offsets[0];
     if (total && (!out || out_capacity < total * W)) return MFCC_HIP_ERROR_BUFFER_SMALL;
@@ -2714,7 +3022,8 @@ int mfcc_hip_bank_push(mfcc_hip_bank *b, const int16_t *samples, const size_t *o
     if ((rc = ensure(h, &b->st_out, &b->st_out_bytes, total * W * esz + 64))) return rc;
     HIP_TRY(h, hipMemcpyAsync(b->st_in, samples + offsets[0], span * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
     const int16_t *d = static_cast<const int16_t *>(b->st_in);
-    rc = b->fixed ? bank_advance<int16_t>(b, d, offsets[0], offsets, static_cast<int16_t *>(b->st_out), total * W, frame_offsets)
+    rc = b->online ? online_advance(b, d, offsets[0], offsets, static_cast<float *>(b->st_out), total * W, frame_offsets)
+         : b->fixed ? bank_advance<int16_t>(b, d, offsets[0], offsets, static_cast<int16_t *>(b->st_out), total * W, frame_offsets)
                   : bank_advance<float>(b, d, offsets[0], offsets, static_cast<float *>(b->st_out), total * W, frame_offsets);
     if (!rc && total) HIP_TRY(h, hipMemcpyAsync(out, b->st_out, total * W * esz, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));        // `samples` and `out` belong to the caller again
@@ -2727,11 +3036,15 @@ int mfcc_hip_bank_flush(mfcc_hip_bank *b, const size_t *streams, size_t n, void 
     std::vector<size_t> list;
     const int rc = bank_list(b, streams, n, list);
     if (rc) return rc;
+    if (b->lag > 0) return MFCC_HIP_ERROR_UNSUPPORTED;      // ragged output: mfcc_hip_bank_flush_ragged
     const bool emit = b->h->r.pad_mode == MFCC_HIP_PAD_STREAM;
     const size_t nf = emit ? list.size() : 0;
     if (n_frames_out) *n_frames_out = nf;
-    if (nf && (!out || out_capacity < nf * row_width(b->h->r))) return MFCC_HIP_ERROR_BUFFER_SMALL;
-    return bank_tail(b, list, emit, out);
+    if (nf && (!out || out_capacity < nf * bank_row_width(b))) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    if (!b->online) return bank_tail(b, list, emit, out);
+    std::vector<size_t> fo(list.size() + 1);
+    bank_flush_offsets(b, list, fo.data());
+    return online_tail(b, list, emit, out, fo.data());
 }
 
 int mfcc_hip_bank_reset(mfcc_hip_bank *b, const size_t *streams, size_t n) {
