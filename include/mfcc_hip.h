@@ -583,6 +583,99 @@ int  mfcc_hip_serial_unpack(const uint8_t *bytes, size_t n_bytes, int n_cep, int
  * reference accumulates in a 32-bit int); returns 1 if it reaches the reference's threshold 1e8,
  * 0 if not, negative on bad arguments.                                                       */
 int  mfcc_hip_eval_power(const int16_t *window, int n_cep, int n_frames, size_t head, long long *power_out);
+/* The same with the reference's own accumulator, a 32-bit `int`: *power_out gets the low 32 bits of the sum read as a
+ * signed number, and the return value compares THAT with 1e8.  The C standard leaves signed overflow undefined; this is
+ * what the reference's loop gives when built with gcc on x86-64 (two's-complement wrap), and what a receiver built that
+ * way decides: two coefficients of -32768 sum to 2^31 and do NOT pass, four of them sum to 0.                    */
+int  mfcc_hip_eval_power32(const int16_t *window, int n_cep, int n_frames, size_t head, int32_t *power_out);
+
+/* ---- the power gate and window extraction on fixed-point rows (DESIGN.md sections 4.10, 6c-quater) ---------------------
+ * The receiver (software/cepstrum.c:93-183) keeps the last n_frames columns of n_cep int16 coefficients, sums c0^2 over
+ * the middle third of that window and lets the window through when the sum reaches POWER_THRESHOLD.  Here: the same
+ * decision for EVERY window of int16 rows in HBM, and the extraction of the windows a mask keeps.
+ * Rows are int16 [row][n_cep], n_cep 1..64 (what the fixed-point entry points and a fixed bank write).  A segment is one
+ * channel or one utterance of T rows.  With n_frames 1..MFCC_HIP_MAX_GATE_WINDOW, stride 1..MFCC_HIP_MAX_GATE_WINDOW and
+ * threshold >= 0 (MFCC_HIP_POWER_THRESHOLD is the reference's):
+ *     n_win    = T >= n_frames ? (T - n_frames) / stride + 1 : 0      window j = rows [j stride, j stride + n_frames)
+ *     size     = n_frames n_cep,  first = size / 3,  last = 2 size / 3
+ *     power_j  = sum of x^2 over the elements i = first, first + n_cep, ... < last of window j taken as a linear array
+ *                (head = 0): with K = ceil((last - first) / n_cep) (0 when last == first), f0 = first / n_cep and
+ *                c0 = first % n_cep this is column c0 of frames f0 .. f0 + K - 1 of the window.  c0 is 0 when size / 3
+ *                is a multiple of n_cep (the reference's 16 x 93) and is NOT 0 in general (5 x 4: c0 = 1, f0 = 1, K = 2)
+ *     gate_j     = power_j >= threshold                                   power exact in int64: at most 1366 * 2^30
+ *     gate_ref_j = (long long)(int32_t)(uint32_t)power_j >= threshold     what the reference's 32-bit `int power` holds on
+ *                two's-complement hardware.  The C standard leaves that overflow undefined; this is what gcc on x86-64
+ *                produces (mfcc_hip_eval_power32).  On loud speech the two gates differ.
+ * Everything is integer arithmetic: every entry point, any tiling, any run gives the same bits.  No atomics.
+ * The ABI version and the parameter block are unchanged.                                                         */
+#define MFCC_HIP_MAX_GATE_WINDOW 4096
+#define MFCC_HIP_POWER_THRESHOLD 100000000LL
+/* Host only (no GPU, no handle): win_offsets[n_segs + 1] = running sum of n_win over the segments seg_offsets[k] ..
+ * seg_offsets[k + 1] (rows; n_segs + 1 entries, must not decrease) -- the global window index every output below is
+ * indexed by.  Window counts depend on lengths only.  Bad ranges, NULL arrays, decreasing offsets:
+ * MFCC_HIP_ERROR_INVALID_PARAM.                                                                                */
+int  mfcc_hip_gate_count(int n_frames, int stride, const size_t *seg_offsets, size_t n_segs, size_t *win_offsets);
+/* The decision.  d_rows int16 [seg_offsets[n_segs]][n_cep] (2-byte aligned; rows before seg_offsets[0] are not read);
+ * d_power int64 (8-byte aligned), d_gate and d_gate_ref uint8 0 / 1, one entry per window at the global window index of
+ * mfcc_hip_gate_count; entries beyond the last window are untouched.  Any of the three may be NULL, not all of them.
+ * Inputs and outputs (or two outputs) that overlap, a parameter outside its range, decreasing offsets:
+ * MFCC_HIP_ERROR_INVALID_PARAM.  Asynchronous on the handle's stream; n_segs = 0 or no window at all is a no-op that
+ * does not look at the data pointers (all of them may then be NULL). */
+int  mfcc_hip_gate_dev(mfcc_hip_handle *h, const void *d_rows, int n_cep, const size_t *seg_offsets, size_t n_segs,
+                       int n_frames, int stride, long long threshold, void *d_power, void *d_gate, void *d_gate_ref);
+/* The selection: the windows whose d_mask byte (one per window, global window index; the gate bytes, the reference bytes
+ * or anything computed from d_power) is not 0, copied whole to d_out, int16 [n_sel][n_frames][n_cep] (2-byte aligned),
+ * packed in window order; overlapping windows are each copied in full.  d_starts (may be NULL; 8-byte aligned) int64
+ * [n_sel]: the first row of every kept window as an index into d_rows.  out_offsets (HOST, n_segs + 1 entries): the
+ * range of every segment in the packed result.  The count depends on the data: the call counts and scans, SYNCHRONIZES
+ * the handle's stream and reads the total; if out_capacity_windows is below it, MFCC_HIP_ERROR_BUFFER_SMALL with
+ * out_offsets filled and nothing written to d_out or d_starts -- size them from out_offsets[n_segs] and call again (a
+ * first call with capacity 0 and d_out NULL is the way to ask).  Otherwise the copy is enqueued; it is asynchronous.
+ * What is written must not overlap what is read: MFCC_HIP_ERROR_INVALID_PARAM, nothing written.                 */
+int  mfcc_hip_gate_windows_dev(mfcc_hip_handle *h, const void *d_rows, int n_cep, const size_t *seg_offsets, size_t n_segs,
+                               int n_frames, int stride, const void *d_mask, void *d_out, void *d_starts,
+                               size_t out_capacity_windows, size_t *out_offsets);
+
+/* ---- gate tracker: the receiver's circular window for N live lines ------------------------
+ * The batched form of cepstrum_refill_window + cepstrum_eval_power: n_lines independent windows whose state lives on
+ * the device, per line a ring of the last D = n_frames + stride - 1 rows (row t of the line in slot t mod D), and on the
+ * host the frames every line has seen since create / reset.  A push takes exactly what mfcc_hip_bank_push_dev of a fixed
+ * bank leaves behind -- the device rows and the host frame_offsets -- so the two chain on one stream with no synchronize
+ * between them.  Window j of a line starts at the line's absolute frame j stride counted from create / reset.  Contract:
+ * any chunking of a line's rows gives the same windows with the same bytes, and they are the windows of
+ * mfcc_hip_gate_dev / mfcc_hip_gate_windows_dev on the line's whole row sequence as one segment.
+ * A tracker counts as a session of its handle (lifetime rule at mfcc_hip_destroy, MFCC_HIP_ERROR_BUSY of the
+ * mfcc_hip_set_* calls); like the handle it is not thread-safe.                                                  */
+typedef struct mfcc_hip_gate mfcc_hip_gate;
+/* n_lines >= 1, the other parameters in the ranges above; every line starts with no frame seen */
+int    mfcc_hip_gate_create(mfcc_hip_handle *h, size_t n_lines, int n_cep, int n_frames, int stride, long long threshold,
+                            mfcc_hip_gate **out);
+/* frees the ring (waits for the tracker's work first); frees the handle too if that was already given to
+ * mfcc_hip_destroy and this was its last session */
+void   mfcc_hip_gate_destroy(mfcc_hip_gate *g);
+/* seen[n_lines]: frames every line has received since create / reset (a host mirror, no device traffic) */
+int    mfcc_hip_gate_seen(const mfcc_hip_gate *g, size_t *seen);
+/* The plan of a push, host only (no GPU, no handle).  Line u has seen[u] = s frames and receives
+ * nf = frame_offsets[u + 1] - frame_offsets[u] more; it completes the windows j with s <= j stride + n_frames - 1 < s + nf.
+ * win_offsets[n_lines + 1]: the running sum of their counts; seen_after[n_lines] (may be NULL) = s + nf. */
+int    mfcc_hip_gate_plan(int n_frames, int stride, const size_t *seen, const size_t *frame_offsets, size_t n_lines,
+                          size_t *win_offsets, size_t *seen_after);
+/* Feed every line its new rows: line u gets rows frame_offsets[u] .. frame_offsets[u + 1] of d_rows (int16 [..][n_cep],
+ * 2-byte aligned; n_lines + 1 offsets, not decreasing; a range may be empty).  Per completed window, in line order then
+ * window order, entries win_offsets[u] .. win_offsets[u + 1] of d_power / d_gate / d_gate_ref as for mfcc_hip_gate_dev
+ * (any may be NULL; not all when a window completes).  capacity_windows below the total: MFCC_HIP_ERROR_BUFFER_SMALL;
+ * that and MFCC_HIP_ERROR_INVALID_PARAM fill win_offsets where they can and consume NOTHING.  Asynchronous on the
+ * handle's stream, no synchronize and no device-to-host copy; d_rows must stay valid until the stream has run it. */
+int    mfcc_hip_gate_push_dev(mfcc_hip_gate *g, const void *d_rows, const size_t *frame_offsets, void *d_power, void *d_gate,
+                              void *d_gate_ref, size_t capacity_windows, size_t *win_offsets);
+/* The listed lines (lines == NULL: all, n is not read; otherwise n distinct indices below n_lines, else
+ * MFCC_HIP_ERROR_INVALID_PARAM and nothing is done) start again at frame 0.  Only the frame counts are zeroed: a line
+ * that has seen nothing reads nothing of its ring.  Ordered on the stream behind the pushes before it; does not wait. */
+int    mfcc_hip_gate_reset(mfcc_hip_gate *g, const size_t *lines, size_t n);
+/* For each listed line the rows of its last completed window, d_out int16 [n][n_frames][n_cep] in the order listed.
+ * A listed line that has completed no window since create / reset, or a repeated or out-of-range index:
+ * MFCC_HIP_ERROR_INVALID_PARAM and nothing is written.  Asynchronous on the handle's stream. */
+int    mfcc_hip_gate_window_dev(mfcc_hip_gate *g, const size_t *lines, size_t n, void *d_out);
 
 #ifdef __cplusplus
 }

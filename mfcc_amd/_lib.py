@@ -45,6 +45,8 @@ VAD_SELECT = 1
 MAX_DELTA_WINDOW = 8
 MAX_VAD_CONTEXT = 64
 MAX_NORMALIZE_WINDOW = 16384
+MAX_GATE_WINDOW = 4096
+POWER_THRESHOLD = 100000000
 
 TABLE_WINDOW_F32 = 0
 TABLE_MEL_POINTS_I32 = 1
@@ -149,6 +151,20 @@ SYMBOLS = {
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "mfcc_hip_bank_flush_ragged": (C.c_int, [_H, C.c_void_p, _SZ, C.c_void_p, _SZ, C.c_void_p]),
     "mfcc_hip_lift_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_double, _PSZ]),
+    "mfcc_hip_eval_power32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int32)]),
+    "mfcc_hip_gate_count": (C.c_int, [C.c_int, C.c_int, C.c_void_p, _SZ, C.c_void_p]),
+    "mfcc_hip_gate_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, _SZ, C.c_int, C.c_int, C.c_longlong, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "mfcc_hip_gate_windows_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, _SZ, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, _SZ, C.c_void_p]),
+    "mfcc_hip_gate_create": (C.c_int, [_H, _SZ, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(_H)]),
+    "mfcc_hip_gate_destroy": (None, [_H]),
+    "mfcc_hip_gate_seen": (C.c_int, [_H, C.c_void_p]),
+    "mfcc_hip_gate_plan": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, _SZ, C.c_void_p, C.c_void_p]),
+    "mfcc_hip_gate_push_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _SZ,
+                                         C.c_void_p]),
+    "mfcc_hip_gate_reset": (C.c_int, [_H, C.c_void_p, _SZ]),
+    "mfcc_hip_gate_window_dev": (C.c_int, [_H, C.c_void_p, _SZ, C.c_void_p]),
 }
 
 _lib = None

@@ -695,6 +695,114 @@ class MFCC:
         return MfccStreamBank(self, n_streams, fixed, normalize=normalize, normalize_window=normalize_window,
                               deltas=deltas, delta_window=delta_window)
 
+    # -- the receiver's power gate on fixed-point rows (software/cepstrum.c:93-183; include/mfcc_hip.h) -----
+    def _gate_rows_in(self, rows, frame_offsets):
+        """``rows`` as a contiguous CUDA int16 tensor (a NumPy array is copied in: the flag says so), its segment
+        offsets as a uint64 array and the row width."""
+        import torch
+        from_numpy = not _is_torch(rows)
+        if from_numpy:
+            rows = np.ascontiguousarray(rows)
+            if rows.dtype != np.int16:
+                raise TypeError("rows must be int16 (what process_fixed returns)")
+            dev = torch.device("cuda", torch.cuda.current_device() if self._device_index is None else self._device_index)
+            rows = torch.from_numpy(rows).to(dev)
+        if rows.dtype != torch.int16 or not rows.is_cuda or not rows.is_contiguous() or rows.dim() not in (2, 3):
+            raise TypeError("rows must be a contiguous 2-D or 3-D CUDA(HIP) int16 tensor")
+        width = int(rows.shape[-1])
+        if not 1 <= width <= 64:
+            raise ValueError("rows must be 1..64 wide, not %d" % width)
+        if frame_offsets is None:
+            nseg = int(rows.shape[0]) if rows.dim() == 3 else 1
+            per = int(rows.shape[1]) if rows.dim() == 3 else int(rows.shape[0])
+            fo = np.arange(nseg + 1, dtype=np.uint64) * np.uint64(per)
+        else:
+            fo = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
+            if fo.ndim != 1 or len(fo) < 1:
+                raise ValueError("frame_offsets must be 1-D with n_segments + 1 entries")
+            if len(fo) > 1 and int(np.diff(fo.astype(np.int64)).min()) < 0:
+                raise ValueError("frame_offsets must not decrease")
+            if int(fo[-1]) * width > rows.numel():
+                raise ValueError("frame_offsets run past the end of rows")
+        self._check_device(rows)
+        return rows, fo, width, from_numpy
+
+    def gate_rows(self, rows, frame_offsets=None, n_frames=93, stride=1, threshold=None):
+        """The receiver's power gate for EVERY window of int16 rows, on the current torch stream.  ``rows``: a CUDA int16
+        tensor ``(rows, n_cep)`` with ``frame_offsets`` (segment ``u`` = rows ``fo[u]:fo[u + 1]``, e.g. what
+        ``process_packed(..., fixed=True)`` returns) or, without them, one segment; ``(channels, rows, n_cep)``: one
+        segment per channel.  Window ``j`` of a segment is its rows ``[j * stride, j * stride + n_frames)``.  Returns
+        ``(power, gate, gate_ref, win_offsets)``: per window the exact int64 sum of squares the reference's loop forms,
+        ``power >= threshold`` (uint8) and the same test on the sum as the reference's 32-bit ``int`` holds it (uint8);
+        segment ``u``'s windows are entries ``win_offsets[u]:win_offsets[u + 1]``.  ``threshold`` defaults to
+        ``wire.POWER_THRESHOLD``.  A NumPy array goes through one copy in and one copy out."""
+        import torch
+        from . import wire
+        nfr, st, thr = wire.gate_args(n_frames, stride, wire.POWER_THRESHOLD if threshold is None else threshold)
+        rows, fo, width, from_numpy = self._gate_rows_in(rows, frame_offsets)
+        wo = wire.gate_count(fo, nfr, st, offsets=True)
+        n = int(wo[-1])
+        power = torch.empty(n, device=rows.device, dtype=torch.int64)
+        gate = torch.empty(n, device=rows.device, dtype=torch.uint8)
+        gate_ref = torch.empty(n, device=rows.device, dtype=torch.uint8)
+        with self._on_torch_stream(rows.device):
+            _lib.check(self._lib.mfcc_hip_gate_dev(self._h, C.c_void_p(rows.data_ptr()), width,
+                                                   fo.ctypes.data_as(C.c_void_p), len(fo) - 1, nfr, st, thr,
+                                                   C.c_void_p(power.data_ptr()), C.c_void_p(gate.data_ptr()),
+                                                   C.c_void_p(gate_ref.data_ptr())), "gate_dev")
+        if from_numpy:
+            return power.cpu().numpy(), gate.cpu().numpy(), gate_ref.cpu().numpy(), wo
+        return power, gate, gate_ref, wo
+
+    def gate_windows(self, rows, mask, frame_offsets=None, n_frames=93, stride=1, out=None):
+        """The windows of ``rows`` (as in :meth:`gate_rows`) whose ``mask`` byte is not 0 -- ``mask``: uint8, one entry per
+        window in the order of :meth:`gate_rows`' outputs, e.g. its ``gate`` or ``gate_ref`` -- copied whole and packed in
+        order: returns ``(windows (n, n_frames, n_cep), starts, out_offsets)`` with ``starts`` (int64) the first row of
+        every kept window as an index into ``rows`` (flattened to 2-D) and segment ``u``'s windows in
+        ``out_offsets[u]:out_offsets[u + 1]``.  Without ``out`` a first call asks for the count
+        (``MFCC_HIP_ERROR_BUFFER_SMALL`` fills the offsets) and the result is sized from it; with ``out``
+        (``(capacity, n_frames, n_cep)``) too small a capacity raises that error.  Waits for the stream once: the count
+        depends on the data."""
+        import torch
+        from . import wire
+        nfr, st, _ = wire.gate_args(n_frames, stride)
+        rows, fo, width, from_numpy = self._gate_rows_in(rows, frame_offsets)
+        wo = wire.gate_count(fo, nfr, st, offsets=True)
+        if not _is_torch(mask):
+            mask = torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)).to(rows.device)
+        if mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.device != rows.device or \
+                mask.numel() != int(wo[-1]):
+            raise ValueError("mask must be a contiguous uint8 tensor of %d entries on %s" % (int(wo[-1]), rows.device))
+        oo = np.zeros(len(fo), dtype=np.uint64)
+
+        def call(o, starts, cap):
+            with self._on_torch_stream(rows.device):
+                return self._lib.mfcc_hip_gate_windows_dev(
+                    self._h, C.c_void_p(rows.data_ptr()), width, fo.ctypes.data_as(C.c_void_p), len(fo) - 1, nfr, st,
+                    C.c_void_p(mask.data_ptr()), C.c_void_p(o.data_ptr() if o is not None else 0),
+                    C.c_void_p(starts.data_ptr() if starts is not None else 0), cap, oo.ctypes.data_as(C.c_void_p))
+        if out is None:
+            rc = call(None, None, 0)
+            if rc not in (_lib.SUCCESS, _lib.ERROR_BUFFER_SMALL):
+                _lib.check(rc, "gate_windows_dev")
+            out = torch.empty((int(oo[-1]), nfr, width), device=rows.device, dtype=torch.int16)
+        elif out.dim() != 3 or tuple(out.shape[1:]) != (nfr, width) or out.dtype != torch.int16 or \
+                not out.is_contiguous() or out.device != rows.device:
+            raise ValueError("out must be a contiguous int16 tensor of shape (capacity, %d, %d) on %s"
+                             % (nfr, width, rows.device))
+        starts = torch.empty(int(out.shape[0]), device=rows.device, dtype=torch.int64)
+        _lib.check(call(out, starts, int(out.shape[0])), "gate_windows_dev")
+        n = int(oo[-1])
+        if from_numpy:
+            return out[:n].cpu().numpy(), starts[:n].cpu().numpy(), oo
+        return out[:n], starts[:n], oo
+
+    def power_gate(self, n_lines, n_cep=None, n_frames=93, stride=1, threshold=None) -> "MfccPowerGate":
+        """A gate tracker for ``n_lines`` live lines on this handle: the receiver's circular window of ``n_frames`` rows
+        of ``n_cep`` (default: this handle's ``nceptrums``) coefficients per line, fed with what a fixed
+        :meth:`stream_bank` returns."""
+        return MfccPowerGate(self, n_lines, self.nceptrums if n_cep is None else n_cep, n_frames, stride, threshold)
+
     # -- file level: mfcc_convert(sess, path_in, path_out), software/main.c:100-177 -----
     def convert_many(self, paths_in, paths_out, fixed=True):
         """``mfcc_convert`` for many files in one ragged launch; returns the frame count of each file."""
@@ -958,6 +1066,132 @@ class MfccStreamBank:
         s, n = self._streams(streams)
         _lib.check(self._lib.mfcc_hip_bank_reset(self._b, None if s is None else s.ctypes.data_as(C.c_void_p), n),
                    "bank_reset")
+
+
+class MfccPowerGate:
+    """The receiver's circular window and power gate (``cepstrum_refill_window`` + ``cepstrum_eval_power``,
+    software/cepstrum.c:93-183) for ``n_lines`` live lines, state on the device.  Window ``j`` of a line is its rows
+    ``[j * stride, j * stride + n_frames)`` counted from create / reset; any chunking gives the windows, bit for bit, of
+    :meth:`MFCC.gate_rows` on the line's whole row sequence."""
+
+    def __init__(self, mfcc: MFCC, n_lines, n_cep, n_frames=93, stride=1, threshold=None):
+        from . import wire
+        self._m = mfcc
+        self._lib = mfcc._lib
+        self.n_lines = int(n_lines)
+        if self.n_lines < 1:
+            raise ValueError("a gate needs at least one line")
+        self.n_frames, self.stride, self.threshold = wire.gate_args(
+            n_frames, stride, wire.POWER_THRESHOLD if threshold is None else threshold, n_cep=n_cep)
+        self.n_cep = int(n_cep)
+        g = C.c_void_p()
+        _lib.check(self._lib.mfcc_hip_gate_create(mfcc._h, self.n_lines, self.n_cep, self.n_frames, self.stride,
+                                                  self.threshold, C.byref(g)), "gate_create")
+        self._g = g
+
+    def close(self):
+        # either order is safe: a handle closed first is kept alive by the library until its last session goes
+        if getattr(self, "_g", None):
+            self._lib.mfcc_hip_gate_destroy(self._g)
+        self._g = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __len__(self):
+        return self.n_lines
+
+    @property
+    def seen(self) -> np.ndarray:
+        """Frames every line has received since create / reset: uint64 ``(n_lines,)`` (a host mirror)."""
+        p = np.zeros(self.n_lines, dtype=np.uint64)
+        _lib.check(self._lib.mfcc_hip_gate_seen(self._g, p.ctypes.data_as(C.c_void_p)), "gate_seen")
+        return p
+
+    def num_windows(self, frame_offsets) -> np.ndarray:
+        """``win_offsets`` a push with these ``frame_offsets`` would give now (host only: ``mfcc_hip_gate_plan``)."""
+        fo = self._offsets(frame_offsets)
+        wo = np.zeros(self.n_lines + 1, dtype=np.uint64)
+        seen = self.seen
+        _lib.check(self._lib.mfcc_hip_gate_plan(self.n_frames, self.stride, seen.ctypes.data_as(C.c_void_p),
+                                                fo.ctypes.data_as(C.c_void_p), self.n_lines,
+                                                wo.ctypes.data_as(C.c_void_p), None), "gate_plan")
+        return wo
+
+    def _offsets(self, frame_offsets):
+        fo = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
+        if fo.ndim != 1 or len(fo) != self.n_lines + 1:
+            raise ValueError("frame_offsets must be 1-D with n_lines + 1 = %d entries" % (self.n_lines + 1))
+        if int(np.diff(fo.astype(np.int64)).min()) < 0:
+            raise ValueError("frame_offsets must not decrease")
+        return fo
+
+    def push(self, rows, frame_offsets):
+        """Feed every line its new rows: ``rows`` int16 ``(sum rows, n_cep)`` with line ``u``'s in
+        ``rows[fo[u]:fo[u + 1]]`` -- exactly what ``MfccStreamBank.push_packed`` of a fixed bank returns.  A CUDA tensor
+        is used in place, asynchronously on the current torch stream (nothing is copied to the host, nothing waits); a
+        NumPy array goes through one copy in and one copy out.  Returns ``(power, gate, gate_ref, win_offsets)`` for the
+        windows this push completed, line ``u``'s in entries ``win_offsets[u]:win_offsets[u + 1]``."""
+        import torch
+        from_numpy = not _is_torch(rows)
+        if from_numpy:
+            rows = np.ascontiguousarray(rows)
+            if rows.dtype != np.int16:
+                raise TypeError("rows must be int16")
+            rows = torch.from_numpy(rows).to(torch.device("cuda", self._m._device_index or 0)
+                                             if self._m._device_index is not None else "cuda")
+        if rows.dtype != torch.int16 or not rows.is_cuda or not rows.is_contiguous() or rows.dim() != 2 or \
+                int(rows.shape[1]) != self.n_cep:
+            raise TypeError("rows must be a contiguous CUDA(HIP) int16 tensor of shape (rows, %d)" % self.n_cep)
+        fo = self._offsets(frame_offsets)
+        if int(fo[-1]) > int(rows.shape[0]):
+            raise ValueError("frame_offsets run past the end of rows")
+        self._m._check_device(rows)
+        n = int(self.num_windows(fo)[-1])
+        power = torch.empty(n, device=rows.device, dtype=torch.int64)
+        gate = torch.empty(n, device=rows.device, dtype=torch.uint8)
+        gate_ref = torch.empty(n, device=rows.device, dtype=torch.uint8)
+        wo = np.zeros(self.n_lines + 1, dtype=np.uint64)
+        with self._m._on_torch_stream(rows.device):
+            _lib.check(self._lib.mfcc_hip_gate_push_dev(self._g, C.c_void_p(rows.data_ptr()),
+                                                        fo.ctypes.data_as(C.c_void_p), C.c_void_p(power.data_ptr()),
+                                                        C.c_void_p(gate.data_ptr()), C.c_void_p(gate_ref.data_ptr()), n,
+                                                        wo.ctypes.data_as(C.c_void_p)), "gate_push_dev")
+        assert int(wo[-1]) == n
+        if from_numpy:
+            return power.cpu().numpy(), gate.cpu().numpy(), gate_ref.cpu().numpy(), wo
+        return power, gate, gate_ref, wo
+
+    def _lines(self, lines):
+        if lines is None:
+            return None, self.n_lines
+        s = np.ascontiguousarray(lines, dtype=np.uint64).reshape(-1)
+        return s, len(s)
+
+    def reset(self, lines=None):
+        """The listed lines (``None``: all) start again at frame 0."""
+        s, n = self._lines(lines)
+        _lib.check(self._lib.mfcc_hip_gate_reset(self._g, None if s is None else s.ctypes.data_as(C.c_void_p), n),
+                   "gate_reset")
+
+    def last_windows(self, lines):
+        """The rows of the last completed window of every listed line: a CUDA int16 tensor
+        ``(len(lines), n_frames, n_cep)`` on the current torch stream.  A line that has completed no window since
+        create / reset raises ``INVALID_PARAM``."""
+        import torch
+        s, n = self._lines(np.arange(self.n_lines) if lines is None else lines)
+        m = self._m
+        dev = torch.device("cuda", torch.cuda.current_device() if m._device_index is None else m._device_index)
+        out = torch.empty((n, self.n_frames, self.n_cep), device=dev, dtype=torch.int16)
+        with m._on_torch_stream(dev):
+            _lib.check(self._lib.mfcc_hip_gate_window_dev(self._g, s.ctypes.data_as(C.c_void_p), n,
+                                                          C.c_void_p(out.data_ptr())), "gate_window_dev")
+        return out
 
 
 def lift_file(mfcc_in, lift_out, nceptrums=32, L=22) -> int:

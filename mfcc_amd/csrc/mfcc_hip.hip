@@ -30,6 +30,7 @@
 #include "kernel_vad.hpp"
 #include "kernel_stream_bank.hpp"
 #include "kernel_stream_bank_online.hpp"
+#include "kernel_gate.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -3053,6 +3054,406 @@ int mfcc_hip_bank_reset(mfcc_hip_bank *b, const size_t *streams, size_t n) {
     const int rc = bank_list(b, streams, n, list);
     if (rc) return rc;
     return bank_tail(b, list, false, nullptr);
+}
+
+}  // extern "C"
+
+// ---- the receiver's power gate and window extraction on int16 rows (kernel_gate.hpp, DESIGN.md sections 4.10 and
+// 6c-quater).  The one-shot entries tile the WINDOW index space of the segments; the tracker keeps a ring of rows per
+// line on the device and its frame counts on the host.
+struct mfcc_hip_gate {
+    mfcc_hip_handle *h = nullptr;
+    size_t n = 0;                        // lines
+    mfcc_gate::Geo g{};
+    int D = 0;                           // ring depth: n_frames + stride - 1
+    long long threshold = 0;
+    int16_t *d_ring = nullptr;           // [n][D][n_cep]
+    std::vector<size_t> seen;            // frames since create / reset: depends on chunk lengths only
+};
+
+namespace {
+
+inline size_t gate_windows(size_t T, size_t n_frames, size_t stride) {
+    return T >= n_frames ? (T - n_frames) / stride + 1 : 0;
+}
+
+inline bool gate_shape_ok(int n_cep, int n_frames, int stride) {
+    return n_cep >= 1 && n_cep <= mfcc_gate::kMaxWidth && n_frames >= 1 && n_frames <= MFCC_HIP_MAX_GATE_WINDOW &&
+           stride >= 1 && stride <= MFCC_HIP_MAX_GATE_WINDOW;
+}
+
+// win_offsets (n_segs + 1) of segments off; INVALID_PARAM where off decreases
+int gate_count(size_t n_frames, size_t stride, const size_t *off, size_t n_segs, size_t *win_offsets) {
+    win_offsets[0] = 0;
+    for (size_t k = 0; k < n_segs; ++k) {
+        if (off[k + 1] < off[k]) return MFCC_HIP_ERROR_INVALID_PARAM;
+        win_offsets[k + 1] = win_offsets[k] + gate_windows(off[k + 1] - off[k], n_frames, stride);
+    }
+    return MFCC_HIP_SUCCESS;
+}
+
+// The tiles of tw windows of segments off[0 .. n_segs] (rows; wo their window offsets, wo[n_segs] > 0): the uniform form
+// when every segment has one length, else the table form in pinned memory: [first tile of every segment (n_segs + 1)]
+// [delta (n_segs)][one record per tile], not yet on the device (gate_wins_upload)
+int gate_wins(mfcc_hip_handle *h, const size_t *off, const size_t *wo, size_t n_segs, size_t stride, size_t tw,
+              mfcc_gate::Wins &w, size_t &table_ll, mfcc_hip_handle::PinnedDesc *&pd) {
+    w = mfcc_gate::Wins{};
+    w.s.width = 1;
+    w.s.tile_rows = int(tw);
+    w.s.n_segs = (long long)n_segs;
+    table_ll = 0;
+    pd = nullptr;
+    const size_t len0 = off[1] - off[0];
+    bool uniform = true;
+    for (size_t k = 1; k < n_segs && uniform; ++k) uniform = off[k + 1] - off[k] == len0;
+    if (uniform) {
+        const size_t nw = wo[1] - wo[0];
+        w.s.seg_rows = (long long)nw;
+        w.s.blocks_per_seg = (long long)((nw + tw - 1) / tw);
+        w.s.n_blocks = w.s.blocks_per_seg * w.s.n_segs;
+        w.base_row = (long long)off[0];
+        w.seg_rows = (long long)len0;
+        return MFCC_HIP_SUCCESS;
+    }
+    size_t n_blocks = 0;
+    for (size_t k = 0; k < n_segs; ++k) n_blocks += (wo[k + 1] - wo[k] + tw - 1) / tw;
+    if (n_segs >= (size_t(1) << 31)) return MFCC_HIP_ERROR_INVALID_PARAM;       // BlockRec::seg is an int
+    table_ll = 2 * n_segs + 1 + 2 * n_blocks;
+    const int rc = desc_acquire(h, table_ll, &pd);
+    if (rc) return rc;
+    long long *blk0 = pd->p, *delta = pd->p + n_segs + 1;
+    auto *rec = reinterpret_cast<mfcc_norm::BlockRec *>(pd->p + 2 * n_segs + 1);
+    size_t b = 0;
+    for (size_t k = 0; k < n_segs; ++k) {
+        blk0[k] = (long long)b;
+        delta[k] = (long long)off[k] - (long long)(wo[k] * stride);
+        for (size_t q = wo[k]; q < wo[k + 1]; q += tw)
+            rec[b++] = mfcc_norm::BlockRec{(long long)q, int(std::min(tw, wo[k + 1] - q)), int(k)};
+    }
+    blk0[n_segs] = (long long)b;
+    w.s.n_blocks = (long long)n_blocks;
+    return MFCC_HIP_SUCCESS;
+}
+
+int gate_wins_upload(mfcc_hip_handle *h, mfcc_gate::Wins &w, size_t table_ll, mfcc_hip_handle::PinnedDesc *pd,
+                     long long *d_table) {
+    if (!pd) return MFCC_HIP_SUCCESS;
+    HIP_TRY(h, hipMemcpyAsync(d_table, pd->p, table_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    w.s.seg_blk0 = d_table;
+    w.delta = d_table + w.s.n_segs + 1;
+    w.s.blk = reinterpret_cast<const mfcc_norm::BlockRec *>(d_table + 2 * w.s.n_segs + 1);
+    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
+    pd->in_flight = true;
+    return MFCC_HIP_SUCCESS;
+}
+
+inline bool ranges_overlap(uintptr_t a_lo, uintptr_t a_hi, uintptr_t b_lo, uintptr_t b_hi) {
+    return a_lo < b_hi && b_lo < a_hi;
+}
+
+inline unsigned gate_grid(const mfcc_hip_handle *h, long long want) {
+    return unsigned(std::max<long long>(1, std::min<long long>(want, (long long)h->n_cu * 8)));
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfcc_hip_eval_power32(const int16_t *window, int n_cep, int n_frames, size_t head, int32_t *power_out) {
+    if (!window || n_cep <= 0 || n_frames <= 0) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const size_t size = size_t(n_cep) * size_t(n_frames);
+    if (head >= size) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const size_t first = 1 * size / 3, last = 2 * size / 3;
+    uint32_t acc = 0;                                  // the reference's `int power`, wrapping as two's complement
+    for (size_t i = first; i < last; i += size_t(n_cep)) {
+        size_t k = head + i;
+        if (k >= size) k -= size;
+        acc += uint32_t(int32_t(window[k]) * int32_t(window[k]));
+    }
+    const int32_t power = int32_t(acc);
+    if (power_out) *power_out = power;
+    return power >= 100000000 ? 1 : 0;                 // POWER_THRESHOLD, cepstrum.c:13
+}
+
+int mfcc_hip_gate_count(int n_frames, int stride, const size_t *seg_offsets, size_t n_segs, size_t *win_offsets) {
+    if (!gate_shape_ok(1, n_frames, stride) || !win_offsets || (n_segs && !seg_offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    return gate_count(size_t(n_frames), size_t(stride), seg_offsets, n_segs, win_offsets);
+}
+
+int mfcc_hip_gate_dev(mfcc_hip_handle *h, const void *d_rows, int n_cep, const size_t *seg_offsets, size_t n_segs,
+                      int n_frames, int stride, long long threshold, void *d_power, void *d_gate, void *d_gate_ref) {
+    static_assert(MFCC_HIP_MAX_GATE_WINDOW == mfcc_gate::kMaxWindow, "window limit");
+    if (!h || !gate_shape_ok(n_cep, n_frames, stride) || threshold < 0 || (n_segs && !seg_offsets))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::vector<size_t> wo(n_segs + 1);
+    int rc = gate_count(size_t(n_frames), size_t(stride), seg_offsets, n_segs, wo.data());
+    if (rc) return rc;
+    const size_t total = wo[n_segs];
+    if (total == 0) return MFCC_HIP_SUCCESS;                 // nothing to write: the pointers are not looked at
+    if (!d_power && !d_gate && !d_gate_ref) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!d_rows || (reinterpret_cast<uintptr_t>(d_rows) & 1) || (reinterpret_cast<uintptr_t>(d_power) & 7))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    // the rows read and the entries written must not overlap
+    const size_t row_bytes = size_t(n_cep) * sizeof(int16_t);
+    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(d_rows) + seg_offsets[0] * row_bytes;
+    const uintptr_t in_hi = reinterpret_cast<uintptr_t>(d_rows) + seg_offsets[n_segs] * row_bytes;
+    const uintptr_t o[3] = {reinterpret_cast<uintptr_t>(d_power), reinterpret_cast<uintptr_t>(d_gate),
+                            reinterpret_cast<uintptr_t>(d_gate_ref)};
+    const size_t ob[3] = {total * sizeof(long long), total, total};
+    for (int i = 0; i < 3; ++i) {
+        if (!o[i]) continue;
+        if (ranges_overlap(in_lo, in_hi, o[i], o[i] + ob[i])) return MFCC_HIP_ERROR_INVALID_PARAM;
+        for (int j = i + 1; j < 3; ++j)
+            if (o[j] && ranges_overlap(o[i], o[i] + ob[i], o[j], o[j] + ob[j])) return MFCC_HIP_ERROR_INVALID_PARAM;
+    }
+    DeviceGuard guard(h->device);
+    const mfcc_gate::Geo g = mfcc_gate::geometry(n_cep, n_frames, stride);
+    mfcc_gate::Wins w;
+    size_t table_ll = 0;
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    if ((rc = gate_wins(h, seg_offsets, wo.data(), n_segs, size_t(stride), size_t(mfcc_gate::power_tile_wins(g.K, stride)), w,
+                        table_ll, pd)))
+        return rc;
+    if ((rc = ensure(h, &h->d_sel, &h->d_sel_bytes, table_ll * sizeof(long long) + 64))) return rc;
+    if ((rc = scratch_acquire(h))) return rc;
+    if ((rc = gate_wins_upload(h, w, table_ll, pd, static_cast<long long *>(h->d_sel)))) return rc;
+    hipLaunchKernelGGL(mfcc_gate::gate_power_kernel, dim3(gate_grid(h, w.s.n_blocks)), dim3(mfcc_gate::kThreads), 0, h->stream,
+                       static_cast<const int16_t *>(d_rows), w, g, threshold, static_cast<long long *>(d_power),
+                       static_cast<unsigned char *>(d_gate), static_cast<unsigned char *>(d_gate_ref));
+    HIP_TRY(h, hipGetLastError());
+    return scratch_release(h);
+}
+
+int mfcc_hip_gate_windows_dev(mfcc_hip_handle *h, const void *d_rows, int n_cep, const size_t *seg_offsets, size_t n_segs,
+                              int n_frames, int stride, const void *d_mask, void *d_out, void *d_starts,
+                              size_t out_capacity_windows, size_t *out_offsets) {
+    if (!h || !gate_shape_ok(n_cep, n_frames, stride) || (n_segs && (!seg_offsets || !out_offsets)))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::vector<size_t> wo(n_segs + 1);
+    int rc = gate_count(size_t(n_frames), size_t(stride), seg_offsets, n_segs, wo.data());
+    if (rc) return rc;
+    const size_t total = wo[n_segs];
+    if (total == 0) {
+        for (size_t k = 0; k <= n_segs && out_offsets; ++k) out_offsets[k] = 0;
+        return MFCC_HIP_SUCCESS;
+    }
+    if (!d_rows || !d_mask || (reinterpret_cast<uintptr_t>(d_rows) & 1) || (reinterpret_cast<uintptr_t>(d_out) & 1) ||
+        (reinterpret_cast<uintptr_t>(d_starts) & 7))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    const mfcc_gate::Geo g = mfcc_gate::geometry(n_cep, n_frames, stride);
+    mfcc_gate::Wins w;
+    size_t table_ll = 0;
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    if ((rc = gate_wins(h, seg_offsets, wo.data(), n_segs, size_t(stride), size_t(mfcc_gate::kSelTileWins), w, table_ll, pd)))
+        return rc;
+    // scratch (h->d_sel): [tile counts][tile prefixes (n_blocks + 1)][segment offsets (n_segs + 1)][tile table]
+    const size_t nb = size_t(w.s.n_blocks);
+    const size_t cnt_b = up256(nb * sizeof(unsigned)), toff_b = up256((nb + 1) * sizeof(long long));
+    const size_t soff_b = up256((n_segs + 1) * sizeof(long long));
+    if ((rc = ensure(h, &h->d_sel, &h->d_sel_bytes, cnt_b + toff_b + soff_b + table_ll * sizeof(long long) + 64))) return rc;
+    if ((rc = scratch_acquire(h))) return rc;
+    char *base = static_cast<char *>(h->d_sel);
+    unsigned *counts = reinterpret_cast<unsigned *>(base);
+    long long *tile_off = reinterpret_cast<long long *>(base + cnt_b), *seg_off = reinterpret_cast<long long *>(base + cnt_b + toff_b);
+    if ((rc = gate_wins_upload(h, w, table_ll, pd, reinterpret_cast<long long *>(base + cnt_b + toff_b + soff_b)))) return rc;
+    const unsigned grid = gate_grid(h, w.s.n_blocks);
+    const unsigned char *mask = static_cast<const unsigned char *>(d_mask);
+    // counts and prefix over the window index space: the selection's own kernels, which only need tile_of
+    hipLaunchKernelGGL(mfcc_vad::vad_count_kernel, dim3(grid), dim3(mfcc_vad::kThreads), 0, h->stream, mask, w.s, counts);
+    hipLaunchKernelGGL(mfcc_vad::vad_scan_kernel, dim3(1), dim3(mfcc_vad::kScanThreads), 0, h->stream, w.s,
+                       static_cast<const unsigned *>(counts), tile_off, seg_off);
+    HIP_TRY(h, hipGetLastError());
+    static_assert(sizeof(size_t) == sizeof(long long), "segment offsets are copied as they are");
+    HIP_TRY(h, hipMemcpyAsync(out_offsets, seg_off, (n_segs + 1) * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // the count depends on the data
+    const size_t n_sel = out_offsets[n_segs];
+    rc = MFCC_HIP_SUCCESS;
+    if (out_capacity_windows < n_sel) {
+        rc = MFCC_HIP_ERROR_BUFFER_SMALL;
+    } else if (n_sel) {
+        // what is read must not overlap what is written
+        const size_t row_bytes = size_t(n_cep) * sizeof(int16_t), win_bytes = size_t(n_frames) * row_bytes;
+        const uintptr_t in_lo = reinterpret_cast<uintptr_t>(d_rows) + seg_offsets[0] * row_bytes;
+        const uintptr_t in_hi = reinterpret_cast<uintptr_t>(d_rows) + seg_offsets[n_segs] * row_bytes;
+        const uintptr_t m_lo = reinterpret_cast<uintptr_t>(d_mask), m_hi = m_lo + total;
+        const uintptr_t o_lo = reinterpret_cast<uintptr_t>(d_out), o_hi = o_lo + n_sel * win_bytes;
+        const uintptr_t s_lo = reinterpret_cast<uintptr_t>(d_starts), s_hi = s_lo + n_sel * sizeof(long long);
+        if (!d_out || ranges_overlap(in_lo, in_hi, o_lo, o_hi) || ranges_overlap(m_lo, m_hi, o_lo, o_hi) ||
+            (d_starts && (ranges_overlap(in_lo, in_hi, s_lo, s_hi) || ranges_overlap(m_lo, m_hi, s_lo, s_hi) ||
+                          ranges_overlap(o_lo, o_hi, s_lo, s_hi))))
+            rc = MFCC_HIP_ERROR_INVALID_PARAM;
+        else
+            hipLaunchKernelGGL(mfcc_gate::gate_gather_kernel, dim3(grid), dim3(mfcc_gate::kThreads), 0, h->stream,
+                               static_cast<const int16_t *>(d_rows), mask, w, g, static_cast<const long long *>(tile_off),
+                               static_cast<int16_t *>(d_out), static_cast<long long *>(d_starts));
+    }
+    const int rc2 = scratch_release(h);
+    if (rc) return rc;
+    HIP_TRY(h, hipGetLastError());
+    return rc2;
+}
+
+int mfcc_hip_gate_plan(int n_frames, int stride, const size_t *seen, const size_t *frame_offsets, size_t n_lines,
+                       size_t *win_offsets, size_t *seen_after) {
+    if (!gate_shape_ok(1, n_frames, stride) || !win_offsets || (n_lines && (!seen || !frame_offsets)))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    win_offsets[0] = 0;
+    for (size_t u = 0; u < n_lines; ++u) {
+        if (frame_offsets[u + 1] < frame_offsets[u]) return MFCC_HIP_ERROR_INVALID_PARAM;
+        const size_t after = seen[u] + (frame_offsets[u + 1] - frame_offsets[u]);
+        // the windows whose last row is one of the new ones: those of `after` rows that `seen` rows did not have
+        win_offsets[u + 1] = win_offsets[u] + gate_windows(after, size_t(n_frames), size_t(stride)) -
+                             gate_windows(seen[u], size_t(n_frames), size_t(stride));
+        if (seen_after) seen_after[u] = after;
+    }
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_gate_create(mfcc_hip_handle *h, size_t n_lines, int n_cep, int n_frames, int stride, long long threshold,
+                         mfcc_hip_gate **out) {
+    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
+    *out = nullptr;
+    if (h->destroy_pending || !n_lines || !gate_shape_ok(n_cep, n_frames, stride) || threshold < 0)
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    mfcc_hip_gate *g = new (std::nothrow) mfcc_hip_gate();
+    if (!g) return MFCC_HIP_ERROR_NO_MEM;
+    g->h = h;
+    g->n = n_lines;
+    g->g = mfcc_gate::geometry(n_cep, n_frames, stride);
+    g->D = n_frames + stride - 1;
+    g->threshold = threshold;
+    g->seen.assign(n_lines, 0);
+    ++h->n_sessions;
+    DeviceGuard guard(h->device);
+    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&g->d_ring), n_lines * size_t(g->D) * size_t(n_cep) * sizeof(int16_t) + 64);
+    if (e != hipSuccess) {
+        h->last_hip = int(e);
+        mfcc_hip_gate_destroy(g);
+        return e == hipErrorOutOfMemory ? MFCC_HIP_ERROR_NO_MEM : MFCC_HIP_ERROR_OTHER;
+    }
+    *out = g;
+    return MFCC_HIP_SUCCESS;
+}
+
+void mfcc_hip_gate_destroy(mfcc_hip_gate *g) {
+    if (!g) return;
+    mfcc_hip_handle *h = g->h;
+    {
+        DeviceGuard guard(h->device);
+        if (h->scratch_used) (void)hipEventSynchronize(h->scratch_done);    // a push may be in flight on a caller's stream
+        (void)hipStreamSynchronize(h->stream);
+        if (g->d_ring) (void)hipFree(g->d_ring);
+        delete g;
+    }
+    if (--h->n_sessions == 0 && h->destroy_pending) mfcc_hip_destroy(h);
+}
+
+int mfcc_hip_gate_seen(const mfcc_hip_gate *g, size_t *seen) {
+    if (!g || !seen) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::copy(g->seen.begin(), g->seen.end(), seen);
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_gate_push_dev(mfcc_hip_gate *g, const void *d_rows, const size_t *frame_offsets, void *d_power, void *d_gate,
+                           void *d_gate_ref, size_t capacity_windows, size_t *win_offsets) {
+    if (!g || !frame_offsets || !win_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    mfcc_hip_handle *h = g->h;
+    const mfcc_gate::Geo &geo = g->g;
+    const size_t n = g->n, nfr = size_t(geo.n_frames), stride = size_t(geo.stride);
+    int rc = mfcc_hip_gate_plan(geo.n_frames, geo.stride, g->seen.data(), frame_offsets, n, win_offsets, nullptr);
+    if (rc) return rc;
+    const size_t total = win_offsets[n];
+    if (total && !d_power && !d_gate && !d_gate_ref) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (reinterpret_cast<uintptr_t>(d_power) & 7) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (capacity_windows < total) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    size_t n_rec = 0, nwmax = 0;
+    for (size_t u = 0; u < n; ++u) {
+        if (frame_offsets[u + 1] == frame_offsets[u]) continue;
+        ++n_rec;
+        nwmax = std::max(nwmax, win_offsets[u + 1] - win_offsets[u]);
+    }
+    if (!n_rec) return MFCC_HIP_SUCCESS;
+    if (!d_rows || (reinterpret_cast<uintptr_t>(d_rows) & 1)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    static_assert(sizeof(mfcc_gate::Rec) == mfcc_gate::kRecLL * sizeof(long long), "record layout");
+    const size_t rec_ll = mfcc_gate::kRecLL * n_rec;
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    if ((rc = desc_acquire(h, rec_ll, &pd))) return rc;
+    auto *rec = reinterpret_cast<mfcc_gate::Rec *>(pd->p);
+    size_t a = 0;
+    for (size_t u = 0; u < n; ++u) {
+        const size_t nf = frame_offsets[u + 1] - frame_offsets[u];
+        if (!nf) continue;
+        rec[a++] = mfcc_gate::Rec{(long long)u, (long long)frame_offsets[u], (long long)g->seen[u], (long long)nf,
+                                  (long long)gate_windows(g->seen[u], nfr, stride),
+                                  (long long)(win_offsets[u + 1] - win_offsets[u]), (long long)win_offsets[u], 0};
+    }
+    // the records at the front of h->d_out, as the banks keep theirs
+    if ((rc = ensure(h, &h->d_out, &h->d_out_bytes, rec_ll * sizeof(long long) + 64))) return rc;
+    if ((rc = scratch_acquire(h))) return rc;
+    if ((rc = bank_desc_upload(h, pd, rec_ll))) return rc;
+    auto *d_rec = static_cast<const mfcc_gate::Rec *>(h->d_out);
+    const int16_t *fresh = static_cast<const int16_t *>(d_rows);
+    if (nwmax)
+        hipLaunchKernelGGL(mfcc_gate::gate_live_kernel,
+                           dim3(gate_grid(h, (long long)((n_rec * nwmax + mfcc_gate::kThreads - 1) / mfcc_gate::kThreads))),
+                           dim3(mfcc_gate::kThreads), 0, h->stream, static_cast<const int16_t *>(g->d_ring), fresh, d_rec,
+                           (long long)n_rec, (long long)nwmax, geo, g->D, g->threshold, static_cast<long long *>(d_power),
+                           static_cast<unsigned char *>(d_gate), static_cast<unsigned char *>(d_gate_ref));
+    hipLaunchKernelGGL(mfcc_gate::gate_carry_kernel, dim3(gate_grid(h, (long long)n_rec)), dim3(mfcc_gate::kThreads), 0,
+                       h->stream, g->d_ring, fresh, d_rec, (long long)n_rec, geo.n_cep, g->D);
+    HIP_TRY(h, hipGetLastError());
+    if ((rc = scratch_release(h))) return rc;
+    for (size_t u = 0; u < n; ++u) g->seen[u] += frame_offsets[u + 1] - frame_offsets[u];
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_gate_reset(mfcc_hip_gate *g, const size_t *lines, size_t n) {
+    if (!g) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!lines) {
+        std::fill(g->seen.begin(), g->seen.end(), size_t(0));
+        return MFCC_HIP_SUCCESS;
+    }
+    std::vector<char> hit(g->n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (lines[i] >= g->n || hit[lines[i]]) return MFCC_HIP_ERROR_INVALID_PARAM;
+        hit[lines[i]] = 1;
+    }
+    // the frame counts travel with every push's records: a line whose count is 0 reads nothing of its ring
+    for (size_t i = 0; i < n; ++i) g->seen[lines[i]] = 0;
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_gate_window_dev(mfcc_hip_gate *g, const size_t *lines, size_t n, void *d_out) {
+    if (!g || (n && !lines)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    mfcc_hip_handle *h = g->h;
+    const mfcc_gate::Geo &geo = g->g;
+    std::vector<char> hit(g->n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (lines[i] >= g->n || hit[lines[i]] || g->seen[lines[i]] < size_t(geo.n_frames)) return MFCC_HIP_ERROR_INVALID_PARAM;
+        hit[lines[i]] = 1;
+    }
+    if (!n) return MFCC_HIP_SUCCESS;
+    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 1)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    const size_t rec_ll = 2 * n;
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    int rc = desc_acquire(h, rec_ll, &pd);
+    if (rc) return rc;
+    auto *rec = reinterpret_cast<mfcc_gate::WinRec *>(pd->p);
+    for (size_t i = 0; i < n; ++i) {
+        const size_t last = gate_windows(g->seen[lines[i]], size_t(geo.n_frames), size_t(geo.stride)) - 1;
+        rec[i] = mfcc_gate::WinRec{(long long)lines[i], (long long)(last * size_t(geo.stride))};
+    }
+    if ((rc = ensure(h, &h->d_out, &h->d_out_bytes, rec_ll * sizeof(long long) + 64))) return rc;
+    if ((rc = scratch_acquire(h))) return rc;
+    if ((rc = bank_desc_upload(h, pd, rec_ll))) return rc;
+    hipLaunchKernelGGL(mfcc_gate::gate_window_kernel, dim3(gate_grid(h, (long long)n)), dim3(mfcc_gate::kThreads), 0, h->stream,
+                       static_cast<const int16_t *>(g->d_ring), static_cast<const mfcc_gate::WinRec *>(h->d_out), (long long)n,
+                       geo, g->D, static_cast<int16_t *>(d_out));
+    HIP_TRY(h, hipGetLastError());
+    return scratch_release(h);
 }
 
 int mfcc_hip_lift_file(const char *mfcc_in, const char *lift_out, int n_cep, double L, size_t *n_frames_out) {
