@@ -64,7 +64,8 @@ enum mfcc_hip_pad_mode {
 enum mfcc_hip_float_impl {
     MFCC_HIP_IMPL_AUTO = 0,     /* fastest kernel that supports the parameters          */
     MFCC_HIP_IMPL_GENERIC = 1,  /* one frame per wave, any supported nfft / n_mel       */
-    MFCC_HIP_IMPL_FUSED512 = 2  /* 512/170/32 specialised kernel                        */
+    MFCC_HIP_IMPL_FUSED512 = 2  /* 512/170/32 specialised kernel; on a framed handle
+                                   (mfcc_hip_create_framed) the 512 / hop 160 one       */
 };
 
 /* what a float output row holds */
@@ -125,6 +126,29 @@ int  mfcc_hip_default_params(mfcc_hip_params *p);
 /* validates, builds the constant tables on the host, uploads them, creates a stream.
  * Fails with MFCC_HIP_ERROR_NOT_FOUND when no GPU is present: there is no CPU fallback. */
 int  mfcc_hip_create(const mfcc_hip_params *p, mfcc_hip_handle **out);
+/*
+ * Frame length below nfft (float path): the speech front ends' framing, e.g. a 25 ms window advancing by 10 ms and
+ * zero-padded to the next power of two -- 400 / 160 / 512 at 16 kHz.  For frame length L:
+ *   - hop <= L <= nfft and L >= 2, else MFCC_HIP_ERROR_INVALID_PARAM (p->hop == 0 still means nfft / 3 and is refused
+ *     when that exceeds L);
+ *   - frame f is samples [f * hop, f * hop + L) of the pre-emphasised stream, multiplied by the periodic Hamming window
+ *     of length L, w[i] = 0.54 - 0.46 cos(2 pi i / L), and zero-padded at the end to nfft;
+ *   - from the FFT on nothing changes: mel points, power_scale (0 -> nfft), DCT and lifter depend on nfft as before;
+ *   - frame counts: NOTEBOOK (n - L) / hop + 1 (0 if n < L), STREAM (n - L) / hop + 2 (1 if n < L).
+ * frame_length 0 or p->nfft IS mfcc_hip_create: the same kernels, the same bits.  The frame length is not part of
+ * mfcc_hip_params (whose size, reserved words and ABI version stay as they are); every function below that takes a
+ * parameter block has a _framed twin, and the plain one is its frame_length = 0 case.
+ * Every float entry point, streaming session and stream bank works on a framed handle ("nfft" in their descriptions
+ * reads "frame length" where it counts the samples of a frame: frame counts, pending < L).  The fixed-point path is the
+ * RTL's, whose window is the ROM curve over nfft samples: on a handle with L < nfft every fixed entry point, fixed
+ * session and fixed bank and the fixed .mfcc writers return MFCC_HIP_ERROR_UNSUPPORTED.
+ * At nfft 512, hop 160, 160 <= L <= 511, n_mel 32 or 16, the handle runs mfcc_fused512_h160_kernel; float_impl GENERIC
+ * forces the generic kernel, FUSED512 means that kernel or MFCC_HIP_ERROR_UNSUPPORTED.  A plain handle at hop 160 keeps
+ * the generic kernel.
+ */
+int  mfcc_hip_create_framed(const mfcc_hip_params *p, int frame_length, mfcc_hip_handle **out);
+/* the effective frame length of a handle (nfft for a plain one); 0 for NULL */
+int  mfcc_hip_frame_length(const mfcc_hip_handle *h);
 /* Lifetime rule: a handle that still has streaming sessions (mfcc_hip_stream_create below) is only MARKED
  * by mfcc_hip_destroy -- its stream, tables and scratch stay valid for those sessions, no new session can be
  * opened on it and no other call may be made with it -- and is freed by the mfcc_hip_stream_destroy of its
@@ -141,6 +165,8 @@ int  mfcc_hip_synchronize(mfcc_hip_handle *h);
 
 /* frame count for a stream of n_samples under p->pad_mode (`nframes`, main.c:95) */
 int  mfcc_hip_num_frames(const mfcc_hip_params *p, size_t n_samples, size_t *n_frames);
+/* ... of a framed handle (mfcc_hip_create_framed; frame_length 0 or nfft: the call above) */
+int  mfcc_hip_num_frames_framed(const mfcc_hip_params *p, int frame_length, size_t n_samples, size_t *n_frames);
 const char *mfcc_hip_strerror(int err);
 /* hipError_t of the last failing runtime call on this handle (0 if none); with h == NULL:
  * of the last failing mfcc_hip_create on this thread */
@@ -161,6 +187,10 @@ enum mfcc_hip_table {
 /* writes up to `cap_bytes`; *n_bytes = size of the table */
 int  mfcc_hip_get_table(const mfcc_hip_params *p, int which, void *buf, size_t cap_bytes,
                         size_t *n_bytes);
+/* ... of a framed handle.  Only MFCC_HIP_TABLE_WINDOW_F32 differs: still float[nfft], the first frame_length entries
+ * are the periodic Hamming window of that length, the rest 0 (MFCC_HIP_TABLE_FX_MEL_DENSE_U32 is UNSUPPORTED) */
+int  mfcc_hip_get_table_framed(const mfcc_hip_params *p, int frame_length, int which, void *buf, size_t cap_bytes,
+                               size_t *n_bytes);
 
 /* ---- the hot path: replaces the per-frame ft601_write / ft601_read loop of
  *      mfcc_convert (software/main.c:128-166) ------------------------------------------ */
@@ -463,6 +493,9 @@ int    mfcc_hip_bank_pending(const mfcc_hip_bank *b, size_t *pending);
  */
 int    mfcc_hip_bank_plan(const mfcc_hip_params *p, const size_t *pending, const size_t *offsets,
                           size_t n_streams, size_t *frame_offsets, size_t *pending_after);
+/* ... for banks of a framed handle (mfcc_hip_create_framed): the frame length L takes nfft's place, pending[u] < L */
+int    mfcc_hip_bank_plan_framed(const mfcc_hip_params *p, int frame_length, const size_t *pending, const size_t *offsets,
+                                 size_t n_streams, size_t *frame_offsets, size_t *pending_after);
 /*
  * Feed every stream a chunk: stream u gets samples[offsets[u] .. offsets[u + 1]) (n_streams + 1 offsets,
  * not decreasing; a range may be empty).  out: [sum frames][n_cep], float or int16_t by the bank's
@@ -535,6 +568,10 @@ int    mfcc_hip_bank_held(const mfcc_hip_bank *b, size_t *held);
 int    mfcc_hip_bank_plan_online(const mfcc_hip_params *p, int lag, const size_t *pending, const size_t *held,
                                  const size_t *offsets, size_t n_streams, size_t *frame_offsets,
                                  size_t *pending_after, size_t *held_after);
+/* ... for online banks of a framed handle: the frame length L takes nfft's place, pending[u] < L */
+int    mfcc_hip_bank_plan_online_framed(const mfcc_hip_params *p, int frame_length, int lag, const size_t *pending,
+                                        const size_t *held, const size_t *offsets, size_t n_streams,
+                                        size_t *frame_offsets, size_t *pending_after, size_t *held_after);
 /*
  * mfcc_hip_bank_flush with a row count per stream; works on every bank.  streams / n as there.  Per listed stream, in
  * the order listed: with MFCC_HIP_PAD_STREAM the zero-padded tail frame is computed and joins the stream as its last

@@ -165,6 +165,15 @@ SYMBOLS = {
                                          C.c_void_p]),
     "mfcc_hip_gate_reset": (C.c_int, [_H, C.c_void_p, _SZ]),
     "mfcc_hip_gate_window_dev": (C.c_int, [_H, C.c_void_p, _SZ, C.c_void_p]),
+    # frame length below nfft: mfcc_hip_create_framed and the _framed twins of the helpers that take a parameter block
+    "mfcc_hip_create_framed": (C.c_int, [C.POINTER(Params), C.c_int, C.POINTER(_H)]),
+    "mfcc_hip_frame_length": (C.c_int, [_H]),
+    "mfcc_hip_num_frames_framed": (C.c_int, [C.POINTER(Params), C.c_int, _SZ, _PSZ]),
+    "mfcc_hip_get_table_framed": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_void_p, _SZ, _PSZ]),
+    "mfcc_hip_bank_plan_framed": (C.c_int, [C.POINTER(Params), C.c_int, C.c_void_p, C.c_void_p, _SZ, C.c_void_p,
+                                            C.c_void_p]),
+    "mfcc_hip_bank_plan_online_framed": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, _SZ, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -132,12 +132,32 @@ def make_params(nfft=512, hop=None, nfilters=32, nceptrums=13, samplerate=16000,
     return p
 
 
-def num_frames(n_samples, **kw) -> int:
-    """Frames a stream of ``n_samples`` yields (host-only; `nframes`, software/main.c:95)."""
+def _win_length(win_length, nfft, hop) -> int:
+    """The effective frame length of ``win_length`` (``None``: ``nfft``), checked like ``mfcc_hip_create_framed`` does:
+    ``hop <= win_length <= nfft`` and ``win_length >= 2``, with ``hop=None`` meaning ``nfft // 3``."""
+    nfft = int(nfft)
+    if win_length is None:
+        return nfft
+    if isinstance(win_length, bool) or not isinstance(win_length, (int, np.integer)):
+        raise ValueError("win_length must be an integer or None, not %r" % (win_length,))
+    win_length = int(win_length)
+    hop = nfft // 3 if hop is None or int(hop) == 0 else int(hop)
+    if win_length < 2 or win_length > nfft:
+        raise ValueError("win_length must be 2..nfft (%d), not %d" % (nfft, win_length))
+    if win_length < hop:
+        raise ValueError("win_length (%d) must not be below hop (%d): samples between frames would be skipped"
+                         % (win_length, hop))
+    return win_length
+
+
+def num_frames(n_samples, win_length=None, **kw) -> int:
+    """Frames a stream of ``n_samples`` yields (host-only; `nframes`, software/main.c:95); ``win_length``: the frame
+    length of a framed handle (``MFCC(win_length=...)``), ``None`` = ``nfft``."""
     lib = _lib.load()
+    L = _win_length(win_length, kw.get("nfft", 512), kw.get("hop"))
     p = make_params(**kw)
     out = C.c_size_t(0)
-    _lib.check(lib.mfcc_hip_num_frames(C.byref(p), int(n_samples), C.byref(out)), "num_frames")
+    _lib.check(lib.mfcc_hip_num_frames_framed(C.byref(p), L, int(n_samples), C.byref(out)), "num_frames")
     return int(out.value)
 
 
@@ -149,14 +169,16 @@ _TABLE_DTYPES = {
 }
 
 
-def get_table(which, **kw) -> np.ndarray:
-    """The constant tables as the library's host code builds them (works without a GPU)."""
+def get_table(which, win_length=None, **kw) -> np.ndarray:
+    """The constant tables as the library's host code builds them (works without a GPU).  ``win_length``: the frame
+    length of a framed handle; only the window table depends on it (``nfft`` floats, zeros from ``win_length`` on)."""
     lib = _lib.load()
+    L = _win_length(win_length, kw.get("nfft", 512), kw.get("hop"))
     p = make_params(**kw)
     n = C.c_size_t(0)
-    _lib.check(lib.mfcc_hip_get_table(C.byref(p), which, None, 0, C.byref(n)), "get_table")
+    _lib.check(lib.mfcc_hip_get_table_framed(C.byref(p), L, which, None, 0, C.byref(n)), "get_table")
     buf = np.empty(n.value, dtype=np.uint8)
-    _lib.check(lib.mfcc_hip_get_table(C.byref(p), which, buf.ctypes.data, buf.nbytes, C.byref(n)))
+    _lib.check(lib.mfcc_hip_get_table_framed(C.byref(p), L, which, buf.ctypes.data, buf.nbytes, C.byref(n)))
     return buf.view(_TABLE_DTYPES[which])
 
 
@@ -171,6 +193,12 @@ class MFCC:
 
     ``hop`` defaults to ``nfft // 3`` like the core (``mfcc.py:43``); the notebook and the host
     driver hard-code 170 for nfft 512, which is the same number.
+
+    ``win_length=L`` frames the audio the way speech front ends do: frame ``f`` is samples ``[f * hop, f * hop + L)``,
+    multiplied by the periodic Hamming window of length ``L`` and zero-padded to ``nfft`` -- a 25 ms window advancing by
+    10 ms at 16 kHz is ``MFCC(nfft=512, hop=160, win_length=400, ...)``.  ``hop <= L <= nfft``; ``None`` (and ``nfft``)
+    is the reference's framing.  Frame counts, sessions and banks count ``L`` samples per frame; :attr:`win_length` is
+    always the effective length.  Float path only: the fixed-point entries raise ``UNSUPPORTED`` when ``L < nfft``.
 
     ``output="logmel"`` makes every float entry point return rows of ``nfilters`` log2 mel band energies
     (the notebook's ``audio_log.T``, -inf for a silent band) instead of ``nceptrums`` cepstra; the width of a
@@ -202,9 +230,10 @@ class MFCC:
                  pad_mode="notebook", power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra",
                  normalize=None, deltas=0, delta_window=2, normalize_window=None, normalize_min_window=_MIN_WINDOW,
                  normalize_center=True, vad=None, vad_column=0, vad_energy_threshold=5.0, vad_energy_mean_scale=0.5,
-                 vad_frames_context=0, vad_proportion_threshold=0.6):
+                 vad_frames_context=0, vad_proportion_threshold=0.6, win_length=None):
         if width != 16:
             raise ValueError("only width=16 (int16 PCM) is supported, like every reference target")
+        self.win_length = _win_length(win_length, nfft, hop)
         norm = normalize_mode(normalize)
         _window_args(normalize_window, normalize_min_window, normalize_center)
         order, window = _delta_args(deltas, delta_window)
@@ -231,7 +260,8 @@ class MFCC:
                     self._device_index = torch.cuda.current_device()
             except ImportError:
                 pass
-        _lib.check(self._lib.mfcc_hip_create(C.byref(self._params), C.byref(h)), "mfcc_hip_create")
+        _lib.check(self._lib.mfcc_hip_create_framed(C.byref(self._params), self.win_length, C.byref(h)),
+                   "mfcc_hip_create")
         self._h = h
         self.normalize = None
         if norm != _lib.NORMALIZE_NONE:
@@ -455,7 +485,8 @@ class MFCC:
 
     def num_frames(self, n_samples) -> int:
         out = C.c_size_t(0)
-        _lib.check(self._lib.mfcc_hip_num_frames(C.byref(self._params), int(n_samples), C.byref(out)))
+        _lib.check(self._lib.mfcc_hip_num_frames_framed(C.byref(self._params), self.win_length, int(n_samples),
+                                                        C.byref(out)))
         return int(out.value)
 
     def kernel_name(self, fixed=False) -> str:
@@ -938,7 +969,7 @@ class MfccStreamBank:
 
     @property
     def pending(self) -> np.ndarray:
-        """Samples every stream holds back for its frame in progress: uint64 ``(n_streams,)``, each below ``nfft``."""
+        """Samples every stream holds back for its frame in progress: uint64 ``(n_streams,)``, each below ``win_length``."""
         p = np.zeros(self.n_streams, dtype=np.uint64)
         _lib.check(self._lib.mfcc_hip_bank_pending(self._b, p.ctypes.data_as(C.c_void_p)), "bank_pending")
         return p
@@ -971,11 +1002,12 @@ class MfccStreamBank:
     def _plan(self, offsets):
         fo = np.zeros(self.n_streams + 1, dtype=np.uint64)
         pending, held = self.pending, self.held
-        _lib.check(self._lib.mfcc_hip_bank_plan_online(C.byref(self._m._params), self.lag,
-                                                       pending.ctypes.data_as(C.c_void_p),
-                                                       held.ctypes.data_as(C.c_void_p),
-                                                       offsets.ctypes.data_as(C.c_void_p), self.n_streams,
-                                                       fo.ctypes.data_as(C.c_void_p), None, None), "bank_plan_online")
+        _lib.check(self._lib.mfcc_hip_bank_plan_online_framed(C.byref(self._m._params), self._m.win_length, self.lag,
+                                                              pending.ctypes.data_as(C.c_void_p),
+                                                              held.ctypes.data_as(C.c_void_p),
+                                                              offsets.ctypes.data_as(C.c_void_p), self.n_streams,
+                                                              fo.ctypes.data_as(C.c_void_p), None, None),
+                   "bank_plan_online")
         return fo
 
     def num_frames(self, lengths) -> np.ndarray:

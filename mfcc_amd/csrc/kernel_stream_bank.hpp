@@ -1,6 +1,8 @@
 // Stream bank: N independent online sessions advanced by one launch (include/mfcc_hip.h: mfcc_hip_bank_*, DESIGN.md
 // section 6c-bis).  These kernels only MOVE samples; the frames are computed by the library's frame kernels, unchanged.
 //
+// "nfft" below is the handle's frame length in samples: nfft itself on a plain handle, the shorter frame of one made by
+// mfcc_hip_create_framed (the kernels take it as their `nfft` argument; it is only the extent of a state row).
 // State: one row of nfft int16 per stream in one [n_streams][nfft] allocation.  Element 0 is the pre-emphasis history
 // sample x[first - 1] (0 after reset), elements 1 .. 1 + pending are the samples of the frame in progress
 // (pending < nfft between calls, so a row always fits).  The host mirrors pending[u]: it depends on lengths only.

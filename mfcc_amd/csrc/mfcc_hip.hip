@@ -24,6 +24,7 @@
 #include "kernel_fused1024_w12.hpp"
 #include "kernel_fused512.hpp"
 #include "kernel_fused512_w12.hpp"
+#include "kernel_fused512_h160.hpp"
 #include "kernel_normalize.hpp"
 #include "kernel_deltas.hpp"
 #include "kernel_normalize_sliding.hpp"
@@ -42,6 +43,7 @@ struct Resolved {
     double power_scale, lifter;
     int device, float_impl;
     int output;                // enum mfcc_hip_output
+    int frame_len;             // samples of a frame (hop <= frame_len <= nfft); the window's length.  nfft: a plain handle
 };
 
 // width of an output row: n_mel log-mel values or n_cep coefficients
@@ -64,6 +66,7 @@ int resolve(const mfcc_hip_params *p, Resolved &r) {
     r.device = p->device;
     r.float_impl = p->float_impl;
     r.output = p->output;
+    r.frame_len = p->nfft;
     if (!is_pow2(r.nfft) || r.nfft < 64 || r.nfft > 1024) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (r.hop < 1 || r.hop > r.nfft) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (r.n_mel < 1 || r.n_mel > mfcc_k::kMaxMel) return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -79,18 +82,41 @@ int resolve(const mfcc_hip_params *p, Resolved &r) {
     return MFCC_HIP_SUCCESS;
 }
 
+// ... and a frame length (mfcc_hip_create_framed): 0 and nfft mean the plain handle
+int resolve_framed(const mfcc_hip_params *p, int frame_length, Resolved &r) {
+    if (frame_length < 0) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const int rc = resolve(p, r);
+    if (rc) return rc;
+    if (frame_length == 0) return MFCC_HIP_SUCCESS;
+    if (frame_length < 2 || frame_length > r.nfft || frame_length < r.hop) return MFCC_HIP_ERROR_INVALID_PARAM;
+    r.frame_len = frame_length;
+    return MFCC_HIP_SUCCESS;
+}
+
+inline bool is_framed(const Resolved &r) { return r.frame_len != r.nfft; }
+
 size_t count_frames(const Resolved &r, size_t n) {
+    const size_t L = size_t(r.frame_len);
     if (r.pad_mode == MFCC_HIP_PAD_NOTEBOOK) {
-        if (n < size_t(r.nfft)) return 0;
-        return (n - size_t(r.nfft)) / size_t(r.hop) + 1;
+        if (n < L) return 0;
+        return (n - L) / size_t(r.hop) + 1;
     }
-    if (n < size_t(r.nfft)) return 1;
-    return (n - size_t(r.nfft)) / size_t(r.hop) + 2;
+    if (n < L) return 1;
+    return (n - L) / size_t(r.hop) + 2;
+}
+
+// the float window of a handle: periodic Hamming over the frame, zeros up to nfft (the frame is zero-padded at the end)
+std::vector<double> frame_window(const Resolved &r) {
+    std::vector<double> w = hamming_periodic(r.frame_len);
+    w.resize(size_t(r.nfft), 0.0);
+    return w;
 }
 
 bool fixed_supported(const Resolved &r) {
     // RTL constraints: FFT sizes are powers of two (mfcc/misc/fft.py:351-353) for both the
-    // nfft-point FFT and the (4 * nfilters)-point DCT FFT; hop = nfft // 3 (mfcc/core/mfcc.py:43)
+    // nfft-point FFT and the (4 * nfilters)-point DCT FFT; hop = nfft // 3 (mfcc/core/mfcc.py:43); the window is the
+    // RTL's ROM curve over nfft samples: no frame length below nfft
+    if (is_framed(r)) return false;
     if (!(is_pow2(4 * r.n_mel) && 4 * r.n_mel <= r.nfft && r.n_mel >= 4 && r.hop == r.nfft / 3 && r.nfft >= 64))
         return false;
     // filter points too dense for the streaming filterbank's ramp logic (filterbank.py:22-34, 88-142): the RTL then
@@ -135,6 +161,8 @@ struct mfcc_hip_handle {
     bool fused_ok = false;
     bool fused_dense = false;     // the fused kernel's banded MFMA list does not fit this sample rate: all pairs
     bool fused_w12 = false;       // the twelve-wave form of the fused 512 kernel runs (kernel_fused512_w12.hpp)
+    bool fused160_ok = false;     // a framed handle at 512 / hop 160: the four-wave form at that hop (kernel_fused512_h160.hpp);
+                                  // its tables are h->fu, its schedule fused_dense; never set together with fused_ok
     bool fused1k_ok = false;      // the fused 1024/341/40 float kernel covers this handle's parameters
     bool fixed512_ok = false;     // the fused fixed-point kernel covers this handle's parameters
     // device tables (one arena)
@@ -295,7 +323,7 @@ int build_tables(mfcc_hip_handle *h) {
     const Resolved &r = h->r;
     Arena a;
     // ---- float
-    std::vector<double> wd = hamming_periodic(r.nfft);
+    std::vector<double> wd = frame_window(r);
     std::vector<float> win(wd.begin(), wd.end());
     const int M = r.nfft / 2;
     std::vector<float2> twf(M), tws(M + 1);
@@ -371,7 +399,21 @@ int build_tables(mfcc_hip_handle *h) {
     h->fused_ok = false;
     h->fused_dense = false;
     bool fused_dcx = false;
-    if (mfcc_fused::supported(r.nfft, r.hop, r.n_mel, r.n_cep)) {
+    // a framed handle (frame_len < nfft) runs none of the fused forms below: their windows span nfft samples
+    const bool framed = is_framed(r);
+    h->fused160_ok = false;
+    if (framed && mfcc_fused160::supported(r.nfft, r.hop, r.frame_len, r.n_mel, r.n_cep)) {
+        // the tables of the hop-170 form (none of them depends on the hop) with the frame's window in place of theirs
+        fused_dcx = mfcc_fused::needs_dc_exact(r.sample_rate, r.n_mel);
+        h->fused160_ok = !fused_dcx &&
+                         mfcc_fused::build_tables<false>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
+        if (!h->fused160_ok) {
+            h->fused_dense = true;
+            h->fused160_ok = mfcc_fused::build_tables<true>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
+        }
+        if (h->fused160_ok) mfcc_fused160::set_window(fused_blob, h->fused_dense, r.frame_len);
+    }
+    if (!framed && mfcc_fused::supported(r.nfft, r.hop, r.n_mel, r.n_cep)) {
         fused_dcx = mfcc_fused::needs_dc_exact(r.sample_rate, r.n_mel);    // only the dense instantiation has the DC path
         h->fused_ok = !fused_dcx &&
                       mfcc_fused::build_tables<false>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
@@ -381,10 +423,10 @@ int build_tables(mfcc_hip_handle *h) {
         }
     }
     size_t o_fu = 0;
-    if (h->fused_ok) o_fu = a.put(fused_blob);
+    if (h->fused_ok || h->fused160_ok) o_fu = a.put(fused_blob);
     std::vector<char> f1k_blob;
     int f1k_var = 0;
-    h->fused1k_ok = mfcc_fused1024::supported(r.nfft, r.hop, r.n_mel, r.n_cep);
+    h->fused1k_ok = !framed && mfcc_fused1024::supported(r.nfft, r.hop, r.n_mel, r.n_cep);
     if (h->fused1k_ok) {
         // Default: the twelve-wave staging with the bf16-split contraction (kernel_fused1024_w12.hpp), every rate.
         // MFCC_HIP_FUSED1024 is a diagnostic override for A/B runs -- f32 / bf16: the eight-wave lockstep staging of
@@ -433,7 +475,7 @@ int build_tables(mfcc_hip_handle *h) {
         h->xt.log2_dct = ilog2(4 * r.n_mel);
         h->xt.n_cep = r.n_cep;
     }
-    if (h->fused_ok) mfcc_fused::bind_tables(b + o_fu, r.n_cep, r.n_mel, h->fused_dense, fused_dcx, h->fu);
+    if (h->fused_ok || h->fused160_ok) mfcc_fused::bind_tables(b + o_fu, r.n_cep, r.n_mel, h->fused_dense, fused_dcx, h->fu);
     {
         // diagnostic override for A/B runs: MFCC_HIP_FUSED512=w4 keeps the four-wave form (not on a log-mel handle:
         // the four-wave form has no log-mel tail)
@@ -463,6 +505,15 @@ bool use_fused(const mfcc_hip_handle *h) {
     return h->fused_ok;
 }
 
+// ... the hop-160 form of a framed handle
+bool use_fused160(const mfcc_hip_handle *h) {
+    if (h->r.float_impl == MFCC_HIP_IMPL_GENERIC) return false;
+    return h->fused160_ok;
+}
+
+// MFCC_HIP_IMPL_FUSED512 asks for the fused 512-point kernel of the handle's framing
+inline bool fused512_any(const mfcc_hip_handle *h) { return h->fused_ok || h->fused160_ok; }
+
 // the generic float kernel for every nfft; LOGMEL: its log-mel form
 template <bool LOGMEL>
 int launch_generic(mfcc_hip_handle *h, const mfcc_k::StreamDesc &s, unsigned blocks, float *o) {
@@ -488,7 +539,7 @@ int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t s
            int halo, void *d_out, size_t *n_frames, size_t force_frames = 0) {
     if (!h || (!d_pcm && n * nch) || halo < 0 || halo > 1) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (!fixed && h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !h->fused_ok)
+    if (!fixed && h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !fused512_any(h))
         return MFCC_HIP_ERROR_UNSUPPORTED;
     // force_frames: the packed stream of the ragged entry points -- every hop position is a frame
     const size_t nf = force_frames ? force_frames : count_frames(h->r, n);
@@ -535,6 +586,11 @@ int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t s
             default:
                 return MFCC_HIP_ERROR_UNSUPPORTED;
         }
+    } else if (use_fused160(h)) {
+        float *o = static_cast<float *>(d_out);
+        if (!(logmel ? mfcc_fused160::launch<true>(s, h->fu, h->fused_dense, o, h->n_cu, h->stream)
+                     : mfcc_fused160::launch<false>(s, h->fu, h->fused_dense, o, h->n_cu, h->stream)))
+            return MFCC_HIP_ERROR_UNSUPPORTED;
     } else if (logmel && use_fused(h)) {
         // log-mel output: the twelve-wave form only (the four-wave one has no log-mel tail)
         if (!mfcc_fused12::launch<true>(s, h->fu, h->fused_dense, static_cast<float *>(d_out), h->n_cu, h->stream))
@@ -1235,7 +1291,7 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     const size_t nf = count_frames(h->r, n);
     if (n_frames) *n_frames = nf;
     if (nf == 0 || nch == 0) return MFCC_HIP_SUCCESS;
-    const size_t ncep = fixed ? row_width(h->r) : out_width(h), hop = size_t(h->r.hop), nfft = size_t(h->r.nfft);   // elements per row
+    const size_t ncep = fixed ? row_width(h->r) : out_width(h), hop = size_t(h->r.hop), flen = size_t(h->r.frame_len);   // elements per row
     const size_t n_out = nf * nch * ncep;
     if (!out || cap < n_out) return MFCC_HIP_ERROR_BUFFER_SMALL;
     DeviceGuard guard(h->device);
@@ -1255,14 +1311,14 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
             chunks.push_back({pcm + c0 * n, k * n, n, n, k, 0, nf, k * nf * ncep, c0 * nf * ncep});
         }
     } else {
-        // long channels: frame ranges [f0, f1) of one channel -- samples f0 * hop - 1 (history) .. (f1 - 1) * hop + nfft
+        // long channels: frame ranges [f0, f1) of one channel -- samples f0 * hop - 1 (history) .. (f1 - 1) * hop + frame_len
         size_t per = (kChunkBytes / sizeof(int16_t)) / hop;
         if (per < 1) per = 1;
         for (size_t c = 0; c < nch; ++c)
             for (size_t f0 = 0; f0 < nf; f0 += per) {
                 const size_t f1 = std::min(nf, f0 + per), halo = f0 ? 1 : 0;
                 const size_t s0 = f0 * hop - halo;
-                size_t s1 = (f1 - 1) * hop + nfft;
+                size_t s1 = (f1 - 1) * hop + flen;
                 if (s1 > n) s1 = n;                                  // the zero-padded tail of STREAM framing
                 chunks.push_back({pcm + c * n + s0, s1 - s0, s1 - s0 - halo, s1 - s0, 1, int(halo), f1 - f0,
                                   (f1 - f0) * ncep, (c * nf + f0) * ncep});
@@ -1373,7 +1429,7 @@ int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm,
                            OutT *d_out, size_t cap, size_t *frame_offsets) {
     if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
-    const size_t hop = size_t(h->r.hop), nfft = size_t(h->r.nfft), ncep = row_width(h->r);   // elements per row
+    const size_t hop = size_t(h->r.hop), flen = size_t(h->r.frame_len), ncep = row_width(h->r);   // elements per row
     DeviceGuard guard(h->device);
     // A corpus of equal-length utterances lying back to back (BASELINE config 5: 10 000 x 10 s) IS a multi-channel
     // stream, channel stride = utterance length: no packing copy, no row gather, no descriptors, the same bits (every
@@ -1419,7 +1475,7 @@ int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm,
         total += nf;
         frame_offsets[u + 1] = total;
         if (nf) {
-            const size_t extent = std::max(n, hop * (nf - 1) + nfft);
+            const size_t extent = std::max(n, hop * (nf - 1) + flen);
             pos = (pos + extent + 1 + hop - 1) / hop * hop;
             last_with_frames = u;
         }
@@ -1505,7 +1561,7 @@ int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm,
             return scratch_release(h);
         }
     }
-    const size_t F = pos / hop, len = pos + nfft + hop;
+    const size_t F = pos / hop, len = pos + flen + hop;
     desc[4 * last_with_frames + 3] = (long long)len;     // the last one also zeroes the tail of the stream
     const size_t desc_bytes = 7 * n_utt * sizeof(long long);
     rc = ensure(h, &h->d_in, &h->d_in_bytes, len * sizeof(int16_t) + 64);
@@ -1756,8 +1812,12 @@ int mfcc_hip_default_params(mfcc_hip_params *p) {
 }
 
 int mfcc_hip_num_frames(const mfcc_hip_params *p, size_t n_samples, size_t *n_frames) {
+    return mfcc_hip_num_frames_framed(p, 0, n_samples, n_frames);
+}
+
+int mfcc_hip_num_frames_framed(const mfcc_hip_params *p, int frame_length, size_t n_samples, size_t *n_frames) {
     Resolved r;
-    int rc = resolve(p, r);
+    int rc = resolve_framed(p, frame_length, r);
     if (rc) return rc;
     if (!n_frames) return MFCC_HIP_ERROR_INVALID_PARAM;
     *n_frames = count_frames(r, n_samples);
@@ -1783,14 +1843,19 @@ static thread_local int g_create_hip_error = 0;
 int mfcc_hip_last_hip_error(const mfcc_hip_handle *h) { return h ? h->last_hip : g_create_hip_error; }
 
 int mfcc_hip_get_table(const mfcc_hip_params *p, int which, void *buf, size_t cap, size_t *n_bytes) {
+    return mfcc_hip_get_table_framed(p, 0, which, buf, cap, n_bytes);
+}
+
+int mfcc_hip_get_table_framed(const mfcc_hip_params *p, int frame_length, int which, void *buf, size_t cap,
+                              size_t *n_bytes) {
     Resolved r;
-    int rc = resolve(p, r);
+    int rc = resolve_framed(p, frame_length, r);
     if (rc) return rc;
     std::vector<char> blob;
     auto put = [&](const void *d, size_t n) { blob.assign((const char *)d, (const char *)d + n); };
     switch (which) {
         case MFCC_HIP_TABLE_WINDOW_F32: {
-            std::vector<double> w = hamming_periodic(r.nfft);
+            std::vector<double> w = frame_window(r);
             std::vector<float> f(w.begin(), w.end());
             put(f.data(), f.size() * 4);
             break;
@@ -1845,11 +1910,15 @@ int mfcc_hip_get_table(const mfcc_hip_params *p, int which, void *buf, size_t ca
     return MFCC_HIP_SUCCESS;
 }
 
-int mfcc_hip_create(const mfcc_hip_params *p, mfcc_hip_handle **out) {
+int mfcc_hip_create(const mfcc_hip_params *p, mfcc_hip_handle **out) { return mfcc_hip_create_framed(p, 0, out); }
+
+int mfcc_hip_frame_length(const mfcc_hip_handle *h) { return h ? h->r.frame_len : 0; }
+
+int mfcc_hip_create_framed(const mfcc_hip_params *p, int frame_length, mfcc_hip_handle **out) {
     if (!out) return MFCC_HIP_ERROR_INVALID_PARAM;
     *out = nullptr;
     Resolved r;
-    int rc = resolve(p, r);
+    int rc = resolve_framed(p, frame_length, r);
     if (rc) return rc;
     int ndev = 0;
     g_create_hip_error = int(hipGetDeviceCount(&ndev));
@@ -1882,7 +1951,7 @@ int mfcc_hip_create(const mfcc_hip_params *p, mfcc_hip_handle **out) {
         return fail(MFCC_HIP_ERROR_OTHER);
     rc = build_tables(h);
     if (rc) return fail(rc);
-    if (r.float_impl == MFCC_HIP_IMPL_FUSED512 && !h->fused_ok) return fail(MFCC_HIP_ERROR_UNSUPPORTED);
+    if (r.float_impl == MFCC_HIP_IMPL_FUSED512 && !fused512_any(h)) return fail(MFCC_HIP_ERROR_UNSUPPORTED);
     *out = h;
     return MFCC_HIP_SUCCESS;
 }
@@ -2198,6 +2267,7 @@ const char *mfcc_hip_kernel_name(const mfcc_hip_handle *h, int fixed) {
     if (fixed) return h->fixed512_ok ? mfcc_fixed512::kernel_name() : "mfcc_fixed_kernel";
     // a log-mel handle runs the twelve-wave forms only (build_tables ignores the diagnostic overrides for it): the
     // names below follow from that
+    if (use_fused160(h)) return mfcc_fused160::kernel_name();
     if (use_fused(h)) return h->fused_w12 ? mfcc_fused12::kernel_name() : mfcc_fused::kernel_name();
     if (h->fused1k_ok && h->r.float_impl == MFCC_HIP_IMPL_AUTO)
         return !h->f1k_w12 ? mfcc_fused1024::kernel_name()
@@ -2371,7 +2441,7 @@ int mfcc_hip_stream_create(mfcc_hip_handle *h, int fixed, mfcc_hip_stream **out)
     s->fixed = fixed != 0;
     ++h->n_sessions;
     DeviceGuard guard(h->device);
-    int rc = stream_reserve(s, size_t(h->r.nfft) * 8, size_t(64) * row_width(h->r) * sizeof(float));
+    int rc = stream_reserve(s, size_t(h->r.frame_len) * 8, size_t(64) * row_width(h->r) * sizeof(float));
     if (rc) {
         mfcc_hip_stream_destroy(s);
         return rc;
@@ -2413,9 +2483,9 @@ int mfcc_hip_stream_push(mfcc_hip_stream *s, const int16_t *samples, size_t n, v
                          size_t *n_frames_out) {
     if (!s || (n && !samples)) return MFCC_HIP_ERROR_INVALID_PARAM;
     mfcc_hip_handle *h = s->h;
-    const size_t nfft = size_t(h->r.nfft), hop = size_t(h->r.hop), ncep = row_width(h->r);
+    const size_t flen = size_t(h->r.frame_len), hop = size_t(h->r.hop), ncep = row_width(h->r);
     const size_t total = s->pending + n;
-    const size_t nf = total >= nfft ? (total - nfft) / hop + 1 : 0;          // frames this push completes
+    const size_t nf = total >= flen ? (total - flen) / hop + 1 : 0;          // frames this push completes
     if (n_frames_out) *n_frames_out = nf;
     if (nf && (!out || cap < nf * ncep)) return MFCC_HIP_ERROR_BUFFER_SMALL;  // nothing consumed yet
     DeviceGuard guard(h->device);
@@ -2458,7 +2528,7 @@ int mfcc_hip_stream_flush(mfcc_hip_stream *s, void *out, size_t cap, size_t *n_f
 }
 
 // ---- stream bank (include/mfcc_hip.h: mfcc_hip_bank_*; kernel_stream_bank.hpp) -------------
-// N sessions whose state rows ([history | pending], nfft int16 each) lie in one device allocation.  A push is planned on
+// N sessions whose state rows ([history | pending], frame_len int16 each) lie in one device allocation.  A push is planned on
 // the host from lengths alone, described by one record per stream in the pinned descriptor pool and carried out by ONE
 // launch of bank_advance_kernel, ONE launch of the frame kernels over the active streams' rows of the work buffer W
 // (h->d_in) and, when the streams complete different numbers of frames, ONE row gather out of h->d_out.
@@ -2472,7 +2542,7 @@ struct mfcc_hip_bank {
     mfcc_hip_handle *h = nullptr;
     bool fixed = false;
     size_t n = 0;                        // streams
-    int16_t *d_state = nullptr;          // [n][nfft]
+    int16_t *d_state = nullptr;          // [n][frame_len]
     std::vector<size_t> pending, after;  // the host mirror and the plan of the push in progress
     // staging of the host-buffer entries (mfcc_hip_bank_push, mfcc_hip_bank_flush): the flat samples and the rows
     void *st_in = nullptr, *st_out = nullptr;
@@ -2491,13 +2561,13 @@ namespace {
 
 // frame_offsets (n + 1) and, where given, pending_after (n) of a push of chunks offsets[u] .. offsets[u + 1]; on
 // INVALID_PARAM frame_offsets is filled up to the offending stream
-int bank_plan_raw(size_t nfft, size_t hop, const size_t *pending, const size_t *offsets, size_t n, size_t *frame_offsets,
+int bank_plan_raw(size_t flen, size_t hop, const size_t *pending, const size_t *offsets, size_t n, size_t *frame_offsets,
                   size_t *pending_after) {
     frame_offsets[0] = 0;
     for (size_t u = 0; u < n; ++u) {
-        if (offsets[u + 1] < offsets[u] || pending[u] >= nfft) return MFCC_HIP_ERROR_INVALID_PARAM;
+        if (offsets[u + 1] < offsets[u] || pending[u] >= flen) return MFCC_HIP_ERROR_INVALID_PARAM;
         size_t nf, pa;
-        mfcc_bank::plan(pending[u], offsets[u + 1] - offsets[u], nfft, hop, nf, pa);
+        mfcc_bank::plan(pending[u], offsets[u + 1] - offsets[u], flen, hop, nf, pa);
         frame_offsets[u + 1] = frame_offsets[u] + nf;
         if (pending_after) pending_after[u] = pa;
     }
@@ -2506,15 +2576,15 @@ int bank_plan_raw(size_t nfft, size_t hop, const size_t *pending, const size_t *
 
 // The same for sessions that return row t once row t + lag is known: frame_offsets counts the rows RETURNED.  held may
 // be NULL with lag = 0; raw_offsets (n + 1, may be NULL) gets the running sum of the frames computed
-int bank_plan_lagged(size_t nfft, size_t hop, size_t lag, const size_t *pending, const size_t *held, const size_t *offsets,
+int bank_plan_lagged(size_t flen, size_t hop, size_t lag, const size_t *pending, const size_t *held, const size_t *offsets,
                      size_t n, size_t *frame_offsets, size_t *pending_after, size_t *held_after, size_t *raw_offsets) {
     frame_offsets[0] = 0;
     if (raw_offsets) raw_offsets[0] = 0;
     for (size_t u = 0; u < n; ++u) {
         const size_t hu = held ? held[u] : 0;
-        if (offsets[u + 1] < offsets[u] || pending[u] >= nfft || hu > lag) return MFCC_HIP_ERROR_INVALID_PARAM;
+        if (offsets[u + 1] < offsets[u] || pending[u] >= flen || hu > lag) return MFCC_HIP_ERROR_INVALID_PARAM;
         size_t nf, pa;
-        mfcc_bank::plan(pending[u], offsets[u + 1] - offsets[u], nfft, hop, nf, pa);
+        mfcc_bank::plan(pending[u], offsets[u + 1] - offsets[u], flen, hop, nf, pa);
         const size_t emitted = hu + nf > lag ? hu + nf - lag : 0;
         frame_offsets[u + 1] = frame_offsets[u] + emitted;
         if (raw_offsets) raw_offsets[u + 1] = raw_offsets[u] + nf;
@@ -2540,8 +2610,8 @@ template <typename OutT>
 int bank_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const size_t *offsets, OutT *d_out, size_t cap,
                  size_t *frame_offsets) {
     mfcc_hip_handle *h = b->h;
-    const size_t nfft = size_t(h->r.nfft), hop = size_t(h->r.hop), W = row_width(h->r), n = b->n;
-    int rc = bank_plan_raw(nfft, hop, b->pending.data(), offsets, n, frame_offsets, b->after.data());
+    const size_t flen = size_t(h->r.frame_len), hop = size_t(h->r.hop), W = row_width(h->r), n = b->n;
+    int rc = bank_plan_raw(flen, hop, b->pending.data(), offsets, n, frame_offsets, b->after.data());
     if (rc) return rc;
     const size_t total_frames = frame_offsets[n];
     if (total_frames && (!d_out || cap < total_frames * W)) return MFCC_HIP_ERROR_BUFFER_SMALL;
@@ -2593,7 +2663,7 @@ int bank_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const
     int16_t *d_w = static_cast<int16_t *>(h->d_in);
     const unsigned blocks = (unsigned)std::min<size_t>(n_rec, size_t(h->n_cu) * 8);
     hipLaunchKernelGGL(mfcc_bank::bank_advance_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, d_samples,
-                       b->d_state, d_w, d_rec, (long long)n_rec, (long long)n_active, (long long)S, h->r.nfft, h->r.hop);
+                       b->d_state, d_w, d_rec, (long long)n_rec, (long long)n_active, (long long)S, h->r.frame_len, h->r.hop);
     if (n_active) {
         OutT *d_rows = lockstep ? d_out : reinterpret_cast<OutT *>(static_cast<char *>(h->d_out) + desc_bytes);
         if ((rc = launch(h, b->fixed, d_w, S - 1, S, n_active, /*halo=*/1, d_rows, nullptr, nfmax))) return rc;
@@ -2663,11 +2733,11 @@ void online_passes(mfcc_hip_bank *b, const mfcc_online::Rec *d_rec, size_t n_cmv
 int online_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const size_t *offsets, float *d_out, size_t cap,
                    size_t *frame_offsets) {
     mfcc_hip_handle *h = b->h;
-    const size_t nfft = size_t(h->r.nfft), hop = size_t(h->r.hop), W = row_width(h->r), WO = bank_row_width(b), n = b->n;
+    const size_t flen = size_t(h->r.frame_len), hop = size_t(h->r.hop), W = row_width(h->r), WO = bank_row_width(b), n = b->n;
     const size_t S = size_t(b->run), L = size_t(b->lag);
     const bool norm = b->norm != MFCC_HIP_NORMALIZE_NONE;
     size_t *rfo = b->raw_fo.data();
-    int rc = bank_plan_lagged(nfft, hop, L, b->pending.data(), b->held.data(), offsets, n, frame_offsets, b->after.data(),
+    int rc = bank_plan_lagged(flen, hop, L, b->pending.data(), b->held.data(), offsets, n, frame_offsets, b->after.data(),
                               b->held_after.data(), rfo);
     if (rc) return rc;
     const size_t total_rows = frame_offsets[n];
@@ -2723,7 +2793,7 @@ int online_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, con
     int16_t *d_w = static_cast<int16_t *>(h->d_in);
     const unsigned blocks = (unsigned)std::min<size_t>(n_rec, size_t(h->n_cu) * 8);
     hipLaunchKernelGGL(mfcc_bank::bank_advance_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, d_samples,
-                       b->d_state, d_w, d_rec, (long long)n_rec, (long long)n_active, (long long)SW, h->r.nfft, h->r.hop);
+                       b->d_state, d_w, d_rec, (long long)n_rec, (long long)n_active, (long long)SW, h->r.frame_len, h->r.hop);
     if (n_active) {
         float *d_raw = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes);
         float *d_stat = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes + rows_bytes);
@@ -2758,7 +2828,7 @@ int bank_list(const mfcc_hip_bank *b, const size_t *streams, size_t n, std::vect
 // The listed streams back to the reset state; emit: their zero-padded tail frames first, to host memory (synchronous)
 int bank_tail(mfcc_hip_bank *b, const std::vector<size_t> &list, bool emit, void *out) {
     mfcc_hip_handle *h = b->h;
-    const size_t k = list.size(), nfft = size_t(h->r.nfft), W = row_width(h->r), S = nfft + 1;
+    const size_t k = list.size(), flen = size_t(h->r.frame_len), W = row_width(h->r), S = flen + 1;
     if (!k) return MFCC_HIP_SUCCESS;
     const size_t esz = b->fixed ? sizeof(int16_t) : sizeof(float);
     DeviceGuard guard(h->device);
@@ -2775,10 +2845,10 @@ int bank_tail(mfcc_hip_bank *b, const std::vector<size_t> &list, bool emit, void
     int16_t *d_w = emit ? static_cast<int16_t *>(h->d_in) : nullptr;
     const unsigned blocks = (unsigned)std::min<size_t>(k, size_t(h->n_cu) * 8);
     hipLaunchKernelGGL(mfcc_bank::bank_flush_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, b->d_state, d_w,
-                       static_cast<const mfcc_bank::Rec *>(h->d_out), (long long)k, (long long)S, h->r.nfft);
+                       static_cast<const mfcc_bank::Rec *>(h->d_out), (long long)k, (long long)S, h->r.frame_len);
     if (emit) {
         // one frame per stream over history | pending | zeros: the tail frame of main.c:134-144
-        if ((rc = launch(h, b->fixed, d_w, nfft, S, k, /*halo=*/1, b->st_out, nullptr, 1))) return rc;
+        if ((rc = launch(h, b->fixed, d_w, flen, S, k, /*halo=*/1, b->st_out, nullptr, 1))) return rc;
         HIP_TRY(h, hipMemcpyAsync(out, b->st_out, k * W * esz, hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(h, hipGetLastError());
@@ -2794,7 +2864,7 @@ int bank_tail(mfcc_hip_bank *b, const std::vector<size_t> &list, bool emit, void
 // cleared: with seen = 0 nothing of them is read
 int online_tail(mfcc_hip_bank *b, const std::vector<size_t> &list, bool emit, void *out, const size_t *fo) {
     mfcc_hip_handle *h = b->h;
-    const size_t k = list.size(), nfft = size_t(h->r.nfft), W = row_width(h->r), WO = bank_row_width(b), SW = nfft + 1;
+    const size_t k = list.size(), flen = size_t(h->r.frame_len), W = row_width(h->r), WO = bank_row_width(b), SW = flen + 1;
     if (!k) return MFCC_HIP_SUCCESS;
     const bool norm = b->norm != MFCC_HIP_NORMALIZE_NONE;
     const size_t nf = emit ? 1 : 0, total = fo[k], S = size_t(b->run);
@@ -2828,10 +2898,10 @@ int online_tail(mfcc_hip_bank *b, const std::vector<size_t> &list, bool emit, vo
     int16_t *d_w = emit ? static_cast<int16_t *>(h->d_in) : nullptr;
     const unsigned blocks = (unsigned)std::min<size_t>(k, size_t(h->n_cu) * 8);
     hipLaunchKernelGGL(mfcc_bank::bank_flush_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, b->d_state, d_w,
-                       static_cast<const mfcc_bank::Rec *>(h->d_out), (long long)k, (long long)SW, h->r.nfft);
+                       static_cast<const mfcc_bank::Rec *>(h->d_out), (long long)k, (long long)SW, h->r.frame_len);
     float *d_raw = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes);
     float *d_stat = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes + rows_bytes);
-    if (emit && (rc = launch(h, false, d_w, nfft, SW, k, /*halo=*/1, d_raw, nullptr, 1))) return rc;
+    if (emit && (rc = launch(h, false, d_w, flen, SW, k, /*halo=*/1, d_raw, nullptr, 1))) return rc;
     if (total) {
         online_passes(b, reinterpret_cast<const mfcc_online::Rec *>(static_cast<const long long *>(h->d_out) + rec_ll), n_cmvn,
                       n_delta, 0, d_raw, d_stat, static_cast<float *>(b->st_out));
@@ -2879,7 +2949,7 @@ int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int w
     }
     ++h->n_sessions;
     DeviceGuard guard(h->device);
-    const size_t bytes = n_streams * size_t(h->r.nfft) * sizeof(int16_t), W = row_width(h->r);
+    const size_t bytes = n_streams * size_t(h->r.frame_len) * sizeof(int16_t), W = row_width(h->r);
     const size_t ring_bytes = n_streams * size_t(b->depth) * W * sizeof(float);
     const size_t tail_bytes = n_streams * size_t(2 * b->lag) * W * sizeof(float);
     auto fail = [&](hipError_t e) {
@@ -2918,7 +2988,7 @@ int mfcc_hip_bank_create_online(mfcc_hip_handle *h, size_t n_streams, int normal
     if (h->destroy_pending || !n_streams) return MFCC_HIP_ERROR_INVALID_PARAM;
     // the bank's settings are its own: the handle must be a raw one, and able to run the float path
     if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !h->fused_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !fused512_any(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (normalize != MFCC_HIP_NORMALIZE_NONE && normalize != MFCC_HIP_NORMALIZE_MEAN && normalize != MFCC_HIP_NORMALIZE_MEAN_VAR)
         return MFCC_HIP_ERROR_INVALID_PARAM;
     if (normalize != MFCC_HIP_NORMALIZE_NONE && (normalize_window < 1 || normalize_window > MFCC_HIP_MAX_NORMALIZE_WINDOW))
@@ -2941,11 +3011,18 @@ int mfcc_hip_bank_held(const mfcc_hip_bank *b, size_t *held) {
 int mfcc_hip_bank_plan_online(const mfcc_hip_params *p, int lag, const size_t *pending, const size_t *held,
                               const size_t *offsets, size_t n_streams, size_t *frame_offsets, size_t *pending_after,
                               size_t *held_after) {
+    return mfcc_hip_bank_plan_online_framed(p, 0, lag, pending, held, offsets, n_streams, frame_offsets, pending_after,
+                                            held_after);
+}
+
+int mfcc_hip_bank_plan_online_framed(const mfcc_hip_params *p, int frame_length, int lag, const size_t *pending,
+                                     const size_t *held, const size_t *offsets, size_t n_streams, size_t *frame_offsets,
+                                     size_t *pending_after, size_t *held_after) {
     if (!p || lag < 0 || !pending || !held || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
     Resolved r;
-    const int rc = resolve(p, r);
+    const int rc = resolve_framed(p, frame_length, r);
     if (rc) return rc;
-    return bank_plan_lagged(size_t(r.nfft), size_t(r.hop), size_t(lag), pending, held, offsets, n_streams, frame_offsets,
+    return bank_plan_lagged(size_t(r.frame_len), size_t(r.hop), size_t(lag), pending, held, offsets, n_streams, frame_offsets,
                             pending_after, held_after, nullptr);
 }
 
@@ -2989,11 +3066,16 @@ int mfcc_hip_bank_pending(const mfcc_hip_bank *b, size_t *pending) {
 
 int mfcc_hip_bank_plan(const mfcc_hip_params *p, const size_t *pending, const size_t *offsets, size_t n_streams,
                        size_t *frame_offsets, size_t *pending_after) {
+    return mfcc_hip_bank_plan_framed(p, 0, pending, offsets, n_streams, frame_offsets, pending_after);
+}
+
+int mfcc_hip_bank_plan_framed(const mfcc_hip_params *p, int frame_length, const size_t *pending, const size_t *offsets,
+                              size_t n_streams, size_t *frame_offsets, size_t *pending_after) {
     if (!p || !pending || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
     Resolved r;
-    const int rc = resolve(p, r);
+    const int rc = resolve_framed(p, frame_length, r);
     if (rc) return rc;
-    return bank_plan_raw(size_t(r.nfft), size_t(r.hop), pending, offsets, n_streams, frame_offsets, pending_after);
+    return bank_plan_raw(size_t(r.frame_len), size_t(r.hop), pending, offsets, n_streams, frame_offsets, pending_after);
 }
 
 int mfcc_hip_bank_push_dev(mfcc_hip_bank *b, const void *d_samples, const size_t *offsets, void *d_out, size_t out_capacity,
@@ -3011,7 +3093,7 @@ int mfcc_hip_bank_push(mfcc_hip_bank *b, const int16_t *samples, const size_t *o
     mfcc_hip_handle *h = b->h;
     const size_t W = bank_row_width(b), esz = b->fixed ? sizeof(int16_t) : sizeof(float);
     // the plan first: a refused push must not have copied anything
-    int rc = bank_plan_lagged(size_t(h->r.nfft), size_t(h->r.hop), size_t(b->lag), b->pending.data(), b->held.data(), offsets,
+    int rc = bank_plan_lagged(size_t(h->r.frame_len), size_t(h->r.hop), size_t(b->lag), b->pending.data(), b->held.data(), offsets,
                               b->n, frame_offsets, nullptr, nullptr, nullptr);
     if (rc) return rc;
     const size_t total = frame_offsets[b->n], span = offsets[b->n] - offsets[0];

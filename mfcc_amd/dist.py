@@ -70,28 +70,33 @@ def plan_items(n_items: int, world: int) -> List[range]:
 
 
 def plan_frames(n_samples: int, world: int, nfft: int = 512, hop: int = 170,
-                n_frames: Optional[int] = None) -> List[FrameShard]:
+                n_frames: Optional[int] = None, frame_length: Optional[int] = None) -> List[FrameShard]:
     """Contiguous frame ranges of ONE stream, with the sample span each rank must read.
+
+    ``frame_length``: the samples a frame owns (``MFCC(win_length=...)``); it defaults to ``nfft`` and takes its place
+    in the counts and spans below.
 
     ``n_frames`` defaults to the notebook count ``(n - nfft)//hop + 1``; pass the STREAM count to
     include the zero-padded tail frame (the rank holding it simply runs past ``n_samples``; the
     kernels zero-pad).  Every rank but the first gets a one-sample history halo."""
+    flen = nfft if frame_length is None else int(frame_length)
     if n_frames is None:
-        n_frames = 0 if n_samples < nfft else (n_samples - nfft) // hop + 1
+        n_frames = 0 if n_samples < flen else (n_samples - flen) // hop + 1
     shards = []
     for rank, fr in enumerate(split_even(n_frames, world)):
         if len(fr) == 0:
             shards.append(FrameShard(rank, fr.start, fr.start, 0, 0, 0))
             continue
         first = fr.start * hop
-        last = (fr.stop - 1) * hop + nfft                     # exclusive
+        last = (fr.stop - 1) * hop + flen                     # exclusive
         halo = 1 if first > 0 else 0
         shards.append(FrameShard(rank, fr.start, fr.stop, first - halo, min(last, n_samples), halo))
     return shards
 
 
 def process_frames_sharded(compute: Callable, pcm: np.ndarray, rank: int, world: int, n_cep: int,
-                           nfft: Optional[int] = None, hop: Optional[int] = None, n_frames: Optional[int] = None):
+                           nfft: Optional[int] = None, hop: Optional[int] = None, n_frames: Optional[int] = None,
+                           frame_length: Optional[int] = None):
     """This rank's part of one stream: returns (shard, coefficients[shard.n_frames, n_cep]).
 
     ``compute(samples, halo, n_frames)`` must return ``n_frames`` rows for frames that start at
@@ -100,10 +105,12 @@ def process_frames_sharded(compute: Callable, pcm: np.ndarray, rank: int, world:
 
     ``nfft`` / ``hop`` default to the geometry ``compute`` carries (its ``nfft`` / ``hop`` attributes, which
     :func:`mfcc_compute` sets from the handle), else to 512 / 170; a value that disagrees with the one ``compute``
-    carries is a ``ValueError`` -- spans planned for another hop would give wrong rows without any other sign."""
+    carries is a ``ValueError`` -- spans planned for another hop would give wrong rows without any other sign.
+    ``frame_length`` likewise (``compute.frame_length``), defaulting to ``nfft``."""
     nfft = _geometry(compute, "nfft", nfft, 512)
     hop = _geometry(compute, "hop", hop, 170)
-    shard = plan_frames(len(pcm), world, nfft, hop, n_frames)[rank]
+    frame_length = _geometry(compute, "frame_length", frame_length, nfft)
+    shard = plan_frames(len(pcm), world, nfft, hop, n_frames, frame_length)[rank]
     if shard.n_frames == 0:
         return shard, np.zeros((0, n_cep), dtype=np.float32)
     out = compute(pcm[shard.sample_lo:shard.sample_hi], shard.halo, shard.n_frames)
@@ -129,10 +136,12 @@ def mfcc_compute(m, fixed: bool = False, device=None) -> Callable:
     because its sample span ends at the end of the stream)."""
     import torch
 
+    flen = int(getattr(m, "win_length", m.nfft))               # the samples a frame owns
+
     def compute(samples, halo, n_frames):
         dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         x = torch.as_tensor(np.ascontiguousarray(samples, dtype=np.int16)).to(dev)
-        need = (n_frames - 1) * m.hop + m.nfft + int(halo)
+        need = (n_frames - 1) * m.hop + flen + int(halo)
         if x.numel() < need and m.num_frames(x.numel() - int(halo)) < n_frames:
             # the zero-padded tail of a STREAM plan run through a NOTEBOOK handle: pad explicitly
             x = torch.cat([x, torch.zeros(need - x.numel(), dtype=torch.int16, device=dev)])
@@ -141,6 +150,7 @@ def mfcc_compute(m, fixed: bool = False, device=None) -> Callable:
         return out[:n_frames].cpu().numpy()
 
     compute.nfft, compute.hop = int(m.nfft), int(m.hop)        # process_frames_sharded plans its spans with these
+    compute.frame_length = flen
     return compute
 
 
