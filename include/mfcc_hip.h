@@ -149,6 +149,47 @@ int  mfcc_hip_create(const mfcc_hip_params *p, mfcc_hip_handle **out);
 int  mfcc_hip_create_framed(const mfcc_hip_params *p, int frame_length, mfcc_hip_handle **out);
 /* the effective frame length of a handle (nfft for a plain one); 0 for NULL */
 int  mfcc_hip_frame_length(const mfcc_hip_handle *h);
+/*
+ * The mel bank as a property of a handle (float path).  MFCC_HIP_MEL_NOTEBOOK is the reference notebook's bank: integer
+ * filter points floor((nfft + 1) / sample_rate * f) between 0 and sample_rate / 2, ramps placed on those points.
+ * MFCC_HIP_MEL_HTK is the bank of the HTK / Kaldi style front ends, with band limits.  Its contract, all of it float64
+ * on the host:
+ *   - mel(f) = 1127 ln(1 + f / 700);
+ *   - edges e_j = mel(low) + j (mel(high) - mel(low)) / (n_mel + 1), j = 0 .. n_mel + 1;
+ *   - bin k lies at m_k = mel(k * sample_rate / nfft), k = 0 .. nfft / 2;
+ *   - W[j][k] = max(0, min((m_k - e_j) / (e_{j+1} - e_j), (e_{j+2} - m_k) / (e_{j+2} - e_{j+1}))), no area
+ *     normalisation, rounded once to fp32 (MFCC_HIP_TABLE_MEL_DENSE_F32 returns exactly these floats);
+ *   - 0 <= low < high <= sample_rate / 2 (high_hz 0 means sample_rate / 2) and 1 <= n_mel <= 64, else
+ *     MFCC_HIP_ERROR_INVALID_PARAM;
+ *   - a filter may be empty at a coarse bin grid (48 kHz with many filters): its band is then -inf in every frame, as
+ *     the definition says;
+ *   - everything outside the matrix is unchanged: pre-emphasis, window, power_scale, log2, DCT, lifter, frame counts.
+ * bank == NULL, or kind NOTEBOOK with both edges 0, IS mfcc_hip_create_framed: the same kernel, the same bits.  NOTEBOOK
+ * with a non-zero edge, an unknown kind, a wrong struct_size or a non-zero reserved word is INVALID_PARAM.
+ * The bank is not part of mfcc_hip_params (whose size, reserved words and ABI version stay as they are).
+ * On an HTK handle:
+ *   - the fixed-point path refuses exactly as on a framed handle: every fixed entry point, fixed session, fixed bank and
+ *     the fixed .mfcc writers return MFCC_HIP_ERROR_UNSUPPORTED;
+ *   - MFCC_HIP_TABLE_MEL_POINTS_I32 and MFCC_HIP_TABLE_FX_MEL_DENSE_U32 are UNSUPPORTED (the bank has no integer points);
+ *   - the float kernel is mfcc_fused512_h160_mb_kernel at nfft 512, hop 160, frame length 160 .. 511, 1 <= n_mel <= 64,
+ *     any sample rate, for log-mel rows and for cepstra with n_cep <= 16 (and no filter weight on bin 0, which no HTK
+ *     bank has); otherwise the generic kernel.  The other fused forms are built around the notebook bank and are never
+ *     selected.  float_impl GENERIC forces the generic kernel, FUSED512 means mfcc_fused512_h160_mb_kernel or
+ *     MFCC_HIP_ERROR_UNSUPPORTED.
+ * Streaming sessions, stream banks, normalization, deltas and VAD work on an HTK handle as on any other.
+ */
+enum mfcc_hip_mel_kind { MFCC_HIP_MEL_NOTEBOOK = 0, MFCC_HIP_MEL_HTK = 1 };
+typedef struct mfcc_hip_mel_bank {
+    uint32_t struct_size;   /* sizeof(mfcc_hip_mel_bank) */
+    int32_t  kind;          /* enum mfcc_hip_mel_kind */
+    float    low_hz;        /* HTK: lower band edge, >= 0 */
+    float    high_hz;       /* HTK: upper band edge; 0 -> sample_rate / 2 */
+    int32_t  reserved[4];   /* must be zero */
+} mfcc_hip_mel_bank;
+int  mfcc_hip_create_banked(const mfcc_hip_params *p, int frame_length, const mfcc_hip_mel_bank *bank,
+                            mfcc_hip_handle **out);
+/* the bank of a handle: kind, low_hz and the effective high_hz (both 0 for a notebook bank) */
+int  mfcc_hip_mel_bank_of(const mfcc_hip_handle *h, mfcc_hip_mel_bank *out);
 /* Lifetime rule: a handle that still has streaming sessions (mfcc_hip_stream_create below) is only MARKED
  * by mfcc_hip_destroy -- its stream, tables and scratch stay valid for those sessions, no new session can be
  * opened on it and no other call may be made with it -- and is freed by the mfcc_hip_stream_destroy of its
@@ -191,6 +232,11 @@ int  mfcc_hip_get_table(const mfcc_hip_params *p, int which, void *buf, size_t c
  * are the periodic Hamming window of that length, the rest 0 (MFCC_HIP_TABLE_FX_MEL_DENSE_U32 is UNSUPPORTED) */
 int  mfcc_hip_get_table_framed(const mfcc_hip_params *p, int frame_length, int which, void *buf, size_t cap_bytes,
                                size_t *n_bytes);
+/* ... of a handle with a mel bank (mfcc_hip_create_banked; bank NULL: the call above).  On an HTK bank
+ * MFCC_HIP_TABLE_MEL_DENSE_F32 is the matrix of the contract and MFCC_HIP_TABLE_MEL_POINTS_I32 and
+ * MFCC_HIP_TABLE_FX_MEL_DENSE_U32 are UNSUPPORTED; the other tables do not depend on the bank */
+int  mfcc_hip_get_table_banked(const mfcc_hip_params *p, int frame_length, const mfcc_hip_mel_bank *bank, int which,
+                               void *buf, size_t cap_bytes, size_t *n_bytes);
 
 /* ---- the hot path: replaces the per-frame ft601_write / ft601_read loop of
  *      mfcc_convert (software/main.c:128-166) ------------------------------------------ */

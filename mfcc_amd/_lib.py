@@ -48,6 +48,9 @@ MAX_NORMALIZE_WINDOW = 16384
 MAX_GATE_WINDOW = 4096
 POWER_THRESHOLD = 100000000
 
+MEL_NOTEBOOK = 0
+MEL_HTK = 1
+
 TABLE_WINDOW_F32 = 0
 TABLE_MEL_POINTS_I32 = 1
 TABLE_MEL_DENSE_F32 = 2
@@ -72,6 +75,17 @@ class Params(C.Structure):
         ("device", C.c_int32),
         ("float_impl", C.c_int32),
         ("output", C.c_int32),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
+class MelBank(C.Structure):
+    """struct mfcc_hip_mel_bank"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("kind", C.c_int32),
+        ("low_hz", C.c_float),
+        ("high_hz", C.c_float),
         ("reserved", C.c_int32 * 4),
     ]
 
@@ -174,6 +188,11 @@ SYMBOLS = {
                                             C.c_void_p]),
     "mfcc_hip_bank_plan_online_framed": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, _SZ, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the mel bank of a handle: mfcc_hip_create_banked and the table helper's _banked twin
+    "mfcc_hip_create_banked": (C.c_int, [C.POINTER(Params), C.c_int, C.POINTER(MelBank), C.POINTER(_H)]),
+    "mfcc_hip_get_table_banked": (C.c_int, [C.POINTER(Params), C.c_int, C.POINTER(MelBank), C.c_int, C.c_void_p, _SZ,
+                                            _PSZ]),
+    "mfcc_hip_mel_bank_of": (C.c_int, [_H, C.POINTER(MelBank)]),
 }
 
 _lib = None

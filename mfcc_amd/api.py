@@ -150,6 +150,42 @@ def _win_length(win_length, nfft, hop) -> int:
     return win_length
 
 
+_MEL = {"notebook": _lib.MEL_NOTEBOOK, "htk": _lib.MEL_HTK}
+
+
+def _mel_bank(mel, fmin, fmax, samplerate, nfilters):
+    """``(mel, fmin, effective fmax, MelBank)`` of the bank arguments (the edges rounded to fp32, as the library holds
+    them and ``mfcc_hip_mel_bank_of`` returns them), checked like ``mfcc_hip_create_banked`` does:
+    ``"notebook"`` takes no band edges (``fmax`` is reported as ``samplerate / 2``, where its points end); ``"htk"``
+    needs ``0 <= fmin < fmax <= samplerate / 2`` (``fmax=None``: ``samplerate / 2``) and 1..64 filters."""
+    def number(v, what):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError("%s must be a finite number, not %r" % (what, v))
+        return float(v)
+    if mel not in _MEL:
+        raise ValueError("mel must be 'notebook' or 'htk', not %r" % (mel,))
+    nyquist = float(int(samplerate)) / 2.0
+    # the bank holds its edges as fp32 (struct mfcc_hip_mel_bank): the checks and the attributes use what it will hold
+    fmin = float(np.float32(number(fmin, "fmin")))
+    top = nyquist if fmax is None else float(np.float32(number(fmax, "fmax")))
+    bank = _lib.MelBank()
+    bank.struct_size = C.sizeof(_lib.MelBank)
+    bank.kind = _MEL[mel]
+    if mel == "notebook":
+        if fmin != 0.0 or fmax is not None:
+            raise ValueError("the notebook bank has no band edges (fmin=%r, fmax=%r): use mel='htk'" % (fmin, fmax))
+        return mel, 0.0, nyquist, bank
+    if not 0.0 <= fmin < top <= nyquist:
+        raise ValueError("need 0 <= fmin < fmax <= samplerate / 2 (%g), not fmin=%g, fmax=%g" % (nyquist, fmin, top))
+    if fmax is not None and top == 0.0:
+        raise ValueError("fmax must be positive, not %r" % (fmax,))
+    if not 1 <= int(nfilters) <= 64:
+        raise ValueError("an htk bank has 1..64 filters, not %r" % (nfilters,))
+    bank.low_hz = fmin
+    bank.high_hz = 0.0 if fmax is None else top
+    return mel, fmin, top, bank
+
+
 def num_frames(n_samples, win_length=None, **kw) -> int:
     """Frames a stream of ``n_samples`` yields (host-only; `nframes`, software/main.c:95); ``win_length``: the frame
     length of a framed handle (``MFCC(win_length=...)``), ``None`` = ``nfft``."""
@@ -169,16 +205,19 @@ _TABLE_DTYPES = {
 }
 
 
-def get_table(which, win_length=None, **kw) -> np.ndarray:
+def get_table(which, win_length=None, mel="notebook", fmin=0.0, fmax=None, **kw) -> np.ndarray:
     """The constant tables as the library's host code builds them (works without a GPU).  ``win_length``: the frame
-    length of a framed handle; only the window table depends on it (``nfft`` floats, zeros from ``win_length`` on)."""
-    lib = _lib.load()
+    length of a framed handle; only the window table depends on it (``nfft`` floats, zeros from ``win_length`` on).
+    ``mel``, ``fmin``, ``fmax``: the bank of the handle (``MFCC(mel=...)``); the dense mel table depends on it, and an
+    ``"htk"`` bank has neither filter points nor a fixed-point table (``UNSUPPORTED``)."""
     L = _win_length(win_length, kw.get("nfft", 512), kw.get("hop"))
+    bank = _mel_bank(mel, fmin, fmax, kw.get("samplerate", 16000), kw.get("nfilters", 32))[3]
+    lib = _lib.load()
     p = make_params(**kw)
     n = C.c_size_t(0)
-    _lib.check(lib.mfcc_hip_get_table_framed(C.byref(p), L, which, None, 0, C.byref(n)), "get_table")
+    _lib.check(lib.mfcc_hip_get_table_banked(C.byref(p), L, C.byref(bank), which, None, 0, C.byref(n)), "get_table")
     buf = np.empty(n.value, dtype=np.uint8)
-    _lib.check(lib.mfcc_hip_get_table_framed(C.byref(p), L, which, buf.ctypes.data, buf.nbytes, C.byref(n)))
+    _lib.check(lib.mfcc_hip_get_table_banked(C.byref(p), L, C.byref(bank), which, buf.ctypes.data, buf.nbytes, C.byref(n)))
     return buf.view(_TABLE_DTYPES[which])
 
 
@@ -199,6 +238,13 @@ class MFCC:
     10 ms at 16 kHz is ``MFCC(nfft=512, hop=160, win_length=400, ...)``.  ``hop <= L <= nfft``; ``None`` (and ``nfft``)
     is the reference's framing.  Frame counts, sessions and banks count ``L`` samples per frame; :attr:`win_length` is
     always the effective length.  Float path only: the fixed-point entries raise ``UNSUPPORTED`` when ``L < nfft``.
+
+    ``mel="htk"`` replaces the notebook's filterbank (integer filter points between 0 and ``samplerate / 2``) by the
+    HTK / Kaldi style one: ``nfilters`` triangles equally spaced on the mel axis ``1127 ln(1 + f / 700)`` between
+    ``fmin`` and ``fmax`` Hz (``None``: ``samplerate / 2``), evaluated at the bin frequencies, no area normalisation
+    (include/mfcc_hip.h has the contract).  Kaldi's 23 bands from 20 Hz are ``MFCC(nfft=512, hop=160, win_length=400,
+    nfilters=23, nceptrums=13, mel="htk", fmin=20)``.  :attr:`mel`, :attr:`fmin` and :attr:`fmax` hold the effective
+    bank.  Float path only, like ``win_length``; sessions, banks and the post-passes take the rows as they are.
 
     ``output="logmel"`` makes every float entry point return rows of ``nfilters`` log2 mel band energies
     (the notebook's ``audio_log.T``, -inf for a silent band) instead of ``nceptrums`` cepstra; the width of a
@@ -230,10 +276,12 @@ class MFCC:
                  pad_mode="notebook", power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra",
                  normalize=None, deltas=0, delta_window=2, normalize_window=None, normalize_min_window=_MIN_WINDOW,
                  normalize_center=True, vad=None, vad_column=0, vad_energy_threshold=5.0, vad_energy_mean_scale=0.5,
-                 vad_frames_context=0, vad_proportion_threshold=0.6, win_length=None):
+                 vad_frames_context=0, vad_proportion_threshold=0.6, win_length=None, mel="notebook", fmin=0.0,
+                 fmax=None):
         if width != 16:
             raise ValueError("only width=16 (int16 PCM) is supported, like every reference target")
         self.win_length = _win_length(win_length, nfft, hop)
+        self.mel, self.fmin, self.fmax, bank = _mel_bank(mel, fmin, fmax, samplerate, nfilters)
         norm = normalize_mode(normalize)
         _window_args(normalize_window, normalize_min_window, normalize_center)
         order, window = _delta_args(deltas, delta_window)
@@ -260,7 +308,7 @@ class MFCC:
                     self._device_index = torch.cuda.current_device()
             except ImportError:
                 pass
-        _lib.check(self._lib.mfcc_hip_create_framed(C.byref(self._params), self.win_length, C.byref(h)),
+        _lib.check(self._lib.mfcc_hip_create_banked(C.byref(self._params), self.win_length, C.byref(bank), C.byref(h)),
                    "mfcc_hip_create")
         self._h = h
         self.normalize = None

@@ -25,6 +25,7 @@
 #include "kernel_fused512.hpp"
 #include "kernel_fused512_w12.hpp"
 #include "kernel_fused512_h160.hpp"
+#include "kernel_fused512_h160_mb.hpp"
 #include "kernel_normalize.hpp"
 #include "kernel_deltas.hpp"
 #include "kernel_normalize_sliding.hpp"
@@ -44,6 +45,8 @@ struct Resolved {
     int device, float_impl;
     int output;                // enum mfcc_hip_output
     int frame_len;             // samples of a frame (hop <= frame_len <= nfft); the window's length.  nfft: a plain handle
+    int mel_kind;              // enum mfcc_hip_mel_kind (mfcc_hip_create_banked); NOTEBOOK: the reference's bank
+    double mel_lo, mel_hi;     // HTK: the band edges in Hz, mel_hi effective (never 0); NOTEBOOK: both 0
 };
 
 // width of an output row: n_mel log-mel values or n_cep coefficients
@@ -67,6 +70,8 @@ int resolve(const mfcc_hip_params *p, Resolved &r) {
     r.float_impl = p->float_impl;
     r.output = p->output;
     r.frame_len = p->nfft;
+    r.mel_kind = MFCC_HIP_MEL_NOTEBOOK;
+    r.mel_lo = r.mel_hi = 0.0;
     if (!is_pow2(r.nfft) || r.nfft < 64 || r.nfft > 1024) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (r.hop < 1 || r.hop > r.nfft) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (r.n_mel < 1 || r.n_mel > mfcc_k::kMaxMel) return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -95,6 +100,32 @@ int resolve_framed(const mfcc_hip_params *p, int frame_length, Resolved &r) {
 
 inline bool is_framed(const Resolved &r) { return r.frame_len != r.nfft; }
 
+// ... and a mel bank (mfcc_hip_create_banked): NULL and NOTEBOOK without edges mean the handle above
+int resolve_banked(const mfcc_hip_params *p, int frame_length, const mfcc_hip_mel_bank *bank, Resolved &r) {
+    const int rc = resolve_framed(p, frame_length, r);
+    if (rc || !bank) return rc;
+    if (bank->struct_size != sizeof(mfcc_hip_mel_bank)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    for (int v : bank->reserved)
+        if (v != 0) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const double lo = double(bank->low_hz), hi = double(bank->high_hz);
+    if (bank->kind == MFCC_HIP_MEL_NOTEBOOK) return (lo == 0.0 && hi == 0.0) ? MFCC_HIP_SUCCESS : MFCC_HIP_ERROR_INVALID_PARAM;
+    if (bank->kind != MFCC_HIP_MEL_HTK) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const double nyq = double(r.sample_rate) / 2.0, top = hi == 0.0 ? nyq : hi;
+    if (!(lo >= 0.0) || !(lo < top) || !(top <= nyq)) return MFCC_HIP_ERROR_INVALID_PARAM;       // NaN fails every test
+    r.mel_kind = MFCC_HIP_MEL_HTK;
+    r.mel_lo = lo;
+    r.mel_hi = top;
+    return MFCC_HIP_SUCCESS;
+}
+
+inline bool is_htk(const Resolved &r) { return r.mel_kind == MFCC_HIP_MEL_HTK; }
+
+// the mel matrix of a handle, [n_mel][nfft / 2 + 1], before the power scale: every float table is built from this
+std::vector<double> handle_mel(const Resolved &r) {
+    if (is_htk(r)) return mel_dense_htk(r.nfft, r.n_mel, double(r.sample_rate), r.mel_lo, r.mel_hi);
+    return mel_dense(r.nfft, r.n_mel, double(r.sample_rate));
+}
+
 size_t count_frames(const Resolved &r, size_t n) {
     const size_t L = size_t(r.frame_len);
     if (r.pad_mode == MFCC_HIP_PAD_NOTEBOOK) {
@@ -115,8 +146,8 @@ std::vector<double> frame_window(const Resolved &r) {
 bool fixed_supported(const Resolved &r) {
     // RTL constraints: FFT sizes are powers of two (mfcc/misc/fft.py:351-353) for both the
     // nfft-point FFT and the (4 * nfilters)-point DCT FFT; hop = nfft // 3 (mfcc/core/mfcc.py:43); the window is the
-    // RTL's ROM curve over nfft samples: no frame length below nfft
-    if (is_framed(r)) return false;
+    // RTL's ROM curve over nfft samples: no frame length below nfft; its filterbank is the notebook's: no HTK bank
+    if (is_framed(r) || is_htk(r)) return false;
     if (!(is_pow2(4 * r.n_mel) && 4 * r.n_mel <= r.nfft && r.n_mel >= 4 && r.hop == r.nfft / 3 && r.nfft >= 64))
         return false;
     // filter points too dense for the streaming filterbank's ramp logic (filterbank.py:22-34, 88-142): the RTL then
@@ -163,6 +194,8 @@ struct mfcc_hip_handle {
     bool fused_w12 = false;       // the twelve-wave form of the fused 512 kernel runs (kernel_fused512_w12.hpp)
     bool fused160_ok = false;     // a framed handle at 512 / hop 160: the four-wave form at that hop (kernel_fused512_h160.hpp);
                                   // its tables are h->fu, its schedule fused_dense; never set together with fused_ok
+    bool fused160mb_ok = false;   // an HTK-bank handle at 512 / hop 160: the matrix-driven form (kernel_fused512_h160_mb.hpp),
+                                  // tables h->fmb; an HTK handle sets none of the other fused flags
     bool fused1k_ok = false;      // the fused 1024/341/40 float kernel covers this handle's parameters
     bool fixed512_ok = false;     // the fused fixed-point kernel covers this handle's parameters
     // device tables (one arena)
@@ -170,6 +203,7 @@ struct mfcc_hip_handle {
     mfcc_k::FloatTables ft{};
     mfcc_k::FixedTables xt{};
     mfcc_fused::FusedTables fu{};
+    mfcc_fused160mb::Tables fmb{};
     mfcc_fixed512::Tables x5{};
     mfcc_fused1024::Tables f1k{};          // bf16-split contraction, set lists for every rate (kernel_fused1024.hpp)
     mfcc_fused1024_f32::Tables f1k_f32{};  // fp32 contraction, one MFMA list per rate (kernel_fused1024_f32.hpp)
@@ -335,7 +369,7 @@ int build_tables(mfcc_hip_handle *h) {
         double ang = -2.0 * kPi * double(k) / double(r.nfft);
         tws[k] = make_float2(float(std::cos(ang)), float(std::sin(ang)));
     }
-    std::vector<double> md = mel_dense(r.nfft, r.n_mel, double(r.sample_rate));
+    std::vector<double> md = handle_mel(r);
     const double inv_s2 = 1.0 / (r.power_scale * r.power_scale);
     std::vector<float> mdf(md.size());
     for (size_t i = 0; i < md.size(); ++i) mdf[i] = float(md[i] * inv_s2);
@@ -400,9 +434,17 @@ int build_tables(mfcc_hip_handle *h) {
     h->fused_dense = false;
     bool fused_dcx = false;
     // a framed handle (frame_len < nfft) runs none of the fused forms below: their windows span nfft samples
-    const bool framed = is_framed(r);
+    // ... and an HTK-bank handle runs the matrix-driven hop-160 form or the generic kernel, nothing else: the band
+    // schedules and DC paths of the other forms are built around the notebook bank
+    const bool framed = is_framed(r), htk = is_htk(r);
+    std::vector<char> fmb_blob;
+    uint32_t fmb_mask = 0;
+    h->fused160mb_ok = htk && mfcc_fused160mb::supported(r.nfft, r.hop, r.frame_len, r.n_mel, r.n_cep, is_logmel(r)) &&
+                       mfcc_fused160mb::build_tables(md, r.n_mel, r.n_cep, r.frame_len, r.power_scale, r.lifter, fmb_blob,
+                                                     fmb_mask);
+    const size_t o_fmb = h->fused160mb_ok ? a.put(fmb_blob) : 0;
     h->fused160_ok = false;
-    if (framed && mfcc_fused160::supported(r.nfft, r.hop, r.frame_len, r.n_mel, r.n_cep)) {
+    if (!htk && framed && mfcc_fused160::supported(r.nfft, r.hop, r.frame_len, r.n_mel, r.n_cep)) {
         // the tables of the hop-170 form (none of them depends on the hop) with the frame's window in place of theirs
         fused_dcx = mfcc_fused::needs_dc_exact(r.sample_rate, r.n_mel);
         h->fused160_ok = !fused_dcx &&
@@ -413,7 +455,7 @@ int build_tables(mfcc_hip_handle *h) {
         }
         if (h->fused160_ok) mfcc_fused160::set_window(fused_blob, h->fused_dense, r.frame_len);
     }
-    if (!framed && mfcc_fused::supported(r.nfft, r.hop, r.n_mel, r.n_cep)) {
+    if (!htk && !framed && mfcc_fused::supported(r.nfft, r.hop, r.n_mel, r.n_cep)) {
         fused_dcx = mfcc_fused::needs_dc_exact(r.sample_rate, r.n_mel);    // only the dense instantiation has the DC path
         h->fused_ok = !fused_dcx &&
                       mfcc_fused::build_tables<false>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
@@ -426,7 +468,7 @@ int build_tables(mfcc_hip_handle *h) {
     if (h->fused_ok || h->fused160_ok) o_fu = a.put(fused_blob);
     std::vector<char> f1k_blob;
     int f1k_var = 0;
-    h->fused1k_ok = !framed && mfcc_fused1024::supported(r.nfft, r.hop, r.n_mel, r.n_cep);
+    h->fused1k_ok = !htk && !framed && mfcc_fused1024::supported(r.nfft, r.hop, r.n_mel, r.n_cep);
     if (h->fused1k_ok) {
         // Default: the twelve-wave staging with the bf16-split contraction (kernel_fused1024_w12.hpp), every rate.
         // MFCC_HIP_FUSED1024 is a diagnostic override for A/B runs -- f32 / bf16: the eight-wave lockstep staging of
@@ -476,6 +518,7 @@ int build_tables(mfcc_hip_handle *h) {
         h->xt.n_cep = r.n_cep;
     }
     if (h->fused_ok || h->fused160_ok) mfcc_fused::bind_tables(b + o_fu, r.n_cep, r.n_mel, h->fused_dense, fused_dcx, h->fu);
+    if (h->fused160mb_ok) mfcc_fused160mb::bind_tables(b + o_fmb, r.n_cep, r.n_mel, fmb_mask, h->fmb);
     {
         // diagnostic override for A/B runs: MFCC_HIP_FUSED512=w4 keeps the four-wave form (not on a log-mel handle:
         // the four-wave form has no log-mel tail)
@@ -511,8 +554,14 @@ bool use_fused160(const mfcc_hip_handle *h) {
     return h->fused160_ok;
 }
 
-// MFCC_HIP_IMPL_FUSED512 asks for the fused 512-point kernel of the handle's framing
-inline bool fused512_any(const mfcc_hip_handle *h) { return h->fused_ok || h->fused160_ok; }
+// ... the matrix-driven hop-160 form of an HTK-bank handle
+bool use_fused160mb(const mfcc_hip_handle *h) {
+    if (h->r.float_impl == MFCC_HIP_IMPL_GENERIC) return false;
+    return h->fused160mb_ok;
+}
+
+// MFCC_HIP_IMPL_FUSED512 asks for the fused 512-point kernel of the handle's framing and bank
+inline bool fused512_any(const mfcc_hip_handle *h) { return h->fused_ok || h->fused160_ok || h->fused160mb_ok; }
 
 // the generic float kernel for every nfft; LOGMEL: its log-mel form
 template <bool LOGMEL>
@@ -586,6 +635,11 @@ int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t s
             default:
                 return MFCC_HIP_ERROR_UNSUPPORTED;
         }
+    } else if (use_fused160mb(h)) {
+        float *o = static_cast<float *>(d_out);
+        if (!(logmel ? mfcc_fused160mb::launch<true>(s, h->fmb, o, h->n_cu, h->stream)
+                     : mfcc_fused160mb::launch<false>(s, h->fmb, o, h->n_cu, h->stream)))
+            return MFCC_HIP_ERROR_UNSUPPORTED;
     } else if (use_fused160(h)) {
         float *o = static_cast<float *>(d_out);
         if (!(logmel ? mfcc_fused160::launch<true>(s, h->fu, h->fused_dense, o, h->n_cu, h->stream)
@@ -1848,8 +1902,13 @@ int mfcc_hip_get_table(const mfcc_hip_params *p, int which, void *buf, size_t ca
 
 int mfcc_hip_get_table_framed(const mfcc_hip_params *p, int frame_length, int which, void *buf, size_t cap,
                               size_t *n_bytes) {
+    return mfcc_hip_get_table_banked(p, frame_length, nullptr, which, buf, cap, n_bytes);
+}
+
+int mfcc_hip_get_table_banked(const mfcc_hip_params *p, int frame_length, const mfcc_hip_mel_bank *bank, int which,
+                              void *buf, size_t cap, size_t *n_bytes) {
     Resolved r;
-    int rc = resolve_framed(p, frame_length, r);
+    int rc = resolve_banked(p, frame_length, bank, r);
     if (rc) return rc;
     std::vector<char> blob;
     auto put = [&](const void *d, size_t n) { blob.assign((const char *)d, (const char *)d + n); };
@@ -1861,12 +1920,13 @@ int mfcc_hip_get_table_framed(const mfcc_hip_params *p, int frame_length, int wh
             break;
         }
         case MFCC_HIP_TABLE_MEL_POINTS_I32: {
+            if (is_htk(r)) return MFCC_HIP_ERROR_UNSUPPORTED;         // the bank has no integer filter points
             std::vector<int> v = mel_points(r.nfft, r.n_mel, double(r.sample_rate));
             put(v.data(), v.size() * 4);
             break;
         }
         case MFCC_HIP_TABLE_MEL_DENSE_F32: {
-            std::vector<double> w = mel_dense(r.nfft, r.n_mel, double(r.sample_rate));
+            std::vector<double> w = handle_mel(r);
             std::vector<float> f(w.begin(), w.end());
             put(f.data(), f.size() * 4);
             break;
@@ -1915,10 +1975,25 @@ int mfcc_hip_create(const mfcc_hip_params *p, mfcc_hip_handle **out) { return mf
 int mfcc_hip_frame_length(const mfcc_hip_handle *h) { return h ? h->r.frame_len : 0; }
 
 int mfcc_hip_create_framed(const mfcc_hip_params *p, int frame_length, mfcc_hip_handle **out) {
+    return mfcc_hip_create_banked(p, frame_length, nullptr, out);
+}
+
+int mfcc_hip_mel_bank_of(const mfcc_hip_handle *h, mfcc_hip_mel_bank *out) {
+    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::memset(out, 0, sizeof *out);
+    out->struct_size = sizeof *out;
+    out->kind = h->r.mel_kind;
+    out->low_hz = float(h->r.mel_lo);
+    out->high_hz = float(h->r.mel_hi);
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_create_banked(const mfcc_hip_params *p, int frame_length, const mfcc_hip_mel_bank *bank,
+                           mfcc_hip_handle **out) {
     if (!out) return MFCC_HIP_ERROR_INVALID_PARAM;
     *out = nullptr;
     Resolved r;
-    int rc = resolve_framed(p, frame_length, r);
+    int rc = resolve_banked(p, frame_length, bank, r);
     if (rc) return rc;
     int ndev = 0;
     g_create_hip_error = int(hipGetDeviceCount(&ndev));
@@ -2267,6 +2342,7 @@ const char *mfcc_hip_kernel_name(const mfcc_hip_handle *h, int fixed) {
     if (fixed) return h->fixed512_ok ? mfcc_fixed512::kernel_name() : "mfcc_fixed_kernel";
     // a log-mel handle runs the twelve-wave forms only (build_tables ignores the diagnostic overrides for it): the
     // names below follow from that
+    if (use_fused160mb(h)) return mfcc_fused160mb::kernel_name();
     if (use_fused160(h)) return mfcc_fused160::kernel_name();
     if (use_fused(h)) return h->fused_w12 ? mfcc_fused12::kernel_name() : mfcc_fused::kernel_name();
     if (h->fused1k_ok && h->r.float_impl == MFCC_HIP_IMPL_AUTO)

@@ -74,6 +74,29 @@ inline std::vector<double> mel_dense(int nfft, int n_mel, double sample_rate) {
     return w;
 }
 
+// HTK-style bank (include/mfcc_hip.h: mfcc_hip_create_banked), all of it in double: mel(f) = 1127 ln(1 + f / 700),
+// n_mel + 2 edges equally spaced on the mel axis between mel(low) and mel(high), bin k at mel(k sample_rate / nfft),
+// triangles on the mel axis with no area normalisation.  Every weight is rounded once to fp32 (and returned as the
+// double that holds that fp32 value), so every table built from this matrix starts from the same bits.
+inline double htk_mel(double f) { return 1127.0 * std::log(1.0 + f / 700.0); }
+
+inline std::vector<double> mel_dense_htk(int nfft, int n_mel, double sample_rate, double low, double high) {
+    const int nb = nfft / 2 + 1;
+    const double ml = htk_mel(low), mh = htk_mel(high);
+    std::vector<double> e(n_mel + 2), m(nb);
+    for (int j = 0; j < n_mel + 2; ++j) e[j] = ml + double(j) * (mh - ml) / double(n_mel + 1);
+    for (int k = 0; k < nb; ++k) m[k] = htk_mel(double(k) * sample_rate / double(nfft));
+    std::vector<double> w(size_t(n_mel) * nb, 0.0);
+    for (int j = 0; j < n_mel; ++j)
+        for (int k = 0; k < nb; ++k) {
+            const double up = (m[k] - e[j]) / (e[j + 1] - e[j]);
+            const double dn = (e[j + 2] - m[k]) / (e[j + 2] - e[j + 1]);
+            const double v = up < dn ? up : dn;
+            w[size_t(j) * nb + k] = v > 0.0 ? double(float(v)) : 0.0;
+        }
+    return w;
+}
+
 // MFCC.ipynb cell 38 dct(): orthonormal DCT-II basis, first n_cep rows; optional
 // sinusoidal lifter of cell 43 / software/lift.py:12-26 folded in (L <= 0: off)
 inline std::vector<double> dct_rows(int n_cep, int n_mel, double lifter_L) {
