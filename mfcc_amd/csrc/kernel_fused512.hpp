@@ -568,6 +568,18 @@ __device__ __forceinline__ void split_bf16_pair(float a, float b, uint32_t &hi, 
     const float ra = a - __uint_as_float(hi << 16), rb = b - __uint_as_float(hi & 0xffff0000u);
     asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(ra), "v"(rb));
 }
+// The same on an ALIGNED register pair (the tail's log-mel values as the 16-byte LDS reads leave them): five instructions --
+// convert, shift and mask into the halves of one pair, ONE packed subtraction for both residuals, convert.  Same bits.
+// (The workers' pairs (pw[kGrpK2[g][2 d]], pw[kGrpK2[g][2 d + 1]]) are not register pairs: there this form costs more in
+// v_mov than it saves; with the K slots reordered to the power codelet's own pairs it does not, 7d.)
+__device__ __forceinline__ void split_bf16_pair(mfcc_codelets::v2f p, uint32_t &hi, uint32_t &lo) {
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi) : "v"(p.x), "v"(p.y));
+    mfcc_codelets::v2f h;
+    h.x = __uint_as_float(hi << 16);
+    h.y = __uint_as_float(hi & 0xffff0000u);
+    const mfcc_codelets::v2f r = p - h;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(r.x), "v"(r.y));
+}
 
 // |X|^2 of a lane's 16 bins -> the B operands of the two K groups, high and low terms
 struct PowerBf {

@@ -240,6 +240,21 @@ struct TileStream {
 #ifndef MFCC_W12_PRIO_P2
 #define MFCC_W12_PRIO_P2 0
 #endif
+#ifndef MFCC_W12_PRIO_PARK
+#define MFCC_W12_PRIO_PARK 3
+#endif
+#ifndef MFCC_W12_PRIO_C16
+#define MFCC_W12_PRIO_C16 3
+#endif
+#ifndef MFCC_W12_PRIO_TAIL
+#define MFCC_W12_PRIO_TAIL 3
+#endif
+
+// Diagnostic builds only (-DMFCC_W12_IDLE=mask, results wrong on purpose): helper work left out for timing --
+// 1: the tail, 2: the parkers' fetch and park, 4: column 16 (tools/ab512t.sh)
+#ifndef MFCC_W12_IDLE
+#define MFCC_W12_IDLE 0
+#endif
 
 // Diagnostic build only (-DMFCC_W12_STAMPS): per wave, the clocks spent working (loop top -> barrier) and the clocks of
 // the whole loop, summed over workgroups; written to a buffer nothing else reads.
@@ -257,7 +272,12 @@ __device__ unsigned long long g_stamps12[kW12Waves * 4];      // [wave]: work ev
 #define W12_LOOP_END
 #endif
 
-template <bool DENSE, bool RAGGED, bool DCX, bool LOGMEL>
+// CEP16: n_cep <= 16 (every shipped front end: 13), the DCT's second M tile -- coefficients 16..31, their products, compares
+// and stores -- does not exist at compile time, and the tail's remaining vector instructions are trimmed (packed Q sums,
+// split on register pairs, store masks computed once: 116 -> 66 per half-step).  LOGMEL runs no DCT: CEP16 = false there.
+// The tail WITH the second M tile keeps the source it had: the same trims there brought back the non-repeatable wrong sums
+// described at the DCT below (tests/test_gpu_dc_band.py, n_cep 32: single coefficients off by 1e-2), DESIGN.md 7d.
+template <bool DENSE, bool RAGGED, bool DCX, bool LOGMEL, bool CEP16 = false>
 __global__ __launch_bounds__(64 * kW12Waves) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, RaggedTables rag, float *__restrict__ out) {
     constexpr int kSets = SetsBf<DENSE>::N;
@@ -404,7 +424,7 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
         const int u = wi * 64 + lane;                  // 0..127
         // the youngest waves of the workgroup lose the issue arbitration against the eight workers (priority, then age)
         // although they have the least to do and everybody waits for them at the barrier
-        __builtin_amdgcn_s_setprio(3);
+        __builtin_amdgcn_s_setprio(MFCC_W12_PRIO_PARK);
         TileStream<RAGGED> pa, pb;
         pa.start(s, g, rag, va, gv, row, out);
         pb.start(s, g, rag, vb, gv, row, out);
@@ -448,6 +468,7 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
         W12_LOOP_BEGIN
         for (int h = 0; h <= last_h; ++h) {
             W12_T0
+            if constexpr (MFCC_W12_IDLE & 2) have_a = have_b = false, ka = nA, kb = nB;
             // A window is re-parked in the half-step in which its group runs pass 1 on operands it already holds in
             // registers: S_A(h / 2 + 1) at even h, S_B((h + 1) / 2) at odd h; the group reads it in its next pass 2
             if (!(h & 1)) {
@@ -477,7 +498,7 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
         W12_LOOP_END;
     } else if (wi == 2) {
         // =========================================================================== column 16 (wave 10)
-        __builtin_amdgcn_s_setprio(3);
+        __builtin_amdgcn_s_setprio(MFCC_W12_PRIO_C16);
         float ax[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) ax[i] = t.a_extra[(1 * kAextra + i) * 64 + lane];
@@ -526,6 +547,8 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
             for (int r = 0; r < 4; ++r) d[(4 * q + r) * 16] = acc[r];
             dts.next(s, rag, row, out);
         };
+        const float *const Vl0 = Vt(0) + lo * kVStride + q, *const Vl1 = Vt(1) + lo * kVStride + q;
+        float *const Ql0 = Qt(0) + (2 * 4) * 256 + lane * 4, *const Ql1 = Qt(1) + (2 * 4) * 256 + lane * 4;
         lds_barrier();                                 // the parkers' two prologue barriers
         if constexpr (DCX) {
             if (nA > 0) dc_tile(0, 0, da);
@@ -538,11 +561,10 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
             // the group in pass 2 at h: A (tile (h - 1) / 2) for odd h, B (tile h / 2 - 1) for even h >= 2
             const int gi = (h & 1) ? 0 : 1;
             const int k = (h & 1) ? (h - 1) / 2 : h / 2 - 1;
-            if (k >= 0 && k < (gi ? nB : nA)) {
-                const float *V = Vt(gi);
-                float *Q = Qt(gi);
-                const float v0 = V[lo * kVStride + 0 + q], v1 = V[lo * kVStride + 4 + q];
-                const float v2 = V[lo * kVStride + 8 + q], v3 = V[lo * kVStride + 12 + q];
+            if (!(MFCC_W12_IDLE & 4) && (unsigned)k < (unsigned)(gi ? nB : nA)) {
+                const float *Vl = (gi ? Vl1 : Vl0);        // this lane's addresses: fixed for the whole launch
+                float *Ql = (gi ? Ql1 : Ql0);
+                const float v0 = Vl[0], v1 = Vl[4], v2 = Vl[8], v3 = Vl[12];
                 f32x4 sp = MFCC_MFMA(ax[0], v0, zero);
                 f32x4 sp2 = MFCC_MFMA(ax[1], v1, zero);
                 sp = MFCC_MFMA(ax[2], v2, sp);
@@ -552,8 +574,8 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                 const float s1 = fmaf(sp[2], sp[2], sp[3] * sp[3]);      // bin 48 + 64 q
                 const f32x4 x0 = MFCC_MFMA(ax[4], s0, zero), y0 = MFCC_MFMA(ax[5], s1, zero);
                 const f32x4 x1 = MFCC_MFMA(ax[6], s0, zero), y1 = MFCC_MFMA(ax[7], s1, zero);
-                *reinterpret_cast<f32x4 *>(Q + (2 * 4 + 0) * 256 + lane * 4) = x0 + y0;
-                *reinterpret_cast<f32x4 *>(Q + (2 * 4 + 1) * 256 + lane * 4) = x1 + y1;
+                *reinterpret_cast<f32x4 *>(Ql) = x0 + y0;
+                *reinterpret_cast<f32x4 *>(Ql + 256) = x1 + y1;
             }
             if constexpr (DCX) {
                 if (h & 1) {
@@ -570,14 +592,15 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
         W12_LOOP_END;
     } else {
         // =========================================================================== tail (wave 11)
-        __builtin_amdgcn_s_setprio(3);
-        float ax[kAextra];
+        __builtin_amdgcn_s_setprio(MFCC_W12_PRIO_TAIL);
+        constexpr int kMTiles = CEP16 ? 1 : 2;         // M tiles of 16 coefficients
+        float ax[8 * kMTiles];
 #pragma unroll
-        for (int i = 0; i < kAextra; ++i) ax[i] = t.a_extra[(0 * kAextra + i) * 64 + lane];
+        for (int i = 0; i < 8 * kMTiles; ++i) ax[i] = t.a_extra[(0 * kAextra + i) * 64 + lane];
 #if MFCC_W12_DCT_BF16
-        u32x4 dct_h[2], dct_l[2];
+        u32x4 dct_h[kMTiles], dct_l[kMTiles];
 #pragma unroll
-        for (int tile = 0; tile < 2; ++tile)
+        for (int tile = 0; tile < kMTiles; ++tile)
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
                 dct_h[tile][d] = t.a_dct_bf[((size_t)tile * 2 + 0) * 256 + d * 64 + lane];
@@ -585,6 +608,10 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
             }
 #endif
         const int lane_off = lo * row + 4 * q;
+        // CEP16: which of this lane's coefficients 4 q + r exist -- lane masks, fixed for the whole launch
+        bool keep_d[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) keep_d[r] = 4 * q + r < t.n_cep;
         TileStream<RAGGED> ta, tb;
         ta.start(s, g, rag, va, gv, row, out);
         tb.start(s, g, rag, vb, gv, row, out);
@@ -609,10 +636,31 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
             // the group that was in pass 2 at h - 1: A (tile h / 2 - 1) for even h, B (tile (h - 3) / 2) for odd h
             const int gi = (h & 1) ? 1 : 0;
             const int k = (h & 1) ? (h - 3) / 2 : h / 2 - 1;
-            if (h >= 2 && k >= 0 && k < (gi ? nB : nA)) {
+            if (!(MFCC_W12_IDLE & 1) && h >= 2 && k >= 0 && k < (gi ? nB : nA)) {
                 const f32x4 *Q4 = reinterpret_cast<const f32x4 *>(Qt(gi)) + lane;
-                f32x4 m0 = ((Q4[0 * 64] + Q4[2 * 64]) + (Q4[4 * 64] + Q4[6 * 64])) + Q4[8 * 64];
-                f32x4 m1 = ((Q4[1 * 64] + Q4[3 * 64]) + (Q4[5 * 64] + Q4[7 * 64])) + Q4[9 * 64];
+                // ((0 + 2) + (4 + 6)) + 8 on the register pairs of the 16-byte reads: four packed additions per pair.  In asm:
+                // from plain vector code the compiler pairs components of DIFFERENT slots and pays three v_mov per sum
+                // (49 instructions for these two lines instead of 16)
+                auto sum5 = [](const f32x4 &a, const f32x4 &b, const f32x4 &c, const f32x4 &d, const f32x4 &e) {
+                    using mfcc_codelets::v2f;
+                    auto add = [](v2f u, v2f v) {
+                        v2f r;
+                        asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(u), "v"(v));
+                        return r;
+                    };
+                    const v2f x = add(add(add(a.xy, b.xy), add(c.xy, d.xy)), e.xy);
+                    const v2f y = add(add(add(a.zw, b.zw), add(c.zw, d.zw)), e.zw);
+                    return (f32x4){x.x, x.y, y.x, y.y};
+                };
+                // (the tail with the second M tile keeps its instruction sequence as it was, see CEP16 below)
+                f32x4 m0, m1;
+                if constexpr (CEP16) {
+                    m0 = sum5(Q4[0 * 64], Q4[2 * 64], Q4[4 * 64], Q4[6 * 64], Q4[8 * 64]);
+                    m1 = sum5(Q4[1 * 64], Q4[3 * 64], Q4[5 * 64], Q4[7 * 64], Q4[9 * 64]);
+                } else {
+                    m0 = ((Q4[0 * 64] + Q4[2 * 64]) + (Q4[4 * 64] + Q4[6 * 64])) + Q4[8 * 64];
+                    m1 = ((Q4[1 * 64] + Q4[3 * 64]) + (Q4[5 * 64] + Q4[7 * 64])) + Q4[9 * 64];
+                }
                 if constexpr (DCX) {                   // bin 0 of frame lo: wave 10's fourteen integer sums, combined in double
                     // sum_j 128^j (lo_j + 256 hi_j) + 128 sum(C), exactly: digits 0..3 and the low 28 bits of the
                     // constant stay below 2^52, digits 4..6 (x 2^-28) and its high part below 2^45 -- every FMA is
@@ -660,7 +708,8 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                     if (gi) finish(tb);
                     else finish(ta);
                 } else {
-                if (t.n_mel <= 16) l1 = zero;          // no filters 16..31 (uniform)
+                if constexpr (DENSE || !CEP16)         // the banded instantiation is the 32-filter bank
+                    if (t.n_mel <= 16) l1 = zero;      // no filters 16..31 (uniform)
 #if MFCC_W12_DCT_BF16
                 // The DCT on bf16-split matrix instructions: K = 32 is the 32 log-mel values of a frame, so an M tile of 16
                 // coefficients is ONE v_mfma_f32_16x16x32_bf16 per term (3 of 16 clocks, which the workers of this SIMD can
@@ -668,16 +717,27 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                 // silent band) would split into (-inf, NaN) and turn c0 = -inf into NaN -- in its own frame only, the
                 // columns of a matrix product do not mix: a tile that holds one runs the fp32 chain as well and the frames
                 // with a -inf take its results (a frame's bits do not depend on what else is in its tile).
-                const float lmin = fminf(fminf(__builtin_fminf(l0[0], l0[1]), __builtin_fminf(l0[2], l0[3])),
-                                         fminf(__builtin_fminf(l1[0], l1[1]), __builtin_fminf(l1[2], l1[3])));
+                // (CEP16: one chain, three v_min3 and a v_min)
+                const float lmin =
+                    CEP16 ? __builtin_fminf(__builtin_fminf(__builtin_fminf(__builtin_fminf(__builtin_fminf(__builtin_fminf(
+                                __builtin_fminf(l0[0], l0[1]), l0[2]), l0[3]), l1[0]), l1[1]), l1[2]), l1[3])
+                          : fminf(fminf(__builtin_fminf(l0[0], l0[1]), __builtin_fminf(l0[2], l0[3])),
+                                  fminf(__builtin_fminf(l1[0], l1[1]), __builtin_fminf(l1[2], l1[3])));
                 const unsigned long long special = __builtin_amdgcn_ballot_w64(!(lmin > -3.0e38f));
                 u32x4 bh, bl;
                 {
                     uint32_t hi, lw;
-                    split_bf16_pair(l0[0], l0[1], hi, lw); bh[0] = hi; bl[0] = lw;
-                    split_bf16_pair(l0[2], l0[3], hi, lw); bh[1] = hi; bl[1] = lw;
-                    split_bf16_pair(l1[0], l1[1], hi, lw); bh[2] = hi; bl[2] = lw;
-                    split_bf16_pair(l1[2], l1[3], hi, lw); bh[3] = hi; bl[3] = lw;
+                    if constexpr (CEP16) {
+                        split_bf16_pair(l0.xy, hi, lw); bh[0] = hi; bl[0] = lw;
+                        split_bf16_pair(l0.zw, hi, lw); bh[1] = hi; bl[1] = lw;
+                        split_bf16_pair(l1.xy, hi, lw); bh[2] = hi; bl[2] = lw;
+                        split_bf16_pair(l1.zw, hi, lw); bh[3] = hi; bl[3] = lw;
+                    } else {
+                        split_bf16_pair(l0[0], l0[1], hi, lw); bh[0] = hi; bl[0] = lw;
+                        split_bf16_pair(l0[2], l0[3], hi, lw); bh[1] = hi; bl[1] = lw;
+                        split_bf16_pair(l1[0], l1[1], hi, lw); bh[2] = hi; bl[2] = lw;
+                        split_bf16_pair(l1[2], l1[3], hi, lw); bh[3] = hi; bl[3] = lw;
+                    }
                 }
                 // THREE INDEPENDENT products per M tile, summed afterwards.  Written as `d = mfma(.., 0); if (n_cep > 16) e =
                 // mfma(.., 0); d = mfma(.., d); if (n_cep > 16) e = mfma(.., e); ...` -- an accumulator chain with the second M
@@ -692,7 +752,7 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                 const f32x4 dA = MFCC_MFMA_BF(dct_h[0], bh, zero), dB = MFCC_MFMA_BF(dct_h[0], bl, zero);
                 const f32x4 dC = MFCC_MFMA_BF(dct_l[0], bh, zero);
                 f32x4 d = (dA + dB) + dC, e = zero;
-                if (t.n_cep > 16) {
+                if constexpr (!CEP16) if (t.n_cep > 16) {
                     const f32x4 eA = MFCC_MFMA_BF(dct_h[1], bh, zero), eB = MFCC_MFMA_BF(dct_h[1], bl, zero);
                     const f32x4 eC = MFCC_MFMA_BF(dct_l[1], bh, zero);
                     e = (eA + eB) + eC;
@@ -703,8 +763,10 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                     for (int r = 0; r < 4; ++r) {
                         d0 = MFCC_MFMA(ax[r], l0[r], d0);
                         d1 = MFCC_MFMA(ax[4 + r], l1[r], d1);
-                        e0 = MFCC_MFMA(ax[8 + r], l0[r], e0);
-                        e1 = MFCC_MFMA(ax[12 + r], l1[r], e1);
+                        if constexpr (!CEP16) {
+                            e0 = MFCC_MFMA(ax[8 + r], l0[r], e0);
+                            e1 = MFCC_MFMA(ax[12 + r], l1[r], e1);
+                        }
                     }
                     // this lane's frame is column lo: its 32 values sit in lanes lo, lo + 16, lo + 32, lo + 48
                     const bool mine = ((special >> lo) & 0x0001000100010001ull) != 0;
@@ -718,7 +780,12 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                     const long long fr0 = (long long)c.c.t_in * kTile;
                     const long long rows_left = c.sl.frames_per_ch - fr0;
                     float *o = c.outp + ((long long)c.c.ch * c.sl.frames_per_ch + fr0) * row + lane_off;
-                    if (lo < rows_left) {
+                    if constexpr (CEP16) {
+                        const bool row_ok = lo < rows_left;     // one compare per tile; the coefficient masks are the launch's
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (row_ok & keep_d[r]) o[r] = d[r];
+                    } else if (lo < rows_left) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             if (4 * q + r < t.n_cep) o[r] = d[r];
@@ -737,6 +804,7 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
                     d1 = MFCC_MFMA(ax[4 + r], l1[r], d1);
                 }
                 // (not `TileStream &c = gi ? tb : ta`: a reference picked at run time puts both walks into scratch)
+                static_assert(!CEP16, "the fp32 tail keeps both M tiles");
                 auto finish = [&](TileStream<RAGGED> &c) {
                     dct_store(c.sl, t, l0, l1, d0, d1, ax, c.c, lo, q, lane_off, c.outp);
                     c.next(s, rag, row, out);
@@ -756,6 +824,26 @@ void mfcc_fused512_w12_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g,
 }
 
 inline const char *kernel_name() { return "mfcc_fused512_w12_kernel"; }
+
+// the instantiation of a call: (DENSE, DCX) from the tables, CEP16 from n_cep where a DCT runs
+template <bool RAGGED, bool LOGMEL>
+inline void launch_w12(bool dcx, bool dense, unsigned wgs, hipStream_t stream, const mfcc_k::StreamDesc &s,
+                       const FusedTables &t, const LaunchGeom &g, const RaggedTables &r, float *out) {
+    auto go = [&](auto dense_c, auto dcx_c, auto cep16_c) {
+        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<decltype(dense_c)::value, RAGGED, decltype(dcx_c)::value, LOGMEL,
+                                                     decltype(cep16_c)::value>),
+                           dim3(wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, r, out);
+    };
+    auto pick = [&](auto cep16_c) {
+        if (dcx) go(std::true_type{}, std::true_type{}, cep16_c);
+        else if (dense) go(std::true_type{}, std::false_type{}, cep16_c);
+        else go(std::false_type{}, std::false_type{}, cep16_c);
+    };
+    if constexpr (!LOGMEL && MFCC_W12_DCT_BF16) {
+        if (t.n_cep <= 16) return pick(std::true_type{});
+    }
+    pick(std::false_type{});
+}
 
 // returns false when the problem does not fit (then the 4-wave kernel runs).  LOGMEL: the log-mel form
 template <bool LOGMEL = false>
@@ -782,12 +870,7 @@ inline bool launch(const mfcc_k::StreamDesc &s, const FusedTables &t, bool dense
     const long long hi = (s.n_samples - kSUsed) / kTileHop;
     g.t_hi = s.n_samples < kSUsed ? -1 : (int)(hi < tiles_per_ch ? hi : tiles_per_ch);
     const RaggedTables none = {nullptr, 0};
-    if (dcx)
-        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<true, false, true, LOGMEL>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, none, out);
-    else if (dense)
-        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<true, false, false, LOGMEL>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, none, out);
-    else
-        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<false, false, false, LOGMEL>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, none, out);
+    launch_w12<false, LOGMEL>(dcx, dense, (unsigned)wgs, stream, s, t, g, none, out);
     return true;
 }
 
@@ -831,12 +914,7 @@ inline bool launch_ragged(const int16_t *d_pcm, const RaggedChan *d_chans, int n
     g.t_lo = 1;
     g.t_hi = -1;
     const RaggedTables r = {d_map, n_tiles};
-    if (dcx)
-        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<true, true, true, LOGMEL>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, r, out);
-    else if (dense)
-        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<true, true, false, LOGMEL>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, r, out);
-    else
-        hipLaunchKernelGGL((mfcc_fused512_w12_kernel<false, true, false, LOGMEL>), dim3((unsigned)wgs), dim3(64 * kW12Waves), 0, stream, s, t, g, r, out);
+    launch_w12<true, LOGMEL>(dcx, dense, (unsigned)wgs, stream, s, t, g, r, out);
     return true;
 }
 
