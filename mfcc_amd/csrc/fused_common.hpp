@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "kernels_generic.hpp"
+#include "launch_geom.hpp"
 
 namespace mfcc_fc {
 
@@ -28,11 +29,12 @@ struct Cursor {
     const int16_t *ptr;      // the tile's first sample: s.pcm + ch * ch_stride + t_in * kTileHop
 };
 
-struct LaunchGeom {
-    int tiles_per_ch, n_ch, grid_div, grid_mod;      // grid = grid_div * tiles_per_ch + grid_mod
-    long long step_ptr, wrap_ptr;                    // samples: ptr step per grid stride / extra step on carry
-    int t_lo, t_hi;                                  // tiles t_lo <= t_in <= t_hi have their window inside the channel
-};
+// LaunchGeom of a stream (launch_geom.hpp); false: the problem does not fit the kernel's 32-bit tile arithmetic
+inline bool launch_geom(const mfcc_k::StreamDesc &s, int n_cu, TileShape k, GridRule rule, int guard_bits, LaunchGeom &g,
+                        unsigned &workgroups) {
+    return launch_geom(s.frames_per_ch, s.total_frames, s.ch_stride, s.n_samples, s.halo, n_cu, k, rule, guard_bits, g,
+                       workgroups);
+}
 
 __device__ __forceinline__ void advance(Cursor &c, const LaunchGeom &g) {
     c.t_in += g.grid_mod;
@@ -58,7 +60,7 @@ __device__ __forceinline__ Window window_of(const Cursor &c, const LaunchGeom &g
     w.ptr = c.ptr;
     w.t_in = c.t_in;
     const int mis = (int)((reinterpret_cast<uintptr_t>(c.ptr) & 15) >> 1);   // samples past alignment
-    // t_lo / t_hi (host): first - 7 - 2 >= -halo (the dword in front of piece 0) and first + kSUsed <= n_samples
+    // t_lo / t_hi (launch_geom.hpp): first - 7 - 2 >= -halo (the dword in front of piece 0) and first + kSUsed <= n_samples
     w.inside = c.t_in >= g.t_lo && c.t_in <= g.t_hi;
     w.shift = w.inside ? mis : 0;
     return w;

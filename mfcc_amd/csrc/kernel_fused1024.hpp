@@ -581,27 +581,13 @@ void mfcc_fused1024_kernel(mfcc_k::StreamDesc s, Tables t, LaunchGeom g, float *
 inline const char *kernel_name() { return "mfcc_fused1024_kernel"; }
 
 inline bool launch(const mfcc_k::StreamDesc &s, const Tables &t, float *out, int n_cu, hipStream_t stream) {
-    const long long tiles_per_ch = (s.frames_per_ch + kTile - 1) / kTile;
-    const long long n_ch = s.total_frames / s.frames_per_ch;
-    const long long n_tiles = tiles_per_ch * n_ch;
-    if (n_tiles >= (1ll << 31) || tiles_per_ch >= (1ll << 26) || n_ch >= (1ll << 31)) return false;
-    long long grid = n_tiles < (long long)n_cu ? n_tiles : (long long)n_cu;
-    if (grid < 1) grid = 1;
     LaunchGeom g;
-    g.tiles_per_ch = (int)tiles_per_ch;
-    g.n_ch = (int)n_ch;
-    g.grid_div = (int)(grid / tiles_per_ch);
-    g.grid_mod = (int)(grid % tiles_per_ch);
-    g.step_ptr = (long long)g.grid_div * s.ch_stride + (long long)g.grid_mod * kTileHop;
-    g.wrap_ptr = s.ch_stride - tiles_per_ch * (long long)kTileHop;
-    g.t_lo = (int)((9 - (long long)s.halo + kTileHop - 1) / kTileHop);
-    if (g.t_lo < 0) g.t_lo = 0;
-    const long long hi = (s.n_samples - kSUsed) / kTileHop;
-    g.t_hi = s.n_samples < kSUsed ? -1 : (int)(hi < tiles_per_ch ? hi : tiles_per_ch);
+    unsigned grid;
+    if (!mfcc_fc::launch_geom(s, n_cu, {kTile, kTileHop, kSUsed}, mfcc_fc::GridRule::kOnePerCu, 31, g, grid)) return false;
     switch (t.variant) {
-    case 1: hipLaunchKernelGGL(mfcc_fused1024_kernel<1>, dim3((unsigned)grid), dim3(64 * kWaves), 0, stream, s, t, g, out); break;
-    case 2: hipLaunchKernelGGL(mfcc_fused1024_kernel<2>, dim3((unsigned)grid), dim3(64 * kWaves), 0, stream, s, t, g, out); break;
-    default: hipLaunchKernelGGL(mfcc_fused1024_kernel<0>, dim3((unsigned)grid), dim3(64 * kWaves), 0, stream, s, t, g, out); break;
+    case 1: hipLaunchKernelGGL(mfcc_fused1024_kernel<1>, dim3(grid), dim3(64 * kWaves), 0, stream, s, t, g, out); break;
+    case 2: hipLaunchKernelGGL(mfcc_fused1024_kernel<2>, dim3(grid), dim3(64 * kWaves), 0, stream, s, t, g, out); break;
+    default: hipLaunchKernelGGL(mfcc_fused1024_kernel<0>, dim3(grid), dim3(64 * kWaves), 0, stream, s, t, g, out); break;
     }
     return true;
 }

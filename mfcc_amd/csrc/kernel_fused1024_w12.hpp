@@ -491,26 +491,10 @@ inline const char *kernel_name() { return "mfcc_fused1024_w12_kernel"; }
 
 // returns false when the problem does not fit (then the eight-wave kernel runs)
 inline bool launch(const mfcc_k::StreamDesc &s, const Tables &t, float *out, int n_cu, hipStream_t stream) {
-    const long long tiles_per_ch = (s.frames_per_ch + kTile - 1) / kTile;
-    const long long n_ch = s.total_frames / s.frames_per_ch;
-    const long long n_tiles = tiles_per_ch * n_ch;
-    if (n_tiles >= (1ll << 30) || tiles_per_ch >= (1ll << 26) || n_ch >= (1ll << 30)) return false;
-    long long wgs = (n_tiles + 1) / 2;
-    if (wgs > n_cu) wgs = n_cu;
-    if (wgs < 1) wgs = 1;
-    const long long grid = 2 * wgs;                      // virtual workgroups: the cursor stride
     LaunchGeom g;
-    g.tiles_per_ch = (int)tiles_per_ch;
-    g.n_ch = (int)n_ch;
-    g.grid_div = (int)(grid / tiles_per_ch);
-    g.grid_mod = (int)(grid % tiles_per_ch);
-    g.step_ptr = (long long)g.grid_div * s.ch_stride + (long long)g.grid_mod * kTileHop;
-    g.wrap_ptr = s.ch_stride - tiles_per_ch * (long long)kTileHop;
-    g.t_lo = (int)((9 - (long long)s.halo + kTileHop - 1) / kTileHop);
-    if (g.t_lo < 0) g.t_lo = 0;
-    const long long hi = (s.n_samples - kSUsed) / kTileHop;
-    g.t_hi = s.n_samples < kSUsed ? -1 : (int)(hi < tiles_per_ch ? hi : tiles_per_ch);
-    const dim3 grid3((unsigned)wgs), block3(64 * kW12Waves);
+    unsigned wgs;
+    if (!mfcc_fc::launch_geom(s, n_cu, {kTile, kTileHop, kSUsed}, mfcc_fc::GridRule::kPairs, 30, g, wgs)) return false;
+    const dim3 grid3(wgs), block3(64 * kW12Waves);
     switch (t.sched) {
     case 1: hipLaunchKernelGGL(mfcc_fused1024_w12_kernel<1>, grid3, block3, 0, stream, s, t, g, out); break;
     case 2: hipLaunchKernelGGL(mfcc_fused1024_w12_kernel<2>, grid3, block3, 0, stream, s, t, g, out); break;
@@ -905,26 +889,10 @@ inline const char *kernel_name() { return "mfcc_fused1024_w12bf_kernel"; }
 
 template <bool LOGMEL = false>
 inline bool launch(const mfcc_k::StreamDesc &s, const Tables &t, float *out, int n_cu, hipStream_t stream) {
-    const long long tiles_per_ch = (s.frames_per_ch + kTile - 1) / kTile;
-    const long long n_ch = s.total_frames / s.frames_per_ch;
-    const long long n_tiles = tiles_per_ch * n_ch;
-    if (n_tiles >= (1ll << 30) || tiles_per_ch >= (1ll << 26) || n_ch >= (1ll << 30)) return false;
-    long long wgs = (n_tiles + 1) / 2;
-    if (wgs > n_cu) wgs = n_cu;
-    if (wgs < 1) wgs = 1;
-    const long long grid = 2 * wgs;
     LaunchGeom g;
-    g.tiles_per_ch = (int)tiles_per_ch;
-    g.n_ch = (int)n_ch;
-    g.grid_div = (int)(grid / tiles_per_ch);
-    g.grid_mod = (int)(grid % tiles_per_ch);
-    g.step_ptr = (long long)g.grid_div * s.ch_stride + (long long)g.grid_mod * kTileHop;
-    g.wrap_ptr = s.ch_stride - tiles_per_ch * (long long)kTileHop;
-    g.t_lo = (int)((9 - (long long)s.halo + kTileHop - 1) / kTileHop);
-    if (g.t_lo < 0) g.t_lo = 0;
-    const long long hi = (s.n_samples - kSUsed) / kTileHop;
-    g.t_hi = s.n_samples < kSUsed ? -1 : (int)(hi < tiles_per_ch ? hi : tiles_per_ch);
-    const dim3 grid3((unsigned)wgs), block3(64 * kW12Waves);
+    unsigned wgs;
+    if (!mfcc_fc::launch_geom(s, n_cu, {kTile, kTileHop, kSUsed}, mfcc_fc::GridRule::kPairs, 30, g, wgs)) return false;
+    const dim3 grid3(wgs), block3(64 * kW12Waves);
     switch (t.variant) {
     case 1: hipLaunchKernelGGL((mfcc_fused1024_w12bf_kernel<1, LOGMEL>), grid3, block3, 0, stream, s, t, g, out); break;
     case 2: hipLaunchKernelGGL((mfcc_fused1024_w12bf_kernel<2, LOGMEL>), grid3, block3, 0, stream, s, t, g, out); break;

@@ -433,26 +433,10 @@ inline const char *kernel_name() { return "mfcc_fused512_h160_mb_kernel"; }
 // returns false when the problem does not fit the kernel's 32-bit tile arithmetic; the geometry is the hop-160 form's
 template <bool LOGMEL>
 inline bool launch(const mfcc_k::StreamDesc &s, const Tables &t, float *out, int n_cu, hipStream_t stream) {
-    const long long tiles_per_ch = (s.frames_per_ch + kTile - 1) / kTile;
-    const long long n_ch = s.total_frames / s.frames_per_ch;
-    const long long n_tiles = tiles_per_ch * n_ch;
-    if (n_tiles >= (1ll << 31) || tiles_per_ch >= (1ll << 26) || n_ch >= (1ll << 31)) return false;
-    long long grid = n_tiles < (long long)n_cu * 2 ? n_tiles : (long long)n_cu * 2;
-    if (grid < 1) grid = 1;
     LaunchGeom g;
-    g.tiles_per_ch = (int)tiles_per_ch;
-    g.n_ch = (int)n_ch;
-    g.grid_div = (int)(grid / tiles_per_ch);
-    g.grid_mod = (int)(grid % tiles_per_ch);
-    g.step_ptr = (long long)g.grid_div * s.ch_stride + (long long)g.grid_mod * kTileHop160;
-    g.wrap_ptr = s.ch_stride - tiles_per_ch * (long long)kTileHop160;
-    // tiles t_lo .. t_hi have their span inside the channel (aligned 16-byte loads); every other tile goes sample by
-    // sample through sample_at_i (kernel_fused512_h160.hpp: launch)
-    g.t_lo = (int)((9 - (long long)s.halo + kTileHop160 - 1) / kTileHop160);
-    if (g.t_lo < 0) g.t_lo = 0;
-    const long long hi = (s.n_samples - kSUsed) / kTileHop160;
-    g.t_hi = s.n_samples < kSUsed ? -1 : (int)(hi < tiles_per_ch ? hi : tiles_per_ch);
-    hipLaunchKernelGGL((mfcc_fused512_h160_mb_kernel<LOGMEL>), dim3((unsigned)grid), dim3(64 * kWaves), 0, stream, s, t, g, out);
+    unsigned grid;
+    if (!mfcc_fc::launch_geom(s, n_cu, {kTile, kTileHop160, kSUsed}, mfcc_fc::GridRule::kTwoPerCu, 31, g, grid)) return false;
+    hipLaunchKernelGGL((mfcc_fused512_h160_mb_kernel<LOGMEL>), dim3(grid), dim3(64 * kWaves), 0, stream, s, t, g, out);
     return true;
 }
 

@@ -53,6 +53,26 @@ struct Resolved {
 inline size_t row_width(const Resolved &r) { return size_t(r.output == MFCC_HIP_OUTPUT_LOGMEL ? r.n_mel : r.n_cep); }
 inline bool is_logmel(const Resolved &r) { return r.output == MFCC_HIP_OUTPUT_LOGMEL; }
 
+// The kernel a handle's float calls run; build_tables decides it when the handle is made.
+enum class FloatKernel {
+    kGeneric,
+    kFused512W12,        // twelve waves (kernel_fused512_w12.hpp): the default at 512/170
+    kFused512,           // four waves (kernel_fused512.hpp)
+    kFused512H160,       // a framed handle at 512 / hop 160 (kernel_fused512_h160.hpp)
+    kFused512H160Mb,     // an HTK-bank handle at 512 / hop 160 (kernel_fused512_h160_mb.hpp)
+    kFused1024W12Bf,     // twelve waves, bf16-split contraction (kernel_fused1024_w12.hpp): the default at 1024/341
+    kFused1024W12F32,    // twelve waves, fp32 contraction
+    kFused1024Bf,        // eight waves, bf16-split contraction (kernel_fused1024.hpp)
+    kFused1024F32,       // eight waves, fp32 contraction (kernel_fused1024_f32.hpp)
+};
+// ... and its fixed-point calls; kNone: every fixed entry point answers UNSUPPORTED
+enum class FixedKernel { kNone, kGeneric, kFixed512 };
+
+inline bool is_fused512(FloatKernel k) {
+    return k == FloatKernel::kFused512W12 || k == FloatKernel::kFused512 || k == FloatKernel::kFused512H160 ||
+           k == FloatKernel::kFused512H160Mb;
+}
+
 int resolve(const mfcc_hip_params *p, Resolved &r) {
     if (!p) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (p->struct_size != sizeof(mfcc_hip_params)) return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -188,16 +208,11 @@ struct mfcc_hip_handle {
     hipStream_t stream = nullptr;
     int last_hip = 0;
     int n_cu = 0;
-    bool fixed_ok = false;
-    bool fused_ok = false;
-    bool fused_dense = false;     // the fused kernel's banded MFMA list does not fit this sample rate: all pairs
-    bool fused_w12 = false;       // the twelve-wave form of the fused 512 kernel runs (kernel_fused512_w12.hpp)
-    bool fused160_ok = false;     // a framed handle at 512 / hop 160: the four-wave form at that hop (kernel_fused512_h160.hpp);
-                                  // its tables are h->fu, its schedule fused_dense; never set together with fused_ok
-    bool fused160mb_ok = false;   // an HTK-bank handle at 512 / hop 160: the matrix-driven form (kernel_fused512_h160_mb.hpp),
-                                  // tables h->fmb; an HTK handle sets none of the other fused flags
-    bool fused1k_ok = false;      // the fused 1024/341/40 float kernel covers this handle's parameters
-    bool fixed512_ok = false;     // the fused fixed-point kernel covers this handle's parameters
+    // which kernel a call runs: both decided once, at the end of build_tables, and only read afterwards (launch,
+    // mfcc_hip_kernel_name, the ragged entry points)
+    FloatKernel float_kernel = FloatKernel::kGeneric;
+    FixedKernel fixed_kernel = FixedKernel::kNone;
+    bool fused_dense = false;     // h->fu holds the all-pairs schedule: the banded MFMA list does not fit this sample rate
     // device tables (one arena)
     void *arena = nullptr;
     mfcc_k::FloatTables ft{};
@@ -205,10 +220,9 @@ struct mfcc_hip_handle {
     mfcc_fused::FusedTables fu{};
     mfcc_fused160mb::Tables fmb{};
     mfcc_fixed512::Tables x5{};
+    // the 1024 forms: one of the two is bound, the one float_kernel names
     mfcc_fused1024::Tables f1k{};          // bf16-split contraction, set lists for every rate (kernel_fused1024.hpp)
     mfcc_fused1024_f32::Tables f1k_f32{};  // fp32 contraction, one MFMA list per rate (kernel_fused1024_f32.hpp)
-    bool f1k_is_f32 = false;      // which of the two forms this handle's rate runs on
-    bool f1k_w12 = false;         // the fp32 form's tables, staged as twelve waves (kernel_fused1024_w12.hpp)
     // descriptor tables of the ragged calls live in pinned host memory, two buffers used in turn: the H2D copy of
     // an asynchronous call reads buffer i while the next call fills buffer 1 - i; the call after that waits for the
     // event recorded behind buffer i's copy before it overwrites it
@@ -393,8 +407,8 @@ int build_tables(mfcc_hip_handle *h) {
     std::vector<int> x5_lanes;
     std::vector<uint32_t> x5_wl;
     FxMel fm;
-    h->fixed_ok = fixed_supported(r) && !is_logmel(r);     // log-mel output is float only: every fixed entry point refuses
-    if (h->fixed_ok) {
+    const bool have_fixed = fixed_supported(r) && !is_logmel(r);     // log-mel output is float only: every fixed entry point refuses
+    if (have_fixed) {
         std::vector<int> cv = fx_window_curve(r.nfft);
         std::vector<int> re, im;
         fx_twiddles(r.nfft, re, im);
@@ -419,10 +433,10 @@ int build_tables(mfcc_hip_handle *h) {
     // ---- fused fixed-point kernel (the RTL's own configuration)
     std::vector<char> x5_blob;
     uint32_t x5_tw[4] = {0, 0, 0, 0};
-    h->fixed512_ok = h->fixed_ok && mfcc_fixed512::supported(r.nfft, r.n_mel, r.n_cep) && x5_lanes_ok &&
-                     mfcc_fixed512::build_tables(r.n_mel, x5_blob, x5_tw);
+    const bool have_fixed512 = have_fixed && mfcc_fixed512::supported(r.nfft, r.n_mel, r.n_cep) && x5_lanes_ok &&
+                               mfcc_fixed512::build_tables(r.n_mel, x5_blob, x5_tw);
     size_t o_x5 = 0, o_x5l = 0, o_x5w = 0;
-    if (h->fixed512_ok) {
+    if (have_fixed512) {
         o_x5 = a.put(x5_blob);
         o_x5l = a.put(x5_lanes);
         o_x5w = a.put(x5_wl);
@@ -430,7 +444,7 @@ int build_tables(mfcc_hip_handle *h) {
 
     // ---- fused 512/170/32 kernel tables
     std::vector<char> fused_blob;
-    h->fused_ok = false;
+    bool have_fused = false;
     h->fused_dense = false;
     bool fused_dcx = false;
     // a framed handle (frame_len < nfft) runs none of the fused forms below: their windows span nfft samples
@@ -439,37 +453,38 @@ int build_tables(mfcc_hip_handle *h) {
     const bool framed = is_framed(r), htk = is_htk(r);
     std::vector<char> fmb_blob;
     uint32_t fmb_mask = 0;
-    h->fused160mb_ok = htk && mfcc_fused160mb::supported(r.nfft, r.hop, r.frame_len, r.n_mel, r.n_cep, is_logmel(r)) &&
-                       mfcc_fused160mb::build_tables(md, r.n_mel, r.n_cep, r.frame_len, r.power_scale, r.lifter, fmb_blob,
-                                                     fmb_mask);
-    const size_t o_fmb = h->fused160mb_ok ? a.put(fmb_blob) : 0;
-    h->fused160_ok = false;
+    const bool have_h160mb = htk && mfcc_fused160mb::supported(r.nfft, r.hop, r.frame_len, r.n_mel, r.n_cep, is_logmel(r)) &&
+                             mfcc_fused160mb::build_tables(md, r.n_mel, r.n_cep, r.frame_len, r.power_scale, r.lifter, fmb_blob,
+                                                           fmb_mask);
+    const size_t o_fmb = have_h160mb ? a.put(fmb_blob) : 0;
+    bool have_h160 = false;
     if (!htk && framed && mfcc_fused160::supported(r.nfft, r.hop, r.frame_len, r.n_mel, r.n_cep)) {
         // the tables of the hop-170 form (none of them depends on the hop) with the frame's window in place of theirs
         fused_dcx = mfcc_fused::needs_dc_exact(r.sample_rate, r.n_mel);
-        h->fused160_ok = !fused_dcx &&
-                         mfcc_fused::build_tables<false>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
-        if (!h->fused160_ok) {
+        have_h160 = !fused_dcx &&
+                    mfcc_fused::build_tables<false>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
+        if (!have_h160) {
             h->fused_dense = true;
-            h->fused160_ok = mfcc_fused::build_tables<true>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
+            have_h160 = mfcc_fused::build_tables<true>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
         }
-        if (h->fused160_ok) mfcc_fused160::set_window(fused_blob, h->fused_dense, r.frame_len);
+        if (have_h160) mfcc_fused160::set_window(fused_blob, h->fused_dense, r.frame_len);
     }
     if (!htk && !framed && mfcc_fused::supported(r.nfft, r.hop, r.n_mel, r.n_cep)) {
         fused_dcx = mfcc_fused::needs_dc_exact(r.sample_rate, r.n_mel);    // only the dense instantiation has the DC path
-        h->fused_ok = !fused_dcx &&
-                      mfcc_fused::build_tables<false>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
-        if (!h->fused_ok) {
+        have_fused = !fused_dcx &&
+                     mfcc_fused::build_tables<false>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
+        if (!have_fused) {
             h->fused_dense = true;
-            h->fused_ok = mfcc_fused::build_tables<true>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
+            have_fused = mfcc_fused::build_tables<true>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
         }
     }
     size_t o_fu = 0;
-    if (h->fused_ok || h->fused160_ok) o_fu = a.put(fused_blob);
+    if (have_fused || have_h160) o_fu = a.put(fused_blob);
     std::vector<char> f1k_blob;
     int f1k_var = 0;
-    h->fused1k_ok = !htk && !framed && mfcc_fused1024::supported(r.nfft, r.hop, r.n_mel, r.n_cep);
-    if (h->fused1k_ok) {
+    bool f1k_fp32 = false, f1k_twelve = false;
+    bool have_1k = !htk && !framed && mfcc_fused1024::supported(r.nfft, r.hop, r.n_mel, r.n_cep);
+    if (have_1k) {
         // Default: the twelve-wave staging with the bf16-split contraction (kernel_fused1024_w12.hpp), every rate.
         // MFCC_HIP_FUSED1024 is a diagnostic override for A/B runs -- f32 / bf16: the eight-wave lockstep staging of
         // either contraction; w12 / w12bf: the twelve-wave staging of either (fp32: the five rates it has lists for)
@@ -477,13 +492,13 @@ int build_tables(mfcc_hip_handle *h) {
         const char *e = is_logmel(r) ? nullptr : std::getenv("MFCC_HIP_FUSED1024");
         auto is = [&](const char *v) { return e && !std::strcmp(e, v); };
         const bool no_f32 = !(is("f32") || is("w12")), no_bf16 = is("f32") || is("w12");
-        h->f1k_w12 = !(is("f32") || is("bf16"));
-        h->f1k_is_f32 = !no_f32 && mfcc_fused1024_f32::build_tables(r.sample_rate, r.power_scale, r.lifter, r.n_cep, f1k_blob, f1k_var);
-        if (!h->f1k_is_f32)
-            h->fused1k_ok = !no_bf16 && mfcc_fused1024::build_tables(r.sample_rate, r.power_scale, r.lifter, r.n_cep, f1k_blob, f1k_var);
+        f1k_twelve = !(is("f32") || is("bf16"));
+        f1k_fp32 = !no_f32 && mfcc_fused1024_f32::build_tables(r.sample_rate, r.power_scale, r.lifter, r.n_cep, f1k_blob, f1k_var);
+        if (!f1k_fp32)
+            have_1k = !no_bf16 && mfcc_fused1024::build_tables(r.sample_rate, r.power_scale, r.lifter, r.n_cep, f1k_blob, f1k_var);
     }
     size_t o_f1k = 0;
-    if (h->fused1k_ok) o_f1k = a.put(f1k_blob);
+    if (have_1k) o_f1k = a.put(f1k_blob);
 
     HIP_TRY(h, hipMalloc(&h->arena, a.host.size() + 256));
     HIP_TRY(h, hipMemcpy(h->arena, a.host.data(), a.host.size(), hipMemcpyHostToDevice));
@@ -500,7 +515,7 @@ int build_tables(mfcc_hip_handle *h) {
     h->ft.window_d = dc_exact ? reinterpret_cast<const double *>(b + o_wd) : nullptr;
     h->ft.n_mel = r.n_mel;
     h->ft.n_cep = r.n_cep;
-    if (h->fixed_ok) {
+    if (have_fixed) {
         h->xt.curve = reinterpret_cast<const int *>(b + o_cv);
         h->xt.tw_fft = reinterpret_cast<const uint2 *>(b + o_xt);
         h->xt.tw_dct = reinterpret_cast<const uint2 *>(b + o_xd);
@@ -517,19 +532,13 @@ int build_tables(mfcc_hip_handle *h) {
         h->xt.log2_dct = ilog2(4 * r.n_mel);
         h->xt.n_cep = r.n_cep;
     }
-    if (h->fused_ok || h->fused160_ok) mfcc_fused::bind_tables(b + o_fu, r.n_cep, r.n_mel, h->fused_dense, fused_dcx, h->fu);
-    if (h->fused160mb_ok) mfcc_fused160mb::bind_tables(b + o_fmb, r.n_cep, r.n_mel, fmb_mask, h->fmb);
-    {
-        // diagnostic override for A/B runs: MFCC_HIP_FUSED512=w4 keeps the four-wave form (not on a log-mel handle:
-        // the four-wave form has no log-mel tail)
-        const char *e = is_logmel(r) ? nullptr : std::getenv("MFCC_HIP_FUSED512");
-        h->fused_w12 = h->fused_ok && !(e && std::strcmp(e, "w4") == 0);
-    }
-    if (h->fused1k_ok) {
-        if (h->f1k_is_f32) mfcc_fused1024_f32::bind_tables(b + o_f1k, r.n_cep, f1k_var, h->f1k_f32);
+    if (have_fused || have_h160) mfcc_fused::bind_tables(b + o_fu, r.n_cep, r.n_mel, h->fused_dense, fused_dcx, h->fu);
+    if (have_h160mb) mfcc_fused160mb::bind_tables(b + o_fmb, r.n_cep, r.n_mel, fmb_mask, h->fmb);
+    if (have_1k) {
+        if (f1k_fp32) mfcc_fused1024_f32::bind_tables(b + o_f1k, r.n_cep, f1k_var, h->f1k_f32);
         else mfcc_fused1024::bind_tables(b + o_f1k, r.n_cep, f1k_var, h->f1k);
     }
-    if (h->fixed512_ok) {
+    if (have_fixed512) {
         mfcc_fixed512::bind_tables(b + o_x5, h->x5);
         h->x5.tw64a = x5_tw[0]; h->x5.tw64b = x5_tw[1]; h->x5.tw192a = x5_tw[2]; h->x5.tw192b = x5_tw[3];
         h->x5.mel_lane = reinterpret_cast<const int4 *>(b + o_x5l);
@@ -540,28 +549,28 @@ int build_tables(mfcc_hip_handle *h) {
         h->x5.n_cep = r.n_cep;
         h->x5.n_mel = r.n_mel;
     }
+
+    // ---- the kernel of every later call, from what was built above and the handle's float_impl
+    h->fixed_kernel = have_fixed512 ? FixedKernel::kFixed512 : have_fixed ? FixedKernel::kGeneric : FixedKernel::kNone;
+    // diagnostic override for A/B runs: MFCC_HIP_FUSED512=w4 keeps the four-wave form (not on a log-mel handle: the
+    // four-wave form has no log-mel tail)
+    const char *e512 = is_logmel(r) ? nullptr : std::getenv("MFCC_HIP_FUSED512");
+    const bool w4 = e512 && std::strcmp(e512, "w4") == 0;
+    h->float_kernel = FloatKernel::kGeneric;
+    if (r.float_impl == MFCC_HIP_IMPL_GENERIC) {
+        // the tables above stay allocated and unused
+    } else if (have_h160mb) {
+        h->float_kernel = FloatKernel::kFused512H160Mb;
+    } else if (have_h160) {
+        h->float_kernel = FloatKernel::kFused512H160;
+    } else if (have_fused) {
+        h->float_kernel = w4 ? FloatKernel::kFused512 : FloatKernel::kFused512W12;
+    } else if (have_1k && r.float_impl == MFCC_HIP_IMPL_AUTO) {
+        h->float_kernel = f1k_twelve ? (f1k_fp32 ? FloatKernel::kFused1024W12F32 : FloatKernel::kFused1024W12Bf)
+                                     : (f1k_fp32 ? FloatKernel::kFused1024F32 : FloatKernel::kFused1024Bf);
+    }
     return MFCC_HIP_SUCCESS;
 }
-
-bool use_fused(const mfcc_hip_handle *h) {
-    if (h->r.float_impl == MFCC_HIP_IMPL_GENERIC) return false;
-    return h->fused_ok;
-}
-
-// ... the hop-160 form of a framed handle
-bool use_fused160(const mfcc_hip_handle *h) {
-    if (h->r.float_impl == MFCC_HIP_IMPL_GENERIC) return false;
-    return h->fused160_ok;
-}
-
-// ... the matrix-driven hop-160 form of an HTK-bank handle
-bool use_fused160mb(const mfcc_hip_handle *h) {
-    if (h->r.float_impl == MFCC_HIP_IMPL_GENERIC) return false;
-    return h->fused160mb_ok;
-}
-
-// MFCC_HIP_IMPL_FUSED512 asks for the fused 512-point kernel of the handle's framing and bank
-inline bool fused512_any(const mfcc_hip_handle *h) { return h->fused_ok || h->fused160_ok || h->fused160mb_ok; }
 
 // the generic float kernel for every nfft; LOGMEL: its log-mel form
 template <bool LOGMEL>
@@ -587,8 +596,8 @@ int launch_generic(mfcc_hip_handle *h, const mfcc_k::StreamDesc &s, unsigned blo
 int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t stride, size_t nch,
            int halo, void *d_out, size_t *n_frames, size_t force_frames = 0) {
     if (!h || (!d_pcm && n * nch) || halo < 0 || halo > 1) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (!fixed && h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !fused512_any(h))
+    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (!fixed && h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel))
         return MFCC_HIP_ERROR_UNSUPPORTED;
     // force_frames: the packed stream of the ragged entry points -- every hop position is a frame
     const size_t nf = force_frames ? force_frames : count_frames(h->r, n);
@@ -609,7 +618,7 @@ int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t s
     DeviceGuard guard(h->device);
     const long long total = s.total_frames;
     const bool logmel = is_logmel(h->r);
-    if (fixed && h->fixed512_ok) {
+    if (fixed && h->fixed_kernel == FixedKernel::kFixed512) {
         mfcc_fixed512::launch(s, h->x5, static_cast<int16_t *>(d_out), h->n_cu, h->stream);
     } else if (fixed) {
         long long blocks = (total + mfcc_k::kWavesPerBlock - 1) / mfcc_k::kWavesPerBlock;
@@ -635,42 +644,59 @@ int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t s
             default:
                 return MFCC_HIP_ERROR_UNSUPPORTED;
         }
-    } else if (use_fused160mb(h)) {
-        float *o = static_cast<float *>(d_out);
-        if (!(logmel ? mfcc_fused160mb::launch<true>(s, h->fmb, o, h->n_cu, h->stream)
-                     : mfcc_fused160mb::launch<false>(s, h->fmb, o, h->n_cu, h->stream)))
-            return MFCC_HIP_ERROR_UNSUPPORTED;
-    } else if (use_fused160(h)) {
-        float *o = static_cast<float *>(d_out);
-        if (!(logmel ? mfcc_fused160::launch<true>(s, h->fu, h->fused_dense, o, h->n_cu, h->stream)
-                     : mfcc_fused160::launch<false>(s, h->fu, h->fused_dense, o, h->n_cu, h->stream)))
-            return MFCC_HIP_ERROR_UNSUPPORTED;
-    } else if (logmel && use_fused(h)) {
-        // log-mel output: the twelve-wave form only (the four-wave one has no log-mel tail)
-        if (!mfcc_fused12::launch<true>(s, h->fu, h->fused_dense, static_cast<float *>(d_out), h->n_cu, h->stream))
-            return MFCC_HIP_ERROR_UNSUPPORTED;
-    } else if (logmel && h->fused1k_ok && h->r.float_impl == MFCC_HIP_IMPL_AUTO) {
-        // the bf16-split twelve-wave form (build_tables leaves the diagnostic overrides aside for a log-mel handle)
-        if (!mfcc_fused1024_w12bf::launch<true>(s, h->f1k, static_cast<float *>(d_out), h->n_cu, h->stream))
-            return MFCC_HIP_ERROR_UNSUPPORTED;
-    } else if (use_fused(h)) {
-        const bool done = h->fused_w12 &&
-                          mfcc_fused12::launch(s, h->fu, h->fused_dense, static_cast<float *>(d_out), h->n_cu, h->stream);
-        if (!done && !mfcc_fused::launch(s, h->fu, h->fused_dense, static_cast<float *>(d_out), h->n_cu, h->stream))
-            return MFCC_HIP_ERROR_UNSUPPORTED;
-    } else if (h->fused1k_ok && h->r.float_impl == MFCC_HIP_IMPL_AUTO &&
-               (h->f1k_is_f32 ? ((h->f1k_w12 && mfcc_fused1024_w12::launch(s, h->f1k_f32, static_cast<float *>(d_out), h->n_cu, h->stream)) ||
-                                 mfcc_fused1024_f32::launch(s, h->f1k_f32, static_cast<float *>(d_out), h->n_cu, h->stream))
-                              : ((h->f1k_w12 && mfcc_fused1024_w12bf::launch(s, h->f1k, static_cast<float *>(d_out), h->n_cu, h->stream)) ||
-                                 mfcc_fused1024::launch(s, h->f1k, static_cast<float *>(d_out), h->n_cu, h->stream)))) {
-        // fused 1024/341/40 kernel launched
     } else {
-        long long blocks = (total + mfcc_k::kWavesPerBlock - 1) / mfcc_k::kWavesPerBlock;
-        long long cap = (long long)h->n_cu * 128;    // measured: 8 per CU 3.55 ms, 32 3.24, 128 3.06 (nfft 256)
-        if (blocks > cap) blocks = cap;
         float *o = static_cast<float *>(d_out);
-        const int rc = logmel ? launch_generic<true>(h, s, (unsigned)blocks, o) : launch_generic<false>(h, s, (unsigned)blocks, o);
-        if (rc) return rc;
+        hipStream_t st = h->stream;
+        const int n_cu = h->n_cu;
+        bool generic = false;
+        // A kernel's launch answers false where the problem does not fit its 32-bit tile arithmetic.  A twelve-wave
+        // form then falls through to the four- / eight-wave form of the same tables, and a 1024 form from there to
+        // the generic kernel; a 512 form and a log-mel handle answer UNSUPPORTED.
+        switch (h->float_kernel) {
+        case FloatKernel::kFused512H160Mb:
+            if (!(logmel ? mfcc_fused160mb::launch<true>(s, h->fmb, o, n_cu, st) : mfcc_fused160mb::launch<false>(s, h->fmb, o, n_cu, st)))
+                return MFCC_HIP_ERROR_UNSUPPORTED;
+            break;
+        case FloatKernel::kFused512H160:
+            if (!(logmel ? mfcc_fused160::launch<true>(s, h->fu, h->fused_dense, o, n_cu, st)
+                         : mfcc_fused160::launch<false>(s, h->fu, h->fused_dense, o, n_cu, st)))
+                return MFCC_HIP_ERROR_UNSUPPORTED;
+            break;
+        case FloatKernel::kFused512W12:
+            if (logmel ? mfcc_fused12::launch<true>(s, h->fu, h->fused_dense, o, n_cu, st)
+                       : mfcc_fused12::launch<false>(s, h->fu, h->fused_dense, o, n_cu, st))
+                break;
+            if (logmel) return MFCC_HIP_ERROR_UNSUPPORTED;       // the four-wave form has no log-mel tail
+            [[fallthrough]];     // does not fit: the four-wave form
+        case FloatKernel::kFused512:
+            if (!mfcc_fused::launch(s, h->fu, h->fused_dense, o, n_cu, st)) return MFCC_HIP_ERROR_UNSUPPORTED;
+            break;
+        case FloatKernel::kFused1024W12Bf:
+            if (logmel ? mfcc_fused1024_w12bf::launch<true>(s, h->f1k, o, n_cu, st)
+                       : mfcc_fused1024_w12bf::launch<false>(s, h->f1k, o, n_cu, st))
+                break;
+            if (logmel) return MFCC_HIP_ERROR_UNSUPPORTED;       // the eight-wave form has no log-mel tail
+            [[fallthrough]];     // does not fit: the eight-wave form
+        case FloatKernel::kFused1024Bf:
+            generic = !mfcc_fused1024::launch(s, h->f1k, o, n_cu, st);       // does not fit: the generic kernel
+            break;
+        case FloatKernel::kFused1024W12F32:
+            if (mfcc_fused1024_w12::launch(s, h->f1k_f32, o, n_cu, st)) break;
+            [[fallthrough]];     // does not fit: the eight-wave form
+        case FloatKernel::kFused1024F32:
+            generic = !mfcc_fused1024_f32::launch(s, h->f1k_f32, o, n_cu, st);   // does not fit: the generic kernel
+            break;
+        case FloatKernel::kGeneric:
+            generic = true;
+            break;
+        }
+        if (generic) {
+            long long blocks = (total + mfcc_k::kWavesPerBlock - 1) / mfcc_k::kWavesPerBlock;
+            long long cap = (long long)n_cu * 128;       // measured: 8 per CU 3.55 ms, 32 3.24, 128 3.06 (nfft 256)
+            if (blocks > cap) blocks = cap;
+            const int rc = logmel ? launch_generic<true>(h, s, (unsigned)blocks, o) : launch_generic<false>(h, s, (unsigned)blocks, o);
+            if (rc) return rc;
+        }
     }
     HIP_TRY(h, hipGetLastError());
     return MFCC_HIP_SUCCESS;
@@ -689,29 +715,97 @@ int ensure(mfcc_hip_handle *h, void **p, size_t *have, size_t want) {
     return MFCC_HIP_SUCCESS;
 }
 
+// ---- the tiles of a segment pass (kernel_normalize.hpp: Segs / tile_of / BlockRec).  Normalization, deltas, sliding
+// normalization, the VAD and the selection all plan their tiles here; each brings its own tile size, its own scratch for
+// the device copy of the table, and its kernels.
+inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
+
+// the uniform form: n_segs segments of seg_rows rows each, back to back from row base_row
+inline mfcc_norm::Segs uniform_segs(int width, int tile_rows, size_t base_row, size_t n_segs, size_t seg_rows) {
+    mfcc_norm::Segs s{};
+    s.width = width;
+    s.tile_rows = tile_rows;
+    s.base_row = (long long)base_row;
+    s.seg_rows = (long long)seg_rows;
+    s.blocks_per_seg = (long long)((seg_rows + size_t(tile_rows) - 1) / size_t(tile_rows));
+    s.n_segs = (long long)n_segs;
+    s.n_blocks = s.blocks_per_seg * s.n_segs;
+    return s;
+}
+
+// Segs and, for the table form, its table [first tile of every segment (n_segs + 1)][one record per tile]: table_ll long
+// longs in the pinned buffer pd, not yet on the device (plan_upload).  The uniform form has pd == nullptr.
+struct SegPlan {
+    mfcc_norm::Segs s;
+    size_t table_ll;
+    mfcc_hip_handle::PinnedDesc *pd;
+};
+
+// The tiles of tr rows of segments off[0 .. n_segs] (off does not decrease, off[n_segs] > off[0]): the uniform form when
+// every segment has one length, else the table form
+int plan_segs(mfcc_hip_handle *h, const size_t *off, size_t n_segs, int width, int tile_rows, SegPlan &pl) {
+    const size_t tr = size_t(tile_rows);
+    pl = SegPlan{};
+    const size_t len0 = off[1] - off[0];
+    bool uniform = true;
+    for (size_t k = 1; k < n_segs && uniform; ++k) uniform = off[k + 1] - off[k] == len0;
+    if (uniform) {
+        pl.s = uniform_segs(width, tile_rows, off[0], n_segs, len0);
+        return MFCC_HIP_SUCCESS;
+    }
+    size_t n_blocks = 0;
+    for (size_t k = 0; k < n_segs; ++k) n_blocks += (off[k + 1] - off[k] + tr - 1) / tr;
+    if (n_segs >= (size_t(1) << 31)) return MFCC_HIP_ERROR_INVALID_PARAM;       // BlockRec::seg is an int
+    static_assert(sizeof(mfcc_norm::BlockRec) == 2 * sizeof(long long), "record layout");
+    pl.table_ll = n_segs + 1 + 2 * n_blocks;
+    const int rc = desc_acquire(h, pl.table_ll, &pl.pd);
+    if (rc) return rc;
+    long long *blk0 = pl.pd->p;
+    auto *rec = reinterpret_cast<mfcc_norm::BlockRec *>(pl.pd->p + n_segs + 1);
+    size_t b = 0;
+    for (size_t k = 0; k < n_segs; ++k) {
+        blk0[k] = (long long)b;
+        for (size_t r = off[k]; r < off[k + 1]; r += tr)
+            rec[b++] = mfcc_norm::BlockRec{(long long)r, int(std::min(tr, off[k + 1] - r)), int(k)};
+    }
+    blk0[n_segs] = (long long)b;
+    pl.s.width = width;
+    pl.s.tile_rows = tile_rows;
+    pl.s.n_segs = (long long)n_segs;
+    pl.s.n_blocks = (long long)n_blocks;
+    return MFCC_HIP_SUCCESS;
+}
+
+// copies a table form's table to d_table (the pass's own scratch, table_ll long longs) and points pl.s at it; the pinned
+// buffer is free again once the event recorded behind the copy has passed
+int plan_upload(mfcc_hip_handle *h, SegPlan &pl, long long *d_table) {
+    if (!pl.pd) return MFCC_HIP_SUCCESS;
+    HIP_TRY(h, hipMemcpyAsync(d_table, pl.pd->p, pl.table_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    pl.s.seg_blk0 = d_table;
+    pl.s.blk = reinterpret_cast<const mfcc_norm::BlockRec *>(d_table + pl.s.n_segs + 1);
+    HIP_TRY(h, hipEventRecord(pl.pd->copied, h->stream));
+    pl.pd->in_flight = true;
+    return MFCC_HIP_SUCCESS;
+}
+
+inline unsigned tile_grid(long long n) { return unsigned(std::min<long long>(n, 1 << 20)); }
+
 // ---- per-segment mean / variance normalization (kernel_normalize.hpp): every float entry point
 // of a handle with a mode other than NONE runs this after its kernels, on the handle's stream, over the rows it wrote.
-// Scratch (h->d_norm): [tile partials: n_blocks * W * 24 B][coefficients: n_segs * W * 8 B][table form: the first tile
-// of every segment (n_segs + 1) and one record per tile].  The table is built in pinned memory (desc_acquire).
-int normalize_enqueue(mfcc_hip_handle *h, float *d_rows, mfcc_norm::Segs s, const long long *host_table,
-                      size_t table_ll, int mode) {
-    const size_t W = size_t(s.width);
-    const size_t part_bytes = (size_t(s.n_blocks) * W * sizeof(mfcc_norm::Part) + 255) & ~size_t(255);
-    const size_t coef_bytes = (size_t(s.n_segs) * W * sizeof(float2) + 255) & ~size_t(255);
-    int rc = ensure(h, &h->d_norm, &h->d_norm_bytes, part_bytes + coef_bytes + table_ll * sizeof(long long) + 64);
+// Scratch (h->d_norm): [tile partials: n_blocks * W * 24 B][coefficients: n_segs * W * 8 B][tile table]
+int normalize_enqueue(mfcc_hip_handle *h, float *d_rows, SegPlan pl, int mode) {
+    const size_t W = size_t(pl.s.width);
+    const size_t part_bytes = up256(size_t(pl.s.n_blocks) * W * sizeof(mfcc_norm::Part));
+    const size_t coef_bytes = up256(size_t(pl.s.n_segs) * W * sizeof(float2));
+    int rc = ensure(h, &h->d_norm, &h->d_norm_bytes, part_bytes + coef_bytes + pl.table_ll * sizeof(long long) + 64);
     if (rc) return rc;
     if ((rc = scratch_acquire(h))) return rc;
     char *base = static_cast<char *>(h->d_norm);
     auto *part = reinterpret_cast<mfcc_norm::Part *>(base);
     auto *coef = reinterpret_cast<float2 *>(base + part_bytes);
-    if (host_table) {
-        long long *d_table = reinterpret_cast<long long *>(base + part_bytes + coef_bytes);
-        HIP_TRY(h, hipMemcpyAsync(d_table, host_table, table_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-        s.seg_blk0 = d_table;
-        s.blk = reinterpret_cast<const mfcc_norm::BlockRec *>(d_table + s.n_segs + 1);
-    }
-    const unsigned grid = unsigned(std::min<long long>(s.n_blocks, 1 << 20));
-    const unsigned grid_f = unsigned(std::min<long long>(s.n_segs, 1 << 20));
+    if ((rc = plan_upload(h, pl, reinterpret_cast<long long *>(base + part_bytes + coef_bytes)))) return rc;
+    const mfcc_norm::Segs &s = pl.s;
+    const unsigned grid = tile_grid(s.n_blocks), grid_f = tile_grid(s.n_segs);
     hipLaunchKernelGGL(mfcc_norm::normalize_stats_kernel, dim3(grid), dim3(mfcc_norm::kThreads), 0, h->stream,
                        static_cast<const float *>(d_rows), s, part);
     hipLaunchKernelGGL(mfcc_norm::normalize_finalize_kernel, dim3(grid_f), dim3(mfcc_norm::kThreads), 0, h->stream, s,
@@ -726,72 +820,29 @@ int normalize_enqueue(mfcc_hip_handle *h, float *d_rows, mfcc_norm::Segs s, cons
 int normalize_uniform(mfcc_hip_handle *h, float *d_rows, int width, size_t base_row, size_t n_segs, size_t seg_rows,
                       int mode) {
     if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0 || seg_rows == 0) return MFCC_HIP_SUCCESS;
-    mfcc_norm::Segs s{};
-    s.width = width;
-    s.tile_rows = mfcc_norm::tile_rows(width);
-    s.base_row = (long long)base_row;
-    s.seg_rows = (long long)seg_rows;
-    s.blocks_per_seg = (long long)((seg_rows + size_t(s.tile_rows) - 1) / size_t(s.tile_rows));
-    s.n_segs = (long long)n_segs;
-    s.n_blocks = s.blocks_per_seg * s.n_segs;
-    return normalize_enqueue(h, d_rows, s, nullptr, 0, mode);
+    const SegPlan pl{uniform_segs(width, mfcc_norm::tile_rows(width), base_row, n_segs, seg_rows), 0, nullptr};
+    return normalize_enqueue(h, d_rows, pl, mode);
 }
 
 // segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
 int normalize_segments(mfcc_hip_handle *h, float *d_rows, int width, const size_t *off, size_t n_segs, int mode) {
     if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0 || off[n_segs] == off[0]) return MFCC_HIP_SUCCESS;
-    const size_t len0 = off[1] - off[0];
-    bool uniform = true;
-    for (size_t k = 1; k < n_segs && uniform; ++k) uniform = off[k + 1] - off[k] == len0;
-    if (uniform) return normalize_uniform(h, d_rows, width, off[0], n_segs, len0, mode);
-    const size_t tr = size_t(mfcc_norm::tile_rows(width));
-    size_t n_blocks = 0;
-    for (size_t k = 0; k < n_segs; ++k) n_blocks += (off[k + 1] - off[k] + tr - 1) / tr;
-    if (n_segs >= (size_t(1) << 31)) return MFCC_HIP_ERROR_INVALID_PARAM;       // BlockRec::seg is an int
-    static_assert(sizeof(mfcc_norm::BlockRec) == 2 * sizeof(long long), "record layout");
-    const size_t table_ll = n_segs + 1 + 2 * n_blocks;
-    mfcc_hip_handle::PinnedDesc *pd = nullptr;
-    int rc = desc_acquire(h, table_ll, &pd);
-    if (rc) return rc;
-    long long *blk0 = pd->p;
-    auto *rec = reinterpret_cast<mfcc_norm::BlockRec *>(pd->p + n_segs + 1);
-    size_t b = 0;
-    for (size_t k = 0; k < n_segs; ++k) {
-        blk0[k] = (long long)b;
-        for (size_t r = off[k]; r < off[k + 1]; r += tr)
-            rec[b++] = mfcc_norm::BlockRec{(long long)r, int(std::min(tr, off[k + 1] - r)), int(k)};
-    }
-    blk0[n_segs] = (long long)b;
-    mfcc_norm::Segs s{};
-    s.width = width;
-    s.tile_rows = int(tr);
-    s.n_segs = (long long)n_segs;
-    s.n_blocks = (long long)n_blocks;
-    rc = normalize_enqueue(h, d_rows, s, pd->p, table_ll, mode);
-    if (rc) return rc;
-    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
-    pd->in_flight = true;
-    return MFCC_HIP_SUCCESS;
+    SegPlan pl;
+    const int rc = plan_segs(h, off, n_segs, width, mfcc_norm::tile_rows(width), pl);
+    return rc ? rc : normalize_enqueue(h, d_rows, pl, mode);
 }
 
 // ---- delta coefficients (kernel_deltas.hpp): a handle with a delta order runs its kernels and
 // its normalization into h->d_stat, then this pass writes the expanded rows to the caller's buffer.  The tile table of
-// a ragged call goes to h->d_dtab ([first tile of every segment (n_segs + 1)][one record per tile], as normalization's)
-int deltas_enqueue(mfcc_hip_handle *h, const float *d_in, float *d_out, mfcc_norm::Segs s, const long long *host_table,
-                   size_t table_ll, int order, int window) {
+// a ragged call goes to h->d_dtab
+int deltas_enqueue(mfcc_hip_handle *h, const float *d_in, float *d_out, SegPlan pl, int order, int window) {
     int rc = scratch_acquire(h);
     if (rc) return rc;
-    if (host_table) {
-        if ((rc = ensure(h, &h->d_dtab, &h->d_dtab_bytes, table_ll * sizeof(long long) + 64))) return rc;
-        long long *d_table = static_cast<long long *>(h->d_dtab);
-        HIP_TRY(h, hipMemcpyAsync(d_table, host_table, table_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-        s.seg_blk0 = d_table;
-        s.blk = reinterpret_cast<const mfcc_norm::BlockRec *>(d_table + s.n_segs + 1);
-    }
-    const unsigned grid = unsigned(std::min<long long>(s.n_blocks, 1 << 20));
+    if (pl.pd && (rc = ensure(h, &h->d_dtab, &h->d_dtab_bytes, pl.table_ll * sizeof(long long) + 64))) return rc;
+    if ((rc = plan_upload(h, pl, static_cast<long long *>(h->d_dtab)))) return rc;
     const mfcc_delta::DeltasKernel kernel = mfcc_delta::deltas_kernel_of(order, window);
     if (!kernel) return MFCC_HIP_ERROR_INVALID_PARAM;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(mfcc_delta::kThreads), 0, h->stream, d_in, d_out, s,
+    hipLaunchKernelGGL(kernel, dim3(tile_grid(pl.s.n_blocks)), dim3(mfcc_delta::kThreads), 0, h->stream, d_in, d_out, pl.s,
                        mfcc_delta::delta_scale(window));
     HIP_TRY(h, hipGetLastError());
     return scratch_release(h);
@@ -801,57 +852,22 @@ int deltas_enqueue(mfcc_hip_handle *h, const float *d_in, float *d_out, mfcc_nor
 int deltas_uniform(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, size_t base_row, size_t n_segs,
                    size_t seg_rows, int order, int window) {
     if (n_segs == 0 || seg_rows == 0) return MFCC_HIP_SUCCESS;
-    mfcc_norm::Segs s{};
-    s.width = width;
-    s.tile_rows = mfcc_delta::tile_rows(width, order, window);
-    s.base_row = (long long)base_row;
-    s.seg_rows = (long long)seg_rows;
-    s.blocks_per_seg = (long long)((seg_rows + size_t(s.tile_rows) - 1) / size_t(s.tile_rows));
-    s.n_segs = (long long)n_segs;
-    s.n_blocks = s.blocks_per_seg * s.n_segs;
-    return deltas_enqueue(h, d_in, d_out, s, nullptr, 0, order, window);
+    const SegPlan pl{uniform_segs(width, mfcc_delta::tile_rows(width, order, window), base_row, n_segs, seg_rows), 0, nullptr};
+    return deltas_enqueue(h, d_in, d_out, pl, order, window);
 }
 
 // segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
 int deltas_segments(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, const size_t *off, size_t n_segs,
                     int order, int window) {
     if (n_segs == 0 || off[n_segs] == off[0]) return MFCC_HIP_SUCCESS;
-    const size_t len0 = off[1] - off[0];
-    bool uniform = true;
-    for (size_t k = 1; k < n_segs && uniform; ++k) uniform = off[k + 1] - off[k] == len0;
-    if (uniform) return deltas_uniform(h, d_in, d_out, width, off[0], n_segs, len0, order, window);
-    const size_t tr = size_t(mfcc_delta::tile_rows(width, order, window));
-    size_t n_blocks = 0;
-    for (size_t k = 0; k < n_segs; ++k) n_blocks += (off[k + 1] - off[k] + tr - 1) / tr;
-    if (n_segs >= (size_t(1) << 31)) return MFCC_HIP_ERROR_INVALID_PARAM;       // BlockRec::seg is an int
-    const size_t table_ll = n_segs + 1 + 2 * n_blocks;
-    mfcc_hip_handle::PinnedDesc *pd = nullptr;
-    int rc = desc_acquire(h, table_ll, &pd);
-    if (rc) return rc;
-    long long *blk0 = pd->p;
-    auto *rec = reinterpret_cast<mfcc_norm::BlockRec *>(pd->p + n_segs + 1);
-    size_t b = 0;
-    for (size_t k = 0; k < n_segs; ++k) {
-        blk0[k] = (long long)b;
-        for (size_t r = off[k]; r < off[k + 1]; r += tr)
-            rec[b++] = mfcc_norm::BlockRec{(long long)r, int(std::min(tr, off[k + 1] - r)), int(k)};
-    }
-    blk0[n_segs] = (long long)b;
-    mfcc_norm::Segs s{};
-    s.width = width;
-    s.tile_rows = int(tr);
-    s.n_segs = (long long)n_segs;
-    s.n_blocks = (long long)n_blocks;
-    rc = deltas_enqueue(h, d_in, d_out, s, pd->p, table_ll, order, window);
-    if (rc) return rc;
-    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
-    pd->in_flight = true;
-    return MFCC_HIP_SUCCESS;
+    SegPlan pl;
+    const int rc = plan_segs(h, off, n_segs, width, mfcc_delta::tile_rows(width, order, window), pl);
+    return rc ? rc : deltas_enqueue(h, d_in, d_out, pl, order, window);
 }
 
 // ---- sliding-window normalization (kernel_normalize_sliding.hpp): out of place.  A handle with
 // a window runs its kernels into h->d_slide, then this pass writes the normalized rows to the caller's buffer (or to
-// h->d_stat, when deltas follow).  The tile table of a ragged call goes to h->d_stab (layout as normalization's)
+// h->d_stat, when deltas follow).  The tile table of a ragged call goes to h->d_stab
 struct SlideArgs {
     int mode, window, min_window, center;
 };
@@ -861,20 +877,13 @@ inline SlideArgs slide_args(const mfcc_hip_handle *h) {
     return SlideArgs{h->norm, h->norm_window, h->norm_min_window, h->norm_center};
 }
 
-int sliding_enqueue(mfcc_hip_handle *h, const float *d_in, float *d_out, mfcc_norm::Segs s, const long long *host_table,
-                    size_t table_ll, SlideArgs a) {
+int sliding_enqueue(mfcc_hip_handle *h, const float *d_in, float *d_out, SegPlan pl, SlideArgs a) {
     int rc = scratch_acquire(h);
     if (rc) return rc;
-    if (host_table) {
-        if ((rc = ensure(h, &h->d_stab, &h->d_stab_bytes, table_ll * sizeof(long long) + 64))) return rc;
-        long long *d_table = static_cast<long long *>(h->d_stab);
-        HIP_TRY(h, hipMemcpyAsync(d_table, host_table, table_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-        s.seg_blk0 = d_table;
-        s.blk = reinterpret_cast<const mfcc_norm::BlockRec *>(d_table + s.n_segs + 1);
-    }
-    const unsigned grid = unsigned(std::min<long long>(s.n_blocks, 1 << 20));
-    hipLaunchKernelGGL(mfcc_slide::normalize_sliding_kernel, dim3(grid), dim3(mfcc_slide::kThreads), 0, h->stream, d_in,
-                       d_out, s, mfcc_slide::run_rows(a.window), a.window, a.min_window, a.center, a.mode);
+    if (pl.pd && (rc = ensure(h, &h->d_stab, &h->d_stab_bytes, pl.table_ll * sizeof(long long) + 64))) return rc;
+    if ((rc = plan_upload(h, pl, static_cast<long long *>(h->d_stab)))) return rc;
+    hipLaunchKernelGGL(mfcc_slide::normalize_sliding_kernel, dim3(tile_grid(pl.s.n_blocks)), dim3(mfcc_slide::kThreads), 0,
+                       h->stream, d_in, d_out, pl.s, mfcc_slide::run_rows(a.window), a.window, a.min_window, a.center, a.mode);
     HIP_TRY(h, hipGetLastError());
     return scratch_release(h);
 }
@@ -883,52 +892,17 @@ int sliding_enqueue(mfcc_hip_handle *h, const float *d_in, float *d_out, mfcc_no
 int sliding_uniform(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, size_t base_row, size_t n_segs,
                     size_t seg_rows, SlideArgs a) {
     if (n_segs == 0 || seg_rows == 0) return MFCC_HIP_SUCCESS;
-    mfcc_norm::Segs s{};
-    s.width = width;
-    s.tile_rows = mfcc_slide::tile_rows(width, a.window);
-    s.base_row = (long long)base_row;
-    s.seg_rows = (long long)seg_rows;
-    s.blocks_per_seg = (long long)((seg_rows + size_t(s.tile_rows) - 1) / size_t(s.tile_rows));
-    s.n_segs = (long long)n_segs;
-    s.n_blocks = s.blocks_per_seg * s.n_segs;
-    return sliding_enqueue(h, d_in, d_out, s, nullptr, 0, a);
+    const SegPlan pl{uniform_segs(width, mfcc_slide::tile_rows(width, a.window), base_row, n_segs, seg_rows), 0, nullptr};
+    return sliding_enqueue(h, d_in, d_out, pl, a);
 }
 
 // segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
 int sliding_segments(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, const size_t *off, size_t n_segs,
                      SlideArgs a) {
     if (n_segs == 0 || off[n_segs] == off[0]) return MFCC_HIP_SUCCESS;
-    const size_t len0 = off[1] - off[0];
-    bool uniform = true;
-    for (size_t k = 1; k < n_segs && uniform; ++k) uniform = off[k + 1] - off[k] == len0;
-    if (uniform) return sliding_uniform(h, d_in, d_out, width, off[0], n_segs, len0, a);
-    const size_t tr = size_t(mfcc_slide::tile_rows(width, a.window));
-    size_t n_blocks = 0;
-    for (size_t k = 0; k < n_segs; ++k) n_blocks += (off[k + 1] - off[k] + tr - 1) / tr;
-    if (n_segs >= (size_t(1) << 31)) return MFCC_HIP_ERROR_INVALID_PARAM;       // BlockRec::seg is an int
-    const size_t table_ll = n_segs + 1 + 2 * n_blocks;
-    mfcc_hip_handle::PinnedDesc *pd = nullptr;
-    int rc = desc_acquire(h, table_ll, &pd);
-    if (rc) return rc;
-    long long *blk0 = pd->p;
-    auto *rec = reinterpret_cast<mfcc_norm::BlockRec *>(pd->p + n_segs + 1);
-    size_t b = 0;
-    for (size_t k = 0; k < n_segs; ++k) {
-        blk0[k] = (long long)b;
-        for (size_t r = off[k]; r < off[k + 1]; r += tr)
-            rec[b++] = mfcc_norm::BlockRec{(long long)r, int(std::min(tr, off[k + 1] - r)), int(k)};
-    }
-    blk0[n_segs] = (long long)b;
-    mfcc_norm::Segs s{};
-    s.width = width;
-    s.tile_rows = int(tr);
-    s.n_segs = (long long)n_segs;
-    s.n_blocks = (long long)n_blocks;
-    rc = sliding_enqueue(h, d_in, d_out, s, pd->p, table_ll, a);
-    if (rc) return rc;
-    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
-    pd->in_flight = true;
-    return MFCC_HIP_SUCCESS;
+    SegPlan pl;
+    const int rc = plan_segs(h, off, n_segs, width, mfcc_slide::tile_rows(width, a.window), pl);
+    return rc ? rc : sliding_enqueue(h, d_in, d_out, pl, a);
 }
 
 // ---- energy VAD and voiced-row selection (kernel_vad.hpp).  The decision reads one column of
@@ -951,59 +925,6 @@ inline bool vad_args_ok(int width, int column, float threshold, float scale, int
            context >= 0 && context <= MFCC_HIP_MAX_VAD_CONTEXT && proportion > 0.0f && proportion < 1.0f;
 }
 
-inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
-
-// The tiles of tr rows of segments off[0 .. n_segs] (off does not decrease, off[n_segs] > off[0]): the uniform form of Segs
-// when every segment has one length, else the table form, built in pinned memory (pd; table_ll long longs) and not yet on
-// the device (vad_table_upload)
-int vad_segs(mfcc_hip_handle *h, const size_t *off, size_t n_segs, int width, size_t tr, mfcc_norm::Segs &s,
-             size_t &table_ll, mfcc_hip_handle::PinnedDesc *&pd) {
-    s = mfcc_norm::Segs{};
-    s.width = width;
-    s.tile_rows = int(tr);
-    s.n_segs = (long long)n_segs;
-    table_ll = 0;
-    pd = nullptr;
-    const size_t len0 = off[1] - off[0];
-    bool uniform = true;
-    for (size_t k = 1; k < n_segs && uniform; ++k) uniform = off[k + 1] - off[k] == len0;
-    if (uniform) {
-        s.base_row = (long long)off[0];
-        s.seg_rows = (long long)len0;
-        s.blocks_per_seg = (long long)((len0 + tr - 1) / tr);
-        s.n_blocks = s.blocks_per_seg * s.n_segs;
-        return MFCC_HIP_SUCCESS;
-    }
-    size_t n_blocks = 0;
-    for (size_t k = 0; k < n_segs; ++k) n_blocks += (off[k + 1] - off[k] + tr - 1) / tr;
-    if (n_segs >= (size_t(1) << 31)) return MFCC_HIP_ERROR_INVALID_PARAM;       // BlockRec::seg is an int
-    table_ll = n_segs + 1 + 2 * n_blocks;
-    const int rc = desc_acquire(h, table_ll, &pd);
-    if (rc) return rc;
-    long long *blk0 = pd->p;
-    auto *rec = reinterpret_cast<mfcc_norm::BlockRec *>(pd->p + n_segs + 1);
-    size_t b = 0;
-    for (size_t k = 0; k < n_segs; ++k) {
-        blk0[k] = (long long)b;
-        for (size_t r = off[k]; r < off[k + 1]; r += tr)
-            rec[b++] = mfcc_norm::BlockRec{(long long)r, int(std::min(tr, off[k + 1] - r)), int(k)};
-    }
-    blk0[n_segs] = (long long)b;
-    s.n_blocks = (long long)n_blocks;
-    return MFCC_HIP_SUCCESS;
-}
-
-int vad_table_upload(mfcc_hip_handle *h, mfcc_norm::Segs &s, size_t table_ll, mfcc_hip_handle::PinnedDesc *pd,
-                     long long *d_table) {
-    if (!pd) return MFCC_HIP_SUCCESS;
-    HIP_TRY(h, hipMemcpyAsync(d_table, pd->p, table_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    s.seg_blk0 = d_table;
-    s.blk = reinterpret_cast<const mfcc_norm::BlockRec *>(d_table + s.n_segs + 1);
-    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
-    pd->in_flight = true;
-    return MFCC_HIP_SUCCESS;
-}
-
 // the tiles of a selection and its scratch in h->d_sel: [tile counts][tile prefixes (n_blocks + 1)][segment offsets
 // (n_segs + 1)][tile table]
 struct SelPlan {
@@ -1013,20 +934,21 @@ struct SelPlan {
 };
 
 int select_plan(mfcc_hip_handle *h, const size_t *off, size_t n_segs, int tile_width, SelPlan &pl) {
-    size_t table_ll = 0;
-    mfcc_hip_handle::PinnedDesc *pd = nullptr;
-    int rc = vad_segs(h, off, n_segs, tile_width, size_t(mfcc_vad::select_tile_rows(tile_width)), pl.s, table_ll, pd);
+    SegPlan sp;
+    int rc = plan_segs(h, off, n_segs, tile_width, mfcc_vad::select_tile_rows(tile_width), sp);
     if (rc) return rc;
-    const size_t nb = size_t(pl.s.n_blocks);
+    const size_t nb = size_t(sp.s.n_blocks);
     const size_t cnt_b = up256(nb * sizeof(unsigned)), toff_b = up256((nb + 1) * sizeof(long long));
     const size_t soff_b = up256((n_segs + 1) * sizeof(long long));
-    if ((rc = ensure(h, &h->d_sel, &h->d_sel_bytes, cnt_b + toff_b + soff_b + table_ll * sizeof(long long) + 64))) return rc;
+    if ((rc = ensure(h, &h->d_sel, &h->d_sel_bytes, cnt_b + toff_b + soff_b + sp.table_ll * sizeof(long long) + 64))) return rc;
     if ((rc = scratch_acquire(h))) return rc;
     char *base = static_cast<char *>(h->d_sel);
     pl.counts = reinterpret_cast<unsigned *>(base);
     pl.tile_off = reinterpret_cast<long long *>(base + cnt_b);
     pl.seg_off = reinterpret_cast<long long *>(base + cnt_b + toff_b);
-    return vad_table_upload(h, pl.s, table_ll, pd, reinterpret_cast<long long *>(base + cnt_b + toff_b + soff_b));
+    rc = plan_upload(h, sp, reinterpret_cast<long long *>(base + cnt_b + toff_b + soff_b));
+    pl.s = sp.s;             // after the upload: the table form points at the device copy
+    return rc;
 }
 
 // the decision on column a.column of rows [..][W], on the tiles of pl (whose counts it fills).  Scratch (h->d_vad):
@@ -1036,26 +958,25 @@ int vad_decide(mfcc_hip_handle *h, const float *d_rows, int W, const size_t *off
     const double *theta = nullptr;
     int rc;
     if (a.scale != 0.0f) {
-        mfcc_norm::Segs sm;
-        size_t table_ll = 0;
-        mfcc_hip_handle::PinnedDesc *pd = nullptr;
-        if ((rc = vad_segs(h, off, n_segs, W, size_t(mfcc_vad::kMeanTileRows), sm, table_ll, pd))) return rc;
+        SegPlan mp;
+        if ((rc = plan_segs(h, off, n_segs, W, mfcc_vad::kMeanTileRows, mp))) return rc;
+        const mfcc_norm::Segs &sm = mp.s;
         const size_t part_b = up256(size_t(sm.n_blocks) * sizeof(mfcc_vad::MeanPart)), theta_b = up256(n_segs * sizeof(double));
-        if ((rc = ensure(h, &h->d_vad, &h->d_vad_bytes, part_b + theta_b + table_ll * sizeof(long long) + 64))) return rc;
+        if ((rc = ensure(h, &h->d_vad, &h->d_vad_bytes, part_b + theta_b + mp.table_ll * sizeof(long long) + 64))) return rc;
         char *base = static_cast<char *>(h->d_vad);
         auto *part = reinterpret_cast<mfcc_vad::MeanPart *>(base);
         double *th = reinterpret_cast<double *>(base + part_b);
-        if ((rc = vad_table_upload(h, sm, table_ll, pd, reinterpret_cast<long long *>(base + part_b + theta_b)))) return rc;
-        hipLaunchKernelGGL(mfcc_vad::vad_mean_kernel, dim3(unsigned(std::min<long long>(sm.n_blocks, 1 << 20))),
+        if ((rc = plan_upload(h, mp, reinterpret_cast<long long *>(base + part_b + theta_b)))) return rc;
+        hipLaunchKernelGGL(mfcc_vad::vad_mean_kernel, dim3(tile_grid(sm.n_blocks)),
                            dim3(mfcc_vad::kThreads), 0, h->stream, d_rows, sm, a.column, part);
-        hipLaunchKernelGGL(mfcc_vad::vad_theta_kernel, dim3(unsigned(std::min<long long>(sm.n_segs, 1 << 20))),
+        hipLaunchKernelGGL(mfcc_vad::vad_theta_kernel, dim3(tile_grid(sm.n_segs)),
                            dim3(mfcc_vad::kThreads), 0, h->stream, sm, static_cast<const mfcc_vad::MeanPart *>(part),
                            double(a.threshold), double(a.scale), th);
         theta = th;
     }
     mfcc_norm::Segs sd = pl.s;
     sd.width = W;
-    hipLaunchKernelGGL(mfcc_vad::vad_decide_kernel, dim3(unsigned(std::min<long long>(sd.n_blocks, 1 << 20))),
+    hipLaunchKernelGGL(mfcc_vad::vad_decide_kernel, dim3(tile_grid(sd.n_blocks)),
                        dim3(mfcc_vad::kThreads), 0, h->stream, d_rows, sd, a.column, theta, double(a.threshold), a.context,
                        a.proportion, d_voiced, pl.counts);
     HIP_TRY(h, hipGetLastError());
@@ -1068,7 +989,7 @@ int select_run(mfcc_hip_handle *h, const float *d_in, int Wp, const unsigned cha
                float *d_out, size_t *out_offsets) {
     mfcc_norm::Segs s = pl.s;
     s.width = Wp;
-    const unsigned grid = unsigned(std::min<long long>(s.n_blocks, 1 << 20));
+    const unsigned grid = tile_grid(s.n_blocks);
     if (!counted)
         hipLaunchKernelGGL(mfcc_vad::vad_count_kernel, dim3(grid), dim3(mfcc_vad::kThreads), 0, h->stream, d_voiced, s,
                            pl.counts);
@@ -1341,7 +1262,7 @@ template <typename OutT>
 int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, size_t nch, OutT *out,
                  size_t cap, size_t *n_frames) {
     if (!h || (!pcm && n * nch)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     const size_t nf = count_frames(h->r, n);
     if (n_frames) *n_frames = nf;
     if (nf == 0 || nch == 0) return MFCC_HIP_SUCCESS;
@@ -1482,7 +1403,7 @@ template <typename OutT>
 int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
                            OutT *d_out, size_t cap, size_t *frame_offsets) {
     if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     const size_t hop = size_t(h->r.hop), flen = size_t(h->r.frame_len), ncep = row_width(h->r);   // elements per row
     DeviceGuard guard(h->device);
     // A corpus of equal-length utterances lying back to back (BASELINE config 5: 10 000 x 10 s) IS a multi-channel
@@ -1540,7 +1461,7 @@ int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm,
     // Float contract on the twelve-wave kernel: no packed copy at all -- per-utterance records, expanded on the device
     // into one record per tile; the kernel reads every utterance where it lies and writes its rows where they belong
     // (kernel_fused512_w12.hpp)
-    if (!fixed && use_fused(h) && h->fused_w12 && std::is_same<OutT, float>::value && rec_fits) {
+    if (!fixed && h->float_kernel == FloatKernel::kFused512W12 && std::is_same<OutT, float>::value && rec_fits) {
         static_assert(sizeof(mfcc_fused12::RaggedChan) == 4 * sizeof(long long), "record layout");
         mfcc_fused12::RaggedChan *rc_host = reinterpret_cast<mfcc_fused12::RaggedChan *>(rec_area);   // 4 long longs each
         long long n_tiles = 0;
@@ -1578,13 +1499,13 @@ int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm,
                 HIP_TRY(h, hipGetLastError());
                 return scratch_release(h);
             }
-            return MFCC_HIP_ERROR_OTHER;               // not launched: cannot happen once fused_w12 is set
+            return MFCC_HIP_ERROR_OTHER;               // not launched: cannot happen with at least one tile
         }
         // more tiles than the tile map's int index: pack and gather below (the pack descriptors are untouched)
     }
     // Fixed contract on the fused kernel: the same -- one record per utterance with frames, the kernel's waves walk
     // consecutive frames and step from one utterance into the next (kernel_fixed512.hpp)
-    if (fixed && h->fixed512_ok && std::is_same<OutT, int16_t>::value && rec_fits) {
+    if (fixed && h->fixed_kernel == FixedKernel::kFixed512 && std::is_same<OutT, int16_t>::value && rec_fits) {
         static_assert(sizeof(mfcc_fixed512::RaggedRec) == 4 * sizeof(long long), "record layout");
         mfcc_fixed512::RaggedRec *rr = reinterpret_cast<mfcc_fixed512::RaggedRec *>(rec_area);
         size_t n_recs = 0;
@@ -1735,7 +1656,7 @@ template <typename OutT>
 int process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const size_t *offsets, size_t n_utt,
                    OutT *out, size_t cap, size_t *frame_offsets) {
     if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     const size_t ncep = fixed ? row_width(h->r) : out_width(h);          // elements per row
     size_t total = 0;
     std::vector<size_t> rel(n_utt + 1, 0);
@@ -2026,7 +1947,7 @@ int mfcc_hip_create_banked(const mfcc_hip_params *p, int frame_length, const mfc
         return fail(MFCC_HIP_ERROR_OTHER);
     rc = build_tables(h);
     if (rc) return fail(rc);
-    if (r.float_impl == MFCC_HIP_IMPL_FUSED512 && !fused512_any(h)) return fail(MFCC_HIP_ERROR_UNSUPPORTED);
+    if (r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel)) return fail(MFCC_HIP_ERROR_UNSUPPORTED);
     *out = h;
     return MFCC_HIP_SUCCESS;
 }
@@ -2339,15 +2260,18 @@ int mfcc_hip_select_dev(mfcc_hip_handle *h, const void *d_in, int row_width, con
 
 const char *mfcc_hip_kernel_name(const mfcc_hip_handle *h, int fixed) {
     if (!h) return "";
-    if (fixed) return h->fixed512_ok ? mfcc_fixed512::kernel_name() : "mfcc_fixed_kernel";
-    // a log-mel handle runs the twelve-wave forms only (build_tables ignores the diagnostic overrides for it): the
-    // names below follow from that
-    if (use_fused160mb(h)) return mfcc_fused160mb::kernel_name();
-    if (use_fused160(h)) return mfcc_fused160::kernel_name();
-    if (use_fused(h)) return h->fused_w12 ? mfcc_fused12::kernel_name() : mfcc_fused::kernel_name();
-    if (h->fused1k_ok && h->r.float_impl == MFCC_HIP_IMPL_AUTO)
-        return !h->f1k_w12 ? mfcc_fused1024::kernel_name()
-                           : h->f1k_is_f32 ? mfcc_fused1024_w12::kernel_name() : mfcc_fused1024_w12bf::kernel_name();
+    if (fixed) return h->fixed_kernel == FixedKernel::kFixed512 ? mfcc_fixed512::kernel_name() : "mfcc_fixed_kernel";
+    switch (h->float_kernel) {
+    case FloatKernel::kFused512W12: return mfcc_fused12::kernel_name();
+    case FloatKernel::kFused512: return mfcc_fused::kernel_name();
+    case FloatKernel::kFused512H160: return mfcc_fused160::kernel_name();
+    case FloatKernel::kFused512H160Mb: return mfcc_fused160mb::kernel_name();
+    case FloatKernel::kFused1024W12Bf: return mfcc_fused1024_w12bf::kernel_name();
+    case FloatKernel::kFused1024W12F32: return mfcc_fused1024_w12::kernel_name();
+    case FloatKernel::kFused1024Bf: return mfcc_fused1024::kernel_name();
+    case FloatKernel::kFused1024F32: return mfcc_fused1024_f32::kernel_name();     // the same string as the bf16 form's
+    case FloatKernel::kGeneric: break;
+    }
     return "mfcc_float_generic_kernel";
 }
 
@@ -2510,7 +2434,7 @@ int mfcc_hip_stream_create(mfcc_hip_handle *h, int fixed, mfcc_hip_stream **out)
     if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // per-call statistics of a stream
     if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;     // deltas need 2 K N frames of lookahead
     if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;        // the threshold's mean is a whole-segment statistic
-    if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     mfcc_hip_stream *s = new (std::nothrow) mfcc_hip_stream();
     if (!s) return MFCC_HIP_ERROR_NO_MEM;
     s->h = h;
@@ -3053,7 +2977,7 @@ int mfcc_hip_bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, mfcc_h
     if (h->destroy_pending || !n_streams) return MFCC_HIP_ERROR_INVALID_PARAM;
     // what mfcc_hip_stream_create refuses: per-call statistics, lookahead and whole-segment thresholds of a stream
     if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (fixed && !h->fixed_ok) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     return bank_create(h, fixed, n_streams, MFCC_HIP_NORMALIZE_NONE, 0, 0, 0, out);
 }
 
@@ -3064,7 +2988,7 @@ int mfcc_hip_bank_create_online(mfcc_hip_handle *h, size_t n_streams, int normal
     if (h->destroy_pending || !n_streams) return MFCC_HIP_ERROR_INVALID_PARAM;
     // the bank's settings are its own: the handle must be a raw one, and able to run the float path
     if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !fused512_any(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (normalize != MFCC_HIP_NORMALIZE_NONE && normalize != MFCC_HIP_NORMALIZE_MEAN && normalize != MFCC_HIP_NORMALIZE_MEAN_VAR)
         return MFCC_HIP_ERROR_INVALID_PARAM;
     if (normalize != MFCC_HIP_NORMALIZE_NONE && (normalize_window < 1 || normalize_window > MFCC_HIP_MAX_NORMALIZE_WINDOW))
