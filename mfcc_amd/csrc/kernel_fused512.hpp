@@ -70,14 +70,12 @@ constexpr int kTFrame = 16 * kTRow + 8;   // 584 words per frame.  Pass 1 stores
 constexpr int kVStride = 18;              // words per frame in the column-16 tile
 constexpr int kAmelBanded = 17;           // mel A operands per wave at 16 kHz: block 0 k2 = 0,1,14,15; block 1 k2 = 2..14
 constexpr int kAmelDense = 32;            // any other band structure: every (k2, block) pair
-// MFCC_MEL_BF16: the mel contraction on v_mfma_f32_16x16x32_bf16 with both operands split in two bf16 terms
-// (W = Wh + Wl, P = Ph + Pl, products Wh Ph + Wh Pl + Wl Ph: 2^-17 relative, fp32 accumulation).  On gfx950 the fp32
-// MFMA is vector-pipe time (tools/alu_probe.hip: an MFMA and k VALU ops of ONE wave take 32 + 4.5 k clocks, and a wave
-// issuing them back to back holds its SIMD partner to one VALU op per MFMA), so 17 of them per wave and tile were 40 %
-// of the kernel's pipe clocks; a K = 32 bf16 MFMA takes 16 clocks on the matrix pipe and covers eight times the bins.
-#ifndef MFCC_MEL_BF16
-#define MFCC_MEL_BF16 1
-#endif
+// The mel contraction runs on v_mfma_f32_16x16x32_bf16 with both operands split in two bf16 terms (W = Wh + Wl,
+// P = Ph + Pl, products Wh Ph + Wh Pl + Wl Ph: 2^-17 relative, fp32 accumulation).  On gfx950 the fp32 MFMA is
+// vector-pipe time (tools/alu_probe.hip: an MFMA and k VALU ops of ONE wave take 32 + 4.5 k clocks, and a wave issuing
+// them back to back holds its SIMD partner to one VALU op per MFMA), so the 17 fp32 MFMAs per wave and tile of the
+// earlier form (FusedTables::a_mel still holds their operands) were 40 % of the kernel's pipe clocks; a K = 32 bf16
+// MFMA takes 16 clocks on the matrix pipe and covers eight times the bins.
 // K slots of the two bf16 MFMAs of a lane: K index 8 g + j  <->  bin(w, g, k2 = kGrp[grp][j])
 constexpr int kGrpK2[2][8] = {{0, 1, 14, 15, 2, 3, 12, 13}, {4, 5, 6, 7, 8, 9, 10, 11}};
 // (filter block, K group) sets of a wave.  BANDED (16 kHz): block 0 only touches k2 in {0, 1, 14, 15} -- group 0
@@ -100,7 +98,6 @@ constexpr int kAextra = 16;               // role operands: role 0 DCT (8 + 8 fo
 constexpr int kFetchers = 192;            // threads that fetch and park the sample window: roles 1..3
 constexpr int kSUsed = 2 * 8 * kFetchers; // 3072 fp32 slots of the window (7 + 15 * 170 + 512 = 3069 are read)
 constexpr int kQWords = kWaves * 2 * 256;  // partial mel sums: [wave][block][lane*4]
-constexpr int kLdsWords = kTile * kTFrame + kTile * kVStride + kQWords + kSUsed;
 // DCX instantiation only (a mel filter with weight on bin 0, see FusedTables::win_dc): the double-precision
 // window rows [16 n2][32 n1] at a row stride of 34 doubles (lane n2 reads 16 bytes at 272 n2 + 16 i: the 16
 // lanes of a ds_read_b128 group cover all 64 banks), and the per-lane partial sums [16 frames][16 n2] at a
@@ -108,6 +105,10 @@ constexpr int kLdsWords = kTile * kTFrame + kTile * kVStride + kQWords + kSUsed;
 constexpr int kWdRow = 34;
 constexpr int kDcRow = 17;
 constexpr int kDcxWords = 2 * (16 * kWdRow + kTile * kDcRow);
+// LDS of a four-wave kernel: T | V | Q (q_words: kQWords, or the bank form's four blocks) | S | the DCX rows
+constexpr int lds_words(int q_words, bool dcx) {
+    return kTile * kTFrame + kTile * kVStride + q_words + kSUsed + (dcx ? kDcxWords : 0);
+}
 
 using mfcc_fc::f32x4;
 using mfcc_fc::i32x4;
@@ -125,8 +126,9 @@ constexpr int kDcDigits = 7;
 struct FusedTables {
     const float *win;     // [16 n2][32 n1]   hamming[16 n1 + n2] / 64 (pre-emphasis x32, real-FFT split x2)
     const float2 *tw;     // [16 n2][16 k1]   W512^(n2 k1)
-    const float *a_mel;   // [4 waves][17][64] mel weights of the bins wave w transforms, in consumption order
-    const uint32_t *a_mel_bf; // [4 waves][sets][hi, lo][4 dwords][64] the same weights as bf16 pairs (MFCC_MEL_BF16)
+    const float *a_mel;   // [4 waves][17][64] mel weights of the bins wave w transforms, in Sched<> order (fp32: no kernel
+                          // reads them any more; they keep their place in the blob and in this kernel argument)
+    const uint32_t *a_mel_bf; // [4 waves][sets][hi, lo][4 dwords][64] the same weights as bf16 pairs
     const float *a_extra; // [4 roles][8][64]  role 0: DCT rows; role 1: column-16 DFT + its mel weights
     const double *win_dc; // [16 n2][32 n1]   hamming[16 n1 + n2] / 32 in double -- or nullptr.  Set when a mel filter has
                           // weight on bin 0 (any sample rate whose first two filter points are both 0: 44.1 kHz, 48 kHz ...).
@@ -192,23 +194,101 @@ inline bool needs_dc_exact(int sample_rate, int n_mel) {
     return false;
 }
 
+// ---- table pieces shared by every four-wave form (this file, kernel_fused512_h160.hpp, kernel_fused512_h160_mb.hpp)
+
+// a window of kNfft samples as the rows [16 n2][32 n1] the kernels read: w[16 n1 + n2] / div
+template <class T>
+inline std::vector<T> window_rows(const std::vector<double> &w, double div) {
+    std::vector<T> rows(16 * 32);
+    for (int n2 = 0; n2 < 16; ++n2)
+        for (int n1 = 0; n1 < 32; ++n1) rows[n2 * 32 + n1] = T(w[16 * n1 + n2] / div);
+    return rows;
+}
+
+// [16 n2][16 k1] W512^(n2 k1) as (cos, sin)
+inline std::vector<float> twiddle_rows() {
+    std::vector<float> tw(16 * 16 * 2);
+    for (int n2 = 0; n2 < 16; ++n2)
+        for (int k1 = 0; k1 < 16; ++k1) {
+            const double a = -2.0 * mfcc_tables::kPi * double(n2 * k1) / 512.0;
+            tw[(n2 * 16 + k1) * 2 + 0] = float(std::cos(a));
+            tw[(n2 * 16 + k1) * 2 + 1] = float(std::sin(a));
+        }
+    return tw;
+}
+
+// role 1 -- column 16: X[16 + 32 k2] = sum_n2 v[n2] W512^(n2 (16 + 32 k2)); MFMA row i = 4g + r:
+// r=0: Re k2=2g, r=1: Im k2=2g, r=2: Re k2=2g+1, r=3: Im k2=2g+1.  e: the role's operands 0..3, [4][64 lanes]
+inline void col16_dft_rows(float *e) {
+    for (int t = 0; t < 4; ++t)
+        for (int l = 0; l < 64; ++l) {
+            const int i = l & 15, n2 = 4 * t + (l >> 4);
+            const int g = i >> 2, r = i & 3, k2 = 2 * g + (r >> 1);
+            const double th = 2.0 * mfcc_tables::kPi * double(n2 * (16 + 32 * k2)) / 512.0;
+            e[t * 64 + l] = float((r & 1) ? -std::sin(th) : std::cos(th));
+        }
+}
+
+inline uint32_t bf16_round(float v) {                                        // round to nearest even, like v_cvt_pk_bf16_f32
+    uint32_t u;
+    std::memcpy(&u, &v, 4);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return u >> 16;
+}
+inline float bf16_val(uint32_t h) {
+    const uint32_t u = h << 16;
+    float v;
+    std::memcpy(&v, &u, 4);
+    return v;
+}
+// a lane's eight K slots as two bf16 terms (w = hi + lo): dword d holds slots (2 d, 2 d + 1), the even one low
+inline void bf16_split8(const float (&w)[8], uint32_t (&vh)[4], uint32_t (&vl)[4]) {
+    uint32_t hi[8], lo[8];
+    for (int j = 0; j < 8; ++j) {
+        hi[j] = bf16_round(w[j]);
+        lo[j] = bf16_round(w[j] - bf16_val(hi[j]));
+    }
+    for (int d = 0; d < 4; ++d) {
+        vh[d] = hi[2 * d] | (hi[2 * d + 1] << 16);
+        vl[d] = lo[2 * d] | (lo[2 * d + 1] << 16);
+    }
+}
+
+// The blob of build_tables, in bytes: the one place its layout is written.  Everything is a multiple of 8 bytes, so the
+// double tables are aligned.
+struct BlobOffsets {
+    size_t win, tw, a_mel, a_extra, a_mel_bf, win_dc, win_dc_lin, a_mel_bf_nodc, w_dc, a_dc_i8, dc_consts, a_dct_bf, total;
+    size_t n_abf;         // dwords of a_mel_bf (and of a_mel_bf_nodc)
+};
+inline BlobOffsets blob_offsets(bool dense) {
+    BlobOffsets o;
+    o.n_abf = size_t(kWaves) * (dense ? SetsBf<true>::N : SetsBf<false>::N) * 2 * 4 * 64;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t off = at; at += bytes; return off; };
+    o.win = take(4 * 16 * 32);
+    o.tw = take(4 * 16 * 16 * 2);
+    o.a_mel = take(4 * size_t(kWaves) * (dense ? kAmelDense : kAmelBanded) * 64);
+    o.a_extra = take(4 * size_t(kWaves) * kAextra * 64);
+    o.a_mel_bf = take(4 * o.n_abf);
+    o.win_dc = take(8 * 16 * 32);
+    o.win_dc_lin = take(8 * 264);
+    o.a_mel_bf_nodc = take(4 * o.n_abf);
+    o.w_dc = take(4 * 32);
+    o.a_dc_i8 = take(4 * 17 * 64 * 4);
+    o.dc_consts = take(8 * 3);
+    o.a_dct_bf = take(4 * 2 * 2 * 256);
+    o.total = at;
+    return o;
+}
+
 template <bool DENSE>
 inline bool build_tables(int sample_rate, double power_scale, double lifter, int n_cep, int n_mel,
                          std::vector<char> &blob) {
     constexpr int kAmel = Sched<DENSE>::N;
     if (n_mel != kMel && !DENSE) return false;
     using namespace mfcc_tables;
-    std::vector<float> win(16 * 32), tw(16 * 16 * 2), amel(size_t(kWaves) * kAmel * 64, 0.0f),
-        aext(size_t(kWaves) * kAextra * 64, 0.0f);
-    std::vector<double> w = hamming_periodic(kNfft);
-    for (int n2 = 0; n2 < 16; ++n2)
-        for (int n1 = 0; n1 < 32; ++n1) win[n2 * 32 + n1] = float(w[16 * n1 + n2] / 64.0);
-    for (int n2 = 0; n2 < 16; ++n2)
-        for (int k1 = 0; k1 < 16; ++k1) {
-            double a = -2.0 * kPi * double(n2 * k1) / 512.0;
-            tw[(n2 * 16 + k1) * 2 + 0] = float(std::cos(a));
-            tw[(n2 * 16 + k1) * 2 + 1] = float(std::sin(a));
-        }
+    std::vector<float> amel(size_t(kWaves) * kAmel * 64, 0.0f), aext(size_t(kWaves) * kAextra * 64, 0.0f);
+    const std::vector<double> w = hamming_periodic(kNfft);
     std::vector<double> md(size_t(kMel) * 257, 0.0);                          // [32][257], rows >= n_mel stay 0
     {
         std::vector<double> m0 = mel_dense(kNfft, n_mel, double(sample_rate));
@@ -241,15 +321,7 @@ inline bool build_tables(int sample_rate, double power_scale, double lifter, int
                     E(0, 8 * half + 4 * blk + r, l) =
                         (coeff < n_cep && filt < n_mel) ? float(dd[size_t(coeff) * n_mel + filt]) : 0.0f;
                 }
-    // role 1 -- column 16: X[16 + 32 k2] = sum_n2 v[n2] W512^(n2 (16 + 32 k2)); MFMA row i = 4g + r:
-    // r=0: Re k2=2g, r=1: Im k2=2g, r=2: Re k2=2g+1, r=3: Im k2=2g+1
-    for (int t = 0; t < 4; ++t)
-        for (int l = 0; l < 64; ++l) {
-            int i = l & 15, n2 = 4 * t + (l >> 4);
-            int g = i >> 2, r = i & 3, k2 = 2 * g + (r >> 1);
-            double th = 2.0 * kPi * double(n2 * (16 + 32 * k2)) / 512.0;
-            E(1, t, l) = float((r & 1) ? -std::sin(th) : std::cos(th));
-        }
+    col16_dft_rows(&E(1, 0, 0));
     // role 1 -- those bins as a K step: lane g supplies bin 16 + 64 g (step 0) / 48 + 64 g (step 1)
     for (int blk = 0; blk < 2; ++blk)
         for (int step = 0; step < 2; ++step)
@@ -261,51 +333,33 @@ inline bool build_tables(int sample_rate, double power_scale, double lifter, int
     for (int f = 0; f < kMel; ++f)
         for (int k = 0; k < 257; ++k)
             if (md[size_t(f) * 257 + k] != 0.0 && !covered[size_t(f) * 257 + k]) return false;
-    auto put = [&](const std::vector<float> &v) {
-        size_t off = blob.size();
-        blob.resize(off + v.size() * 4);
-        std::memcpy(blob.data() + off, v.data(), v.size() * 4);
-    };
     // bf16 split of the same weights for the K = 32 MFMAs: lane l of wave wv, set s, holds rows m = l & 15 of filter
     // block blk[s] at K slots j = 0..7 <-> bin(wv, l >> 4, kGrpK2[grp[s]][j]); dword d = slots (2 d, 2 d + 1)
     constexpr int kSets = SetsBf<DENSE>::N;
-    std::vector<float> abf(size_t(kWaves) * kSets * 2 * 4 * 64, 0.0f);      // uint32 payload, moved as floats
-    std::vector<float> abf_nodc(abf.size(), 0.0f);                           // the same with bin 0's weights taken out
+    std::vector<uint32_t> abf(size_t(kWaves) * kSets * 2 * 4 * 64, 0u);
+    std::vector<uint32_t> abf_nodc(abf.size(), 0u);                          // the same with bin 0's weights taken out
     bool covered_ok = true;
-    auto make_abf = [&](std::vector<float> &dst, bool zero_dc) {
-        auto bf16_round = [](float v) -> uint32_t {                          // round to nearest even, like v_cvt_pk_bf16_f32
-            uint32_t u;
-            std::memcpy(&u, &v, 4);
-            u += 0x7fffu + ((u >> 16) & 1u);
-            return u >> 16;
-        };
-        auto bf16_val = [](uint32_t h) -> float {
-            uint32_t u = h << 16;
-            float v;
-            std::memcpy(&v, &u, 4);
-            return v;
-        };
+    auto make_abf = [&](std::vector<uint32_t> &dst, bool zero_dc) {
         std::vector<char> cov2(size_t(kMel) * 257, 0);
         for (int wv = 0; wv < kWaves; ++wv)
             for (int st = 0; st < kSets; ++st)
                 for (int l = 0; l < 64; ++l) {
-                    uint32_t hi[8], lo[8];
+                    float wgt[8];
                     for (int j = 0; j < 8; ++j) {
                         const int k2 = kGrpK2[SetsBf<DENSE>::grp[st]][j];
                         const int filt = SetsBf<DENSE>::blk[st] * 16 + (l & 15), k1 = 4 * wv + (l >> 4);
-                        float wgt = 0.0f;
+                        wgt[j] = 0.0f;
                         if (!(k1 == 0 && k2 > 8)) {
                             const int bin = k2 < 8 ? k1 + 32 * k2 : 32 * (16 - k2) - k1;
-                            wgt = (zero_dc && bin == 0) ? 0.0f : float(md[size_t(filt) * 257 + bin] * inv);
+                            wgt[j] = (zero_dc && bin == 0) ? 0.0f : float(md[size_t(filt) * 257 + bin] * inv);
                             cov2[size_t(filt) * 257 + bin] = 1;
                         }
-                        hi[j] = bf16_round(wgt);
-                        lo[j] = bf16_round(wgt - bf16_val(hi[j]));
                     }
+                    uint32_t vh[4], vl[4];
+                    bf16_split8(wgt, vh, vl);
                     for (int d = 0; d < 4; ++d) {
-                        const uint32_t vh = hi[2 * d] | (hi[2 * d + 1] << 16), vl = lo[2 * d] | (lo[2 * d + 1] << 16);
-                        std::memcpy(&dst[((size_t(wv) * kSets + st) * 2 + 0) * 256 + d * 64 + l], &vh, 4);
-                        std::memcpy(&dst[((size_t(wv) * kSets + st) * 2 + 1) * 256 + d * 64 + l], &vl, 4);
+                        dst[((size_t(wv) * kSets + st) * 2 + 0) * 256 + d * 64 + l] = vh[d];
+                        dst[((size_t(wv) * kSets + st) * 2 + 1) * 256 + d * 64 + l] = vl[d];
                     }
                 }
         // the sets must cover what the fp32 schedule covers (bins 16 mod 32 come from column 16 either way)
@@ -316,27 +370,15 @@ inline bool build_tables(int sample_rate, double power_scale, double lifter, int
     make_abf(abf, false);
     make_abf(abf_nodc, true);
     if (!covered_ok) return false;
-    blob.clear();
-    put(win); put(tw); put(amel); put(aext); put(abf);
-    // double-precision window rows for the DC bin (8-byte aligned: everything before is a multiple of 8 bytes)
-    std::vector<double> wd(16 * 32);
-    for (int n2 = 0; n2 < 16; ++n2)
-        for (int n1 = 0; n1 < 32; ++n1) wd[n2 * 32 + n1] = w[16 * n1 + n2] / 32.0;
-    size_t off = blob.size();
-    blob.resize(off + wd.size() * 8);
-    std::memcpy(blob.data() + off, wd.data(), wd.size() * 8);
-    // ... and for the twelve-wave form of the DC path: the window in sample order (n = 0 .. 256, padded to 264), the
-    // weights without bin 0, bin 0's weight per filter
+    // the window in sample order for the twelve-wave form of the DC path (n = 0 .. 256, padded to 264), bin 0's weight
+    // per filter
     std::vector<double> wl(264, 0.0);
     for (int n = 0; n <= 256; ++n) wl[n] = w[n] / 32.0;
-    off = blob.size();
-    blob.resize(off + wl.size() * 8);
-    std::memcpy(blob.data() + off, wl.data(), wl.size() * 8);
-    put(abf_nodc);
     std::vector<float> wdc(32, 0.0f);
     for (int f = 0; f < kMel; ++f) wdc[f] = float(md[size_t(f) * 257] * inv);
-    put(wdc);
     // bin 0 on the raw samples: e[n] = 32 x[n] - 31 x[n-1], X[0] = sum_n (w[n] / 32) e[n] = sum_{m=-1}^{511} c[m] x[m]
+    std::vector<uint32_t> adc(size_t(17) * 64 * 4, 0u);
+    double consts[3];
     {
         double c[513], maxc = 0.0;
         for (int m = -1; m <= 511; ++m) {
@@ -347,7 +389,6 @@ inline bool build_tables(int sample_rate, double power_scale, double lifter, int
         int B = 0;
         while (std::ldexp(maxc, B + 1) < 2.7e14) ++B;
         long long sumC = 0;
-        std::vector<uint32_t> adc(size_t(17) * 64 * 4, 0u);
         for (int tau = 0; tau < 513; ++tau) {
             long long C = std::llround(std::ldexp(c[tau], B));
             sumC += C;
@@ -366,78 +407,81 @@ inline bool build_tables(int sample_rate, double power_scale, double lifter, int
             }
             if (C != 0) return false;
         }
-        {
-            size_t o1 = blob.size();
-            blob.resize(o1 + adc.size() * 4);
-            std::memcpy(blob.data() + o1, adc.data(), adc.size() * 4);
-        }
         // 128 sum(C) (the lo bytes are taken as lo - 128), split like the kernel's two partial sums: hi 2^28 + lo
         const long long bias = 128 * sumC, bias_lo = ((bias % (1ll << 28)) + (1ll << 28)) % (1ll << 28);
-        const double consts[3] = {std::ldexp(1.0, -B), double(bias_lo), double((bias - bias_lo) >> 28)};
-        size_t o2 = blob.size();
-        blob.resize(o2 + sizeof(consts));
-        std::memcpy(blob.data() + o2, consts, sizeof(consts));
+        consts[0] = std::ldexp(1.0, -B);
+        consts[1] = double(bias_lo);
+        consts[2] = double((bias - bias_lo) >> 28);
     }
-    {
-        auto bf16_round = [](float v) -> uint32_t {                          // round to nearest even, like v_cvt_pk_bf16_f32
-            uint32_t u;
-            std::memcpy(&u, &v, 4);
-            u += 0x7fffu + ((u >> 16) & 1u);
-            return u >> 16;
-        };
-        auto bf16_val = [](uint32_t h) -> float {
-            uint32_t u = h << 16;
-            float v;
-            std::memcpy(&v, &u, 4);
-            return v;
-        };
-        std::vector<float> adct(size_t(2) * 2 * 256, 0.0f);                  // uint32 payload, moved as floats
-        for (int tile = 0; tile < 2; ++tile)
-            for (int l = 0; l < 64; ++l) {
-                uint32_t hi[8], lo[8];
-                for (int j = 0; j < 8; ++j) {
-                    const int coeff = 16 * tile + (l & 15), q = l >> 4, filt = j < 4 ? 4 * q + j : 16 + 4 * q + (j - 4);
-                    const float w = (coeff < n_cep && filt < n_mel) ? float(dd[size_t(coeff) * n_mel + filt]) : 0.0f;
-                    hi[j] = bf16_round(w);
-                    lo[j] = bf16_round(w - bf16_val(hi[j]));
-                }
-                for (int d = 0; d < 4; ++d) {
-                    const uint32_t vh = hi[2 * d] | (hi[2 * d + 1] << 16), vl = lo[2 * d] | (lo[2 * d + 1] << 16);
-                    std::memcpy(&adct[(size_t(tile) * 2 + 0) * 256 + d * 64 + l], &vh, 4);
-                    std::memcpy(&adct[(size_t(tile) * 2 + 1) * 256 + d * 64 + l], &vl, 4);
-                }
+    // the DCT rows as bf16 pairs (FusedTables::a_dct_bf)
+    std::vector<uint32_t> adct(size_t(2) * 2 * 256, 0u);
+    for (int tile = 0; tile < 2; ++tile)
+        for (int l = 0; l < 64; ++l) {
+            float wgt[8];
+            for (int j = 0; j < 8; ++j) {
+                const int coeff = 16 * tile + (l & 15), q = l >> 4, filt = j < 4 ? 4 * q + j : 16 + 4 * q + (j - 4);
+                wgt[j] = (coeff < n_cep && filt < n_mel) ? float(dd[size_t(coeff) * n_mel + filt]) : 0.0f;
             }
-        put(adct);
-    }
-    return true;
+            uint32_t vh[4], vl[4];
+            bf16_split8(wgt, vh, vl);
+            for (int d = 0; d < 4; ++d) {
+                adct[(size_t(tile) * 2 + 0) * 256 + d * 64 + l] = vh[d];
+                adct[(size_t(tile) * 2 + 1) * 256 + d * 64 + l] = vl[d];
+            }
+        }
+    const BlobOffsets o = blob_offsets(DENSE);
+    blob.assign(o.total, 0);
+    bool fits = true;                                                        // every table fills its slot exactly
+    auto place = [&](size_t off, size_t end, const void *p, size_t bytes) {
+        if (off + bytes == end) std::memcpy(blob.data() + off, p, bytes);
+        else fits = false;
+    };
+    const std::vector<float> win = window_rows<float>(w, 64.0), tw = twiddle_rows();
+    const std::vector<double> wd = window_rows<double>(w, 32.0);             // the DC bin's rows (kernel_fused512.hpp: DCX)
+    place(o.win, o.tw, win.data(), win.size() * 4);
+    place(o.tw, o.a_mel, tw.data(), tw.size() * 4);
+    place(o.a_mel, o.a_extra, amel.data(), amel.size() * 4);
+    place(o.a_extra, o.a_mel_bf, aext.data(), aext.size() * 4);
+    place(o.a_mel_bf, o.win_dc, abf.data(), abf.size() * 4);
+    place(o.win_dc, o.win_dc_lin, wd.data(), wd.size() * 8);
+    place(o.win_dc_lin, o.a_mel_bf_nodc, wl.data(), wl.size() * 8);
+    place(o.a_mel_bf_nodc, o.w_dc, abf_nodc.data(), abf_nodc.size() * 4);
+    place(o.w_dc, o.a_dc_i8, wdc.data(), wdc.size() * 4);
+    place(o.a_dc_i8, o.dc_consts, adc.data(), adc.size() * 4);
+    place(o.dc_consts, o.a_dct_bf, consts, sizeof(consts));
+    place(o.a_dct_bf, o.total, adct.data(), adct.size() * 4);
+    return fits;
 }
 
+// Puts the window of a frame of L samples (L <= kNfft, zero-padded) into a blob made by build_tables: the fp32 rows the
+// kernel keeps in registers and the double rows of the DC path, both [16 n2][32 n1] with zeros from sample L on.
+inline void set_window(std::vector<char> &blob, bool dense, int L) {
+    std::vector<double> w = mfcc_tables::hamming_periodic(L);
+    w.resize(kNfft, 0.0);
+    const std::vector<float> win = window_rows<float>(w, 64.0);
+    const std::vector<double> wd = window_rows<double>(w, 32.0);
+    const BlobOffsets o = blob_offsets(dense);
+    std::memcpy(blob.data() + o.win, win.data(), win.size() * sizeof(float));
+    std::memcpy(blob.data() + o.win_dc, wd.data(), wd.size() * sizeof(double));
+}
+
+// device pointer arithmetic only
 inline void bind_tables(const char *b, int n_cep, int n_mel, bool dense, bool dc_exact, FusedTables &t) {
-    t.n_mel = n_mel;
-    const int kAmel = dense ? kAmelDense : kAmelBanded;
-    // device pointer arithmetic only; layout = build_tables' put() order
+    const BlobOffsets o = blob_offsets(dense);
     t.n_cep = n_cep;
-    const float *f = reinterpret_cast<const float *>(b);
-    t.win = f;                  f += 16 * 32;
-    t.tw = reinterpret_cast<const float2 *>(f); f += 16 * 16 * 2;
-    t.a_mel = f;                f += kWaves * kAmel * 64;
-    t.a_extra = f;              f += kWaves * kAextra * 64;
-    t.a_mel_bf = reinterpret_cast<const uint32_t *>(f);
-    const int n_abf = kWaves * (dense ? SetsBf<true>::N : SetsBf<false>::N) * 2 * 4 * 64;
-    f += n_abf;
-    t.win_dc = dc_exact ? reinterpret_cast<const double *>(f) : nullptr;
-    f += 2 * 16 * 32;
-    t.win_dc_lin = reinterpret_cast<const double *>(f);
-    f += 2 * 264;
-    t.a_mel_bf_nodc = reinterpret_cast<const uint32_t *>(f);
-    f += n_abf;
-    t.w_dc = f;
-    f += 32;
-    t.a_dc_i8 = reinterpret_cast<const uint32_t *>(f);
-    f += 17 * 64 * 4;
-    t.dc_consts = reinterpret_cast<const double *>(f);
-    f += 6;
-    t.a_dct_bf = reinterpret_cast<const uint32_t *>(f);
+    t.n_mel = n_mel;
+    t.win = reinterpret_cast<const float *>(b + o.win);
+    t.tw = reinterpret_cast<const float2 *>(b + o.tw);
+    t.a_mel = reinterpret_cast<const float *>(b + o.a_mel);
+    t.a_extra = reinterpret_cast<const float *>(b + o.a_extra);
+    t.a_mel_bf = reinterpret_cast<const uint32_t *>(b + o.a_mel_bf);
+    t.win_dc = dc_exact ? reinterpret_cast<const double *>(b + o.win_dc) : nullptr;
+    t.win_dc_lin = reinterpret_cast<const double *>(b + o.win_dc_lin);
+    t.a_mel_bf_nodc = reinterpret_cast<const uint32_t *>(b + o.a_mel_bf_nodc);
+    t.w_dc = reinterpret_cast<const float *>(b + o.w_dc);
+    t.a_dc_i8 = reinterpret_cast<const uint32_t *>(b + o.a_dc_i8);
+    t.dc_consts = reinterpret_cast<const double *>(b + o.dc_consts);
+    t.a_dct_bf = reinterpret_cast<const uint32_t *>(b + o.a_dct_bf);
 }
 
 // ---- device
@@ -452,7 +496,8 @@ __device__ __forceinline__ void wave_lds_fence() {
 #define MFCC_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 // Diagnostic build only (-DMFCC_FUSED_STAMPS): per-wave cycle sums of the phases of a tile, written
-// to a buffer of their own that nothing else reads.  No stamp executes in the product build.
+// to a buffer of their own that nothing else reads (tile_loop_w4: both kernels on it).  No stamp executes in the
+// product build.
 #ifdef MFCC_FUSED_STAMPS
 __device__ unsigned long long g_stamps[4 * 12 + 16];   // [wave][12 phases], then [48 + wave]: tile loops
 #define MFCC_STAMP(i)                                                                         \
@@ -475,12 +520,14 @@ __device__ unsigned long long g_stamps[4 * 12 + 16];   // [wave][12 phases], the
 // What is parked in LDS is the pre-emphasised sample e[i] = 32 x[i] - 31 x[i-1] as fp32 (exact:
 // |e| < 2^21) -- computed once per sample here instead of once per (frame, sample) in pass 1, where
 // three overlapping frames would each redo it.  Windows that stick out of the channel (stream start
-// without history, zero-padded tail) are filled sample by sample with the stream's edge rules.
+// without history, zero-padded tail) are filled sample by sample with the stream's edge rules;
+// TILE_HOP, the samples between consecutive tiles, places the tile in the channel there.
 struct Fetch {
     i32x4 v0, v1;
     int p0, p1;          // dword in front of v0 / v1: its high half is the piece's predecessor sample
 };
 
+template <int TILE_HOP>
 __device__ __forceinline__ void fetch_window(const mfcc_k::StreamDesc &s, const Window &w, int u, Fetch &f) {
     if (w.inside) {
         const i32x4 *g = reinterpret_cast<const i32x4 *>(w.ptr - w.shift);
@@ -490,7 +537,7 @@ __device__ __forceinline__ void fetch_window(const mfcc_k::StreamDesc &s, const 
         f.v1 = g[kFetchers + u];
         f.p1 = g32[4 * (kFetchers + u) - 1];
     } else {
-        const long long first = (long long)w.t_in * kTileHop;      // channel-relative
+        const long long first = (long long)w.t_in * TILE_HOP;      // channel-relative
         const int16_t *base = w.ptr - first;
         int h[16];
 #pragma unroll
@@ -553,6 +600,23 @@ __device__ __forceinline__ void dct_store(const mfcc_k::StreamDesc &s, const Fus
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (16 + 4 * q + r < t.n_cep) o[16 + r] = e0[r] + e1[r];
+        }
+    }
+}
+
+// log-mel tail: register r of block b is filter 16 b + 4 q + r of frame lo (mel_log2); lane_off = lo * n_mel + 4 q
+__device__ __forceinline__ void logmel_store(const mfcc_k::StreamDesc &s, const FusedTables &t, const f32x4 &l0,
+                                             const f32x4 &l1, const Cursor &c, int lo, int lane_off,
+                                             float *__restrict__ out) {
+    const long long fr0 = (long long)c.t_in * kTile;
+    const long long rows_left = s.frames_per_ch - fr0;
+    float *o = out + ((long long)c.ch * s.frames_per_ch + fr0) * t.n_mel + lane_off;
+    if (lo < rows_left) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = l0[r];
+        if (t.n_mel > 16) {                    // filters 16..31 (uniform branch)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[16 + r] = l1[r];
         }
     }
 }
@@ -631,59 +695,31 @@ __device__ __forceinline__ void mel_bf_blocks(const f32x4 (&acc)[SetsBf<DENSE>::
     }
 }
 
-// one mel MFMA of the schedule: block 0 accumulates in (x0, y0), block 1 in (x1, y1), alternating
-template <bool DENSE, int I>
-__device__ __forceinline__ void mel_step(const float (&am)[Sched<DENSE>::N], const float (&pw)[16], f32x4 &x0, f32x4 &y0,
-                                         f32x4 &x1, f32x4 &y1) {
-    constexpr int k2 = Sched<DENSE>::k2[I], blk = Sched<DENSE>::blk[I];
-    f32x4 &acc = blk ? ((I & 1) ? y1 : x1) : ((I & 1) ? y0 : x0);
-    acc = MFCC_MFMA(am[I], pw[k2], acc);
-}
-
-template <bool DENSE, int LO, int HI>
-__device__ __forceinline__ void mel_steps(const float (&am)[Sched<DENSE>::N], const float (&pw)[16], f32x4 &x0, f32x4 &y0,
-                                          f32x4 &x1, f32x4 &y1) {
-    if constexpr (LO < HI) {
-        mel_step<DENSE, LO>(am, pw, x0, y0, x1, y1);
-        mel_steps<DENSE, LO + 1, HI>(am, pw, x0, y0, x1, y1);
-    }
-}
-
-// role 0: mel MFMAs with one DCT MFMA (coefficients 0..15 of the previous tile) after every second one
-template <bool DENSE, int I>
-__device__ __forceinline__ void mel_dct_steps(const float (&am)[Sched<DENSE>::N], const float (&pw)[16],
-                                              const float (&ax)[kAextra], const f32x4 &lm0, const f32x4 &lm1, f32x4 &x0,
-                                              f32x4 &y0, f32x4 &x1, f32x4 &y1, f32x4 &d0, f32x4 &d1) {
-    if constexpr (I < Sched<DENSE>::N) {
-        mel_step<DENSE, I>(am, pw, x0, y0, x1, y1);
-        if constexpr ((I & 1) && I / 2 < 8) {
-            constexpr int j = I / 2, r = j >> 1;
-            if constexpr (j & 1) d1 = MFCC_MFMA(ax[4 + r], lm1[r], d1);
-            else d0 = MFCC_MFMA(ax[r], lm0[r], d0);
-        }
-        mel_dct_steps<DENSE, I + 1>(am, pw, ax, lm0, lm1, x0, y0, x1, y1, d0, d1);
-    }
-}
-
-template <bool DENSE, bool DCX>
-__global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void mfcc_fused512_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, float *__restrict__ out) {
-    [[maybe_unused]] constexpr int kAmel = Sched<DENSE>::N;
-    __shared__ __attribute__((aligned(16))) float lds[kLdsWords + (DCX ? kDcxWords : 0)];
+// ---- the tile loop of mfcc_fused512_kernel (HOP = 170, LOGMEL = false) and of mfcc_fused512_h160_kernel (HOP = 160:
+// kernel_fused512_h160.hpp): the header's tile, written once.  HOP: samples between consecutive frames -- the lane's slot
+// in the parked span, the cursor's start, the tile step of the fetch's edge path; LOGMEL: the tail stores the n_mel log2
+// values instead of running the DCT; lds: lds_words(kQWords, DCX) floats.  The arguments are taken by value, as a kernel
+// takes them: with references the compiler allocates other registers and the instantiations' rates move by up to 4 %
+// either way.
+template <int HOP, bool DENSE, bool DCX, bool LOGMEL>
+__device__ __forceinline__ void tile_loop_w4(const mfcc_k::StreamDesc s, const FusedTables t, const LaunchGeom g,
+                                             float *__restrict__ out, float *lds) {
+    constexpr int kTileHopT = kTile * HOP;           // samples between consecutive tiles
+    static_assert(7 + (kTile - 1) * HOP + kNfft <= kSUsed, "a tile's frames must lie inside the parked span");
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int role = wave;             // which extra job the wave has in the MFMA window (see header)
     const int lo = lane & 15;          // n2 in pass 1, k1 in pass 2, frame column in the MFMA phase
     const int q = lane >> 4;           // quarter of the wave; K index g in the MFMA phase
-    // frame of the tile this quarter transforms.  The two quarters of a 32-lane half are 8 frames =
-    // 1360 samples = 16 (mod 32) LDS banks apart, so their ds_read_b32 of the window never collide.
+    // frame of the tile this quarter transforms: the two quarters of a 32-lane half are 8 frames apart (what that
+    // means for the LDS banks of their sample reads depends on HOP: kernel_fused512_h160.hpp)
     const int fr_id = wave + 8 * (q & 1) + 4 * (q >> 1);
 
-    float *const Tt = lds;                                         // [16 frames][548]: [16 n2][34] each
+    float *const Tt = lds;                                         // [16 frames][584]
     float *const Vt = Tt + kTile * kTFrame;                        // [16 frames][18]
     float *const Qt = Vt + kTile * kVStride;                       // [4 waves][2 blocks][256]
-    float *const Sf = Qt + kQWords;                                // pre-emphasised sample window, fp32
+    float *const Sf = Qt + kQWords;                                // pre-emphasised sample span, fp32
     double *const Wd = reinterpret_cast<double *>(Sf + kSUsed);    // DCX: double window rows, [16][kWdRow]
     double *const Dc = Wd + 16 * kWdRow;                           // DCX: partial DC sums, [16 frames][kDcRow]
     if constexpr (DCX) {
@@ -692,14 +728,14 @@ void mfcc_fused512_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, flo
 
     // per-lane constants, resident for the whole kernel
     using mfcc_codelets::v2f;
-    v2f wp[16];                                    // window pairs (w[2m], w[2m+1]) of this lane's samples
+    v2f wp[16];                                    // window pairs (w[2m], w[2m+1]) of this lane's samples (zero from
+                                                   // sample L on in a framed handle)
 #pragma unroll
     for (int i = 0; i < 16; ++i) wp[i] = reinterpret_cast<const v2f *>(t.win)[lo * 16 + i];
     v2f tw[16];                                    // W512^(n2 k1) as (cos, sin)
 #pragma unroll
     for (int i = 0; i < 16; ++i) tw[i] = reinterpret_cast<const v2f *>(t.tw)[lo * 16 + i];
     float ax[kAextra];
-#if MFCC_MEL_BF16
     constexpr int kSets = SetsBf<DENSE>::N;
     u32x4 ah[kSets], al[kSets];
 #pragma unroll
@@ -709,39 +745,34 @@ void mfcc_fused512_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, flo
             ah[st][d] = t.a_mel_bf[((wave * kSets + st) * 2 + 0) * 256 + d * 64 + lane];
             al[st][d] = t.a_mel_bf[((wave * kSets + st) * 2 + 1) * 256 + d * 64 + lane];
         }
-#else
-    float am[kAmel];
-#pragma unroll
-    for (int i = 0; i < kAmel; ++i) am[i] = t.a_mel[(wave * kAmel + i) * 64 + lane];
-#endif
 #pragma unroll
     for (int i = 0; i < kAextra; ++i) ax[i] = t.a_extra[(role * kAextra + i) * 64 + lane];
 
-    // slot of this lane's sample n1 = 0 in the window, before the per-tile alignment shift
-    const int lane_slot = fr_id * kHop + lo;
+    // slot of this lane's sample n1 = 0 in the span, before the per-tile alignment shift
+    const int lane_slot = fr_id * HOP + lo;
     const int fetcher = (role - 1) * 64 + lane;     // 0..191 in roles 1..3
     const bool fetches = role != 0;
-    const int lane_off = lo * t.n_cep + 4 * q;
+    const int lane_off = lo * (LOGMEL ? t.n_mel : t.n_cep) + 4 * q;
 
     Cursor cur;
     cur.ch = (int)(blockIdx.x / (unsigned)g.tiles_per_ch);
     cur.t_in = (int)(blockIdx.x - (unsigned)cur.ch * (unsigned)g.tiles_per_ch);
-    cur.ptr = s.pcm + (long long)cur.ch * s.ch_stride + (long long)cur.t_in * kTileHop;
+    cur.ptr = s.pcm + (long long)cur.ch * s.ch_stride + (long long)cur.t_in * kTileHopT;
 
-    // first tile: fetch and park the sample window
+    // first tile: fetch and park the sample span
     Fetch fx;
     int shift = 0;
     if (cur.ch < g.n_ch) {
         const Window w0 = window_of(cur, g);
         shift = w0.shift;
         if (fetches) {
-            fetch_window(s, w0, fetcher, fx);
+            fetch_window<kTileHopT>(s, w0, fetcher, fx);
             park_window(Sf, fetcher, fx);
         }
     }
     __syncthreads();
 
-    // the role-0 wave finishes tile t (log2, DCT, store) during tile t + 1, so that the other waves
+    // the role-0 wave finishes tile t (log2, DCT or log-mel store) during tile t + 1, so that the other waves
     // never wait for it: it picks the summed mel energies out of Q right after B2 (Q is rewritten only
     // after the next B1) and carries their log2 and the tile's coordinates to its MFMA window
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -755,7 +786,7 @@ void mfcc_fused512_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, flo
 #endif
     while (cur.ch < g.n_ch) {
         // ---------------- pass 1: windowed real FFT-32 over n1 of the pre-emphasised samples
-        mfcc_codelets::v2f ep[16];                 // (e[2m], e[2m+1]) of this lane's samples i = 16 n1 + n2
+        v2f ep[16];                                // (e[2m], e[2m+1]) of this lane's samples i = 16 n1 + n2
         {
             const float *sp = Sf + lane_slot + shift;
 #pragma unroll
@@ -784,19 +815,19 @@ void mfcc_fused512_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, flo
         if (more) {
             const Window wn = window_of(cur, g);
             next_shift = wn.shift;
-            if (fetches) fetch_window(s, wn, fetcher, fx);
+            if (fetches) fetch_window<kTileHopT>(s, wn, fetcher, fx);
         }
         if (role == 0 && have_prev) mel_log2(Qt, lane, t.n_mel, lm0, lm1);
         MFCC_STAMP(6);
 
         // windowed real FFT-32 over n1, twiddled by W512^(n2 k1): columns 0..15 as (re, im) pairs, column 16
-        mfcc_codelets::v2f ty[16];
+        v2f ty[16];
         float y16;
         mfcc_codelets::rfft32_tw(ep, wp, tw, ty, y16);
         MFCC_STAMP(7);
 
-        // transpose through LDS: T[frame][n2][k1]
-        mfcc_codelets::v2f *tcol0 = reinterpret_cast<mfcc_codelets::v2f *>(Tt + fr_id * kTFrame) + lo;
+        // transpose through LDS: T[frame][k1][n2]
+        v2f *tcol0 = reinterpret_cast<v2f *>(Tt + fr_id * kTFrame) + lo;
 #pragma unroll
         for (int k1 = 0; k1 < 16; ++k1) tcol0[k1 * (kTRow / 2)] = ty[k1];
         Vt[fr_id * kVStride + lo] = y16;
@@ -807,16 +838,16 @@ void mfcc_fused512_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, flo
         // ---------------- pass 2: complex FFT-16 over n2 for frame lo, column k1 = 4 wave + q
         float pw[16];                            // |X|^2 at bin(wave, q, k2)
         {
-            mfcc_codelets::v2f x[16];
+            v2f x[16];
             const f32x4 *trow = reinterpret_cast<const f32x4 *>(Tt + lo * kTFrame + (4 * wave + q) * kTRow);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const f32x4 a = trow[i];
-                x[2 * i] = (mfcc_codelets::v2f){a[0], a[1]};
-                x[2 * i + 1] = (mfcc_codelets::v2f){a[2], a[3]};
+                x[2 * i] = (v2f){a[0], a[1]};
+                x[2 * i + 1] = (v2f){a[2], a[3]};
             }
             MFCC_STAMP(1);
-            mfcc_codelets::v2f pp[8];                // (|z[k2]|^2, |z[k2 + 8]|^2): the codelet's last layer is transposed
+            v2f pp[8];                               // (|z[k2]|^2, |z[k2 + 8]|^2): the codelet's last layer is transposed
             mfcc_codelets::cfft16_pow(x, pp);
 #pragma unroll
             for (int k2 = 0; k2 < 8; ++k2) pw[k2] = pp[k2].x, pw[k2 + 8] = pp[k2].y;
@@ -838,26 +869,32 @@ void mfcc_fused512_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, flo
 
         // ---------------- MFMA window (frame column = lo, K index = q)
         f32x4 x0 = zero, y0 = zero, x1 = zero, y1 = zero;
-#if MFCC_MEL_BF16
         PowerBf pb;
         split_power(pw, pb);
         f32x4 acc[kSets];
 #pragma unroll
         for (int st = 0; st < kSets; ++st) acc[st] = zero;
         if (role == 0) {
-            // this tile's mel MFMAs with the previous tile's DCT MFMAs (coefficients 0..15, fp32) in between
-            f32x4 d0 = zero, d1 = zero;
-            mel_bf_all<DENSE, 0>(ah, al, pb, acc, [&](auto i) {
-                constexpr int I = decltype(i)::value;
-                if constexpr (I < 8) {
-                    constexpr int r = I >> 1;
-                    if constexpr (I & 1) d1 = MFCC_MFMA(ax[4 + r], lm1[r], d1);
-                    else d0 = MFCC_MFMA(ax[r], lm0[r], d0);
-                }
-            });
-            mel_bf_blocks<DENSE>(acc, x0, x1);
-            MFCC_STAMP(8);
-            if (have_prev) dct_store(s, t, lm0, lm1, d0, d1, ax, prev, lo, q, lane_off, out);
+            if constexpr (LOGMEL) {
+                mel_bf_all<DENSE, 0>(ah, al, pb, acc, [](auto) {});
+                mel_bf_blocks<DENSE>(acc, x0, x1);
+                MFCC_STAMP(8);
+                if (have_prev) logmel_store(s, t, lm0, lm1, prev, lo, lane_off, out);
+            } else {
+                // this tile's mel MFMAs with the previous tile's DCT MFMAs (coefficients 0..15, fp32) in between
+                f32x4 d0 = zero, d1 = zero;
+                mel_bf_all<DENSE, 0>(ah, al, pb, acc, [&](auto i) {
+                    constexpr int I = decltype(i)::value;
+                    if constexpr (I < 8) {
+                        constexpr int r = I >> 1;
+                        if constexpr (I & 1) d1 = MFCC_MFMA(ax[4 + r], lm1[r], d1);
+                        else d0 = MFCC_MFMA(ax[r], lm0[r], d0);
+                    }
+                });
+                mel_bf_blocks<DENSE>(acc, x0, x1);
+                MFCC_STAMP(8);
+                if (have_prev) dct_store(s, t, lm0, lm1, d0, d1, ax, prev, lo, q, lane_off, out);
+            }
         } else if (role == 1) {
             // column 16 -> bins 16 + 32 j of this tile (a 16 x 16 real DFT matrix on fp32 MFMAs), fed to both filter
             // blocks from registers at the end
@@ -885,46 +922,13 @@ void mfcc_fused512_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, flo
             mel_bf_blocks<DENSE>(acc, x0, x1);
             MFCC_STAMP(8);
         }
-#else
-        if (role == 0) {
-            // this tile's mel MFMAs and the previous tile's DCT MFMAs (coefficients 0..15) in ONE basic block,
-            // interleaved: six independent accumulator chains instead of two long tails (lm = 0 before the
-            // first tile; only the store depends on have_prev)
-            f32x4 d0 = zero, d1 = zero;
-            mel_dct_steps<DENSE, 0>(am, pw, ax, lm0, lm1, x0, y0, x1, y1, d0, d1);
-            MFCC_STAMP(8);
-            if (have_prev) dct_store(s, t, lm0, lm1, d0, d1, ax, prev, lo, q, lane_off, out);
-        } else if (role == 1) {
-            // column 16 -> bins 16 + 32 j of this tile (a 16 x 16 real DFT matrix, two chains of two MFMAs),
-            // fed to both filter blocks from registers at the end; its chain hides among the mel MFMAs
-            const float v0 = Vt[lo * kVStride + 0 + q], v1 = Vt[lo * kVStride + 4 + q];
-            const float v2 = Vt[lo * kVStride + 8 + q], v3 = Vt[lo * kVStride + 12 + q];
-            f32x4 sp = MFCC_MFMA(ax[0], v0, zero);
-            f32x4 sp2 = MFCC_MFMA(ax[1], v1, zero);
-            mel_steps<DENSE, 0, 2>(am, pw, x0, y0, x1, y1);
-            sp = MFCC_MFMA(ax[2], v2, sp);
-            sp2 = MFCC_MFMA(ax[3], v3, sp2);
-            mel_steps<DENSE, 2, kAmel>(am, pw, x0, y0, x1, y1);
-            sp += sp2;
-            const float s0 = fmaf(sp[0], sp[0], sp[1] * sp[1]);      // bin 16 + 64 q
-            const float s1 = fmaf(sp[2], sp[2], sp[3] * sp[3]);      // bin 48 + 64 q
-            x0 = MFCC_MFMA(ax[4], s0, x0);
-            y0 = MFCC_MFMA(ax[5], s1, y0);
-            x1 = MFCC_MFMA(ax[6], s0, x1);
-            y1 = MFCC_MFMA(ax[7], s1, y1);
-            MFCC_STAMP(8);
-        } else {
-            mel_steps<DENSE, 0, kAmel>(am, pw, x0, y0, x1, y1);
-            MFCC_STAMP(8);
-        }
-#endif
         MFCC_STAMP(9);
         *reinterpret_cast<f32x4 *>(Qt + (2 * wave + 0) * 256 + lane * 4) = x0 + y0;
         *reinterpret_cast<f32x4 *>(Qt + (2 * wave + 1) * 256 + lane * 4) = x1 + y1;
         prev = me;
         have_prev = true;
         MFCC_STAMP(10);
-        // park the next tile's sample window (every read of the current one happened before B1)
+        // park the next tile's sample span (every read of the current one happened before B1)
         if (more && fetches) park_window(Sf, fetcher, fx);
         shift = next_shift;
         MFCC_STAMP(4);
@@ -934,13 +938,17 @@ void mfcc_fused512_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, flo
     // the last tile of this workgroup
     if (role == 0 && have_prev) {
         mel_log2(Qt, lane, t.n_mel, lm0, lm1);
-        f32x4 d0 = zero, d1 = zero;
+        if constexpr (LOGMEL) {
+            logmel_store(s, t, lm0, lm1, prev, lo, lane_off, out);
+        } else {
+            f32x4 d0 = zero, d1 = zero;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            d0 = MFCC_MFMA(ax[r], lm0[r], d0);
-            d1 = MFCC_MFMA(ax[4 + r], lm1[r], d1);
+            for (int r = 0; r < 4; ++r) {
+                d0 = MFCC_MFMA(ax[r], lm0[r], d0);
+                d1 = MFCC_MFMA(ax[4 + r], lm1[r], d1);
+            }
+            dct_store(s, t, lm0, lm1, d0, d1, ax, prev, lo, q, lane_off, out);
         }
-        dct_store(s, t, lm0, lm1, d0, d1, ax, prev, lo, q, lane_off, out);
     }
 #ifdef MFCC_FUSED_STAMPS
     if (lane == 0) {
@@ -948,6 +956,13 @@ void mfcc_fused512_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, flo
         atomicAdd(&g_stamps[48 + wave], 1ull);
     }
 #endif
+}
+
+template <bool DENSE, bool DCX>
+__global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void mfcc_fused512_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, float *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float lds[lds_words(kQWords, DCX)];
+    tile_loop_w4<kHop, DENSE, DCX, false>(s, t, g, out, lds);
 }
 
 inline const char *kernel_name() { return "mfcc_fused512_kernel"; }

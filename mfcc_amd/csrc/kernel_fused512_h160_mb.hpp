@@ -1,9 +1,11 @@
 // Fused 512-point float kernel at hop 160 for a mel bank given as a matrix: one to four blocks of 16 filters
 // (1 <= n_mel <= 64), the HTK-style banks of mfcc_hip_create_banked.  DESIGN.md section 4.12.
 //
-// This is kernel_fused512_h160.hpp -- the 16-frame tile, the sample span parked in LDS with the integer pre-emphasis,
-// the edge path through sample_at_i, the windowed real FFT-32 and the complex FFT-16, split_power, the two barriers,
-// the tail one tile behind -- with the mel contraction driven by the handle's matrix instead of a compile-time list:
+// This is the tile loop of kernel_fused512.hpp (tile_loop_w4) at hop 160 -- the 16-frame tile, the sample span parked in LDS with the integer
+// pre-emphasis, the windowed real FFT-32 and the complex FFT-16, split_power, the two barriers, the tail one tile behind
+// -- without the DC path and with the mel contraction driven by the handle's matrix instead of a compile-time list.
+// fetch_window<TILE_HOP>, parking, split_power and the host table helpers are mfcc_fused's; the loop itself is repeated
+// here (DESIGN.md section 4.1 says why), so a change to the passes, the barriers or the parking belongs in both.
 //
 //  sets     the host walks the matrix with the bin <-> (wave, quarter, k2) map of mfcc_fused::build_tables and lists the
 //           (filter block, K group) pairs that carry a non-zero weight (build_tables below; 4 to 6 of the 8 possible for
@@ -20,8 +22,6 @@
 //           to zero before the DCT (their DCT weight is zero too: no -inf * 0) and is not stored by the log-mel tail.
 //  bin 0    a bank with weight on the DC bin is refused by build_tables (an HTK bank with low >= 0 has none): there is
 //           no double-precision DC path here.
-//
-// kernel_fused512.hpp and kernel_fused512_h160.hpp are used through their namespaces and not edited.
 #pragma once
 
 #include "kernel_fused512_h160.hpp"
@@ -34,8 +34,7 @@ constexpr int kMaxBlocks = 4;                              // filter blocks of 1
 constexpr int kMaxPairs = 2 * kMaxBlocks;                  // (block, K group) pairs; pair index = 2 block + group
 constexpr int kMaxCepMb = 16;                              // one M tile of DCT coefficients
 constexpr int kQWordsMb = kWaves * kMaxBlocks * 256;       // partial mel sums: [wave][block][lane * 4]
-constexpr int kLdsWordsMb = kTile * kTFrame + kTile * kVStride + kQWordsMb + kSUsed;
-static_assert(kLdsWordsMb * 4 <= 80 * 1024, "two workgroups per CU");
+static_assert(lds_words(kQWordsMb, false) * 4 <= 80 * 1024, "two workgroups per CU");
 
 // the parameters this kernel covers (the bank itself is checked by build_tables)
 inline bool supported(int nfft, int hop, int frame_len, int n_mel, int n_cep, bool logmel) {
@@ -70,19 +69,10 @@ inline bool build_tables(const std::vector<double> &md, int n_mel, int n_cep, in
     auto W = [&](int filt, int bin) -> float { return filt < n_mel ? float(md[size_t(filt) * 257 + bin] * inv) : 0.0f; };
     auto bin_of = [](int k1, int k2) { return k2 < 8 ? k1 + 32 * k2 : 32 * (16 - k2) - k1; };
 
-    std::vector<float> win(16 * 32), tw(16 * 16 * 2), aext(size_t(kWaves) * kAextra * 64, 0.0f);
-    {
-        std::vector<double> w = hamming_periodic(frame_len);
-        w.resize(kNfft, 0.0);
-        for (int n2 = 0; n2 < 16; ++n2)
-            for (int n1 = 0; n1 < 32; ++n1) win[n2 * 32 + n1] = float(w[16 * n1 + n2] / 64.0);
-    }
-    for (int n2 = 0; n2 < 16; ++n2)
-        for (int k1 = 0; k1 < 16; ++k1) {
-            const double a = -2.0 * kPi * double(n2 * k1) / 512.0;
-            tw[(n2 * 16 + k1) * 2 + 0] = float(std::cos(a));
-            tw[(n2 * 16 + k1) * 2 + 1] = float(std::sin(a));
-        }
+    std::vector<double> w = hamming_periodic(frame_len);
+    w.resize(kNfft, 0.0);
+    const std::vector<float> win = window_rows<float>(w, 64.0), tw = twiddle_rows();
+    std::vector<float> aext(size_t(kWaves) * kAextra * 64, 0.0f);
     // the set list: pair (block, group) is needed when any wave has a non-zero weight in it
     set_mask = 0;
     for (int blk = 0; blk < nb; ++blk)
@@ -105,14 +95,8 @@ inline bool build_tables(const std::vector<double> &md, int n_mel, int n_cep, in
                 const int coeff = l & 15, filt = 16 * blk + 4 * (l >> 4) + r;
                 E(0, 4 * blk + r, l) = (coeff < n_cep && filt < n_mel) ? float(dd[size_t(coeff) * n_mel + filt]) : 0.0f;
             }
-    // role 1 -- column 16, as in mfcc_fused::build_tables: X[16 + 32 k2] = sum_n2 v[n2] W512^(n2 (16 + 32 k2))
-    for (int t = 0; t < 4; ++t)
-        for (int l = 0; l < 64; ++l) {
-            const int i = l & 15, n2 = 4 * t + (l >> 4);
-            const int g = i >> 2, r = i & 3, k2 = 2 * g + (r >> 1);
-            const double th = 2.0 * kPi * double(n2 * (16 + 32 * k2)) / 512.0;
-            E(1, t, l) = float((r & 1) ? -std::sin(th) : std::cos(th));
-        }
+    // role 1 -- column 16 ...
+    col16_dft_rows(&E(1, 0, 0));
     std::vector<char> covered(size_t(16 * kMaxBlocks) * 257, 0);
     // ... and those bins as a K step: lane g supplies bin 16 + 64 g (step 0) / 48 + 64 g (step 1)
     for (int blk = 0; blk < nb; ++blk)
@@ -124,18 +108,6 @@ inline bool build_tables(const std::vector<double> &md, int n_mel, int n_cep, in
             }
     // bf16 split of the listed sets: lane l of wave wv holds row m = l & 15 of the set's filter block at K slots
     // j = 0..7 <-> bin(wv, l >> 4, kGrpK2[grp][j]); dword d = slots (2 d, 2 d + 1); one u32x4 per lane and term
-    auto bf16_round = [](float v) -> uint32_t {                          // round to nearest even, like v_cvt_pk_bf16_f32
-        uint32_t u;
-        std::memcpy(&u, &v, 4);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return u >> 16;
-    };
-    auto bf16_val = [](uint32_t h) -> float {
-        uint32_t u = h << 16;
-        float v;
-        std::memcpy(&v, &u, 4);
-        return v;
-    };
     std::vector<uint32_t> abf(size_t(kWaves) * (n_sets ? n_sets : 1) * 2 * 64 * 4, 0u);
     for (int wv = 0; wv < kWaves; ++wv) {
         int st = 0;
@@ -143,21 +115,19 @@ inline bool build_tables(const std::vector<double> &md, int n_mel, int n_cep, in
             if (!((set_mask >> p) & 1)) continue;
             const int blk = p >> 1, grp = p & 1;
             for (int l = 0; l < 64; ++l) {
-                uint32_t hi[8], lo[8];
+                float wgt[8];
                 for (int j = 0; j < 8; ++j) {
                     const int k2 = kGrpK2[grp][j], filt = blk * 16 + (l & 15), k1 = 4 * wv + (l >> 4);
-                    float wgt = 0.0f;
+                    wgt[j] = 0.0f;
                     if (!(k1 == 0 && k2 > 8)) {
-                        wgt = W(filt, bin_of(k1, k2));
+                        wgt[j] = W(filt, bin_of(k1, k2));
                         covered[size_t(filt) * 257 + bin_of(k1, k2)] = 1;
                     }
-                    hi[j] = bf16_round(wgt);
-                    lo[j] = bf16_round(wgt - bf16_val(hi[j]));
                 }
-                for (int d = 0; d < 4; ++d) {
-                    abf[(((size_t(wv) * n_sets + st) * 2 + 0) * 64 + l) * 4 + d] = hi[2 * d] | (hi[2 * d + 1] << 16);
-                    abf[(((size_t(wv) * n_sets + st) * 2 + 1) * 64 + l) * 4 + d] = lo[2 * d] | (lo[2 * d + 1] << 16);
-                }
+                uint32_t vh[4], vl[4];
+                bf16_split8(wgt, vh, vl);
+                std::memcpy(&abf[(((size_t(wv) * n_sets + st) * 2 + 0) * 64 + l) * 4], vh, sizeof vh);
+                std::memcpy(&abf[(((size_t(wv) * n_sets + st) * 2 + 1) * 64 + l) * 4], vl, sizeof vl);
             }
             ++st;
         }
@@ -274,7 +244,7 @@ __device__ __forceinline__ void mel_sets(const Tables &t, int wave, int lane, co
 template <bool LOGMEL>
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void mfcc_fused512_h160_mb_kernel(mfcc_k::StreamDesc s, Tables t, LaunchGeom g, float *__restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float lds[kLdsWordsMb];
+    __shared__ __attribute__((aligned(16))) float lds[lds_words(kQWordsMb, false)];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -318,7 +288,7 @@ void mfcc_fused512_h160_mb_kernel(mfcc_k::StreamDesc s, Tables t, LaunchGeom g, 
         const Window w0 = window_of(cur, g);
         shift = w0.shift;
         if (fetches) {
-            fetch_window160(s, w0, fetcher, fx);
+            fetch_window<kTileHop160>(s, w0, fetcher, fx);
             park_window(Sf, fetcher, fx);
         }
     }
@@ -346,7 +316,7 @@ void mfcc_fused512_h160_mb_kernel(mfcc_k::StreamDesc s, Tables t, LaunchGeom g, 
         if (more) {
             const Window wn = window_of(cur, g);
             next_shift = wn.shift;
-            if (fetches) fetch_window160(s, wn, fetcher, fx);
+            if (fetches) fetch_window<kTileHop160>(s, wn, fetcher, fx);
         }
         if (role == 0 && have_prev) mel_log2_mb(Qt, lane, q, t.n_blocks, t.n_mel, lm);
 
