@@ -61,15 +61,16 @@ def _frames_source(x, L, hop, pad_mode, halo):
 
 
 def reference_and_bound(pcm, model, L, hop, nfft=512, n_mel=32, sample_rate=16000, power_scale=512.0, n_cep=13,
-                        pad_mode="notebook", halo=0, output="cepstra"):
+                        pad_mode="notebook", halo=0, output="cepstra", lifter=0.0):
     """float64 reference and per-value bound of int16 ``pcm`` (n,) or (channels, n) for the arithmetic ``model`` of
     ``eb.MODELS``.  ``output="logmel"``: the log-mel rows under the log-mel bound of tests/logmel_bound.py, built on
     these stages: the identity as the DCT basis, plus that module's absolute term for the log and its further charge for
-    a bf16 x 2-split mel contraction, whose error a log-mel value sees undiluted (both are explained there)."""
+    a bf16 x 2-split mel contraction, whose error a log-mel value sees undiluted (both are explained there).
+    ``lifter``: the cepstra (not log-mel rows) and their bound times ``1 + (lifter / 2) sin(pi k / lifter)``."""
     pcm = np.asarray(pcm)
     if pcm.ndim == 2:
-        rb = [reference_and_bound(c, model, L, hop, nfft, n_mel, sample_rate, power_scale, n_cep, pad_mode, halo, output)
-              for c in pcm]
+        rb = [reference_and_bound(c, model, L, hop, nfft, n_mel, sample_rate, power_scale, n_cep, pad_mode, halo, output,
+                                  lifter) for c in pcm]
         return np.stack([r for r, _ in rb]), np.stack([b for _, b in rb])
     x, drop = _frames_source(pcm, L, hop, pad_mode, halo)
     cep, st = framed_notebook(x, L, hop, nfft, n_mel, sample_rate, power_scale)
@@ -78,14 +79,14 @@ def reference_and_bound(pcm, model, L, hop, nfft=512, n_mel=32, sample_rate=1600
         st["dct_basis"] = np.eye(n_mel)
         ref, n_cep = st["logmel"], n_mel
     else:
-        ref = cep[drop:, :n_cep]
+        ref = mf.lifter(cep[drop:, :n_cep], lifter) if lifter else cep[drop:, :n_cep]
     if len(ref) == 0:
         return ref, np.zeros_like(ref)
     if output == "logmel":
         with np.errstate(invalid="ignore"):      # inf x 0 of the identity basis: only in rows the bound leaves open
             extra = lb.BF16X2_MEL_EXTRA if eb.MODELS[model][0] == "bf16x2" else 0.0
             return ref, eb.bound_from_stages(st, model, n_cep) + lb.LOG2_ABS + extra
-    return ref, eb.bound_from_stages(st, model, n_cep)
+    return ref, eb.bound_from_stages(st, model, n_cep, lifter)
 
 
 def check(got, ref, bound, what=""):

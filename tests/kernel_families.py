@@ -82,6 +82,25 @@ FIXED = [
 ALL = FLOAT + FIXED
 IDS = [f.id for f in ALL]
 
+# HTK banks at 512 / 160 by the set mask mfcc_fused160mb::build_tables derives from their matrix (bit 2 block + group: the
+# (filter block, K group) pair carries weight; the bank kernel branches on it and indexes its operands by a running
+# count).  id -> (n_mel, fmin, fmax, sample rate, mask).  tests/test_fused512_tables_host.py proves the masks on the CPU,
+# tests/test_gpu_melbank.py runs every one; the banks of the other tests give 3, 13, 45 and 213 only.
+MASK_BANKS = {
+    "m0_1f_bin16": (1, 480, 530, 16000, 0),             # no set at all: all weight on bin 16, through column 16
+    "m1_1f": (1, 3000, 3400, 16000, 1),                 # block 0, group 0 only
+    "m2_2f_high": (2, 6000, 8000, 16000, 2),            # group 1 without group 0
+    "m10_24f_high": (24, 4000, 8000, 16000, 10),        # two blocks, group 1 only
+    "m11_17f_8k": (17, 300, 3400, 8000, 11),            # second block with one filter
+    "m21_40f_telephone": (40, 300, 3400, 16000, 21),    # three blocks, group 0 only
+    "m42_40f_high": (40, 4000, 8000, 16000, 42),        # three blocks, group 1 only
+    "m53_48f": (48, 20, 8000, 16000, 53),               # three full blocks
+    "m170_64f_high": (64, 5000, 8000, 16000, 170),      # four blocks, group 1 only
+    "m181_49f": (49, 20, 8000, 16000, 181),             # fourth block with one filter
+    "m11_17f": (17, 20, 8000, 16000, 11),
+    "m45_33f": (33, 20, 8000, 16000, 45),
+}
+
 
 def open_handle(mfcc_amd, fam: Family, pad_mode="notebook", **over):
     """An ``MFCC`` handle of the family; fails unless the library reports the family's kernel."""

@@ -81,14 +81,15 @@ def matrix(nfft, n_mel, sample_rate, low, high):
 
 
 def reference_and_bound(pcm, model, L, hop, nfft=512, n_mel=32, sample_rate=16000, power_scale=512.0, n_cep=13,
-                        pad_mode="notebook", halo=0, output="cepstra", low=0.0, high=None):
+                        pad_mode="notebook", halo=0, output="cepstra", low=0.0, high=None, lifter=0.0):
     """float64 reference and per-value bound of int16 ``pcm`` (n,) or (channels, n) for the arithmetic ``model`` of
     ``eb.MODELS`` (named by the caller: ``bf16x2/fp32`` for mfcc_fused512_h160_mb_kernel, ``fp32/fp32`` for the generic
-    kernel).  ``output="logmel"``: the log-mel rows under the log-mel bound, as in framed_ref."""
+    kernel).  ``output="logmel"``: the log-mel rows under the log-mel bound, as in framed_ref; ``lifter``: the cepstra
+    times ``1 + (lifter / 2) sin(pi k / lifter)``, as in framed_ref."""
     pcm = np.asarray(pcm)
     if pcm.ndim == 2:
         rb = [reference_and_bound(c, model, L, hop, nfft, n_mel, sample_rate, power_scale, n_cep, pad_mode, halo, output,
-                                  low, high) for c in pcm]
+                                  low, high, lifter) for c in pcm]
         return np.stack([r for r, _ in rb]), np.stack([b for _, b in rb])
     x, drop = fr._frames_source(pcm, L, hop, pad_mode, halo)
     cep, st = banked_notebook(x, matrix(nfft, n_mel, sample_rate, low, high), L, hop, nfft, power_scale)
@@ -97,14 +98,14 @@ def reference_and_bound(pcm, model, L, hop, nfft=512, n_mel=32, sample_rate=1600
         st["dct_basis"] = np.eye(n_mel)
         ref, n_cep = st["logmel"], n_mel
     else:
-        ref = cep[drop:, :n_cep]
+        ref = mf.lifter(cep[drop:, :n_cep], lifter) if lifter else cep[drop:, :n_cep]
     if len(ref) == 0:
         return ref, np.zeros_like(ref)
     if output == "logmel":
         with np.errstate(invalid="ignore"):      # inf x 0 of the identity basis: only in rows the bound leaves open
             extra = lb.BF16X2_MEL_EXTRA if eb.MODELS[model][0] == "bf16x2" else 0.0
             return ref, eb.bound_from_stages(st, model, n_cep) + lb.LOG2_ABS + extra
-    return ref, eb.bound_from_stages(st, model, n_cep)
+    return ref, eb.bound_from_stages(st, model, n_cep, lifter)
 
 
 def check(got, ref, bound, what=""):

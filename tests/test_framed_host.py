@@ -234,3 +234,34 @@ def test_framed_ref_known_answers_on_the_golden_wav(wav_pcm):
     np.testing.assert_allclose(cep[0, :3], [31.91789058, 2.56199734, -1.83419968], rtol=0, atol=1e-6)
     np.testing.assert_allclose(cep[500, :3], [40.52235812, -11.34543673, 0.36045787], rtol=0, atol=1e-6)
     assert st["power"].shape == (1112, 257) and st["mel"].shape == st["logmel"].shape == (1112, 32)
+
+
+@pytest.mark.parametrize("output", ["cepstra", "logmel"])
+def test_the_lifter_argument_of_both_references(wav_pcm, output):
+    """``lifter=0`` is the call without it, which is the stages' own rows and bound; ``lifter=22`` is those rows and that
+    bound times ``1 + 11 sin(pi k / 22)``, and leaves log-mel rows alone (the library's lifter is folded into the DCT)."""
+    import melbank_ref as mr
+    from oracle import error_bound as eb
+    x = wav_pcm[3000:3000 + 20 * 160 + 400].copy()
+    x[1500:2500] = 0                                                    # two all-zero frames: NaN rows of the bound
+    kw = dict(L=400, hop=160, nfft=512, n_mel=32, n_cep=16, output=output)
+    weights = 1.0 + 11.0 * np.sin(np.pi * np.arange(16) / 22.0)
+    for ref_mod, more in ((fr, {}), (mr, dict(low=20.0, high=8000))):
+        plain, bound = ref_mod.reference_and_bound(x, "bf16x2/fp32", **kw, **more)
+        zero, zbound = ref_mod.reference_and_bound(x, "bf16x2/fp32", lifter=0.0, **kw, **more)
+        lift, lbound = ref_mod.reference_and_bound(x, "bf16x2/fp32", lifter=22.0, **kw, **more)
+        assert np.array_equal(zero, plain, equal_nan=True) and np.array_equal(zbound, bound, equal_nan=True)
+        assert np.isnan(bound).all(axis=1).sum() >= 2 and np.isfinite(bound).all(axis=1).sum() >= 10
+        if output == "logmel":
+            assert plain.shape == (21, 32)
+            assert np.array_equal(lift, plain, equal_nan=True) and np.array_equal(lbound, bound, equal_nan=True)
+            continue
+        if ref_mod is fr:
+            cep, st = fr.framed_notebook(x, 400, 160)
+        else:
+            cep, st = mr.banked_notebook(x, mr.matrix(512, 32, 16000, 20.0, 8000), 400, 160)
+        assert np.array_equal(plain, cep[:, :16], equal_nan=True)
+        assert np.array_equal(bound, eb.bound_from_stages(st, "bf16x2/fp32", 16), equal_nan=True)
+        assert np.array_equal(lift, plain * weights, equal_nan=True)
+        assert np.array_equal(lbound, bound * np.abs(weights), equal_nan=True)
+        assert np.array_equal(lift, mf.lifter(plain, 22), equal_nan=True)

@@ -10,6 +10,8 @@ import subprocess
 
 import pytest
 
+import kernel_families as kf
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mfcc_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "fused512_tables.json")
@@ -53,6 +55,24 @@ def test_blobs_are_byte_for_byte_what_they_were(driver):
     assert len(lines) == len(CASES)
     for case, line in zip(CASES, lines):
         assert line == golden[case], case
+
+
+def test_set_masks_of_the_banks_the_gpu_tests_run(driver):
+    """kernel_families.MASK_BANKS, the bank list of tests/test_gpu_melbank.py: every bank is accepted and gives the set
+    mask the list claims, and together they reach the masks the golden cases do not.  Not part of the golden file."""
+    cases = ["mb %d %d %d 400 %g %g 0" % (rate, n_mel, min(13, n_mel), lo, hi)
+             for n_mel, lo, hi, rate, _ in kf.MASK_BANKS.values()]
+    lines = subprocess.run([driver], input="\n".join(cases) + "\n", capture_output=True, text=True,
+                           check=True).stdout.splitlines()
+    assert len(lines) == len(cases)
+    for (name, bank), line in zip(kf.MASK_BANKS.items(), lines):
+        ok, _, _, mask = line.split()
+        assert ok == "1" and int(mask) == bank[4], (name, line)
+        n_mel = bank[0]
+        assert bank[4] < 1 << (2 * ((n_mel + 15) // 16)), name                          # pairs of the blocks present only
+    golden = json.load(open(GOLDEN))
+    seen = {int(golden[c].split()[3]) for c in BANK}
+    assert {b[4] for b in kf.MASK_BANKS.values()} - seen == {0, 1, 2, 10, 11, 21, 42, 53, 170, 181}
 
 
 def test_the_cases_cover_what_they_claim():

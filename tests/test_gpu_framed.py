@@ -3,7 +3,10 @@ kernel and the generic kernel against the float64 reference of tests/framed_ref.
 oracle/error_bound.py; tile and buffer edges of the new kernel; every float entry point against the dense device call
 of the same handle, bit for bit; the post-passes; the fixed path's refusals; plain handles unchanged.
 
-Small shapes only: 48 frames per channel for the reference checks, at most a few tiles elsewhere."""
+The range the fused kernel accepts beyond 400 / 13 -- frame lengths 160 .. 511, 1 .. 32 cepstra, the lifter -- is
+computed at its ends, not only selected.  The steady state of the tile loop is tests/test_gpu_steady_state.py's.
+
+Small shapes only: 37 to 48 frames per channel for the reference checks, at most a few tiles elsewhere."""
 import numpy as np
 import pytest
 
@@ -65,7 +68,7 @@ def _ref_kw(kw):
     ps = kw.get("power_scale", 512.0)
     return dict(L=kw["win_length"], hop=kw["hop"], nfft=kw["nfft"], n_mel=kw["nfilters"],
                 sample_rate=int(kw.get("samplerate", 16000)), power_scale=float(ps) if ps else float(kw["nfft"]),
-                n_cep=kw["nceptrums"])
+                n_cep=kw["nceptrums"], lifter=float(kw.get("lifter", 0.0)))
 
 
 def _check(got, pcm, kw, kernel, pad="notebook", halo=0, what="", output="cepstra", all_bounded=False):
@@ -167,6 +170,68 @@ def test_a_frame_does_not_depend_on_its_tile(mfcc_amd, wav_pcm):
         for k in (1, 5, 15, 16, 17):
             b = as_np(m.process(_dev(np.concatenate([pre[:k * hop], x]))))
             assert same(a[1:], b[k + 1:]), k
+
+
+# ------------------------------------------------------------------------------------------------ the accepted range
+
+LENGTHS = [160, 161, 255, 511]                     # the ends of mfcc_fused160::supported, one off, and an odd middle
+
+
+@pytest.mark.parametrize("pad", ["notebook", "stream"])
+@pytest.mark.parametrize("L", LENGTHS)
+def test_frame_lengths_of_the_accepted_range(mfcc_amd, wav_pcm, L, pad):
+    """The six kinds at 37 frames, every coefficient of every frame bounded; then 1, 16 and 17 frames in a tensor that
+    ends with the last channel's last sample, so slots L .. 511 of the last frame lie past the end of the buffer (352
+    samples at L = 160)."""
+    kw = dict(ASR, win_length=L)
+    with _open(mfcc_amd, kw, NEW, pad_mode=pad) as m:
+        assert m.win_length == L
+        worst = 0.0
+        for nfr in (37, 1, 16, 17):
+            n = _length(nfr, pad, L)
+            assert m.num_frames(n) == nfr
+            pcm = kf.channels(n, 7, wav_pcm)
+            got = m.process(_dev(pcm))                                   # contiguous: nothing behind the last sample
+            assert tuple(got.shape) == (len(kf.KINDS), nfr, 13)
+            worst = max(worst, _check(got, pcm, kw, NEW, pad, what="L %d, %s, %d frames" % (L, pad, nfr),
+                                      all_bounded=True))
+    print("L %d, %s: worst error / bound %.3f" % (L, pad, worst))
+
+
+@pytest.mark.parametrize("n_cep,lifter", [(1, 0.0), (16, 0.0), (17, 0.0), (32, 0.0), (13, 22.0), (32, 22.0)])
+def test_cepstra_counts_and_the_lifter(mfcc_amd, wav_pcm, n_cep, lifter):
+    kw = dict(ASR, nceptrums=n_cep, lifter=lifter)
+    n = _length(37, "notebook")
+    pcm = kf.channels(n, 7, wav_pcm)
+    with _open(mfcc_amd, kw, NEW) as m:
+        got = m.process(_dev(pcm))
+        assert tuple(got.shape) == (len(kf.KINDS), 37, n_cep)
+        worst = _check(got, pcm, kw, NEW, what="%d cepstra, lifter %g" % (n_cep, lifter), all_bounded=True)
+    print("%d cepstra, lifter %g: worst error / bound %.3f" % (n_cep, lifter, worst))
+
+
+@pytest.mark.parametrize("pad", ["notebook", "stream"])
+@pytest.mark.parametrize("L", [160, 511])
+def test_sessions_and_banks_at_the_ends_of_the_frame_lengths(mfcc_amd, wav_pcm, L, pad):
+    """A session fed in uneven chunks and flushed, and a raw bank of 4, equal the dense call bit for bit.  L = hop: a
+    line never holds a whole hop of history behind the frames it has produced."""
+    kw = dict(ASR, win_length=L)
+    n = 36 * 160 + L + 7
+    pcm = kf.channels(n, 11, wav_pcm, kinds=("speech", "noise", "silences", "uniform"))
+    with _open(mfcc_amd, kw, NEW, pad_mode=pad) as m:
+        R = as_np(m.process(_dev(pcm)))
+        assert R.shape == (4, m.num_frames(n), 13)
+        _check(R, pcm, kw, NEW, pad, what="L %d, %s" % (L, pad))
+        with m.stream() as s:
+            rows = [s.push(c) for c in _chunks(pcm[0], (1, 159, 160, 161, 1000))]
+            assert s.pending < L
+            rows.append(s.flush())
+            assert same(np.concatenate(rows), R[0]), (L, pad, "session")
+        sizes = [(1, 159, 160, 161, 1000), (0, 700, 0, 33), (2048,), (399, 0, 1, 160)]
+        with m.stream_bank(4) as b:
+            rows = _feed(b, pcm, sizes, L)
+            for u in range(4):
+                assert same(rows[u], R[u]), (L, pad, "bank", u)
 
 
 # ------------------------------------------------------------------------------------------------ entry points

@@ -2,8 +2,10 @@
 mfcc_fused512_h160_kernel (both tile_loop_w4 of kernel_fused512.hpp) and the two of mfcc_fused512_h160_mb_kernel (its
 own copy of that loop), so a change made to one copy and not to the other shows here.
 
-Shape: 2 channels of 37 frames at an odd channel stride -- three 16-frame tiles per channel, the last one partial, so a
-workgroup's loop has a first tile, a middle tile with a previous tile to finish, and the epilogue.
+Shape: 2 channels of 37 frames at an odd channel stride -- three 16-frame tiles per channel, the last one partial.  The
+six tiles go to six workgroups: each runs one tile (an edge-path one, an aligned one, a partial one) and the epilogue
+behind the loop.  The steady state of the loop -- a previous tile to finish, a next one to fetch -- needs more tiles than
+the launch has workgroups: tests/test_gpu_steady_state.py runs every instantiation listed here that way.
 
 Sample rates (mfcc_fused::needs_dc_exact and the banded test of mfcc_fused::build_tables):
   16000  the banded set list                                    <DENSE, DCX> = <false, false>
