@@ -25,50 +25,29 @@
 //    j' = 0..7, role 2: j' = 8..15; 8 MFMAs + their mel MFMAs each); role 0 finishes the previous tile (log2, DCT-II as 12
 //    fp32 MFMAs per 16 coefficients, store) and neither fetches nor parks samples.
 //
-// This form serves every sample rate and coefficient count.  Since the second half of round 3 this file is (a) the tables, set
-// lists and helpers of the kernel that runs -- the TWELVE-wave staging of this contraction, kernel_fused1024_w12.hpp
+// This form serves every sample rate and coefficient count.  Since the second half of round 3 this file is (a) the set
+// lists and the tables of the kernel that runs -- the TWELVE-wave staging of this contraction, kernel_fused1024_w12.hpp
 // (mfcc_fused1024_w12bf_kernel: 1.00 ms against 1.36 for the kernel below on config 4's shape) -- and (b) the eight-wave
-// LOCKSTEP staging below, an A/B form (MFCC_HIP_FUSED1024=bf16).  What else was built and measured in round 3 and dropped
-// (DESIGN.md 4.2): 8-frame tiles in two 4-wave workgroups per CU (every per-tile cost twice, MFMAs half empty: 260 vector
-// instructions per frame against 195, 9-13 % slower), and producer / consumer waves on the 16-frame tile (pass 1 of tile k + 1
-// in registers beside pass 2 of tile k: the stores of T behind the barrier are an LDS-bound interval nothing overlaps, 12 %
-// slower).
+// LOCKSTEP staging below, an A/B form (MFCC_HIP_FUSED1024=bf16).  The geometry, the bin map, the host code of the tables
+// that do not depend on the contraction and the device helpers (fetch / park, mel_log2, dct_store, split_bf16_pair) are
+// shared with the fp32 form: fused1024_common.hpp.  The lockstep loop itself exists twice, here and in
+// kernel_fused1024_f32.hpp (DESIGN.md 4.2 says why): a change to the passes, the barriers or the parking belongs in both.
+// What else was built and measured in round 3 and dropped: 8-frame tiles in two 4-wave workgroups per CU
+// (every per-tile cost twice, MFMAs half empty: 260 vector instructions per frame against 195, 9-13 % slower), and
+// producer / consumer waves on the 16-frame tile (pass 1 of tile k + 1 in registers beside pass 2 of tile k: the stores of
+// T behind the barrier are an LDS-bound interval nothing overlaps, 12 % slower).
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <cmath>
-#include <cstring>
-#include <vector>
-
-#include "codelets_gen.hpp"
-#include "fused_common.hpp"
-#include "kernels_generic.hpp"
-#include "tables.hpp"
+#include "fused1024_common.hpp"
 
 namespace mfcc_fused1024 {
 
-constexpr int kNfft = 1024, kHop = 341, kMel = 40, kMaxCep = 40;
-constexpr int kTile = 16, kWaves = 8;
-constexpr int kTileHop = kTile * kHop;            // 5456 samples between consecutive tiles
-constexpr int kTRow = 64;                         // words per k1 row of the transpose tile T[frame][k1][n2]: 32 complex
-constexpr int kTFrame = 16 * kTRow + 4;           // 1028 words per frame: (row, frame) strides of (16, 257) 16-byte units make
-                                                  // every ds_read_b128 of pass 2 conflict free (brute-forced over the lane groups)
-constexpr int kVStride = 34;                      // words per frame in the column-16 tile
-constexpr int kBlocks = 3;                        // 16-filter blocks of the 40 filters
-constexpr int kQWords = kWaves * kBlocks * 256;   // partial mel sums: [wave][block][lane * 4]
-constexpr int kFetchers = 64 * (kWaves - 1);      // roles 1..7 fetch and park the sample window
-constexpr int kPieces = (7 + (kTile - 1) * kHop + kNfft + 7) / 8;       // 769 pieces of 8 samples are read
-constexpr int kSecond = kPieces - kFetchers;      // fetchers that take a second piece (321)
-constexpr int kSUsed = 8 * kPieces;               // 6152 fp32 slots
+using namespace mfcc_f1k;
+
 constexpr int kTwRow = 36;                        // words per n2 row of the twiddle table in LDS (9 16-byte units: the
                                                   // 16 lanes of a ds_read_b128 group hit 16 different units mod 16)
 constexpr int kLdsWords = kTile * kTFrame + kTile * kVStride + kQWords + kSUsed + 32 * kTwRow;
 constexpr int kAextra = 14;                       // role operands: DCT rows (12) / column-16 DFT (8) + its mel weights (6)
-
-// K slots of the two bf16 MFMAs of a lane: K index 8 q + i  <->  output m = kGrpM[grp][i] of lane group q
-constexpr int kGrpM[2][8] = {{0, 1, 2, 3, 12, 13, 14, 15}, {4, 5, 6, 7, 8, 9, 10, 11}};
 
 // (K group, filter block) sets of a variant; c16[mb][blk]: the filter blocks that column 16's bins 16 + 32 j' reach,
 // j' < 8 (mb = 0, bins 16..240) / j' >= 8 (mb = 1, bins 272..496).  build_tables picks the first variant that covers the
@@ -101,19 +80,6 @@ inline SetsView sets_view(int v) {
     return {Sets<0>::N, Sets<0>::grp, Sets<0>::blk, Sets<0>::c16};
 }
 
-using mfcc_fc::f32x4;
-using mfcc_fc::i32x4;
-using mfcc_fc::Cursor;
-using mfcc_fc::LaunchGeom;
-using mfcc_fc::Window;
-using mfcc_fc::advance;
-using mfcc_fc::window_of;
-using mfcc_fc::preemph8;
-using mfcc_fc::lds_barrier;
-using mfcc_codelets::v2f;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 struct Tables {
     int variant;           // which Sets<VAR> the operand tables were laid out for
     const float *win;      // [32 n2][32 n1]  hamming[32 n1 + n2] / 64
@@ -127,32 +93,11 @@ struct Tables {
     int n_cep;
 };
 
-inline bool supported(int nfft, int hop, int n_mel, int n_cep) {
-    return nfft == kNfft && hop == kHop && n_mel == kMel && n_cep >= 1 && n_cep <= kMaxCep;
-}
-
-// bin of output m of the (k1, h) lane; -1: a duplicate that another lane supplies
-inline int bin_of(int k1, int h, int m) {
-    const int k2 = 2 * m + h;
-    if (k2 < 16) return k1 + 32 * k2;
-    if (k1 == 0 && k2 > 16) return -1;
-    return 32 * (32 - k2) - k1;
-}
-
 inline bool build_tables_for(int variant, int sample_rate, double power_scale, double lifter, int n_cep,
                              std::vector<char> &blob) {
     using namespace mfcc_tables;
     const SetsView sv = sets_view(variant);
-    std::vector<float> win(32 * 32), tw(32 * 16 * 2), aext(size_t(3) * kAextra * 64, 0.0f), adct(size_t(2) * 12 * 64, 0.0f);
-    std::vector<double> w = hamming_periodic(kNfft);
-    for (int n2 = 0; n2 < 32; ++n2)
-        for (int n1 = 0; n1 < 32; ++n1) win[n2 * 32 + n1] = float(w[32 * n1 + n2] / 64.0);
-    for (int n2 = 0; n2 < 32; ++n2)
-        for (int k1 = 0; k1 < 16; ++k1) {
-            double a = -2.0 * kPi * double(n2 * k1) / 1024.0;
-            tw[(n2 * 16 + k1) * 2 + 0] = float(std::cos(a));
-            tw[(n2 * 16 + k1) * 2 + 1] = float(std::sin(a));
-        }
+    std::vector<float> aext(size_t(3) * kAextra * 64, 0.0f), adct(size_t(2) * 12 * 64, 0.0f);
     const int nb = kNfft / 2 + 1;                                             // 513
     std::vector<double> md = mel_dense(kNfft, kMel, double(sample_rate));     // [40][513]
     for (int f = 0; f < kMel; ++f)
@@ -161,66 +106,40 @@ inline bool build_tables_for(int variant, int sample_rate, double power_scale, d
     const double inv = 1.0 / (power_scale * power_scale);
     std::vector<char> covered(size_t(kMel) * nb, 0);
     auto Wt = [&](int filt, int bin) -> double { return filt < kMel ? md[size_t(filt) * nb + bin] * inv : 0.0; };
-    auto bf16_round = [](float v) -> uint32_t {                              // round to nearest even, like v_cvt_pk_bf16_f32
-        uint32_t u;
-        std::memcpy(&u, &v, 4);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return u >> 16;
-    };
-    auto bf16_val = [](uint32_t h) -> float {
-        uint32_t u = h << 16;
-        float v;
-        std::memcpy(&v, &u, 4);
-        return v;
-    };
     // mel operands: lane l of wave wv, set st holds rows l & 15 of filter block blk[st] at K slots i = 0..7
     // <-> bin(k1 = 4 (wv >> 1) + (l >> 4), h = wv & 1, m = kGrpM[grp[st]][i]); dword d = slots (2 d, 2 d + 1)
     std::vector<uint32_t> abf(size_t(kWaves) * sv.n * 2 * 4 * 64, 0u);
     for (int wv = 0; wv < kWaves; ++wv)
         for (int st = 0; st < sv.n; ++st)
             for (int l = 0; l < 64; ++l) {
-                uint32_t hi[8], lo[8];
+                float wgt[8];
                 for (int i = 0; i < 8; ++i) {
                     const int filt = sv.blk[st] * 16 + (l & 15), k1 = 4 * (wv >> 1) + (l >> 4);
                     const int bin = bin_of(k1, wv & 1, kGrpM[sv.grp[st]][i]);
-                    float wgt = 0.0f;
+                    wgt[i] = 0.0f;
                     if (bin >= 0 && filt < kMel) {
-                        wgt = float(Wt(filt, bin));
+                        wgt[i] = float(Wt(filt, bin));
                         covered[size_t(filt) * nb + bin] = 1;
                     }
-                    hi[i] = bf16_round(wgt);
-                    lo[i] = bf16_round(wgt - bf16_val(hi[i]));
                 }
+                uint32_t vh[4], vl[4];
+                mfcc_fused::bf16_split8(wgt, vh, vl);
                 const size_t base = (size_t(wv) * sv.n + st) * 2 * 256;
                 for (int d = 0; d < 4; ++d) {
-                    abf[base + 0 * 256 + d * 64 + l] = hi[2 * d] | (hi[2 * d + 1] << 16);
-                    abf[base + 1 * 256 + d * 64 + l] = lo[2 * d] | (lo[2 * d + 1] << 16);
+                    abf[base + 0 * 256 + d * 64 + l] = vh[d];
+                    abf[base + 1 * 256 + d * 64 + l] = vl[d];
                 }
             }
     auto E = [&](int role, int idx, int lane) -> float & { return aext[(size_t(role) * kAextra + idx) * 64 + lane]; };
-    // role 0 -- DCT rows: lane (coeff = l & 15, g = l >> 4) holds D[16 tile + coeff][16 blk + 4 g + r]
+    // role 0 -- DCT rows of coefficients 0..15; 16..31 and 32..47 in a table of their own
     std::vector<double> dd = dct_rows(n_cep, kMel, lifter);                   // [n_cep][40]
-    for (int tile = 0; tile < 3; ++tile)
-        for (int blk = 0; blk < kBlocks; ++blk)
-            for (int r = 0; r < 4; ++r)
-                for (int l = 0; l < 64; ++l) {
-                    const int coeff = 16 * tile + (l & 15), filt = 16 * blk + 4 * (l >> 4) + r;
-                    const float v = (coeff < n_cep && filt < kMel) ? float(dd[size_t(coeff) * kMel + filt]) : 0.0f;
-                    if (tile == 0) E(0, 4 * blk + r, l) = v;
-                    else adct[(size_t(tile - 1) * 12 + 4 * blk + r) * 64 + l] = v;
-                }
-    // roles 1, 2 -- column 16: X[16 + 32 j'] = sum_n2 v[n2] W1024^(n2 (16 + 32 j')), j' = 8 (role - 1) + 0..7; MFMA row
-    // i = 4 g + r holds r = 0: Re j' = jb + 2 g, r = 1: Im (same j'), r = 2: Re j' + 1, r = 3: Im; K step t covers n2 = 4 t + (l >> 4)
+    dct_tile_rows(dd, n_cep, 0, &E(0, 0, 0));
+    for (int tile = 1; tile < 3; ++tile) dct_tile_rows(dd, n_cep, tile, &adct[size_t(tile - 1) * 12 * 64]);
+    // roles 1, 2 -- column 16's DFT rows, then its bins as K steps of fp32 MFMAs: lane group q supplies bin
+    // 16 + 32 (8 mb + 2 q + step) to block blk
     for (int role = 1; role <= 2; ++role) {
         const int mb = role - 1;
-        for (int t = 0; t < 8; ++t)
-            for (int l = 0; l < 64; ++l) {
-                const int i = l & 15, n2 = 4 * t + (l >> 4);
-                const int g = i >> 2, r = i & 3, jp = 8 * mb + 2 * g + (r >> 1);
-                const double th = 2.0 * kPi * double(n2 * (16 + 32 * jp)) / 1024.0;
-                E(role, t, l) = float((r & 1) ? -std::sin(th) : std::cos(th));
-            }
-        // its bins as K steps of fp32 MFMAs: lane group q supplies bin 16 + 32 (8 mb + 2 q + step) to block blk
+        col16_dft_rows(mb, &E(role, 0, 0));
         for (int blk = 0; blk < kBlocks; ++blk)
             for (int step = 0; step < 2; ++step)
                 for (int l = 0; l < 64; ++l) {
@@ -233,22 +152,17 @@ inline bool build_tables_for(int variant, int sample_rate, double power_scale, d
     for (int f = 0; f < kMel; ++f)
         for (int k = 0; k < nb; ++k)
             if (md[size_t(f) * nb + k] != 0.0 && !covered[size_t(f) * nb + k]) return false;
-    auto put = [&](const void *p, size_t bytes) {
-        size_t off = blob.size();
-        blob.resize(off + bytes);
-        std::memcpy(blob.data() + off, p, bytes);
-    };
-    blob.clear();
-    put(win.data(), win.size() * 4);
-    put(tw.data(), tw.size() * 4);
-    put(aext.data(), aext.size() * 4);
-    put(adct.data(), adct.size() * 4);
-    put(abf.data(), abf.size() * 4);
-    std::vector<uint32_t> abf4(abf.size());
+    std::vector<uint32_t> abf4(abf.size());                                   // the twelve-wave form's layout
     for (size_t op = 0; op < abf.size() / 256; ++op)
         for (int d = 0; d < 4; ++d)
             for (int l = 0; l < 64; ++l) abf4[op * 256 + l * 4 + d] = abf[op * 256 + d * 64 + l];
-    put(abf4.data(), abf4.size() * 4);
+    blob.clear();
+    put(blob, window_rows());
+    put(blob, twiddle_rows());
+    put(blob, aext);
+    put(blob, adct);
+    put(blob, abf);
+    put(blob, abf4);
     return true;
 }
 
@@ -271,103 +185,7 @@ inline void bind_tables(const char *b, int n_cep, int variant, Tables &t) {
     t.a_bf4 = t.a_bf + (size_t)kWaves * sets_view(variant).n * 2 * 256;
 }
 
-// ---- device (helpers shared in spirit with kernel_fused512.hpp; kept local so the two kernels stay independent)
-
-#define MFCC1K_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-#define MFCC1K_MFMA_BF(a, b, c) \
-    __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, (a)), __builtin_bit_cast(bf16x8, (b)), (c), 0, 0, 0)
-
-struct Fetch {
-    i32x4 v0, v1;
-    int p0, p1;
-};
-
-// fetcher u (0..447) takes pieces u and 448 + u (< 769) of the window, plus the dword in front of each
-__device__ __forceinline__ void fetch_window(const mfcc_k::StreamDesc &s, const Window &w, int u, Fetch &f) {
-    if (w.inside) {
-        const i32x4 *g = reinterpret_cast<const i32x4 *>(w.ptr - w.shift);
-        const int *g32 = reinterpret_cast<const int *>(g);
-        f.v0 = g[u];
-        f.p0 = g32[4 * u - 1];
-        f.v1 = (i32x4){0, 0, 0, 0};
-        f.p1 = 0;
-        if (u < kSecond) {
-            f.v1 = g[kFetchers + u];
-            f.p1 = g32[4 * (kFetchers + u) - 1];
-        }
-    } else {
-        const long long first = (long long)w.t_in * kTileHop;
-        const int16_t *base = w.ptr - first;
-        int h[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const long long i = first + (k < 8 ? 0 : 8 * kFetchers) + 8 * u + (k & 7);
-            h[k] = mfcc_k::sample_at_i(s, base, i) & 0xFFFF;
-        }
-        f.v0 = (i32x4){h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
-        f.v1 = (i32x4){h[8] | (h[9] << 16), h[10] | (h[11] << 16), h[12] | (h[13] << 16), h[14] | (h[15] << 16)};
-        f.p0 = mfcc_k::sample_at_i(s, base, first + 8 * u - 1) << 16;
-        f.p1 = mfcc_k::sample_at_i(s, base, first + 8 * (kFetchers + u) - 1) << 16;
-    }
-}
-
-__device__ __forceinline__ void park_window(float *Sf, int u, const Fetch &f) {
-    preemph8(f.p0, f.v0, Sf + 8 * u);
-    if (u < kSecond) preemph8(f.p1, f.v1, Sf + 8 * (kFetchers + u));
-}
-
-// (a, b) -> their bf16 roundings packed in one dword (a low) and the bf16 roundings of what the first rounding lost
-__device__ __forceinline__ void split_bf16_pair(float a, float b, uint32_t &hi, uint32_t &lo) {
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi) : "v"(a), "v"(b));
-    const float ra = a - __uint_as_float(hi << 16), rb = b - __uint_as_float(hi & 0xffff0000u);
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(ra), "v"(rb));
-}
-
-// summed mel energies of a finished tile and their log2; register r of block b is filter 16 b + 4 q + r of
-// frame lo.  Filters 40..47 do not exist: their (zero) sums must not reach the DCT as -inf * 0
-__device__ __forceinline__ void mel_log2(const float *Qt, int lane, int q, f32x4 (&lm)[kBlocks]) {
-    const f32x4 *Q4 = reinterpret_cast<const f32x4 *>(Qt) + lane;
-#pragma unroll
-    for (int b = 0; b < kBlocks; ++b) {
-        f32x4 m = Q4[(0 * kBlocks + b) * 64];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) m += Q4[(w * kBlocks + b) * 64];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) lm[b][r] = __builtin_amdgcn_logf(m[r]);
-    }
-    if (q >= 2) lm[2] = (f32x4){0.f, 0.f, 0.f, 0.f};
-}
-
-// d[0] + d[1] + d[2] = coefficients 0..15 of the previous tile (their 12 MFMAs are issued by the caller); 16..31 and
-// 32..39 are further M tiles whose A operands are fetched here (uniform branches; 12 coalesced dwords per lane out of L2)
-__device__ __forceinline__ void dct_store(const mfcc_k::StreamDesc &s, const Tables &t, const f32x4 (&d)[kBlocks],
-                                          const f32x4 (&lm)[kBlocks], const Cursor &c, int lo, int q, int lane,
-                                          int lane_off, float *__restrict__ out) {
-    const long long fr0 = (long long)c.t_in * kTile;
-    const long long rows_left = s.frames_per_ch - fr0;
-    float *o = out + ((long long)c.ch * s.frames_per_ch + fr0) * t.n_cep + lane_off;
-    const bool mine = lo < rows_left;
-    if (mine) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (4 * q + r < t.n_cep) o[r] = (d[0][r] + d[1][r]) + d[2][r];
-    }
-    for (int tile = 1; 16 * tile < t.n_cep; ++tile) {
-        const float *hi = t.a_dct_hi + (size_t)(tile - 1) * 12 * 64 + lane;
-        asm volatile("" : "+v"(hi));                   // not hoisted out of the tile loop: no registers to hold it
-        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        f32x4 e[kBlocks] = {zero, zero, zero};
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int b = 0; b < kBlocks; ++b) e[b] = MFCC1K_MFMA(hi[(4 * b + r) * 64], lm[b][r], e[b]);
-        if (mine) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (16 * tile + 4 * q + r < t.n_cep) o[16 * tile + r] = (e[0][r] + e[1][r]) + e[2][r];
-        }
-    }
-}
+// ---- device: the eight-wave LOCKSTEP staging of this contraction
 
 template <int VAR>
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
@@ -557,7 +375,7 @@ void mfcc_fused1024_kernel(mfcc_k::StreamDesc s, Tables t, LaunchGeom g, float *
                     }
             }
         }
-        if (role == 0 && have_prev) dct_store(s, t, d, lm, prev, lo, q, lane, lane_off, out);
+        if (role == 0 && have_prev) dct_store<-1>(s, t.n_cep, t.a_dct_hi, d, lm, prev, lo, q, lane, lane_off, out);
 #pragma unroll
         for (int b = 0; b < kBlocks; ++b)
             *reinterpret_cast<f32x4 *>(Qt + ((wave * kBlocks + b) * 64 + lane) * 4) = fin[b];
@@ -574,7 +392,7 @@ void mfcc_fused1024_kernel(mfcc_k::StreamDesc s, Tables t, LaunchGeom g, float *
         for (int r = 0; r < 4; ++r)
 #pragma unroll
             for (int b = 0; b < kBlocks; ++b) d[b] = MFCC1K_MFMA(ax[4 * b + r], lm[b][r], d[b]);
-        dct_store(s, t, d, lm, prev, lo, q, lane, lane_off, out);
+        dct_store<-1>(s, t.n_cep, t.a_dct_hi, d, lm, prev, lo, q, lane, lane_off, out);
     }
 }
 

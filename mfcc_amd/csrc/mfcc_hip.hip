@@ -3641,10 +3641,10 @@ int mfcc_hip_debug_read_stamps12(unsigned long long *dst) {
 
 #ifdef MFCC_1K12_STAMPS
 extern "C" int mfcc_hip_debug_read_stamps1k(unsigned long long *dst) {
-    if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(mfcc_fused1024_w12::g_stamps1k), sizeof(unsigned long long) * 144) != hipSuccess)
+    if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(mfcc_fused1024_w12bf::g_stamps1k), sizeof(unsigned long long) * 144) != hipSuccess)
         return MFCC_HIP_ERROR_OTHER;
     unsigned long long z[144] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(mfcc_fused1024_w12::g_stamps1k), z, sizeof z) != hipSuccess) return MFCC_HIP_ERROR_OTHER;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(mfcc_fused1024_w12bf::g_stamps1k), z, sizeof z) != hipSuccess) return MFCC_HIP_ERROR_OTHER;
     return MFCC_HIP_SUCCESS;
 }
 #endif

@@ -144,6 +144,15 @@ CASES = {
                            stride_per_cu=1, model="fp32/fp32"),
     "1024_bf16_40c": _plain("mfcc_fused1024_kernel", 1024, 40, n_cep=40, env={"MFCC_HIP_FUSED1024": "bf16"},
                             stride_per_cu=1, model="bf16x2/fp32"),
+    # the four forms at 32 kHz: Sets<2>, whose five sets change the waits and the register pressure of the bf16 forms,
+    # and the fp32 list with the most MFMAs
+    "1024_32k_40c": _plain(W12BF, 1024, 40, rate=32000, n_cep=40),
+    "1024_w12_32k_40c": _plain("mfcc_fused1024_w12_kernel", 1024, 40, rate=32000, n_cep=40,
+                               env={"MFCC_HIP_FUSED1024": "w12"}),
+    "1024_f32_32k_40c": _plain("mfcc_fused1024_kernel", 1024, 40, rate=32000, n_cep=40,
+                               env={"MFCC_HIP_FUSED1024": "f32"}, stride_per_cu=1, model="fp32/fp32"),
+    "1024_bf16_32k_40c": _plain("mfcc_fused1024_kernel", 1024, 40, rate=32000, n_cep=40,
+                                env={"MFCC_HIP_FUSED1024": "bf16"}, stride_per_cu=1, model="bf16x2/fp32"),
 }
 
 

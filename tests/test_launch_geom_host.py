@@ -21,10 +21,11 @@ KERNELS = {
     "fused512_h160":    (["kernel_fused512.hpp", "kernel_fused512_h160.hpp"], "kTileHop160", 16, 2560, 3072, TWO_PER_CU, 31),
     "fused512_h160_mb": (["kernel_fused512.hpp", "kernel_fused512_h160.hpp", "kernel_fused512_h160_mb.hpp"],
                          "kTileHop160", 16, 2560, 3072, TWO_PER_CU, 31),
-    "fused1024":        (["kernel_fused1024.hpp"], "kTileHop", 16, 5456, 6152, ONE_PER_CU, 31),
-    "fused1024_f32":    (["kernel_fused1024_f32.hpp"], "kTileHop", 16, 5456, 6152, ONE_PER_CU, 31),
-    "fused1024_w12":    (["kernel_fused1024_f32.hpp"], "kTileHop", 16, 5456, 6152, PAIRS, 30),      # namespace of the f32 form
-    "fused1024_w12bf":  (["kernel_fused1024.hpp"], "kTileHop", 16, 5456, 6152, PAIRS, 30),          # ... of the bf16 form
+    # the four 1024 forms take their geometry from one header
+    "fused1024":        (["fused1024_common.hpp", "kernel_fused1024.hpp"], "kTileHop", 16, 5456, 6152, ONE_PER_CU, 31),
+    "fused1024_f32":    (["fused1024_common.hpp", "kernel_fused1024_f32.hpp"], "kTileHop", 16, 5456, 6152, ONE_PER_CU, 31),
+    "fused1024_w12":    (["fused1024_common.hpp", "kernel_fused1024_w12.hpp"], "kTileHop", 16, 5456, 6152, PAIRS, 30),
+    "fused1024_w12bf":  (["fused1024_common.hpp", "kernel_fused1024_w12.hpp"], "kTileHop", 16, 5456, 6152, PAIRS, 30),
 }
 
 
