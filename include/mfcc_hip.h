@@ -443,6 +443,61 @@ int  mfcc_hip_select_dev(mfcc_hip_handle *h, const void *d_in, int row_width, co
                          const size_t *seg_offsets, size_t n_segs, void *d_out, size_t out_capacity_rows,
                          size_t *out_offsets);
 
+/* ---- per-channel energy normalization, PCEN --------------------------------------------
+ * An automatic gain control per mel band in place of the log (Wang et al. 2017): a first-order smoother over time and a
+ * root compression.  It runs on the log-mel rows of an MFCC_HIP_OUTPUT_LOGMEL handle, [frame][n_mel], log2 energies;
+ * a segment is one channel of a dense call or one utterance of a ragged one.  With E_t = 2^x_t (a non-finite x, the -inf
+ * of a silent band included, counts as E = 0: a legitimate zero here, not a hole), per column:
+ *     M_0 = E_0,   M_t = (1 - s) M_{t-1} + s E_t,   y_t = (E_t / (eps + M_t)^alpha + delta)^r - delta^r
+ * The order of operations is fixed by tiles of T = MFCC_HIP_PCEN_TILE frames counted from the segment's first row
+ * (frame t = slot k = t % T of tile i = t / T), all in fp32, nothing contracted but the fmaf's named:
+ *     constants (mfcc_hip_pcen_constants, float64 rounded once):  a = (float)(1 - (double)s),
+ *                 A_k = (float)((1 - (double)s)^(k + 1)), k = 0..T-1,  D_r = (float)(delta^r)
+ *     local smoother  L_{i,-1} = 0,  L_{i,k} = fmaf(a, L_{i,k-1}, s * E_t)
+ *     carry           C_0 = E_0,  M_t = fmaf(A_k, C_i, L_{i,k}),  C_{i+1} = M of slot T - 1 of tile i
+ *     output          g = log2(eps + M_t),  q = exp2(-alpha * g),  u = fmaf(E_t, q, delta),
+ *                     y_t = exp2(r * log2(u)) - D_r          (u = 0, only possible with delta = 0, gives y = 0)
+ * exp2 / log2 are the hardware's (v_exp_f32 / v_log_f32, the log the mel kernels use): log2 energies are expected in
+ * [-126, 127] or non-finite.  Every finite result is within |y - ref| <= c (|ref| + delta^r) of the float64 definition
+ * (c: DESIGN.md section 4.13) and a segment's bits depend on its rows, the row width and the parameters alone: the same
+ * from every entry point, any chunking of a host call, any 4-byte alignment, any run.
+ * eps and delta are in the units of the handle's mel energies, which carry power_scale (default 512 with int16 samples:
+ * speech bands are roughly 1e2 .. 1e7; librosa.pcen's defaults assume input scaled by 2^31).  Nothing is rescaled.
+ * s is the smoother's coefficient itself (librosa: b).                                                            */
+#define MFCC_HIP_PCEN_TILE 128
+typedef struct mfcc_hip_pcen {
+    uint32_t struct_size;   /* sizeof(mfcc_hip_pcen) */
+    float s;                /* smoother coefficient, 0 < s <= 1              (0.025) */
+    float alpha;            /* gain normalization strength, 0 <= alpha <= 1  (0.98)  */
+    float delta;            /* bias before the root, delta >= 0              (2)     */
+    float r;                /* root, 0 < r <= 1                              (0.5)   */
+    float eps;              /* floor of the smoother, eps > 0                (1e-6)  */
+    int32_t reserved[3];    /* must be 0 */
+} mfcc_hip_pcen;
+/* Host-only, no GPU needed.  defaults: the paper's values.  constants: decay[MFCC_HIP_PCEN_TILE] = A_k, *a, *delta_r as
+ * defined above (any of the three may be NULL).  A NULL block, a wrong struct_size, a non-zero reserved word, a value
+ * that is not finite or lies outside its range: MFCC_HIP_ERROR_INVALID_PARAM.                                    */
+int  mfcc_hip_pcen_defaults(mfcc_hip_pcen *p);
+int  mfcc_hip_pcen_constants(const mfcc_hip_pcen *p, float *decay, float *a, float *delta_r);
+/* The handle's PCEN applies to every float call enqueued after it, like its normalization.  The passes of a call run in
+ * this order: the MFCC kernels; the VAD decision on the raw log-mel rows (its thresholds are in log2 units); PCEN in
+ * place; normalization (per segment or sliding); deltas; selection.  p = NULL switches it off: the state after
+ * mfcc_hip_create, every entry point gives the bits it gave before.  A handle whose output is not
+ * MFCC_HIP_OUTPUT_LOGMEL: MFCC_HIP_ERROR_UNSUPPORTED; live streaming sessions: MFCC_HIP_ERROR_BUSY; a bad block:
+ * MFCC_HIP_ERROR_INVALID_PARAM.  A PCEN handle refuses what a normalizing handle refuses, for the same reasons (the
+ * smoother of a shard or of a session is not the stream's): the fixed-point entry points, mfcc_hip_stream_create,
+ * mfcc_hip_bank_create(_online, _online_pcen: a bank's PCEN is its own, on a raw handle), mfcc_hip_convert_wav(s) and
+ * mfcc_hip_process_i16_dev with halo = 1 return MFCC_HIP_ERROR_UNSUPPORTED.  In the host-buffer entry points it takes
+ * the route of per-segment normalization: frame-range chunks of a long channel are not independent.
+ * mfcc_hip_time_dev times the pass too.  The parameter block of the handle and the ABI version are unchanged.     */
+int  mfcc_hip_set_pcen(mfcc_hip_handle *h, const mfcc_hip_pcen *p);
+/* The kernels' direct entry: PCEN of float32 rows [seg_offsets[n_segs]][row_width] in HBM in place, segment k = rows
+ * seg_offsets[k] .. seg_offsets[k + 1] (host array, n_segs + 1 entries, must not decrease; rows before seg_offsets[0]
+ * and behind the last segment are not touched).  row_width 1..64, d_rows 4-byte aligned, any handle.  Asynchronous on
+ * the handle's stream; n_segs = 0 is a no-op.  E.g. the gathered rows of a frame-range-sharded stream.            */
+int  mfcc_hip_pcen_dev(mfcc_hip_handle *h, void *d_rows, int row_width, const size_t *seg_offsets, size_t n_segs,
+                       const mfcc_hip_pcen *p);
+
 /* name of the kernel symbol process_*_dev launches for this handle (to match rocprofv3 rows).  A log-mel handle runs
  * the log-mel instantiation of the kernel named (the default form: MFCC_HIP_FUSED512 / MFCC_HIP_FUSED1024 do not
  * apply to it) */
@@ -598,6 +653,18 @@ int    mfcc_hip_bank_reset(mfcc_hip_bank *b, const size_t *streams, size_t n);
  * push consumes nothing.  mfcc_hip_bank_push_dev stays asynchronous: held depends on chunk lengths only. */
 int    mfcc_hip_bank_create_online(mfcc_hip_handle *h, size_t n_streams, int normalize, int normalize_window,
                                    int delta_order, int delta_window, mfcc_hip_bank **out);
+/* The same with PCEN (mfcc_hip_set_pcen) in front of the normalization, as state of the bank: per stream and column
+ * the carry C of the tile in progress and its local smoother L, n_streams * 2 * W * 4 bytes; the frame count since
+ * create / reset, which the host mirrors, gives the slot of every fresh row.  h must be a RAW handle with
+ * MFCC_HIP_OUTPUT_LOGMEL (MFCC_HIP_ERROR_UNSUPPORTED otherwise); a bad block is MFCC_HIP_ERROR_INVALID_PARAM;
+ * p = NULL is mfcc_hip_bank_create_online, bit for bit.  The PCEN rows are what enters the normalization's ring and
+ * the deltas; with MFCC_HIP_NORMALIZE_NONE and order 0 they go straight to the caller's rows.  A flush's zero-padded
+ * tail frame goes through it like any row; reset and flush stay host-only bookkeeping (with a frame count of 0 nothing
+ * of C / L is read) and mfcc_hip_bank_push_dev stays asynchronous.  Contract: any pushes followed by a flush give, per
+ * stream and bit for bit, the rows of the one-shot call by a handle with the same p (mfcc_hip_set_pcen), normalize,
+ * normalize_window, min_window 1, center 0, delta_order, delta_window.                                            */
+int    mfcc_hip_bank_create_online_pcen(mfcc_hip_handle *h, size_t n_streams, const mfcc_hip_pcen *p, int normalize,
+                                        int normalize_window, int delta_order, int delta_window, mfcc_hip_bank **out);
 /* floats per row: W (1 + delta_order); W for a plain bank (int16 elements for a fixed one); 0 for NULL */
 size_t mfcc_hip_bank_row_width(const mfcc_hip_bank *b);
 /* delta_order * delta_window; 0 for a plain bank or NULL */

@@ -90,6 +90,21 @@ class MelBank(C.Structure):
     ]
 
 
+class Pcen(C.Structure):
+    """struct mfcc_hip_pcen"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("s", C.c_float),
+        ("alpha", C.c_float),
+        ("delta", C.c_float),
+        ("r", C.c_float),
+        ("eps", C.c_float),
+        ("reserved", C.c_int32 * 3),
+    ]
+
+
+PCEN_TILE = 128
+
 # every symbol include/mfcc_hip.h declares: name -> (restype, argtypes)
 _H = C.c_void_p
 _SZ = C.c_size_t
@@ -193,6 +208,13 @@ SYMBOLS = {
     "mfcc_hip_get_table_banked": (C.c_int, [C.POINTER(Params), C.c_int, C.POINTER(MelBank), C.c_int, C.c_void_p, _SZ,
                                             _PSZ]),
     "mfcc_hip_mel_bank_of": (C.c_int, [_H, C.POINTER(MelBank)]),
+    # PCEN: the host-only helpers, the handle's setting and the kernels' direct entry
+    "mfcc_hip_pcen_defaults": (C.c_int, [C.POINTER(Pcen)]),
+    "mfcc_hip_pcen_constants": (C.c_int, [C.POINTER(Pcen), C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mfcc_hip_set_pcen": (C.c_int, [_H, C.POINTER(Pcen)]),
+    "mfcc_hip_pcen_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, _SZ, C.POINTER(Pcen)]),
+    "mfcc_hip_bank_create_online_pcen": (C.c_int, [_H, _SZ, C.POINTER(Pcen), C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.POINTER(_H)]),
 }
 
 _lib = None

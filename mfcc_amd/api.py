@@ -16,6 +16,7 @@ buffers.  Without a GPU :class:`MFCC` construction raises ``MfccHipError(NOT_FOU
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -82,6 +83,75 @@ def _vad_args(mode=None, column=0, energy_threshold=5.0, energy_mean_scale=0.5, 
         raise ValueError("vad_proportion_threshold must lie strictly between 0 and 1, not %r" % (proportion_threshold,))
     return (m, int(column), float(energy_threshold), float(energy_mean_scale), int(frames_context),
             float(proportion_threshold))
+
+
+PCEN_DEFAULTS = dict(s=0.025, alpha=0.98, delta=2.0, r=0.5, eps=1e-6)      # Wang et al. 2017; mfcc_hip_pcen_defaults
+
+
+def pcen_smoothing(time_constant, samplerate, hop) -> float:
+    """librosa.pcen's smoother coefficient of a time constant in seconds: ``(sqrt(1 + 4 t^2) - 1) / (2 t^2)`` with
+    ``t = time_constant * samplerate / hop``."""
+    t = float(time_constant) * float(samplerate) / float(hop)
+    return (math.sqrt(1.0 + 4.0 * t * t) - 1.0) / (2.0 * t * t)
+
+
+def _pcen_args(pcen=None, samplerate=16000, hop=170, **kw):
+    """``struct mfcc_hip_pcen`` of ``pcen`` (``True``: the defaults; a dict of ``s`` or ``time_constant``, ``alpha``,
+    ``delta``, ``r``, ``eps``; keywords on top of it), ``None`` for ``None`` / ``False``, or ValueError: real numbers
+    that stay finite as fp32, ``0 < s <= 1``, ``0 <= alpha <= 1``, ``delta >= 0``, ``0 < r <= 1``, ``eps > 0``."""
+    def is_f32(v):                                  # a real number that is still finite as the float the ABI takes
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and \
+            abs(float(v)) <= float(np.finfo(np.float32).max)
+    if pcen is None or pcen is False:
+        if kw:
+            raise ValueError("PCEN parameters %s without pcen" % sorted(kw))
+        return None
+    if pcen is True:
+        pcen = {}
+    if not isinstance(pcen, dict):
+        raise ValueError("pcen must be None, True or a dict of parameters, not %r" % (pcen,))
+    a = dict(pcen, **kw)
+    unknown = sorted(set(a) - set(PCEN_DEFAULTS) - {"time_constant"})
+    if unknown:
+        raise ValueError("unknown PCEN parameters %s (known: s, time_constant, alpha, delta, r, eps)" % unknown)
+    if "time_constant" in a:
+        tc = a.pop("time_constant")
+        if "s" in a:
+            raise ValueError("pcen takes s or time_constant, not both")
+        if not is_f32(tc) or not float(tc) > 0.0:
+            raise ValueError("pcen time_constant must be a finite number of seconds > 0, not %r" % (tc,))
+        a["s"] = pcen_smoothing(tc, samplerate, hop)
+    v = dict(PCEN_DEFAULTS, **a)
+    for k in PCEN_DEFAULTS:
+        if not is_f32(v[k]):
+            raise ValueError("pcen %s must be a finite number, not %r" % (k, v[k]))
+    f = {k: float(np.float32(v[k])) for k in PCEN_DEFAULTS}              # the values the library sees
+    if not 0.0 < f["s"] <= 1.0:
+        raise ValueError("pcen s must lie in (0, 1], not %r" % (v["s"],))
+    if not 0.0 <= f["alpha"] <= 1.0:
+        raise ValueError("pcen alpha must lie in [0, 1], not %r" % (v["alpha"],))
+    if not f["delta"] >= 0.0:
+        raise ValueError("pcen delta must be >= 0, not %r" % (v["delta"],))
+    if not 0.0 < f["r"] <= 1.0:
+        raise ValueError("pcen r must lie in (0, 1], not %r" % (v["r"],))
+    if not f["eps"] > 0.0:
+        raise ValueError("pcen eps must be > 0 (as fp32), not %r" % (v["eps"],))
+    p = _lib.Pcen()
+    p.struct_size = C.sizeof(_lib.Pcen)
+    p.s, p.alpha, p.delta, p.r, p.eps = f["s"], f["alpha"], f["delta"], f["r"], f["eps"]
+    return p
+
+
+def pcen_constants(pcen=True, samplerate=16000, hop=170, **kw):
+    """``(decay[128], a, delta_r)`` of mfcc_hip_pcen_constants: the fp32 constants of the tile form.  No GPU needed."""
+    p = _pcen_args(pcen, samplerate, hop, **kw)
+    if p is None:
+        raise ValueError("pcen_constants needs parameters")
+    decay = np.empty(_lib.PCEN_TILE, dtype=np.float32)
+    a, dr = C.c_float(), C.c_float()
+    _lib.check(_lib.load().mfcc_hip_pcen_constants(C.byref(p), decay.ctypes.data_as(C.c_void_p), C.byref(a), C.byref(dr)),
+               "pcen_constants")
+    return decay, np.float32(a.value), np.float32(dr.value)
 
 
 _MIN_WINDOW = 100                  # default minimum window of the causal form (Kaldi's --min-cmn-window)
@@ -267,6 +337,14 @@ class MFCC:
     that come back are the voiced ones.  ``process`` then takes ONE utterance and returns ``(voiced, num_features)``;
     ``process_batch`` / ``process_packed`` return the shorter utterances; everything that returns a dense
     ``(channels, frames, ...)`` result, ``process_fixed``, :meth:`stream` and ``convert*`` raise ``UNSUPPORTED``.
+
+    ``pcen=True`` or ``pcen=dict(s=... | time_constant=..., alpha=..., delta=..., r=..., eps=...)`` (with
+    ``output="logmel"``) replaces the log of every band by per-channel energy normalization (Wang et al. 2017,
+    ``librosa.pcen``): ``M_t = (1 - s) M_{t-1} + s E_t`` from ``M_0 = E_0`` over the channel / utterance and
+    ``y = (E / (eps + M)^alpha + delta)^r - delta^r``, a silent band counting as ``E = 0``.  Defaults 0.025, 0.98, 2,
+    0.5, 1e-6; ``time_constant`` is in seconds and converts like librosa's.  ``eps`` and ``delta`` are in the units of
+    this handle's mel energies (they carry ``power_scale``); nothing is rescaled.  It runs before normalization and
+    deltas, the VAD still decides on the raw rows; the entry points a normalizing handle refuses refuse it too.
     """
 
     deltas, delta_window = 0, 2                 # the state after mfcc_hip_create
@@ -277,9 +355,10 @@ class MFCC:
                  normalize=None, deltas=0, delta_window=2, normalize_window=None, normalize_min_window=_MIN_WINDOW,
                  normalize_center=True, vad=None, vad_column=0, vad_energy_threshold=5.0, vad_energy_mean_scale=0.5,
                  vad_frames_context=0, vad_proportion_threshold=0.6, win_length=None, mel="notebook", fmin=0.0,
-                 fmax=None):
+                 fmax=None, pcen=None):
         if width != 16:
             raise ValueError("only width=16 (int16 PCM) is supported, like every reference target")
+        _pcen_args(pcen, samplerate, hop or int(nfft) // 3)
         self.win_length = _win_length(win_length, nfft, hop)
         self.mel, self.fmin, self.fmax, bank = _mel_bank(mel, fmin, fmax, samplerate, nfilters)
         norm = normalize_mode(normalize)
@@ -311,6 +390,9 @@ class MFCC:
         _lib.check(self._lib.mfcc_hip_create_banked(C.byref(self._params), self.win_length, C.byref(bank), C.byref(h)),
                    "mfcc_hip_create")
         self._h = h
+        self.pcen = None
+        if pcen is not None and pcen is not False:
+            self.set_pcen(pcen)
         self.normalize = None
         if norm != _lib.NORMALIZE_NONE:
             self.set_normalize(normalize)
@@ -452,6 +534,26 @@ class MFCC:
                                                      C.c_void_p(out.data_ptr()), fo.ctypes.data_as(C.c_void_p),
                                                      len(fo) - 1, order, window), "deltas_dev")
         return out
+
+    def set_pcen(self, pcen=True, **params):
+        """The handle's PCEN for every float call after this one: ``None`` / ``False`` (off), ``True`` (the paper's
+        parameters) or a dict of ``s`` (or ``time_constant`` in seconds), ``alpha``, ``delta``, ``r``, ``eps``; keywords
+        go on top.  Needs ``output="logmel"``.  :attr:`pcen` holds the effective parameters, or ``None``."""
+        p = _pcen_args(pcen, self.samplerate, self.hop, **params)
+        _lib.check(self._lib.mfcc_hip_set_pcen(self._h, C.byref(p) if p is not None else None), "set_pcen")
+        self.pcen = None if p is None else dict(s=p.s, alpha=p.alpha, delta=p.delta, r=p.r, eps=p.eps)
+
+    def pcen_rows(self, rows, frame_offsets=None, **params):
+        """PCEN of a CUDA float32 tensor of log2 energies in place, on the current torch stream; returns it.  ``rows``
+        and the segments as in :meth:`normalize_rows`; ``width`` 1..64, independent of this handle's own rows.  The
+        parameters are :meth:`set_pcen`'s keywords (default: the paper's), not the handle's setting."""
+        p = _pcen_args(True, self.samplerate, self.hop, **params)
+        fo = self._segments(rows, frame_offsets)
+        self._check_device(rows)
+        with self._on_torch_stream(rows.device):
+            _lib.check(self._lib.mfcc_hip_pcen_dev(self._h, C.c_void_p(rows.data_ptr()), int(rows.shape[-1]),
+                                                   fo.ctypes.data_as(C.c_void_p), len(fo) - 1, C.byref(p)), "pcen_dev")
+        return rows
 
     def set_normalize(self, mode):
         """The handle's normalization for every float call after this one (None, ``"mean"``, ``"meanvar"``)."""
@@ -762,7 +864,7 @@ class MFCC:
         return MfccStream(self, fixed)
 
     def stream_bank(self, n_streams, fixed=False, *, normalize=None, normalize_window=None, deltas=0,
-                    delta_window=2) -> "MfccStreamBank":
+                    delta_window=2, pcen=None) -> "MfccStreamBank":
         """``n_streams`` streaming sessions on this handle that advance together: one launch per push.
 
         ``normalize`` (``"mean"`` / ``"meanvar"``, with ``normalize_window=N``) and ``deltas`` (1 or 2, with
@@ -770,9 +872,13 @@ class MFCC:
         ``[max(0, t - N), t + 1)`` of their own stream and expanded to ``[s | D | DD]``; row ``t`` is returned once
         row ``t + deltas * delta_window`` is known, :meth:`MfccStreamBank.flush` returns the rest.  Pushes followed
         by a flush equal ``MFCC(..., normalize=..., normalize_window=N, normalize_min_window=1,
-        normalize_center=False, deltas=..., delta_window=...).process`` of the whole signal, bit for bit."""
+        normalize_center=False, deltas=..., delta_window=...).process`` of the whole signal, bit for bit.
+
+        ``pcen`` (``True`` or a dict, see :meth:`set_pcen`; a raw ``output="logmel"`` handle) runs PCEN on every
+        stream's rows before that, the smoother carried from push to push: two floats per stream and band.  The
+        one-shot call it equals then has ``pcen=`` the same parameters."""
         return MfccStreamBank(self, n_streams, fixed, normalize=normalize, normalize_window=normalize_window,
-                              deltas=deltas, delta_window=delta_window)
+                              deltas=deltas, delta_window=delta_window, pcen=pcen)
 
     # -- the receiver's power gate on fixed-point rows (software/cepstrum.c:93-183; include/mfcc_hip.h) -----
     def _gate_rows_in(self, rows, frame_offsets):
@@ -967,7 +1073,7 @@ class MfccStreamBank:
     lockstep) compute exactly the frames returned; a mixed push computes ``active streams x most frames of any``."""
 
     def __init__(self, mfcc: MFCC, n_streams, fixed=False, *, normalize=None, normalize_window=None, deltas=0,
-                 delta_window=2):
+                 delta_window=2, pcen=None):
         self._m = mfcc
         self._lib = mfcc._lib
         self.fixed = bool(fixed)
@@ -984,13 +1090,18 @@ class MfccStreamBank:
             window = _window_args(normalize_window, 1, False)[0]
         else:
             window = 0
-        self.online = mode != _lib.NORMALIZE_NONE or order != 0 or normalize_window is not None
+        p = None if pcen is None or pcen is False else _pcen_args(pcen, mfcc.samplerate, mfcc.hop)
+        self.online = mode != _lib.NORMALIZE_NONE or order != 0 or normalize_window is not None or p is not None
         if self.online and self.fixed:
-            raise ValueError("normalize / deltas of a stream bank are float only: fixed=True takes neither")
+            raise ValueError("pcen / normalize / deltas of a stream bank are float only: fixed=True takes none of them")
+        self.pcen = None if p is None else dict(s=p.s, alpha=p.alpha, delta=p.delta, r=p.r, eps=p.eps)
         self.normalize, self.normalize_window = (normalize if mode != _lib.NORMALIZE_NONE else None), (window or None)
         self.deltas, self.delta_window = order, dwin
         b = C.c_void_p()
-        if self.online:
+        if p is not None:
+            _lib.check(self._lib.mfcc_hip_bank_create_online_pcen(mfcc._h, self.n_streams, C.byref(p), mode, window, order,
+                                                                  dwin, C.byref(b)), "bank_create_online_pcen")
+        elif self.online:
             _lib.check(self._lib.mfcc_hip_bank_create_online(mfcc._h, self.n_streams, mode, window, order, dwin,
                                                              C.byref(b)), "bank_create_online")
         else:

@@ -29,6 +29,7 @@
 #include "kernel_normalize.hpp"
 #include "kernel_deltas.hpp"
 #include "kernel_normalize_sliding.hpp"
+#include "kernel_pcen.hpp"
 #include "kernel_vad.hpp"
 #include "kernel_stream_bank.hpp"
 #include "kernel_stream_bank_online.hpp"
@@ -293,6 +294,12 @@ struct mfcc_hip_handle {
     size_t d_sel_bytes = 0;
     void *d_final = nullptr;
     size_t d_final_bytes = 0;
+    // PCEN (mfcc_hip_set_pcen): on / off and the parameters as the kernels take them; the pass's scratch (d_pcen: tile
+    // ends, carries, tile table)
+    bool pcen_on = false;
+    mfcc_pcen::Prm pcen{};
+    void *d_pcen = nullptr;
+    size_t d_pcen_bytes = 0;
 };
 
 namespace {
@@ -832,6 +839,72 @@ int normalize_segments(mfcc_hip_handle *h, float *d_rows, int width, const size_
     return rc ? rc : normalize_enqueue(h, d_rows, pl, mode);
 }
 
+// ---- PCEN (kernel_pcen.hpp): in place on the raw log-mel rows, before the normalization.
+// Scratch (h->d_pcen): [tile ends: n_blocks * W floats][carries: n_blocks * W floats][tile table]
+bool pcen_ok(const mfcc_hip_pcen *p) {
+    if (!p || p->struct_size != sizeof(mfcc_hip_pcen) || p->reserved[0] || p->reserved[1] || p->reserved[2]) return false;
+    if (!std::isfinite(p->s) || !std::isfinite(p->alpha) || !std::isfinite(p->delta) || !std::isfinite(p->r) ||
+        !std::isfinite(p->eps))
+        return false;
+    return p->s > 0.0f && p->s <= 1.0f && p->alpha >= 0.0f && p->alpha <= 1.0f && p->delta >= 0.0f && p->r > 0.0f &&
+           p->r <= 1.0f && p->eps > 0.0f;
+}
+
+// the constants of the tile form: float64 on the host, rounded once
+mfcc_pcen::Prm pcen_prm(const mfcc_hip_pcen &p) {
+    mfcc_pcen::Prm q{};
+    const double d = 1.0 - double(p.s);
+    q.s = p.s;
+    q.a = float(d);
+    q.alpha = p.alpha;
+    q.r = p.r;
+    q.eps = p.eps;
+    q.delta = p.delta;
+    q.delta_r = float(std::pow(double(p.delta), double(p.r)));
+    for (int k = 0; k < mfcc_pcen::kTile; ++k) q.decay[k] = float(std::pow(d, double(k + 1)));
+    return q;
+}
+
+int pcen_enqueue(mfcc_hip_handle *h, float *d_rows, SegPlan pl, const mfcc_pcen::Prm &prm) {
+    const size_t W = size_t(pl.s.width);
+    const size_t tile_bytes = up256(size_t(pl.s.n_blocks) * W * sizeof(float));
+    int rc = ensure(h, &h->d_pcen, &h->d_pcen_bytes, 2 * tile_bytes + pl.table_ll * sizeof(long long) + 64);
+    if (rc) return rc;
+    if ((rc = scratch_acquire(h))) return rc;
+    char *base = static_cast<char *>(h->d_pcen);
+    float *lend = reinterpret_cast<float *>(base), *carry = reinterpret_cast<float *>(base + tile_bytes);
+    if ((rc = plan_upload(h, pl, reinterpret_cast<long long *>(base + 2 * tile_bytes)))) return rc;
+    const mfcc_norm::Segs &s = pl.s;
+    const long long G = mfcc_pcen::tiles_per_group(s.width);
+    const unsigned grid = tile_grid((s.n_blocks + G - 1) / G);
+    const unsigned grid_c = tile_grid((s.n_segs * s.width + mfcc_pcen::kThreads - 1) / mfcc_pcen::kThreads);
+    hipLaunchKernelGGL(mfcc_pcen::pcen_tile_end_kernel, dim3(grid), dim3(mfcc_pcen::kThreads), 0, h->stream,
+                       static_cast<const float *>(d_rows), s, prm, lend);
+    hipLaunchKernelGGL(mfcc_pcen::pcen_carry_kernel, dim3(grid_c), dim3(mfcc_pcen::kThreads), 0, h->stream,
+                       static_cast<const float *>(d_rows), s, prm, static_cast<const float *>(lend), carry);
+    hipLaunchKernelGGL(mfcc_pcen::pcen_apply_kernel, dim3(grid), dim3(mfcc_pcen::kThreads), 0, h->stream, d_rows, s, prm,
+                       static_cast<const float *>(carry));
+    HIP_TRY(h, hipGetLastError());
+    return scratch_release(h);
+}
+
+// n_segs segments of seg_rows rows each, back to back from row base_row
+int pcen_uniform(mfcc_hip_handle *h, float *d_rows, int width, size_t base_row, size_t n_segs, size_t seg_rows,
+                 const mfcc_pcen::Prm &prm) {
+    if (n_segs == 0 || seg_rows == 0) return MFCC_HIP_SUCCESS;
+    const SegPlan pl{uniform_segs(width, mfcc_pcen::kTile, base_row, n_segs, seg_rows), 0, nullptr};
+    return pcen_enqueue(h, d_rows, pl, prm);
+}
+
+// segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
+int pcen_segments(mfcc_hip_handle *h, float *d_rows, int width, const size_t *off, size_t n_segs,
+                  const mfcc_pcen::Prm &prm) {
+    if (n_segs == 0 || off[n_segs] == off[0]) return MFCC_HIP_SUCCESS;
+    SegPlan pl;
+    const int rc = plan_segs(h, off, n_segs, width, mfcc_pcen::kTile, pl);
+    return rc ? rc : pcen_enqueue(h, d_rows, pl, prm);
+}
+
 // ---- delta coefficients (kernel_deltas.hpp): a handle with a delta order runs its kernels and
 // its normalization into h->d_stat, then this pass writes the expanded rows to the caller's buffer.  The tile table of
 // a ragged call goes to h->d_dtab
@@ -1048,6 +1121,7 @@ int launch_expanded(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stri
     float *stat = K ? static_cast<float *>(h->d_stat) : static_cast<float *>(d_out);
     float *raw = sl ? static_cast<float *>(h->d_slide) : stat;
     if ((rc = launch(h, false, d_pcm, n, stride, nch, 0, raw, n_frames))) return rc;
+    if (h->pcen_on && (rc = pcen_uniform(h, raw, int(W), 0, nch, nf, h->pcen))) return rc;
     rc = sl ? sliding_uniform(h, raw, stat, int(W), 0, nch, nf, slide_args(h))
             : normalize_uniform(h, stat, int(W), 0, nch, nf, h->norm);
     if (rc) return rc;
@@ -1059,12 +1133,15 @@ int launch_expanded(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stri
 // the dense float device path with the handle's normalization: the launch, then one segment per channel
 int launch_float_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo, void *d_out,
                      size_t *n_frames) {
-    if (h && (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order) && halo)
+    if (h && (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->pcen_on) && halo)
         return MFCC_HIP_ERROR_UNSUPPORTED;                                       // a shard of a longer stream
     if (h && (h->delta_order || sliding(h))) return launch_expanded(h, d_pcm, n, stride, nch, d_out, n_frames);
     int rc = launch(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
-    if (rc || h->norm == MFCC_HIP_NORMALIZE_NONE) return rc;
+    if (rc || (h->norm == MFCC_HIP_NORMALIZE_NONE && !h->pcen_on)) return rc;
     DeviceGuard guard(h->device);
+    if (h->pcen_on &&
+        (rc = pcen_uniform(h, static_cast<float *>(d_out), int(row_width(h->r)), 0, nch, count_frames(h->r, n), h->pcen)))
+        return rc;
     return normalize_uniform(h, static_cast<float *>(d_out), int(row_width(h->r)), 0, nch, count_frames(h->r, n), h->norm);
 }
 
@@ -1307,7 +1384,9 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     // output; frame-range chunks write every channel's static rows to h->d_stat, which is normalized and expanded into
     // the whole result after the pipeline
     const int norm = fixed ? MFCC_HIP_NORMALIZE_NONE : h->norm;
-    const bool whole = (norm != MFCC_HIP_NORMALIZE_NONE || K) && ch_bytes > kChunkBytes;
+    // PCEN is recursive along the channel: it takes the route of the per-segment normalization
+    const bool pcen = !fixed && h->pcen_on;
+    const bool whole = (norm != MFCC_HIP_NORMALIZE_NONE || K || pcen) && ch_bytes > kChunkBytes;
     OutT *d_full = nullptr;
     float *d_stat = nullptr;
     if (whole) {
@@ -1338,6 +1417,10 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
         if (sl) rows = whole ? d_slide + c.out_off / size_t(1 + K) : d_slide;
         const int lrc = launch(h, fixed, d_in, c.n, c.stride, c.nch, c.halo, rows, nullptr, c.halo || c.frames != nf ? c.frames : 0);
         if (lrc || whole) return lrc;
+        if (pcen) {
+            const int prc = pcen_uniform(h, reinterpret_cast<float *>(rows), int(W), 0, c.nch, nf, h->pcen);
+            if (prc) return prc;
+        }
         const int nrc = sl ? sliding_uniform(h, d_slide, reinterpret_cast<float *>(stat_c), int(W), 0, c.nch, nf, slide_args(h))
                            : normalize_uniform(h, reinterpret_cast<float *>(rows), int(W), 0, c.nch, nf, norm);
         if (nrc || !K) return nrc;
@@ -1345,6 +1428,7 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     });
     if (rc || !whole) return rc ? rc : (K || sl ? scratch_release(h) : MFCC_HIP_SUCCESS);
     float *stat = K ? d_stat : reinterpret_cast<float *>(d_full);
+    if (pcen && (rc = pcen_uniform(h, sl ? d_slide : stat, int(W), 0, nch, nf, h->pcen))) return rc;
     rc = sl ? sliding_uniform(h, d_slide, stat, int(W), 0, nch, nf, slide_args(h))
             : normalize_uniform(h, stat, int(W), 0, nch, nf, norm);
     if (rc) return rc;
@@ -1567,8 +1651,12 @@ template <typename OutT>
 int process_ragged_dev_static(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
                               OutT *d_out, size_t cap, size_t *frame_offsets) {
     const int rc = process_ragged_dev_raw<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
-    if (rc || fixed || h->norm == MFCC_HIP_NORMALIZE_NONE || n_utt == 0) return rc;
+    if (rc || fixed || (h->norm == MFCC_HIP_NORMALIZE_NONE && !h->pcen_on) || n_utt == 0) return rc;
     DeviceGuard guard(h->device);
+    if (h->pcen_on) {
+        const int prc = pcen_segments(h, reinterpret_cast<float *>(d_out), int(row_width(h->r)), frame_offsets, n_utt, h->pcen);
+        if (prc) return prc;
+    }
     return normalize_segments(h, reinterpret_cast<float *>(d_out), int(row_width(h->r)), frame_offsets, n_utt, h->norm);
 }
 
@@ -1602,6 +1690,7 @@ int process_ragged_dev_select(mfcc_hip_handle *h, const int16_t *d_pcm, const si
     SelPlan pl;
     if ((rc = select_plan(h, frame_offsets, n_utt, int(WO), pl))) return rc;
     if ((rc = vad_decide(h, raw, int(W), frame_offsets, n_utt, vad_args(h), voiced, pl))) return rc;
+    if (h->pcen_on && (rc = pcen_segments(h, raw, int(W), frame_offsets, n_utt, h->pcen))) return rc;   // after the decision
     rc = sl ? sliding_segments(h, raw, stat, int(W), frame_offsets, n_utt, slide_args(h))
             : normalize_segments(h, stat, int(W), frame_offsets, n_utt, h->norm);
     if (rc) return rc;
@@ -1638,6 +1727,7 @@ int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, con
     if (sl) {
         float *raw = static_cast<float *>(h->d_slide);
         if ((rc = process_ragged_dev_raw<float>(h, false, d_pcm, offsets, n_utt, raw, total * W, frame_offsets))) return rc;
+        if (h->pcen_on && (rc = pcen_segments(h, raw, int(W), frame_offsets, n_utt, h->pcen))) return rc;
         if ((rc = sliding_segments(h, raw, stat, int(W), frame_offsets, n_utt, slide_args(h)))) return rc;
     } else if ((rc = process_ragged_dev_static<float>(h, false, d_pcm, offsets, n_utt, stat, total * W, frame_offsets))) {
         return rc;
@@ -1985,6 +2075,7 @@ void mfcc_hip_destroy(mfcc_hip_handle *h) {
     if (h->d_in) (void)hipFree(h->d_in);
     if (h->d_out) (void)hipFree(h->d_out);
     if (h->d_norm) (void)hipFree(h->d_norm);
+    if (h->d_pcen) (void)hipFree(h->d_pcen);
     if (h->d_full) (void)hipFree(h->d_full);
     if (h->d_stat) (void)hipFree(h->d_stat);
     if (h->d_dtab) (void)hipFree(h->d_dtab);
@@ -2024,6 +2115,7 @@ int mfcc_hip_process_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_
 int mfcc_hip_process_fixed_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_t nch,
                                int16_t *out, size_t cap, size_t *n_frames) {
     if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
+    if (h && h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;                          // ... nor PCEN
     if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
     if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... nor frame selection
     return process_host<int16_t>(h, true, pcm, n, nch, out, cap, n_frames);
@@ -2037,6 +2129,7 @@ int mfcc_hip_process_ragged_i16(mfcc_hip_handle *h, const int16_t *pcm, const si
 int mfcc_hip_process_ragged_fixed_i16(mfcc_hip_handle *h, const int16_t *pcm, const size_t *offsets, size_t n_utt,
                                       int16_t *out, size_t cap, size_t *frame_offsets) {
     if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
+    if (h && h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;                          // ... nor PCEN
     if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
     if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... nor frame selection
     return process_ragged<int16_t>(h, true, pcm, offsets, n_utt, out, cap, frame_offsets);
@@ -2051,6 +2144,7 @@ int mfcc_hip_process_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const
 int mfcc_hip_process_ragged_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const size_t *offsets, size_t n_utt,
                                           void *d_out, size_t cap, size_t *frame_offsets) {
     if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
+    if (h && h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;                          // ... nor PCEN
     if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
     if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... nor frame selection
     return process_ragged_dev<int16_t>(h, true, static_cast<const int16_t *>(d_pcm), offsets, n_utt,
@@ -2066,6 +2160,7 @@ int mfcc_hip_process_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, si
 int mfcc_hip_process_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride,
                                    size_t nch, int halo, void *d_out, size_t *n_frames) {
     if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
+    if (h && h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;                          // ... nor PCEN
     if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
     if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... nor frame selection
     return launch(h, true, d_pcm, n, stride, nch, halo, d_out, n_frames);
@@ -2074,7 +2169,7 @@ int mfcc_hip_process_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t
 int mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n, size_t stride,
                       size_t nch, void *d_out, int warmup, int iters, float *avg_ms) {
     if (!h || iters < 1 || warmup < 0 || !avg_ms) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (fixed && (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (fixed && (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->pcen_on)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;        // a dense result cannot hold rows of different counts
     DeviceGuard guard(h->device);
     // what process_*_dev enqueues: with normalization or deltas on, the float launch and the passes behind it
@@ -2127,6 +2222,50 @@ int mfcc_hip_normalize_dev(mfcc_hip_handle *h, void *d_rows, int row_width, cons
     if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0) return MFCC_HIP_SUCCESS;
     DeviceGuard guard(h->device);
     return normalize_segments(h, static_cast<float *>(d_rows), row_width, seg_offsets, n_segs, mode);
+}
+
+int mfcc_hip_pcen_defaults(mfcc_hip_pcen *p) {
+    if (!p) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::memset(p, 0, sizeof *p);
+    p->struct_size = sizeof(mfcc_hip_pcen);
+    p->s = 0.025f;
+    p->alpha = 0.98f;
+    p->delta = 2.0f;
+    p->r = 0.5f;
+    p->eps = 1e-6f;
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_pcen_constants(const mfcc_hip_pcen *p, float *decay, float *a, float *delta_r) {
+    if (!pcen_ok(p)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const mfcc_pcen::Prm q = pcen_prm(*p);
+    if (decay) std::memcpy(decay, q.decay, sizeof q.decay);
+    if (a) *a = q.a;
+    if (delta_r) *delta_r = q.delta_r;
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_set_pcen(mfcc_hip_handle *h, const mfcc_hip_pcen *p) {
+    if (!h || (p && !pcen_ok(p))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (p && !is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;      // PCEN reads log2 band energies
+    if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
+    h->pcen_on = p != nullptr;
+    if (p) h->pcen = pcen_prm(*p);
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_pcen_dev(mfcc_hip_handle *h, void *d_rows, int row_width, const size_t *seg_offsets, size_t n_segs,
+                      const mfcc_hip_pcen *p) {
+    if (!h || !pcen_ok(p)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (row_width < 1 || row_width > mfcc_pcen::kMaxWidth || (n_segs && !seg_offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    for (size_t k = 0; k < n_segs; ++k)
+        if (seg_offsets[k + 1] < seg_offsets[k]) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (n_segs && seg_offsets[n_segs] > seg_offsets[0] &&
+        (!d_rows || (reinterpret_cast<uintptr_t>(d_rows) & 3)))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (n_segs == 0) return MFCC_HIP_SUCCESS;
+    DeviceGuard guard(h->device);
+    return pcen_segments(h, static_cast<float *>(d_rows), row_width, seg_offsets, n_segs, pcen_prm(*p));
 }
 
 int mfcc_hip_set_normalize_window(mfcc_hip_handle *h, int window, int min_window, int center) {
@@ -2279,7 +2418,7 @@ int mfcc_hip_convert_wav(mfcc_hip_handle *h, const char *wav_in, const char *mfc
                          size_t *n_frames_out) {
     if (!h || !wav_in || !mfcc_out) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
-    if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;     // ... raw ones
+    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;     // ... raw ones
     if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... n_cep wide
     if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                            // ... of every frame
     std::vector<int16_t> pcm;
@@ -2323,7 +2462,7 @@ int mfcc_hip_convert_wavs(mfcc_hip_handle *h, const char *const *wav_in, const c
                           int fixed, size_t *n_frames_each) {
     if (!h || (n_files && (!wav_in || !mfcc_out))) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
-    if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;     // ... raw ones
+    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;     // ... raw ones
     if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... n_cep wide
     if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                            // ... of every frame
     std::vector<int16_t> pcm;
@@ -2432,6 +2571,7 @@ int mfcc_hip_stream_create(mfcc_hip_handle *h, int fixed, mfcc_hip_stream **out)
     *out = nullptr;
     if (h->destroy_pending) return MFCC_HIP_ERROR_INVALID_PARAM;        // the handle was already given back
     if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // per-call statistics of a stream
+    if (h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;                           // ... and a per-call smoother
     if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;     // deltas need 2 K N frames of lookahead
     if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;        // the threshold's mean is a whole-segment statistic
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
@@ -2555,6 +2695,11 @@ struct mfcc_hip_bank {
     float *d_ring = nullptr;             // [n][depth][W] raw rows (norm != NONE)
     float *d_tail = nullptr;             // [n][2 lag][W] static rows (lag > 0)
     std::vector<size_t> seen, held, held_after, raw_fo;
+    // PCEN of an online bank (mfcc_hip_bank_create_online_pcen): the parameters and, on
+    // the device, [n][2][W] carry and local smoother per (stream, column), then the decay table A_k
+    bool pcen = false;
+    mfcc_pcen::Prm pcen_prm{};
+    float *d_pcen = nullptr;
 };
 
 namespace {
@@ -2722,10 +2867,21 @@ void online_passes(mfcc_hip_bank *b, const mfcc_online::Rec *d_rec, size_t n_cmv
         hipLaunchKernelGGL(mfcc_online::online_deltas_kernel, dim3((unsigned)std::min(n_delta, cap)),
                            dim3(mfcc_online::kThreads), 0, h->stream, b->d_tail, stat, y, d_rec + n_cmvn, (long long)n_delta, W,
                            b->order, b->dwin, mfcc_delta::delta_scale(b->dwin));
-    if (n_carry)
+    if (n_carry && (b->d_ring || b->d_tail))
         hipLaunchKernelGGL(mfcc_online::online_carry_kernel, dim3((unsigned)std::min(n_carry, cap)),
                            dim3(mfcc_online::kThreads), 0, h->stream, b->d_ring, b->d_tail, d_raw, stat,
                            d_rec + n_cmvn + n_delta, (long long)n_carry, W, b->depth, 2 * b->lag);
+}
+
+// PCEN of the fresh raw rows of an online bank, before its CMVN: in place when CMVN or deltas follow (the PCEN rows are
+// what enters the ring and the tail), else straight to the caller's rows
+void online_pcen(mfcc_hip_bank *b, const mfcc_pcen::OnlineRec *d_rec, size_t n_rec, const float *d_raw, float *dst) {
+    mfcc_hip_handle *h = b->h;
+    const int W = int(row_width(h->r));
+    const size_t blocks = std::min((n_rec * size_t(W) + mfcc_pcen::kThreads - 1) / mfcc_pcen::kThreads, size_t(h->n_cu) * 8);
+    hipLaunchKernelGGL(mfcc_pcen::online_pcen_kernel, dim3((unsigned)blocks), dim3(mfcc_pcen::kThreads), 0, h->stream, d_raw, dst,
+                       d_rec, (long long)n_rec, W, b->pcen_prm,
+                       static_cast<const float *>(b->d_pcen + b->n * 2 * size_t(W)), b->d_pcen);
 }
 
 // bank_advance of an online bank (float): the frame launch always writes raw rows [active][nfmax][W] into the handle's
@@ -2760,12 +2916,17 @@ int online_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, con
     DeviceGuard guard(h->device);
     const size_t SW = 1 + max_total;
     // [0, 5 n_rec): the bank's records, active streams first; then the CMVN, delta and carry records
-    const size_t rec_ll = mfcc_bank::kRecLL * n_rec, desc_ll = rec_ll + mfcc_online::kRecLL * (n_cmvn + n_delta + n_active);
+    // ... and, with PCEN, its records behind them
+    const size_t rec_ll = mfcc_bank::kRecLL * n_rec, on_ll = mfcc_online::kRecLL * (n_cmvn + n_delta + n_active);
+    const size_t desc_ll = rec_ll + on_ll + (b->pcen ? mfcc_pcen::kOnlineRecLL * n_active : 0);
+    const bool post = norm || b->order;                  // passes behind PCEN: it then runs in place on the raw rows
     static_assert(sizeof(mfcc_online::Rec) == mfcc_online::kRecLL * sizeof(long long), "record layout");
+    static_assert(sizeof(mfcc_pcen::OnlineRec) == mfcc_pcen::kOnlineRecLL * sizeof(long long), "record layout");
     mfcc_hip_handle::PinnedDesc *pd = nullptr;
     if ((rc = desc_acquire(h, desc_ll, &pd))) return rc;
     auto *rec = reinterpret_cast<mfcc_bank::Rec *>(pd->p);
     auto *cm = reinterpret_cast<mfcc_online::Rec *>(pd->p + rec_ll), *de = cm + n_cmvn, *ca = de + n_delta;
+    auto *pc = reinterpret_cast<mfcc_pcen::OnlineRec *>(pd->p + rec_ll + on_ll);
     size_t a = 0, q = n_active;
     for (size_t u = 0; u < n; ++u) {
         const size_t n_new = offsets[u + 1] - offsets[u], nf = rfo[u + 1] - rfo[u];
@@ -2781,6 +2942,9 @@ int online_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, con
         if (b->order)
             de += online_delta_recs(de, u, row0, seen, nf, seen - b->held[u], emitted, g, frame_offsets[u], mfcc_online::kNoEdge);
         ca[a] = mfcc_online::Rec{(long long)u, (long long)row0, (long long)seen, (long long)nf, 0, 0, 0, 0};
+        if (b->pcen)
+            pc[a] = mfcc_pcen::OnlineRec{(long long)u, (long long)row0, (long long)seen, (long long)nf,
+                                         (long long)(post ? row0 : frame_offsets[u])};
         rec[a++] = c;
     }
     const size_t desc_bytes = up256(desc_ll * sizeof(long long));
@@ -2798,6 +2962,10 @@ int online_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, con
         float *d_raw = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes);
         float *d_stat = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes + rows_bytes);
         if ((rc = launch(h, false, d_w, SW - 1, SW, n_active, /*halo=*/1, d_raw, nullptr, nfmax))) return rc;
+        if (b->pcen) {
+            const long long *pc_ll = reinterpret_cast<const long long *>(d_rec) + rec_ll + on_ll;
+            online_pcen(b, reinterpret_cast<const mfcc_pcen::OnlineRec *>(pc_ll), n_active, d_raw, post ? d_raw : d_out);
+        }
         online_passes(b, reinterpret_cast<const mfcc_online::Rec *>(reinterpret_cast<const long long *>(d_rec) + rec_ll),
                       n_cmvn, n_delta, n_active, d_raw, d_stat, d_out);
     }
@@ -2875,15 +3043,20 @@ int online_tail(mfcc_hip_bank *b, const std::vector<size_t> &list, bool emit, vo
         if (b->order) n_delta += (fo[i + 1] - fo[i] + g - 1) / g;
     }
     DeviceGuard guard(h->device);
-    const size_t rec_ll = mfcc_bank::kRecLL * k, desc_ll = rec_ll + mfcc_online::kRecLL * (n_cmvn + n_delta);
+    const size_t rec_ll = mfcc_bank::kRecLL * k, on_ll = mfcc_online::kRecLL * (n_cmvn + n_delta);
+    const bool pcen = b->pcen && emit;                   // the tail frame goes through PCEN like any row
+    const bool post = norm || b->order;
+    const size_t desc_ll = rec_ll + on_ll + (pcen ? mfcc_pcen::kOnlineRecLL * k : 0);
     mfcc_hip_handle::PinnedDesc *pd = nullptr;
     int rc = desc_acquire(h, desc_ll, &pd);
     if (rc) return rc;
     auto *rec = reinterpret_cast<mfcc_bank::Rec *>(pd->p);
     auto *cm = reinterpret_cast<mfcc_online::Rec *>(pd->p + rec_ll), *de = cm + n_cmvn;
+    auto *pc = reinterpret_cast<mfcc_pcen::OnlineRec *>(pd->p + rec_ll + on_ll);
     for (size_t i = 0; i < k; ++i) {
         const size_t u = list[i], seen = b->seen[u];
         rec[i] = mfcc_bank::Rec{(long long)u, 0, 0, (long long)b->pending[u], 1};
+        if (pcen) pc[i] = mfcc_pcen::OnlineRec{(long long)u, (long long)i, (long long)seen, 1, (long long)(post ? i : fo[i])};
         if (norm) cm += online_cmvn_recs(cm, u, i, seen, nf, S, b->order ? i : fo[i]);
         if (b->order)
             de += online_delta_recs(de, u, i, seen, nf, seen - b->held[u], fo[i + 1] - fo[i], g, fo[i],
@@ -2903,6 +3076,11 @@ int online_tail(mfcc_hip_bank *b, const std::vector<size_t> &list, bool emit, vo
     float *d_stat = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes + rows_bytes);
     if (emit && (rc = launch(h, false, d_w, flen, SW, k, /*halo=*/1, d_raw, nullptr, 1))) return rc;
     if (total) {
+        if (pcen) {
+            const long long *pc_ll = static_cast<const long long *>(h->d_out) + rec_ll + on_ll;
+            online_pcen(b, reinterpret_cast<const mfcc_pcen::OnlineRec *>(pc_ll), k, d_raw,
+                        post ? d_raw : static_cast<float *>(b->st_out));
+        }
         online_passes(b, reinterpret_cast<const mfcc_online::Rec *>(static_cast<const long long *>(h->d_out) + rec_ll), n_cmvn,
                       n_delta, 0, d_raw, d_stat, static_cast<float *>(b->st_out));
         HIP_TRY(h, hipMemcpyAsync(out, b->st_out, total * WO * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -2923,7 +3101,7 @@ void bank_flush_offsets(const mfcc_hip_bank *b, const std::vector<size_t> &list,
 
 // a bank on a checked handle; norm / order as validated by the caller (NONE and 0: a plain bank)
 int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int window, int order, int dwin,
-                mfcc_hip_bank **out) {
+                mfcc_hip_bank **out, const mfcc_pcen::Prm *pcen = nullptr) {
     mfcc_hip_bank *b = new (std::nothrow) mfcc_hip_bank();
     if (!b) return MFCC_HIP_ERROR_NO_MEM;
     b->h = h;
@@ -2935,7 +3113,11 @@ int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int w
     b->held.assign(n_streams, 0);
     b->held_after.assign(n_streams, 0);
     b->raw_fo.assign(n_streams + 1, 0);
-    b->online = norm != MFCC_HIP_NORMALIZE_NONE || order != 0;
+    b->online = norm != MFCC_HIP_NORMALIZE_NONE || order != 0 || pcen;
+    if (pcen) {
+        b->pcen = true;
+        b->pcen_prm = *pcen;
+    }
     if (norm != MFCC_HIP_NORMALIZE_NONE) {
         b->norm = norm;
         b->window = window;
@@ -2960,6 +3142,13 @@ int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int w
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_state), bytes + 64);
     if (e == hipSuccess && ring_bytes) e = hipMalloc(reinterpret_cast<void **>(&b->d_ring), ring_bytes + 64);
     if (e == hipSuccess && tail_bytes) e = hipMalloc(reinterpret_cast<void **>(&b->d_tail), tail_bytes + 64);
+    if (e == hipSuccess && b->pcen) {
+        const size_t state_floats = n_streams * 2 * W;
+        e = hipMalloc(reinterpret_cast<void **>(&b->d_pcen), (state_floats + mfcc_pcen::kTile) * sizeof(float) + 64);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(b->d_pcen + state_floats, b->pcen_prm.decay, sizeof b->pcen_prm.decay, hipMemcpyHostToDevice,
+                               h->stream);
+    }
     if (e == hipSuccess) e = hipMemsetAsync(b->d_state, 0, bytes, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(e);
@@ -2976,7 +3165,7 @@ int mfcc_hip_bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, mfcc_h
     *out = nullptr;
     if (h->destroy_pending || !n_streams) return MFCC_HIP_ERROR_INVALID_PARAM;
     // what mfcc_hip_stream_create refuses: per-call statistics, lookahead and whole-segment thresholds of a stream
-    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode || h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     return bank_create(h, fixed, n_streams, MFCC_HIP_NORMALIZE_NONE, 0, 0, 0, out);
 }
@@ -2987,7 +3176,7 @@ int mfcc_hip_bank_create_online(mfcc_hip_handle *h, size_t n_streams, int normal
     *out = nullptr;
     if (h->destroy_pending || !n_streams) return MFCC_HIP_ERROR_INVALID_PARAM;
     // the bank's settings are its own: the handle must be a raw one, and able to run the float path
-    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode || h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (normalize != MFCC_HIP_NORMALIZE_NONE && normalize != MFCC_HIP_NORMALIZE_MEAN && normalize != MFCC_HIP_NORMALIZE_MEAN_VAR)
         return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -2996,6 +3185,26 @@ int mfcc_hip_bank_create_online(mfcc_hip_handle *h, size_t n_streams, int normal
     if (delta_order < 0 || delta_order > 2 || delta_window < 1 || delta_window > mfcc_delta::kMaxWindow)
         return MFCC_HIP_ERROR_INVALID_PARAM;
     return bank_create(h, 0, n_streams, normalize, normalize_window, delta_order, delta_window, out);
+}
+
+int mfcc_hip_bank_create_online_pcen(mfcc_hip_handle *h, size_t n_streams, const mfcc_hip_pcen *p, int normalize,
+                                     int normalize_window, int delta_order, int delta_window, mfcc_hip_bank **out) {
+    if (!p) return mfcc_hip_bank_create_online(h, n_streams, normalize, normalize_window, delta_order, delta_window, out);
+    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
+    *out = nullptr;
+    if (h->destroy_pending || !n_streams || !pcen_ok(p)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    // the bank's settings are its own: a raw log-mel handle that can run the float path
+    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode || h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (!is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (normalize != MFCC_HIP_NORMALIZE_NONE && normalize != MFCC_HIP_NORMALIZE_MEAN && normalize != MFCC_HIP_NORMALIZE_MEAN_VAR)
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (normalize != MFCC_HIP_NORMALIZE_NONE && (normalize_window < 1 || normalize_window > MFCC_HIP_MAX_NORMALIZE_WINDOW))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (delta_order < 0 || delta_order > 2 || delta_window < 1 || delta_window > mfcc_delta::kMaxWindow)
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    const mfcc_pcen::Prm prm = pcen_prm(*p);
+    return bank_create(h, 0, n_streams, normalize, normalize_window, delta_order, delta_window, out, &prm);
 }
 
 size_t mfcc_hip_bank_row_width(const mfcc_hip_bank *b) { return b ? bank_row_width(b) : 0; }
@@ -3049,6 +3258,7 @@ void mfcc_hip_bank_destroy(mfcc_hip_bank *b) {
         if (b->d_state) (void)hipFree(b->d_state);
         if (b->d_ring) (void)hipFree(b->d_ring);
         if (b->d_tail) (void)hipFree(b->d_tail);
+        if (b->d_pcen) (void)hipFree(b->d_pcen);
         if (b->st_in) (void)hipFree(b->st_in);
         if (b->st_out) (void)hipFree(b->st_out);
         delete b;
