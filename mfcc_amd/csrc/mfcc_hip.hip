@@ -795,17 +795,60 @@ int plan_upload(mfcc_hip_handle *h, SegPlan &pl, long long *d_table) {
     return MFCC_HIP_SUCCESS;
 }
 
+// ---- which rows are segments: n_segs runs of seg_rows rows back to back from row base_row (a dense call: one per
+// channel), or segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
+struct SegSpan {
+    const size_t *off;      // nullptr: the uniform form
+    size_t n_segs, base_row, seg_rows;
+};
+
+inline SegSpan span_uniform(size_t base_row, size_t n_segs, size_t seg_rows) { return SegSpan{nullptr, n_segs, base_row, seg_rows}; }
+inline SegSpan span_offsets(const size_t *off, size_t n_segs) { return SegSpan{off, n_segs, 0, 0}; }
+
+// no segment, or no row in any: every pass answers success before anything else
+inline bool span_empty(const SegSpan &sp) {
+    return sp.n_segs == 0 || (sp.off ? sp.off[sp.n_segs] == sp.off[0] : sp.seg_rows == 0);
+}
+
+// the tiles of tile_rows rows of a span that is not empty.  The uniform form is filled in as it is -- a dense call may
+// have tens of thousands of channels: no loop, no table; the offsets form is plan_segs's
+int plan_span(mfcc_hip_handle *h, const SegSpan &sp, int width, int tile_rows, SegPlan &pl) {
+    if (sp.off) return plan_segs(h, sp.off, sp.n_segs, width, tile_rows, pl);
+    pl = SegPlan{uniform_segs(width, tile_rows, sp.base_row, sp.n_segs, sp.seg_rows), 0, nullptr};
+    return MFCC_HIP_SUCCESS;
+}
+
+// the checks of the direct entries (mfcc_hip_*_dev on rows): segment offsets that do not decrease, and address ranges
+// [lo, hi) -- or byte ranges behind two pointers -- that do not overlap
+inline bool offsets_ok(const size_t *off, size_t n_segs) {
+    for (size_t k = 0; k < n_segs; ++k)
+        if (off[k + 1] < off[k]) return false;
+    return true;
+}
+
+inline bool ranges_overlap(uintptr_t a_lo, uintptr_t a_hi, uintptr_t b_lo, uintptr_t b_hi) {
+    return a_lo < b_hi && b_lo < a_hi;
+}
+
+inline bool ranges_overlap(const void *a, size_t a_lo, size_t a_hi, const void *b, size_t b_lo, size_t b_hi) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return ranges_overlap(pa + a_lo, pa + a_hi, pb + b_lo, pb + b_hi);
+}
+
 inline unsigned tile_grid(long long n) { return unsigned(std::min<long long>(n, 1 << 20)); }
 
-// ---- per-segment mean / variance normalization (kernel_normalize.hpp): every float entry point
-// of a handle with a mode other than NONE runs this after its kernels, on the handle's stream, over the rows it wrote.
+// ---- per-segment mean / variance normalization (kernel_normalize.hpp): in place.
 // Scratch (h->d_norm): [tile partials: n_blocks * W * 24 B][coefficients: n_segs * W * 8 B][tile table]
-int normalize_enqueue(mfcc_hip_handle *h, float *d_rows, SegPlan pl, int mode) {
-    const size_t W = size_t(pl.s.width);
+int normalize_pass(mfcc_hip_handle *h, float *d_rows, int width, const SegSpan &sp, int mode) {
+    if (span_empty(sp) || mode == MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_SUCCESS;
+    SegPlan pl;
+    int rc = plan_span(h, sp, width, mfcc_norm::tile_rows(width), pl);
+    if (rc) return rc;
+    const size_t W = size_t(width);
     const size_t part_bytes = up256(size_t(pl.s.n_blocks) * W * sizeof(mfcc_norm::Part));
     const size_t coef_bytes = up256(size_t(pl.s.n_segs) * W * sizeof(float2));
-    int rc = ensure(h, &h->d_norm, &h->d_norm_bytes, part_bytes + coef_bytes + pl.table_ll * sizeof(long long) + 64);
-    if (rc) return rc;
+    if ((rc = ensure(h, &h->d_norm, &h->d_norm_bytes, part_bytes + coef_bytes + pl.table_ll * sizeof(long long) + 64)))
+        return rc;
     if ((rc = scratch_acquire(h))) return rc;
     char *base = static_cast<char *>(h->d_norm);
     auto *part = reinterpret_cast<mfcc_norm::Part *>(base);
@@ -823,23 +866,7 @@ int normalize_enqueue(mfcc_hip_handle *h, float *d_rows, SegPlan pl, int mode) {
     return scratch_release(h);
 }
 
-// n_segs segments of seg_rows rows each, back to back from row base_row
-int normalize_uniform(mfcc_hip_handle *h, float *d_rows, int width, size_t base_row, size_t n_segs, size_t seg_rows,
-                      int mode) {
-    if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0 || seg_rows == 0) return MFCC_HIP_SUCCESS;
-    const SegPlan pl{uniform_segs(width, mfcc_norm::tile_rows(width), base_row, n_segs, seg_rows), 0, nullptr};
-    return normalize_enqueue(h, d_rows, pl, mode);
-}
-
-// segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
-int normalize_segments(mfcc_hip_handle *h, float *d_rows, int width, const size_t *off, size_t n_segs, int mode) {
-    if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0 || off[n_segs] == off[0]) return MFCC_HIP_SUCCESS;
-    SegPlan pl;
-    const int rc = plan_segs(h, off, n_segs, width, mfcc_norm::tile_rows(width), pl);
-    return rc ? rc : normalize_enqueue(h, d_rows, pl, mode);
-}
-
-// ---- PCEN (kernel_pcen.hpp): in place on the raw log-mel rows, before the normalization.
+// ---- PCEN (kernel_pcen.hpp): in place on the raw log-mel rows.
 // Scratch (h->d_pcen): [tile ends: n_blocks * W floats][carries: n_blocks * W floats][tile table]
 bool pcen_ok(const mfcc_hip_pcen *p) {
     if (!p || p->struct_size != sizeof(mfcc_hip_pcen) || p->reserved[0] || p->reserved[1] || p->reserved[2]) return false;
@@ -865,11 +892,14 @@ mfcc_pcen::Prm pcen_prm(const mfcc_hip_pcen &p) {
     return q;
 }
 
-int pcen_enqueue(mfcc_hip_handle *h, float *d_rows, SegPlan pl, const mfcc_pcen::Prm &prm) {
-    const size_t W = size_t(pl.s.width);
-    const size_t tile_bytes = up256(size_t(pl.s.n_blocks) * W * sizeof(float));
-    int rc = ensure(h, &h->d_pcen, &h->d_pcen_bytes, 2 * tile_bytes + pl.table_ll * sizeof(long long) + 64);
+int pcen_pass(mfcc_hip_handle *h, float *d_rows, int width, const SegSpan &sp, const mfcc_pcen::Prm &prm) {
+    if (span_empty(sp)) return MFCC_HIP_SUCCESS;
+    SegPlan pl;
+    int rc = plan_span(h, sp, width, mfcc_pcen::kTile, pl);
     if (rc) return rc;
+    const size_t W = size_t(width);
+    const size_t tile_bytes = up256(size_t(pl.s.n_blocks) * W * sizeof(float));
+    if ((rc = ensure(h, &h->d_pcen, &h->d_pcen_bytes, 2 * tile_bytes + pl.table_ll * sizeof(long long) + 64))) return rc;
     if ((rc = scratch_acquire(h))) return rc;
     char *base = static_cast<char *>(h->d_pcen);
     float *lend = reinterpret_cast<float *>(base), *carry = reinterpret_cast<float *>(base + tile_bytes);
@@ -888,29 +918,13 @@ int pcen_enqueue(mfcc_hip_handle *h, float *d_rows, SegPlan pl, const mfcc_pcen:
     return scratch_release(h);
 }
 
-// n_segs segments of seg_rows rows each, back to back from row base_row
-int pcen_uniform(mfcc_hip_handle *h, float *d_rows, int width, size_t base_row, size_t n_segs, size_t seg_rows,
-                 const mfcc_pcen::Prm &prm) {
-    if (n_segs == 0 || seg_rows == 0) return MFCC_HIP_SUCCESS;
-    const SegPlan pl{uniform_segs(width, mfcc_pcen::kTile, base_row, n_segs, seg_rows), 0, nullptr};
-    return pcen_enqueue(h, d_rows, pl, prm);
-}
-
-// segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
-int pcen_segments(mfcc_hip_handle *h, float *d_rows, int width, const size_t *off, size_t n_segs,
-                  const mfcc_pcen::Prm &prm) {
-    if (n_segs == 0 || off[n_segs] == off[0]) return MFCC_HIP_SUCCESS;
+// ---- delta coefficients (kernel_deltas.hpp): out of place, the last step of post_chain.  The
+// tile table of a ragged call goes to h->d_dtab
+int deltas_pass(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, const SegSpan &sp, int order, int window) {
+    if (span_empty(sp)) return MFCC_HIP_SUCCESS;
     SegPlan pl;
-    const int rc = plan_segs(h, off, n_segs, width, mfcc_pcen::kTile, pl);
-    return rc ? rc : pcen_enqueue(h, d_rows, pl, prm);
-}
-
-// ---- delta coefficients (kernel_deltas.hpp): a handle with a delta order runs its kernels and
-// its normalization into h->d_stat, then this pass writes the expanded rows to the caller's buffer.  The tile table of
-// a ragged call goes to h->d_dtab
-int deltas_enqueue(mfcc_hip_handle *h, const float *d_in, float *d_out, SegPlan pl, int order, int window) {
-    int rc = scratch_acquire(h);
-    if (rc) return rc;
+    int rc = plan_span(h, sp, width, mfcc_delta::tile_rows(width, order, window), pl);
+    if (rc || (rc = scratch_acquire(h))) return rc;
     if (pl.pd && (rc = ensure(h, &h->d_dtab, &h->d_dtab_bytes, pl.table_ll * sizeof(long long) + 64))) return rc;
     if ((rc = plan_upload(h, pl, static_cast<long long *>(h->d_dtab)))) return rc;
     const mfcc_delta::DeltasKernel kernel = mfcc_delta::deltas_kernel_of(order, window);
@@ -921,26 +935,8 @@ int deltas_enqueue(mfcc_hip_handle *h, const float *d_in, float *d_out, SegPlan 
     return scratch_release(h);
 }
 
-// n_segs segments of seg_rows rows each, back to back from row base_row
-int deltas_uniform(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, size_t base_row, size_t n_segs,
-                   size_t seg_rows, int order, int window) {
-    if (n_segs == 0 || seg_rows == 0) return MFCC_HIP_SUCCESS;
-    const SegPlan pl{uniform_segs(width, mfcc_delta::tile_rows(width, order, window), base_row, n_segs, seg_rows), 0, nullptr};
-    return deltas_enqueue(h, d_in, d_out, pl, order, window);
-}
-
-// segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
-int deltas_segments(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, const size_t *off, size_t n_segs,
-                    int order, int window) {
-    if (n_segs == 0 || off[n_segs] == off[0]) return MFCC_HIP_SUCCESS;
-    SegPlan pl;
-    const int rc = plan_segs(h, off, n_segs, width, mfcc_delta::tile_rows(width, order, window), pl);
-    return rc ? rc : deltas_enqueue(h, d_in, d_out, pl, order, window);
-}
-
-// ---- sliding-window normalization (kernel_normalize_sliding.hpp): out of place.  A handle with
-// a window runs its kernels into h->d_slide, then this pass writes the normalized rows to the caller's buffer (or to
-// h->d_stat, when deltas follow).  The tile table of a ragged call goes to h->d_stab
+// ---- sliding-window normalization (kernel_normalize_sliding.hpp): out of place, raw -> stat
+// of post_route.  The tile table of a ragged call goes to h->d_stab
 struct SlideArgs {
     int mode, window, min_window, center;
 };
@@ -950,32 +946,17 @@ inline SlideArgs slide_args(const mfcc_hip_handle *h) {
     return SlideArgs{h->norm, h->norm_window, h->norm_min_window, h->norm_center};
 }
 
-int sliding_enqueue(mfcc_hip_handle *h, const float *d_in, float *d_out, SegPlan pl, SlideArgs a) {
-    int rc = scratch_acquire(h);
-    if (rc) return rc;
+int sliding_pass(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, const SegSpan &sp, SlideArgs a) {
+    if (span_empty(sp)) return MFCC_HIP_SUCCESS;
+    SegPlan pl;
+    int rc = plan_span(h, sp, width, mfcc_slide::tile_rows(width, a.window), pl);
+    if (rc || (rc = scratch_acquire(h))) return rc;
     if (pl.pd && (rc = ensure(h, &h->d_stab, &h->d_stab_bytes, pl.table_ll * sizeof(long long) + 64))) return rc;
     if ((rc = plan_upload(h, pl, static_cast<long long *>(h->d_stab)))) return rc;
     hipLaunchKernelGGL(mfcc_slide::normalize_sliding_kernel, dim3(tile_grid(pl.s.n_blocks)), dim3(mfcc_slide::kThreads), 0,
                        h->stream, d_in, d_out, pl.s, mfcc_slide::run_rows(a.window), a.window, a.min_window, a.center, a.mode);
     HIP_TRY(h, hipGetLastError());
     return scratch_release(h);
-}
-
-// n_segs segments of seg_rows rows each, back to back from row base_row
-int sliding_uniform(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, size_t base_row, size_t n_segs,
-                    size_t seg_rows, SlideArgs a) {
-    if (n_segs == 0 || seg_rows == 0) return MFCC_HIP_SUCCESS;
-    const SegPlan pl{uniform_segs(width, mfcc_slide::tile_rows(width, a.window), base_row, n_segs, seg_rows), 0, nullptr};
-    return sliding_enqueue(h, d_in, d_out, pl, a);
-}
-
-// segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
-int sliding_segments(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, const size_t *off, size_t n_segs,
-                     SlideArgs a) {
-    if (n_segs == 0 || off[n_segs] == off[0]) return MFCC_HIP_SUCCESS;
-    SegPlan pl;
-    const int rc = plan_segs(h, off, n_segs, width, mfcc_slide::tile_rows(width, a.window), pl);
-    return rc ? rc : sliding_enqueue(h, d_in, d_out, pl, a);
 }
 
 // ---- energy VAD and voiced-row selection (kernel_vad.hpp).  The decision reads one column of
@@ -1006,10 +987,11 @@ struct SelPlan {
     long long *tile_off, *seg_off;
 };
 
-int select_plan(mfcc_hip_handle *h, const size_t *off, size_t n_segs, int tile_width, SelPlan &pl) {
+int select_plan(mfcc_hip_handle *h, const SegSpan &span, int tile_width, SelPlan &pl) {
     SegPlan sp;
-    int rc = plan_segs(h, off, n_segs, tile_width, mfcc_vad::select_tile_rows(tile_width), sp);
+    int rc = plan_span(h, span, tile_width, mfcc_vad::select_tile_rows(tile_width), sp);
     if (rc) return rc;
+    const size_t n_segs = span.n_segs;
     const size_t nb = size_t(sp.s.n_blocks);
     const size_t cnt_b = up256(nb * sizeof(unsigned)), toff_b = up256((nb + 1) * sizeof(long long));
     const size_t soff_b = up256((n_segs + 1) * sizeof(long long));
@@ -1026,15 +1008,15 @@ int select_plan(mfcc_hip_handle *h, const size_t *off, size_t n_segs, int tile_w
 
 // the decision on column a.column of rows [..][W], on the tiles of pl (whose counts it fills).  Scratch (h->d_vad):
 // [tile partials of the mean][theta per segment][tile table of the mean]
-int vad_decide(mfcc_hip_handle *h, const float *d_rows, int W, const size_t *off, size_t n_segs, VadArgs a,
-               unsigned char *d_voiced, const SelPlan &pl) {
+int vad_decide(mfcc_hip_handle *h, const float *d_rows, int W, const SegSpan &sp, VadArgs a, unsigned char *d_voiced,
+               const SelPlan &pl) {
     const double *theta = nullptr;
     int rc;
     if (a.scale != 0.0f) {
         SegPlan mp;
-        if ((rc = plan_segs(h, off, n_segs, W, mfcc_vad::kMeanTileRows, mp))) return rc;
+        if ((rc = plan_span(h, sp, W, mfcc_vad::kMeanTileRows, mp))) return rc;
         const mfcc_norm::Segs &sm = mp.s;
-        const size_t part_b = up256(size_t(sm.n_blocks) * sizeof(mfcc_vad::MeanPart)), theta_b = up256(n_segs * sizeof(double));
+        const size_t part_b = up256(size_t(sm.n_blocks) * sizeof(mfcc_vad::MeanPart)), theta_b = up256(sp.n_segs * sizeof(double));
         if ((rc = ensure(h, &h->d_vad, &h->d_vad_bytes, part_b + theta_b + mp.table_ll * sizeof(long long) + 64))) return rc;
         char *base = static_cast<char *>(h->d_vad);
         auto *part = reinterpret_cast<mfcc_vad::MeanPart *>(base);
@@ -1080,24 +1062,24 @@ int select_run(mfcc_hip_handle *h, const float *d_in, int Wp, const unsigned cha
     return MFCC_HIP_SUCCESS;
 }
 
-// segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
-int vad_segments(mfcc_hip_handle *h, const float *d_rows, int W, const size_t *off, size_t n_segs, VadArgs a,
-                 unsigned char *d_voiced) {
-    if (n_segs == 0 || off[n_segs] == off[0]) return MFCC_HIP_SUCCESS;
+// the decision alone, on tiles of its own
+int vad_segments(mfcc_hip_handle *h, const float *d_rows, int W, const SegSpan &sp, VadArgs a, unsigned char *d_voiced) {
+    if (span_empty(sp)) return MFCC_HIP_SUCCESS;
     SelPlan pl;
-    int rc = select_plan(h, off, n_segs, 1, pl);           // tiles of kMaxTileRows rows
-    if (rc || (rc = vad_decide(h, d_rows, W, off, n_segs, a, d_voiced, pl))) return rc;
+    int rc = select_plan(h, sp, 1, pl);                    // tiles of kMaxTileRows rows
+    if (rc || (rc = vad_decide(h, d_rows, W, sp, a, d_voiced, pl))) return rc;
     return scratch_release(h);
 }
 
-int select_segments(mfcc_hip_handle *h, const float *d_in, int Wp, const unsigned char *d_voiced, const size_t *off,
-                    size_t n_segs, float *d_out, size_t *out_offsets) {
-    if (n_segs == 0 || off[n_segs] == off[0]) {
-        for (size_t k = 0; k <= n_segs && out_offsets; ++k) out_offsets[k] = 0;
+// the selection alone: counts the mask's bytes itself
+int select_segments(mfcc_hip_handle *h, const float *d_in, int Wp, const unsigned char *d_voiced, const SegSpan &sp,
+                    float *d_out, size_t *out_offsets) {
+    if (span_empty(sp)) {
+        for (size_t k = 0; k <= sp.n_segs && out_offsets; ++k) out_offsets[k] = 0;
         return MFCC_HIP_SUCCESS;
     }
     SelPlan pl;
-    const int rc = select_plan(h, off, n_segs, Wp, pl);
+    const int rc = select_plan(h, sp, Wp, pl);
     if (rc) return rc;
     return select_run(h, d_in, Wp, d_voiced, pl, false, d_out, out_offsets);
 }
@@ -1105,44 +1087,87 @@ int select_segments(mfcc_hip_handle *h, const float *d_in, int Wp, const unsigne
 // width of a float output row of this handle: the static row, times 1 + the delta order
 inline size_t out_width(const mfcc_hip_handle *h) { return row_width(h->r) * size_t(1 + h->delta_order); }
 
-// the dense float device path of a handle with deltas: the launch and the normalization into h->d_stat, then the
-// expanded rows into d_out, one segment per channel
-int launch_expanded(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch, void *d_out,
-                    size_t *n_frames) {
-    const size_t nf = count_frames(h->r, n), W = row_width(h->r);
-    if (nf == 0 || nch == 0 || !d_out) return launch(h, false, d_pcm, n, stride, nch, 0, d_out, n_frames);
-    DeviceGuard guard(h->device);
-    // with a normalization window the kernels' raw rows go to h->d_slide and the sliding pass writes the statics
-    const bool sl = sliding(h);
-    const int K = h->delta_order;
-    int rc = K ? ensure(h, &h->d_stat, &h->d_stat_bytes, nf * nch * W * sizeof(float) + 64) : MFCC_HIP_SUCCESS;
-    if (!rc && sl) rc = ensure(h, &h->d_slide, &h->d_slide_bytes, nf * nch * W * sizeof(float) + 64);
-    if (rc || (rc = scratch_acquire(h))) return rc;
-    float *stat = K ? static_cast<float *>(h->d_stat) : static_cast<float *>(d_out);
-    float *raw = sl ? static_cast<float *>(h->d_slide) : stat;
-    if ((rc = launch(h, false, d_pcm, n, stride, nch, 0, raw, n_frames))) return rc;
-    if (h->pcen_on && (rc = pcen_uniform(h, raw, int(W), 0, nch, nf, h->pcen))) return rc;
-    rc = sl ? sliding_uniform(h, raw, stat, int(W), 0, nch, nf, slide_args(h))
-            : normalize_uniform(h, stat, int(W), 0, nch, nf, h->norm);
-    if (rc) return rc;
-    if (K && (rc = deltas_uniform(h, stat, static_cast<float *>(d_out), int(W), 0, nch, nf, K, h->delta_window)))
-        return rc;
-    return scratch_release(h);
+// ---- the passes behind the float kernels.  Every float entry point of a handle runs them in
+// ONE order, enqueued by post_chain and nowhere else: the VAD decision on the raw rows, PCEN, the normalization (sliding or
+// per segment), deltas; the voiced-row selection (select_run) follows where the handle selects.
+// A handle with any of them is refused (UNSUPPORTED) by every fixed-point entry point and by the entry points that see
+// part of a stream: there is no fixed-point normalization, PCEN, delta or frame selection, and the float ones are
+// whole-segment passes.
+inline bool has_post(const mfcc_hip_handle *h) {
+    return h->norm != MFCC_HIP_NORMALIZE_NONE || h->pcen_on || h->delta_order || h->vad_mode;
 }
 
-// the dense float device path with the handle's normalization: the launch, then one segment per channel
+// Where the rows of a call go.  The kernels write `raw`; PCEN works on it in place; the sliding normalization moves it to
+// `stat`, the per-segment one works on `stat` (= raw) in place; deltas expand `stat` into `out`.  So `stat` is h->d_stat
+// iff the handle has a delta order (else out), and `raw` is h->d_slide iff its normalization slides (else stat).
+struct PostRoute {
+    float *raw, *stat, *out;
+    unsigned char *voiced;      // the decision's byte per row (selection only)
+    bool staged;                // some of them lie in the handle's scratch, acquired before the kernels: the caller
+                                // releases it behind the chain (a selection: select_run does)
+};
+
+// the rule, at `at` floats into h->d_stat / h->d_slide (already grown)
+inline PostRoute route_to(const mfcc_hip_handle *h, float *out, size_t at = 0) {
+    PostRoute rt{};
+    rt.out = out;
+    rt.stat = h->delta_order ? static_cast<float *>(h->d_stat) + at : out;
+    rt.raw = sliding(h) ? static_cast<float *>(h->d_slide) + at : rt.stat;
+    rt.staged = h->delta_order || sliding(h);
+    return rt;
+}
+
+// grows h->d_stat / h->d_slide for `rows` static rows where the rule needs them
+int stage_rows(mfcc_hip_handle *h, size_t rows) {
+    const size_t bytes = rows * row_width(h->r) * sizeof(float) + 64;
+    int rc = h->delta_order ? ensure(h, &h->d_stat, &h->d_stat_bytes, bytes) : MFCC_HIP_SUCCESS;
+    if (!rc && sliding(h)) rc = ensure(h, &h->d_slide, &h->d_slide_bytes, bytes);
+    return rc;
+}
+
+// the route of a device call of `rows` frames into d_out; select: every frame goes to h->d_final first and its byte to
+// h->d_voiced, select_run then moves the voiced rows to d_out
+int post_route(mfcc_hip_handle *h, size_t rows, float *d_out, bool select, PostRoute &rt) {
+    int rc = MFCC_HIP_SUCCESS;
+    if (select) {
+        rc = ensure(h, &h->d_final, &h->d_final_bytes, rows * out_width(h) * sizeof(float) + 64);
+        if (!rc) rc = ensure(h, &h->d_voiced, &h->d_voiced_bytes, rows + 64);
+    }
+    if (rc || (rc = stage_rows(h, rows))) return rc;
+    rt = route_to(h, select ? static_cast<float *>(h->d_final) : d_out);
+    rt.voiced = select ? static_cast<unsigned char *>(h->d_voiced) : nullptr;
+    rt.staged = rt.staged || select;
+    return rt.staged ? scratch_acquire(h) : MFCC_HIP_SUCCESS;
+}
+
+// the chain over the segments of sp; sel: the tiles of the selection that follows, whose counts the decision fills
+int post_chain(mfcc_hip_handle *h, const SegSpan &sp, const PostRoute &rt, const SelPlan *sel) {
+    const int W = int(row_width(h->r));
+    int rc;
+    if (sel && (rc = vad_decide(h, rt.raw, W, sp, vad_args(h), rt.voiced, *sel))) return rc;
+    if (h->pcen_on && (rc = pcen_pass(h, rt.raw, W, sp, h->pcen))) return rc;
+    if ((rc = sliding(h) ? sliding_pass(h, rt.raw, rt.stat, W, sp, slide_args(h))
+                         : normalize_pass(h, rt.stat, W, sp, h->norm)))
+        return rc;
+    if (h->delta_order && (rc = deltas_pass(h, rt.stat, rt.out, W, sp, h->delta_order, h->delta_window))) return rc;
+    return MFCC_HIP_SUCCESS;
+}
+
+// the dense float device path: the launch, then the chain with one segment per channel
 int launch_float_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo, void *d_out,
                      size_t *n_frames) {
-    if (h && (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->pcen_on) && halo)
-        return MFCC_HIP_ERROR_UNSUPPORTED;                                       // a shard of a longer stream
-    if (h && (h->delta_order || sliding(h))) return launch_expanded(h, d_pcm, n, stride, nch, d_out, n_frames);
-    int rc = launch(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
-    if (rc || (h->norm == MFCC_HIP_NORMALIZE_NONE && !h->pcen_on)) return rc;
+    // nothing behind the kernels (the headline of bench.py): the launch and nothing else
+    if (!h || !has_post(h))
+        return launch(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
+    if (halo) return MFCC_HIP_ERROR_UNSUPPORTED;                                 // a shard of a longer stream
+    const size_t nf = count_frames(h->r, n);
+    if (nf == 0 || nch == 0 || !d_out) return launch(h, false, d_pcm, n, stride, nch, 0, d_out, n_frames);
     DeviceGuard guard(h->device);
-    if (h->pcen_on &&
-        (rc = pcen_uniform(h, static_cast<float *>(d_out), int(row_width(h->r)), 0, nch, count_frames(h->r, n), h->pcen)))
-        return rc;
-    return normalize_uniform(h, static_cast<float *>(d_out), int(row_width(h->r)), 0, nch, count_frames(h->r, n), h->norm);
+    PostRoute rt;
+    int rc = post_route(h, nf * nch, static_cast<float *>(d_out), false, rt);
+    if (rc || (rc = launch(h, false, d_pcm, n, stride, nch, 0, rt.raw, n_frames))) return rc;
+    if ((rc = post_chain(h, span_uniform(0, nch, nf), rt, nullptr)) || !rt.staged) return rc;
+    return scratch_release(h);
 }
 
 // ---- host buffers in, host buffers out: the shape of the reference's own caller (software/main.c:100-177: file in,
@@ -1348,9 +1373,8 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     if (!out || cap < n_out) return MFCC_HIP_ERROR_BUFFER_SMALL;
     DeviceGuard guard(h->device);
     const size_t kChunkBytes = host_chunk_bytes();
-    // deltas: the static rows (W wide, 1 + K times narrower than the output rows) go to h->d_stat first
+    // deltas: the static rows are 1 + K times narrower than the output rows
     const int K = fixed ? 0 : h->delta_order;
-    const size_t W = row_width(h->r);
 
     // ---- the chunks
     std::vector<HostChunk> chunks;
@@ -1376,34 +1400,24 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
                                   (f1 - f0) * ncep, (c * nf + f0) * ncep});
             }
     }
-    // normalization: no row may leave the device before its channel's statistics exist.  Chunks of whole channels
-    // normalize their own rows before the copy back; frame-range chunks of long channels write into one device buffer of
-    // the whole result, which is normalized and copied back after the pipeline
-    // The same holds for deltas, which need the neighbouring frames of the channel: a chunk edge is not a channel edge.
-    // With deltas, chunks of whole channels write their static rows to h->d_stat and expand them into the chunk's
-    // output; frame-range chunks write every channel's static rows to h->d_stat, which is normalized and expanded into
-    // the whole result after the pipeline
-    const int norm = fixed ? MFCC_HIP_NORMALIZE_NONE : h->norm;
-    // PCEN is recursive along the channel: it takes the route of the per-segment normalization
-    const bool pcen = !fixed && h->pcen_on;
-    const bool whole = (norm != MFCC_HIP_NORMALIZE_NONE || K || pcen) && ch_bytes > kChunkBytes;
+    // The chain (post_chain) works on whole channels: no row may leave the device before its channel's statistics exist,
+    // deltas need the neighbouring frames and PCEN is recursive along the channel -- a chunk edge is not a channel edge.
+    // Chunks of whole channels run the chain on their own rows before the copy back; frame-range chunks of long channels
+    // write into one device buffer of the whole result (and its staging), which goes through the chain and is copied
+    // back after the pipeline
+    const bool post = !fixed && has_post(h);
+    const bool whole = post && ch_bytes > kChunkBytes;
     OutT *d_full = nullptr;
-    float *d_stat = nullptr;
     if (whole) {
         const int rc = ensure(h, &h->d_full, &h->d_full_bytes, n_out * sizeof(OutT) + 64);
         if (rc) return rc;
         d_full = static_cast<OutT *>(h->d_full);
     }
-    // a normalization window: the kernels' raw rows go to h->d_slide (sized like d_stat), the sliding pass reads them
-    const bool sl = !fixed && sliding(h);
-    float *d_slide = nullptr;
-    if (K || sl) {
-        const size_t stage = (whole ? nch : std::min(nch, kChunkBytes / (ch_bytes ? ch_bytes : 1) + 1)) * nf * W * sizeof(float) + 64;
-        int rc = K ? ensure(h, &h->d_stat, &h->d_stat_bytes, stage) : MFCC_HIP_SUCCESS;
-        if (!rc && sl) rc = ensure(h, &h->d_slide, &h->d_slide_bytes, stage);
+    // the staging of the chain (route_to's rule) holds the rows of one chunk, or of the whole result
+    const bool staged = post && (K || sliding(h));
+    if (staged) {
+        int rc = stage_rows(h, (whole ? nch : std::min(nch, kChunkBytes / (ch_bytes ? ch_bytes : 1) + 1)) * nf);
         if (rc || (rc = scratch_acquire(h))) return rc;
-        d_stat = static_cast<float *>(h->d_stat);
-        d_slide = static_cast<float *>(h->d_slide);
     }
     std::vector<PipeChunk> pc;
     pc.reserve(chunks.size());
@@ -1412,29 +1426,19 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     int rc = run_host_pipeline(h, pc, pcm, nch * ch_bytes, out, whole ? 0 : n_out * sizeof(OutT), [&](size_t i, void *d_in, void *d_out) {
         const HostChunk &c = chunks[i];
         void *rows = whole ? static_cast<void *>(d_full + c.out_off) : d_out;
-        if (K) rows = whole ? d_stat + c.out_off / size_t(1 + K) : d_stat;
-        void *stat_c = rows;                             // where this chunk's normalized statics go
-        if (sl) rows = whole ? d_slide + c.out_off / size_t(1 + K) : d_slide;
-        const int lrc = launch(h, fixed, d_in, c.n, c.stride, c.nch, c.halo, rows, nullptr, c.halo || c.frames != nf ? c.frames : 0);
-        if (lrc || whole) return lrc;
-        if (pcen) {
-            const int prc = pcen_uniform(h, reinterpret_cast<float *>(rows), int(W), 0, c.nch, nf, h->pcen);
-            if (prc) return prc;
+        PostRoute rt{};
+        if (post) {
+            // a frame-range chunk writes its rows of the whole result, W wide where they are statics
+            rt = route_to(h, static_cast<float *>(rows), whole ? c.out_off / size_t(1 + K) : 0);
+            rows = rt.raw;
         }
-        const int nrc = sl ? sliding_uniform(h, d_slide, reinterpret_cast<float *>(stat_c), int(W), 0, c.nch, nf, slide_args(h))
-                           : normalize_uniform(h, reinterpret_cast<float *>(rows), int(W), 0, c.nch, nf, norm);
-        if (nrc || !K) return nrc;
-        return deltas_uniform(h, d_stat, reinterpret_cast<float *>(d_out), int(W), 0, c.nch, nf, K, h->delta_window);
+        const int lrc = launch(h, fixed, d_in, c.n, c.stride, c.nch, c.halo, rows, nullptr, c.halo || c.frames != nf ? c.frames : 0);
+        if (lrc || whole || !post) return lrc;
+        return post_chain(h, span_uniform(0, c.nch, nf), rt, nullptr);
     });
-    if (rc || !whole) return rc ? rc : (K || sl ? scratch_release(h) : MFCC_HIP_SUCCESS);
-    float *stat = K ? d_stat : reinterpret_cast<float *>(d_full);
-    if (pcen && (rc = pcen_uniform(h, sl ? d_slide : stat, int(W), 0, nch, nf, h->pcen))) return rc;
-    rc = sl ? sliding_uniform(h, d_slide, stat, int(W), 0, nch, nf, slide_args(h))
-            : normalize_uniform(h, stat, int(W), 0, nch, nf, norm);
-    if (rc) return rc;
-    if (K && (rc = deltas_uniform(h, stat, reinterpret_cast<float *>(d_full), int(W), 0, nch, nf, K, h->delta_window)))
-        return rc;
-    if ((K || sl) && (rc = scratch_release(h))) return rc;
+    if (rc || !whole) return rc ? rc : (staged ? scratch_release(h) : MFCC_HIP_SUCCESS);
+    if ((rc = post_chain(h, span_uniform(0, nch, nf), route_to(h, reinterpret_cast<float *>(d_full)), nullptr))) return rc;
+    if (staged && (rc = scratch_release(h))) return rc;
     HIP_TRY(h, hipMemcpyAsync(out, d_full, n_out * sizeof(OutT), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MFCC_HIP_SUCCESS;
@@ -1645,97 +1649,37 @@ int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm,
     return scratch_release(h);
 }
 
-// ... and the handle's normalization over the dense result, one segment per utterance (float contract only: the
-// public fixed-point entry points refuse a normalizing handle)
-template <typename OutT>
-int process_ragged_dev_static(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
-                              OutT *d_out, size_t cap, size_t *frame_offsets) {
-    const int rc = process_ragged_dev_raw<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
-    if (rc || fixed || (h->norm == MFCC_HIP_NORMALIZE_NONE && !h->pcen_on) || n_utt == 0) return rc;
-    DeviceGuard guard(h->device);
-    if (h->pcen_on) {
-        const int prc = pcen_segments(h, reinterpret_cast<float *>(d_out), int(row_width(h->r)), frame_offsets, n_utt, h->pcen);
-        if (prc) return prc;
-    }
-    return normalize_segments(h, reinterpret_cast<float *>(d_out), int(row_width(h->r)), frame_offsets, n_utt, h->norm);
-}
-
-// ... and with MFCC_HIP_VAD_SELECT: the kernels, the decision on the raw rows, normalization and deltas over ALL frames
-// into h->d_final, then only the voiced rows to d_out; frame_offsets describes those.  Synchronizes (select_run)
-int process_ragged_dev_select(mfcc_hip_handle *h, const int16_t *d_pcm, const size_t *offsets, size_t n_utt, float *d_out,
-                              size_t cap, size_t *frame_offsets) {
-    size_t total = 0;
-    for (size_t u = 0; u < n_utt; ++u) {
-        if (offsets[u + 1] < offsets[u])            // refused by the call below
-            return process_ragged_dev_static<float>(h, false, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
-        total += count_frames(h->r, offsets[u + 1] - offsets[u]);
-    }
-    const size_t W = row_width(h->r), WO = out_width(h);
-    // nothing to write, or a buffer too small for every frame: the static call fills frame_offsets and gives the answer
-    if (total == 0 || !d_out || cap < total * WO)
-        return process_ragged_dev_static<float>(h, false, d_pcm, offsets, n_utt, total ? nullptr : d_out, 0, frame_offsets);
-    DeviceGuard guard(h->device);
-    const bool sl = sliding(h);
-    const int K = h->delta_order;
-    int rc = ensure(h, &h->d_final, &h->d_final_bytes, total * WO * sizeof(float) + 64);
-    if (!rc) rc = ensure(h, &h->d_voiced, &h->d_voiced_bytes, total + 64);
-    if (!rc && K) rc = ensure(h, &h->d_stat, &h->d_stat_bytes, total * W * sizeof(float) + 64);
-    if (!rc && sl) rc = ensure(h, &h->d_slide, &h->d_slide_bytes, total * W * sizeof(float) + 64);
-    if (rc || (rc = scratch_acquire(h))) return rc;
-    float *fin = static_cast<float *>(h->d_final);
-    float *stat = K ? static_cast<float *>(h->d_stat) : fin;
-    float *raw = sl ? static_cast<float *>(h->d_slide) : stat;
-    unsigned char *voiced = static_cast<unsigned char *>(h->d_voiced);
-    if ((rc = process_ragged_dev_raw<float>(h, false, d_pcm, offsets, n_utt, raw, total * W, frame_offsets))) return rc;
-    SelPlan pl;
-    if ((rc = select_plan(h, frame_offsets, n_utt, int(WO), pl))) return rc;
-    if ((rc = vad_decide(h, raw, int(W), frame_offsets, n_utt, vad_args(h), voiced, pl))) return rc;
-    if (h->pcen_on && (rc = pcen_segments(h, raw, int(W), frame_offsets, n_utt, h->pcen))) return rc;   // after the decision
-    rc = sl ? sliding_segments(h, raw, stat, int(W), frame_offsets, n_utt, slide_args(h))
-            : normalize_segments(h, stat, int(W), frame_offsets, n_utt, h->norm);
-    if (rc) return rc;
-    if (K && (rc = deltas_segments(h, stat, fin, int(W), frame_offsets, n_utt, K, h->delta_window))) return rc;
-    return select_run(h, fin, int(WO), voiced, pl, true, d_out, frame_offsets);
-}
-
-// ... and with deltas: the static rows go to h->d_stat, then the expanded rows to d_out, one segment per utterance
+// ... and the chain over the result, one segment per utterance (float contract only: the public fixed-point entry points
+// refuse a handle with a pass).  A handle that stages (deltas, a normalization window, MFCC_HIP_VAD_SELECT) has its kernels
+// write into the staging, which takes the frame count first.  With MFCC_HIP_VAD_SELECT every frame goes through the chain
+// into h->d_final, then only the voiced rows to d_out; frame_offsets describes those, and the call synchronizes (select_run)
 template <typename OutT>
 int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
                        OutT *d_out, size_t cap, size_t *frame_offsets) {
-    if (h && !fixed && h->vad_mode && offsets && frame_offsets && std::is_same<OutT, float>::value)
-        return process_ragged_dev_select(h, d_pcm, offsets, n_utt, reinterpret_cast<float *>(d_out), cap, frame_offsets);
-    if (!h || fixed || !(h->delta_order || sliding(h)) || !offsets || !frame_offsets)
-        return process_ragged_dev_static<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
+    if (!h || fixed || !has_post(h) || !offsets || !frame_offsets)
+        return process_ragged_dev_raw<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
+    const bool sel = h->vad_mode != MFCC_HIP_VAD_OFF, staged = sel || h->delta_order || sliding(h);
+    const size_t W = row_width(h->r), WO = out_width(h);
     size_t total = 0;
-    for (size_t u = 0; u < n_utt; ++u) {
+    for (size_t u = 0; staged && u < n_utt; ++u) {
         if (offsets[u + 1] < offsets[u])            // refused by the call below
-            return process_ragged_dev_static<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
+            return process_ragged_dev_raw<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
         total += count_frames(h->r, offsets[u + 1] - offsets[u]);
     }
-    const size_t W = row_width(h->r);
-    // nothing to write, or a buffer too small: the static call fills frame_offsets and gives the answer
-    if (total == 0 || !d_out || cap < total * out_width(h))
-        return process_ragged_dev_static<OutT>(h, fixed, d_pcm, offsets, n_utt, total ? nullptr : d_out, 0, frame_offsets);
+    // nothing to write, or a buffer too small for every frame: the plain call fills frame_offsets and gives the answer
+    if (staged && (total == 0 || !d_out || cap < total * WO))
+        return process_ragged_dev_raw<OutT>(h, fixed, d_pcm, offsets, n_utt, total ? nullptr : d_out, 0, frame_offsets);
     DeviceGuard guard(h->device);
-    // with a normalization window the raw rows go to h->d_slide and the sliding pass writes the statics
-    const bool sl = sliding(h);
-    const int K = h->delta_order;
-    int rc = K ? ensure(h, &h->d_stat, &h->d_stat_bytes, total * W * sizeof(float) + 64) : MFCC_HIP_SUCCESS;
-    if (!rc && sl) rc = ensure(h, &h->d_slide, &h->d_slide_bytes, total * W * sizeof(float) + 64);
-    if (rc || (rc = scratch_acquire(h))) return rc;
-    float *stat = K ? static_cast<float *>(h->d_stat) : reinterpret_cast<float *>(d_out);
-    if (sl) {
-        float *raw = static_cast<float *>(h->d_slide);
-        if ((rc = process_ragged_dev_raw<float>(h, false, d_pcm, offsets, n_utt, raw, total * W, frame_offsets))) return rc;
-        if (h->pcen_on && (rc = pcen_segments(h, raw, int(W), frame_offsets, n_utt, h->pcen))) return rc;
-        if ((rc = sliding_segments(h, raw, stat, int(W), frame_offsets, n_utt, slide_args(h)))) return rc;
-    } else if ((rc = process_ragged_dev_static<float>(h, false, d_pcm, offsets, n_utt, stat, total * W, frame_offsets))) {
+    PostRoute rt;
+    int rc = post_route(h, total, reinterpret_cast<float *>(d_out), sel, rt);
+    if (rc || (rc = process_ragged_dev_raw<float>(h, false, d_pcm, offsets, n_utt, rt.raw, staged ? total * W : cap, frame_offsets)))
         return rc;
-    }
-    if (K && (rc = deltas_segments(h, stat, reinterpret_cast<float *>(d_out), int(W), frame_offsets, n_utt, K,
-                                   h->delta_window)))
-        return rc;
-    return scratch_release(h);
+    const SegSpan sp = span_offsets(frame_offsets, n_utt);
+    SelPlan pl;
+    if (sel && (rc = select_plan(h, sp, int(WO), pl))) return rc;
+    if ((rc = post_chain(h, sp, rt, sel ? &pl : nullptr))) return rc;
+    if (sel) return select_run(h, rt.out, int(WO), rt.voiced, pl, true, reinterpret_cast<float *>(d_out), frame_offsets);
+    return rt.staged ? scratch_release(h) : MFCC_HIP_SUCCESS;
 }
 
 // Host buffers: the corpus goes to the device in ONE copy (the span offsets[0] .. offsets[n_utt] as it lies), runs through
@@ -2114,10 +2058,7 @@ int mfcc_hip_process_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_
 
 int mfcc_hip_process_fixed_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_t nch,
                                int16_t *out, size_t cap, size_t *n_frames) {
-    if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
-    if (h && h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;                          // ... nor PCEN
-    if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
-    if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... nor frame selection
+    if (h && has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
     return process_host<int16_t>(h, true, pcm, n, nch, out, cap, n_frames);
 }
 
@@ -2128,10 +2069,7 @@ int mfcc_hip_process_ragged_i16(mfcc_hip_handle *h, const int16_t *pcm, const si
 
 int mfcc_hip_process_ragged_fixed_i16(mfcc_hip_handle *h, const int16_t *pcm, const size_t *offsets, size_t n_utt,
                                       int16_t *out, size_t cap, size_t *frame_offsets) {
-    if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
-    if (h && h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;                          // ... nor PCEN
-    if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
-    if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... nor frame selection
+    if (h && has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
     return process_ragged<int16_t>(h, true, pcm, offsets, n_utt, out, cap, frame_offsets);
 }
 
@@ -2143,10 +2081,7 @@ int mfcc_hip_process_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const
 
 int mfcc_hip_process_ragged_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const size_t *offsets, size_t n_utt,
                                           void *d_out, size_t cap, size_t *frame_offsets) {
-    if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
-    if (h && h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;                          // ... nor PCEN
-    if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
-    if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... nor frame selection
+    if (h && has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
     return process_ragged_dev<int16_t>(h, true, static_cast<const int16_t *>(d_pcm), offsets, n_utt,
                                        static_cast<int16_t *>(d_out), cap, frame_offsets);
 }
@@ -2159,17 +2094,14 @@ int mfcc_hip_process_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, si
 
 int mfcc_hip_process_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride,
                                    size_t nch, int halo, void *d_out, size_t *n_frames) {
-    if (h && h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // no fixed-point normalization
-    if (h && h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;                          // ... nor PCEN
-    if (h && h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                      // ... nor deltas
-    if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... nor frame selection
+    if (h && has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
     return launch(h, true, d_pcm, n, stride, nch, halo, d_out, n_frames);
 }
 
 int mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n, size_t stride,
                       size_t nch, void *d_out, int warmup, int iters, float *avg_ms) {
     if (!h || iters < 1 || warmup < 0 || !avg_ms) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (fixed && (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->pcen_on)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (fixed && has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;        // a dense result cannot hold rows of different counts
     DeviceGuard guard(h->device);
     // what process_*_dev enqueues: with normalization or deltas on, the float launch and the passes behind it
@@ -2214,14 +2146,13 @@ int mfcc_hip_normalize_dev(mfcc_hip_handle *h, void *d_rows, int row_width, cons
                            int mode) {
     if (!h || mode < MFCC_HIP_NORMALIZE_NONE || mode > MFCC_HIP_NORMALIZE_MEAN_VAR) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (row_width < 1 || row_width > mfcc_norm::kMaxWidth || (n_segs && !seg_offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    for (size_t k = 0; k < n_segs; ++k)
-        if (seg_offsets[k + 1] < seg_offsets[k]) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!offsets_ok(seg_offsets, n_segs)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (n_segs && seg_offsets[n_segs] > seg_offsets[0] &&
         (!d_rows || (reinterpret_cast<uintptr_t>(d_rows) & 3)))
         return MFCC_HIP_ERROR_INVALID_PARAM;
     if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0) return MFCC_HIP_SUCCESS;
     DeviceGuard guard(h->device);
-    return normalize_segments(h, static_cast<float *>(d_rows), row_width, seg_offsets, n_segs, mode);
+    return normalize_pass(h, static_cast<float *>(d_rows), row_width, span_offsets(seg_offsets, n_segs), mode);
 }
 
 int mfcc_hip_pcen_defaults(mfcc_hip_pcen *p) {
@@ -2258,14 +2189,13 @@ int mfcc_hip_pcen_dev(mfcc_hip_handle *h, void *d_rows, int row_width, const siz
                       const mfcc_hip_pcen *p) {
     if (!h || !pcen_ok(p)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (row_width < 1 || row_width > mfcc_pcen::kMaxWidth || (n_segs && !seg_offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    for (size_t k = 0; k < n_segs; ++k)
-        if (seg_offsets[k + 1] < seg_offsets[k]) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!offsets_ok(seg_offsets, n_segs)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (n_segs && seg_offsets[n_segs] > seg_offsets[0] &&
         (!d_rows || (reinterpret_cast<uintptr_t>(d_rows) & 3)))
         return MFCC_HIP_ERROR_INVALID_PARAM;
     if (n_segs == 0) return MFCC_HIP_SUCCESS;
     DeviceGuard guard(h->device);
-    return pcen_segments(h, static_cast<float *>(d_rows), row_width, seg_offsets, n_segs, pcen_prm(*p));
+    return pcen_pass(h, static_cast<float *>(d_rows), row_width, span_offsets(seg_offsets, n_segs), pcen_prm(*p));
 }
 
 int mfcc_hip_set_normalize_window(mfcc_hip_handle *h, int window, int min_window, int center) {
@@ -2288,21 +2218,17 @@ int mfcc_hip_normalize_sliding_dev(mfcc_hip_handle *h, const void *d_in, int row
     if (window < 1 || window > MFCC_HIP_MAX_NORMALIZE_WINDOW || min_window < 1 || min_window > window || center < 0 ||
         center > 1)
         return MFCC_HIP_ERROR_INVALID_PARAM;
-    for (size_t k = 0; k < n_segs; ++k)
-        if (seg_offsets[k + 1] < seg_offsets[k]) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!offsets_ok(seg_offsets, n_segs)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0 || seg_offsets[n_segs] == seg_offsets[0]) return MFCC_HIP_SUCCESS;
     if (!d_in || !d_out || (reinterpret_cast<uintptr_t>(d_in) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
         return MFCC_HIP_ERROR_INVALID_PARAM;
     // the byte ranges the pass reads and writes must not overlap: a window reaches into rows already written
     const size_t r0 = seg_offsets[0], r1 = seg_offsets[n_segs], row_bytes = size_t(row_width) * sizeof(float);
-    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(d_in) + r0 * row_bytes;
-    const uintptr_t in_hi = reinterpret_cast<uintptr_t>(d_in) + r1 * row_bytes;
-    const uintptr_t out_lo = reinterpret_cast<uintptr_t>(d_out) + r0 * row_bytes;
-    const uintptr_t out_hi = reinterpret_cast<uintptr_t>(d_out) + r1 * row_bytes;
-    if (in_lo < out_hi && out_lo < in_hi) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (ranges_overlap(d_in, r0 * row_bytes, r1 * row_bytes, d_out, r0 * row_bytes, r1 * row_bytes))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
     DeviceGuard guard(h->device);
-    return sliding_segments(h, static_cast<const float *>(d_in), static_cast<float *>(d_out), row_width, seg_offsets,
-                            n_segs, SlideArgs{mode, window, min_window, center});
+    return sliding_pass(h, static_cast<const float *>(d_in), static_cast<float *>(d_out), row_width,
+                        span_offsets(seg_offsets, n_segs), SlideArgs{mode, window, min_window, center});
 }
 
 int mfcc_hip_set_deltas(mfcc_hip_handle *h, int order, int window) {
@@ -2319,21 +2245,18 @@ int mfcc_hip_deltas_dev(mfcc_hip_handle *h, const void *d_in, int width, void *d
     if (!h || width < 1 || width > mfcc_delta::kMaxWidth || order < 1 || order > 2 || window < 1 ||
         window > MFCC_HIP_MAX_DELTA_WINDOW || (n_segs && !seg_offsets))
         return MFCC_HIP_ERROR_INVALID_PARAM;
-    for (size_t k = 0; k < n_segs; ++k)
-        if (seg_offsets[k + 1] < seg_offsets[k]) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!offsets_ok(seg_offsets, n_segs)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (n_segs == 0 || seg_offsets[n_segs] == seg_offsets[0]) return MFCC_HIP_SUCCESS;
     if (!d_in || !d_out || (reinterpret_cast<uintptr_t>(d_in) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
         return MFCC_HIP_ERROR_INVALID_PARAM;
     // the byte ranges the pass reads and writes must not overlap
-    const size_t r0 = seg_offsets[0], r1 = seg_offsets[n_segs], W = size_t(width), WO = W * size_t(1 + order);
-    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(d_in) + r0 * W * sizeof(float);
-    const uintptr_t in_hi = reinterpret_cast<uintptr_t>(d_in) + r1 * W * sizeof(float);
-    const uintptr_t out_lo = reinterpret_cast<uintptr_t>(d_out) + r0 * WO * sizeof(float);
-    const uintptr_t out_hi = reinterpret_cast<uintptr_t>(d_out) + r1 * WO * sizeof(float);
-    if (in_lo < out_hi && out_lo < in_hi) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const size_t r0 = seg_offsets[0], r1 = seg_offsets[n_segs];
+    const size_t in_bytes = size_t(width) * sizeof(float), out_bytes = in_bytes * size_t(1 + order);
+    if (ranges_overlap(d_in, r0 * in_bytes, r1 * in_bytes, d_out, r0 * out_bytes, r1 * out_bytes))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
     DeviceGuard guard(h->device);
-    return deltas_segments(h, static_cast<const float *>(d_in), static_cast<float *>(d_out), width, seg_offsets, n_segs,
-                           order, window);
+    return deltas_pass(h, static_cast<const float *>(d_in), static_cast<float *>(d_out), width,
+                       span_offsets(seg_offsets, n_segs), order, window);
 }
 
 int mfcc_hip_set_vad(mfcc_hip_handle *h, int mode, int column, float energy_threshold, float energy_mean_scale,
@@ -2358,18 +2281,14 @@ int mfcc_hip_vad_dev(mfcc_hip_handle *h, const void *d_rows, int row_width, int 
     if (!h || row_width < 1 || row_width > mfcc_vad::kMaxWidth || (n_segs && !seg_offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (!vad_args_ok(row_width, column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold))
         return MFCC_HIP_ERROR_INVALID_PARAM;
-    for (size_t k = 0; k < n_segs; ++k)
-        if (seg_offsets[k + 1] < seg_offsets[k]) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!offsets_ok(seg_offsets, n_segs)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (n_segs == 0 || seg_offsets[n_segs] == seg_offsets[0]) return MFCC_HIP_SUCCESS;
     if (!d_rows || !d_voiced || (reinterpret_cast<uintptr_t>(d_rows) & 3)) return MFCC_HIP_ERROR_INVALID_PARAM;
     // the rows read and the bytes written must not overlap
     const size_t r0 = seg_offsets[0], r1 = seg_offsets[n_segs], row_bytes = size_t(row_width) * sizeof(float);
-    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(d_rows) + r0 * row_bytes;
-    const uintptr_t in_hi = reinterpret_cast<uintptr_t>(d_rows) + r1 * row_bytes;
-    const uintptr_t out_lo = reinterpret_cast<uintptr_t>(d_voiced) + r0, out_hi = reinterpret_cast<uintptr_t>(d_voiced) + r1;
-    if (in_lo < out_hi && out_lo < in_hi) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (ranges_overlap(d_rows, r0 * row_bytes, r1 * row_bytes, d_voiced, r0, r1)) return MFCC_HIP_ERROR_INVALID_PARAM;
     DeviceGuard guard(h->device);
-    return vad_segments(h, static_cast<const float *>(d_rows), row_width, seg_offsets, n_segs,
+    return vad_segments(h, static_cast<const float *>(d_rows), row_width, span_offsets(seg_offsets, n_segs),
                         VadArgs{column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold},
                         static_cast<unsigned char *>(d_voiced));
 }
@@ -2378,23 +2297,20 @@ int mfcc_hip_select_dev(mfcc_hip_handle *h, const void *d_in, int row_width, con
                         size_t n_segs, void *d_out, size_t out_capacity_rows, size_t *out_offsets) {
     if (!h || row_width < 1 || row_width > mfcc_vad::kMaxSelectWidth || (n_segs && (!seg_offsets || !out_offsets)))
         return MFCC_HIP_ERROR_INVALID_PARAM;
-    for (size_t k = 0; k < n_segs; ++k)
-        if (seg_offsets[k + 1] < seg_offsets[k]) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!offsets_ok(seg_offsets, n_segs)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (n_segs == 0 || seg_offsets[n_segs] == seg_offsets[0])
-        return select_segments(h, nullptr, row_width, nullptr, seg_offsets, n_segs, nullptr, out_offsets);
+        return select_segments(h, nullptr, row_width, nullptr, span_offsets(seg_offsets, n_segs), nullptr, out_offsets);
     if (!d_in || !d_voiced || !d_out || (reinterpret_cast<uintptr_t>(d_in) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
         return MFCC_HIP_ERROR_INVALID_PARAM;
     // the rows and the mask read must not overlap the rows that may be written (every row may be voiced)
     const size_t r0 = seg_offsets[0], r1 = seg_offsets[n_segs], row_bytes = size_t(row_width) * sizeof(float);
-    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(d_in) + r0 * row_bytes;
-    const uintptr_t in_hi = reinterpret_cast<uintptr_t>(d_in) + r1 * row_bytes;
-    const uintptr_t v_lo = reinterpret_cast<uintptr_t>(d_voiced) + r0, v_hi = reinterpret_cast<uintptr_t>(d_voiced) + r1;
-    const uintptr_t out_lo = reinterpret_cast<uintptr_t>(d_out), out_hi = out_lo + (r1 - r0) * row_bytes;
-    if ((in_lo < out_hi && out_lo < in_hi) || (v_lo < out_hi && out_lo < v_hi)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (ranges_overlap(d_in, r0 * row_bytes, r1 * row_bytes, d_out, 0, (r1 - r0) * row_bytes) ||
+        ranges_overlap(d_voiced, r0, r1, d_out, 0, (r1 - r0) * row_bytes))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
     if (out_capacity_rows < r1 - r0) return MFCC_HIP_ERROR_BUFFER_SMALL;
     DeviceGuard guard(h->device);
     return select_segments(h, static_cast<const float *>(d_in), row_width, static_cast<const unsigned char *>(d_voiced),
-                           seg_offsets, n_segs, static_cast<float *>(d_out), out_offsets);
+                           span_offsets(seg_offsets, n_segs), static_cast<float *>(d_out), out_offsets);
 }
 
 const char *mfcc_hip_kernel_name(const mfcc_hip_handle *h, int fixed) {
@@ -3165,7 +3081,7 @@ int mfcc_hip_bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, mfcc_h
     *out = nullptr;
     if (h->destroy_pending || !n_streams) return MFCC_HIP_ERROR_INVALID_PARAM;
     // what mfcc_hip_stream_create refuses: per-call statistics, lookahead and whole-segment thresholds of a stream
-    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode || h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     return bank_create(h, fixed, n_streams, MFCC_HIP_NORMALIZE_NONE, 0, 0, 0, out);
 }
@@ -3176,7 +3092,7 @@ int mfcc_hip_bank_create_online(mfcc_hip_handle *h, size_t n_streams, int normal
     *out = nullptr;
     if (h->destroy_pending || !n_streams) return MFCC_HIP_ERROR_INVALID_PARAM;
     // the bank's settings are its own: the handle must be a raw one, and able to run the float path
-    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode || h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (normalize != MFCC_HIP_NORMALIZE_NONE && normalize != MFCC_HIP_NORMALIZE_MEAN && normalize != MFCC_HIP_NORMALIZE_MEAN_VAR)
         return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -3194,7 +3110,7 @@ int mfcc_hip_bank_create_online_pcen(mfcc_hip_handle *h, size_t n_streams, const
     *out = nullptr;
     if (h->destroy_pending || !n_streams || !pcen_ok(p)) return MFCC_HIP_ERROR_INVALID_PARAM;
     // the bank's settings are its own: a raw log-mel handle that can run the float path
-    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->delta_order || h->vad_mode || h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (!is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (normalize != MFCC_HIP_NORMALIZE_NONE && normalize != MFCC_HIP_NORMALIZE_MEAN && normalize != MFCC_HIP_NORMALIZE_MEAN_VAR)
@@ -3437,10 +3353,6 @@ int gate_wins_upload(mfcc_hip_handle *h, mfcc_gate::Wins &w, size_t table_ll, mf
     HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
     pd->in_flight = true;
     return MFCC_HIP_SUCCESS;
-}
-
-inline bool ranges_overlap(uintptr_t a_lo, uintptr_t a_hi, uintptr_t b_lo, uintptr_t b_hi) {
-    return a_lo < b_hi && b_lo < a_hi;
 }
 
 inline unsigned gate_grid(const mfcc_hip_handle *h, long long want) {
