@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bank_plan.hpp"
 #include "kernel_normalize.hpp"
 
 namespace mfcc_pcen {
@@ -157,12 +158,7 @@ __global__ __launch_bounds__(kThreads) void pcen_apply_kernel(float *__restrict_
 // ---- the online bank's form (mfcc_hip_bank_create_online_pcen).  State per (stream,
 // column): the carry C of the tile in progress and its local smoother L, state[stream][2][W].  The stream's frame
 // count `seen` (mirrored on the host) gives the slot of its first fresh row; with seen = 0 nothing of the state is read.
-// The nf fresh rows of `stream` start at row row0 of `raw`; their PCEN goes to row out_row of `dst` (dst == raw: in place)
-struct OnlineRec {
-    long long stream, row0, seen, nf, out_row;
-};
-constexpr int kOnlineRecLL = 5;                            // a record as long longs in the pinned descriptor pool
-
+// One OnlineRec (bank_plan.hpp) per stream with fresh rows.
 // one thread per (record, column): the fresh rows in order, through element() with the slot's A_k (decay: A_k in HBM,
 // the slot differs from lane to lane); L starts from 0 at slot 0, C is latched from M at slot kTile - 1 -- the values
 // pcen_carry_kernel and pcen_apply_kernel give the same frames of a one-shot segment

@@ -31,22 +31,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bank_plan.hpp"                       // Rec, and the plan that fills it
+
 namespace mfcc_bank {
 
 constexpr int kThreads = 256;
-
-// one stream of a push / flush / reset; `src` is the offset of its chunk in the samples buffer
-struct Rec {
-    long long stream, src, n_new, pending, nf;
-};
-constexpr int kRecLL = 5;                      // a record as long longs in the pinned descriptor pool
-
-// The plan of one stream: frames a push of n_new samples completes and what stays pending (always < nfft)
-__host__ __device__ inline void plan(size_t pending, size_t n_new, size_t nfft, size_t hop, size_t &nf, size_t &pending_after) {
-    const size_t total = pending + n_new;
-    nf = total >= nfft ? (total - nfft) / hop + 1 : 0;
-    pending_after = total - nf * hop;
-}
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 struct __attribute__((packed, aligned(2))) Unaligned16 {

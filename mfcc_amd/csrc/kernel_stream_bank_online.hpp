@@ -35,21 +35,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bank_plan.hpp"                                   // Rec (one struct for the three passes), kNoEdge
 #include "kernel_normalize_sliding.hpp"
 
 namespace mfcc_online {
 
 constexpr int kThreads = 256;
 constexpr int kLdsFloats = 4096;                           // 16 KB of LDS per workgroup, as kernel_deltas.hpp
-constexpr long long kNoEdge = 0x7fffffffffffffffLL;        // `last` of a stream that goes on
-
-// cmvn:   rows [t0, cnt) of `stream` (cnt = t1), row `seen` is written to row out_row of y
-// deltas: rows [t0, t0 + cnt) of `stream` are emitted, row t0 to row out_row of y; indices clamp to [0, last]
-// carry:  the nf fresh rows of `stream`
-struct Rec {
-    long long stream, row0, seen, nf, t0, cnt, out_row, last;
-};
-constexpr int kRecLL = 8;                                  // a record as long longs in the pinned descriptor pool
 
 // emitted rows per tile of the delta kernel: K = 1: (g + 2L) W static floats; K = 2: (g + 2L) W static and
 // (g + 2Nd) W delta floats.  At least 8 for every W <= 64, Nd <= 8

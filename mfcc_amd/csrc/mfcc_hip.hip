@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/mfcc_hip.h"
+#include "bank_plan.hpp"
 #include "kernels_generic.hpp"
 #include "kernel_fixed512.hpp"
 #include "kernel_fused1024.hpp"
@@ -2598,421 +2599,190 @@ struct mfcc_hip_bank {
     mfcc_hip_handle *h = nullptr;
     bool fixed = false;
     size_t n = 0;                        // streams
+    mfcc_bank::Settings s{};             // what the plans of a push, flush or reset read (bank_plan.hpp)
     int16_t *d_state = nullptr;          // [n][frame_len]
     std::vector<size_t> pending, after;  // the host mirror and the plan of the push in progress
     // staging of the host-buffer entries (mfcc_hip_bank_push, mfcc_hip_bank_flush): the flat samples and the rows
     void *st_in = nullptr, *st_out = nullptr;
     size_t st_in_bytes = 0, st_out_bytes = 0;
     // online bank (mfcc_hip_bank_create_online; kernel_stream_bank_online.hpp): causal CMVN
-    // over `window` rows and deltas of `order` x `dwin`, lag = order * dwin.  seen[u] = frames computed since reset,
+    // over `window` rows and deltas of s.order x `dwin`, lag s.L = order * dwin.  seen[u] = frames computed since reset,
     // held[u] <= lag = finished rows not yet returned; both depend on chunk lengths only
-    bool online = false;
-    int norm = MFCC_HIP_NORMALIZE_NONE, window = 0, run = 0, depth = 0, order = 0, dwin = 0, lag = 0;
+    int norm = MFCC_HIP_NORMALIZE_NONE, window = 0, depth = 0, dwin = 0;
     float *d_ring = nullptr;             // [n][depth][W] raw rows (norm != NONE)
     float *d_tail = nullptr;             // [n][2 lag][W] static rows (lag > 0)
     std::vector<size_t> seen, held, held_after, raw_fo;
     // PCEN of an online bank (mfcc_hip_bank_create_online_pcen): the parameters and, on
     // the device, [n][2][W] carry and local smoother per (stream, column), then the decay table A_k
-    bool pcen = false;
     mfcc_pcen::Prm pcen_prm{};
     float *d_pcen = nullptr;
 };
 
 namespace {
 
-// frame_offsets (n + 1) and, where given, pending_after (n) of a push of chunks offsets[u] .. offsets[u + 1]; on
-// INVALID_PARAM frame_offsets is filled up to the offending stream
-int bank_plan_raw(size_t flen, size_t hop, const size_t *pending, const size_t *offsets, size_t n, size_t *frame_offsets,
-                  size_t *pending_after) {
-    frame_offsets[0] = 0;
-    for (size_t u = 0; u < n; ++u) {
-        if (offsets[u + 1] < offsets[u] || pending[u] >= flen) return MFCC_HIP_ERROR_INVALID_PARAM;
-        size_t nf, pa;
-        mfcc_bank::plan(pending[u], offsets[u + 1] - offsets[u], flen, hop, nf, pa);
-        frame_offsets[u + 1] = frame_offsets[u] + nf;
-        if (pending_after) pending_after[u] = pa;
-    }
-    return MFCC_HIP_SUCCESS;
+inline mfcc_bank::State bank_state(const mfcc_hip_bank *b) {
+    return mfcc_bank::State{b->pending.data(), b->seen.data(), b->held.data()};
 }
 
-// The same for sessions that return row t once row t + lag is known: frame_offsets counts the rows RETURNED.  held may
-// be NULL with lag = 0; raw_offsets (n + 1, may be NULL) gets the running sum of the frames computed
-int bank_plan_lagged(size_t flen, size_t hop, size_t lag, const size_t *pending, const size_t *held, const size_t *offsets,
-                     size_t n, size_t *frame_offsets, size_t *pending_after, size_t *held_after, size_t *raw_offsets) {
-    frame_offsets[0] = 0;
-    if (raw_offsets) raw_offsets[0] = 0;
-    for (size_t u = 0; u < n; ++u) {
-        const size_t hu = held ? held[u] : 0;
-        if (offsets[u + 1] < offsets[u] || pending[u] >= flen || hu > lag) return MFCC_HIP_ERROR_INVALID_PARAM;
-        size_t nf, pa;
-        mfcc_bank::plan(pending[u], offsets[u + 1] - offsets[u], flen, hop, nf, pa);
-        const size_t emitted = hu + nf > lag ? hu + nf - lag : 0;
-        frame_offsets[u + 1] = frame_offsets[u] + emitted;
-        if (raw_offsets) raw_offsets[u + 1] = raw_offsets[u] + nf;
-        if (pending_after) pending_after[u] = pa;
-        if (held_after) held_after[u] = hu + nf - emitted;
-    }
-    return MFCC_HIP_SUCCESS;
-}
-
-inline size_t bank_row_width(const mfcc_hip_bank *b) { return row_width(b->h->r) * size_t(1 + b->order); }
-
-// descriptors at the front of h->d_out (what follows them there is the row scratch of a mixed push)
-int bank_desc_upload(mfcc_hip_handle *h, mfcc_hip_handle::PinnedDesc *pd, size_t n_ll) {
-    HIP_TRY(h, hipMemcpyAsync(h->d_out, pd->p, n_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+// n_ll descriptors of pd on their way to d_dst, on the handle's stream
+int desc_upload(mfcc_hip_handle *h, mfcc_hip_handle::PinnedDesc *pd, size_t n_ll, void *d_dst) {
+    HIP_TRY(h, hipMemcpyAsync(d_dst, pd->p, n_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
     pd->in_flight = true;
     return MFCC_HIP_SUCCESS;
 }
 
-// The push proper: device buffers, asynchronous on the handle's stream.  Stream u's chunk is d_samples[offsets[u] - shift ..
-// offsets[u + 1] - shift).  Nothing is consumed unless MFCC_HIP_SUCCESS is returned.
+// The scratch buffer *buf of the handle grown to `want` bytes and taken (scratch_acquire), the descriptors of pd (none
+// without one) on their way to its front
+int desc_stage(mfcc_hip_handle *h, void **buf, size_t *have, size_t want, mfcc_hip_handle::PinnedDesc *pd, size_t n_ll) {
+    int rc;
+    if ((rc = ensure(h, buf, have, want))) return rc;
+    if ((rc = scratch_acquire(h))) return rc;
+    return pd ? desc_upload(h, pd, n_ll, *buf) : MFCC_HIP_SUCCESS;
+}
+
+// a record table of the descriptor block at the front of h->d_out
+template <class T>
+inline const T *desc_table(const mfcc_hip_handle *h, const mfcc_bank::Table &t) {
+    return reinterpret_cast<const T *>(static_cast<const long long *>(h->d_out) + t.off);
+}
+
 template <typename OutT>
-int bank_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const size_t *offsets, OutT *d_out, size_t cap,
+void bank_gather(mfcc_hip_handle *h, const mfcc_bank::Layout &l, const void *d_rows, void *y, int W) {
+    const unsigned blocks = (unsigned)std::min<size_t>(l.gather.n, size_t(h->n_cu) * 8);
+    hipLaunchKernelGGL(gather_rows_kernel<OutT>, dim3(blocks), dim3(256), 0, h->stream, static_cast<const OutT *>(d_rows),
+                       static_cast<OutT *>(y), desc_table<long long>(h, l.gather), (long long)l.gather.n, W);
+}
+
+// What follows the frame launch of a push or an end, on the handle's stream; y: the rows of the result.  A plain bank
+// gathers the rows of a mixed push.  An online bank runs PCEN over the fresh raw rows -- in place when CMVN or deltas
+// follow (the PCEN rows are what enters the ring and the tail), else straight to y -- then CMVN, the deltas and, in a
+// push, the carry into ring and tail (a flush resets instead)
+void bank_passes(mfcc_hip_bank *b, const mfcc_bank::Layout &l, void *y) {
+    mfcc_hip_handle *h = b->h;
+    const mfcc_bank::Settings &s = b->s;
+    const int W = int(s.W);
+    const size_t cap = size_t(h->n_cu) * 8;
+    float *d_raw = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + l.raw_off);
+    float *d_stat = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + l.stat_off), *out = static_cast<float *>(y);
+    if (!s.online()) {
+        if (l.gather.n) b->fixed ? bank_gather<int16_t>(h, l, d_raw, y, W) : bank_gather<float>(h, l, d_raw, y, W);
+        return;
+    }
+    if (l.pcen.n) {
+        const size_t blocks = std::min((l.pcen.n * s.W + mfcc_pcen::kThreads - 1) / mfcc_pcen::kThreads, cap);
+        hipLaunchKernelGGL(mfcc_pcen::online_pcen_kernel, dim3((unsigned)blocks), dim3(mfcc_pcen::kThreads), 0, h->stream, d_raw,
+                           s.post() ? d_raw : out, desc_table<mfcc_pcen::OnlineRec>(h, l.pcen), (long long)l.pcen.n, W,
+                           b->pcen_prm, static_cast<const float *>(b->d_pcen + b->n * 2 * s.W), b->d_pcen);
+    }
+    if (l.cmvn.n) {
+        const size_t G = size_t(mfcc_online::kThreads / W), blocks = std::min((l.cmvn.n + G - 1) / G, cap);
+        hipLaunchKernelGGL(mfcc_online::online_cmvn_kernel, dim3((unsigned)blocks), dim3(mfcc_online::kThreads), 0, h->stream,
+                           b->d_ring, d_raw, s.order ? d_stat : out, desc_table<mfcc_online::Rec>(h, l.cmvn),
+                           (long long)l.cmvn.n, W, b->window, b->depth, b->norm);
+    }
+    const float *stat = s.norm ? d_stat : d_raw;
+    if (l.delta.n)
+        hipLaunchKernelGGL(mfcc_online::online_deltas_kernel, dim3((unsigned)std::min(l.delta.n, cap)),
+                           dim3(mfcc_online::kThreads), 0, h->stream, b->d_tail, stat, out,
+                           desc_table<mfcc_online::Rec>(h, l.delta), (long long)l.delta.n, W, s.order, b->dwin,
+                           mfcc_delta::delta_scale(b->dwin));
+    if (l.carry.n)
+        hipLaunchKernelGGL(mfcc_online::online_carry_kernel, dim3((unsigned)std::min(l.carry.n, cap)),
+                           dim3(mfcc_online::kThreads), 0, h->stream, b->d_ring, b->d_tail, d_raw, stat,
+                           desc_table<mfcc_online::Rec>(h, l.carry), (long long)l.carry.n, W, b->depth, 2 * int(s.L));
+}
+
+// The push proper: device buffers, asynchronous on the handle's stream.  Stream u's chunk is d_samples[offsets[u] - shift ..
+// offsets[u + 1] - shift); cap counts elements of the bank's (expanded) rows.  The frame launch runs once over the work
+// buffer as [active] channels of nfmax frames: straight into d_out when a plain bank's streams are in lockstep, else
+// into the scratch behind the descriptors, and bank_passes follow.  Nothing is consumed unless MFCC_HIP_SUCCESS is returned
+int bank_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const size_t *offsets, void *d_out, size_t cap,
                  size_t *frame_offsets) {
     mfcc_hip_handle *h = b->h;
-    const size_t flen = size_t(h->r.frame_len), hop = size_t(h->r.hop), W = row_width(h->r), n = b->n;
-    int rc = bank_plan_raw(flen, hop, b->pending.data(), offsets, n, frame_offsets, b->after.data());
-    if (rc) return rc;
-    const size_t total_frames = frame_offsets[n];
-    if (total_frames && (!d_out || cap < total_frames * W)) return MFCC_HIP_ERROR_BUFFER_SMALL;
-    size_t n_rec = 0, n_active = 0, nfmax = 0, nfmin = ~size_t(0), max_total = 0;
-    for (size_t u = 0; u < n; ++u) {
-        const size_t n_new = offsets[u + 1] - offsets[u], nf = frame_offsets[u + 1] - frame_offsets[u];
-        if (!n_new) continue;                          // nothing of this stream changes (nf > 0 needs new samples)
-        ++n_rec;
-        if (!nf) continue;
-        ++n_active;
-        nfmax = std::max(nfmax, nf);
-        nfmin = std::min(nfmin, nf);
-        max_total = std::max(max_total, b->pending[u] + n_new);
-    }
-    if (!n_rec) return MFCC_HIP_SUCCESS;
-    if (!d_samples) return MFCC_HIP_ERROR_INVALID_PARAM;
-    DeviceGuard guard(h->device);
-    const bool lockstep = n_active && nfmin == nfmax;    // the frame kernels' [active][nf][row] IS the result
-    const size_t S = 1 + max_total;
-    // [0, 5 n_rec): the records, active streams first; [5 n_rec, 5 n_rec + 3 n_active): the row gather of a mixed push
-    const size_t rec_ll = mfcc_bank::kRecLL * n_rec, desc_ll = rec_ll + 3 * n_active;
-    static_assert(sizeof(mfcc_bank::Rec) == mfcc_bank::kRecLL * sizeof(long long), "record layout");
-    mfcc_hip_handle::PinnedDesc *pd = nullptr;
-    if ((rc = desc_acquire(h, desc_ll, &pd))) return rc;
-    auto *rec = reinterpret_cast<mfcc_bank::Rec *>(pd->p);
-    long long *gat = pd->p + rec_ll;
-    size_t a = 0, q = n_active;
-    for (size_t u = 0; u < n; ++u) {
-        const size_t n_new = offsets[u + 1] - offsets[u], nf = frame_offsets[u + 1] - frame_offsets[u];
-        if (!n_new) continue;
-        const mfcc_bank::Rec c{(long long)u, (long long)(offsets[u] - shift), (long long)n_new, (long long)b->pending[u],
-                               (long long)nf};
-        if (!nf) {
-            rec[q++] = c;
-            continue;
-        }
-        gat[3 * a] = (long long)(a * nfmax);
-        gat[3 * a + 1] = (long long)frame_offsets[u];
-        gat[3 * a + 2] = (long long)nf;
-        rec[a++] = c;
-    }
-    const size_t desc_bytes = up256(desc_ll * sizeof(long long));
-    const size_t rows_bytes = lockstep ? 0 : n_active * nfmax * W * sizeof(OutT);
-    if (n_active && (rc = ensure(h, &h->d_in, &h->d_in_bytes, n_active * S * sizeof(int16_t) + 256))) return rc;
-    if ((rc = ensure(h, &h->d_out, &h->d_out_bytes, desc_bytes + rows_bytes + 64))) return rc;
-    if ((rc = scratch_acquire(h))) return rc;
-    if ((rc = bank_desc_upload(h, pd, desc_ll))) return rc;
-    auto *d_rec = static_cast<const mfcc_bank::Rec *>(h->d_out);
-    int16_t *d_w = static_cast<int16_t *>(h->d_in);
-    const unsigned blocks = (unsigned)std::min<size_t>(n_rec, size_t(h->n_cu) * 8);
-    hipLaunchKernelGGL(mfcc_bank::bank_advance_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, d_samples,
-                       b->d_state, d_w, d_rec, (long long)n_rec, (long long)n_active, (long long)S, h->r.frame_len, h->r.hop);
-    if (n_active) {
-        OutT *d_rows = lockstep ? d_out : reinterpret_cast<OutT *>(static_cast<char *>(h->d_out) + desc_bytes);
-        if ((rc = launch(h, b->fixed, d_w, S - 1, S, n_active, /*halo=*/1, d_rows, nullptr, nfmax))) return rc;
-        if (!lockstep) {
-            const unsigned gblocks = (unsigned)std::min<size_t>(n_active, size_t(h->n_cu) * 8);
-            hipLaunchKernelGGL(gather_rows_kernel<OutT>, dim3(gblocks), dim3(256), 0, h->stream, d_rows, d_out,
-                               reinterpret_cast<const long long *>(d_rec) + rec_ll, (long long)n_active, (int)W);
-        }
-    }
-    HIP_TRY(h, hipGetLastError());
-    if ((rc = scratch_release(h))) return rc;
-    b->pending.swap(b->after);
-    return MFCC_HIP_SUCCESS;
-}
-
-
-// The runs of the causal CMVN that cover the fresh rows [seen, seen + nf) of a stream: S rows each, counted from frame 0
-inline size_t online_runs(size_t seen, size_t nf, size_t S) { return nf ? (seen + nf - 1) / S - seen / S + 1 : 0; }
-
-// records of the CMVN pass for one stream (rec may be NULL: count only)
-size_t online_cmvn_recs(mfcc_online::Rec *rec, size_t u, size_t row0, size_t seen, size_t nf, size_t S, size_t out_row) {
-    const size_t k = online_runs(seen, nf, S);
-    if (rec)
-        for (size_t i = 0, t0 = seen / S * S; i < k; ++i, t0 += S)
-            rec[i] = mfcc_online::Rec{(long long)u, (long long)row0, (long long)seen, (long long)nf, (long long)t0,
-                                      (long long)std::min(t0 + S, seen + nf), (long long)out_row, 0};
-    return k;
-}
-
-// records of the delta pass: rows [e, e + emitted) of stream u to rows out_row .. of the result, g rows per tile
-size_t online_delta_recs(mfcc_online::Rec *rec, size_t u, size_t row0, size_t seen, size_t nf, size_t e, size_t emitted,
-                         size_t g, size_t out_row, long long last) {
-    const size_t k = (emitted + g - 1) / g;
-    if (rec)
-        for (size_t i = 0; i < k; ++i)
-            rec[i] = mfcc_online::Rec{(long long)u, (long long)row0, (long long)seen, (long long)nf, (long long)(e + i * g),
-                                      (long long)std::min(g, emitted - i * g), (long long)(out_row + i * g), last};
-    return k;
-}
-
-// the passes of an online bank over fresh raw rows, on the handle's stream; d_rec: the three record tables one behind
-// the other on the device.  y: the caller's rows.  carry: also append to ring and tail (a push; a flush resets instead)
-void online_passes(mfcc_hip_bank *b, const mfcc_online::Rec *d_rec, size_t n_cmvn, size_t n_delta, size_t n_carry,
-                   const float *d_raw, float *d_stat, float *y) {
-    mfcc_hip_handle *h = b->h;
-    const int W = int(row_width(h->r));
-    const size_t cap = size_t(h->n_cu) * 8;
-    const bool norm = b->norm != MFCC_HIP_NORMALIZE_NONE;
-    if (norm && n_cmvn) {
-        const size_t G = size_t(mfcc_online::kThreads / W), blocks = std::min((n_cmvn + G - 1) / G, cap);
-        hipLaunchKernelGGL(mfcc_online::online_cmvn_kernel, dim3((unsigned)blocks), dim3(mfcc_online::kThreads), 0, h->stream,
-                           b->d_ring, d_raw, b->order ? d_stat : y, d_rec, (long long)n_cmvn, W, b->window, b->depth, b->norm);
-    }
-    const float *stat = norm ? d_stat : d_raw;
-    if (b->order && n_delta)
-        hipLaunchKernelGGL(mfcc_online::online_deltas_kernel, dim3((unsigned)std::min(n_delta, cap)),
-                           dim3(mfcc_online::kThreads), 0, h->stream, b->d_tail, stat, y, d_rec + n_cmvn, (long long)n_delta, W,
-                           b->order, b->dwin, mfcc_delta::delta_scale(b->dwin));
-    if (n_carry && (b->d_ring || b->d_tail))
-        hipLaunchKernelGGL(mfcc_online::online_carry_kernel, dim3((unsigned)std::min(n_carry, cap)),
-                           dim3(mfcc_online::kThreads), 0, h->stream, b->d_ring, b->d_tail, d_raw, stat,
-                           d_rec + n_cmvn + n_delta, (long long)n_carry, W, b->depth, 2 * b->lag);
-}
-
-// PCEN of the fresh raw rows of an online bank, before its CMVN: in place when CMVN or deltas follow (the PCEN rows are
-// what enters the ring and the tail), else straight to the caller's rows
-void online_pcen(mfcc_hip_bank *b, const mfcc_pcen::OnlineRec *d_rec, size_t n_rec, const float *d_raw, float *dst) {
-    mfcc_hip_handle *h = b->h;
-    const int W = int(row_width(h->r));
-    const size_t blocks = std::min((n_rec * size_t(W) + mfcc_pcen::kThreads - 1) / mfcc_pcen::kThreads, size_t(h->n_cu) * 8);
-    hipLaunchKernelGGL(mfcc_pcen::online_pcen_kernel, dim3((unsigned)blocks), dim3(mfcc_pcen::kThreads), 0, h->stream, d_raw, dst,
-                       d_rec, (long long)n_rec, W, b->pcen_prm,
-                       static_cast<const float *>(b->d_pcen + b->n * 2 * size_t(W)), b->d_pcen);
-}
-
-// bank_advance of an online bank (float): the frame launch always writes raw rows [active][nfmax][W] into the handle's
-// scratch; CMVN, deltas and the carry follow on the same stream.  cap counts expanded floats
-int online_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const size_t *offsets, float *d_out, size_t cap,
-                   size_t *frame_offsets) {
-    mfcc_hip_handle *h = b->h;
-    const size_t flen = size_t(h->r.frame_len), hop = size_t(h->r.hop), W = row_width(h->r), WO = bank_row_width(b), n = b->n;
-    const size_t S = size_t(b->run), L = size_t(b->lag);
-    const bool norm = b->norm != MFCC_HIP_NORMALIZE_NONE;
+    const mfcc_bank::State st = bank_state(b);
     size_t *rfo = b->raw_fo.data();
-    int rc = bank_plan_lagged(flen, hop, L, b->pending.data(), b->held.data(), offsets, n, frame_offsets, b->after.data(),
-                              b->held_after.data(), rfo);
-    if (rc) return rc;
-    const size_t total_rows = frame_offsets[n];
-    if (total_rows && (!d_out || cap < total_rows * WO)) return MFCC_HIP_ERROR_BUFFER_SMALL;
-    const size_t g = b->order ? size_t(mfcc_online::tile_rows(int(W), b->order, b->dwin)) : 1;
-    size_t n_rec = 0, n_active = 0, nfmax = 0, max_total = 0, n_cmvn = 0, n_delta = 0;
-    for (size_t u = 0; u < n; ++u) {
-        const size_t n_new = offsets[u + 1] - offsets[u], nf = rfo[u + 1] - rfo[u];
-        if (!n_new) continue;
-        ++n_rec;
-        if (!nf) continue;
-        ++n_active;
-        nfmax = std::max(nfmax, nf);
-        max_total = std::max(max_total, b->pending[u] + n_new);
-        if (norm) n_cmvn += online_runs(b->seen[u], nf, S);
-        if (b->order) n_delta += (frame_offsets[u + 1] - frame_offsets[u] + g - 1) / g;
-    }
-    if (!n_rec) return MFCC_HIP_SUCCESS;
-    if (!d_samples) return MFCC_HIP_ERROR_INVALID_PARAM;
+    mfcc_bank::Layout l;
+    int rc = mfcc_bank::push_plan(b->s, st, offsets, b->n, d_samples != nullptr, d_out != nullptr, cap, frame_offsets,
+                                  b->after.data(), b->held_after.data(), rfo, l);
+    if (rc || !l.n_rec) return rc;
     DeviceGuard guard(h->device);
-    const size_t SW = 1 + max_total;
-    // [0, 5 n_rec): the bank's records, active streams first; then the CMVN, delta and carry records
-    // ... and, with PCEN, its records behind them
-    const size_t rec_ll = mfcc_bank::kRecLL * n_rec, on_ll = mfcc_online::kRecLL * (n_cmvn + n_delta + n_active);
-    const size_t desc_ll = rec_ll + on_ll + (b->pcen ? mfcc_pcen::kOnlineRecLL * n_active : 0);
-    const bool post = norm || b->order;                  // passes behind PCEN: it then runs in place on the raw rows
-    static_assert(sizeof(mfcc_online::Rec) == mfcc_online::kRecLL * sizeof(long long), "record layout");
-    static_assert(sizeof(mfcc_pcen::OnlineRec) == mfcc_pcen::kOnlineRecLL * sizeof(long long), "record layout");
     mfcc_hip_handle::PinnedDesc *pd = nullptr;
-    if ((rc = desc_acquire(h, desc_ll, &pd))) return rc;
-    auto *rec = reinterpret_cast<mfcc_bank::Rec *>(pd->p);
-    auto *cm = reinterpret_cast<mfcc_online::Rec *>(pd->p + rec_ll), *de = cm + n_cmvn, *ca = de + n_delta;
-    auto *pc = reinterpret_cast<mfcc_pcen::OnlineRec *>(pd->p + rec_ll + on_ll);
-    size_t a = 0, q = n_active;
-    for (size_t u = 0; u < n; ++u) {
-        const size_t n_new = offsets[u + 1] - offsets[u], nf = rfo[u + 1] - rfo[u];
-        if (!n_new) continue;
-        const mfcc_bank::Rec c{(long long)u, (long long)(offsets[u] - shift), (long long)n_new, (long long)b->pending[u],
-                               (long long)nf};
-        if (!nf) {
-            rec[q++] = c;
-            continue;
-        }
-        const size_t row0 = a * nfmax, seen = b->seen[u], emitted = frame_offsets[u + 1] - frame_offsets[u];
-        if (norm) cm += online_cmvn_recs(cm, u, row0, seen, nf, S, b->order ? row0 : frame_offsets[u]);
-        if (b->order)
-            de += online_delta_recs(de, u, row0, seen, nf, seen - b->held[u], emitted, g, frame_offsets[u], mfcc_online::kNoEdge);
-        ca[a] = mfcc_online::Rec{(long long)u, (long long)row0, (long long)seen, (long long)nf, 0, 0, 0, 0};
-        if (b->pcen)
-            pc[a] = mfcc_pcen::OnlineRec{(long long)u, (long long)row0, (long long)seen, (long long)nf,
-                                         (long long)(post ? row0 : frame_offsets[u])};
-        rec[a++] = c;
-    }
-    const size_t desc_bytes = up256(desc_ll * sizeof(long long));
-    const size_t rows_bytes = up256(n_active * nfmax * W * sizeof(float));
-    if (n_active && (rc = ensure(h, &h->d_in, &h->d_in_bytes, n_active * SW * sizeof(int16_t) + 256))) return rc;
-    if ((rc = ensure(h, &h->d_out, &h->d_out_bytes, desc_bytes + 2 * rows_bytes + 64))) return rc;
-    if ((rc = scratch_acquire(h))) return rc;
-    if ((rc = bank_desc_upload(h, pd, desc_ll))) return rc;
-    auto *d_rec = static_cast<const mfcc_bank::Rec *>(h->d_out);
+    if ((rc = desc_acquire(h, l.desc_ll, &pd))) return rc;
+    mfcc_bank::push_fill(b->s, st, offsets, shift, b->n, frame_offsets, rfo, l, pd->p);
+    if (l.in_bytes && (rc = ensure(h, &h->d_in, &h->d_in_bytes, l.in_bytes))) return rc;
+    if ((rc = desc_stage(h, &h->d_out, &h->d_out_bytes, l.out_bytes, pd, l.desc_ll))) return rc;
     int16_t *d_w = static_cast<int16_t *>(h->d_in);
-    const unsigned blocks = (unsigned)std::min<size_t>(n_rec, size_t(h->n_cu) * 8);
+    const unsigned blocks = (unsigned)std::min<size_t>(l.n_rec, size_t(h->n_cu) * 8);
     hipLaunchKernelGGL(mfcc_bank::bank_advance_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, d_samples,
-                       b->d_state, d_w, d_rec, (long long)n_rec, (long long)n_active, (long long)SW, h->r.frame_len, h->r.hop);
-    if (n_active) {
-        float *d_raw = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes);
-        float *d_stat = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes + rows_bytes);
-        if ((rc = launch(h, false, d_w, SW - 1, SW, n_active, /*halo=*/1, d_raw, nullptr, nfmax))) return rc;
-        if (b->pcen) {
-            const long long *pc_ll = reinterpret_cast<const long long *>(d_rec) + rec_ll + on_ll;
-            online_pcen(b, reinterpret_cast<const mfcc_pcen::OnlineRec *>(pc_ll), n_active, d_raw, post ? d_raw : d_out);
-        }
-        online_passes(b, reinterpret_cast<const mfcc_online::Rec *>(reinterpret_cast<const long long *>(d_rec) + rec_ll),
-                      n_cmvn, n_delta, n_active, d_raw, d_stat, d_out);
+                       b->d_state, d_w, desc_table<mfcc_bank::Rec>(h, l.bank), (long long)l.n_rec, (long long)l.n_active,
+                       (long long)l.stride, h->r.frame_len, h->r.hop);
+    if (l.n_active) {
+        void *d_rows = l.direct ? d_out : static_cast<char *>(h->d_out) + l.raw_off;
+        if ((rc = launch(h, b->fixed, d_w, l.stride - 1, l.stride, l.n_active, /*halo=*/1, d_rows, nullptr, l.nfmax))) return rc;
+        bank_passes(b, l, d_out);
     }
     HIP_TRY(h, hipGetLastError());
     if ((rc = scratch_release(h))) return rc;
-    for (size_t u = 0; u < n; ++u) b->seen[u] += rfo[u + 1] - rfo[u];
+    for (size_t u = 0; u < b->n; ++u) b->seen[u] += rfo[u + 1] - rfo[u];
     b->pending.swap(b->after);
     b->held.swap(b->held_after);
     return MFCC_HIP_SUCCESS;
 }
 
-// `streams` of a flush / reset as a list: NULL = every stream, else n distinct indices below the bank's size
-int bank_list(const mfcc_hip_bank *b, const size_t *streams, size_t n, std::vector<size_t> &list) {
+// `idx` of a flush / reset / window request as a list: NULL = every index below `size`, else n distinct ones below it
+int bank_list(size_t size, const size_t *idx, size_t n, std::vector<size_t> &list) {
     list.clear();
-    if (!streams) {
-        for (size_t u = 0; u < b->n; ++u) list.push_back(u);
+    if (!idx) {
+        for (size_t u = 0; u < size; ++u) list.push_back(u);
         return MFCC_HIP_SUCCESS;
     }
-    std::vector<char> seen(b->n, 0);
+    std::vector<char> hit(size, 0);
     for (size_t i = 0; i < n; ++i) {
-        if (streams[i] >= b->n || seen[streams[i]]) return MFCC_HIP_ERROR_INVALID_PARAM;
-        seen[streams[i]] = 1;
-        list.push_back(streams[i]);
+        if (idx[i] >= size || hit[idx[i]]) return MFCC_HIP_ERROR_INVALID_PARAM;
+        hit[idx[i]] = 1;
+        list.push_back(idx[i]);
     }
     return MFCC_HIP_SUCCESS;
 }
 
-// The listed streams back to the reset state; emit: their zero-padded tail frames first, to host memory (synchronous)
-int bank_tail(mfcc_hip_bank *b, const std::vector<size_t> &list, bool emit, void *out) {
+// The end of the listed streams.  give: a flush, to host memory (synchronous): with the handle's pad mode STREAM the
+// zero-padded tail frame (main.c:134-144: one frame over history | pending | zeros) joins each stream as its last row,
+// the held rows and that one are returned with the end clamped -- fo[i + 1] - fo[i] rows of stream list[i] (fo NULL:
+// not wanted).  Without give: a reset, nothing is returned.  Either way the streams are back in the reset state.  The
+// ring and the tail of an online bank are not cleared: with seen = 0 nothing of them is read
+int bank_end(mfcc_hip_bank *b, const std::vector<size_t> &list, bool give, void *out, size_t cap, size_t *fo) {
     mfcc_hip_handle *h = b->h;
-    const size_t k = list.size(), flen = size_t(h->r.frame_len), W = row_width(h->r), S = flen + 1;
-    if (!k) return MFCC_HIP_SUCCESS;
-    const size_t esz = b->fixed ? sizeof(int16_t) : sizeof(float);
+    const mfcc_bank::State st = bank_state(b);
+    const bool emit = give && h->r.pad_mode == MFCC_HIP_PAD_STREAM;
+    if (!fo) fo = b->raw_fo.data();                      // list.size() <= b->n
+    mfcc_bank::Layout l;
+    int rc = mfcc_bank::end_plan(b->s, st, list.data(), list.size(), emit, give, out != nullptr, cap, fo, l);
+    if (rc || !l.n_rec) return rc;
+    const size_t result_bytes = fo[l.n_rec] * b->s.out_width() * b->s.elem;
     DeviceGuard guard(h->device);
     mfcc_hip_handle::PinnedDesc *pd = nullptr;
-    int rc = desc_acquire(h, mfcc_bank::kRecLL * k, &pd);
-    if (rc) return rc;
-    auto *rec = reinterpret_cast<mfcc_bank::Rec *>(pd->p);
-    for (size_t i = 0; i < k; ++i) rec[i] = mfcc_bank::Rec{(long long)list[i], 0, 0, (long long)b->pending[list[i]], 1};
-    if (emit && (rc = ensure(h, &h->d_in, &h->d_in_bytes, k * S * sizeof(int16_t) + 256))) return rc;
-    if (emit && (rc = ensure(h, &b->st_out, &b->st_out_bytes, k * W * esz + 64))) return rc;
-    if ((rc = ensure(h, &h->d_out, &h->d_out_bytes, mfcc_bank::kRecLL * k * sizeof(long long) + 64))) return rc;
-    if ((rc = scratch_acquire(h))) return rc;
-    if ((rc = bank_desc_upload(h, pd, mfcc_bank::kRecLL * k))) return rc;
+    if ((rc = desc_acquire(h, l.desc_ll, &pd))) return rc;
+    mfcc_bank::end_fill(b->s, st, list.data(), fo, l, pd->p);
+    if (l.in_bytes && (rc = ensure(h, &h->d_in, &h->d_in_bytes, l.in_bytes))) return rc;
+    if (result_bytes && (rc = ensure(h, &b->st_out, &b->st_out_bytes, result_bytes + 64))) return rc;
+    if ((rc = desc_stage(h, &h->d_out, &h->d_out_bytes, l.out_bytes, pd, l.desc_ll))) return rc;
     int16_t *d_w = emit ? static_cast<int16_t *>(h->d_in) : nullptr;
-    const unsigned blocks = (unsigned)std::min<size_t>(k, size_t(h->n_cu) * 8);
+    const unsigned blocks = (unsigned)std::min<size_t>(l.n_rec, size_t(h->n_cu) * 8);
     hipLaunchKernelGGL(mfcc_bank::bank_flush_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, b->d_state, d_w,
-                       static_cast<const mfcc_bank::Rec *>(h->d_out), (long long)k, (long long)S, h->r.frame_len);
+                       desc_table<mfcc_bank::Rec>(h, l.bank), (long long)l.n_rec, (long long)l.stride, h->r.frame_len);
     if (emit) {
-        // one frame per stream over history | pending | zeros: the tail frame of main.c:134-144
-        if ((rc = launch(h, b->fixed, d_w, flen, S, k, /*halo=*/1, b->st_out, nullptr, 1))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(out, b->st_out, k * W * esz, hipMemcpyDeviceToHost, h->stream));
+        void *d_rows = l.direct ? b->st_out : static_cast<char *>(h->d_out) + l.raw_off;
+        if ((rc = launch(h, b->fixed, d_w, l.stride - 1, l.stride, l.n_active, /*halo=*/1, d_rows, nullptr, 1))) return rc;
     }
+    bank_passes(b, l, b->st_out);
+    if (result_bytes) HIP_TRY(h, hipMemcpyAsync(out, b->st_out, result_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipGetLastError());
     if ((rc = scratch_release(h))) return rc;
     for (size_t u : list) b->pending[u] = b->seen[u] = b->held[u] = 0;
-    if (emit) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    // as it has been: a plain bank waits for its tail frames, an online one after every flush
+    if (emit || (give && b->s.online())) HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MFCC_HIP_SUCCESS;
-}
-
-// The end of the listed streams of an online bank, to host memory (synchronous): the zero-padded tail frame (emit) joins
-// each stream as its last row, the held rows and that one are returned with the end clamped -- fo[i + 1] - fo[i] =
-// held + emit rows of stream list[i] -- and the streams are back in the reset state.  The ring and the tail are not
-// cleared: with seen = 0 nothing of them is read
-int online_tail(mfcc_hip_bank *b, const std::vector<size_t> &list, bool emit, void *out, const size_t *fo) {
-    mfcc_hip_handle *h = b->h;
-    const size_t k = list.size(), flen = size_t(h->r.frame_len), W = row_width(h->r), WO = bank_row_width(b), SW = flen + 1;
-    if (!k) return MFCC_HIP_SUCCESS;
-    const bool norm = b->norm != MFCC_HIP_NORMALIZE_NONE;
-    const size_t nf = emit ? 1 : 0, total = fo[k], S = size_t(b->run);
-    const size_t g = b->order ? size_t(mfcc_online::tile_rows(int(W), b->order, b->dwin)) : 1;
-    size_t n_cmvn = 0, n_delta = 0;
-    for (size_t i = 0; i < k; ++i) {
-        if (norm) n_cmvn += online_runs(b->seen[list[i]], nf, S);
-        if (b->order) n_delta += (fo[i + 1] - fo[i] + g - 1) / g;
-    }
-    DeviceGuard guard(h->device);
-    const size_t rec_ll = mfcc_bank::kRecLL * k, on_ll = mfcc_online::kRecLL * (n_cmvn + n_delta);
-    const bool pcen = b->pcen && emit;                   // the tail frame goes through PCEN like any row
-    const bool post = norm || b->order;
-    const size_t desc_ll = rec_ll + on_ll + (pcen ? mfcc_pcen::kOnlineRecLL * k : 0);
-    mfcc_hip_handle::PinnedDesc *pd = nullptr;
-    int rc = desc_acquire(h, desc_ll, &pd);
-    if (rc) return rc;
-    auto *rec = reinterpret_cast<mfcc_bank::Rec *>(pd->p);
-    auto *cm = reinterpret_cast<mfcc_online::Rec *>(pd->p + rec_ll), *de = cm + n_cmvn;
-    auto *pc = reinterpret_cast<mfcc_pcen::OnlineRec *>(pd->p + rec_ll + on_ll);
-    for (size_t i = 0; i < k; ++i) {
-        const size_t u = list[i], seen = b->seen[u];
-        rec[i] = mfcc_bank::Rec{(long long)u, 0, 0, (long long)b->pending[u], 1};
-        if (pcen) pc[i] = mfcc_pcen::OnlineRec{(long long)u, (long long)i, (long long)seen, 1, (long long)(post ? i : fo[i])};
-        if (norm) cm += online_cmvn_recs(cm, u, i, seen, nf, S, b->order ? i : fo[i]);
-        if (b->order)
-            de += online_delta_recs(de, u, i, seen, nf, seen - b->held[u], fo[i + 1] - fo[i], g, fo[i],
-                                    (long long)(seen + nf) - 1);
-    }
-    const size_t desc_bytes = up256(desc_ll * sizeof(long long)), rows_bytes = up256(k * W * sizeof(float));
-    if (emit && (rc = ensure(h, &h->d_in, &h->d_in_bytes, k * SW * sizeof(int16_t) + 256))) return rc;
-    if (total && (rc = ensure(h, &b->st_out, &b->st_out_bytes, total * WO * sizeof(float) + 64))) return rc;
-    if ((rc = ensure(h, &h->d_out, &h->d_out_bytes, desc_bytes + 2 * rows_bytes + 64))) return rc;
-    if ((rc = scratch_acquire(h))) return rc;
-    if ((rc = bank_desc_upload(h, pd, desc_ll))) return rc;
-    int16_t *d_w = emit ? static_cast<int16_t *>(h->d_in) : nullptr;
-    const unsigned blocks = (unsigned)std::min<size_t>(k, size_t(h->n_cu) * 8);
-    hipLaunchKernelGGL(mfcc_bank::bank_flush_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, b->d_state, d_w,
-                       static_cast<const mfcc_bank::Rec *>(h->d_out), (long long)k, (long long)SW, h->r.frame_len);
-    float *d_raw = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes);
-    float *d_stat = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + desc_bytes + rows_bytes);
-    if (emit && (rc = launch(h, false, d_w, flen, SW, k, /*halo=*/1, d_raw, nullptr, 1))) return rc;
-    if (total) {
-        if (pcen) {
-            const long long *pc_ll = static_cast<const long long *>(h->d_out) + rec_ll + on_ll;
-            online_pcen(b, reinterpret_cast<const mfcc_pcen::OnlineRec *>(pc_ll), k, d_raw,
-                        post ? d_raw : static_cast<float *>(b->st_out));
-        }
-        online_passes(b, reinterpret_cast<const mfcc_online::Rec *>(static_cast<const long long *>(h->d_out) + rec_ll), n_cmvn,
-                      n_delta, 0, d_raw, d_stat, static_cast<float *>(b->st_out));
-        HIP_TRY(h, hipMemcpyAsync(out, b->st_out, total * WO * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_TRY(h, hipGetLastError());
-    if ((rc = scratch_release(h))) return rc;
-    for (size_t u : list) b->pending[u] = b->seen[u] = b->held[u] = 0;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return MFCC_HIP_SUCCESS;
-}
-
-// rows a flush returns per listed stream, as running sums fo[k + 1]
-void bank_flush_offsets(const mfcc_hip_bank *b, const std::vector<size_t> &list, size_t *fo) {
-    const size_t emit = b->h->r.pad_mode == MFCC_HIP_PAD_STREAM ? 1 : 0;
-    fo[0] = 0;
-    for (size_t i = 0; i < list.size(); ++i) fo[i + 1] = fo[i] + b->held[list[i]] + emit;
 }
 
 // a bank on a checked handle; norm / order as validated by the caller (NONE and 0: a plain bank)
@@ -3029,27 +2799,32 @@ int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int w
     b->held.assign(n_streams, 0);
     b->held_after.assign(n_streams, 0);
     b->raw_fo.assign(n_streams + 1, 0);
-    b->online = norm != MFCC_HIP_NORMALIZE_NONE || order != 0 || pcen;
-    if (pcen) {
-        b->pcen = true;
-        b->pcen_prm = *pcen;
-    }
+    mfcc_bank::Settings &s = b->s;
+    const size_t W = row_width(h->r);
+    s.flen = size_t(h->r.frame_len);
+    s.hop = size_t(h->r.hop);
+    s.W = W;
+    s.elem = fixed ? sizeof(int16_t) : sizeof(float);
+    s.pcen = pcen != nullptr;
+    if (pcen) b->pcen_prm = *pcen;
     if (norm != MFCC_HIP_NORMALIZE_NONE) {
+        s.norm = true;
+        s.S = size_t(mfcc_slide::run_rows(window));
         b->norm = norm;
         b->window = window;
-        b->run = mfcc_slide::run_rows(window);
-        b->depth = b->window + b->run;
+        b->depth = window + int(s.S);
     }
     if (order) {
-        b->order = order;
+        s.order = order;
+        s.L = size_t(order * dwin);
+        s.g = size_t(mfcc_online::tile_rows(int(W), order, dwin));
         b->dwin = dwin;
-        b->lag = order * dwin;
     }
     ++h->n_sessions;
     DeviceGuard guard(h->device);
-    const size_t bytes = n_streams * size_t(h->r.frame_len) * sizeof(int16_t), W = row_width(h->r);
+    const size_t bytes = n_streams * s.flen * sizeof(int16_t);
     const size_t ring_bytes = n_streams * size_t(b->depth) * W * sizeof(float);
-    const size_t tail_bytes = n_streams * size_t(2 * b->lag) * W * sizeof(float);
+    const size_t tail_bytes = n_streams * 2 * s.L * W * sizeof(float);
     auto fail = [&](hipError_t e) {
         h->last_hip = int(e);
         mfcc_hip_bank_destroy(b);
@@ -3058,7 +2833,7 @@ int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int w
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_state), bytes + 64);
     if (e == hipSuccess && ring_bytes) e = hipMalloc(reinterpret_cast<void **>(&b->d_ring), ring_bytes + 64);
     if (e == hipSuccess && tail_bytes) e = hipMalloc(reinterpret_cast<void **>(&b->d_tail), tail_bytes + 64);
-    if (e == hipSuccess && b->pcen) {
+    if (e == hipSuccess && s.pcen) {
         const size_t state_floats = n_streams * 2 * W;
         e = hipMalloc(reinterpret_cast<void **>(&b->d_pcen), (state_floats + mfcc_pcen::kTile) * sizeof(float) + 64);
         if (e == hipSuccess)
@@ -3072,60 +2847,51 @@ int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int w
     return MFCC_HIP_SUCCESS;
 }
 
+// The checks the three create entries share, then the bank.  The bank's settings are its own: the handle must be a raw
+// one (what mfcc_hip_stream_create refuses: per-call statistics, lookahead and whole-segment thresholds of a stream)
+// that can run the path asked for; an online bank (float) takes log-mel rows where it has PCEN
+int bank_create_checked(mfcc_hip_handle *h, int fixed, bool online, size_t n_streams, const mfcc_hip_pcen *p, int normalize,
+                        int normalize_window, int delta_order, int delta_window, mfcc_hip_bank **out) {
+    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
+    *out = nullptr;
+    if (h->destroy_pending || !n_streams || (p && !pcen_ok(p))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (p && !is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (online && h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (normalize != MFCC_HIP_NORMALIZE_NONE && normalize != MFCC_HIP_NORMALIZE_MEAN && normalize != MFCC_HIP_NORMALIZE_MEAN_VAR)
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (normalize != MFCC_HIP_NORMALIZE_NONE && (normalize_window < 1 || normalize_window > MFCC_HIP_MAX_NORMALIZE_WINDOW))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (delta_order < 0 || delta_order > 2 || delta_window < 1 || delta_window > mfcc_delta::kMaxWindow)
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    mfcc_pcen::Prm prm{};
+    if (p) prm = pcen_prm(*p);
+    return bank_create(h, fixed, n_streams, normalize, normalize_window, delta_order, delta_window, out, p ? &prm : nullptr);
+}
+
 }  // namespace
 
 extern "C" {
 
 int mfcc_hip_bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, mfcc_hip_bank **out) {
-    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
-    *out = nullptr;
-    if (h->destroy_pending || !n_streams) return MFCC_HIP_ERROR_INVALID_PARAM;
-    // what mfcc_hip_stream_create refuses: per-call statistics, lookahead and whole-segment thresholds of a stream
-    if (has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
-    return bank_create(h, fixed, n_streams, MFCC_HIP_NORMALIZE_NONE, 0, 0, 0, out);
+    return bank_create_checked(h, fixed, false, n_streams, nullptr, MFCC_HIP_NORMALIZE_NONE, 0, 0, 1, out);
 }
 
 int mfcc_hip_bank_create_online(mfcc_hip_handle *h, size_t n_streams, int normalize, int normalize_window, int delta_order,
                                 int delta_window, mfcc_hip_bank **out) {
-    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
-    *out = nullptr;
-    if (h->destroy_pending || !n_streams) return MFCC_HIP_ERROR_INVALID_PARAM;
-    // the bank's settings are its own: the handle must be a raw one, and able to run the float path
-    if (has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel)) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (normalize != MFCC_HIP_NORMALIZE_NONE && normalize != MFCC_HIP_NORMALIZE_MEAN && normalize != MFCC_HIP_NORMALIZE_MEAN_VAR)
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (normalize != MFCC_HIP_NORMALIZE_NONE && (normalize_window < 1 || normalize_window > MFCC_HIP_MAX_NORMALIZE_WINDOW))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (delta_order < 0 || delta_order > 2 || delta_window < 1 || delta_window > mfcc_delta::kMaxWindow)
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    return bank_create(h, 0, n_streams, normalize, normalize_window, delta_order, delta_window, out);
+    return bank_create_checked(h, 0, true, n_streams, nullptr, normalize, normalize_window, delta_order, delta_window, out);
 }
 
+// p == NULL: no PCEN, mfcc_hip_bank_create_online
 int mfcc_hip_bank_create_online_pcen(mfcc_hip_handle *h, size_t n_streams, const mfcc_hip_pcen *p, int normalize,
                                      int normalize_window, int delta_order, int delta_window, mfcc_hip_bank **out) {
-    if (!p) return mfcc_hip_bank_create_online(h, n_streams, normalize, normalize_window, delta_order, delta_window, out);
-    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
-    *out = nullptr;
-    if (h->destroy_pending || !n_streams || !pcen_ok(p)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    // the bank's settings are its own: a raw log-mel handle that can run the float path
-    if (has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (!is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel)) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (normalize != MFCC_HIP_NORMALIZE_NONE && normalize != MFCC_HIP_NORMALIZE_MEAN && normalize != MFCC_HIP_NORMALIZE_MEAN_VAR)
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (normalize != MFCC_HIP_NORMALIZE_NONE && (normalize_window < 1 || normalize_window > MFCC_HIP_MAX_NORMALIZE_WINDOW))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (delta_order < 0 || delta_order > 2 || delta_window < 1 || delta_window > mfcc_delta::kMaxWindow)
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    const mfcc_pcen::Prm prm = pcen_prm(*p);
-    return bank_create(h, 0, n_streams, normalize, normalize_window, delta_order, delta_window, out, &prm);
+    return bank_create_checked(h, 0, true, n_streams, p, normalize, normalize_window, delta_order, delta_window, out);
 }
 
-size_t mfcc_hip_bank_row_width(const mfcc_hip_bank *b) { return b ? bank_row_width(b) : 0; }
+size_t mfcc_hip_bank_row_width(const mfcc_hip_bank *b) { return b ? b->s.out_width() : 0; }
 
-int mfcc_hip_bank_lag(const mfcc_hip_bank *b) { return b ? b->lag : 0; }
+int mfcc_hip_bank_lag(const mfcc_hip_bank *b) { return b ? int(b->s.L) : 0; }
 
 int mfcc_hip_bank_held(const mfcc_hip_bank *b, size_t *held) {
     if (!b || !held) return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -3147,21 +2913,16 @@ int mfcc_hip_bank_plan_online_framed(const mfcc_hip_params *p, int frame_length,
     Resolved r;
     const int rc = resolve_framed(p, frame_length, r);
     if (rc) return rc;
-    return bank_plan_lagged(size_t(r.frame_len), size_t(r.hop), size_t(lag), pending, held, offsets, n_streams, frame_offsets,
-                            pending_after, held_after, nullptr);
+    return mfcc_bank::plan_streams(size_t(r.frame_len), size_t(r.hop), size_t(lag), pending, held, offsets, n_streams,
+                                   frame_offsets, pending_after, held_after, nullptr);
 }
 
 int mfcc_hip_bank_flush_ragged(mfcc_hip_bank *b, const size_t *streams, size_t n, void *out, size_t out_capacity,
                                size_t *frame_offsets) {
     if (!b || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
     std::vector<size_t> list;
-    const int rc = bank_list(b, streams, n, list);
-    if (rc) return rc;
-    bank_flush_offsets(b, list, frame_offsets);
-    const size_t total = frame_offsets[list.size()];
-    if (total && (!out || out_capacity < total * bank_row_width(b))) return MFCC_HIP_ERROR_BUFFER_SMALL;
-    const bool emit = b->h->r.pad_mode == MFCC_HIP_PAD_STREAM;
-    return b->online ? online_tail(b, list, emit, out, frame_offsets) : bank_tail(b, list, emit, out);
+    const int rc = bank_list(b->n, streams, n, list);
+    return rc ? rc : bank_end(b, list, true, out, out_capacity, frame_offsets);
 }
 
 void mfcc_hip_bank_destroy(mfcc_hip_bank *b) {
@@ -3201,26 +2962,24 @@ int mfcc_hip_bank_plan_framed(const mfcc_hip_params *p, int frame_length, const 
     Resolved r;
     const int rc = resolve_framed(p, frame_length, r);
     if (rc) return rc;
-    return bank_plan_raw(size_t(r.frame_len), size_t(r.hop), pending, offsets, n_streams, frame_offsets, pending_after);
+    return mfcc_bank::plan_streams(size_t(r.frame_len), size_t(r.hop), 0, pending, nullptr, offsets, n_streams, frame_offsets,
+                                   pending_after, nullptr, nullptr);
 }
 
 int mfcc_hip_bank_push_dev(mfcc_hip_bank *b, const void *d_samples, const size_t *offsets, void *d_out, size_t out_capacity,
                            size_t *frame_offsets) {
     if (!b || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
-    const int16_t *d = static_cast<const int16_t *>(d_samples);
-    if (b->online) return online_advance(b, d, 0, offsets, static_cast<float *>(d_out), out_capacity, frame_offsets);
-    return b->fixed ? bank_advance<int16_t>(b, d, 0, offsets, static_cast<int16_t *>(d_out), out_capacity, frame_offsets)
-                    : bank_advance<float>(b, d, 0, offsets, static_cast<float *>(d_out), out_capacity, frame_offsets);
+    return bank_advance(b, static_cast<const int16_t *>(d_samples), 0, offsets, d_out, out_capacity, frame_offsets);
 }
 
 int mfcc_hip_bank_push(mfcc_hip_bank *b, const int16_t *samples, const size_t *offsets, void *out, size_t out_capacity,
                        size_t *frame_offsets) {
     if (!b || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
     mfcc_hip_handle *h = b->h;
-    const size_t W = bank_row_width(b), esz = b->fixed ? sizeof(int16_t) : sizeof(float);
+    const size_t W = b->s.out_width(), esz = b->s.elem;
     // the plan first: a refused push must not have copied anything
-    int rc = bank_plan_lagged(size_t(h->r.frame_len), size_t(h->r.hop), size_t(b->lag), b->pending.data(), b->held.data(), offsets,
-                              b->n, frame_offsets, nullptr, nullptr, nullptr);
+    int rc = mfcc_bank::plan_streams(b->s.flen, b->s.hop, b->s.L, b->pending.data(), b->held.data(), offsets, b->n, frame_offsets,
+                                     nullptr, nullptr, nullptr);
     if (rc) return rc;
     const size_t total = frame_offsets[b->n], span = offsets[b->n] - offsets[0];
     if (total && (!out || out_capacity < total * W)) return MFCC_HIP_ERROR_BUFFER_SMALL;
@@ -3230,10 +2989,7 @@ int mfcc_hip_bank_push(mfcc_hip_bank *b, const int16_t *samples, const size_t *o
     if ((rc = ensure(h, &b->st_in, &b->st_in_bytes, span * sizeof(int16_t) + 64))) return rc;
     if ((rc = ensure(h, &b->st_out, &b->st_out_bytes, total * W * esz + 64))) return rc;
     HIP_TRY(h, hipMemcpyAsync(b->st_in, samples + offsets[0], span * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
-    const int16_t *d = static_cast<const int16_t *>(b->st_in);
-    rc = b->online ? online_advance(b, d, offsets[0], offsets, static_cast<float *>(b->st_out), total * W, frame_offsets)
-         : b->fixed ? bank_advance<int16_t>(b, d, offsets[0], offsets, static_cast<int16_t *>(b->st_out), total * W, frame_offsets)
-                  : bank_advance<float>(b, d, offsets[0], offsets, static_cast<float *>(b->st_out), total * W, frame_offsets);
+    rc = bank_advance(b, static_cast<const int16_t *>(b->st_in), offsets[0], offsets, b->st_out, total * W, frame_offsets);
     if (!rc && total) HIP_TRY(h, hipMemcpyAsync(out, b->st_out, total * W * esz, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));        // `samples` and `out` belong to the caller again
     return rc;
@@ -3243,25 +2999,18 @@ int mfcc_hip_bank_flush(mfcc_hip_bank *b, const size_t *streams, size_t n, void 
                         size_t *n_frames_out) {
     if (!b) return MFCC_HIP_ERROR_INVALID_PARAM;
     std::vector<size_t> list;
-    const int rc = bank_list(b, streams, n, list);
+    const int rc = bank_list(b->n, streams, n, list);
     if (rc) return rc;
-    if (b->lag > 0) return MFCC_HIP_ERROR_UNSUPPORTED;      // ragged output: mfcc_hip_bank_flush_ragged
-    const bool emit = b->h->r.pad_mode == MFCC_HIP_PAD_STREAM;
-    const size_t nf = emit ? list.size() : 0;
-    if (n_frames_out) *n_frames_out = nf;
-    if (nf && (!out || out_capacity < nf * bank_row_width(b))) return MFCC_HIP_ERROR_BUFFER_SMALL;
-    if (!b->online) return bank_tail(b, list, emit, out);
-    std::vector<size_t> fo(list.size() + 1);
-    bank_flush_offsets(b, list, fo.data());
-    return online_tail(b, list, emit, out, fo.data());
+    if (b->s.L > 0) return MFCC_HIP_ERROR_UNSUPPORTED;      // ragged output: mfcc_hip_bank_flush_ragged
+    if (n_frames_out) *n_frames_out = b->h->r.pad_mode == MFCC_HIP_PAD_STREAM ? list.size() : 0;
+    return bank_end(b, list, true, out, out_capacity, nullptr);
 }
 
 int mfcc_hip_bank_reset(mfcc_hip_bank *b, const size_t *streams, size_t n) {
     if (!b) return MFCC_HIP_ERROR_INVALID_PARAM;
     std::vector<size_t> list;
-    const int rc = bank_list(b, streams, n, list);
-    if (rc) return rc;
-    return bank_tail(b, list, false, nullptr);
+    const int rc = bank_list(b->n, streams, n, list);
+    return rc ? rc : bank_end(b, list, false, nullptr, 0, nullptr);
 }
 
 }  // extern "C"
@@ -3343,16 +3092,13 @@ int gate_wins(mfcc_hip_handle *h, const size_t *off, const size_t *wo, size_t n_
     return MFCC_HIP_SUCCESS;
 }
 
-int gate_wins_upload(mfcc_hip_handle *h, mfcc_gate::Wins &w, size_t table_ll, mfcc_hip_handle::PinnedDesc *pd,
-                     long long *d_table) {
-    if (!pd) return MFCC_HIP_SUCCESS;
-    HIP_TRY(h, hipMemcpyAsync(d_table, pd->p, table_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+// the table form's pointers, once its table is on its way to d_table (pd: none in the uniform form)
+void gate_wins_at(mfcc_gate::Wins &w, const mfcc_hip_handle::PinnedDesc *pd, const void *d_table_v) {
+    if (!pd) return;
+    const long long *d_table = static_cast<const long long *>(d_table_v);
     w.s.seg_blk0 = d_table;
     w.delta = d_table + w.s.n_segs + 1;
     w.s.blk = reinterpret_cast<const mfcc_norm::BlockRec *>(d_table + 2 * w.s.n_segs + 1);
-    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
-    pd->in_flight = true;
-    return MFCC_HIP_SUCCESS;
 }
 
 inline unsigned gate_grid(const mfcc_hip_handle *h, long long want) {
@@ -3418,9 +3164,8 @@ int mfcc_hip_gate_dev(mfcc_hip_handle *h, const void *d_rows, int n_cep, const s
     if ((rc = gate_wins(h, seg_offsets, wo.data(), n_segs, size_t(stride), size_t(mfcc_gate::power_tile_wins(g.K, stride)), w,
                         table_ll, pd)))
         return rc;
-    if ((rc = ensure(h, &h->d_sel, &h->d_sel_bytes, table_ll * sizeof(long long) + 64))) return rc;
-    if ((rc = scratch_acquire(h))) return rc;
-    if ((rc = gate_wins_upload(h, w, table_ll, pd, static_cast<long long *>(h->d_sel)))) return rc;
+    if ((rc = desc_stage(h, &h->d_sel, &h->d_sel_bytes, table_ll * sizeof(long long) + 64, pd, table_ll))) return rc;
+    gate_wins_at(w, pd, h->d_sel);
     hipLaunchKernelGGL(mfcc_gate::gate_power_kernel, dim3(gate_grid(h, w.s.n_blocks)), dim3(mfcc_gate::kThreads), 0, h->stream,
                        static_cast<const int16_t *>(d_rows), w, g, threshold, static_cast<long long *>(d_power),
                        static_cast<unsigned char *>(d_gate), static_cast<unsigned char *>(d_gate_ref));
@@ -3460,7 +3205,8 @@ int mfcc_hip_gate_windows_dev(mfcc_hip_handle *h, const void *d_rows, int n_cep,
     char *base = static_cast<char *>(h->d_sel);
     unsigned *counts = reinterpret_cast<unsigned *>(base);
     long long *tile_off = reinterpret_cast<long long *>(base + cnt_b), *seg_off = reinterpret_cast<long long *>(base + cnt_b + toff_b);
-    if ((rc = gate_wins_upload(h, w, table_ll, pd, reinterpret_cast<long long *>(base + cnt_b + toff_b + soff_b)))) return rc;
+    if (pd && (rc = desc_upload(h, pd, table_ll, base + cnt_b + toff_b + soff_b))) return rc;
+    gate_wins_at(w, pd, base + cnt_b + toff_b + soff_b);
     const unsigned grid = gate_grid(h, w.s.n_blocks);
     const unsigned char *mask = static_cast<const unsigned char *>(d_mask);
     // counts and prefix over the window index space: the selection's own kernels, which only need tile_of
@@ -3594,9 +3340,7 @@ int mfcc_hip_gate_push_dev(mfcc_hip_gate *g, const void *d_rows, const size_t *f
                                   (long long)(win_offsets[u + 1] - win_offsets[u]), (long long)win_offsets[u], 0};
     }
     // the records at the front of h->d_out, as the banks keep theirs
-    if ((rc = ensure(h, &h->d_out, &h->d_out_bytes, rec_ll * sizeof(long long) + 64))) return rc;
-    if ((rc = scratch_acquire(h))) return rc;
-    if ((rc = bank_desc_upload(h, pd, rec_ll))) return rc;
+    if ((rc = desc_stage(h, &h->d_out, &h->d_out_bytes, rec_ll * sizeof(long long) + 64, pd, rec_ll))) return rc;
     auto *d_rec = static_cast<const mfcc_gate::Rec *>(h->d_out);
     const int16_t *fresh = static_cast<const int16_t *>(d_rows);
     if (nwmax)
@@ -3615,17 +3359,11 @@ int mfcc_hip_gate_push_dev(mfcc_hip_gate *g, const void *d_rows, const size_t *f
 
 int mfcc_hip_gate_reset(mfcc_hip_gate *g, const size_t *lines, size_t n) {
     if (!g) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (!lines) {
-        std::fill(g->seen.begin(), g->seen.end(), size_t(0));
-        return MFCC_HIP_SUCCESS;
-    }
-    std::vector<char> hit(g->n, 0);
-    for (size_t i = 0; i < n; ++i) {
-        if (lines[i] >= g->n || hit[lines[i]]) return MFCC_HIP_ERROR_INVALID_PARAM;
-        hit[lines[i]] = 1;
-    }
+    std::vector<size_t> list;                           // lines == NULL: every line
+    const int rc = bank_list(g->n, lines, n, list);
+    if (rc) return rc;
     // the frame counts travel with every push's records: a line whose count is 0 reads nothing of its ring
-    for (size_t i = 0; i < n; ++i) g->seen[lines[i]] = 0;
+    for (size_t u : list) g->seen[u] = 0;
     return MFCC_HIP_SUCCESS;
 }
 
@@ -3633,12 +3371,11 @@ int mfcc_hip_gate_window_dev(mfcc_hip_gate *g, const size_t *lines, size_t n, vo
     if (!g || (n && !lines)) return MFCC_HIP_ERROR_INVALID_PARAM;
     mfcc_hip_handle *h = g->h;
     const mfcc_gate::Geo &geo = g->g;
-    std::vector<char> hit(g->n, 0);
-    for (size_t i = 0; i < n; ++i) {
-        if (lines[i] >= g->n || hit[lines[i]] || g->seen[lines[i]] < size_t(geo.n_frames)) return MFCC_HIP_ERROR_INVALID_PARAM;
-        hit[lines[i]] = 1;
-    }
     if (!n) return MFCC_HIP_SUCCESS;
+    std::vector<size_t> list;
+    if (bank_list(g->n, lines, n, list)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    for (size_t u : list)
+        if (g->seen[u] < size_t(geo.n_frames)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 1)) return MFCC_HIP_ERROR_INVALID_PARAM;
     DeviceGuard guard(h->device);
     const size_t rec_ll = 2 * n;
@@ -3650,9 +3387,7 @@ int mfcc_hip_gate_window_dev(mfcc_hip_gate *g, const size_t *lines, size_t n, vo
         const size_t last = gate_windows(g->seen[lines[i]], size_t(geo.n_frames), size_t(geo.stride)) - 1;
         rec[i] = mfcc_gate::WinRec{(long long)lines[i], (long long)(last * size_t(geo.stride))};
     }
-    if ((rc = ensure(h, &h->d_out, &h->d_out_bytes, rec_ll * sizeof(long long) + 64))) return rc;
-    if ((rc = scratch_acquire(h))) return rc;
-    if ((rc = bank_desc_upload(h, pd, rec_ll))) return rc;
+    if ((rc = desc_stage(h, &h->d_out, &h->d_out_bytes, rec_ll * sizeof(long long) + 64, pd, rec_ll))) return rc;
     hipLaunchKernelGGL(mfcc_gate::gate_window_kernel, dim3(gate_grid(h, (long long)n)), dim3(mfcc_gate::kThreads), 0, h->stream,
                        static_cast<const int16_t *>(g->d_ring), static_cast<const mfcc_gate::WinRec *>(h->d_out), (long long)n,
                        geo, g->D, static_cast<int16_t *>(d_out));
