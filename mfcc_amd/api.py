@@ -436,6 +436,19 @@ class MFCC:
             raise ValueError("frame_offsets run past the end of rows")
         return fo
 
+    @staticmethod
+    def _out(rows, out, want, dtype, make):
+        """``out`` checked -- shape ``want`` (None: any capacity), dtype, contiguous, on the device of ``rows`` -- or,
+        without one, what ``make()`` returns."""
+        if out is None:
+            return make()
+        fits = out.dim() == len(want) and all(w is None or w == int(n) for w, n in zip(want, out.shape))
+        if not fits or out.dtype != dtype or not out.is_contiguous() or out.device != rows.device:
+            shape = "(%s)" % ", ".join("capacity" if w is None else str(w) for w in want) if None in want else str(want)
+            raise ValueError("out must be a contiguous %s tensor of shape %s on %s"
+                             % (str(dtype).split(".")[-1], shape, rows.device))
+        return out
+
     def vad_rows(self, rows, frame_offsets=None, column=0, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0,
                  proportion_threshold=0.6, out=None):
         """The energy VAD decision on a CUDA float32 tensor of RAW static rows, on the current torch stream: a uint8
@@ -448,11 +461,8 @@ class MFCC:
         a = _vad_args("select", column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold,
                       width=width)
         want = tuple(rows.shape[:-1])
-        if out is None:
-            out = torch.zeros(want, device=rows.device, dtype=torch.uint8) if frame_offsets is not None else \
-                torch.empty(want, device=rows.device, dtype=torch.uint8)
-        elif tuple(out.shape) != want or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != rows.device:
-            raise ValueError("out must be a contiguous uint8 tensor of shape %s on %s" % (want, rows.device))
+        make = torch.zeros if frame_offsets is not None else torch.empty
+        out = self._out(rows, out, want, torch.uint8, lambda: make(want, device=rows.device, dtype=torch.uint8))
         self._check_device(rows)
         with self._on_torch_stream(rows.device):
             _lib.check(self._lib.mfcc_hip_vad_dev(self._h, C.c_void_p(rows.data_ptr()), width, a[1],
@@ -474,11 +484,8 @@ class MFCC:
             raise ValueError("voiced must be a contiguous uint8 tensor of shape %s on %s"
                              % (tuple(rows.shape[:-1]), rows.device))
         need = int(fo[-1]) - int(fo[0])
-        if out is None:
-            out = torch.empty((need, width), device=rows.device, dtype=torch.float32)
-        elif out.dim() != 2 or int(out.shape[1]) != width or out.dtype != torch.float32 or not out.is_contiguous() or \
-                out.device != rows.device:
-            raise ValueError("out must be a contiguous float32 tensor of shape (capacity, %d) on %s" % (width, rows.device))
+        out = self._out(rows, out, (None, width), torch.float32,
+                        lambda: torch.empty((need, width), device=rows.device, dtype=torch.float32))
         self._check_device(rows)
         oo = np.zeros(len(fo), dtype=np.uint64)
         with self._on_torch_stream(rows.device):
@@ -509,25 +516,10 @@ class MFCC:
         segments are left as they are."""
         import torch
         order, window = _delta_args(order, window, orders=(1, 2))
-        if rows.dtype != torch.float32 or not rows.is_cuda or not rows.is_contiguous() or rows.dim() not in (2, 3):
-            raise TypeError("rows must be a contiguous 2-D or 3-D CUDA(HIP) float32 tensor")
+        fo = self._segments(rows, frame_offsets)
         width = int(rows.shape[-1])
-        if frame_offsets is None:
-            nseg = int(rows.shape[0]) if rows.dim() == 3 else 1
-            per = int(rows.shape[1]) if rows.dim() == 3 else int(rows.shape[0])
-            fo = np.arange(nseg + 1, dtype=np.uint64) * np.uint64(per)
-        else:
-            fo = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
-            if fo.ndim != 1 or len(fo) < 1:
-                raise ValueError("frame_offsets must be 1-D with n_segments + 1 entries")
-            if len(fo) > 1 and int(fo[-1]) * width > rows.numel():
-                raise ValueError("frame_offsets run past the end of rows")
         want = tuple(rows.shape[:-1]) + (width * (1 + order),)
-        if out is None:
-            out = torch.empty(want, device=rows.device, dtype=torch.float32)
-        elif tuple(out.shape) != want or out.dtype != torch.float32 or not out.is_contiguous() or \
-                out.device != rows.device:
-            raise ValueError("out must be a contiguous float32 tensor of shape %s on %s" % (want, rows.device))
+        out = self._out(rows, out, want, torch.float32, lambda: torch.empty(want, device=rows.device, dtype=torch.float32))
         self._check_device(rows)
         with self._on_torch_stream(rows.device):
             _lib.check(self._lib.mfcc_hip_deltas_dev(self._h, C.c_void_p(rows.data_ptr()), width,
@@ -572,29 +564,14 @@ class MFCC:
         w, m, c = _window_args(window, min_window, center)
         if not w and out is not None:
             raise ValueError("out is for the sliding form (window=...); without a window rows are normalized in place")
-        if rows.dtype != torch.float32 or not rows.is_cuda or not rows.is_contiguous() or rows.dim() not in (2, 3):
-            raise TypeError("rows must be a contiguous 2-D or 3-D CUDA(HIP) float32 tensor")
+        fo = self._segments(rows, frame_offsets)
         width = int(rows.shape[-1])
-        if frame_offsets is None:
-            nseg = int(rows.shape[0]) if rows.dim() == 3 else 1
-            per = int(rows.shape[1]) if rows.dim() == 3 else int(rows.shape[0])
-            fo = np.arange(nseg + 1, dtype=np.uint64) * np.uint64(per)
-        else:
-            fo = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
-            if fo.ndim != 1 or len(fo) < 1:
-                raise ValueError("frame_offsets must be 1-D with n_segments + 1 entries")
-            if len(fo) > 1 and int(fo[-1]) * width > rows.numel():
-                raise ValueError("frame_offsets run past the end of rows")
         self._check_device(rows)
         if w:
-            if out is None:
-                # a new tensor: rows the segments do not cover (and every row, for mode None) are copies of the input
+            def make():         # a new tensor: rows the segments do not cover (and every row, for mode None) are copies of the input
                 whole = frame_offsets is None and normalize_mode(mode) != _lib.NORMALIZE_NONE
-                out = torch.empty_like(rows) if whole else rows.clone()
-            elif tuple(out.shape) != tuple(rows.shape) or out.dtype != torch.float32 or not out.is_contiguous() or \
-                    out.device != rows.device:
-                raise ValueError("out must be a contiguous float32 tensor of shape %s on %s"
-                                 % (tuple(rows.shape), rows.device))
+                return torch.empty_like(rows) if whole else rows.clone()
+            out = self._out(rows, out, tuple(rows.shape), torch.float32, make)
             with self._on_torch_stream(rows.device):
                 _lib.check(self._lib.mfcc_hip_normalize_sliding_dev(
                     self._h, C.c_void_p(rows.data_ptr()), width, C.c_void_p(out.data_ptr()),

@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "seg_plan.hpp"      // Segs, BlockRec, tile_of: shared with the host planner
+
 namespace mfcc_norm {
 
 constexpr int kThreads = 256;
@@ -29,43 +31,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // rows per tile: a function of the row width only
 __host__ __device__ inline int tile_rows(int width) { return kTileFloats / width; }
 
-// one tile of a segment (table form of Segs)
-struct BlockRec {
-    long long row0;
-    int rows;
-    int seg;
-};
-
 // per-column partial of one tile: count, mean and sum of squared deviations of the finite values
 struct Part {
     double n, mean, m2;
 };
-
-// The tiles of a call.  Uniform form (blk == nullptr): n_segs segments of seg_rows rows each, back to back from row
-// base_row, blocks_per_seg tiles each (a dense multi-channel call, equal-length utterances).  Table form: one record
-// per tile and the first tile of every segment (seg_blk0, n_segs + 1 entries), built on the host.
-struct Segs {
-    long long base_row, seg_rows, blocks_per_seg;
-    const BlockRec *blk;
-    const long long *seg_blk0;
-    long long n_blocks, n_segs;
-    int width, tile_rows;
-};
-
-__device__ __forceinline__ void tile_of(const Segs &s, long long b, long long &row0, int &rows, long long &seg) {
-    if (!s.blk) {
-        seg = b / s.blocks_per_seg;
-        const long long k = b - seg * s.blocks_per_seg;
-        row0 = s.base_row + seg * s.seg_rows + k * s.tile_rows;
-        const long long left = s.seg_rows - k * s.tile_rows;
-        rows = int(left < s.tile_rows ? left : s.tile_rows);
-    } else {
-        const BlockRec r = s.blk[b];
-        row0 = r.row0;
-        rows = r.rows;
-        seg = r.seg;
-    }
-}
 
 __device__ __forceinline__ bool finite(float v) { return __builtin_isfinite(v); }
 

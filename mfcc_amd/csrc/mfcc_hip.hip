@@ -18,6 +18,7 @@
 
 #include "../../include/mfcc_hip.h"
 #include "bank_plan.hpp"
+#include "seg_plan.hpp"
 #include "kernels_generic.hpp"
 #include "kernel_fixed512.hpp"
 #include "kernel_fused1024.hpp"
@@ -203,6 +204,12 @@ SparseRows pack_rows(const std::vector<T> &dense, int rows, int cols, std::vecto
 
 }  // namespace
 
+// a device buffer that only grows (ensure)
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+};
+
 struct mfcc_hip_handle {
     Resolved r;
     int device = 0;
@@ -238,10 +245,7 @@ struct mfcc_hip_handle {
     // scratch for the host-buffer and ragged entry points.  It is reused by calls that may run on different
     // streams (mfcc_hip_set_stream): scratch_done is recorded behind every use and the next use on ANOTHER stream
     // waits for it on the device (an event outlives the stream it was recorded on)
-    void *d_in = nullptr;
-    size_t d_in_bytes = 0;
-    void *d_out = nullptr;
-    size_t d_out_bytes = 0;
+    DevBuf d_in, d_out;
     hipEvent_t scratch_done = nullptr;
     hipStream_t scratch_stream = nullptr;
     bool scratch_used = false;
@@ -249,8 +253,7 @@ struct mfcc_hip_handle {
     static constexpr int kPipe = 3;
     hipStream_t s_in = nullptr, s_out = nullptr;
     hipEvent_t ev_in[kPipe] = {}, ev_k[kPipe] = {}, ev_out[kPipe] = {};
-    void *p_in[kPipe] = {}, *p_out[kPipe] = {};
-    size_t p_in_bytes[kPipe] = {}, p_out_bytes[kPipe] = {};
+    DevBuf p_in[kPipe], p_out[kPipe];
     // streaming sessions opened on this handle that are still alive.  mfcc_hip_destroy with live sessions only marks
     // the handle; the last mfcc_hip_stream_destroy then tears it down (include/mfcc_hip.h: lifetime)
     int n_sessions = 0;
@@ -258,28 +261,19 @@ struct mfcc_hip_handle {
     // per-segment normalization (mfcc_hip_set_normalize): the mode, the stats / coefficient / tile-table scratch and,
     // for host-buffer calls whose chunks cut a channel, the whole result on the device (run_host_pipeline)
     int norm = MFCC_HIP_NORMALIZE_NONE;
-    void *d_norm = nullptr;
-    size_t d_norm_bytes = 0;
-    void *d_full = nullptr;
-    size_t d_full_bytes = 0;
+    DevBuf d_norm, d_full;
     // delta coefficients (mfcc_hip_set_deltas): order 0 (off), 1 or 2 and the window; the static rows the delta pass
     // reads (d_stat) and its tile table (d_dtab)
     int delta_order = 0;
     int delta_window = 2;
-    void *d_stat = nullptr;
-    size_t d_stat_bytes = 0;
-    void *d_dtab = nullptr;
-    size_t d_dtab_bytes = 0;
+    DevBuf d_stat, d_dtab;
     // sliding-window normalization (mfcc_hip_set_normalize_window): window 0 (off: the per-segment form), the minimum
     // window of the causal form and centered / causal; the raw rows the sliding pass reads (d_slide: it cannot run
     // in place) and its tile table (d_stab)
     int norm_window = 0;
     int norm_min_window = 1;
     int norm_center = 1;
-    void *d_slide = nullptr;
-    size_t d_slide_bytes = 0;
-    void *d_stab = nullptr;
-    size_t d_stab_bytes = 0;
+    DevBuf d_slide, d_stab;
     // energy VAD (mfcc_hip_set_vad): the mode and the rule's parameters; the decision's scratch (d_vad: tile partials,
     // thresholds, tile table), the mask (d_voiced), the selection's scratch (d_sel: tile counts, prefixes, segment
     // offsets, tile table) and the final rows of a SELECT call before the gather moves them to the caller (d_final)
@@ -287,20 +281,12 @@ struct mfcc_hip_handle {
     int vad_column = 0;
     int vad_context = 0;
     float vad_threshold = 5.0f, vad_scale = 0.5f, vad_proportion = 0.6f;
-    void *d_vad = nullptr;
-    size_t d_vad_bytes = 0;
-    void *d_voiced = nullptr;
-    size_t d_voiced_bytes = 0;
-    void *d_sel = nullptr;
-    size_t d_sel_bytes = 0;
-    void *d_final = nullptr;
-    size_t d_final_bytes = 0;
+    DevBuf d_vad, d_voiced, d_sel, d_final;
     // PCEN (mfcc_hip_set_pcen): on / off and the parameters as the kernels take them; the pass's scratch (d_pcen: tile
     // ends, carries, tile table)
     bool pcen_on = false;
     mfcc_pcen::Prm pcen{};
-    void *d_pcen = nullptr;
-    size_t d_pcen_bytes = 0;
+    DevBuf d_pcen;
 };
 
 namespace {
@@ -362,6 +348,36 @@ int desc_acquire(mfcc_hip_handle *h, size_t n, mfcc_hip_handle::PinnedDesc **out
     if (!d.copied) HIP_TRY(h, hipEventCreateWithFlags(&d.copied, hipEventDisableTiming));
     *out = &d;
     return MFCC_HIP_SUCCESS;
+}
+
+// n_ll descriptors of pd on their way to d_dst, on the handle's stream; the pinned buffer is free again once the event
+// recorded behind the copy has passed
+int desc_upload(mfcc_hip_handle *h, mfcc_hip_handle::PinnedDesc *pd, size_t n_ll, void *d_dst) {
+    HIP_TRY(h, hipMemcpyAsync(d_dst, pd->p, n_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
+    pd->in_flight = true;
+    return MFCC_HIP_SUCCESS;
+}
+
+int ensure(mfcc_hip_handle *h, DevBuf &b, size_t want) {
+    if (b.bytes >= want && b.p) return MFCC_HIP_SUCCESS;
+    if (b.p) {
+        HIP_TRY(h, hipFree(b.p));
+        b = DevBuf{};
+    }
+    const size_t sz = want + want / 4 + 4096;
+    HIP_TRY(h, hipMalloc(&b.p, sz));
+    b.bytes = sz;
+    return MFCC_HIP_SUCCESS;
+}
+
+// The scratch buffer b of the handle grown to `want` bytes (0: left as it is) and taken (scratch_acquire), the
+// descriptors of pd (none without one) on their way to byte `at` of it
+int desc_stage(mfcc_hip_handle *h, DevBuf &b, size_t want, mfcc_hip_handle::PinnedDesc *pd, size_t n_ll, size_t at = 0) {
+    int rc;
+    if (want && (rc = ensure(h, b, want))) return rc;
+    if ((rc = scratch_acquire(h))) return rc;
+    return pd ? desc_upload(h, pd, n_ll, static_cast<char *>(b.p) + at) : MFCC_HIP_SUCCESS;
 }
 
 struct Arena {
@@ -710,130 +726,36 @@ int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t s
     return MFCC_HIP_SUCCESS;
 }
 
-int ensure(mfcc_hip_handle *h, void **p, size_t *have, size_t want) {
-    if (*have >= want && *p) return MFCC_HIP_SUCCESS;
-    if (*p) {
-        HIP_TRY(h, hipFree(*p));
-        *p = nullptr;
-        *have = 0;
-    }
-    size_t sz = want + want / 4 + 4096;
-    HIP_TRY(h, hipMalloc(p, sz));
-    *have = sz;
-    return MFCC_HIP_SUCCESS;
-}
+// ---- the tiles and the scratch of a segment pass (seg_plan.hpp).  Normalization, PCEN, deltas,
+// sliding normalization, the VAD, the selection and the gate all stage here; each brings its own tile size, its own
+// buffer, the areas it wants in front of the table, and its kernels.
+using namespace mfcc_seg;
 
-// ---- the tiles of a segment pass (kernel_normalize.hpp: Segs / tile_of / BlockRec).  Normalization, deltas, sliding
-// normalization, the VAD and the selection all plan their tiles here; each brings its own tile size, its own scratch for
-// the device copy of the table, and its kernels.
-inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
-
-// the uniform form: n_segs segments of seg_rows rows each, back to back from row base_row
-inline mfcc_norm::Segs uniform_segs(int width, int tile_rows, size_t base_row, size_t n_segs, size_t seg_rows) {
-    mfcc_norm::Segs s{};
-    s.width = width;
-    s.tile_rows = tile_rows;
-    s.base_row = (long long)base_row;
-    s.seg_rows = (long long)seg_rows;
-    s.blocks_per_seg = (long long)((seg_rows + size_t(tile_rows) - 1) / size_t(tile_rows));
-    s.n_segs = (long long)n_segs;
-    s.n_blocks = s.blocks_per_seg * s.n_segs;
-    return s;
-}
-
-// Segs and, for the table form, its table [first tile of every segment (n_segs + 1)][one record per tile]: table_ll long
-// longs in the pinned buffer pd, not yet on the device (plan_upload).  The uniform form has pd == nullptr.
-struct SegPlan {
-    mfcc_norm::Segs s;
-    size_t table_ll;
-    mfcc_hip_handle::PinnedDesc *pd;
+struct Staged {
+    mfcc_norm::Segs s;                      // the table form points at the device copy
+    const long long *extra;                 // the extra column there (nullptr: none, or the uniform form)
+    char *area[kMaxAreas];
 };
 
-// The tiles of tr rows of segments off[0 .. n_segs] (off does not decrease, off[n_segs] > off[0]): the uniform form when
-// every segment has one length, else the table form
-int plan_segs(mfcc_hip_handle *h, const size_t *off, size_t n_segs, int width, int tile_rows, SegPlan &pl) {
-    const size_t tr = size_t(tile_rows);
-    pl = SegPlan{};
-    const size_t len0 = off[1] - off[0];
-    bool uniform = true;
-    for (size_t k = 1; k < n_segs && uniform; ++k) uniform = off[k + 1] - off[k] == len0;
-    if (uniform) {
-        pl.s = uniform_segs(width, tile_rows, off[0], n_segs, len0);
-        return MFCC_HIP_SUCCESS;
-    }
-    size_t n_blocks = 0;
-    for (size_t k = 0; k < n_segs; ++k) n_blocks += (off[k + 1] - off[k] + tr - 1) / tr;
-    if (n_segs >= (size_t(1) << 31)) return MFCC_HIP_ERROR_INVALID_PARAM;       // BlockRec::seg is an int
-    static_assert(sizeof(mfcc_norm::BlockRec) == 2 * sizeof(long long), "record layout");
-    pl.table_ll = n_segs + 1 + 2 * n_blocks;
-    const int rc = desc_acquire(h, pl.table_ll, &pl.pd);
+// The tiles of tile_rows units of a span that is not empty, with `areas` in buf: count, pinned buffer and fill (table
+// form only), buf grown (a pass that needs no byte allocates nothing) and taken, the table on its way behind the areas
+int seg_stage(mfcc_hip_handle *h, const SegSpan &sp, int width, int tile_rows, const Column *extra, DevBuf &buf,
+              const Area *areas, int n_areas, Staged &st) {
+    Plan pl;
+    int rc = plan_count(sp, width, tile_rows, extra, pl);
     if (rc) return rc;
-    long long *blk0 = pl.pd->p;
-    auto *rec = reinterpret_cast<mfcc_norm::BlockRec *>(pl.pd->p + n_segs + 1);
-    size_t b = 0;
-    for (size_t k = 0; k < n_segs; ++k) {
-        blk0[k] = (long long)b;
-        for (size_t r = off[k]; r < off[k + 1]; r += tr)
-            rec[b++] = mfcc_norm::BlockRec{(long long)r, int(std::min(tr, off[k + 1] - r)), int(k)};
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    if (pl.table_ll) {
+        if ((rc = desc_acquire(h, pl.table_ll, &pd))) return rc;
+        plan_fill(sp, extra, pl, pd->p);
     }
-    blk0[n_segs] = (long long)b;
-    pl.s.width = width;
-    pl.s.tile_rows = tile_rows;
-    pl.s.n_segs = (long long)n_segs;
-    pl.s.n_blocks = (long long)n_blocks;
+    const Scratch lay = lay_out(areas, n_areas, pl);
+    if ((rc = desc_stage(h, buf, n_areas || pd ? lay.total : 0, pd, pl.table_ll, lay.table_off))) return rc;
+    char *base = static_cast<char *>(buf.p);
+    st.extra = plan_bind(pl, reinterpret_cast<const long long *>(base + lay.table_off));
+    st.s = pl.s;
+    for (int i = 0; i < n_areas; ++i) st.area[i] = base + lay.off[i];
     return MFCC_HIP_SUCCESS;
-}
-
-// copies a table form's table to d_table (the pass's own scratch, table_ll long longs) and points pl.s at it; the pinned
-// buffer is free again once the event recorded behind the copy has passed
-int plan_upload(mfcc_hip_handle *h, SegPlan &pl, long long *d_table) {
-    if (!pl.pd) return MFCC_HIP_SUCCESS;
-    HIP_TRY(h, hipMemcpyAsync(d_table, pl.pd->p, pl.table_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    pl.s.seg_blk0 = d_table;
-    pl.s.blk = reinterpret_cast<const mfcc_norm::BlockRec *>(d_table + pl.s.n_segs + 1);
-    HIP_TRY(h, hipEventRecord(pl.pd->copied, h->stream));
-    pl.pd->in_flight = true;
-    return MFCC_HIP_SUCCESS;
-}
-
-// ---- which rows are segments: n_segs runs of seg_rows rows back to back from row base_row (a dense call: one per
-// channel), or segment k = rows off[k] .. off[k + 1] (off does not decrease; checked by the caller)
-struct SegSpan {
-    const size_t *off;      // nullptr: the uniform form
-    size_t n_segs, base_row, seg_rows;
-};
-
-inline SegSpan span_uniform(size_t base_row, size_t n_segs, size_t seg_rows) { return SegSpan{nullptr, n_segs, base_row, seg_rows}; }
-inline SegSpan span_offsets(const size_t *off, size_t n_segs) { return SegSpan{off, n_segs, 0, 0}; }
-
-// no segment, or no row in any: every pass answers success before anything else
-inline bool span_empty(const SegSpan &sp) {
-    return sp.n_segs == 0 || (sp.off ? sp.off[sp.n_segs] == sp.off[0] : sp.seg_rows == 0);
-}
-
-// the tiles of tile_rows rows of a span that is not empty.  The uniform form is filled in as it is -- a dense call may
-// have tens of thousands of channels: no loop, no table; the offsets form is plan_segs's
-int plan_span(mfcc_hip_handle *h, const SegSpan &sp, int width, int tile_rows, SegPlan &pl) {
-    if (sp.off) return plan_segs(h, sp.off, sp.n_segs, width, tile_rows, pl);
-    pl = SegPlan{uniform_segs(width, tile_rows, sp.base_row, sp.n_segs, sp.seg_rows), 0, nullptr};
-    return MFCC_HIP_SUCCESS;
-}
-
-// the checks of the direct entries (mfcc_hip_*_dev on rows): segment offsets that do not decrease, and address ranges
-// [lo, hi) -- or byte ranges behind two pointers -- that do not overlap
-inline bool offsets_ok(const size_t *off, size_t n_segs) {
-    for (size_t k = 0; k < n_segs; ++k)
-        if (off[k + 1] < off[k]) return false;
-    return true;
-}
-
-inline bool ranges_overlap(uintptr_t a_lo, uintptr_t a_hi, uintptr_t b_lo, uintptr_t b_hi) {
-    return a_lo < b_hi && b_lo < a_hi;
-}
-
-inline bool ranges_overlap(const void *a, size_t a_lo, size_t a_hi, const void *b, size_t b_lo, size_t b_hi) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return ranges_overlap(pa + a_lo, pa + a_hi, pb + b_lo, pb + b_hi);
 }
 
 inline unsigned tile_grid(long long n) { return unsigned(std::min<long long>(n, 1 << 20)); }
@@ -842,20 +764,14 @@ inline unsigned tile_grid(long long n) { return unsigned(std::min<long long>(n, 
 // Scratch (h->d_norm): [tile partials: n_blocks * W * 24 B][coefficients: n_segs * W * 8 B][tile table]
 int normalize_pass(mfcc_hip_handle *h, float *d_rows, int width, const SegSpan &sp, int mode) {
     if (span_empty(sp) || mode == MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_SUCCESS;
-    SegPlan pl;
-    int rc = plan_span(h, sp, width, mfcc_norm::tile_rows(width), pl);
-    if (rc) return rc;
     const size_t W = size_t(width);
-    const size_t part_bytes = up256(size_t(pl.s.n_blocks) * W * sizeof(mfcc_norm::Part));
-    const size_t coef_bytes = up256(size_t(pl.s.n_segs) * W * sizeof(float2));
-    if ((rc = ensure(h, &h->d_norm, &h->d_norm_bytes, part_bytes + coef_bytes + pl.table_ll * sizeof(long long) + 64)))
-        return rc;
-    if ((rc = scratch_acquire(h))) return rc;
-    char *base = static_cast<char *>(h->d_norm);
-    auto *part = reinterpret_cast<mfcc_norm::Part *>(base);
-    auto *coef = reinterpret_cast<float2 *>(base + part_bytes);
-    if ((rc = plan_upload(h, pl, reinterpret_cast<long long *>(base + part_bytes + coef_bytes)))) return rc;
-    const mfcc_norm::Segs &s = pl.s;
+    const Area areas[] = {{W * sizeof(mfcc_norm::Part), 0, 0}, {0, W * sizeof(float2), 0}};
+    Staged st;
+    const int rc = seg_stage(h, sp, width, mfcc_norm::tile_rows(width), nullptr, h->d_norm, areas, 2, st);
+    if (rc) return rc;
+    auto *part = reinterpret_cast<mfcc_norm::Part *>(st.area[0]);
+    auto *coef = reinterpret_cast<float2 *>(st.area[1]);
+    const mfcc_norm::Segs &s = st.s;
     const unsigned grid = tile_grid(s.n_blocks), grid_f = tile_grid(s.n_segs);
     hipLaunchKernelGGL(mfcc_norm::normalize_stats_kernel, dim3(grid), dim3(mfcc_norm::kThreads), 0, h->stream,
                        static_cast<const float *>(d_rows), s, part);
@@ -895,17 +811,12 @@ mfcc_pcen::Prm pcen_prm(const mfcc_hip_pcen &p) {
 
 int pcen_pass(mfcc_hip_handle *h, float *d_rows, int width, const SegSpan &sp, const mfcc_pcen::Prm &prm) {
     if (span_empty(sp)) return MFCC_HIP_SUCCESS;
-    SegPlan pl;
-    int rc = plan_span(h, sp, width, mfcc_pcen::kTile, pl);
+    const Area areas[] = {{size_t(width) * sizeof(float), 0, 0}, {size_t(width) * sizeof(float), 0, 0}};
+    Staged st;
+    const int rc = seg_stage(h, sp, width, mfcc_pcen::kTile, nullptr, h->d_pcen, areas, 2, st);
     if (rc) return rc;
-    const size_t W = size_t(width);
-    const size_t tile_bytes = up256(size_t(pl.s.n_blocks) * W * sizeof(float));
-    if ((rc = ensure(h, &h->d_pcen, &h->d_pcen_bytes, 2 * tile_bytes + pl.table_ll * sizeof(long long) + 64))) return rc;
-    if ((rc = scratch_acquire(h))) return rc;
-    char *base = static_cast<char *>(h->d_pcen);
-    float *lend = reinterpret_cast<float *>(base), *carry = reinterpret_cast<float *>(base + tile_bytes);
-    if ((rc = plan_upload(h, pl, reinterpret_cast<long long *>(base + 2 * tile_bytes)))) return rc;
-    const mfcc_norm::Segs &s = pl.s;
+    float *lend = reinterpret_cast<float *>(st.area[0]), *carry = reinterpret_cast<float *>(st.area[1]);
+    const mfcc_norm::Segs &s = st.s;
     const long long G = mfcc_pcen::tiles_per_group(s.width);
     const unsigned grid = tile_grid((s.n_blocks + G - 1) / G);
     const unsigned grid_c = tile_grid((s.n_segs * s.width + mfcc_pcen::kThreads - 1) / mfcc_pcen::kThreads);
@@ -923,14 +834,12 @@ int pcen_pass(mfcc_hip_handle *h, float *d_rows, int width, const SegSpan &sp, c
 // tile table of a ragged call goes to h->d_dtab
 int deltas_pass(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, const SegSpan &sp, int order, int window) {
     if (span_empty(sp)) return MFCC_HIP_SUCCESS;
-    SegPlan pl;
-    int rc = plan_span(h, sp, width, mfcc_delta::tile_rows(width, order, window), pl);
-    if (rc || (rc = scratch_acquire(h))) return rc;
-    if (pl.pd && (rc = ensure(h, &h->d_dtab, &h->d_dtab_bytes, pl.table_ll * sizeof(long long) + 64))) return rc;
-    if ((rc = plan_upload(h, pl, static_cast<long long *>(h->d_dtab)))) return rc;
+    Staged st;
+    const int rc = seg_stage(h, sp, width, mfcc_delta::tile_rows(width, order, window), nullptr, h->d_dtab, nullptr, 0, st);
+    if (rc) return rc;
     const mfcc_delta::DeltasKernel kernel = mfcc_delta::deltas_kernel_of(order, window);
     if (!kernel) return MFCC_HIP_ERROR_INVALID_PARAM;
-    hipLaunchKernelGGL(kernel, dim3(tile_grid(pl.s.n_blocks)), dim3(mfcc_delta::kThreads), 0, h->stream, d_in, d_out, pl.s,
+    hipLaunchKernelGGL(kernel, dim3(tile_grid(st.s.n_blocks)), dim3(mfcc_delta::kThreads), 0, h->stream, d_in, d_out, st.s,
                        mfcc_delta::delta_scale(window));
     HIP_TRY(h, hipGetLastError());
     return scratch_release(h);
@@ -949,13 +858,11 @@ inline SlideArgs slide_args(const mfcc_hip_handle *h) {
 
 int sliding_pass(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, const SegSpan &sp, SlideArgs a) {
     if (span_empty(sp)) return MFCC_HIP_SUCCESS;
-    SegPlan pl;
-    int rc = plan_span(h, sp, width, mfcc_slide::tile_rows(width, a.window), pl);
-    if (rc || (rc = scratch_acquire(h))) return rc;
-    if (pl.pd && (rc = ensure(h, &h->d_stab, &h->d_stab_bytes, pl.table_ll * sizeof(long long) + 64))) return rc;
-    if ((rc = plan_upload(h, pl, static_cast<long long *>(h->d_stab)))) return rc;
-    hipLaunchKernelGGL(mfcc_slide::normalize_sliding_kernel, dim3(tile_grid(pl.s.n_blocks)), dim3(mfcc_slide::kThreads), 0,
-                       h->stream, d_in, d_out, pl.s, mfcc_slide::run_rows(a.window), a.window, a.min_window, a.center, a.mode);
+    Staged st;
+    const int rc = seg_stage(h, sp, width, mfcc_slide::tile_rows(width, a.window), nullptr, h->d_stab, nullptr, 0, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mfcc_slide::normalize_sliding_kernel, dim3(tile_grid(st.s.n_blocks)), dim3(mfcc_slide::kThreads), 0,
+                       h->stream, d_in, d_out, st.s, mfcc_slide::run_rows(a.window), a.window, a.min_window, a.center, a.mode);
     HIP_TRY(h, hipGetLastError());
     return scratch_release(h);
 }
@@ -988,22 +895,16 @@ struct SelPlan {
     long long *tile_off, *seg_off;
 };
 
+inline SelPlan sel_plan_of(const Staged &st) {
+    return SelPlan{st.s, reinterpret_cast<unsigned *>(st.area[0]), reinterpret_cast<long long *>(st.area[1]),
+                   reinterpret_cast<long long *>(st.area[2])};
+}
+
 int select_plan(mfcc_hip_handle *h, const SegSpan &span, int tile_width, SelPlan &pl) {
-    SegPlan sp;
-    int rc = plan_span(h, span, tile_width, mfcc_vad::select_tile_rows(tile_width), sp);
-    if (rc) return rc;
-    const size_t n_segs = span.n_segs;
-    const size_t nb = size_t(sp.s.n_blocks);
-    const size_t cnt_b = up256(nb * sizeof(unsigned)), toff_b = up256((nb + 1) * sizeof(long long));
-    const size_t soff_b = up256((n_segs + 1) * sizeof(long long));
-    if ((rc = ensure(h, &h->d_sel, &h->d_sel_bytes, cnt_b + toff_b + soff_b + sp.table_ll * sizeof(long long) + 64))) return rc;
-    if ((rc = scratch_acquire(h))) return rc;
-    char *base = static_cast<char *>(h->d_sel);
-    pl.counts = reinterpret_cast<unsigned *>(base);
-    pl.tile_off = reinterpret_cast<long long *>(base + cnt_b);
-    pl.seg_off = reinterpret_cast<long long *>(base + cnt_b + toff_b);
-    rc = plan_upload(h, sp, reinterpret_cast<long long *>(base + cnt_b + toff_b + soff_b));
-    pl.s = sp.s;             // after the upload: the table form points at the device copy
+    Staged st;
+    const int rc = seg_stage(h, span, tile_width, mfcc_vad::select_tile_rows(tile_width), nullptr, h->d_sel,
+                             kSelectAreas, 3, st);
+    if (!rc) pl = sel_plan_of(st);
     return rc;
 }
 
@@ -1014,15 +915,12 @@ int vad_decide(mfcc_hip_handle *h, const float *d_rows, int W, const SegSpan &sp
     const double *theta = nullptr;
     int rc;
     if (a.scale != 0.0f) {
-        SegPlan mp;
-        if ((rc = plan_span(h, sp, W, mfcc_vad::kMeanTileRows, mp))) return rc;
+        const Area areas[] = {{sizeof(mfcc_vad::MeanPart), 0, 0}, {0, sizeof(double), 0}};
+        Staged mp;
+        if ((rc = seg_stage(h, sp, W, mfcc_vad::kMeanTileRows, nullptr, h->d_vad, areas, 2, mp))) return rc;
         const mfcc_norm::Segs &sm = mp.s;
-        const size_t part_b = up256(size_t(sm.n_blocks) * sizeof(mfcc_vad::MeanPart)), theta_b = up256(sp.n_segs * sizeof(double));
-        if ((rc = ensure(h, &h->d_vad, &h->d_vad_bytes, part_b + theta_b + mp.table_ll * sizeof(long long) + 64))) return rc;
-        char *base = static_cast<char *>(h->d_vad);
-        auto *part = reinterpret_cast<mfcc_vad::MeanPart *>(base);
-        double *th = reinterpret_cast<double *>(base + part_b);
-        if ((rc = plan_upload(h, mp, reinterpret_cast<long long *>(base + part_b + theta_b)))) return rc;
+        auto *part = reinterpret_cast<mfcc_vad::MeanPart *>(mp.area[0]);
+        double *th = reinterpret_cast<double *>(mp.area[1]);
         hipLaunchKernelGGL(mfcc_vad::vad_mean_kernel, dim3(tile_grid(sm.n_blocks)),
                            dim3(mfcc_vad::kThreads), 0, h->stream, d_rows, sm, a.column, part);
         hipLaunchKernelGGL(mfcc_vad::vad_theta_kernel, dim3(tile_grid(sm.n_segs)),
@@ -1112,8 +1010,8 @@ struct PostRoute {
 inline PostRoute route_to(const mfcc_hip_handle *h, float *out, size_t at = 0) {
     PostRoute rt{};
     rt.out = out;
-    rt.stat = h->delta_order ? static_cast<float *>(h->d_stat) + at : out;
-    rt.raw = sliding(h) ? static_cast<float *>(h->d_slide) + at : rt.stat;
+    rt.stat = h->delta_order ? static_cast<float *>(h->d_stat.p) + at : out;
+    rt.raw = sliding(h) ? static_cast<float *>(h->d_slide.p) + at : rt.stat;
     rt.staged = h->delta_order || sliding(h);
     return rt;
 }
@@ -1121,8 +1019,8 @@ inline PostRoute route_to(const mfcc_hip_handle *h, float *out, size_t at = 0) {
 // grows h->d_stat / h->d_slide for `rows` static rows where the rule needs them
 int stage_rows(mfcc_hip_handle *h, size_t rows) {
     const size_t bytes = rows * row_width(h->r) * sizeof(float) + 64;
-    int rc = h->delta_order ? ensure(h, &h->d_stat, &h->d_stat_bytes, bytes) : MFCC_HIP_SUCCESS;
-    if (!rc && sliding(h)) rc = ensure(h, &h->d_slide, &h->d_slide_bytes, bytes);
+    int rc = h->delta_order ? ensure(h, h->d_stat, bytes) : MFCC_HIP_SUCCESS;
+    if (!rc && sliding(h)) rc = ensure(h, h->d_slide, bytes);
     return rc;
 }
 
@@ -1131,12 +1029,12 @@ int stage_rows(mfcc_hip_handle *h, size_t rows) {
 int post_route(mfcc_hip_handle *h, size_t rows, float *d_out, bool select, PostRoute &rt) {
     int rc = MFCC_HIP_SUCCESS;
     if (select) {
-        rc = ensure(h, &h->d_final, &h->d_final_bytes, rows * out_width(h) * sizeof(float) + 64);
-        if (!rc) rc = ensure(h, &h->d_voiced, &h->d_voiced_bytes, rows + 64);
+        rc = ensure(h, h->d_final, rows * out_width(h) * sizeof(float) + 64);
+        if (!rc) rc = ensure(h, h->d_voiced, rows + 64);
     }
     if (rc || (rc = stage_rows(h, rows))) return rc;
-    rt = route_to(h, select ? static_cast<float *>(h->d_final) : d_out);
-    rt.voiced = select ? static_cast<unsigned char *>(h->d_voiced) : nullptr;
+    rt = route_to(h, select ? static_cast<float *>(h->d_final.p) : d_out);
+    rt.voiced = select ? static_cast<unsigned char *>(h->d_voiced.p) : nullptr;
     rt.staged = rt.staged || select;
     return rt.staged ? scratch_acquire(h) : MFCC_HIP_SUCCESS;
 }
@@ -1283,9 +1181,9 @@ int run_host_pipeline(mfcc_hip_handle *h, const std::vector<PipeChunk> &chunks, 
             HIP_TRY(h, hipEventCreateWithFlags(&h->ev_k[i], hipEventDisableTiming));
             HIP_TRY(h, hipEventCreateWithFlags(&h->ev_out[i], hipEventDisableTiming));
         }
-        int rc = ensure(h, &h->p_in[i], &h->p_in_bytes[i], max_in + 64);
+        int rc = ensure(h, h->p_in[i], max_in + 64);
         if (rc) return rc;
-        if ((rc = ensure(h, &h->p_out[i], &h->p_out_bytes[i], max_out + 64))) return rc;
+        if ((rc = ensure(h, h->p_out[i], max_out + 64))) return rc;
     }
     // the copy streams start behind whatever is queued on the handle's stream
     HIP_TRY(h, hipEventRecord(h->ev_k[0], h->stream));
@@ -1336,14 +1234,14 @@ int run_host_pipeline(mfcc_hip_handle *h, const std::vector<PipeChunk> &chunks, 
             pin_in.release_below(chunks[i - kPipe + 1].in);
             pin_out.release_below(chunks[i - kPipe + 1].out);
         }
-        if (c.in_bytes) PIPE_TRY(pin_in.copy(h->p_in[slot], c.in, c.in_bytes, hipMemcpyHostToDevice, h->s_in));
+        if (c.in_bytes) PIPE_TRY(pin_in.copy(h->p_in[slot].p, c.in, c.in_bytes, hipMemcpyHostToDevice, h->s_in));
         PIPE_TRY(hipEventRecord(h->ev_in[slot], h->s_in));
         PIPE_TRY(hipStreamWaitEvent(h->stream, h->ev_in[slot], 0));
-        const int rc = enqueue(i, h->p_in[slot], h->p_out[slot]);
+        const int rc = enqueue(i, h->p_in[slot].p, h->p_out[slot].p);
         if (rc) return fail(rc);
         PIPE_TRY(hipEventRecord(h->ev_k[slot], h->stream));
         PIPE_TRY(hipStreamWaitEvent(h->s_out, h->ev_k[slot], 0));
-        if (c.out_bytes) PIPE_TRY(pin_out.copy(c.out, h->p_out[slot], c.out_bytes, hipMemcpyDeviceToHost, h->s_out));
+        if (c.out_bytes) PIPE_TRY(pin_out.copy(c.out, h->p_out[slot].p, c.out_bytes, hipMemcpyDeviceToHost, h->s_out));
         PIPE_TRY(hipEventRecord(h->ev_out[slot], h->s_out));
     }
     PIPE_TRY(hipStreamSynchronize(h->s_out));
@@ -1410,9 +1308,9 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     const bool whole = post && ch_bytes > kChunkBytes;
     OutT *d_full = nullptr;
     if (whole) {
-        const int rc = ensure(h, &h->d_full, &h->d_full_bytes, n_out * sizeof(OutT) + 64);
+        const int rc = ensure(h, h->d_full, n_out * sizeof(OutT) + 64);
         if (rc) return rc;
-        d_full = static_cast<OutT *>(h->d_full);
+        d_full = static_cast<OutT *>(h->d_full.p);
     }
     // the staging of the chain (route_to's rule) holds the rows of one chunk, or of the whole result
     const bool staged = post && (K || sliding(h));
@@ -1571,14 +1469,14 @@ int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm,
         if (n_tiles < (1ll << 30)) {
             const size_t chan_bytes = n_utt * sizeof(mfcc_fused12::RaggedChan);
             const size_t map_off = (chan_bytes + 255) & ~size_t(255);
-            rc = ensure(h, &h->d_in, &h->d_in_bytes, map_off + size_t(n_tiles) * sizeof(mfcc_fused12::RaggedTile) + 64);
+            rc = ensure(h, h->d_in, map_off + size_t(n_tiles) * sizeof(mfcc_fused12::RaggedTile) + 64);
             if (rc) return rc;
             if ((rc = scratch_acquire(h))) return rc;
-            HIP_TRY(h, hipMemcpyAsync(h->d_in, rc_host, chan_bytes, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(h->d_in.p, rc_host, chan_bytes, hipMemcpyHostToDevice, h->stream));
             HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
             pd->in_flight = true;
-            auto *d_chans = static_cast<const mfcc_fused12::RaggedChan *>(h->d_in);
-            auto *d_map = reinterpret_cast<mfcc_fused12::RaggedTile *>(static_cast<char *>(h->d_in) + map_off);
+            auto *d_chans = static_cast<const mfcc_fused12::RaggedChan *>(h->d_in.p);
+            auto *d_map = reinterpret_cast<mfcc_fused12::RaggedTile *>(static_cast<char *>(h->d_in.p) + map_off);
             const bool launched =
                 is_logmel(h->r) ? mfcc_fused12::launch_ragged<true>(d_pcm, d_chans, (int)n_utt, d_map, (int)n_tiles, h->fu,
                                                                     h->fused_dense, reinterpret_cast<float *>(d_out), h->n_cu, h->stream)
@@ -1612,13 +1510,13 @@ int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm,
         }
         {
             const size_t rec_bytes = n_recs * sizeof(mfcc_fixed512::RaggedRec);
-            rc = ensure(h, &h->d_in, &h->d_in_bytes, rec_bytes + 64);
+            rc = ensure(h, h->d_in, rec_bytes + 64);
             if (rc) return rc;
             if ((rc = scratch_acquire(h))) return rc;
-            HIP_TRY(h, hipMemcpyAsync(h->d_in, rr, rec_bytes, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(h->d_in.p, rr, rec_bytes, hipMemcpyHostToDevice, h->stream));
             HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
             pd->in_flight = true;
-            mfcc_fixed512::launch_ragged(d_pcm, static_cast<const mfcc_fixed512::RaggedRec *>(h->d_in), (int)n_recs,
+            mfcc_fixed512::launch_ragged(d_pcm, static_cast<const mfcc_fixed512::RaggedRec *>(h->d_in.p), (int)n_recs,
                                          (long long)total, h->r.hop, h->x5, reinterpret_cast<int16_t *>(d_out), h->n_cu,
                                          h->stream);
             HIP_TRY(h, hipGetLastError());
@@ -1628,21 +1526,21 @@ int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm,
     const size_t F = pos / hop, len = pos + flen + hop;
     desc[4 * last_with_frames + 3] = (long long)len;     // the last one also zeroes the tail of the stream
     const size_t desc_bytes = 7 * n_utt * sizeof(long long);
-    rc = ensure(h, &h->d_in, &h->d_in_bytes, len * sizeof(int16_t) + 64);
+    rc = ensure(h, h->d_in, len * sizeof(int16_t) + 64);
     if (rc) return rc;
-    rc = ensure(h, &h->d_out, &h->d_out_bytes, F * ncep * sizeof(OutT) + desc_bytes + 64);
+    rc = ensure(h, h->d_out, F * ncep * sizeof(OutT) + desc_bytes + 64);
     if (rc) return rc;
     if ((rc = scratch_acquire(h))) return rc;
-    OutT *d_all = static_cast<OutT *>(h->d_out);
+    OutT *d_all = static_cast<OutT *>(h->d_out.p);
     const size_t desc_off = (F * ncep * sizeof(OutT) + 7) & ~size_t(7);
-    long long *d_desc = reinterpret_cast<long long *>(static_cast<char *>(h->d_out) + desc_off);
+    long long *d_desc = reinterpret_cast<long long *>(static_cast<char *>(h->d_out.p) + desc_off);
     HIP_TRY(h, hipMemcpyAsync(d_desc, desc, desc_bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
     pd->in_flight = true;
     const unsigned blocks = (unsigned)std::min<size_t>(n_utt, size_t(h->n_cu) * 8);
     hipLaunchKernelGGL(pack_utterances_kernel, dim3(blocks), dim3(256), 0, h->stream, d_pcm,
-                       static_cast<int16_t *>(h->d_in), d_desc, (long long)n_utt);
-    rc = launch(h, fixed, h->d_in, len, len, 1, 0, d_all, nullptr, F);
+                       static_cast<int16_t *>(h->d_in.p), d_desc, (long long)n_utt);
+    rc = launch(h, fixed, h->d_in.p, len, len, 1, 0, d_all, nullptr, F);
     if (rc) return rc;
     hipLaunchKernelGGL(gather_rows_kernel<OutT>, dim3(blocks), dim3(256), 0, h->stream, d_all, d_out,
                        d_desc + 4 * n_utt, (long long)n_utt, (int)ncep);
@@ -2011,25 +1909,15 @@ void mfcc_hip_destroy(mfcc_hip_handle *h) {
         if (h->ev_in[i]) (void)hipEventDestroy(h->ev_in[i]);
         if (h->ev_k[i]) (void)hipEventDestroy(h->ev_k[i]);
         if (h->ev_out[i]) (void)hipEventDestroy(h->ev_out[i]);
-        if (h->p_in[i]) (void)hipFree(h->p_in[i]);
-        if (h->p_out[i]) (void)hipFree(h->p_out[i]);
+        if (h->p_in[i].p) (void)hipFree(h->p_in[i].p);
+        if (h->p_out[i].p) (void)hipFree(h->p_out[i].p);
     }
     if (h->s_in) (void)hipStreamDestroy(h->s_in);
     if (h->s_out) (void)hipStreamDestroy(h->s_out);
     if (h->arena) (void)hipFree(h->arena);
-    if (h->d_in) (void)hipFree(h->d_in);
-    if (h->d_out) (void)hipFree(h->d_out);
-    if (h->d_norm) (void)hipFree(h->d_norm);
-    if (h->d_pcen) (void)hipFree(h->d_pcen);
-    if (h->d_full) (void)hipFree(h->d_full);
-    if (h->d_stat) (void)hipFree(h->d_stat);
-    if (h->d_dtab) (void)hipFree(h->d_dtab);
-    if (h->d_slide) (void)hipFree(h->d_slide);
-    if (h->d_stab) (void)hipFree(h->d_stab);
-    if (h->d_vad) (void)hipFree(h->d_vad);
-    if (h->d_voiced) (void)hipFree(h->d_voiced);
-    if (h->d_sel) (void)hipFree(h->d_sel);
-    if (h->d_final) (void)hipFree(h->d_final);
+    for (DevBuf *b : {&h->d_in, &h->d_out, &h->d_norm, &h->d_pcen, &h->d_full, &h->d_stat, &h->d_dtab, &h->d_slide, &h->d_stab,
+                      &h->d_vad, &h->d_voiced, &h->d_sel, &h->d_final})
+        if (b->p) (void)hipFree(b->p);
     delete h;
 }
 
@@ -2146,12 +2034,9 @@ int mfcc_hip_set_normalize(mfcc_hip_handle *h, int mode) {
 int mfcc_hip_normalize_dev(mfcc_hip_handle *h, void *d_rows, int row_width, const size_t *seg_offsets, size_t n_segs,
                            int mode) {
     if (!h || mode < MFCC_HIP_NORMALIZE_NONE || mode > MFCC_HIP_NORMALIZE_MEAN_VAR) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (row_width < 1 || row_width > mfcc_norm::kMaxWidth || (n_segs && !seg_offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (!offsets_ok(seg_offsets, n_segs)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (n_segs && seg_offsets[n_segs] > seg_offsets[0] &&
-        (!d_rows || (reinterpret_cast<uintptr_t>(d_rows) & 3)))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0) return MFCC_HIP_SUCCESS;
+    const RowPtr ptr[] = {{d_rows, 4, size_t(row_width) * sizeof(float), kWrite, false}};
+    const int rc = check_rows(RowCall{row_width, mfcc_norm::kMaxWidth, seg_offsets, n_segs, nullptr, ptr, 1});
+    if (rc != kProceed || mode == MFCC_HIP_NORMALIZE_NONE) return rc < 0 ? rc : MFCC_HIP_SUCCESS;
     DeviceGuard guard(h->device);
     return normalize_pass(h, static_cast<float *>(d_rows), row_width, span_offsets(seg_offsets, n_segs), mode);
 }
@@ -2189,12 +2074,9 @@ int mfcc_hip_set_pcen(mfcc_hip_handle *h, const mfcc_hip_pcen *p) {
 int mfcc_hip_pcen_dev(mfcc_hip_handle *h, void *d_rows, int row_width, const size_t *seg_offsets, size_t n_segs,
                       const mfcc_hip_pcen *p) {
     if (!h || !pcen_ok(p)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (row_width < 1 || row_width > mfcc_pcen::kMaxWidth || (n_segs && !seg_offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (!offsets_ok(seg_offsets, n_segs)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (n_segs && seg_offsets[n_segs] > seg_offsets[0] &&
-        (!d_rows || (reinterpret_cast<uintptr_t>(d_rows) & 3)))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (n_segs == 0) return MFCC_HIP_SUCCESS;
+    const RowPtr ptr[] = {{d_rows, 4, size_t(row_width) * sizeof(float), kWrite, false}};
+    const int rc = check_rows(RowCall{row_width, mfcc_pcen::kMaxWidth, seg_offsets, n_segs, nullptr, ptr, 1});
+    if (rc != kProceed) return rc < 0 ? rc : MFCC_HIP_SUCCESS;
     DeviceGuard guard(h->device);
     return pcen_pass(h, static_cast<float *>(d_rows), row_width, span_offsets(seg_offsets, n_segs), pcen_prm(*p));
 }
@@ -2215,18 +2097,16 @@ int mfcc_hip_normalize_sliding_dev(mfcc_hip_handle *h, const void *d_in, int row
                                    int center) {
     static_assert(MFCC_HIP_MAX_NORMALIZE_WINDOW == mfcc_slide::kMaxWindow, "window limit");
     if (!h || mode < MFCC_HIP_NORMALIZE_NONE || mode > MFCC_HIP_NORMALIZE_MEAN_VAR) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (row_width < 1 || row_width > mfcc_slide::kMaxWidth || (n_segs && !seg_offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (window < 1 || window > MFCC_HIP_MAX_NORMALIZE_WINDOW || min_window < 1 || min_window > window || center < 0 ||
         center > 1)
         return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (!offsets_ok(seg_offsets, n_segs)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (mode == MFCC_HIP_NORMALIZE_NONE || n_segs == 0 || seg_offsets[n_segs] == seg_offsets[0]) return MFCC_HIP_SUCCESS;
-    if (!d_in || !d_out || (reinterpret_cast<uintptr_t>(d_in) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    // the byte ranges the pass reads and writes must not overlap: a window reaches into rows already written
-    const size_t r0 = seg_offsets[0], r1 = seg_offsets[n_segs], row_bytes = size_t(row_width) * sizeof(float);
-    if (ranges_overlap(d_in, r0 * row_bytes, r1 * row_bytes, d_out, r0 * row_bytes, r1 * row_bytes))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
+    // the byte ranges the pass reads and writes must not overlap: a window reaches into rows already written.  Mode NONE
+    // touches neither pointer: none is looked at
+    const size_t row_bytes = size_t(row_width) * sizeof(float);
+    const RowPtr ptr[] = {{d_in, 4, row_bytes, kRead, false}, {d_out, 4, row_bytes, kWrite, false}};
+    const bool none = mode == MFCC_HIP_NORMALIZE_NONE;
+    const int rc = check_rows(RowCall{row_width, mfcc_slide::kMaxWidth, seg_offsets, n_segs, nullptr, ptr, none ? 0 : 2});
+    if (rc != kProceed || none) return rc < 0 ? rc : MFCC_HIP_SUCCESS;
     DeviceGuard guard(h->device);
     return sliding_pass(h, static_cast<const float *>(d_in), static_cast<float *>(d_out), row_width,
                         span_offsets(seg_offsets, n_segs), SlideArgs{mode, window, min_window, center});
@@ -2243,18 +2123,13 @@ int mfcc_hip_set_deltas(mfcc_hip_handle *h, int order, int window) {
 
 int mfcc_hip_deltas_dev(mfcc_hip_handle *h, const void *d_in, int width, void *d_out, const size_t *seg_offsets,
                         size_t n_segs, int order, int window) {
-    if (!h || width < 1 || width > mfcc_delta::kMaxWidth || order < 1 || order > 2 || window < 1 ||
-        window > MFCC_HIP_MAX_DELTA_WINDOW || (n_segs && !seg_offsets))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (!offsets_ok(seg_offsets, n_segs)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (n_segs == 0 || seg_offsets[n_segs] == seg_offsets[0]) return MFCC_HIP_SUCCESS;
-    if (!d_in || !d_out || (reinterpret_cast<uintptr_t>(d_in) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!h || order < 1 || order > 2 || window < 1 || window > MFCC_HIP_MAX_DELTA_WINDOW) return MFCC_HIP_ERROR_INVALID_PARAM;
     // the byte ranges the pass reads and writes must not overlap
-    const size_t r0 = seg_offsets[0], r1 = seg_offsets[n_segs];
-    const size_t in_bytes = size_t(width) * sizeof(float), out_bytes = in_bytes * size_t(1 + order);
-    if (ranges_overlap(d_in, r0 * in_bytes, r1 * in_bytes, d_out, r0 * out_bytes, r1 * out_bytes))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
+    const size_t in_bytes = size_t(width) * sizeof(float);
+    const RowPtr ptr[] = {{d_in, 4, in_bytes, kRead, false},
+                          {d_out, 4, in_bytes * size_t(1 + order), kWrite, false}};
+    const int rc = check_rows(RowCall{width, mfcc_delta::kMaxWidth, seg_offsets, n_segs, nullptr, ptr, 2});
+    if (rc != kProceed) return rc < 0 ? rc : MFCC_HIP_SUCCESS;
     DeviceGuard guard(h->device);
     return deltas_pass(h, static_cast<const float *>(d_in), static_cast<float *>(d_out), width,
                        span_offsets(seg_offsets, n_segs), order, window);
@@ -2279,15 +2154,13 @@ int mfcc_hip_set_vad(mfcc_hip_handle *h, int mode, int column, float energy_thre
 int mfcc_hip_vad_dev(mfcc_hip_handle *h, const void *d_rows, int row_width, int column, const size_t *seg_offsets,
                      size_t n_segs, float energy_threshold, float energy_mean_scale, int frames_context,
                      float proportion_threshold, void *d_voiced) {
-    if (!h || row_width < 1 || row_width > mfcc_vad::kMaxWidth || (n_segs && !seg_offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (!vad_args_ok(row_width, column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold))
+    if (!h || !vad_args_ok(row_width, column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold))
         return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (!offsets_ok(seg_offsets, n_segs)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (n_segs == 0 || seg_offsets[n_segs] == seg_offsets[0]) return MFCC_HIP_SUCCESS;
-    if (!d_rows || !d_voiced || (reinterpret_cast<uintptr_t>(d_rows) & 3)) return MFCC_HIP_ERROR_INVALID_PARAM;
     // the rows read and the bytes written must not overlap
-    const size_t r0 = seg_offsets[0], r1 = seg_offsets[n_segs], row_bytes = size_t(row_width) * sizeof(float);
-    if (ranges_overlap(d_rows, r0 * row_bytes, r1 * row_bytes, d_voiced, r0, r1)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const RowPtr ptr[] = {{d_rows, 4, size_t(row_width) * sizeof(float), kRead, false},
+                          {d_voiced, 1, 1, kWrite, false}};
+    const int rc = check_rows(RowCall{row_width, mfcc_vad::kMaxWidth, seg_offsets, n_segs, nullptr, ptr, 2});
+    if (rc != kProceed) return rc < 0 ? rc : MFCC_HIP_SUCCESS;
     DeviceGuard guard(h->device);
     return vad_segments(h, static_cast<const float *>(d_rows), row_width, span_offsets(seg_offsets, n_segs),
                         VadArgs{column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold},
@@ -2296,19 +2169,16 @@ int mfcc_hip_vad_dev(mfcc_hip_handle *h, const void *d_rows, int row_width, int 
 
 int mfcc_hip_select_dev(mfcc_hip_handle *h, const void *d_in, int row_width, const void *d_voiced, const size_t *seg_offsets,
                         size_t n_segs, void *d_out, size_t out_capacity_rows, size_t *out_offsets) {
-    if (!h || row_width < 1 || row_width > mfcc_vad::kMaxSelectWidth || (n_segs && (!seg_offsets || !out_offsets)))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (!offsets_ok(seg_offsets, n_segs)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (n_segs == 0 || seg_offsets[n_segs] == seg_offsets[0])
-        return select_segments(h, nullptr, row_width, nullptr, span_offsets(seg_offsets, n_segs), nullptr, out_offsets);
-    if (!d_in || !d_voiced || !d_out || (reinterpret_cast<uintptr_t>(d_in) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!h || (n_segs && !out_offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
     // the rows and the mask read must not overlap the rows that may be written (every row may be voiced)
-    const size_t r0 = seg_offsets[0], r1 = seg_offsets[n_segs], row_bytes = size_t(row_width) * sizeof(float);
-    if (ranges_overlap(d_in, r0 * row_bytes, r1 * row_bytes, d_out, 0, (r1 - r0) * row_bytes) ||
-        ranges_overlap(d_voiced, r0, r1, d_out, 0, (r1 - r0) * row_bytes))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (out_capacity_rows < r1 - r0) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    const size_t row_bytes = size_t(row_width) * sizeof(float);
+    const RowPtr ptr[] = {{d_in, 4, row_bytes, kRead, false}, {d_voiced, 1, 1, kRead, false},
+                          {d_out, 4, row_bytes, kWritePacked, false}};
+    const int rc = check_rows(RowCall{row_width, mfcc_vad::kMaxSelectWidth, seg_offsets, n_segs, nullptr, ptr, 3});
+    if (rc == kNothing)
+        return select_segments(h, nullptr, row_width, nullptr, span_offsets(seg_offsets, n_segs), nullptr, out_offsets);
+    if (rc != kProceed) return rc;
+    if (out_capacity_rows < seg_offsets[n_segs] - seg_offsets[0]) return MFCC_HIP_ERROR_BUFFER_SMALL;
     DeviceGuard guard(h->device);
     return select_segments(h, static_cast<const float *>(d_in), row_width, static_cast<const unsigned char *>(d_voiced),
                            span_offsets(seg_offsets, n_segs), static_cast<float *>(d_out), out_offsets);
@@ -2331,6 +2201,14 @@ const char *mfcc_hip_kernel_name(const mfcc_hip_handle *h, int fixed) {
     return "mfcc_float_generic_kernel";
 }
 
+// float coefficients -> the int16 a `.mfcc` file holds: astype(np.int16) of software/lift.py:39 (truncate)
+static inline int16_t to_mfcc_i16(float v) {
+    if (!(v == v)) v = 0.0f;
+    if (v > 32767.0f) v = 32767.0f;
+    if (v < -32768.0f) v = -32768.0f;
+    return int16_t(v);
+}
+
 int mfcc_hip_convert_wav(mfcc_hip_handle *h, const char *wav_in, const char *mfcc_out, int fixed,
                          size_t *n_frames_out) {
     if (!h || !wav_in || !mfcc_out) return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -2350,13 +2228,7 @@ int mfcc_hip_convert_wav(mfcc_hip_handle *h, const char *wav_in, const char *mfc
         std::vector<float> f(cep.size());
         rc = mfcc_hip_process_i16(h, pcm.data(), pcm.size(), 1, f.data(), f.size(), nullptr);
         if (rc) return rc;
-        for (size_t i = 0; i < f.size(); ++i) {
-            float v = f[i];                                   // astype(np.int16): truncate
-            if (!(v == v)) v = 0.0f;
-            if (v > 32767.0f) v = 32767.0f;
-            if (v < -32768.0f) v = -32768.0f;
-            cep[i] = int16_t(v);
-        }
+        for (size_t i = 0; i < f.size(); ++i) cep[i] = to_mfcc_i16(f[i]);
     }
     FILE *o = std::fopen(mfcc_out, "wb");
     if (!o) return MFCC_HIP_ERROR_IO;
@@ -2365,14 +2237,6 @@ int mfcc_hip_convert_wav(mfcc_hip_handle *h, const char *wav_in, const char *mfc
     if (wr != cep.size()) return MFCC_HIP_ERROR_IO;
     if (n_frames_out) *n_frames_out = nf;
     return MFCC_HIP_SUCCESS;
-}
-
-// float coefficients -> the int16 a `.mfcc` file holds: astype(np.int16) of software/lift.py:39 (truncate)
-static inline int16_t to_mfcc_i16(float v) {
-    if (!(v == v)) v = 0.0f;
-    if (v > 32767.0f) v = 32767.0f;
-    if (v < -32768.0f) v = -32768.0f;
-    return int16_t(v);
 }
 
 int mfcc_hip_convert_wavs(mfcc_hip_handle *h, const char *const *wav_in, const char *const *mfcc_out, size_t n_files,
@@ -2603,8 +2467,7 @@ struct mfcc_hip_bank {
     int16_t *d_state = nullptr;          // [n][frame_len]
     std::vector<size_t> pending, after;  // the host mirror and the plan of the push in progress
     // staging of the host-buffer entries (mfcc_hip_bank_push, mfcc_hip_bank_flush): the flat samples and the rows
-    void *st_in = nullptr, *st_out = nullptr;
-    size_t st_in_bytes = 0, st_out_bytes = 0;
+    DevBuf st_in, st_out;
     // online bank (mfcc_hip_bank_create_online; kernel_stream_bank_online.hpp): causal CMVN
     // over `window` rows and deltas of s.order x `dwin`, lag s.L = order * dwin.  seen[u] = frames computed since reset,
     // held[u] <= lag = finished rows not yet returned; both depend on chunk lengths only
@@ -2624,27 +2487,10 @@ inline mfcc_bank::State bank_state(const mfcc_hip_bank *b) {
     return mfcc_bank::State{b->pending.data(), b->seen.data(), b->held.data()};
 }
 
-// n_ll descriptors of pd on their way to d_dst, on the handle's stream
-int desc_upload(mfcc_hip_handle *h, mfcc_hip_handle::PinnedDesc *pd, size_t n_ll, void *d_dst) {
-    HIP_TRY(h, hipMemcpyAsync(d_dst, pd->p, n_ll * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
-    pd->in_flight = true;
-    return MFCC_HIP_SUCCESS;
-}
-
-// The scratch buffer *buf of the handle grown to `want` bytes and taken (scratch_acquire), the descriptors of pd (none
-// without one) on their way to its front
-int desc_stage(mfcc_hip_handle *h, void **buf, size_t *have, size_t want, mfcc_hip_handle::PinnedDesc *pd, size_t n_ll) {
-    int rc;
-    if ((rc = ensure(h, buf, have, want))) return rc;
-    if ((rc = scratch_acquire(h))) return rc;
-    return pd ? desc_upload(h, pd, n_ll, *buf) : MFCC_HIP_SUCCESS;
-}
-
 // a record table of the descriptor block at the front of h->d_out
 template <class T>
 inline const T *desc_table(const mfcc_hip_handle *h, const mfcc_bank::Table &t) {
-    return reinterpret_cast<const T *>(static_cast<const long long *>(h->d_out) + t.off);
+    return reinterpret_cast<const T *>(static_cast<const long long *>(h->d_out.p) + t.off);
 }
 
 template <typename OutT>
@@ -2663,8 +2509,8 @@ void bank_passes(mfcc_hip_bank *b, const mfcc_bank::Layout &l, void *y) {
     const mfcc_bank::Settings &s = b->s;
     const int W = int(s.W);
     const size_t cap = size_t(h->n_cu) * 8;
-    float *d_raw = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + l.raw_off);
-    float *d_stat = reinterpret_cast<float *>(static_cast<char *>(h->d_out) + l.stat_off), *out = static_cast<float *>(y);
+    float *d_raw = reinterpret_cast<float *>(static_cast<char *>(h->d_out.p) + l.raw_off);
+    float *d_stat = reinterpret_cast<float *>(static_cast<char *>(h->d_out.p) + l.stat_off), *out = static_cast<float *>(y);
     if (!s.online()) {
         if (l.gather.n) b->fixed ? bank_gather<int16_t>(h, l, d_raw, y, W) : bank_gather<float>(h, l, d_raw, y, W);
         return;
@@ -2710,15 +2556,15 @@ int bank_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const
     mfcc_hip_handle::PinnedDesc *pd = nullptr;
     if ((rc = desc_acquire(h, l.desc_ll, &pd))) return rc;
     mfcc_bank::push_fill(b->s, st, offsets, shift, b->n, frame_offsets, rfo, l, pd->p);
-    if (l.in_bytes && (rc = ensure(h, &h->d_in, &h->d_in_bytes, l.in_bytes))) return rc;
-    if ((rc = desc_stage(h, &h->d_out, &h->d_out_bytes, l.out_bytes, pd, l.desc_ll))) return rc;
-    int16_t *d_w = static_cast<int16_t *>(h->d_in);
+    if (l.in_bytes && (rc = ensure(h, h->d_in, l.in_bytes))) return rc;
+    if ((rc = desc_stage(h, h->d_out, l.out_bytes, pd, l.desc_ll))) return rc;
+    int16_t *d_w = static_cast<int16_t *>(h->d_in.p);
     const unsigned blocks = (unsigned)std::min<size_t>(l.n_rec, size_t(h->n_cu) * 8);
     hipLaunchKernelGGL(mfcc_bank::bank_advance_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, d_samples,
                        b->d_state, d_w, desc_table<mfcc_bank::Rec>(h, l.bank), (long long)l.n_rec, (long long)l.n_active,
                        (long long)l.stride, h->r.frame_len, h->r.hop);
     if (l.n_active) {
-        void *d_rows = l.direct ? d_out : static_cast<char *>(h->d_out) + l.raw_off;
+        void *d_rows = l.direct ? d_out : static_cast<char *>(h->d_out.p) + l.raw_off;
         if ((rc = launch(h, b->fixed, d_w, l.stride - 1, l.stride, l.n_active, /*halo=*/1, d_rows, nullptr, l.nfmax))) return rc;
         bank_passes(b, l, d_out);
     }
@@ -2764,19 +2610,19 @@ int bank_end(mfcc_hip_bank *b, const std::vector<size_t> &list, bool give, void 
     mfcc_hip_handle::PinnedDesc *pd = nullptr;
     if ((rc = desc_acquire(h, l.desc_ll, &pd))) return rc;
     mfcc_bank::end_fill(b->s, st, list.data(), fo, l, pd->p);
-    if (l.in_bytes && (rc = ensure(h, &h->d_in, &h->d_in_bytes, l.in_bytes))) return rc;
-    if (result_bytes && (rc = ensure(h, &b->st_out, &b->st_out_bytes, result_bytes + 64))) return rc;
-    if ((rc = desc_stage(h, &h->d_out, &h->d_out_bytes, l.out_bytes, pd, l.desc_ll))) return rc;
-    int16_t *d_w = emit ? static_cast<int16_t *>(h->d_in) : nullptr;
+    if (l.in_bytes && (rc = ensure(h, h->d_in, l.in_bytes))) return rc;
+    if (result_bytes && (rc = ensure(h, b->st_out, result_bytes + 64))) return rc;
+    if ((rc = desc_stage(h, h->d_out, l.out_bytes, pd, l.desc_ll))) return rc;
+    int16_t *d_w = emit ? static_cast<int16_t *>(h->d_in.p) : nullptr;
     const unsigned blocks = (unsigned)std::min<size_t>(l.n_rec, size_t(h->n_cu) * 8);
     hipLaunchKernelGGL(mfcc_bank::bank_flush_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, b->d_state, d_w,
                        desc_table<mfcc_bank::Rec>(h, l.bank), (long long)l.n_rec, (long long)l.stride, h->r.frame_len);
     if (emit) {
-        void *d_rows = l.direct ? b->st_out : static_cast<char *>(h->d_out) + l.raw_off;
+        void *d_rows = l.direct ? b->st_out.p : static_cast<char *>(h->d_out.p) + l.raw_off;
         if ((rc = launch(h, b->fixed, d_w, l.stride - 1, l.stride, l.n_active, /*halo=*/1, d_rows, nullptr, 1))) return rc;
     }
-    bank_passes(b, l, b->st_out);
-    if (result_bytes) HIP_TRY(h, hipMemcpyAsync(out, b->st_out, result_bytes, hipMemcpyDeviceToHost, h->stream));
+    bank_passes(b, l, b->st_out.p);
+    if (result_bytes) HIP_TRY(h, hipMemcpyAsync(out, b->st_out.p, result_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipGetLastError());
     if ((rc = scratch_release(h))) return rc;
     for (size_t u : list) b->pending[u] = b->seen[u] = b->held[u] = 0;
@@ -2936,8 +2782,8 @@ void mfcc_hip_bank_destroy(mfcc_hip_bank *b) {
         if (b->d_ring) (void)hipFree(b->d_ring);
         if (b->d_tail) (void)hipFree(b->d_tail);
         if (b->d_pcen) (void)hipFree(b->d_pcen);
-        if (b->st_in) (void)hipFree(b->st_in);
-        if (b->st_out) (void)hipFree(b->st_out);
+        if (b->st_in.p) (void)hipFree(b->st_in.p);
+        if (b->st_out.p) (void)hipFree(b->st_out.p);
         delete b;
     }
     if (--h->n_sessions == 0 && h->destroy_pending) mfcc_hip_destroy(h);
@@ -2986,11 +2832,11 @@ int mfcc_hip_bank_push(mfcc_hip_bank *b, const int16_t *samples, const size_t *o
     if (!span) return MFCC_HIP_SUCCESS;
     if (!samples) return MFCC_HIP_ERROR_INVALID_PARAM;
     DeviceGuard guard(h->device);
-    if ((rc = ensure(h, &b->st_in, &b->st_in_bytes, span * sizeof(int16_t) + 64))) return rc;
-    if ((rc = ensure(h, &b->st_out, &b->st_out_bytes, total * W * esz + 64))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(b->st_in, samples + offsets[0], span * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
-    rc = bank_advance(b, static_cast<const int16_t *>(b->st_in), offsets[0], offsets, b->st_out, total * W, frame_offsets);
-    if (!rc && total) HIP_TRY(h, hipMemcpyAsync(out, b->st_out, total * W * esz, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = ensure(h, b->st_in, span * sizeof(int16_t) + 64))) return rc;
+    if ((rc = ensure(h, b->st_out, total * W * esz + 64))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(b->st_in.p, samples + offsets[0], span * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+    rc = bank_advance(b, static_cast<const int16_t *>(b->st_in.p), offsets[0], offsets, b->st_out.p, total * W, frame_offsets);
+    if (!rc && total) HIP_TRY(h, hipMemcpyAsync(out, b->st_out.p, total * W * esz, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));        // `samples` and `out` belong to the caller again
     return rc;
 }
@@ -3049,56 +2895,16 @@ int gate_count(size_t n_frames, size_t stride, const size_t *off, size_t n_segs,
     return MFCC_HIP_SUCCESS;
 }
 
-// The tiles of tw windows of segments off[0 .. n_segs] (rows; wo their window offsets, wo[n_segs] > 0): the uniform form
-// when every segment has one length, else the table form in pinned memory: [first tile of every segment (n_segs + 1)]
-// [delta (n_segs)][one record per tile], not yet on the device (gate_wins_upload)
-int gate_wins(mfcc_hip_handle *h, const size_t *off, const size_t *wo, size_t n_segs, size_t stride, size_t tw,
-              mfcc_gate::Wins &w, size_t &table_ll, mfcc_hip_handle::PinnedDesc *&pd) {
-    w = mfcc_gate::Wins{};
-    w.s.width = 1;
-    w.s.tile_rows = int(tw);
-    w.s.n_segs = (long long)n_segs;
-    table_ll = 0;
-    pd = nullptr;
-    const size_t len0 = off[1] - off[0];
-    bool uniform = true;
-    for (size_t k = 1; k < n_segs && uniform; ++k) uniform = off[k + 1] - off[k] == len0;
-    if (uniform) {
-        const size_t nw = wo[1] - wo[0];
-        w.s.seg_rows = (long long)nw;
-        w.s.blocks_per_seg = (long long)((nw + tw - 1) / tw);
-        w.s.n_blocks = w.s.blocks_per_seg * w.s.n_segs;
-        w.base_row = (long long)off[0];
-        w.seg_rows = (long long)len0;
-        return MFCC_HIP_SUCCESS;
-    }
-    size_t n_blocks = 0;
-    for (size_t k = 0; k < n_segs; ++k) n_blocks += (wo[k + 1] - wo[k] + tw - 1) / tw;
-    if (n_segs >= (size_t(1) << 31)) return MFCC_HIP_ERROR_INVALID_PARAM;       // BlockRec::seg is an int
-    table_ll = 2 * n_segs + 1 + 2 * n_blocks;
-    const int rc = desc_acquire(h, table_ll, &pd);
+// The tiles of tw windows of segments off[0 .. n_segs] (rows; wo their window offsets, wo[n_segs] > 0), staged in
+// h->d_sel behind `areas`: a plan over the window index space whose extra column is delta[k] = off[k] - wo[k] * stride
+int gate_stage(mfcc_hip_handle *h, const size_t *off, const size_t *wo, size_t n_segs, size_t stride, size_t tw,
+               const Area *areas, int n_areas, Staged &st, mfcc_gate::Wins &w) {
+    const Column delta{off, stride};
+    const int rc = seg_stage(h, span_offsets(wo, n_segs), 1, int(tw), &delta, h->d_sel, areas, n_areas, st);
     if (rc) return rc;
-    long long *blk0 = pd->p, *delta = pd->p + n_segs + 1;
-    auto *rec = reinterpret_cast<mfcc_norm::BlockRec *>(pd->p + 2 * n_segs + 1);
-    size_t b = 0;
-    for (size_t k = 0; k < n_segs; ++k) {
-        blk0[k] = (long long)b;
-        delta[k] = (long long)off[k] - (long long)(wo[k] * stride);
-        for (size_t q = wo[k]; q < wo[k + 1]; q += tw)
-            rec[b++] = mfcc_norm::BlockRec{(long long)q, int(std::min(tw, wo[k + 1] - q)), int(k)};
-    }
-    blk0[n_segs] = (long long)b;
-    w.s.n_blocks = (long long)n_blocks;
+    const bool equal = !st.s.blk;                      // equal segments: their rows, as first_row() steps through them
+    w = mfcc_gate::Wins{st.s, st.extra, equal ? (long long)off[0] : 0, equal ? (long long)(off[1] - off[0]) : 0};
     return MFCC_HIP_SUCCESS;
-}
-
-// the table form's pointers, once its table is on its way to d_table (pd: none in the uniform form)
-void gate_wins_at(mfcc_gate::Wins &w, const mfcc_hip_handle::PinnedDesc *pd, const void *d_table_v) {
-    if (!pd) return;
-    const long long *d_table = static_cast<const long long *>(d_table_v);
-    w.s.seg_blk0 = d_table;
-    w.delta = d_table + w.s.n_segs + 1;
-    w.s.blk = reinterpret_cast<const mfcc_norm::BlockRec *>(d_table + 2 * w.s.n_segs + 1);
 }
 
 inline unsigned gate_grid(const mfcc_hip_handle *h, long long want) {
@@ -3138,34 +2944,22 @@ int mfcc_hip_gate_dev(mfcc_hip_handle *h, const void *d_rows, int n_cep, const s
     std::vector<size_t> wo(n_segs + 1);
     int rc = gate_count(size_t(n_frames), size_t(stride), seg_offsets, n_segs, wo.data());
     if (rc) return rc;
-    const size_t total = wo[n_segs];
-    if (total == 0) return MFCC_HIP_SUCCESS;                 // nothing to write: the pointers are not looked at
+    // the rows read and the entries written (one per window; an output may be NULL) must not overlap each other.  No
+    // window: nothing to write, the pointers are not looked at
+    const RowPtr ptr[] = {{d_rows, 2, size_t(n_cep) * sizeof(int16_t), kRead, false},
+                          {d_power, 8, sizeof(long long), kWritePacked, true},
+                          {d_gate, 1, 1, kWritePacked, true},
+                          {d_gate_ref, 1, 1, kWritePacked, true}};
+    rc = check_rows(RowCall{n_cep, mfcc_gate::kMaxWidth, seg_offsets, n_segs, wo.data(), ptr, 4});
+    if (rc != kProceed) return rc < 0 ? rc : MFCC_HIP_SUCCESS;
     if (!d_power && !d_gate && !d_gate_ref) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (!d_rows || (reinterpret_cast<uintptr_t>(d_rows) & 1) || (reinterpret_cast<uintptr_t>(d_power) & 7))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    // the rows read and the entries written must not overlap
-    const size_t row_bytes = size_t(n_cep) * sizeof(int16_t);
-    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(d_rows) + seg_offsets[0] * row_bytes;
-    const uintptr_t in_hi = reinterpret_cast<uintptr_t>(d_rows) + seg_offsets[n_segs] * row_bytes;
-    const uintptr_t o[3] = {reinterpret_cast<uintptr_t>(d_power), reinterpret_cast<uintptr_t>(d_gate),
-                            reinterpret_cast<uintptr_t>(d_gate_ref)};
-    const size_t ob[3] = {total * sizeof(long long), total, total};
-    for (int i = 0; i < 3; ++i) {
-        if (!o[i]) continue;
-        if (ranges_overlap(in_lo, in_hi, o[i], o[i] + ob[i])) return MFCC_HIP_ERROR_INVALID_PARAM;
-        for (int j = i + 1; j < 3; ++j)
-            if (o[j] && ranges_overlap(o[i], o[i] + ob[i], o[j], o[j] + ob[j])) return MFCC_HIP_ERROR_INVALID_PARAM;
-    }
     DeviceGuard guard(h->device);
     const mfcc_gate::Geo g = mfcc_gate::geometry(n_cep, n_frames, stride);
+    Staged st;
     mfcc_gate::Wins w;
-    size_t table_ll = 0;
-    mfcc_hip_handle::PinnedDesc *pd = nullptr;
-    if ((rc = gate_wins(h, seg_offsets, wo.data(), n_segs, size_t(stride), size_t(mfcc_gate::power_tile_wins(g.K, stride)), w,
-                        table_ll, pd)))
+    if ((rc = gate_stage(h, seg_offsets, wo.data(), n_segs, size_t(stride), size_t(mfcc_gate::power_tile_wins(g.K, stride)),
+                         nullptr, 0, st, w)))
         return rc;
-    if ((rc = desc_stage(h, &h->d_sel, &h->d_sel_bytes, table_ll * sizeof(long long) + 64, pd, table_ll))) return rc;
-    gate_wins_at(w, pd, h->d_sel);
     hipLaunchKernelGGL(mfcc_gate::gate_power_kernel, dim3(gate_grid(h, w.s.n_blocks)), dim3(mfcc_gate::kThreads), 0, h->stream,
                        static_cast<const int16_t *>(d_rows), w, g, threshold, static_cast<long long *>(d_power),
                        static_cast<unsigned char *>(d_gate), static_cast<unsigned char *>(d_gate_ref));
@@ -3182,40 +2976,33 @@ int mfcc_hip_gate_windows_dev(mfcc_hip_handle *h, const void *d_rows, int n_cep,
     int rc = gate_count(size_t(n_frames), size_t(stride), seg_offsets, n_segs, wo.data());
     if (rc) return rc;
     const size_t total = wo[n_segs];
-    if (total == 0) {
+    // how much is written is not known yet: the outputs' alignment now, their ranges below
+    const size_t row_bytes = size_t(n_cep) * sizeof(int16_t);
+    const RowPtr ptr[] = {{d_rows, 2, row_bytes, kRead, false}, {d_mask, 1, 1, kRead, false},
+                          {d_out, 2, 0, kUnsized, true}, {d_starts, 8, 0, kUnsized, true}};
+    rc = check_rows(RowCall{n_cep, mfcc_gate::kMaxWidth, seg_offsets, n_segs, wo.data(), ptr, 4});
+    if (rc == kNothing) {
         for (size_t k = 0; k <= n_segs && out_offsets; ++k) out_offsets[k] = 0;
         return MFCC_HIP_SUCCESS;
     }
-    if (!d_rows || !d_mask || (reinterpret_cast<uintptr_t>(d_rows) & 1) || (reinterpret_cast<uintptr_t>(d_out) & 1) ||
-        (reinterpret_cast<uintptr_t>(d_starts) & 7))
-        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (rc != kProceed) return rc;
     DeviceGuard guard(h->device);
     const mfcc_gate::Geo g = mfcc_gate::geometry(n_cep, n_frames, stride);
+    Staged st;
     mfcc_gate::Wins w;
-    size_t table_ll = 0;
-    mfcc_hip_handle::PinnedDesc *pd = nullptr;
-    if ((rc = gate_wins(h, seg_offsets, wo.data(), n_segs, size_t(stride), size_t(mfcc_gate::kSelTileWins), w, table_ll, pd)))
+    if ((rc = gate_stage(h, seg_offsets, wo.data(), n_segs, size_t(stride), size_t(mfcc_gate::kSelTileWins),
+                         kSelectAreas, 3, st, w)))
         return rc;
-    // scratch (h->d_sel): [tile counts][tile prefixes (n_blocks + 1)][segment offsets (n_segs + 1)][tile table]
-    const size_t nb = size_t(w.s.n_blocks);
-    const size_t cnt_b = up256(nb * sizeof(unsigned)), toff_b = up256((nb + 1) * sizeof(long long));
-    const size_t soff_b = up256((n_segs + 1) * sizeof(long long));
-    if ((rc = ensure(h, &h->d_sel, &h->d_sel_bytes, cnt_b + toff_b + soff_b + table_ll * sizeof(long long) + 64))) return rc;
-    if ((rc = scratch_acquire(h))) return rc;
-    char *base = static_cast<char *>(h->d_sel);
-    unsigned *counts = reinterpret_cast<unsigned *>(base);
-    long long *tile_off = reinterpret_cast<long long *>(base + cnt_b), *seg_off = reinterpret_cast<long long *>(base + cnt_b + toff_b);
-    if (pd && (rc = desc_upload(h, pd, table_ll, base + cnt_b + toff_b + soff_b))) return rc;
-    gate_wins_at(w, pd, base + cnt_b + toff_b + soff_b);
+    const SelPlan sel = sel_plan_of(st);
     const unsigned grid = gate_grid(h, w.s.n_blocks);
     const unsigned char *mask = static_cast<const unsigned char *>(d_mask);
     // counts and prefix over the window index space: the selection's own kernels, which only need tile_of
-    hipLaunchKernelGGL(mfcc_vad::vad_count_kernel, dim3(grid), dim3(mfcc_vad::kThreads), 0, h->stream, mask, w.s, counts);
+    hipLaunchKernelGGL(mfcc_vad::vad_count_kernel, dim3(grid), dim3(mfcc_vad::kThreads), 0, h->stream, mask, w.s, sel.counts);
     hipLaunchKernelGGL(mfcc_vad::vad_scan_kernel, dim3(1), dim3(mfcc_vad::kScanThreads), 0, h->stream, w.s,
-                       static_cast<const unsigned *>(counts), tile_off, seg_off);
+                       static_cast<const unsigned *>(sel.counts), sel.tile_off, sel.seg_off);
     HIP_TRY(h, hipGetLastError());
     static_assert(sizeof(size_t) == sizeof(long long), "segment offsets are copied as they are");
-    HIP_TRY(h, hipMemcpyAsync(out_offsets, seg_off, (n_segs + 1) * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out_offsets, sel.seg_off, (n_segs + 1) * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));            // the count depends on the data
     const size_t n_sel = out_offsets[n_segs];
     rc = MFCC_HIP_SUCCESS;
@@ -3223,7 +3010,7 @@ int mfcc_hip_gate_windows_dev(mfcc_hip_handle *h, const void *d_rows, int n_cep,
         rc = MFCC_HIP_ERROR_BUFFER_SMALL;
     } else if (n_sel) {
         // what is read must not overlap what is written
-        const size_t row_bytes = size_t(n_cep) * sizeof(int16_t), win_bytes = size_t(n_frames) * row_bytes;
+        const size_t win_bytes = size_t(n_frames) * row_bytes;
         const uintptr_t in_lo = reinterpret_cast<uintptr_t>(d_rows) + seg_offsets[0] * row_bytes;
         const uintptr_t in_hi = reinterpret_cast<uintptr_t>(d_rows) + seg_offsets[n_segs] * row_bytes;
         const uintptr_t m_lo = reinterpret_cast<uintptr_t>(d_mask), m_hi = m_lo + total;
@@ -3235,7 +3022,7 @@ int mfcc_hip_gate_windows_dev(mfcc_hip_handle *h, const void *d_rows, int n_cep,
             rc = MFCC_HIP_ERROR_INVALID_PARAM;
         else
             hipLaunchKernelGGL(mfcc_gate::gate_gather_kernel, dim3(grid), dim3(mfcc_gate::kThreads), 0, h->stream,
-                               static_cast<const int16_t *>(d_rows), mask, w, g, static_cast<const long long *>(tile_off),
+                               static_cast<const int16_t *>(d_rows), mask, w, g, static_cast<const long long *>(sel.tile_off),
                                static_cast<int16_t *>(d_out), static_cast<long long *>(d_starts));
     }
     const int rc2 = scratch_release(h);
@@ -3340,8 +3127,8 @@ int mfcc_hip_gate_push_dev(mfcc_hip_gate *g, const void *d_rows, const size_t *f
                                   (long long)(win_offsets[u + 1] - win_offsets[u]), (long long)win_offsets[u], 0};
     }
     // the records at the front of h->d_out, as the banks keep theirs
-    if ((rc = desc_stage(h, &h->d_out, &h->d_out_bytes, rec_ll * sizeof(long long) + 64, pd, rec_ll))) return rc;
-    auto *d_rec = static_cast<const mfcc_gate::Rec *>(h->d_out);
+    if ((rc = desc_stage(h, h->d_out, rec_ll * sizeof(long long) + 64, pd, rec_ll))) return rc;
+    auto *d_rec = static_cast<const mfcc_gate::Rec *>(h->d_out.p);
     const int16_t *fresh = static_cast<const int16_t *>(d_rows);
     if (nwmax)
         hipLaunchKernelGGL(mfcc_gate::gate_live_kernel,
@@ -3387,9 +3174,9 @@ int mfcc_hip_gate_window_dev(mfcc_hip_gate *g, const size_t *lines, size_t n, vo
         const size_t last = gate_windows(g->seen[lines[i]], size_t(geo.n_frames), size_t(geo.stride)) - 1;
         rec[i] = mfcc_gate::WinRec{(long long)lines[i], (long long)(last * size_t(geo.stride))};
     }
-    if ((rc = desc_stage(h, &h->d_out, &h->d_out_bytes, rec_ll * sizeof(long long) + 64, pd, rec_ll))) return rc;
+    if ((rc = desc_stage(h, h->d_out, rec_ll * sizeof(long long) + 64, pd, rec_ll))) return rc;
     hipLaunchKernelGGL(mfcc_gate::gate_window_kernel, dim3(gate_grid(h, (long long)n)), dim3(mfcc_gate::kThreads), 0, h->stream,
-                       static_cast<const int16_t *>(g->d_ring), static_cast<const mfcc_gate::WinRec *>(h->d_out), (long long)n,
+                       static_cast<const int16_t *>(g->d_ring), static_cast<const mfcc_gate::WinRec *>(h->d_out.p), (long long)n,
                        geo, g->D, static_cast<int16_t *>(d_out));
     HIP_TRY(h, hipGetLastError());
     return scratch_release(h);
