@@ -498,6 +498,63 @@ int  mfcc_hip_set_pcen(mfcc_hip_handle *h, const mfcc_hip_pcen *p);
 int  mfcc_hip_pcen_dev(mfcc_hip_handle *h, void *d_rows, int row_width, const size_t *seg_offsets, size_t n_segs,
                        const mfcc_hip_pcen *p);
 
+/* ---- sample formats ----------------------------------------------------------------------
+ * What a sample pointer holds is a property of the handle.  Every format is decoded to int16 on the device by one
+ * streaming pass (decode_samples_kernel) in front of the kernels; from there on a call takes exactly the route it takes
+ * on int16 input.  The rules, all integers 32-bit two's complement; b is the byte, w the 32-bit word, x the float:
+ *   ULAW   (ITU-T G.711 mu-law)   u = ~b & 0xff;  t = (((u & 0x0f) << 3) + 0x84) << ((u & 0x70) >> 4);
+ *                                 s = (u & 0x80) ? 0x84 - t : t - 0x84
+ *                                 (0x00 -> -32124, 0x80 -> +32124, 0x7f and 0xff -> 0)
+ *   ALAW   (ITU-T G.711 A-law)    a = b ^ 0x55;  seg = (a & 0x70) >> 4;  t = (a & 0x0f) << 4;
+ *                                 seg == 0: t += 8;  seg == 1: t += 0x108;  otherwise t = (t + 0x108) << (seg - 1);
+ *                                 s = (a & 0x80) ? t : -t
+ *                                 (0x55 -> -8, 0xd5 -> +8, 0x2a -> -32256, 0xaa -> +32256)
+ *   U8     (offset binary)        s = (b - 128) << 8
+ *   I2S32                         s = (int16_t)(uint16_t)((uint32_t)w >> 10): bits 25..10 of the word, what the
+ *                                 reference's I2S receiver keeps, `source.data.eq(da_shreg[-22:-6])`  mfcc/io/i2s_mic.py:62
+ *   S32                           s = w >> 16, arithmetic shift
+ *   F32                           v = x * 32768.0f (one fp32 multiply);  r = rintf(v) (ties to even);
+ *                                 s = r < -32768 ? -32768 : r > 32767 ? 32767 : (int)r;  NaN gives 0, +-inf saturate
+ *   S16                           identity                                                                          */
+enum mfcc_hip_sample_format {
+    MFCC_HIP_SAMPLE_S16   = 0,  /* int16: the state after mfcc_hip_create, today's bits */
+    MFCC_HIP_SAMPLE_ULAW  = 1,  /* 1 byte, ITU-T G.711 mu-law */
+    MFCC_HIP_SAMPLE_ALAW  = 2,  /* 1 byte, ITU-T G.711 A-law */
+    MFCC_HIP_SAMPLE_U8    = 3,  /* 1 byte, offset binary (8-bit WAV) */
+    MFCC_HIP_SAMPLE_I2S32 = 4,  /* 4 bytes, an I2S word as the reference's receiver cuts it */
+    MFCC_HIP_SAMPLE_S32   = 5,  /* 4 bytes, int32 full scale */
+    MFCC_HIP_SAMPLE_F32   = 6   /* 4 bytes, float in [-1, 1) */
+};
+/* bytes of one sample: 2, 1, 1, 1, 4, 4, 4; 0 for an unknown format */
+size_t mfcc_hip_sample_size(int format);
+/* Host only, no GPU, no handle: the rules above on n samples at `in` (any alignment) -> out[n].  An unknown format, or a
+ * NULL pointer with n > 0: MFCC_HIP_ERROR_INVALID_PARAM.  For callers and for the CPU tests. */
+int  mfcc_hip_decode_host(int format, const void *in, size_t n, int16_t *out);
+/* The kernels' direct entry: n samples at d_in (aligned to the format's sample size; 1-byte formats take any address)
+ * -> int16 at d_out (2-byte aligned).  The two byte ranges must not overlap; a misaligned or NULL pointer, an overlap or
+ * an unknown format: MFCC_HIP_ERROR_INVALID_PARAM.  Asynchronous on the handle's stream; n = 0 is a no-op that looks at
+ * no pointer; any handle (its own format is not read).  S16 is a copy. */
+int  mfcc_hip_decode_dev(mfcc_hip_handle *h, int format, const void *d_in, size_t n, void *d_out);
+/* The handle's input format, applied to every call enqueued after it: EVERY sample pointer of every entry point is read
+ * in it -- dense, ragged, host and device buffers, float and fixed, mfcc_hip_stream_push, mfcc_hip_bank_push / _push_dev
+ * and mfcc_hip_time_dev (which times the decode too).  The declared `const int16_t *` stays; the caller casts.  Sample
+ * counts, strides, `offsets` and `halo` keep counting SAMPLES, not bytes; the halo sample is decoded like any other.
+ * The result is, bit for bit, what the same call returns on an S16 handle given mfcc_hip_decode_host of the input.
+ * A device pointer must be aligned to the format's sample size, else MFCC_HIP_ERROR_INVALID_PARAM.
+ * A call on a handle with another format than S16 needs 2 * samples bytes of device memory for the decoded samples (a
+ * scratch area of the handle that grows on demand and is never shrunk; a dense strided call rounds every channel up to 8
+ * samples): MFCC_HIP_ERROR_NO_MEM if it cannot be had.  The host-buffer entry points copy the raw bytes through the
+ * same chunked copy pipeline (chunks are cut by sample count, as for S16) and decode every chunk on the device.
+ * MFCC_HIP_SAMPLE_S16 is the state after mfcc_hip_create: no decode is enqueued, every entry point gives the bits and
+ * the launches it gives without this call, mfcc_hip_kernel_name does not depend on the format.
+ * A session or a bank reads its samples in the format its handle had when it was created: like the other setters this
+ * call answers MFCC_HIP_ERROR_BUSY while sessions live.  Unknown format or NULL handle: MFCC_HIP_ERROR_INVALID_PARAM.
+ * mfcc_hip_convert_wav(s) read 16-bit PCM files whatever the format.  MFCC_HIP_ERROR_BUFFER_SMALL and
+ * MFCC_HIP_ERROR_INVALID_PARAM still consume nothing.  The parameter block and the ABI version are unchanged. */
+int  mfcc_hip_set_sample_format(mfcc_hip_handle *h, int format);
+/* the handle's format (MFCC_HIP_SAMPLE_S16 for NULL) */
+int  mfcc_hip_sample_format(const mfcc_hip_handle *h);
+
 /* name of the kernel symbol process_*_dev launches for this handle (to match rocprofv3 rows).  A log-mel handle runs
  * the log-mel instantiation of the kernel named (the default form: MFCC_HIP_FUSED512 / MFCC_HIP_FUSED1024 do not
  * apply to it) */

@@ -51,6 +51,15 @@ POWER_THRESHOLD = 100000000
 MEL_NOTEBOOK = 0
 MEL_HTK = 1
 
+# enum mfcc_hip_sample_format
+SAMPLE_S16 = 0
+SAMPLE_ULAW = 1
+SAMPLE_ALAW = 2
+SAMPLE_U8 = 3
+SAMPLE_I2S32 = 4
+SAMPLE_S32 = 5
+SAMPLE_F32 = 6
+
 TABLE_WINDOW_F32 = 0
 TABLE_MEL_POINTS_I32 = 1
 TABLE_MEL_DENSE_F32 = 2
@@ -215,6 +224,12 @@ SYMBOLS = {
     "mfcc_hip_pcen_dev": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, _SZ, C.POINTER(Pcen)]),
     "mfcc_hip_bank_create_online_pcen": (C.c_int, [_H, _SZ, C.POINTER(Pcen), C.c_int, C.c_int, C.c_int, C.c_int,
                                                    C.POINTER(_H)]),
+    # sample formats: the host-only helpers, the kernels' direct entry and the handle's setting
+    "mfcc_hip_sample_size": (C.c_size_t, [C.c_int]),
+    "mfcc_hip_decode_host": (C.c_int, [C.c_int, C.c_void_p, _SZ, C.c_void_p]),
+    "mfcc_hip_decode_dev": (C.c_int, [_H, C.c_int, C.c_void_p, _SZ, C.c_void_p]),
+    "mfcc_hip_set_sample_format": (C.c_int, [_H, C.c_int]),
+    "mfcc_hip_sample_format": (C.c_int, [_H]),
 }
 
 _lib = None

@@ -33,6 +33,20 @@ _NORMALIZE = {None: _lib.NORMALIZE_NONE, "none": _lib.NORMALIZE_NONE, "mean": _l
               "meanvar": _lib.NORMALIZE_MEAN_VAR}
 
 
+# sample_format -> (enum mfcc_hip_sample_format, the dtype a sample array must have)
+_SAMPLE = {"s16": (_lib.SAMPLE_S16, np.int16), "ulaw": (_lib.SAMPLE_ULAW, np.uint8), "alaw": (_lib.SAMPLE_ALAW, np.uint8),
+           "u8": (_lib.SAMPLE_U8, np.uint8), "i2s32": (_lib.SAMPLE_I2S32, np.int32), "s32": (_lib.SAMPLE_S32, np.int32),
+           "f32": (_lib.SAMPLE_F32, np.float32)}
+
+
+def _sample_args(sample_format):
+    """(name, enum value, NumPy dtype) of a sample format, or ValueError."""
+    if not isinstance(sample_format, str) or sample_format not in _SAMPLE:
+        raise ValueError("sample_format must be one of %s, not %r" % (", ".join(repr(k) for k in _SAMPLE), sample_format))
+    code, dtype = _SAMPLE[sample_format]
+    return sample_format, code, np.dtype(dtype)
+
+
 def normalize_mode(mode) -> int:
     """``None`` / ``"none"``, ``"mean"`` or ``"meanvar"`` -> ``enum mfcc_hip_normalize``."""
     try:
@@ -345,19 +359,52 @@ class MFCC:
     0.5, 1e-6; ``time_constant`` is in seconds and converts like librosa's.  ``eps`` and ``delta`` are in the units of
     this handle's mel energies (they carry ``power_scale``); nothing is rescaled.  It runs before normalization and
     deltas, the VAD still decides on the raw rows; the entry points a normalizing handle refuses refuse it too.
+
+    ``sample_format`` is what a sample array holds: ``"s16"`` (int16, the default: nothing changes), ``"ulaw"`` /
+    ``"alaw"`` (G.711 bytes, uint8), ``"u8"`` (offset binary, uint8), ``"i2s32"`` (int32 I2S words as the reference's
+    receiver cuts them: bits 25..10), ``"s32"`` (int32 full scale) or ``"f32"`` (float32 in [-1, 1), rounded to
+    nearest even and saturated).  The samples are decoded to int16 on the device in front of the kernels
+    (include/mfcc_hip.h has every rule, :func:`decode` applies them alone) and every method -- ``process``,
+    ``process_fixed``, ``process_batch``, ``process_packed``, :meth:`stream`, :meth:`stream_bank` -- then REQUIRES the
+    matching dtype (``TypeError`` otherwise) and returns, bit for bit, what an ``"s16"`` handle returns on the decoded
+    samples.  ``convert*`` keep reading 16-bit WAV files.
     """
 
     deltas, delta_window = 0, 2                 # the state after mfcc_hip_create
     vad = None
+    sample_format = "s16"
+
+    def _sample_np(self):
+        """The NumPy dtype a sample array of this handle must have."""
+        return np.dtype(_SAMPLE[self.sample_format][1])
+
+    def _samples_host(self, x, what="pcm"):
+        """``x`` as a contiguous NumPy array of the handle's sample dtype, or TypeError."""
+        x = np.ascontiguousarray(x)
+        if x.dtype != self._sample_np():
+            if self.sample_format == "s16":
+                raise TypeError("%s must be int16 (the core's sink is signed 16 bit, mfcc.py:29)" % what)
+            raise TypeError("%s must be %s for sample_format=%r, not %s"
+                            % (what, self._sample_np().name, self.sample_format, x.dtype))
+        return x
+
+    def _samples_dev_ok(self, t):
+        """Whether a torch tensor is a CUDA(HIP) tensor of the handle's sample dtype."""
+        import torch
+        return t.is_cuda and t.dtype == getattr(torch, self._sample_np().name)
+
+    def _dev_what(self):
+        return "CUDA(HIP) %s" % self._sample_np().name
 
     def __init__(self, width=16, nfft=512, samplerate=16e3, nfilters=16, nceptrums=16, *, hop=None,
                  pad_mode="notebook", power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra",
                  normalize=None, deltas=0, delta_window=2, normalize_window=None, normalize_min_window=_MIN_WINDOW,
                  normalize_center=True, vad=None, vad_column=0, vad_energy_threshold=5.0, vad_energy_mean_scale=0.5,
                  vad_frames_context=0, vad_proportion_threshold=0.6, win_length=None, mel="notebook", fmin=0.0,
-                 fmax=None, pcen=None):
+                 fmax=None, pcen=None, sample_format="s16"):
         if width != 16:
             raise ValueError("only width=16 (int16 PCM) is supported, like every reference target")
+        fmt_name, fmt_code, _ = _sample_args(sample_format)
         _pcen_args(pcen, samplerate, hop or int(nfft) // 3)
         self.win_length = _win_length(win_length, nfft, hop)
         self.mel, self.fmin, self.fmax, bank = _mel_bank(mel, fmin, fmax, samplerate, nfilters)
@@ -390,6 +437,8 @@ class MFCC:
         _lib.check(self._lib.mfcc_hip_create_banked(C.byref(self._params), self.win_length, C.byref(bank), C.byref(h)),
                    "mfcc_hip_create")
         self._h = h
+        if fmt_code != _lib.SAMPLE_S16:
+            self.set_sample_format(fmt_name)
         self.pcen = None
         if pcen is not None and pcen is not False:
             self.set_pcen(pcen)
@@ -408,6 +457,13 @@ class MFCC:
         if vad_args[0] != _lib.VAD_OFF:
             self.set_vad(vad, vad_column, vad_energy_threshold, vad_energy_mean_scale, vad_frames_context,
                          vad_proportion_threshold)
+
+    def set_sample_format(self, sample_format):
+        """What the sample arrays of every call after this one hold (``"s16"``, ``"ulaw"``, ``"alaw"``, ``"u8"``,
+        ``"i2s32"``, ``"s32"``, ``"f32"``); ``BUSY`` while sessions or banks of this handle live."""
+        name, code, _ = _sample_args(sample_format)
+        _lib.check(self._lib.mfcc_hip_set_sample_format(self._h, code), "set_sample_format")
+        self.sample_format = name
 
     def set_vad(self, mode, column=0, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0,
                 proportion_threshold=0.6):
@@ -638,9 +694,7 @@ class MFCC:
 
     # -- the hot path ---------------------------------------------------------------
     def _host(self, pcm, fixed):
-        pcm = np.ascontiguousarray(pcm)
-        if pcm.dtype != np.int16:
-            raise TypeError("pcm must be int16 (the core's sink is signed 16 bit, mfcc.py:29)")
+        pcm = self._samples_host(pcm)
         squeeze = pcm.ndim == 1
         if squeeze:
             pcm = pcm[None, :]
@@ -658,8 +712,8 @@ class MFCC:
 
     def _dev(self, pcm, fixed, halo, out):
         import torch
-        if pcm.dtype != torch.int16 or not pcm.is_cuda:
-            raise TypeError("device path needs a CUDA(HIP) int16 tensor")
+        if not self._samples_dev_ok(pcm):
+            raise TypeError("device path needs a %s tensor" % self._dev_what())
         squeeze = pcm.dim() == 1
         if squeeze:
             pcm = pcm[None, :]
@@ -744,12 +798,15 @@ class MFCC:
         ``process`` / ``process_fixed`` on each utterance."""
         if len(utterances) and _is_torch(utterances[0]):
             return self._batch_dev(utterances, fixed)
-        utts = [np.ascontiguousarray(u, dtype=np.int16).reshape(-1) for u in utterances]
+        if self.sample_format == "s16":
+            utts = [np.ascontiguousarray(u, dtype=np.int16).reshape(-1) for u in utterances]
+        else:
+            utts = [self._samples_host(u, "utterances").reshape(-1) for u in utterances]
         n = len(utts)
         offsets = np.zeros(n + 1, dtype=np.uint64)
         if n:
             offsets[1:] = np.cumsum([u.size for u in utts], dtype=np.uint64)
-        flat = np.concatenate(utts) if n and int(offsets[-1]) else np.zeros(0, dtype=np.int16)
+        flat = np.concatenate(utts) if n and int(offsets[-1]) else np.zeros(0, dtype=self._sample_np())
         fo = np.zeros(n + 1, dtype=np.uint64)
         nf = sum(self.num_frames(u.size) for u in utts)
         out = np.empty((nf, self._row(fixed)), dtype=np.int16 if fixed else np.float32)
@@ -763,20 +820,20 @@ class MFCC:
         """``process_batch`` for torch CUDA int16 tensors: stays on the device, asynchronous on the current stream."""
         import torch
         utts = [u.reshape(-1) for u in utterances]
-        if any(u.dtype != torch.int16 or not u.is_cuda for u in utts):
-            raise TypeError("device path needs CUDA(HIP) int16 tensors")
+        if any(not self._samples_dev_ok(u) for u in utts):
+            raise TypeError("device path needs %s tensors" % self._dev_what())
         n = len(utts)
         offsets = np.zeros(n + 1, dtype=np.uint64)
         offsets[1:] = np.cumsum([u.numel() for u in utts], dtype=np.uint64)
         # utterances that are consecutive views of one buffer (a corpus already laid out in HBM) are used in place
         in_place = n > 0 and all(u.is_contiguous() for u in utts) and all(
-            utts[i].data_ptr() + 2 * utts[i].numel() == utts[i + 1].data_ptr() and
+            utts[i].data_ptr() + utts[i].element_size() * utts[i].numel() == utts[i + 1].data_ptr() and
             utts[i].untyped_storage().data_ptr() == utts[0].untyped_storage().data_ptr() for i in range(n - 1))
         if in_place:
             base = utts[0]
             flat = torch.as_strided(base, (int(offsets[-1]),), (1,), storage_offset=base.storage_offset())
         else:
-            flat = torch.cat(utts) if int(offsets[-1]) else torch.zeros(0, dtype=torch.int16, device=utts[0].device)
+            flat = torch.cat(utts) if int(offsets[-1]) else torch.zeros(0, dtype=utts[0].dtype, device=utts[0].device)
         out, fo = self.process_packed(flat, offsets, fixed=fixed)
         return [out[int(fo[i]):int(fo[i + 1])] for i in range(n)]
 
@@ -788,8 +845,8 @@ class MFCC:
         as channels of one multi-channel launch (no packing copy); the bits are the same.  On a ``vad="select"`` handle
         ``out`` still needs room for every frame; what is returned is ``(out[:fo[-1]], fo)``, the voiced rows."""
         import torch
-        if flat.dtype != torch.int16 or not flat.is_cuda or flat.dim() != 1 or not flat.is_contiguous():
-            raise TypeError("flat must be a contiguous 1-D CUDA(HIP) int16 tensor")
+        if not self._samples_dev_ok(flat) or flat.dim() != 1 or not flat.is_contiguous():
+            raise TypeError("flat must be a contiguous 1-D %s tensor" % self._dev_what())
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = len(offsets) - 1
         if n < 0 or (n >= 0 and len(offsets) and int(offsets[-1]) > flat.numel()):
@@ -1022,7 +1079,10 @@ class MfccStream:
     def push(self, samples) -> np.ndarray:
         """``sink``: int16 samples in; returns the ``(frames, num_features)`` they complete (possibly 0 rows)."""
         samples = np.ascontiguousarray(samples)
-        if samples.dtype != np.int16 or samples.ndim != 1:
+        if samples.dtype != self._m._sample_np() or samples.ndim != 1:
+            if self._m.sample_format != "s16":
+                raise TypeError("samples must be a 1-D %s array for sample_format=%r"
+                                % (self._m._sample_np().name, self._m.sample_format))
             raise TypeError("samples must be a 1-D int16 array (the core's sink is signed 16 bit, mfcc.py:29)")
         out = self._out(int(self._lib.mfcc_hip_stream_max_frames(self._s, samples.size)))
         nf = C.c_size_t(0)
@@ -1165,12 +1225,15 @@ class MfccStreamBank:
         if len(chunks) != self.n_streams:
             raise ValueError("one chunk per stream: %d, not %d" % (self.n_streams, len(chunks)))
         cs = [np.ascontiguousarray(c) for c in chunks]
-        if any(c.dtype != np.int16 or c.ndim != 1 for c in cs):
+        dt = self._m._sample_np()
+        if any(c.dtype != dt or c.ndim != 1 for c in cs):
+            if self._m.sample_format != "s16":
+                raise TypeError("chunks must be 1-D %s arrays for sample_format=%r" % (dt.name, self._m.sample_format))
             raise TypeError("chunks must be 1-D int16 arrays (the core's sink is signed 16 bit, mfcc.py:29)")
         n = self.n_streams
         offsets = np.zeros(n + 1, dtype=np.uint64)
         offsets[1:] = np.cumsum([c.size for c in cs], dtype=np.uint64)
-        flat = np.concatenate(cs) if int(offsets[-1]) else np.zeros(0, dtype=np.int16)
+        flat = np.concatenate(cs) if int(offsets[-1]) else np.zeros(0, dtype=dt)
         nf = int(self._plan(offsets)[-1])
         out = np.empty((nf, self._row()), dtype=np.int16 if self.fixed else np.float32)
         fo = np.zeros(n + 1, dtype=np.uint64)
@@ -1187,8 +1250,8 @@ class MfccStreamBank:
         of every stream.  Lines in lockstep pass ``x.reshape(-1)`` with ``arange`` offsets and view the result as
         ``(n_streams, frames, num_features)``."""
         import torch
-        if flat.dtype != torch.int16 or not flat.is_cuda or flat.dim() != 1 or not flat.is_contiguous():
-            raise TypeError("flat must be a contiguous 1-D CUDA(HIP) int16 tensor")
+        if not self._m._samples_dev_ok(flat) or flat.dim() != 1 or not flat.is_contiguous():
+            raise TypeError("flat must be a contiguous 1-D %s tensor" % self._m._dev_what())
         offsets = self._offsets(offsets)
         if int(offsets[-1]) > flat.numel():
             raise ValueError("offsets run past the end of flat")
@@ -1360,6 +1423,40 @@ class MfccPowerGate:
             _lib.check(self._lib.mfcc_hip_gate_window_dev(self._g, s.ctypes.data_as(C.c_void_p), n,
                                                           C.c_void_p(out.data_ptr())), "gate_window_dev")
         return out
+
+
+_decode_handles = {}          # device index -> the handle decode() launches on (mfcc_hip_decode_dev takes any)
+
+
+def decode(x, sample_format, mfcc=None):
+    """The int16 samples a handle with ``sample_format`` computes on, by the rules of include/mfcc_hip.h, same shape as
+    ``x`` (whose dtype must be the format's: uint8, int32, float32 or int16).  A NumPy array goes through
+    ``mfcc_hip_decode_host`` (no GPU needed); a CUDA tensor through ``mfcc_hip_decode_dev``, asynchronous on the current
+    torch stream, on ``mfcc`` (any handle of that device) or on a handle this function keeps per device."""
+    name, code, dtype = _sample_args(sample_format)
+    lib = _lib.load()
+    if not _is_torch(x):
+        x = np.ascontiguousarray(x)
+        if x.dtype != dtype:
+            raise TypeError("x must be %s for sample_format=%r, not %s" % (dtype.name, name, x.dtype))
+        out = np.empty(x.shape, dtype=np.int16)
+        _lib.check(lib.mfcc_hip_decode_host(code, x.ctypes.data_as(C.c_void_p), x.size, out.ctypes.data_as(C.c_void_p)),
+                   "decode_host")
+        return out
+    import torch
+    if not x.is_cuda or x.dtype != getattr(torch, dtype.name):
+        raise TypeError("x must be a CUDA(HIP) %s tensor for sample_format=%r" % (dtype.name, name))
+    x = x.contiguous()
+    if mfcc is None:
+        mfcc = _decode_handles.get(x.device.index)
+        if mfcc is None:
+            mfcc = _decode_handles[x.device.index] = MFCC(nfft=512, nfilters=32, nceptrums=13, device=x.device.index)
+    mfcc._check_device(x)
+    out = torch.empty(x.shape, device=x.device, dtype=torch.int16)
+    with mfcc._on_torch_stream(x.device):
+        _lib.check(lib.mfcc_hip_decode_dev(mfcc._h, code, C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(out.data_ptr())),
+                   "decode_dev")
+    return out
 
 
 def lift_file(mfcc_in, lift_out, nceptrums=32, L=22) -> int:

@@ -54,4 +54,22 @@ inline bool launch_geom(long long frames_per_ch, long long total_frames, long lo
     return true;
 }
 
+// ---- the sample decode (kernel_decode.hpp): a streaming pass, grid-stride over groups of kDecodeGroup samples per lane.
+// x strides over the groups of a row, y over the rows; the grid comes from the CU count -- at most kDecodeBlocksPerCu
+// workgroups per CU over both axes (32 waves per CU, what a CU holds) -- and is only cut where there are fewer groups
+// than that.  One trip of the grid covers gx * kDecodeThreads groups of every row
+constexpr int kDecodeThreads = 256, kDecodeGroup = 8, kDecodeBlocksPerCu = 8, kDecodeMaxRowsY = 65535;
+
+inline void decode_grid(long long groups_per_row, long long rows, int n_cu, unsigned &gx, unsigned &gy) {
+    long long y = rows < kDecodeMaxRowsY ? rows : kDecodeMaxRowsY;
+    if (y < 1) y = 1;
+    long long cap = (long long)n_cu * kDecodeBlocksPerCu / y;
+    if (cap < 1) cap = 1;
+    long long x = (groups_per_row + kDecodeThreads - 1) / kDecodeThreads;
+    if (x > cap) x = cap;
+    if (x < 1) x = 1;
+    gx = (unsigned)x;
+    gy = (unsigned)y;
+}
+
 }  // namespace mfcc_fc

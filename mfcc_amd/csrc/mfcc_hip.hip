@@ -36,6 +36,7 @@
 #include "kernel_stream_bank.hpp"
 #include "kernel_stream_bank_online.hpp"
 #include "kernel_gate.hpp"
+#include "kernel_decode.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -287,6 +288,10 @@ struct mfcc_hip_handle {
     bool pcen_on = false;
     mfcc_pcen::Prm pcen{};
     DevBuf d_pcen;
+    // sample format (mfcc_hip_set_sample_format): what every sample pointer holds; the decoded int16 samples of a call
+    // (d_dec) and the raw bytes of a session's push on their way to the decode (d_raw)
+    int sample_fmt = MFCC_HIP_SAMPLE_S16;
+    DevBuf d_dec, d_raw;
 };
 
 namespace {
@@ -378,6 +383,45 @@ int desc_stage(mfcc_hip_handle *h, DevBuf &b, size_t want, mfcc_hip_handle::Pinn
     if (want && (rc = ensure(h, b, want))) return rc;
     if ((rc = scratch_acquire(h))) return rc;
     return pd ? desc_upload(h, pd, n_ll, static_cast<char *>(b.p) + at) : MFCC_HIP_SUCCESS;
+}
+
+// ---- sample formats (kernel_decode.hpp): one streaming pass in front of the kernels turns the
+// samples of a call into int16 in h->d_dec, and the call goes on from there as it does on int16 input
+inline bool decodes(const mfcc_hip_handle *h) { return h->sample_fmt != MFCC_HIP_SAMPLE_S16; }
+inline size_t sample_bytes(const mfcc_hip_handle *h) { return mfcc_decode::sample_size(h->sample_fmt); }
+inline bool sample_aligned(const mfcc_hip_handle *h, const void *p) {
+    return (reinterpret_cast<uintptr_t>(p) & (sample_bytes(h) - 1)) == 0;
+}
+// sample i behind p, in the handle's format
+inline const void *sample_at(const mfcc_hip_handle *h, const void *p, size_t i) {
+    return static_cast<const char *>(p) + i * sample_bytes(h);
+}
+
+// rows of n samples in the handle's format (row r at sample r * in_stride of d_in) -> int16 rows of out_stride samples
+// at d_out, on the handle's stream.  More than one row: out_stride is a multiple of 8, or the rows lie back to back
+int decode_rows(mfcc_hip_handle *h, const void *d_in, size_t n, size_t rows, size_t in_stride, int16_t *d_out,
+                size_t out_stride) {
+    if (!n || !rows) return MFCC_HIP_SUCCESS;
+    if (rows > 1 && in_stride == n && out_stride == n) {         // back to back on both sides: one row
+        n *= rows;
+        rows = 1;
+    }
+    if (!mfcc_decode::launch(h->sample_fmt, d_in, d_out, n, rows, in_stride, out_stride, h->n_cu, h->stream))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    HIP_TRY(h, hipGetLastError());
+    return MFCC_HIP_SUCCESS;
+}
+
+// ... into the handle's scratch area, grown and taken (the caller releases it behind the kernels that read it): rows
+// back to back where the input's are, else every row rounded up to 8 samples
+int decode_to_scratch(mfcc_hip_handle *h, const void *d_in, size_t n, size_t rows, size_t in_stride, const int16_t **out,
+                      size_t *out_stride) {
+    const size_t stride = rows <= 1 || in_stride == n ? n : (n + 7) & ~size_t(7);
+    int rc = ensure(h, h->d_dec, rows * stride * sizeof(int16_t) + 64);
+    if (rc || (rc = scratch_acquire(h))) return rc;
+    *out = static_cast<const int16_t *>(h->d_dec.p);
+    *out_stride = stride;
+    return decode_rows(h, d_in, n, rows, rows <= 1 ? n : in_stride, static_cast<int16_t *>(h->d_dec.p), stride);
 }
 
 struct Arena {
@@ -1069,6 +1113,27 @@ int launch_float_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t str
     return scratch_release(h);
 }
 
+// The dense device entries on a handle with a sample format: the samples the call reads -- n + halo of every channel --
+// decoded into the scratch area, then the route of int16 input on it.  MFCC_HIP_SAMPLE_S16: that route and nothing else
+int dense_dev(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo, void *d_out,
+              size_t *n_frames) {
+    auto route = [&](const void *p, size_t st) {
+        return fixed ? launch(h, true, p, n, st, nch, halo, d_out, n_frames)
+                     : launch_float_dev(h, p, n, st, nch, halo, d_out, n_frames);
+    };
+    if (!h || !decodes(h)) return route(d_pcm, stride);
+    // what launch() refuses, before anything is read
+    if ((!d_pcm && n * nch) || halo < 0 || halo > 1 || !sample_aligned(h, d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (nch > 1 && stride < n + size_t(halo)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (count_frames(h->r, n) == 0 || nch == 0 || !d_out) return route(d_pcm, stride);      // no sample is read
+    DeviceGuard guard(h->device);
+    const int16_t *dec = nullptr;
+    size_t dec_stride = 0;
+    int rc = decode_to_scratch(h, d_pcm, n + size_t(halo), nch, stride, &dec, &dec_stride);
+    if (rc || (rc = route(dec, dec_stride))) return rc;
+    return scratch_release(h);
+}
+
 // ---- host buffers in, host buffers out: the shape of the reference's own caller (software/main.c:100-177: file in,
 // file out).  The input crosses PCIe at 340 B per frame, which is 25 times what the kernel needs per frame in time, so this
 // path is a COPY pipeline: the batch is cut into chunks of ~64 MB (whole channels, or frame ranges of a long channel with
@@ -1081,7 +1146,7 @@ int launch_float_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t str
 // 16 MB 3.94 -- every chunk costs ~60 us of calls and a kernel launch that cannot fill the chip.  A batch that fits one
 // chunk takes the plain blocking copies (pinning it first only adds its 13 us per MB in front).
 struct HostChunk {
-    const int16_t *in;      // first sample handed to the kernel (the halo sample when halo = 1)
+    const void *in;         // first sample handed to the kernel (the halo sample when halo = 1)
     size_t in_samples;      // samples copied (all channels of the chunk; incl. the halo sample)
     size_t n, stride, nch;  // launch geometry: samples per channel after the halo, channel stride, channels
     int halo;
@@ -1274,6 +1339,10 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     const size_t kChunkBytes = host_chunk_bytes();
     // deltas: the static rows are 1 + K times narrower than the output rows
     const int K = fixed ? 0 : h->delta_order;
+    // a sample format: the chunks are cut by sample count exactly as for int16, their raw bytes cross the wire and every
+    // chunk is decoded on the device in front of its kernel
+    const bool dec = decodes(h);
+    const size_t ssz = sample_bytes(h);
 
     // ---- the chunks
     std::vector<HostChunk> chunks;
@@ -1283,7 +1352,7 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
         if (per < 1) per = 1;
         for (size_t c0 = 0; c0 < nch; c0 += per) {
             const size_t k = std::min(per, nch - c0);
-            chunks.push_back({pcm + c0 * n, k * n, n, n, k, 0, nf, k * nf * ncep, c0 * nf * ncep});
+            chunks.push_back({sample_at(h, pcm, c0 * n), k * n, n, n, k, 0, nf, k * nf * ncep, c0 * nf * ncep});
         }
     } else {
         // long channels: frame ranges [f0, f1) of one channel -- samples f0 * hop - 1 (history) .. (f1 - 1) * hop + frame_len
@@ -1295,7 +1364,7 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
                 const size_t s0 = f0 * hop - halo;
                 size_t s1 = (f1 - 1) * hop + flen;
                 if (s1 > n) s1 = n;                                  // the zero-padded tail of STREAM framing
-                chunks.push_back({pcm + c * n + s0, s1 - s0, s1 - s0 - halo, s1 - s0, 1, int(halo), f1 - f0,
+                chunks.push_back({sample_at(h, pcm, c * n + s0), s1 - s0, s1 - s0 - halo, s1 - s0, 1, int(halo), f1 - f0,
                                   (f1 - f0) * ncep, (c * nf + f0) * ncep});
             }
     }
@@ -1321,9 +1390,17 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     std::vector<PipeChunk> pc;
     pc.reserve(chunks.size());
     for (const HostChunk &c : chunks)
-        pc.push_back({c.in, c.in_samples * sizeof(int16_t), out + c.out_off, whole ? 0 : c.out_elems * sizeof(OutT)});
-    int rc = run_host_pipeline(h, pc, pcm, nch * ch_bytes, out, whole ? 0 : n_out * sizeof(OutT), [&](size_t i, void *d_in, void *d_out) {
+        pc.push_back({c.in, c.in_samples * ssz, out + c.out_off, whole ? 0 : c.out_elems * sizeof(OutT)});
+    int rc = run_host_pipeline(h, pc, pcm, nch * n * ssz, out, whole ? 0 : n_out * sizeof(OutT), [&](size_t i, void *d_raw, void *d_out) {
         const HostChunk &c = chunks[i];
+        const void *d_in = d_raw;
+        size_t in_stride = c.stride;
+        if (dec) {
+            const int16_t *p = nullptr;
+            const int drc = decode_to_scratch(h, d_raw, c.n + size_t(c.halo), c.nch, c.stride, &p, &in_stride);
+            if (drc) return drc;
+            d_in = p;
+        }
         void *rows = whole ? static_cast<void *>(d_full + c.out_off) : d_out;
         PostRoute rt{};
         if (post) {
@@ -1331,13 +1408,13 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
             rt = route_to(h, static_cast<float *>(rows), whole ? c.out_off / size_t(1 + K) : 0);
             rows = rt.raw;
         }
-        const int lrc = launch(h, fixed, d_in, c.n, c.stride, c.nch, c.halo, rows, nullptr, c.halo || c.frames != nf ? c.frames : 0);
+        const int lrc = launch(h, fixed, d_in, c.n, in_stride, c.nch, c.halo, rows, nullptr, c.halo || c.frames != nf ? c.frames : 0);
         if (lrc || whole || !post) return lrc;
         return post_chain(h, span_uniform(0, c.nch, nf), rt, nullptr);
     });
-    if (rc || !whole) return rc ? rc : (staged ? scratch_release(h) : MFCC_HIP_SUCCESS);
+    if (rc || !whole) return rc ? rc : (staged || dec ? scratch_release(h) : MFCC_HIP_SUCCESS);
     if ((rc = post_chain(h, span_uniform(0, nch, nf), route_to(h, reinterpret_cast<float *>(d_full)), nullptr))) return rc;
-    if (staged && (rc = scratch_release(h))) return rc;
+    if ((staged || dec) && (rc = scratch_release(h))) return rc;
     HIP_TRY(h, hipMemcpyAsync(out, d_full, n_out * sizeof(OutT), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MFCC_HIP_SUCCESS;
@@ -1553,8 +1630,8 @@ int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm,
 // write into the staging, which takes the frame count first.  With MFCC_HIP_VAD_SELECT every frame goes through the chain
 // into h->d_final, then only the voiced rows to d_out; frame_offsets describes those, and the call synchronizes (select_run)
 template <typename OutT>
-int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
-                       OutT *d_out, size_t cap, size_t *frame_offsets) {
+int process_ragged_dev_i16(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
+                           OutT *d_out, size_t cap, size_t *frame_offsets) {
     if (!h || fixed || !has_post(h) || !offsets || !frame_offsets)
         return process_ragged_dev_raw<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
     const bool sel = h->vad_mode != MFCC_HIP_VAD_OFF, staged = sel || h->delta_order || sliding(h);
@@ -1579,6 +1656,27 @@ int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, con
     if ((rc = post_chain(h, sp, rt, sel ? &pl : nullptr))) return rc;
     if (sel) return select_run(h, rt.out, int(WO), rt.voiced, pl, true, reinterpret_cast<float *>(d_out), frame_offsets);
     return rt.staged ? scratch_release(h) : MFCC_HIP_SUCCESS;
+}
+
+// ... on a handle with a sample format: the span offsets[0] .. offsets[n_utt] decoded into the scratch area, then the call
+// above on it with the offsets counted from its start.  MFCC_HIP_SAMPLE_S16: the call above and nothing else
+template <typename OutT>
+int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
+                       OutT *d_out, size_t cap, size_t *frame_offsets) {
+    if (!h || !decodes(h) || !offsets || !frame_offsets || !n_utt)
+        return process_ragged_dev_i16<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
+    if (!offsets_ok(offsets, n_utt) || !sample_aligned(h, d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const size_t span = offsets[n_utt] - offsets[0];
+    if (!span || !d_pcm)                                  // no sample is read
+        return process_ragged_dev_i16<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
+    std::vector<size_t> loc(n_utt + 1);
+    for (size_t u = 0; u <= n_utt; ++u) loc[u] = offsets[u] - offsets[0];
+    DeviceGuard guard(h->device);
+    const int16_t *dec = nullptr;
+    size_t stride = 0;
+    int rc = decode_to_scratch(h, sample_at(h, d_pcm, offsets[0]), span, 1, span, &dec, &stride);
+    if (rc || (rc = process_ragged_dev_i16<OutT>(h, fixed, dec, loc.data(), n_utt, d_out, cap, frame_offsets))) return rc;
+    return scratch_release(h);
 }
 
 // Host buffers: the corpus goes to the device in ONE copy (the span offsets[0] .. offsets[n_utt] as it lies), runs through
@@ -1611,8 +1709,9 @@ int process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const siz
     }
     DeviceGuard guard(h->device);
     // the same copy pipeline as process_host: chunks of whole utterances, ~64 MB each; every chunk is one call of the
-    // device-resident ragged path on its own offsets, its rows land behind those of the chunk before it
-    const size_t kChunkBytes = host_chunk_bytes();
+    // device-resident ragged path on its own offsets, its rows land behind those of the chunk before it.  A sample format:
+    // the chunks are cut by sample count as for int16, their raw bytes cross the wire and the ragged path decodes them
+    const size_t kChunkBytes = host_chunk_bytes(), ssz = sample_bytes(h);
     struct Range { size_t u0, u1, rows0; };
     std::vector<Range> ranges;
     std::vector<PipeChunk> pc;
@@ -1623,7 +1722,7 @@ int process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const siz
             const bool last = u + 1 == n_utt;
             if (last || (rel[u + 1] - rel[u0]) * sizeof(int16_t) >= kChunkBytes) {
                 ranges.push_back({u0, u + 1, rows0});
-                pc.push_back({pcm + offsets[0] + rel[u0], (rel[u + 1] - rel[u0]) * sizeof(int16_t), out + rows0 * ncep,
+                pc.push_back({sample_at(h, pcm, offsets[0] + rel[u0]), (rel[u + 1] - rel[u0]) * ssz, out + rows0 * ncep,
                               (rows - rows0) * ncep * sizeof(OutT)});
                 u0 = u + 1;
                 rows0 = rows;
@@ -1636,7 +1735,7 @@ int process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const siz
     // copy back shrinks and lands behind the voiced rows of the chunks before it
     const bool sel_mode = !fixed && h->vad_mode;
     size_t sel_rows = 0;
-    return run_host_pipeline(h, pc, pcm + offsets[0], rel[n_utt] * sizeof(int16_t), out, total * ncep * sizeof(OutT),
+    return run_host_pipeline(h, pc, sample_at(h, pcm, offsets[0]), rel[n_utt] * ssz, out, total * ncep * sizeof(OutT),
                              [&](size_t i, void *d_in, void *d_out) {
         const Range &r = ranges[i];
         const size_t k = r.u1 - r.u0;
@@ -1916,7 +2015,7 @@ void mfcc_hip_destroy(mfcc_hip_handle *h) {
     if (h->s_out) (void)hipStreamDestroy(h->s_out);
     if (h->arena) (void)hipFree(h->arena);
     for (DevBuf *b : {&h->d_in, &h->d_out, &h->d_norm, &h->d_pcen, &h->d_full, &h->d_stat, &h->d_dtab, &h->d_slide, &h->d_stab,
-                      &h->d_vad, &h->d_voiced, &h->d_sel, &h->d_final})
+                      &h->d_vad, &h->d_voiced, &h->d_sel, &h->d_final, &h->d_dec, &h->d_raw})
         if (b->p) (void)hipFree(b->p);
     delete h;
 }
@@ -1978,13 +2077,13 @@ int mfcc_hip_process_ragged_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm,
 int mfcc_hip_process_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch,
                              int halo, void *d_out, size_t *n_frames) {
     if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;   // a dense result cannot hold rows of different counts
-    return launch_float_dev(h, d_pcm, n, stride, nch, halo, d_out, n_frames);
+    return dense_dev(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
 }
 
 int mfcc_hip_process_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride,
                                    size_t nch, int halo, void *d_out, size_t *n_frames) {
     if (h && has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
-    return launch(h, true, d_pcm, n, stride, nch, halo, d_out, n_frames);
+    return dense_dev(h, true, d_pcm, n, stride, nch, halo, d_out, n_frames);
 }
 
 int mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n, size_t stride,
@@ -1993,11 +2092,9 @@ int mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n
     if (fixed && has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;        // a dense result cannot hold rows of different counts
     DeviceGuard guard(h->device);
-    // what process_*_dev enqueues: with normalization or deltas on, the float launch and the passes behind it
-    auto once = [&]() {
-        return fixed ? launch(h, true, d_pcm, n, stride, nch, 0, d_out, nullptr)
-                     : launch_float_dev(h, d_pcm, n, stride, nch, 0, d_out, nullptr);
-    };
+    // what process_*_dev enqueues: with a sample format the decode, with normalization or deltas on the passes behind
+    // the float launch
+    auto once = [&]() { return dense_dev(h, fixed != 0, d_pcm, n, stride, nch, 0, d_out, nullptr); };
     for (int i = 0; i < warmup; ++i) {
         int rc = once();
         if (rc) return rc;
@@ -2201,6 +2298,51 @@ const char *mfcc_hip_kernel_name(const mfcc_hip_handle *h, int fixed) {
     return "mfcc_float_generic_kernel";
 }
 
+// ---- sample formats (include/mfcc_hip.h: enum mfcc_hip_sample_format; kernel_decode.hpp)
+size_t mfcc_hip_sample_size(int format) { return mfcc_decode::sample_size(format); }
+
+int mfcc_hip_decode_host(int format, const void *in, size_t n, int16_t *out) {
+    if (!mfcc_decode::known(format) || (n && (!in || !out))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (n) mfcc_decode::decode_host(format, in, n, out);
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_decode_dev(mfcc_hip_handle *h, int format, const void *d_in, size_t n, void *d_out) {
+    if (!h || !mfcc_decode::known(format)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!n) return MFCC_HIP_SUCCESS;
+    const size_t size = mfcc_decode::sample_size(format);
+    const uintptr_t i_lo = reinterpret_cast<uintptr_t>(d_in), o_lo = reinterpret_cast<uintptr_t>(d_out);
+    if (!d_in || !d_out || (i_lo & (size - 1)) || (o_lo & 1)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (ranges_overlap(i_lo, i_lo + n * size, o_lo, o_lo + n * sizeof(int16_t))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    if (format == MFCC_HIP_SAMPLE_S16) {
+        HIP_TRY(h, hipMemcpyAsync(d_out, d_in, n * sizeof(int16_t), hipMemcpyDeviceToDevice, h->stream));
+        return MFCC_HIP_SUCCESS;
+    }
+    mfcc_decode::launch(format, d_in, static_cast<int16_t *>(d_out), n, 1, n, n, h->n_cu, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_set_sample_format(mfcc_hip_handle *h, int format) {
+    if (!h || !mfcc_decode::known(format)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
+    h->sample_fmt = format;
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_sample_format(const mfcc_hip_handle *h) { return h ? h->sample_fmt : MFCC_HIP_SAMPLE_S16; }
+
+// the WAV readers hand 16-bit PCM to the host entry points whatever the handle's format: S16 for the scope
+struct PcmFormatGuard {
+    mfcc_hip_handle *h;
+    int fmt;
+    explicit PcmFormatGuard(mfcc_hip_handle *hh) : h(hh), fmt(hh->sample_fmt) { h->sample_fmt = MFCC_HIP_SAMPLE_S16; }
+    ~PcmFormatGuard() { h->sample_fmt = fmt; }
+    PcmFormatGuard(const PcmFormatGuard &) = delete;
+    PcmFormatGuard &operator=(const PcmFormatGuard &) = delete;
+};
+
 // float coefficients -> the int16 a `.mfcc` file holds: astype(np.int16) of software/lift.py:39 (truncate)
 static inline int16_t to_mfcc_i16(float v) {
     if (!(v == v)) v = 0.0f;
@@ -2221,6 +2363,7 @@ int mfcc_hip_convert_wav(mfcc_hip_handle *h, const char *wav_in, const char *mfc
     if (rc) return rc;
     const size_t nf = count_frames(h->r, pcm.size());
     std::vector<int16_t> cep(nf * size_t(h->r.n_cep));
+    PcmFormatGuard pcm16(h);
     if (fixed) {
         rc = mfcc_hip_process_fixed_i16(h, pcm.data(), pcm.size(), 1, cep.data(), cep.size(), nullptr);
         if (rc) return rc;
@@ -2261,6 +2404,7 @@ int mfcc_hip_convert_wavs(mfcc_hip_handle *h, const char *const *wav_in, const c
     const size_t ncep = size_t(h->r.n_cep);
     std::vector<int16_t> cep(total * ncep);
     int rc;
+    PcmFormatGuard pcm16(h);
     if (fixed) {
         rc = mfcc_hip_process_ragged_fixed_i16(h, pcm.data(), off.data(), n_files, cep.data(), cep.size(), fo.data());
         if (rc) return rc;
@@ -2412,9 +2556,17 @@ int mfcc_hip_stream_push(mfcc_hip_stream *s, const int16_t *samples, size_t n, v
     DeviceGuard guard(h->device);
     int rc = stream_reserve(s, total, nf * ncep * sizeof(float));
     if (rc) return rc;
-    if (n)
+    if (n && decodes(h)) {
+        // the raw bytes to the device, decoded straight to their place behind the pending samples
+        const size_t raw = n * sample_bytes(h);
+        if ((rc = ensure(h, h->d_raw, raw + 64)) || (rc = scratch_acquire(h))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->d_raw.p, samples, raw, hipMemcpyHostToDevice, h->stream));
+        if ((rc = decode_rows(h, h->d_raw.p, n, 1, n, s->buf[s->cur] + 1 + s->pending, n)) || (rc = scratch_release(h)))
+            return rc;
+    } else if (n) {
         HIP_TRY(h, hipMemcpyAsync(s->buf[s->cur] + 1 + s->pending, samples, n * sizeof(int16_t), hipMemcpyHostToDevice,
                                   h->stream));
+    }
     if (nf) {
         rc = stream_emit(s, total, nf, out);
         if (rc) return rc;
@@ -2552,12 +2704,24 @@ int bank_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const
     int rc = mfcc_bank::push_plan(b->s, st, offsets, b->n, d_samples != nullptr, d_out != nullptr, cap, frame_offsets,
                                   b->after.data(), b->held_after.data(), rfo, l);
     if (rc || !l.n_rec) return rc;
+    // a sample format: the span offsets[0] .. offsets[n] of the chunks is decoded into the handle's scratch area in front
+    // of the parking kernel, which then reads its chunks there, counted from the span's start
+    const bool dec = decodes(h);
+    const size_t span = offsets[b->n] - offsets[0];
+    const void *d_span = dec ? sample_at(h, d_samples, offsets[0] - shift) : nullptr;
+    if (dec && !sample_aligned(h, d_samples)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (dec) shift = offsets[0];
     DeviceGuard guard(h->device);
     mfcc_hip_handle::PinnedDesc *pd = nullptr;
     if ((rc = desc_acquire(h, l.desc_ll, &pd))) return rc;
     mfcc_bank::push_fill(b->s, st, offsets, shift, b->n, frame_offsets, rfo, l, pd->p);
     if (l.in_bytes && (rc = ensure(h, h->d_in, l.in_bytes))) return rc;
+    if (dec && (rc = ensure(h, h->d_dec, span * sizeof(int16_t) + 64))) return rc;
     if ((rc = desc_stage(h, h->d_out, l.out_bytes, pd, l.desc_ll))) return rc;
+    if (dec) {
+        if ((rc = decode_rows(h, d_span, span, 1, span, static_cast<int16_t *>(h->d_dec.p), span))) return rc;
+        d_samples = static_cast<const int16_t *>(h->d_dec.p);
+    }
     int16_t *d_w = static_cast<int16_t *>(h->d_in.p);
     const unsigned blocks = (unsigned)std::min<size_t>(l.n_rec, size_t(h->n_cu) * 8);
     hipLaunchKernelGGL(mfcc_bank::bank_advance_kernel, dim3(blocks), dim3(mfcc_bank::kThreads), 0, h->stream, d_samples,
@@ -2832,9 +2996,10 @@ int mfcc_hip_bank_push(mfcc_hip_bank *b, const int16_t *samples, const size_t *o
     if (!span) return MFCC_HIP_SUCCESS;
     if (!samples) return MFCC_HIP_ERROR_INVALID_PARAM;
     DeviceGuard guard(h->device);
-    if ((rc = ensure(h, b->st_in, span * sizeof(int16_t) + 64))) return rc;
+    const size_t raw = span * sample_bytes(h);              // the chunks as they are: the device push decodes them
+    if ((rc = ensure(h, b->st_in, raw + 64))) return rc;
     if ((rc = ensure(h, b->st_out, total * W * esz + 64))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(b->st_in.p, samples + offsets[0], span * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(b->st_in.p, sample_at(h, samples, offsets[0]), raw, hipMemcpyHostToDevice, h->stream));
     rc = bank_advance(b, static_cast<const int16_t *>(b->st_in.p), offsets[0], offsets, b->st_out.p, total * W, frame_offsets);
     if (!rc && total) HIP_TRY(h, hipMemcpyAsync(out, b->st_out.p, total * W * esz, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));        // `samples` and `out` belong to the caller again
