@@ -43,6 +43,7 @@
 #include <cstring>
 #include <vector>
 
+#include "batch_plan.hpp"        // RaggedRec: shared with the host plan
 #include "kernels_generic.hpp"
 #include "tables.hpp"
 
@@ -317,15 +318,6 @@ __device__ __forceinline__ void dct_stage(uint32_t &s0, uint32_t &s1, const uint
     s1 = lower ? recv : s1;
     bfly(s0, s1, twd[2 * (ST - 1)], twd[2 * (ST - 1) + 1]);
 }
-
-// One utterance of a ragged corpus (mfcc_hip_process_ragged_*): an independent stream that starts from reset and is
-// zero-padded at its end, exactly like a channel of the plain call.  Only utterances with frames > 0 get a record.
-struct RaggedRec {
-    long long pcm_off;       // first sample, relative to StreamDesc::pcm
-    long long out_row;       // first output row (frame) of the utterance == frames of all utterances before it
-    int n_samples, frames;
-    int pad0, pad1;
-};
 
 struct Geom {
     long long frames_per_ch;          // plain

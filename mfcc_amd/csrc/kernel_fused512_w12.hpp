@@ -45,6 +45,7 @@
 // 2 w, group B 2 w + 1 of the 4-wave form's tile order.
 #pragma once
 
+#include "batch_plan.hpp"        // RaggedChan, RaggedTile: shared with the host plan
 #include "kernel_fused512.hpp"
 
 namespace mfcc_fused12 {
@@ -128,27 +129,8 @@ __device__ __forceinline__ Cursor cursor_of(const mfcc_k::StreamDesc &s, const L
     return c;
 }
 
-// ---- ragged corpora without a packing copy: the tiles of utterances of different lengths, straight out of the
-// caller's buffer.  The host writes one record per utterance, a small kernel expands them into one 32-byte record per
-// tile, and a wave fetches its next tile's record with one scalar load, a tile ahead of its use.  Every utterance is an independent stream that starts from reset
-// (history 0) and is zero-padded at its end, exactly like a channel of the plain call -- so the frames are the same
-// bits as one call per utterance.
-struct RaggedChan {
-    long long pcm_off;       // first sample of the utterance, relative to StreamDesc::pcm
-    long long out_row;       // first output row (frame) of the utterance
-    int n_samples, frames;   // of the utterance
-    int t_hi;                // tiles 1 .. t_hi have their whole window inside the utterance
-    int tile0;               // index of its first tile in the tile map
-};
-// what a wave needs to know about a tile, in one 32-byte record (one s_load_dwordx8): expanded from the utterance
-// records by ragged_tile_map_kernel
-struct RaggedTile {
-    long long pcm_off;       // first sample of the tile's utterance, relative to StreamDesc::pcm
-    long long out_row;       // first output row (frame) of that utterance
-    int n_samples, frames;   // of the utterance
-    int t_hi;                // tiles 1 .. t_hi of the utterance have their whole window inside it
-    int t_in;                // the tile's index inside its utterance
-};
+// ---- ragged corpora without a packing copy: RaggedChan (one per utterance, written by the host) and RaggedTile (one per
+// tile, expanded from them on the device) are in batch_plan.hpp, with the plan that fills them
 struct RaggedTables {
     const RaggedTile *tiles; // [n_tiles]
     int n_tiles;
@@ -860,12 +842,6 @@ inline bool launch(const mfcc_k::StreamDesc &s, const FusedTables &t, bool dense
 
 // ---- ragged corpus, host side: per-utterance records (built by the caller in pinned memory), the tile map (built on
 // the device from them), the launch
-inline int ragged_t_hi(long long n_samples, long long tiles) {
-    if (n_samples < kSUsed) return -1;
-    const long long hi = (n_samples - kSUsed) / kTileHop;
-    return (int)(hi < tiles ? hi : tiles);
-}
-
 __global__ void ragged_tile_map_kernel(const RaggedChan *__restrict__ chans, int n_chan, RaggedTile *__restrict__ tiles) {
     for (int u = blockIdx.x; u < n_chan; u += gridDim.x) {
         const RaggedChan ch = chans[u];

@@ -18,6 +18,7 @@
 
 #include "../../include/mfcc_hip.h"
 #include "bank_plan.hpp"
+#include "batch_plan.hpp"
 #include "seg_plan.hpp"
 #include "kernels_generic.hpp"
 #include "kernel_fixed512.hpp"
@@ -150,15 +151,11 @@ std::vector<double> handle_mel(const Resolved &r) {
     return mel_dense(r.nfft, r.n_mel, double(r.sample_rate));
 }
 
-size_t count_frames(const Resolved &r, size_t n) {
-    const size_t L = size_t(r.frame_len);
-    if (r.pad_mode == MFCC_HIP_PAD_NOTEBOOK) {
-        if (n < L) return 0;
-        return (n - L) / size_t(r.hop) + 1;
-    }
-    if (n < L) return 1;
-    return (n - L) / size_t(r.hop) + 2;
+inline mfcc_batch::Framing framing(const Resolved &r) {
+    return {size_t(r.frame_len), size_t(r.hop), r.pad_mode != MFCC_HIP_PAD_NOTEBOOK};
 }
+
+size_t count_frames(const Resolved &r, size_t n) { return mfcc_batch::frames_of(framing(r), n); }
 
 // the float window of a handle: periodic Hamming over the frame, zeros up to nfft (the frame is zero-padded at the end)
 std::vector<double> frame_window(const Resolved &r) {
@@ -1145,15 +1142,7 @@ int dense_dev(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_
 // 64 MB chunks pinned 3.20 ms (0.141 G frames/s = 48 GB/s of input against 53 GB/s for the bare H2D copy), 32 MB 3.68,
 // 16 MB 3.94 -- every chunk costs ~60 us of calls and a kernel launch that cannot fill the chip.  A batch that fits one
 // chunk takes the plain blocking copies (pinning it first only adds its 13 us per MB in front).
-struct HostChunk {
-    const void *in;         // first sample handed to the kernel (the halo sample when halo = 1)
-    size_t in_samples;      // samples copied (all channels of the chunk; incl. the halo sample)
-    size_t n, stride, nch;  // launch geometry: samples per channel after the halo, channel stride, channels
-    int halo;
-    size_t frames;          // frames per channel of this chunk (forced: a frame range of a longer stream)
-    size_t out_elems;       // coefficients written
-    size_t out_off;         // offset into `out`, in elements
-};
+using mfcc_batch::HostChunk;      // one chunk of a dense call (batch_plan.hpp: cut_dense)
 
 // A caller's buffer pinned block by block for the duration of a call: page-aligned blocks of 16 MB, registered when a
 // copy first touches them and released when every chunk that could touch them is done.  A copy must stay inside ONE
@@ -1332,7 +1321,7 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     const size_t nf = count_frames(h->r, n);
     if (n_frames) *n_frames = nf;
     if (nf == 0 || nch == 0) return MFCC_HIP_SUCCESS;
-    const size_t ncep = fixed ? row_width(h->r) : out_width(h), hop = size_t(h->r.hop), flen = size_t(h->r.frame_len);   // elements per row
+    const size_t ncep = fixed ? row_width(h->r) : out_width(h);   // elements per row
     const size_t n_out = nf * nch * ncep;
     if (!out || cap < n_out) return MFCC_HIP_ERROR_BUFFER_SMALL;
     DeviceGuard guard(h->device);
@@ -1344,37 +1333,14 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     const bool dec = decodes(h);
     const size_t ssz = sample_bytes(h);
 
-    // ---- the chunks
-    std::vector<HostChunk> chunks;
-    const size_t ch_bytes = n * sizeof(int16_t);
-    if (ch_bytes <= kChunkBytes) {
-        size_t per = kChunkBytes / (ch_bytes ? ch_bytes : 1);
-        if (per < 1) per = 1;
-        for (size_t c0 = 0; c0 < nch; c0 += per) {
-            const size_t k = std::min(per, nch - c0);
-            chunks.push_back({sample_at(h, pcm, c0 * n), k * n, n, n, k, 0, nf, k * nf * ncep, c0 * nf * ncep});
-        }
-    } else {
-        // long channels: frame ranges [f0, f1) of one channel -- samples f0 * hop - 1 (history) .. (f1 - 1) * hop + frame_len
-        size_t per = (kChunkBytes / sizeof(int16_t)) / hop;
-        if (per < 1) per = 1;
-        for (size_t c = 0; c < nch; ++c)
-            for (size_t f0 = 0; f0 < nf; f0 += per) {
-                const size_t f1 = std::min(nf, f0 + per), halo = f0 ? 1 : 0;
-                const size_t s0 = f0 * hop - halo;
-                size_t s1 = (f1 - 1) * hop + flen;
-                if (s1 > n) s1 = n;                                  // the zero-padded tail of STREAM framing
-                chunks.push_back({sample_at(h, pcm, c * n + s0), s1 - s0, s1 - s0 - halo, s1 - s0, 1, int(halo), f1 - f0,
-                                  (f1 - f0) * ncep, (c * nf + f0) * ncep});
-            }
-    }
+    const std::vector<HostChunk> chunks = mfcc_batch::cut_dense(n, nch, nf, ncep, framing(h->r), kChunkBytes);
     // The chain (post_chain) works on whole channels: no row may leave the device before its channel's statistics exist,
     // deltas need the neighbouring frames and PCEN is recursive along the channel -- a chunk edge is not a channel edge.
     // Chunks of whole channels run the chain on their own rows before the copy back; frame-range chunks of long channels
     // write into one device buffer of the whole result (and its staging), which goes through the chain and is copied
     // back after the pipeline
     const bool post = !fixed && has_post(h);
-    const bool whole = post && ch_bytes > kChunkBytes;
+    const bool whole = post && mfcc_batch::dense_cuts_channels(n, kChunkBytes);
     OutT *d_full = nullptr;
     if (whole) {
         const int rc = ensure(h, h->d_full, n_out * sizeof(OutT) + 64);
@@ -1384,13 +1350,14 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     // the staging of the chain (route_to's rule) holds the rows of one chunk, or of the whole result
     const bool staged = post && (K || sliding(h));
     if (staged) {
-        int rc = stage_rows(h, (whole ? nch : std::min(nch, kChunkBytes / (ch_bytes ? ch_bytes : 1) + 1)) * nf);
+        int rc = stage_rows(h, whole ? nch * nf : mfcc_batch::max_chunk_rows(chunks));
         if (rc || (rc = scratch_acquire(h))) return rc;
     }
     std::vector<PipeChunk> pc;
     pc.reserve(chunks.size());
     for (const HostChunk &c : chunks)
-        pc.push_back({c.in, c.in_samples * ssz, out + c.out_off, whole ? 0 : c.out_elems * sizeof(OutT)});
+        pc.push_back({sample_at(h, pcm, c.in_off), c.in_samples * ssz, out + c.out_off,
+                      whole ? 0 : c.out_elems * sizeof(OutT)});
     int rc = run_host_pipeline(h, pc, pcm, nch * n * ssz, out, whole ? 0 : n_out * sizeof(OutT), [&](size_t i, void *d_raw, void *d_out) {
         const HostChunk &c = chunks[i];
         const void *d_in = d_raw;
@@ -1463,220 +1430,126 @@ __global__ void pack_utterances_kernel(const int16_t *__restrict__ src, int16_t 
     }
 }
 
+// The fused 512 kernel's tiles, for the scan and the tile records (batch_plan.hpp does not include a kernel header)
+constexpr mfcc_batch::TileGeom kRaggedTiles = {mfcc_fused::kTile, mfcc_fused::kTileHop, mfcc_fused::kSUsed};
+
+inline mfcc_batch::Scan ragged_scan(const mfcc_hip_handle *h, const size_t *offsets, size_t n_utt, size_t *frame_offsets) {
+    return mfcc_batch::scan(offsets, n_utt, framing(h->r), size_t(kRaggedTiles.tile), frame_offsets);
+}
+
+// The launch of a scanned corpus with at least one frame, d_out large enough: route -> fill -> desc_stage -> launch
+// (batch_plan.hpp).  d_pcm is int16; fo: the scan's frame offsets
 template <typename OutT>
-int process_ragged_dev_raw(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
-                           OutT *d_out, size_t cap, size_t *frame_offsets) {
-    if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
-    const size_t hop = size_t(h->r.hop), flen = size_t(h->r.frame_len), ncep = row_width(h->r);   // elements per row
-    DeviceGuard guard(h->device);
-    // A corpus of equal-length utterances lying back to back (BASELINE config 5: 10 000 x 10 s) IS a multi-channel
-    // stream, channel stride = utterance length: no packing copy, no row gather, no descriptors, the same bits (every
-    // channel of the plain call starts from reset, its frames are the utterance's frames and the rows come out dense).
-    // Checked first: this is the per-step host work of a sharded corpus (bench.py `enqueue_us_per_step`).
-    if (n_utt >= 1 && offsets[1] >= offsets[0]) {
-        const size_t n0 = offsets[1] - offsets[0];
-        const size_t nf0 = count_frames(h->r, n0);
-        bool uniform = nf0 > 0;
-        for (size_t u = 1; u < n_utt && uniform; ++u) uniform = offsets[u + 1] - offsets[u] == n0;
-        if (uniform) {
-            if (!d_pcm) return MFCC_HIP_ERROR_INVALID_PARAM;
-            for (size_t u = 0; u <= n_utt; ++u) frame_offsets[u] = u * nf0;
-            if (!d_out || cap < n_utt * nf0 * ncep) return MFCC_HIP_ERROR_BUFFER_SMALL;
-            return launch(h, fixed, d_pcm + offsets[0], n0, n0, n_utt, 0, d_out, nullptr);
-        }
-    }
-    // [0, 4n): pack descriptors, [4n, 7n): row-gather descriptors, [7n, 11n): the fused kernels' per-utterance records
-    // (their own region: a corpus the records cannot describe falls through to pack-and-gather with [0, 7n) intact);
-    // in pinned memory: the H2D copies below are asynchronous
+int ragged_launch(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt, OutT *d_out,
+                  const size_t *fo, const mfcc_batch::Scan &sc) {
+    using mfcc_batch::Records;
+    using mfcc_batch::Route;
+    Records kernel = Records::kNone;        // what the kernel of this call reads utterances from
+    if (!fixed && h->float_kernel == FloatKernel::kFused512W12 && std::is_same<OutT, float>::value) kernel = Records::kTiles;
+    if (fixed && h->fixed_kernel == FixedKernel::kFixed512 && std::is_same<OutT, int16_t>::value) kernel = Records::kFrames;
+    const Route route = mfcc_batch::route(kernel, fixed, sc, n_utt);
+    // Checked first: this is the per-step host work of a sharded corpus (BASELINE config 5: 10 000 x 10 s; bench.py
+    // `enqueue_us_per_step`) -- no packing copy, no row gather, no descriptors, the same bits (every channel of the
+    // plain call starts from reset, its frames are the utterance's frames and the rows come out dense)
+    if (route == Route::kUniform) return launch(h, fixed, d_pcm + offsets[0], sc.len0, sc.len0, n_utt, 0, d_out, nullptr);
+    // the table in pinned memory: its H2D copy is asynchronous
     mfcc_hip_handle::PinnedDesc *pd = nullptr;
-    int rc = desc_acquire(h, 11 * n_utt, &pd);
+    int rc = desc_acquire(h, mfcc_batch::table_ll(route, n_utt), &pd);
     if (rc) return rc;
-    long long *desc = pd->p;
-    long long *rec_area = desc + 7 * n_utt;
-    for (size_t i = 0; i < 7 * n_utt; ++i) desc[i] = 0;
-    size_t last_with_frames = n_utt;
-    size_t pos = 0, total = 0;
-    bool rec_fits = n_utt < (size_t(1) << 31);       // the records' int fields (else: pack and gather, below)
-    frame_offsets[0] = 0;
-    for (size_t u = 0; u < n_utt; ++u) {
-        if (offsets[u + 1] < offsets[u]) return MFCC_HIP_ERROR_INVALID_PARAM;
-        const size_t n = offsets[u + 1] - offsets[u];
-        if (n && !d_pcm) return MFCC_HIP_ERROR_INVALID_PARAM;
-        if (n >= (size_t(1) << 31)) rec_fits = false;
-        const size_t nf = count_frames(h->r, n);
-        desc[4 * u] = (long long)offsets[u];
-        desc[4 * u + 1] = (long long)pos;
-        desc[4 * u + 2] = nf ? (long long)n : 0;
-        desc[4 * n_utt + 3 * u] = (long long)(pos / hop);
-        desc[4 * n_utt + 3 * u + 1] = (long long)total;
-        desc[4 * n_utt + 3 * u + 2] = (long long)nf;
-        total += nf;
-        frame_offsets[u + 1] = total;
-        if (nf) {
-            const size_t extent = std::max(n, hop * (nf - 1) + flen);
-            pos = (pos + extent + 1 + hop - 1) / hop * hop;
-            last_with_frames = u;
-        }
-        desc[4 * u + 3] = (long long)pos;          // this utterance's part of the stream ends where the next begins
+    if (route == Route::kTileRecords) {
+        // no packed copy at all: the kernel reads every utterance where it lies and writes its rows where they belong
+        // (kernel_fused512_w12.hpp)
+        const mfcc_batch::TilePlan p =
+            mfcc_batch::fill_chans(offsets, fo, n_utt, kRaggedTiles, reinterpret_cast<mfcc_fused12::RaggedChan *>(pd->p));
+        if ((rc = desc_stage(h, h->d_in, p.bytes, pd, p.chan_ll))) return rc;
+        auto *d_chans = static_cast<const mfcc_fused12::RaggedChan *>(h->d_in.p);
+        auto *d_map = reinterpret_cast<mfcc_fused12::RaggedTile *>(static_cast<char *>(h->d_in.p) + p.map_off);
+        const bool launched =
+            is_logmel(h->r) ? mfcc_fused12::launch_ragged<true>(d_pcm, d_chans, (int)n_utt, d_map, (int)p.n_tiles, h->fu,
+                                                                h->fused_dense, reinterpret_cast<float *>(d_out), h->n_cu, h->stream)
+                            : mfcc_fused12::launch_ragged(d_pcm, d_chans, (int)n_utt, d_map, (int)p.n_tiles, h->fu,
+                                                          h->fused_dense, reinterpret_cast<float *>(d_out), h->n_cu, h->stream);
+        if (!launched) return MFCC_HIP_ERROR_OTHER;               // cannot happen with at least one tile
+    } else if (route == Route::kFrameRecords) {
+        // the same: the kernel's waves walk consecutive frames and step from one utterance into the next
+        // (kernel_fixed512.hpp)
+        const mfcc_batch::RecPlan p =
+            mfcc_batch::fill_recs(offsets, fo, n_utt, reinterpret_cast<mfcc_fixed512::RaggedRec *>(pd->p));
+        if ((rc = desc_stage(h, h->d_in, p.bytes, pd, p.rec_ll))) return rc;
+        mfcc_fixed512::launch_ragged(d_pcm, static_cast<const mfcc_fixed512::RaggedRec *>(h->d_in.p), (int)p.n_recs,
+                                     (long long)sc.total, h->r.hop, h->x5, reinterpret_cast<int16_t *>(d_out), h->n_cu, h->stream);
+    } else {
+        const size_t ncep = row_width(h->r);
+        const mfcc_batch::PackPlan p = mfcc_batch::fill_pack(offsets, fo, n_utt, framing(h->r), ncep * sizeof(OutT), pd->p);
+        if ((rc = ensure(h, h->d_in, p.in_bytes))) return rc;
+        if ((rc = desc_stage(h, h->d_out, p.out_bytes, pd, p.desc_ll, p.desc_off))) return rc;
+        OutT *d_all = static_cast<OutT *>(h->d_out.p);
+        long long *d_desc = reinterpret_cast<long long *>(static_cast<char *>(h->d_out.p) + p.desc_off);
+        const unsigned blocks = (unsigned)std::min<size_t>(n_utt, size_t(h->n_cu) * 8);
+        hipLaunchKernelGGL(pack_utterances_kernel, dim3(blocks), dim3(256), 0, h->stream, d_pcm,
+                           static_cast<int16_t *>(h->d_in.p), d_desc, (long long)n_utt);
+        if ((rc = launch(h, fixed, h->d_in.p, p.len, p.len, 1, 0, d_all, nullptr, p.F))) return rc;
+        hipLaunchKernelGGL(gather_rows_kernel<OutT>, dim3(blocks), dim3(256), 0, h->stream, d_all, d_out,
+                           d_desc + p.gather_ll, (long long)n_utt, (int)ncep);
     }
-    if (total == 0) return MFCC_HIP_SUCCESS;
-    if (!d_out || cap < total * ncep) return MFCC_HIP_ERROR_BUFFER_SMALL;
-    // Float contract on the twelve-wave kernel: no packed copy at all -- per-utterance records, expanded on the device
-    // into one record per tile; the kernel reads every utterance where it lies and writes its rows where they belong
-    // (kernel_fused512_w12.hpp)
-    if (!fixed && h->float_kernel == FloatKernel::kFused512W12 && std::is_same<OutT, float>::value && rec_fits) {
-        static_assert(sizeof(mfcc_fused12::RaggedChan) == 4 * sizeof(long long), "record layout");
-        mfcc_fused12::RaggedChan *rc_host = reinterpret_cast<mfcc_fused12::RaggedChan *>(rec_area);   // 4 long longs each
-        long long n_tiles = 0;
-        for (size_t u = 0; u < n_utt; ++u) {
-            const size_t n = offsets[u + 1] - offsets[u];
-            const size_t nf = frame_offsets[u + 1] - frame_offsets[u];
-            const long long tiles = (long long)((nf + mfcc_fused::kTile - 1) / mfcc_fused::kTile);
-            mfcc_fused12::RaggedChan c;
-            c.pcm_off = (long long)offsets[u];
-            c.out_row = (long long)frame_offsets[u];
-            c.n_samples = (int)n;
-            c.frames = (int)nf;
-            c.t_hi = mfcc_fused12::ragged_t_hi((long long)n, tiles);
-            c.tile0 = (int)n_tiles;
-            rc_host[u] = c;
-            n_tiles += tiles;
-        }
-        if (n_tiles < (1ll << 30)) {
-            const size_t chan_bytes = n_utt * sizeof(mfcc_fused12::RaggedChan);
-            const size_t map_off = (chan_bytes + 255) & ~size_t(255);
-            rc = ensure(h, h->d_in, map_off + size_t(n_tiles) * sizeof(mfcc_fused12::RaggedTile) + 64);
-            if (rc) return rc;
-            if ((rc = scratch_acquire(h))) return rc;
-            HIP_TRY(h, hipMemcpyAsync(h->d_in.p, rc_host, chan_bytes, hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
-            pd->in_flight = true;
-            auto *d_chans = static_cast<const mfcc_fused12::RaggedChan *>(h->d_in.p);
-            auto *d_map = reinterpret_cast<mfcc_fused12::RaggedTile *>(static_cast<char *>(h->d_in.p) + map_off);
-            const bool launched =
-                is_logmel(h->r) ? mfcc_fused12::launch_ragged<true>(d_pcm, d_chans, (int)n_utt, d_map, (int)n_tiles, h->fu,
-                                                                    h->fused_dense, reinterpret_cast<float *>(d_out), h->n_cu, h->stream)
-                                : mfcc_fused12::launch_ragged(d_pcm, d_chans, (int)n_utt, d_map, (int)n_tiles, h->fu,
-                                                              h->fused_dense, reinterpret_cast<float *>(d_out), h->n_cu, h->stream);
-            if (launched) {
-                HIP_TRY(h, hipGetLastError());
-                return scratch_release(h);
-            }
-            return MFCC_HIP_ERROR_OTHER;               // not launched: cannot happen with at least one tile
-        }
-        // more tiles than the tile map's int index: pack and gather below (the pack descriptors are untouched)
-    }
-    // Fixed contract on the fused kernel: the same -- one record per utterance with frames, the kernel's waves walk
-    // consecutive frames and step from one utterance into the next (kernel_fixed512.hpp)
-    if (fixed && h->fixed_kernel == FixedKernel::kFixed512 && std::is_same<OutT, int16_t>::value && rec_fits) {
-        static_assert(sizeof(mfcc_fixed512::RaggedRec) == 4 * sizeof(long long), "record layout");
-        mfcc_fixed512::RaggedRec *rr = reinterpret_cast<mfcc_fixed512::RaggedRec *>(rec_area);
-        size_t n_recs = 0;
-        for (size_t u = 0; u < n_utt; ++u) {
-            const size_t n = offsets[u + 1] - offsets[u];
-            const size_t nf = frame_offsets[u + 1] - frame_offsets[u];
-            if (!nf) continue;
-            mfcc_fixed512::RaggedRec c;
-            c.pcm_off = (long long)offsets[u];
-            c.out_row = (long long)frame_offsets[u];
-            c.n_samples = (int)n;
-            c.frames = (int)nf;
-            c.pad0 = c.pad1 = 0;
-            rr[n_recs++] = c;
-        }
-        {
-            const size_t rec_bytes = n_recs * sizeof(mfcc_fixed512::RaggedRec);
-            rc = ensure(h, h->d_in, rec_bytes + 64);
-            if (rc) return rc;
-            if ((rc = scratch_acquire(h))) return rc;
-            HIP_TRY(h, hipMemcpyAsync(h->d_in.p, rr, rec_bytes, hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
-            pd->in_flight = true;
-            mfcc_fixed512::launch_ragged(d_pcm, static_cast<const mfcc_fixed512::RaggedRec *>(h->d_in.p), (int)n_recs,
-                                         (long long)total, h->r.hop, h->x5, reinterpret_cast<int16_t *>(d_out), h->n_cu,
-                                         h->stream);
-            HIP_TRY(h, hipGetLastError());
-            return scratch_release(h);
-        }
-    }
-    const size_t F = pos / hop, len = pos + flen + hop;
-    desc[4 * last_with_frames + 3] = (long long)len;     // the last one also zeroes the tail of the stream
-    const size_t desc_bytes = 7 * n_utt * sizeof(long long);
-    rc = ensure(h, h->d_in, len * sizeof(int16_t) + 64);
-    if (rc) return rc;
-    rc = ensure(h, h->d_out, F * ncep * sizeof(OutT) + desc_bytes + 64);
-    if (rc) return rc;
-    if ((rc = scratch_acquire(h))) return rc;
-    OutT *d_all = static_cast<OutT *>(h->d_out.p);
-    const size_t desc_off = (F * ncep * sizeof(OutT) + 7) & ~size_t(7);
-    long long *d_desc = reinterpret_cast<long long *>(static_cast<char *>(h->d_out.p) + desc_off);
-    HIP_TRY(h, hipMemcpyAsync(d_desc, desc, desc_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipEventRecord(pd->copied, h->stream));
-    pd->in_flight = true;
-    const unsigned blocks = (unsigned)std::min<size_t>(n_utt, size_t(h->n_cu) * 8);
-    hipLaunchKernelGGL(pack_utterances_kernel, dim3(blocks), dim3(256), 0, h->stream, d_pcm,
-                       static_cast<int16_t *>(h->d_in.p), d_desc, (long long)n_utt);
-    rc = launch(h, fixed, h->d_in.p, len, len, 1, 0, d_all, nullptr, F);
-    if (rc) return rc;
-    hipLaunchKernelGGL(gather_rows_kernel<OutT>, dim3(blocks), dim3(256), 0, h->stream, d_all, d_out,
-                       d_desc + 4 * n_utt, (long long)n_utt, (int)ncep);
     HIP_TRY(h, hipGetLastError());
     return scratch_release(h);
 }
 
-// ... and the chain over the result, one segment per utterance (float contract only: the public fixed-point entry points
-// refuse a handle with a pass).  A handle that stages (deltas, a normalization window, MFCC_HIP_VAD_SELECT) has its kernels
-// write into the staging, which takes the frame count first.  With MFCC_HIP_VAD_SELECT every frame goes through the chain
-// into h->d_final, then only the voiced rows to d_out; frame_offsets describes those, and the call synchronizes (select_run)
+// A scanned corpus on the device, in the handle's sample format: what is left to refuse, the decode of the span
+// offsets[0] .. offsets[n_utt] into the scratch area (MFCC_HIP_SAMPLE_S16: none), the launch, and the chain over the result,
+// one segment per utterance (float contract only: the public fixed-point entry points refuse a handle with a pass).  A
+// handle that stages (deltas, a normalization window, MFCC_HIP_VAD_SELECT) has its kernels write into the staging.  With
+// MFCC_HIP_VAD_SELECT every frame goes through the chain into h->d_final, then only the voiced rows to d_out;
+// frame_offsets describes those, and the call synchronizes (select_run)
 template <typename OutT>
-int process_ragged_dev_i16(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
-                           OutT *d_out, size_t cap, size_t *frame_offsets) {
-    if (!h || fixed || !has_post(h) || !offsets || !frame_offsets)
-        return process_ragged_dev_raw<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
-    const bool sel = h->vad_mode != MFCC_HIP_VAD_OFF, staged = sel || h->delta_order || sliding(h);
-    const size_t W = row_width(h->r), WO = out_width(h);
-    size_t total = 0;
-    for (size_t u = 0; staged && u < n_utt; ++u) {
-        if (offsets[u + 1] < offsets[u])            // refused by the call below
-            return process_ragged_dev_raw<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
-        total += count_frames(h->r, offsets[u + 1] - offsets[u]);
-    }
-    // nothing to write, or a buffer too small for every frame: the plain call fills frame_offsets and gives the answer
-    if (staged && (total == 0 || !d_out || cap < total * WO))
-        return process_ragged_dev_raw<OutT>(h, fixed, d_pcm, offsets, n_utt, total ? nullptr : d_out, 0, frame_offsets);
+int ragged_scanned(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt, OutT *d_out,
+                   size_t cap, size_t *frame_offsets, const mfcc_batch::Scan &sc) {
+    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (sc.max_len && !d_pcm) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (sc.total == 0) return MFCC_HIP_SUCCESS;
+    const bool post = !fixed && has_post(h), sel = post && h->vad_mode != MFCC_HIP_VAD_OFF;
+    const size_t WO = post ? out_width(h) : row_width(h->r);
+    if (!d_out || cap < sc.total * WO) return MFCC_HIP_ERROR_BUFFER_SMALL;    // frame_offsets: the counts, to size d_out by
     DeviceGuard guard(h->device);
-    PostRoute rt;
-    int rc = post_route(h, total, reinterpret_cast<float *>(d_out), sel, rt);
-    if (rc || (rc = process_ragged_dev_raw<float>(h, false, d_pcm, offsets, n_utt, rt.raw, staged ? total * W : cap, frame_offsets)))
-        return rc;
-    const SegSpan sp = span_offsets(frame_offsets, n_utt);
-    SelPlan pl;
-    if (sel && (rc = select_plan(h, sp, int(WO), pl))) return rc;
-    if ((rc = post_chain(h, sp, rt, sel ? &pl : nullptr))) return rc;
-    if (sel) return select_run(h, rt.out, int(WO), rt.voiced, pl, true, reinterpret_cast<float *>(d_out), frame_offsets);
-    return rt.staged ? scratch_release(h) : MFCC_HIP_SUCCESS;
+    int rc;
+    std::vector<size_t> loc;
+    const bool dec = decodes(h);
+    if (dec) {
+        loc.resize(n_utt + 1);
+        for (size_t u = 0; u <= n_utt; ++u) loc[u] = offsets[u] - offsets[0];
+        const size_t span = loc[n_utt];
+        size_t stride = 0;
+        if ((rc = decode_to_scratch(h, sample_at(h, d_pcm, offsets[0]), span, 1, span, &d_pcm, &stride))) return rc;
+        offsets = loc.data();
+    }
+    if (!post) {
+        rc = ragged_launch<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, frame_offsets, sc);
+    } else {
+        PostRoute rt;
+        if ((rc = post_route(h, sc.total, reinterpret_cast<float *>(d_out), sel, rt)) ||
+            (rc = ragged_launch<float>(h, false, d_pcm, offsets, n_utt, rt.raw, frame_offsets, sc)))
+            return rc;
+        const SegSpan sp = span_offsets(frame_offsets, n_utt);
+        SelPlan pl;
+        if (sel && (rc = select_plan(h, sp, int(WO), pl))) return rc;
+        if ((rc = post_chain(h, sp, rt, sel ? &pl : nullptr))) return rc;
+        if (sel) rc = select_run(h, rt.out, int(WO), rt.voiced, pl, true, reinterpret_cast<float *>(d_out), frame_offsets);
+        else if (rt.staged) rc = scratch_release(h);
+    }
+    return rc || !dec ? rc : scratch_release(h);
 }
 
-// ... on a handle with a sample format: the span offsets[0] .. offsets[n_utt] decoded into the scratch area, then the call
-// above on it with the offsets counted from its start.  MFCC_HIP_SAMPLE_S16: the call above and nothing else
+// the device entry: the one scan of the call, then the above.  The order of the refusals is the entry's own
 template <typename OutT>
 int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
                        OutT *d_out, size_t cap, size_t *frame_offsets) {
-    if (!h || !decodes(h) || !offsets || !frame_offsets || !n_utt)
-        return process_ragged_dev_i16<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
-    if (!offsets_ok(offsets, n_utt) || !sample_aligned(h, d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    const size_t span = offsets[n_utt] - offsets[0];
-    if (!span || !d_pcm)                                  // no sample is read
-        return process_ragged_dev_i16<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
-    std::vector<size_t> loc(n_utt + 1);
-    for (size_t u = 0; u <= n_utt; ++u) loc[u] = offsets[u] - offsets[0];
-    DeviceGuard guard(h->device);
-    const int16_t *dec = nullptr;
-    size_t stride = 0;
-    int rc = decode_to_scratch(h, sample_at(h, d_pcm, offsets[0]), span, 1, span, &dec, &stride);
-    if (rc || (rc = process_ragged_dev_i16<OutT>(h, fixed, dec, loc.data(), n_utt, d_out, cap, frame_offsets))) return rc;
-    return scratch_release(h);
+    if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const bool dec = decodes(h) && n_utt;                 // a sample format looks at the offsets and the pointer first
+    if (!dec && fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
+    const mfcc_batch::Scan sc = ragged_scan(h, offsets, n_utt, frame_offsets);
+    if (sc.rc || (dec && !sample_aligned(h, d_pcm))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    return ragged_scanned<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets, sc);
 }
 
 // Host buffers: the corpus goes to the device in ONE copy (the span offsets[0] .. offsets[n_utt] as it lies), runs through
@@ -1689,61 +1562,41 @@ int process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const siz
     if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     const size_t ncep = fixed ? row_width(h->r) : out_width(h);          // elements per row
-    size_t total = 0;
-    std::vector<size_t> rel(n_utt + 1, 0);
-    for (size_t u = 0; u < n_utt; ++u) {
-        if (offsets[u + 1] < offsets[u]) return MFCC_HIP_ERROR_INVALID_PARAM;
-        const size_t n = offsets[u + 1] - offsets[u];
-        if (n && !pcm) return MFCC_HIP_ERROR_INVALID_PARAM;
-        rel[u + 1] = offsets[u + 1] - offsets[0];
-        total += count_frames(h->r, n);
-    }
-    if (total == 0) {
-        for (size_t u = 0; u <= n_utt; ++u) frame_offsets[u] = 0;
-        return MFCC_HIP_SUCCESS;
-    }
-    if (!out || cap < total * ncep) {
-        frame_offsets[0] = 0;                            // the counts, as before, so that the caller can size `out`
-        for (size_t u = 0; u < n_utt; ++u) frame_offsets[u + 1] = frame_offsets[u] + count_frames(h->r, rel[u + 1] - rel[u]);
-        return MFCC_HIP_ERROR_BUFFER_SMALL;
-    }
+    const mfcc_batch::Scan sc = ragged_scan(h, offsets, n_utt, frame_offsets);
+    if (sc.rc || (sc.max_len && !pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (sc.total == 0) return MFCC_HIP_SUCCESS;                          // frame_offsets: all zero
+    if (!out || cap < sc.total * ncep) return MFCC_HIP_ERROR_BUFFER_SMALL;      // the counts, so that the caller can size `out`
     DeviceGuard guard(h->device);
     // the same copy pipeline as process_host: chunks of whole utterances, ~64 MB each; every chunk is one call of the
     // device-resident ragged path on its own offsets, its rows land behind those of the chunk before it.  A sample format:
     // the chunks are cut by sample count as for int16, their raw bytes cross the wire and the ragged path decodes them
-    const size_t kChunkBytes = host_chunk_bytes(), ssz = sample_bytes(h);
-    struct Range { size_t u0, u1, rows0; };
-    std::vector<Range> ranges;
+    const size_t ssz = sample_bytes(h);
+    const std::vector<mfcc_batch::UttRange> ranges =
+        mfcc_batch::cut_ragged(offsets, frame_offsets, n_utt, host_chunk_bytes());
     std::vector<PipeChunk> pc;
-    {
-        size_t u0 = 0, rows = 0, rows0 = 0;
-        for (size_t u = 0; u < n_utt; ++u) {
-            rows += count_frames(h->r, rel[u + 1] - rel[u]);
-            const bool last = u + 1 == n_utt;
-            if (last || (rel[u + 1] - rel[u0]) * sizeof(int16_t) >= kChunkBytes) {
-                ranges.push_back({u0, u + 1, rows0});
-                pc.push_back({sample_at(h, pcm, offsets[0] + rel[u0]), (rel[u + 1] - rel[u0]) * ssz, out + rows0 * ncep,
-                              (rows - rows0) * ncep * sizeof(OutT)});
-                u0 = u + 1;
-                rows0 = rows;
-            }
-        }
-    }
-    frame_offsets[0] = 0;
+    pc.reserve(ranges.size());
+    for (const mfcc_batch::UttRange &r : ranges)
+        pc.push_back({sample_at(h, pcm, offsets[r.u0]), (offsets[r.u1] - offsets[r.u0]) * ssz, out + r.rows0 * ncep,
+                      (r.rows1 - r.rows0) * ncep * sizeof(OutT)});
+    // the frame counts of the scan, chunk by chunk (a chunk's call does not count them again)
+    const std::vector<size_t> counts(frame_offsets, frame_offsets + n_utt + 1);
     std::vector<size_t> loc, fo;
     // MFCC_HIP_VAD_SELECT: every chunk returns its voiced rows only (the call below synchronizes and reports them), so its
     // copy back shrinks and lands behind the voiced rows of the chunks before it
     const bool sel_mode = !fixed && h->vad_mode;
     size_t sel_rows = 0;
-    return run_host_pipeline(h, pc, sample_at(h, pcm, offsets[0]), rel[n_utt] * ssz, out, total * ncep * sizeof(OutT),
-                             [&](size_t i, void *d_in, void *d_out) {
-        const Range &r = ranges[i];
+    return run_host_pipeline(h, pc, sample_at(h, pcm, offsets[0]), (offsets[n_utt] - offsets[0]) * ssz, out,
+                             sc.total * ncep * sizeof(OutT), [&](size_t i, void *d_in, void *d_out) {
+        const mfcc_batch::UttRange &r = ranges[i];
         const size_t k = r.u1 - r.u0;
         loc.assign(k + 1, 0);
         fo.assign(k + 1, 0);
-        for (size_t j = 0; j <= k; ++j) loc[j] = rel[r.u0 + j] - rel[r.u0];
-        const int rc = process_ragged_dev<OutT>(h, fixed, static_cast<const int16_t *>(d_in), loc.data(), k,
-                                                static_cast<OutT *>(d_out), pc[i].out_bytes / sizeof(OutT), fo.data());
+        for (size_t j = 0; j <= k; ++j) loc[j] = offsets[r.u0 + j] - offsets[r.u0];
+        const mfcc_batch::Scan csc =
+            mfcc_batch::scan_with(loc.data(), k, size_t(kRaggedTiles.tile),
+                                  [&](size_t u, size_t) { return counts[r.u0 + u + 1] - counts[r.u0 + u]; }, fo.data());
+        const int rc = ragged_scanned<OutT>(h, fixed, static_cast<const int16_t *>(d_in), loc.data(), k,
+                                            static_cast<OutT *>(d_out), pc[i].out_bytes / sizeof(OutT), fo.data(), csc);
         const size_t rows0 = sel_mode ? sel_rows : r.rows0;
         for (size_t j = 1; j <= k; ++j) frame_offsets[r.u0 + j] = rows0 + fo[j];
         if (sel_mode && !rc) {
