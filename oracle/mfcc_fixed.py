@@ -12,6 +12,23 @@ unpinned" against the RTL: it is a careful reading of the source, cross-checked
 by (a) an independent structural model (``oracle/mfcc_fixed_structural.py``: the
 three-RAM scheduler, the streaming window counter, the filterbank registers, the
 log FSM written the way the hardware is) and (b) closeness to the float model.
+The two restatements agree over the reachable range of every integer stage, not just on
+speech: ``tests/fixed_stimuli.py`` writes inputs on the pre-emphasised side and inverts
+pre-emphasis (a bijection modulo 2**16), and ``tests/test_fixed_reach_host.py`` compares
+the two stage by stage there.  Reach at 512/32, measured by ``fixed_stimuli.reach``
+(older inputs: golden wav, synthetic speech, noise, square, zeros, -32768, sine):
+
+    quantity                                   older inputs      stimuli
+    re*re + im*im before >> 2 (pow2.py:32)     2**21.40          2**28.21 (17593**2, bin 0)
+    the same at a bin a filter reads           2**21.40          2**26.90 (bound 2**26.92)
+    largest |fft_re|, |fft_im|                 1531, 1615        17593, 11137
+    mel == 0 in a frame with mel >= 2**15      318               713
+    OR of all mel                              0xFFFF            0xFFFF
+    largest log                                32764             32766
+    pre-emphasis wraps up / down               1596 / 1571       5299 / 4912
+    16-bit wrap in an FFT-512 / DCT-FFT stage  never             never (unreachable)
+
+The same power mark holds at 64/4, 256/16, 512/8, 512/16 and 1024/64.
 What IS pinned by data the reference holds (``tests/golden/notebook_known_answers.json``,
 extracted from the stored outputs of ``notebook/MFCC.ipynb``): the 64-entry window ROM,
 ``offsetlast`` and the full 512-entry reconstructed window curve (cell 17), and the 34

@@ -6,6 +6,9 @@ must report, and the contract its results are held to -- TEST INFRASTRUCTURE ONL
 
 A test asserts ``kernel_name()`` before anything else, so that a handle rerouted to another kernel fails loudly
 instead of testing the wrong code.  All geometry comes from ``nfft`` / ``hop`` of the row.
+
+The input kinds below stay quiet behind pre-emphasis, full scale included; ``fixed_stimuli.STIMULI`` is the loud set
+of the fixed families (tests/test_gpu_fixed_reach.py).
 """
 from __future__ import annotations
 
