@@ -30,10 +30,11 @@ def split(a):
 
 
 def emulate(pcm, model, n_cep=13, nfft=512, hop=170, n_mel=32, sample_rate=16000, power_scale=512.0, lifter=0.0,
-            mutant=None):
+            mutant=None, output="cepstra"):
     """fp32 / bf16 x 2 emulation of a kernel of ``model`` (notebook framing), optionally with a ``mutant``:
     ("coef", frame % 16, coef, delta), ("mel", term), ("dct", term) -- split term 0: Wh Ph, 1: Wh Pl (Dh Ll),
-    2: Wl Ph (Dl Lh) dropped in tile column 15 -- or ("emphasis",): history 0 at the first frame of every tile."""
+    2: Wl Ph (Dl Lh) dropped in tile column 15 -- or ("emphasis",): history 0 at the first frame of every tile.
+    ``output="logmel"``: the fp32 log-mel rows (``n_cep`` is ignored; a "coef" mutant names a band)."""
     mel_kind, dct_kind = eb.MODELS[model]
     x = np.asarray(pcm, dtype=np.float64)
     emph = mf.pre_emphasis(x)                                   # exact in fp32: (32 x - 31 x') / 32
@@ -61,9 +62,12 @@ def emulate(pcm, model, n_cep=13, nfft=512, hop=170, n_mel=32, sample_rate=16000
         E = (terms[0] + terms[1]) + terms[2]
     with np.errstate(divide="ignore"):
         Lm = np.log2(E.astype(np.float32))
-    D = mf.dct_basis(n_mel, n_mel)[:n_cep].astype(np.float32)
+    if output == "logmel":
+        n_cep, dct_kind, D = n_mel, "identity", None
+    else:
+        D = mf.dct_basis(n_mel, n_mel)[:n_cep].astype(np.float32)
     with np.errstate(invalid="ignore"):
-        c = Lm @ D.T
+        c = Lm.copy() if D is None else Lm @ D.T
         if dct_kind == "bf16x2":
             Dh, Dl = split(D)
             Lh, Ll = split(Lm)
