@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MFCC_HIP_LIB: diagnostic override for A/B runs of experimental builds of the same ABI (tools/ab.sh)
 LIB_PATH = os.environ.get("MFCC_HIP_LIB") or os.path.join(_HERE, "libmfcc_hip.so")
@@ -114,8 +116,19 @@ class Pcen(C.Structure):
 
 PCEN_TILE = 128
 
+Handle = C.c_void_p           # what a create call fills in: Handle(), passed with byref
+
+
+def ptr(x):
+    """The address of a NumPy array's or a torch tensor's first element as the plain integer every ``c_void_p`` argument
+    below takes; ``None`` stays ``None``, a NULL pointer.  The caller keeps ``x`` alive over the call."""
+    if x is None:
+        return None
+    return x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr()
+
+
 # every symbol include/mfcc_hip.h declares: name -> (restype, argtypes)
-_H = C.c_void_p
+_H = Handle
 _SZ = C.c_size_t
 _PSZ = C.POINTER(C.c_size_t)
 SYMBOLS = {

@@ -15,6 +15,7 @@ buffers.  Without a GPU :class:`MFCC` construction raises ``MfccHipError(NOT_FOU
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
@@ -22,7 +23,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import MfccHipError, Params
+from ._lib import MfccHipError, Params, ptr
 
 PAD_NOTEBOOK = _lib.PAD_NOTEBOOK
 PAD_STREAM = _lib.PAD_STREAM
@@ -55,12 +56,21 @@ def normalize_mode(mode) -> int:
         raise ValueError("normalize must be None, 'mean' or 'meanvar', not %r" % (mode,)) from None
 
 
+def _is_int(v):
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+
+def _is_f32(v):
+    """A real number that is still finite as the float the ABI takes."""
+    return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and \
+        abs(float(v)) <= float(np.finfo(np.float32).max)
+
+
 def _delta_args(order, window, orders=(0, 1, 2)):
     """(order, window) as ints, or ValueError: order in ``orders``, window 1..8 (MFCC_HIP_MAX_DELTA_WINDOW)."""
-    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or int(order) not in orders:
+    if not _is_int(order) or int(order) not in orders:
         raise ValueError("deltas must be one of %s, not %r" % (orders, order))
-    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or \
-            not 1 <= int(window) <= _lib.MAX_DELTA_WINDOW:
+    if not _is_int(window) or not 1 <= int(window) <= _lib.MAX_DELTA_WINDOW:
         raise ValueError("delta_window must be 1..%d, not %r" % (_lib.MAX_DELTA_WINDOW, window))
     return int(order), int(window)
 
@@ -74,26 +84,20 @@ def _vad_args(mode=None, column=0, energy_threshold=5.0, energy_mean_scale=0.5, 
     mfcc_hip_set_vad / mfcc_hip_vad_dev, or ValueError: mode ``None`` or ``"select"``, column an int >= 0 (below
     ``width`` when given), a finite threshold, a finite scale >= 0, context 0..64 (MFCC_HIP_MAX_VAD_CONTEXT),
     0 < proportion < 1.  The defaults are Kaldi's compute-vad-energy."""
-    def is_int(v):
-        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
-
-    def is_f32(v):                                  # a real number that is still finite as the float the ABI takes
-        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and \
-            abs(float(v)) <= float(np.finfo(np.float32).max)
     try:
         m = _VAD[mode]
     except (KeyError, TypeError):
         raise ValueError("vad must be None or 'select', not %r" % (mode,)) from None
-    if not is_int(column) or int(column) < 0 or (width is not None and int(column) >= int(width)):
+    if not _is_int(column) or int(column) < 0 or (width is not None and int(column) >= int(width)):
         raise ValueError("vad_column must be an int in 0..%s, not %r" % ("width - 1" if width is None else width - 1,
                                                                          column))
-    if not is_f32(energy_threshold):
+    if not _is_f32(energy_threshold):
         raise ValueError("vad_energy_threshold must be a finite number, not %r" % (energy_threshold,))
-    if not is_f32(energy_mean_scale) or energy_mean_scale < 0:
+    if not _is_f32(energy_mean_scale) or energy_mean_scale < 0:
         raise ValueError("vad_energy_mean_scale must be a finite number >= 0, not %r" % (energy_mean_scale,))
-    if not is_int(frames_context) or not 0 <= int(frames_context) <= _lib.MAX_VAD_CONTEXT:
+    if not _is_int(frames_context) or not 0 <= int(frames_context) <= _lib.MAX_VAD_CONTEXT:
         raise ValueError("vad_frames_context must be 0..%d, not %r" % (_lib.MAX_VAD_CONTEXT, frames_context))
-    if not is_f32(proportion_threshold) or not 0.0 < float(np.float32(proportion_threshold)) < 1.0:
+    if not _is_f32(proportion_threshold) or not 0.0 < float(np.float32(proportion_threshold)) < 1.0:
         raise ValueError("vad_proportion_threshold must lie strictly between 0 and 1, not %r" % (proportion_threshold,))
     return (m, int(column), float(energy_threshold), float(energy_mean_scale), int(frames_context),
             float(proportion_threshold))
@@ -113,9 +117,6 @@ def _pcen_args(pcen=None, samplerate=16000, hop=170, **kw):
     """``struct mfcc_hip_pcen`` of ``pcen`` (``True``: the defaults; a dict of ``s`` or ``time_constant``, ``alpha``,
     ``delta``, ``r``, ``eps``; keywords on top of it), ``None`` for ``None`` / ``False``, or ValueError: real numbers
     that stay finite as fp32, ``0 < s <= 1``, ``0 <= alpha <= 1``, ``delta >= 0``, ``0 < r <= 1``, ``eps > 0``."""
-    def is_f32(v):                                  # a real number that is still finite as the float the ABI takes
-        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and \
-            abs(float(v)) <= float(np.finfo(np.float32).max)
     if pcen is None or pcen is False:
         if kw:
             raise ValueError("PCEN parameters %s without pcen" % sorted(kw))
@@ -132,12 +133,12 @@ def _pcen_args(pcen=None, samplerate=16000, hop=170, **kw):
         tc = a.pop("time_constant")
         if "s" in a:
             raise ValueError("pcen takes s or time_constant, not both")
-        if not is_f32(tc) or not float(tc) > 0.0:
+        if not _is_f32(tc) or not float(tc) > 0.0:
             raise ValueError("pcen time_constant must be a finite number of seconds > 0, not %r" % (tc,))
         a["s"] = pcen_smoothing(tc, samplerate, hop)
     v = dict(PCEN_DEFAULTS, **a)
     for k in PCEN_DEFAULTS:
-        if not is_f32(v[k]):
+        if not _is_f32(v[k]):
             raise ValueError("pcen %s must be a finite number, not %r" % (k, v[k]))
     f = {k: float(np.float32(v[k])) for k in PCEN_DEFAULTS}              # the values the library sees
     if not 0.0 < f["s"] <= 1.0:
@@ -163,7 +164,7 @@ def pcen_constants(pcen=True, samplerate=16000, hop=170, **kw):
         raise ValueError("pcen_constants needs parameters")
     decay = np.empty(_lib.PCEN_TILE, dtype=np.float32)
     a, dr = C.c_float(), C.c_float()
-    _lib.check(_lib.load().mfcc_hip_pcen_constants(C.byref(p), decay.ctypes.data_as(C.c_void_p), C.byref(a), C.byref(dr)),
+    _lib.check(_lib.load().mfcc_hip_pcen_constants(C.byref(p), ptr(decay), C.byref(a), C.byref(dr)),
                "pcen_constants")
     return decay, np.float32(a.value), np.float32(dr.value)
 
@@ -175,17 +176,15 @@ def _window_args(window, min_window=_MIN_WINDOW, center=True):
     """(window, min_window, center) as ints for mfcc_hip_set_normalize_window, or ValueError.  ``window`` None: off,
     (0, 1, 1).  Otherwise 1 <= min_window <= window <= 16 384 (MFCC_HIP_MAX_NORMALIZE_WINDOW); a ``min_window`` left
     at its default is clamped to ``window``."""
-    def is_int(v):
-        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
-    if isinstance(center, bool) or (is_int(center) and int(center) in (0, 1)):
+    if isinstance(center, bool) or (_is_int(center) and int(center) in (0, 1)):
         center = int(center)
     else:
         raise ValueError("normalize_center must be True or False, not %r" % (center,))
     if window is None:
         return 0, 1, center
-    if not is_int(window) or not 1 <= int(window) <= _lib.MAX_NORMALIZE_WINDOW:
+    if not _is_int(window) or not 1 <= int(window) <= _lib.MAX_NORMALIZE_WINDOW:
         raise ValueError("normalize_window must be None or 1..%d, not %r" % (_lib.MAX_NORMALIZE_WINDOW, window))
-    if not is_int(min_window):
+    if not _is_int(min_window):
         raise ValueError("normalize_min_window must be an int, not %r" % (min_window,))
     window, min_window = int(window), int(min_window)
     if min_window == _MIN_WINDOW:
@@ -222,7 +221,7 @@ def _win_length(win_length, nfft, hop) -> int:
     nfft = int(nfft)
     if win_length is None:
         return nfft
-    if isinstance(win_length, bool) or not isinstance(win_length, (int, np.integer)):
+    if not _is_int(win_length):
         raise ValueError("win_length must be an integer or None, not %r" % (win_length,))
     win_length = int(win_length)
     hop = nfft // 3 if hop is None or int(hop) == 0 else int(hop)
@@ -301,7 +300,7 @@ def get_table(which, win_length=None, mel="notebook", fmin=0.0, fmax=None, **kw)
     n = C.c_size_t(0)
     _lib.check(lib.mfcc_hip_get_table_banked(C.byref(p), L, C.byref(bank), which, None, 0, C.byref(n)), "get_table")
     buf = np.empty(n.value, dtype=np.uint8)
-    _lib.check(lib.mfcc_hip_get_table_banked(C.byref(p), L, C.byref(bank), which, buf.ctypes.data, buf.nbytes, C.byref(n)))
+    _lib.check(lib.mfcc_hip_get_table_banked(C.byref(p), L, C.byref(bank), which, ptr(buf), buf.nbytes, C.byref(n)))
     return buf.view(_TABLE_DTYPES[which])
 
 
@@ -309,7 +308,103 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
-class MFCC:
+# ---- what every entry point does to its arrays in front of the library call: one helper per job
+def _offsets(offsets, what, of, n=None, limit=None, unit=1, ordered=True, limit_from=1):
+    """``offsets`` (segment, utterance or line ``u`` = entries ``u``, ``u + 1``) as a contiguous 1-D uint64 array, or
+    ValueError: not 1-D, no entry (``n`` given: not ``n + 1`` entries), decreasing, or the last one times ``unit`` beyond
+    ``limit`` (the size of ``of``).  ``ordered=False`` leaves the order unchecked: the segment passes hand a decreasing
+    list to the library (``INVALID_PARAM``), ``process_packed`` checks it on the lengths it needs anyway.
+    ``limit_from=2`` (the segment passes) holds only a list with a segment to the limit: one entry reads nothing."""
+    a = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if a.ndim != 1 or (len(a) < 1 if n is None else len(a) != n + 1):
+        raise ValueError("%s must be 1-D with %s entries" % (what, "n + 1 (n >= 0)" if n is None else n + 1))
+    if ordered and bool((a[1:] < a[:-1]).any()):
+        raise ValueError("%s must not decrease" % what)
+    if limit is not None and len(a) >= limit_from and int(a[-1]) * unit > limit:
+        raise ValueError("%s run past the end of %s" % (what, of))
+    return a
+
+
+def _shape_offsets(shape):
+    """The offsets of the rows of a ``(frames, width)`` tensor, one segment, or of a ``(channels, frames, width)`` one,
+    a segment per channel."""
+    nseg, per = (int(shape[0]), int(shape[1])) if len(shape) == 3 else (1, int(shape[0]))
+    return np.arange(nseg + 1, dtype=np.uint64) * np.uint64(per)
+
+
+def _length_offsets(lengths):
+    """``[0, l0, l0 + l1, ...]`` of a sequence of lengths."""
+    a = np.zeros(len(lengths) + 1, dtype=np.uint64)
+    if len(lengths):
+        a[1:] = np.cumsum(lengths, dtype=np.uint64)
+    return a
+
+
+def _indices(idx, n_all):
+    """The index list of a ``flush`` / ``reset``: ``(uint64 array, its length)``, or ``(None, n_all)`` for ``None`` = all."""
+    if idx is None:
+        return None, n_all
+    s = np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1)
+    return s, len(s)
+
+
+def _host_samples(x, sample_format, what, ndim=None):
+    """``x`` as a contiguous NumPy array, or TypeError: the dtype is not the one of ``sample_format``, or (``ndim``
+    given) the rank is not ``ndim``."""
+    x = np.ascontiguousarray(x)
+    dtype = np.dtype(_SAMPLE[sample_format][1])
+    if x.dtype != dtype or (ndim is not None and x.ndim != ndim):
+        want, got = (dtype.name, x.dtype) if ndim is None else ("%d-D %s" % (ndim, dtype.name), "%d-D %s" % (x.ndim, x.dtype))
+        if sample_format == "s16":
+            raise TypeError("%s must be %s (the core's sink is signed 16 bit, mfcc.py:29)" % (what, want))
+        raise TypeError("%s must be %s for sample_format=%r, not %s" % (what, want, sample_format, got))
+    return x
+
+
+def _out(like, out, want, dtype, make):
+    """``out`` checked -- shape ``want`` (``None`` in it: any capacity), dtype, contiguous, on the device of ``like`` --
+    or, without one, what ``make()`` returns.  The kernels get raw pointers: anything else would be an out-of-bounds write."""
+    if out is None:
+        return make()
+    shape = tuple(out.shape)
+    fits = shape == want or (len(shape) == len(want) and all(w is None or w == n for w, n in zip(want, shape)))
+    if not fits or out.dtype != dtype or not out.is_contiguous() or out.device != like.device:
+        shape = "(%s)" % ", ".join("capacity" if w is None else str(w) for w in want) if None in want else str(want)
+        raise ValueError("out must be a contiguous %s tensor of shape %s on %s"
+                         % (str(dtype).split(".")[-1], shape, like.device))
+    return out
+
+
+def _numpy_if(from_numpy, *tensors):
+    """The results of a call whose input was a NumPy array: NumPy arrays as well (one copy out)."""
+    return tuple(t.cpu().numpy() for t in tensors) if from_numpy else tensors
+
+
+class _Owner:
+    """Owns one object of the library: a subclass names the attribute that holds its pointer and the entry point that
+    destroys it."""
+    _ptr = _destroy = None
+
+    def close(self):
+        # either order is safe: a handle closed first is kept alive by the library until its last session / bank / gate goes
+        if getattr(self, self._ptr, None):
+            getattr(self._lib, self._destroy)(getattr(self, self._ptr))
+        setattr(self, self._ptr, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class MFCC(_Owner):
     """``MFCC(width=16, nfft=512, samplerate=16e3, nfilters=16, nceptrums=16)`` -- same
     constructor arguments as ``mfcc/core/mfcc.py:20-21``; extra keyword arguments select the
     host driver's framing (``pad_mode``), the float path's power scale / lifter and the device.
@@ -373,20 +468,11 @@ class MFCC:
     deltas, delta_window = 0, 2                 # the state after mfcc_hip_create
     vad = None
     sample_format = "s16"
+    _ptr, _destroy = "_h", "mfcc_hip_destroy"
 
     def _sample_np(self):
         """The NumPy dtype a sample array of this handle must have."""
         return np.dtype(_SAMPLE[self.sample_format][1])
-
-    def _samples_host(self, x, what="pcm"):
-        """``x`` as a contiguous NumPy array of the handle's sample dtype, or TypeError."""
-        x = np.ascontiguousarray(x)
-        if x.dtype != self._sample_np():
-            if self.sample_format == "s16":
-                raise TypeError("%s must be int16 (the core's sink is signed 16 bit, mfcc.py:29)" % what)
-            raise TypeError("%s must be %s for sample_format=%r, not %s"
-                            % (what, self._sample_np().name, self.sample_format, x.dtype))
-        return x
 
     def _samples_dev_ok(self, t):
         """Whether a torch tensor is a CUDA(HIP) tensor of the handle's sample dtype."""
@@ -424,7 +510,7 @@ class MFCC:
                                    lifter=lifter, device=device, impl=impl, output=output)
         self.hop = self._params.hop or self.nfft // 3
         self.output = "logmel" if self._params.output == _lib.OUTPUT_LOGMEL else "cepstra"
-        h = C.c_void_p()
+        h = _lib.Handle()
         self._device_index = None
         if int(device) < 0:
             # "the current device" is resolved NOW, by the library, from torch's current device
@@ -480,30 +566,11 @@ class MFCC:
         import torch
         if rows.dtype != torch.float32 or not rows.is_cuda or not rows.is_contiguous() or rows.dim() not in (2, 3):
             raise TypeError("rows must be a contiguous 2-D or 3-D CUDA(HIP) float32 tensor")
-        width = int(rows.shape[-1])
         if frame_offsets is None:
-            nseg = int(rows.shape[0]) if rows.dim() == 3 else 1
-            per = int(rows.shape[1]) if rows.dim() == 3 else int(rows.shape[0])
-            return np.arange(nseg + 1, dtype=np.uint64) * np.uint64(per)
-        fo = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
-        if fo.ndim != 1 or len(fo) < 1:
-            raise ValueError("frame_offsets must be 1-D with n_segments + 1 entries")
-        if len(fo) > 1 and int(fo[-1]) * width > rows.numel():
-            raise ValueError("frame_offsets run past the end of rows")
-        return fo
-
-    @staticmethod
-    def _out(rows, out, want, dtype, make):
-        """``out`` checked -- shape ``want`` (None: any capacity), dtype, contiguous, on the device of ``rows`` -- or,
-        without one, what ``make()`` returns."""
-        if out is None:
-            return make()
-        fits = out.dim() == len(want) and all(w is None or w == int(n) for w, n in zip(want, out.shape))
-        if not fits or out.dtype != dtype or not out.is_contiguous() or out.device != rows.device:
-            shape = "(%s)" % ", ".join("capacity" if w is None else str(w) for w in want) if None in want else str(want)
-            raise ValueError("out must be a contiguous %s tensor of shape %s on %s"
-                             % (str(dtype).split(".")[-1], shape, rows.device))
-        return out
+            return _shape_offsets(rows.shape)
+        # a decreasing list is the library's to refuse; one entry is no segment: nothing is read, whatever it says
+        return _offsets(frame_offsets, "frame_offsets", "rows", limit=rows.numel(), unit=int(rows.shape[-1]),
+                        ordered=False, limit_from=2)
 
     def vad_rows(self, rows, frame_offsets=None, column=0, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0,
                  proportion_threshold=0.6, out=None):
@@ -518,12 +585,10 @@ class MFCC:
                       width=width)
         want = tuple(rows.shape[:-1])
         make = torch.zeros if frame_offsets is not None else torch.empty
-        out = self._out(rows, out, want, torch.uint8, lambda: make(want, device=rows.device, dtype=torch.uint8))
+        out = _out(rows, out, want, torch.uint8, lambda: make(want, device=rows.device, dtype=torch.uint8))
         self._check_device(rows)
-        with self._on_torch_stream(rows.device):
-            _lib.check(self._lib.mfcc_hip_vad_dev(self._h, C.c_void_p(rows.data_ptr()), width, a[1],
-                                                  fo.ctypes.data_as(C.c_void_p), len(fo) - 1, a[2], a[3], a[4], a[5],
-                                                  C.c_void_p(out.data_ptr())), "vad_dev")
+        self._call(rows.device, "vad_dev", self._h, ptr(rows), width, a[1], ptr(fo), len(fo) - 1, a[2], a[3], a[4], a[5],
+                   ptr(out))
         return out
 
     def select_rows(self, rows, voiced, frame_offsets=None, out=None):
@@ -540,15 +605,12 @@ class MFCC:
             raise ValueError("voiced must be a contiguous uint8 tensor of shape %s on %s"
                              % (tuple(rows.shape[:-1]), rows.device))
         need = int(fo[-1]) - int(fo[0])
-        out = self._out(rows, out, (None, width), torch.float32,
-                        lambda: torch.empty((need, width), device=rows.device, dtype=torch.float32))
+        out = _out(rows, out, (None, width), torch.float32,
+                   lambda: torch.empty((need, width), device=rows.device, dtype=torch.float32))
         self._check_device(rows)
         oo = np.zeros(len(fo), dtype=np.uint64)
-        with self._on_torch_stream(rows.device):
-            _lib.check(self._lib.mfcc_hip_select_dev(self._h, C.c_void_p(rows.data_ptr()), width,
-                                                     C.c_void_p(voiced.data_ptr()), fo.ctypes.data_as(C.c_void_p),
-                                                     len(fo) - 1, C.c_void_p(out.data_ptr()), int(out.shape[0]),
-                                                     oo.ctypes.data_as(C.c_void_p)), "select_dev")
+        self._call(rows.device, "select_dev", self._h, ptr(rows), width, ptr(voiced), ptr(fo), len(fo) - 1, ptr(out),
+                   int(out.shape[0]), ptr(oo))
         return out[:int(oo[-1])], oo
 
     def set_normalize_window(self, window, min_window=_MIN_WINDOW, center=True):
@@ -575,12 +637,9 @@ class MFCC:
         fo = self._segments(rows, frame_offsets)
         width = int(rows.shape[-1])
         want = tuple(rows.shape[:-1]) + (width * (1 + order),)
-        out = self._out(rows, out, want, torch.float32, lambda: torch.empty(want, device=rows.device, dtype=torch.float32))
+        out = _out(rows, out, want, torch.float32, lambda: torch.empty(want, device=rows.device, dtype=torch.float32))
         self._check_device(rows)
-        with self._on_torch_stream(rows.device):
-            _lib.check(self._lib.mfcc_hip_deltas_dev(self._h, C.c_void_p(rows.data_ptr()), width,
-                                                     C.c_void_p(out.data_ptr()), fo.ctypes.data_as(C.c_void_p),
-                                                     len(fo) - 1, order, window), "deltas_dev")
+        self._call(rows.device, "deltas_dev", self._h, ptr(rows), width, ptr(out), ptr(fo), len(fo) - 1, order, window)
         return out
 
     def set_pcen(self, pcen=True, **params):
@@ -598,9 +657,7 @@ class MFCC:
         p = _pcen_args(True, self.samplerate, self.hop, **params)
         fo = self._segments(rows, frame_offsets)
         self._check_device(rows)
-        with self._on_torch_stream(rows.device):
-            _lib.check(self._lib.mfcc_hip_pcen_dev(self._h, C.c_void_p(rows.data_ptr()), int(rows.shape[-1]),
-                                                   fo.ctypes.data_as(C.c_void_p), len(fo) - 1, C.byref(p)), "pcen_dev")
+        self._call(rows.device, "pcen_dev", self._h, ptr(rows), int(rows.shape[-1]), ptr(fo), len(fo) - 1, C.byref(p))
         return rows
 
     def set_normalize(self, mode):
@@ -627,35 +684,12 @@ class MFCC:
             def make():         # a new tensor: rows the segments do not cover (and every row, for mode None) are copies of the input
                 whole = frame_offsets is None and normalize_mode(mode) != _lib.NORMALIZE_NONE
                 return torch.empty_like(rows) if whole else rows.clone()
-            out = self._out(rows, out, tuple(rows.shape), torch.float32, make)
-            with self._on_torch_stream(rows.device):
-                _lib.check(self._lib.mfcc_hip_normalize_sliding_dev(
-                    self._h, C.c_void_p(rows.data_ptr()), width, C.c_void_p(out.data_ptr()),
-                    fo.ctypes.data_as(C.c_void_p), len(fo) - 1, normalize_mode(mode), w, m, c), "normalize_sliding_dev")
+            out = _out(rows, out, tuple(rows.shape), torch.float32, make)
+            self._call(rows.device, "normalize_sliding_dev", self._h, ptr(rows), width, ptr(out), ptr(fo), len(fo) - 1,
+                       normalize_mode(mode), w, m, c)
             return out
-        with self._on_torch_stream(rows.device):
-            _lib.check(self._lib.mfcc_hip_normalize_dev(self._h, C.c_void_p(rows.data_ptr()), width,
-                                                        fo.ctypes.data_as(C.c_void_p), len(fo) - 1,
-                                                        normalize_mode(mode)), "normalize_dev")
+        self._call(rows.device, "normalize_dev", self._h, ptr(rows), width, ptr(fo), len(fo) - 1, normalize_mode(mode))
         return rows
-
-    # -- lifetime (``reset`` of the core clears all state: every call here starts from reset)
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mfcc_hip_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     @property
     def num_features(self) -> int:
@@ -684,7 +718,7 @@ class MFCC:
     def set_stream(self, stream_ptr):
         """Launch on a caller-provided hipStream_t (e.g. ``torch.cuda.current_stream().cuda_stream``;
         0 / None is the HIP null stream, torch's default)."""
-        _lib.check(self._lib.mfcc_hip_set_stream(self._h, C.c_void_p(stream_ptr or 0)))
+        _lib.check(self._lib.mfcc_hip_set_stream(self._h, stream_ptr or None))
 
     def use_own_stream(self):
         _lib.check(self._lib.mfcc_hip_use_own_stream(self._h))
@@ -694,7 +728,7 @@ class MFCC:
 
     # -- the hot path ---------------------------------------------------------------
     def _host(self, pcm, fixed):
-        pcm = self._samples_host(pcm)
+        pcm = _host_samples(pcm, self.sample_format, "pcm")
         squeeze = pcm.ndim == 1
         if squeeze:
             pcm = pcm[None, :]
@@ -705,7 +739,7 @@ class MFCC:
         out = np.empty((nch, nf, self._row(fixed)), dtype=np.int16 if fixed else np.float32)
         got = C.c_size_t(0)
         fn = self._lib.mfcc_hip_process_fixed_i16 if fixed else self._lib.mfcc_hip_process_i16
-        _lib.check(fn(self._h, pcm.ctypes.data, n, nch, out.ctypes.data, out.size, C.byref(got)),
+        _lib.check(fn(self._h, ptr(pcm), n, nch, ptr(out), out.size, C.byref(got)),
                    "process" if not self.vad else self._DENSE_VAD)
         assert got.value == nf
         return out[0] if squeeze else out
@@ -727,18 +761,12 @@ class MFCC:
         self._check_device(pcm)
         odt = torch.int16 if fixed else torch.float32
         row = self._row(fixed)
-        if out is None:
-            out = torch.empty((nch, nf, row), device=pcm.device, dtype=odt)
-        else:
-            # the kernel gets raw pointers: a wrong shape / dtype / layout / device would be an out-of-bounds write
-            want = (nf, row) if squeeze and out.dim() == 2 else (nch, nf, row)
-            if tuple(out.shape) != want or out.dtype != odt or not out.is_contiguous() or out.device != pcm.device:
-                raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (odt, want, pcm.device))
-        fn = self._lib.mfcc_hip_process_fixed_i16_dev if fixed else self._lib.mfcc_hip_process_i16_dev
+        want = (nf, row) if squeeze and out is not None and out.dim() == 2 else (nch, nf, row)
+        out = _out(pcm, out, want, odt, lambda: torch.empty(want, device=pcm.device, dtype=odt))
         got = C.c_size_t(0)
-        with self._on_torch_stream(pcm.device):
-            _lib.check(fn(self._h, C.c_void_p(pcm.data_ptr()), n, pcm.stride(0), nch, int(halo),
-                          C.c_void_p(out.data_ptr()), C.byref(got)), "process_dev" if not self.vad else self._DENSE_VAD)
+        self._call(pcm.device, "process_fixed_i16_dev" if fixed else "process_i16_dev", self._h, ptr(pcm), n,
+                   pcm.stride(0), nch, int(halo), ptr(out), C.byref(got),
+                   what="process_dev" if not self.vad else self._DENSE_VAD)
         if squeeze and out.dim() == 3:
             return out[0]
         return out
@@ -746,28 +774,39 @@ class MFCC:
     _DENSE_VAD = ("process: a vad='select' handle returns a different number of rows per channel; pass one 1-D "
                   "utterance, or use process_batch / process_packed")
 
-    def _check_device(self, t):
-        """The handle's tables, stream and scratch live on ONE GPU: refuse tensors of another one."""
+    def _device(self):
+        """The handle's GPU as a torch device -- its tables, stream and scratch live on ONE: what the handle allocates
+        or copies in goes there.  ``device=-1`` was resolved from torch's current device when the handle was made."""
+        import torch
         if self._device_index is None:
-            import torch
             self._device_index = torch.cuda.current_device() if self._params.device < 0 else int(self._params.device)
-        if t.device.index != self._device_index:
+        return torch.device("cuda", self._device_index)
+
+    def _check_device(self, t):
+        """Refuse tensors of another GPU than the handle's."""
+        if t.device.index != (self._device_index if self._device_index is not None else self._device().index):
             raise ValueError("tensor on %s but this MFCC handle was created on cuda:%d" % (t.device, self._device_index))
 
+    @contextlib.contextmanager
     def _on_torch_stream(self, device):
         """Context: launch on torch's current stream of `device`, then go back to the handle's own stream, so
         that later host-path calls do not run on (or outlive) a stream torch owns."""
-        import contextlib
         import torch
+        self.set_stream(torch.cuda.current_stream(device).cuda_stream)
+        try:
+            yield
+        finally:
+            self.use_own_stream()
 
-        @contextlib.contextmanager
-        def ctx():
-            self.set_stream(torch.cuda.current_stream(device).cuda_stream)
-            try:
-                yield
-            finally:
-                self.use_own_stream()
-        return ctx()
+    def _call(self, device, name, obj, *args, what=None, ok=()):
+        """``mfcc_hip_<name>(obj, *args)`` on torch's current stream of ``device``; ``obj`` is this handle's ``_h`` or the
+        pointer of one of its sessions, banks or gates.  A code that is neither success nor in ``ok`` raises
+        ``MfccHipError`` with ``what`` (default: the name); the code is returned."""
+        with self._on_torch_stream(device):
+            rc = getattr(self._lib, "mfcc_hip_" + name)(obj, *args)
+        if rc not in ok:
+            _lib.check(rc, what or name)
+        return rc
 
     def process(self, pcm, halo=0, out=None):
         """Float contract: int16 PCM ``(n,)`` / ``(channels, n)`` -> float32 ``(.., frames, num_features)``.
@@ -801,18 +840,15 @@ class MFCC:
         if self.sample_format == "s16":
             utts = [np.ascontiguousarray(u, dtype=np.int16).reshape(-1) for u in utterances]
         else:
-            utts = [self._samples_host(u, "utterances").reshape(-1) for u in utterances]
+            utts = [_host_samples(u, self.sample_format, "utterances").reshape(-1) for u in utterances]
         n = len(utts)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            offsets[1:] = np.cumsum([u.size for u in utts], dtype=np.uint64)
+        offsets = _length_offsets([u.size for u in utts])
         flat = np.concatenate(utts) if n and int(offsets[-1]) else np.zeros(0, dtype=self._sample_np())
         fo = np.zeros(n + 1, dtype=np.uint64)
         nf = sum(self.num_frames(u.size) for u in utts)
         out = np.empty((nf, self._row(fixed)), dtype=np.int16 if fixed else np.float32)
         fn = self._lib.mfcc_hip_process_ragged_fixed_i16 if fixed else self._lib.mfcc_hip_process_ragged_i16
-        _lib.check(fn(self._h, flat.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), n,
-                      out.ctypes.data_as(C.c_void_p), out.size, fo.ctypes.data_as(C.c_void_p)), "process_ragged")
+        _lib.check(fn(self._h, ptr(flat), ptr(offsets), n, ptr(out), out.size, ptr(fo)), "process_ragged")
         assert int(fo[-1]) == nf or (self.vad and not fixed and int(fo[-1]) <= nf)
         return [out[int(fo[i]):int(fo[i + 1])] for i in range(n)]
 
@@ -823,8 +859,7 @@ class MFCC:
         if any(not self._samples_dev_ok(u) for u in utts):
             raise TypeError("device path needs %s tensors" % self._dev_what())
         n = len(utts)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum([u.numel() for u in utts], dtype=np.uint64)
+        offsets = _length_offsets([u.numel() for u in utts])
         # utterances that are consecutive views of one buffer (a corpus already laid out in HBM) are used in place
         in_place = n > 0 and all(u.is_contiguous() for u in utts) and all(
             utts[i].data_ptr() + utts[i].element_size() * utts[i].numel() == utts[i + 1].data_ptr() and
@@ -847,12 +882,10 @@ class MFCC:
         import torch
         if not self._samples_dev_ok(flat) or flat.dim() != 1 or not flat.is_contiguous():
             raise TypeError("flat must be a contiguous 1-D %s tensor" % self._dev_what())
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        offsets = _offsets(offsets, "offsets", "flat", limit=flat.numel(), ordered=False)
         n = len(offsets) - 1
-        if n < 0 or (n >= 0 and len(offsets) and int(offsets[-1]) > flat.numel()):
-            raise ValueError("offsets run past the end of flat")
         self._check_device(flat)
-        lens = np.diff(offsets.astype(np.int64))
+        lens = np.diff(offsets.astype(np.int64))             # the order is checked here: the lengths are needed anyway
         if n and int(lens.min()) < 0:
             raise ValueError("offsets must not decrease")
         fo = np.zeros(n + 1, dtype=np.uint64)
@@ -865,14 +898,9 @@ class MFCC:
             nf = int(sum(self.num_frames(int(v)) * int(c) for v, c in zip(uniq, counts)))
         odt = torch.int16 if fixed else torch.float32
         row = self._row(fixed)
-        if out is None:
-            out = torch.empty((nf, row), device=flat.device, dtype=odt)
-        elif tuple(out.shape) != (nf, row) or out.dtype != odt or not out.is_contiguous() or out.device != flat.device:
-            raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (odt, (nf, row), flat.device))
-        fn = self._lib.mfcc_hip_process_ragged_fixed_i16_dev if fixed else self._lib.mfcc_hip_process_ragged_i16_dev
-        with self._on_torch_stream(flat.device):
-            _lib.check(fn(self._h, C.c_void_p(flat.data_ptr()), offsets.ctypes.data_as(C.c_void_p), n,
-                          C.c_void_p(out.data_ptr()), out.numel(), fo.ctypes.data_as(C.c_void_p)), "process_ragged_dev")
+        out = _out(flat, out, (nf, row), odt, lambda: torch.empty((nf, row), device=flat.device, dtype=odt))
+        self._call(flat.device, "process_ragged_fixed_i16_dev" if fixed else "process_ragged_i16_dev", self._h, ptr(flat),
+                   ptr(offsets), n, ptr(out), out.numel(), ptr(fo), what="process_ragged_dev")
         if self.vad and not fixed:
             return out[:int(fo[-1])], fo                 # the voiced rows; the entry point has waited for the stream
         assert int(fo[-1]) == nf
@@ -880,17 +908,13 @@ class MFCC:
 
     def time_launches(self, pcm, out, fixed=False, warmup=2, iters=10) -> float:
         """Average kernel time in ms over ``iters`` launches, HIP events on the launch stream."""
-        import torch
         if pcm.dim() == 1:
             pcm = pcm[None, :]
         self._check_device(pcm)
         ms = C.c_float(0)
-        with self._on_torch_stream(pcm.device):
-            _lib.check(self._lib.mfcc_hip_time_dev(self._h, int(fixed), C.c_void_p(pcm.data_ptr()), pcm.shape[1],
-                                                   pcm.stride(0), pcm.shape[0], C.c_void_p(out.data_ptr()),
-                                                   warmup, iters, C.byref(ms)), "time_dev")
+        self._call(pcm.device, "time_dev", self._h, int(fixed), ptr(pcm), pcm.shape[1], pcm.stride(0), pcm.shape[0], ptr(out),
+                   warmup, iters, C.byref(ms))
         return float(ms.value)
-
 
     # -- online mode: the core's own interface, sink / source / reset (mfcc/core/mfcc.py:28-30) -----
     def stream(self, fixed=False) -> "MfccStream":
@@ -915,34 +939,31 @@ class MFCC:
                               deltas=deltas, delta_window=delta_window, pcen=pcen)
 
     # -- the receiver's power gate on fixed-point rows (software/cepstrum.c:93-183; include/mfcc_hip.h) -----
+    def _int16_rows_in(self, rows):
+        """``(rows, False)`` for a torch tensor; a NumPy int16 array is copied to the handle's GPU: ``(the copy, True)``,
+        and :func:`_numpy_if` then copies the results out."""
+        if _is_torch(rows):
+            return rows, False
+        import torch
+        rows = np.ascontiguousarray(rows)
+        if rows.dtype != np.int16:
+            raise TypeError("rows must be int16 (what process_fixed returns)")
+        return torch.from_numpy(rows).to(self._device()), True
+
     def _gate_rows_in(self, rows, frame_offsets):
         """``rows`` as a contiguous CUDA int16 tensor (a NumPy array is copied in: the flag says so), its segment
         offsets as a uint64 array and the row width."""
         import torch
-        from_numpy = not _is_torch(rows)
-        if from_numpy:
-            rows = np.ascontiguousarray(rows)
-            if rows.dtype != np.int16:
-                raise TypeError("rows must be int16 (what process_fixed returns)")
-            dev = torch.device("cuda", torch.cuda.current_device() if self._device_index is None else self._device_index)
-            rows = torch.from_numpy(rows).to(dev)
+        rows, from_numpy = self._int16_rows_in(rows)
         if rows.dtype != torch.int16 or not rows.is_cuda or not rows.is_contiguous() or rows.dim() not in (2, 3):
             raise TypeError("rows must be a contiguous 2-D or 3-D CUDA(HIP) int16 tensor")
         width = int(rows.shape[-1])
         if not 1 <= width <= 64:
             raise ValueError("rows must be 1..64 wide, not %d" % width)
         if frame_offsets is None:
-            nseg = int(rows.shape[0]) if rows.dim() == 3 else 1
-            per = int(rows.shape[1]) if rows.dim() == 3 else int(rows.shape[0])
-            fo = np.arange(nseg + 1, dtype=np.uint64) * np.uint64(per)
+            fo = _shape_offsets(rows.shape)
         else:
-            fo = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
-            if fo.ndim != 1 or len(fo) < 1:
-                raise ValueError("frame_offsets must be 1-D with n_segments + 1 entries")
-            if len(fo) > 1 and int(np.diff(fo.astype(np.int64)).min()) < 0:
-                raise ValueError("frame_offsets must not decrease")
-            if int(fo[-1]) * width > rows.numel():
-                raise ValueError("frame_offsets run past the end of rows")
+            fo = _offsets(frame_offsets, "frame_offsets", "rows", limit=rows.numel(), unit=width)
         self._check_device(rows)
         return rows, fo, width, from_numpy
 
@@ -964,14 +985,9 @@ class MFCC:
         power = torch.empty(n, device=rows.device, dtype=torch.int64)
         gate = torch.empty(n, device=rows.device, dtype=torch.uint8)
         gate_ref = torch.empty(n, device=rows.device, dtype=torch.uint8)
-        with self._on_torch_stream(rows.device):
-            _lib.check(self._lib.mfcc_hip_gate_dev(self._h, C.c_void_p(rows.data_ptr()), width,
-                                                   fo.ctypes.data_as(C.c_void_p), len(fo) - 1, nfr, st, thr,
-                                                   C.c_void_p(power.data_ptr()), C.c_void_p(gate.data_ptr()),
-                                                   C.c_void_p(gate_ref.data_ptr())), "gate_dev")
-        if from_numpy:
-            return power.cpu().numpy(), gate.cpu().numpy(), gate_ref.cpu().numpy(), wo
-        return power, gate, gate_ref, wo
+        self._call(rows.device, "gate_dev", self._h, ptr(rows), width, ptr(fo), len(fo) - 1, nfr, st, thr, ptr(power),
+                   ptr(gate), ptr(gate_ref))
+        return _numpy_if(from_numpy, power, gate, gate_ref) + (wo,)
 
     def gate_windows(self, rows, mask, frame_offsets=None, n_frames=93, stride=1, out=None):
         """The windows of ``rows`` (as in :meth:`gate_rows`) whose ``mask`` byte is not 0 -- ``mask``: uint8, one entry per
@@ -994,27 +1010,18 @@ class MFCC:
             raise ValueError("mask must be a contiguous uint8 tensor of %d entries on %s" % (int(wo[-1]), rows.device))
         oo = np.zeros(len(fo), dtype=np.uint64)
 
-        def call(o, starts, cap):
-            with self._on_torch_stream(rows.device):
-                return self._lib.mfcc_hip_gate_windows_dev(
-                    self._h, C.c_void_p(rows.data_ptr()), width, fo.ctypes.data_as(C.c_void_p), len(fo) - 1, nfr, st,
-                    C.c_void_p(mask.data_ptr()), C.c_void_p(o.data_ptr() if o is not None else 0),
-                    C.c_void_p(starts.data_ptr() if starts is not None else 0), cap, oo.ctypes.data_as(C.c_void_p))
-        if out is None:
-            rc = call(None, None, 0)
-            if rc not in (_lib.SUCCESS, _lib.ERROR_BUFFER_SMALL):
-                _lib.check(rc, "gate_windows_dev")
-            out = torch.empty((int(oo[-1]), nfr, width), device=rows.device, dtype=torch.int16)
-        elif out.dim() != 3 or tuple(out.shape[1:]) != (nfr, width) or out.dtype != torch.int16 or \
-                not out.is_contiguous() or out.device != rows.device:
-            raise ValueError("out must be a contiguous int16 tensor of shape (capacity, %d, %d) on %s"
-                             % (nfr, width, rows.device))
+        def call(o, starts, cap, ok=()):
+            self._call(rows.device, "gate_windows_dev", self._h, ptr(rows), width, ptr(fo), len(fo) - 1, nfr, st, ptr(mask),
+                       ptr(o), ptr(starts), cap, ptr(oo), ok=ok)
+
+        def sized():                                    # the count is asked for: BUFFER_SMALL fills the offsets
+            call(None, None, 0, ok=(_lib.ERROR_BUFFER_SMALL,))
+            return torch.empty((int(oo[-1]), nfr, width), device=rows.device, dtype=torch.int16)
+        out = _out(rows, out, (None, nfr, width), torch.int16, sized)
         starts = torch.empty(int(out.shape[0]), device=rows.device, dtype=torch.int64)
-        _lib.check(call(out, starts, int(out.shape[0])), "gate_windows_dev")
+        call(out, starts, int(out.shape[0]))
         n = int(oo[-1])
-        if from_numpy:
-            return out[:n].cpu().numpy(), starts[:n].cpu().numpy(), oo
-        return out[:n], starts[:n], oo
+        return _numpy_if(from_numpy, out[:n], starts[:n]) + (oo,)
 
     def power_gate(self, n_lines, n_cep=None, n_frames=93, stride=1, threshold=None) -> "MfccPowerGate":
         """A gate tracker for ``n_lines`` live lines on this handle: the receiver's circular window of ``n_frames`` rows
@@ -1041,33 +1048,21 @@ class MFCC:
         return int(nf.value)
 
 
-class MfccStream:
+class MfccStream(_Owner):
     """Online mode -- the stream interface of the nMigen core (``sink`` in, ``source`` out, ``reset``;
     mfcc/core/mfcc.py:28-30,116) and of its targets (wav2mfcc.py:27-42: bit 31 = soft reset; mic2mfcc.py:19-30).
     The session keeps the core's cross-frame state on the device: one pre-emphasis history sample and the
     samples of the frame in progress.  Any chunking gives the one-shot result, frame for frame, bit for bit."""
 
+    _ptr, _destroy = "_s", "mfcc_hip_stream_destroy"
+
     def __init__(self, mfcc: MFCC, fixed=False):
         self._m = mfcc
         self._lib = mfcc._lib
         self.fixed = bool(fixed)
-        s = C.c_void_p()
+        s = _lib.Handle()
         _lib.check(self._lib.mfcc_hip_stream_create(mfcc._h, int(self.fixed), C.byref(s)), "stream_create")
         self._s = s
-
-    def close(self):
-        # either order is safe: a handle closed first is kept alive by the library until its last session goes
-        if getattr(self, "_s", None):
-            self._lib.mfcc_hip_stream_destroy(self._s)
-        self._s = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     @property
     def pending(self) -> int:
@@ -1078,15 +1073,10 @@ class MfccStream:
 
     def push(self, samples) -> np.ndarray:
         """``sink``: int16 samples in; returns the ``(frames, num_features)`` they complete (possibly 0 rows)."""
-        samples = np.ascontiguousarray(samples)
-        if samples.dtype != self._m._sample_np() or samples.ndim != 1:
-            if self._m.sample_format != "s16":
-                raise TypeError("samples must be a 1-D %s array for sample_format=%r"
-                                % (self._m._sample_np().name, self._m.sample_format))
-            raise TypeError("samples must be a 1-D int16 array (the core's sink is signed 16 bit, mfcc.py:29)")
+        samples = _host_samples(samples, self._m.sample_format, "samples", ndim=1)
         out = self._out(int(self._lib.mfcc_hip_stream_max_frames(self._s, samples.size)))
         nf = C.c_size_t(0)
-        _lib.check(self._lib.mfcc_hip_stream_push(self._s, samples.ctypes.data, samples.size, out.ctypes.data,
+        _lib.check(self._lib.mfcc_hip_stream_push(self._s, ptr(samples), samples.size, ptr(out),
                                                   out.size, C.byref(nf)), "stream_push")
         return out[:nf.value]
 
@@ -1095,7 +1085,7 @@ class MfccStream:
         ``pad_mode="stream"``, nothing with ``"notebook"``; the session is reset afterwards."""
         out = self._out(1)
         nf = C.c_size_t(0)
-        _lib.check(self._lib.mfcc_hip_stream_flush(self._s, out.ctypes.data, out.size, C.byref(nf)), "stream_flush")
+        _lib.check(self._lib.mfcc_hip_stream_flush(self._s, ptr(out), out.size, C.byref(nf)), "stream_flush")
         return out[:nf.value]
 
     def reset(self):
@@ -1103,11 +1093,13 @@ class MfccStream:
         _lib.check(self._lib.mfcc_hip_stream_reset(self._s), "stream_reset")
 
 
-class MfccStreamBank:
+class MfccStreamBank(_Owner):
     """``n_streams`` independent :class:`MfccStream` sessions (N live lines) whose state lives on the device and which
     advance together: one push takes one chunk per stream and runs ONE launch of the frame kernels.  Every stream gets
     the rows a session of its own would have returned for the same chunks, bit for bit.  Equal chunks (lines in
     lockstep) compute exactly the frames returned; a mixed push computes ``active streams x most frames of any``."""
+
+    _ptr, _destroy = "_b", "mfcc_hip_bank_destroy"
 
     def __init__(self, mfcc: MFCC, n_streams, fixed=False, *, normalize=None, normalize_window=None, deltas=0,
                  delta_window=2, pcen=None):
@@ -1134,7 +1126,7 @@ class MfccStreamBank:
         self.pcen = None if p is None else dict(s=p.s, alpha=p.alpha, delta=p.delta, r=p.r, eps=p.eps)
         self.normalize, self.normalize_window = (normalize if mode != _lib.NORMALIZE_NONE else None), (window or None)
         self.deltas, self.delta_window = order, dwin
-        b = C.c_void_p()
+        b = _lib.Handle()
         if p is not None:
             _lib.check(self._lib.mfcc_hip_bank_create_online_pcen(mfcc._h, self.n_streams, C.byref(p), mode, window, order,
                                                                   dwin, C.byref(b)), "bank_create_online_pcen")
@@ -1146,20 +1138,6 @@ class MfccStreamBank:
                        "bank_create")
         self._b = b
 
-    def close(self):
-        # either order is safe: a handle closed first is kept alive by the library until its last bank / session goes
-        if getattr(self, "_b", None):
-            self._lib.mfcc_hip_bank_destroy(self._b)
-        self._b = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
     def __len__(self):
         return self.n_streams
 
@@ -1167,7 +1145,7 @@ class MfccStreamBank:
     def pending(self) -> np.ndarray:
         """Samples every stream holds back for its frame in progress: uint64 ``(n_streams,)``, each below ``win_length``."""
         p = np.zeros(self.n_streams, dtype=np.uint64)
-        _lib.check(self._lib.mfcc_hip_bank_pending(self._b, p.ctypes.data_as(C.c_void_p)), "bank_pending")
+        _lib.check(self._lib.mfcc_hip_bank_pending(self._b, ptr(p)), "bank_pending")
         return p
 
     @property
@@ -1184,26 +1162,15 @@ class MfccStreamBank:
     def held(self) -> np.ndarray:
         """Finished rows every stream has not returned yet: uint64 ``(n_streams,)``, each at most ``lag``."""
         p = np.zeros(self.n_streams, dtype=np.uint64)
-        _lib.check(self._lib.mfcc_hip_bank_held(self._b, p.ctypes.data_as(C.c_void_p)), "bank_held")
+        _lib.check(self._lib.mfcc_hip_bank_held(self._b, ptr(p)), "bank_held")
         return p
-
-    def _offsets(self, offsets):
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        if offsets.ndim != 1 or len(offsets) != self.n_streams + 1:
-            raise ValueError("offsets must be 1-D with n_streams + 1 = %d entries" % (self.n_streams + 1))
-        if int(np.diff(offsets.astype(np.int64)).min()) < 0:
-            raise ValueError("offsets must not decrease")
-        return offsets
 
     def _plan(self, offsets):
         fo = np.zeros(self.n_streams + 1, dtype=np.uint64)
         pending, held = self.pending, self.held
         _lib.check(self._lib.mfcc_hip_bank_plan_online_framed(C.byref(self._m._params), self._m.win_length, self.lag,
-                                                              pending.ctypes.data_as(C.c_void_p),
-                                                              held.ctypes.data_as(C.c_void_p),
-                                                              offsets.ctypes.data_as(C.c_void_p), self.n_streams,
-                                                              fo.ctypes.data_as(C.c_void_p), None, None),
-                   "bank_plan_online")
+                                                              ptr(pending), ptr(held), ptr(offsets), self.n_streams,
+                                                              ptr(fo), None, None), "bank_plan_online")
         return fo
 
     def num_frames(self, lengths) -> np.ndarray:
@@ -1212,9 +1179,7 @@ class MfccStreamBank:
         lengths = np.asarray(lengths, dtype=np.uint64).reshape(-1)
         if len(lengths) != self.n_streams:
             raise ValueError("one length per stream: %d, not %d" % (self.n_streams, len(lengths)))
-        offsets = np.zeros(self.n_streams + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum(lengths, dtype=np.uint64)
-        return self._plan(offsets)
+        return self._plan(_length_offsets(lengths))
 
     def _row(self):
         return self.num_features
@@ -1224,22 +1189,14 @@ class MfccStreamBank:
         ``(frames_u, num_features)`` arrays, the frames each stream completed (views of one buffer).  Synchronous."""
         if len(chunks) != self.n_streams:
             raise ValueError("one chunk per stream: %d, not %d" % (self.n_streams, len(chunks)))
-        cs = [np.ascontiguousarray(c) for c in chunks]
-        dt = self._m._sample_np()
-        if any(c.dtype != dt or c.ndim != 1 for c in cs):
-            if self._m.sample_format != "s16":
-                raise TypeError("chunks must be 1-D %s arrays for sample_format=%r" % (dt.name, self._m.sample_format))
-            raise TypeError("chunks must be 1-D int16 arrays (the core's sink is signed 16 bit, mfcc.py:29)")
+        cs = [_host_samples(c, self._m.sample_format, "chunks", ndim=1) for c in chunks]
         n = self.n_streams
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum([c.size for c in cs], dtype=np.uint64)
-        flat = np.concatenate(cs) if int(offsets[-1]) else np.zeros(0, dtype=dt)
+        offsets = _length_offsets([c.size for c in cs])
+        flat = np.concatenate(cs) if int(offsets[-1]) else np.zeros(0, dtype=self._m._sample_np())
         nf = int(self._plan(offsets)[-1])
         out = np.empty((nf, self._row()), dtype=np.int16 if self.fixed else np.float32)
         fo = np.zeros(n + 1, dtype=np.uint64)
-        _lib.check(self._lib.mfcc_hip_bank_push(self._b, flat.ctypes.data_as(C.c_void_p),
-                                                offsets.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
-                                                out.size, fo.ctypes.data_as(C.c_void_p)), "bank_push")
+        _lib.check(self._lib.mfcc_hip_bank_push(self._b, ptr(flat), ptr(offsets), ptr(out), out.size, ptr(fo)), "bank_push")
         assert int(fo[-1]) == nf
         return [out[int(fo[u]):int(fo[u + 1])] for u in range(n)]
 
@@ -1252,31 +1209,17 @@ class MfccStreamBank:
         import torch
         if not self._m._samples_dev_ok(flat) or flat.dim() != 1 or not flat.is_contiguous():
             raise TypeError("flat must be a contiguous 1-D %s tensor" % self._m._dev_what())
-        offsets = self._offsets(offsets)
-        if int(offsets[-1]) > flat.numel():
-            raise ValueError("offsets run past the end of flat")
+        offsets = _offsets(offsets, "offsets", "flat", n=self.n_streams, limit=flat.numel())
         m = self._m
         m._check_device(flat)
         nf = int(self._plan(offsets)[-1])
         odt = torch.int16 if self.fixed else torch.float32
         row = self._row()
-        if out is None:
-            out = torch.empty((nf, row), device=flat.device, dtype=odt)
-        elif tuple(out.shape) != (nf, row) or out.dtype != odt or not out.is_contiguous() or out.device != flat.device:
-            raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (odt, (nf, row), flat.device))
+        out = _out(flat, out, (nf, row), odt, lambda: torch.empty((nf, row), device=flat.device, dtype=odt))
         fo = np.zeros(self.n_streams + 1, dtype=np.uint64)
-        with m._on_torch_stream(flat.device):
-            _lib.check(self._lib.mfcc_hip_bank_push_dev(self._b, C.c_void_p(flat.data_ptr()),
-                                                        offsets.ctypes.data_as(C.c_void_p), C.c_void_p(out.data_ptr()),
-                                                        out.numel(), fo.ctypes.data_as(C.c_void_p)), "bank_push_dev")
+        m._call(flat.device, "bank_push_dev", self._b, ptr(flat), ptr(offsets), ptr(out), out.numel(), ptr(fo))
         assert int(fo[-1]) == nf
         return out, fo
-
-    def _streams(self, streams):
-        if streams is None:
-            return None, self.n_streams
-        s = np.ascontiguousarray(streams, dtype=np.uint64).reshape(-1)
-        return s, len(s)
 
     def flush(self, streams=None) -> list:
         """End of the listed streams (``None``: all): per stream, in the order listed, what :meth:`MfccStream.flush`
@@ -1284,26 +1227,25 @@ class MfccStreamBank:
         returns the rows the stream still holds (:attr:`held`) first, with the tail frame as the stream's last row and
         the delta indices clamped there: arrays of different lengths (``mfcc_hip_bank_flush_ragged``).  They are reset
         afterwards; the other streams are not touched."""
-        s, n = self._streams(streams)
+        s, n = _indices(streams, self.n_streams)
         out = np.empty((n * (self.lag + 1), self._row()), dtype=np.int16 if self.fixed else np.float32)
         fo = np.zeros(n + 1, dtype=np.uint64)
-        _lib.check(self._lib.mfcc_hip_bank_flush_ragged(self._b, None if s is None else s.ctypes.data_as(C.c_void_p), n,
-                                                        out.ctypes.data_as(C.c_void_p), out.size,
-                                                        fo.ctypes.data_as(C.c_void_p)), "bank_flush_ragged")
+        _lib.check(self._lib.mfcc_hip_bank_flush_ragged(self._b, ptr(s), n, ptr(out), out.size, ptr(fo)), "bank_flush_ragged")
         return [out[int(fo[i]):int(fo[i + 1])] for i in range(n)]
 
     def reset(self, streams=None):
         """``MFCC.reset`` for the listed streams (``None``: all): drop pending samples, history back to 0."""
-        s, n = self._streams(streams)
-        _lib.check(self._lib.mfcc_hip_bank_reset(self._b, None if s is None else s.ctypes.data_as(C.c_void_p), n),
-                   "bank_reset")
+        s, n = _indices(streams, self.n_streams)
+        _lib.check(self._lib.mfcc_hip_bank_reset(self._b, ptr(s), n), "bank_reset")
 
 
-class MfccPowerGate:
+class MfccPowerGate(_Owner):
     """The receiver's circular window and power gate (``cepstrum_refill_window`` + ``cepstrum_eval_power``,
     software/cepstrum.c:93-183) for ``n_lines`` live lines, state on the device.  Window ``j`` of a line is its rows
     ``[j * stride, j * stride + n_frames)`` counted from create / reset; any chunking gives the windows, bit for bit, of
     :meth:`MFCC.gate_rows` on the line's whole row sequence."""
+
+    _ptr, _destroy = "_g", "mfcc_hip_gate_destroy"
 
     def __init__(self, mfcc: MFCC, n_lines, n_cep, n_frames=93, stride=1, threshold=None):
         from . import wire
@@ -1315,24 +1257,10 @@ class MfccPowerGate:
         self.n_frames, self.stride, self.threshold = wire.gate_args(
             n_frames, stride, wire.POWER_THRESHOLD if threshold is None else threshold, n_cep=n_cep)
         self.n_cep = int(n_cep)
-        g = C.c_void_p()
+        g = _lib.Handle()
         _lib.check(self._lib.mfcc_hip_gate_create(mfcc._h, self.n_lines, self.n_cep, self.n_frames, self.stride,
                                                   self.threshold, C.byref(g)), "gate_create")
         self._g = g
-
-    def close(self):
-        # either order is safe: a handle closed first is kept alive by the library until its last session goes
-        if getattr(self, "_g", None):
-            self._lib.mfcc_hip_gate_destroy(self._g)
-        self._g = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def __len__(self):
         return self.n_lines
@@ -1341,26 +1269,17 @@ class MfccPowerGate:
     def seen(self) -> np.ndarray:
         """Frames every line has received since create / reset: uint64 ``(n_lines,)`` (a host mirror)."""
         p = np.zeros(self.n_lines, dtype=np.uint64)
-        _lib.check(self._lib.mfcc_hip_gate_seen(self._g, p.ctypes.data_as(C.c_void_p)), "gate_seen")
+        _lib.check(self._lib.mfcc_hip_gate_seen(self._g, ptr(p)), "gate_seen")
         return p
 
     def num_windows(self, frame_offsets) -> np.ndarray:
         """``win_offsets`` a push with these ``frame_offsets`` would give now (host only: ``mfcc_hip_gate_plan``)."""
-        fo = self._offsets(frame_offsets)
+        fo = _offsets(frame_offsets, "frame_offsets", "rows", n=self.n_lines)
         wo = np.zeros(self.n_lines + 1, dtype=np.uint64)
         seen = self.seen
-        _lib.check(self._lib.mfcc_hip_gate_plan(self.n_frames, self.stride, seen.ctypes.data_as(C.c_void_p),
-                                                fo.ctypes.data_as(C.c_void_p), self.n_lines,
-                                                wo.ctypes.data_as(C.c_void_p), None), "gate_plan")
+        _lib.check(self._lib.mfcc_hip_gate_plan(self.n_frames, self.stride, ptr(seen), ptr(fo), self.n_lines, ptr(wo), None),
+                   "gate_plan")
         return wo
-
-    def _offsets(self, frame_offsets):
-        fo = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
-        if fo.ndim != 1 or len(fo) != self.n_lines + 1:
-            raise ValueError("frame_offsets must be 1-D with n_lines + 1 = %d entries" % (self.n_lines + 1))
-        if int(np.diff(fo.astype(np.int64)).min()) < 0:
-            raise ValueError("frame_offsets must not decrease")
-        return fo
 
     def push(self, rows, frame_offsets):
         """Feed every line its new rows: ``rows`` int16 ``(sum rows, n_cep)`` with line ``u``'s in
@@ -1369,59 +1288,36 @@ class MfccPowerGate:
         NumPy array goes through one copy in and one copy out.  Returns ``(power, gate, gate_ref, win_offsets)`` for the
         windows this push completed, line ``u``'s in entries ``win_offsets[u]:win_offsets[u + 1]``."""
         import torch
-        from_numpy = not _is_torch(rows)
-        if from_numpy:
-            rows = np.ascontiguousarray(rows)
-            if rows.dtype != np.int16:
-                raise TypeError("rows must be int16")
-            rows = torch.from_numpy(rows).to(torch.device("cuda", self._m._device_index or 0)
-                                             if self._m._device_index is not None else "cuda")
+        rows, from_numpy = self._m._int16_rows_in(rows)
         if rows.dtype != torch.int16 or not rows.is_cuda or not rows.is_contiguous() or rows.dim() != 2 or \
                 int(rows.shape[1]) != self.n_cep:
             raise TypeError("rows must be a contiguous CUDA(HIP) int16 tensor of shape (rows, %d)" % self.n_cep)
-        fo = self._offsets(frame_offsets)
-        if int(fo[-1]) > int(rows.shape[0]):
-            raise ValueError("frame_offsets run past the end of rows")
+        fo = _offsets(frame_offsets, "frame_offsets", "rows", n=self.n_lines, limit=int(rows.shape[0]))
         self._m._check_device(rows)
         n = int(self.num_windows(fo)[-1])
         power = torch.empty(n, device=rows.device, dtype=torch.int64)
         gate = torch.empty(n, device=rows.device, dtype=torch.uint8)
         gate_ref = torch.empty(n, device=rows.device, dtype=torch.uint8)
         wo = np.zeros(self.n_lines + 1, dtype=np.uint64)
-        with self._m._on_torch_stream(rows.device):
-            _lib.check(self._lib.mfcc_hip_gate_push_dev(self._g, C.c_void_p(rows.data_ptr()),
-                                                        fo.ctypes.data_as(C.c_void_p), C.c_void_p(power.data_ptr()),
-                                                        C.c_void_p(gate.data_ptr()), C.c_void_p(gate_ref.data_ptr()), n,
-                                                        wo.ctypes.data_as(C.c_void_p)), "gate_push_dev")
+        self._m._call(rows.device, "gate_push_dev", self._g, ptr(rows), ptr(fo), ptr(power), ptr(gate), ptr(gate_ref), n,
+                      ptr(wo))
         assert int(wo[-1]) == n
-        if from_numpy:
-            return power.cpu().numpy(), gate.cpu().numpy(), gate_ref.cpu().numpy(), wo
-        return power, gate, gate_ref, wo
-
-    def _lines(self, lines):
-        if lines is None:
-            return None, self.n_lines
-        s = np.ascontiguousarray(lines, dtype=np.uint64).reshape(-1)
-        return s, len(s)
+        return _numpy_if(from_numpy, power, gate, gate_ref) + (wo,)
 
     def reset(self, lines=None):
         """The listed lines (``None``: all) start again at frame 0."""
-        s, n = self._lines(lines)
-        _lib.check(self._lib.mfcc_hip_gate_reset(self._g, None if s is None else s.ctypes.data_as(C.c_void_p), n),
-                   "gate_reset")
+        s, n = _indices(lines, self.n_lines)
+        _lib.check(self._lib.mfcc_hip_gate_reset(self._g, ptr(s), n), "gate_reset")
 
     def last_windows(self, lines):
         """The rows of the last completed window of every listed line: a CUDA int16 tensor
         ``(len(lines), n_frames, n_cep)`` on the current torch stream.  A line that has completed no window since
         create / reset raises ``INVALID_PARAM``."""
         import torch
-        s, n = self._lines(np.arange(self.n_lines) if lines is None else lines)
-        m = self._m
-        dev = torch.device("cuda", torch.cuda.current_device() if m._device_index is None else m._device_index)
+        s, n = _indices(np.arange(self.n_lines) if lines is None else lines, self.n_lines)
+        dev = self._m._device()
         out = torch.empty((n, self.n_frames, self.n_cep), device=dev, dtype=torch.int16)
-        with m._on_torch_stream(dev):
-            _lib.check(self._lib.mfcc_hip_gate_window_dev(self._g, s.ctypes.data_as(C.c_void_p), n,
-                                                          C.c_void_p(out.data_ptr())), "gate_window_dev")
+        self._m._call(dev, "gate_window_dev", self._g, ptr(s), n, ptr(out))
         return out
 
 
@@ -1436,12 +1332,9 @@ def decode(x, sample_format, mfcc=None):
     name, code, dtype = _sample_args(sample_format)
     lib = _lib.load()
     if not _is_torch(x):
-        x = np.ascontiguousarray(x)
-        if x.dtype != dtype:
-            raise TypeError("x must be %s for sample_format=%r, not %s" % (dtype.name, name, x.dtype))
+        x = _host_samples(x, name, "x")
         out = np.empty(x.shape, dtype=np.int16)
-        _lib.check(lib.mfcc_hip_decode_host(code, x.ctypes.data_as(C.c_void_p), x.size, out.ctypes.data_as(C.c_void_p)),
-                   "decode_host")
+        _lib.check(lib.mfcc_hip_decode_host(code, ptr(x), x.size, ptr(out)), "decode_host")
         return out
     import torch
     if not x.is_cuda or x.dtype != getattr(torch, dtype.name):
@@ -1453,9 +1346,7 @@ def decode(x, sample_format, mfcc=None):
             mfcc = _decode_handles[x.device.index] = MFCC(nfft=512, nfilters=32, nceptrums=13, device=x.device.index)
     mfcc._check_device(x)
     out = torch.empty(x.shape, device=x.device, dtype=torch.int16)
-    with mfcc._on_torch_stream(x.device):
-        _lib.check(lib.mfcc_hip_decode_dev(mfcc._h, code, C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(out.data_ptr())),
-                   "decode_dev")
+    mfcc._call(x.device, "decode_dev", mfcc._h, code, ptr(x), x.numel(), ptr(out))
     return out
 
 
