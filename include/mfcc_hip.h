@@ -555,6 +555,102 @@ int  mfcc_hip_set_sample_format(mfcc_hip_handle *h, int format);
 /* the handle's format (MFCC_HIP_SAMPLE_S16 for NULL) */
 int  mfcc_hip_sample_format(const mfcc_hip_handle *h);
 
+/* ---- sample rates ------------------------------------------------------------------------
+ * An integer polyphase resampler: int16 in, int16 out, the same bits from the host entry and from the kernel.
+ * in_rate, out_rate: positive integers.  g = gcd(in_rate, out_rate), L = out_rate / g, M = in_rate / g.
+ * Constants: Z = 16 zero crossings, Kaiser beta = 7.5, roll-off 0.90.  s = min(1, L / M), fc = 0.90 s,
+ * H = ceil(Z / s) (in integers: 16 for L >= M, else (16 M + L - 1) div L), K = 2 H taps per phase, L phases.
+ * Design, in double:  g(d) = fc sinc(fc d) I0(beta sqrt(1 - (d / H)^2)) / I0(beta) for |d| <= H, else 0, with
+ *   sinc(x) = sin(pi x) / (pi x) and I0 the modified Bessel function of order 0.
+ * Phase p, tap k: d = k - H + 1 - p / L.
+ * Table T[p][k], int16, Q14: rint(16384 g / sum_k g) per phase (ties to even); the residual 16384 - sum_k T[p][k] is
+ *   then added to the phase's largest tap (the first of them), so every phase sums to exactly 16384.
+ * Output m >= 0:  q = (m M) div L,  p = (m M) mod L  (the product 64-bit),
+ *   acc = sum_{k < K} T[p][k] x[q - H + 1 + k], with x[i] = 0 outside [0, n), a 32-bit integer,
+ *   y[m] = sat16((acc + 8192) >> 14), arithmetic shift.
+ *   The table is only accepted if sum_k |T[p][k]| <= 65535 for every phase, so acc cannot wrap on any int16 input.
+ * Count: n_out = (n L + M - 1) div M.
+ * MFCC_HIP_ERROR_UNSUPPORTED if L > 1024, M > 1024 or the table (2 L K bytes) exceeds 64 KiB;
+ * MFCC_HIP_ERROR_INVALID_PARAM for a rate <= 0, a NULL pointer that is needed, or n >= 2^40.
+ * in_rate == out_rate is L = M = 1, K = 32: the roll-off filter at the rate's own Nyquist, NOT a copy. */
+/* L, M and K of a ratio (any may be NULL).  Host only. */
+int  mfcc_hip_resample_geometry(int in_rate, int out_rate, int *L, int *M, int *K);
+/* *n_out = outputs of n input samples.  Host only. */
+int  mfcc_hip_resample_count(int in_rate, int out_rate, size_t n, size_t *n_out);
+/* the table, L rows of K taps: *n (may be NULL) = L K also on MFCC_HIP_ERROR_BUFFER_SMALL (cap < L K, nothing written;
+ * buf may then be NULL).  Host only. */
+int  mfcc_hip_resample_taps(int in_rate, int out_rate, int16_t *buf, size_t cap, size_t *n);
+/* Host only, no GPU, no handle: the rule on the n samples at `in` -> out[n_out].  cap < n_out:
+ * MFCC_HIP_ERROR_BUFFER_SMALL, nothing written.  For callers and for the CPU tests. */
+int  mfcc_hip_resample_host(int in_rate, int out_rate, const int16_t *in, size_t n, int16_t *out, size_t cap);
+/* The kernel's direct entry: n int16 at d_in -> n_out int16 at d_out, both 2-byte aligned at any int16 offset, the byte
+ * ranges [d_in, d_in + 2 n) and [d_out, d_out + 2 n_out) not overlapping (a misaligned or NULL pointer or an overlap:
+ * MFCC_HIP_ERROR_INVALID_PARAM); cap < n_out: MFCC_HIP_ERROR_BUFFER_SMALL, nothing enqueued.  Asynchronous on the
+ * handle's stream; n = 0 is a no-op that looks at no pointer; any handle (its own rate and format are not read).  The
+ * handle keeps the table of the last ratio on its device: a call with another ratio builds and copies a new one and
+ * waits for the stream once. */
+int  mfcc_hip_resample_dev(mfcc_hip_handle *h, int in_rate, int out_rate, const void *d_in, size_t n, void *d_out, size_t cap);
+/* The handle's input rate, applied to every call enqueued after it: every sample pointer of the one-shot entry points
+ * holds samples at in_rate, and the call returns, bit for bit, what the same handle without an input rate returns on
+ * mfcc_hip_resample_host(in_rate, params.sample_rate) of the (decoded) input.  The order is decode -> resample ->
+ * route; the resampled samples go to a scratch area of the handle that grows on demand and is never shrunk (2 bytes per
+ * output sample, a dense strided call rounds every channel up to 8 samples; MFCC_HIP_ERROR_NO_MEM if it cannot be had).
+ * in_rate = 0 or params.sample_rate: off, the state after mfcc_hip_create -- no pass is enqueued, every entry point is
+ * the code it was.  Sample counts, strides and `offsets` keep counting the CALLER's samples; frame counts are those of
+ * the resampled lengths, count_frames(mfcc_hip_resample_count(n)).
+ *   - dense device calls and mfcc_hip_time_dev (which times the pass too): every channel on its own, zeros outside it;
+ *   - ragged device calls: every utterance on its own, zeros outside it, by one launch; the new offsets on the host;
+ *   - the fixed-point entry points likewise;
+ *   - the host-buffer entry points take the unchunked route: one copy in, the device route, one copy back
+ *     (MFCC_HIP_ERROR_NO_MEM where that does not fit);
+ *   - mfcc_hip_convert_wav(s) expect a WAV of in_rate.
+ * MFCC_HIP_ERROR_UNSUPPORTED with a rate set: dense calls with halo = 1 (a shard's edge would need its neighbour's
+ * samples), mfcc_hip_stream_create and every mfcc_hip_bank_create* (a line's conversion keeps state between pushes).
+ * A ratio mfcc_hip_resample_geometry refuses is refused alike; in_rate < 0 or a NULL handle:
+ * MFCC_HIP_ERROR_INVALID_PARAM; MFCC_HIP_ERROR_BUSY while sessions, banks or gates live.  The call copies the ratio's
+ * table to the device (and waits for the handle's stream once if it held another ratio's). */
+int  mfcc_hip_set_input_rate(mfcc_hip_handle *h, int in_rate);
+/* the handle's input rate, 0 where none is set (and for NULL) */
+int  mfcc_hip_input_rate(const mfcc_hip_handle *h);
+
+/* Live lines: the streaming form of the same rule, an object of its own that is composed with a bank on the device
+ * (as mfcc_hip_gate is, behind one).  After c input samples a line has emitted E(c) = count(max(c - H, 0)) outputs: the
+ * latency is H input samples.  The line keeps c on the host and its last K - 1 samples on the device.  A flush emits
+ * the outputs E(c) .. count(c) - 1 on zeros beyond the end and puts the line back to c = 0.  Pushes plus flush,
+ * concatenated, are the one-shot result of the concatenated chunks, bit for bit, whatever the chunking.
+ * The chunks are in sample_format and are decoded in front, like a bank's; the int16 output and out_offsets go straight
+ * into mfcc_hip_bank_push_dev of an S16 handle's bank at out_rate (a line's flush output is pushed to the bank before
+ * the bank's own flush).  The object lives on the handle's device and stream and uses its scratch areas; while it lives
+ * the handle's setters answer MFCC_HIP_ERROR_BUSY and mfcc_hip_destroy is deferred, as with a session. */
+typedef struct mfcc_hip_resampler mfcc_hip_resampler;
+/* n_lines >= 1 lines from c = 0.  A ratio mfcc_hip_resample_geometry refuses is refused alike; an unknown format, no
+ * line or a NULL pointer: MFCC_HIP_ERROR_INVALID_PARAM. */
+int  mfcc_hip_resampler_create(mfcc_hip_handle *h, size_t n_lines, int sample_format, int in_rate, int out_rate,
+                               mfcc_hip_resampler **out);
+void mfcc_hip_resampler_destroy(mfcc_hip_resampler *r);
+/* seen[n_lines]: every line's c */
+int  mfcc_hip_resampler_seen(const mfcc_hip_resampler *r, size_t *seen);
+/* the listed lines (distinct; NULL: every line) back to c = 0 without output.  Host only, takes effect in stream order. */
+int  mfcc_hip_resampler_reset(mfcc_hip_resampler *r, const size_t *lines, size_t n);
+/* From lengths alone, no device: out_offsets[n_lines + 1] of lines that have seen seen[u] samples,
+ *   flush = 0: for a push of the chunks offsets[u] .. offsets[u + 1]:   E(seen + len) - E(seen) outputs each;
+ *   flush != 0: for a flush behind those chunks (offsets NULL: no chunks): count(seen + len) - E(seen + len) each. */
+int  mfcc_hip_resampler_plan(int in_rate, int out_rate, const size_t *seen, const size_t *offsets, size_t n_lines, int flush,
+                             size_t *out_offsets);
+/* One chunk per line, line u = samples offsets[u] .. offsets[u + 1] of d_in (in sample_format, aligned to its sample
+ * size; a chunk may be empty), one launch (two with a decode).  Line u's outputs land at d_out[out_offsets[u] ..
+ * out_offsets[u + 1]) (int16, 2-byte aligned), out_offsets[n_lines + 1] is filled on the host before the call returns:
+ * asynchronous on the handle's stream, no synchronization.  cap (in int16) below out_offsets[n_lines]:
+ * MFCC_HIP_ERROR_BUFFER_SMALL with out_offsets filled; that and MFCC_HIP_ERROR_INVALID_PARAM (decreasing offsets, a NULL
+ * or misaligned pointer that is needed) consume nothing and enqueue nothing.  d_in and d_out must not overlap. */
+int  mfcc_hip_resampler_push_dev(mfcc_hip_resampler *r, const void *d_in, const size_t *offsets, void *d_out, size_t cap,
+                                 size_t *out_offsets);
+/* The end of the listed lines (distinct; NULL: every line, then n is ignored): line lines[i]'s last outputs at
+ * d_out[out_offsets[i] .. out_offsets[i + 1]), out_offsets[n + 1]; the lines are at c = 0 afterwards.  Asynchronous;
+ * refusals as above. */
+int  mfcc_hip_resampler_flush_dev(mfcc_hip_resampler *r, const size_t *lines, size_t n, void *d_out, size_t cap,
+                                  size_t *out_offsets);
+
 /* name of the kernel symbol process_*_dev launches for this handle (to match rocprofv3 rows).  A log-mel handle runs
  * the log-mel instantiation of the kernel named (the default form: MFCC_HIP_FUSED512 / MFCC_HIP_FUSED1024 do not
  * apply to it) */

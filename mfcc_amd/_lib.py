@@ -243,6 +243,22 @@ SYMBOLS = {
     "mfcc_hip_decode_dev": (C.c_int, [_H, C.c_int, C.c_void_p, _SZ, C.c_void_p]),
     "mfcc_hip_set_sample_format": (C.c_int, [_H, C.c_int]),
     "mfcc_hip_sample_format": (C.c_int, [_H]),
+    # sample rates: the host-only helpers and the kernel's direct entry
+    "mfcc_hip_resample_geometry": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mfcc_hip_resample_count": (C.c_int, [C.c_int, C.c_int, _SZ, C.POINTER(_SZ)]),
+    "mfcc_hip_resample_taps": (C.c_int, [C.c_int, C.c_int, C.c_void_p, _SZ, C.POINTER(_SZ)]),
+    "mfcc_hip_resample_host": (C.c_int, [C.c_int, C.c_int, C.c_void_p, _SZ, C.c_void_p, _SZ]),
+    "mfcc_hip_resample_dev": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, _SZ, C.c_void_p, _SZ]),
+    "mfcc_hip_set_input_rate": (C.c_int, [_H, C.c_int]),
+    "mfcc_hip_input_rate": (C.c_int, [_H]),
+    # live lines: the streaming resampler
+    "mfcc_hip_resampler_create": (C.c_int, [_H, _SZ, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
+    "mfcc_hip_resampler_destroy": (None, [_H]),
+    "mfcc_hip_resampler_seen": (C.c_int, [_H, C.c_void_p]),
+    "mfcc_hip_resampler_reset": (C.c_int, [_H, C.c_void_p, _SZ]),
+    "mfcc_hip_resampler_plan": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, _SZ, C.c_int, C.c_void_p]),
+    "mfcc_hip_resampler_push_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, _SZ, C.c_void_p]),
+    "mfcc_hip_resampler_flush_dev": (C.c_int, [_H, C.c_void_p, _SZ, C.c_void_p, _SZ, C.c_void_p]),
 }
 
 _lib = None

@@ -463,11 +463,20 @@ class MFCC(_Owner):
     ``process_fixed``, ``process_batch``, ``process_packed``, :meth:`stream`, :meth:`stream_bank` -- then REQUIRES the
     matching dtype (``TypeError`` otherwise) and returns, bit for bit, what an ``"s16"`` handle returns on the decoded
     samples.  ``convert*`` keep reading 16-bit WAV files.
+
+    ``input_rate`` (an integer number of samples per second, e.g. 8000 on a 16 kHz handle) is the rate the sample
+    arrays of the one-shot methods are at: they are converted to ``samplerate`` on the device, behind the decode and in
+    front of the kernels, by the integer polyphase rule of include/mfcc_hip.h (:func:`resample` applies it alone), and
+    every method returns, bit for bit, what the handle without it returns on the resampled samples -- every channel and
+    every utterance on its own.  ``None``, 0 or ``samplerate`` itself: off.  ``process(..., halo=1)``, :meth:`stream` and
+    :meth:`stream_bank` raise ``UNSUPPORTED`` on such a handle (live lines go through :meth:`resampler`); ``convert*``
+    expect WAV files of that rate.
     """
 
     deltas, delta_window = 0, 2                 # the state after mfcc_hip_create
     vad = None
     sample_format = "s16"
+    input_rate = None
     _ptr, _destroy = "_h", "mfcc_hip_destroy"
 
     def _sample_np(self):
@@ -487,7 +496,7 @@ class MFCC(_Owner):
                  normalize=None, deltas=0, delta_window=2, normalize_window=None, normalize_min_window=_MIN_WINDOW,
                  normalize_center=True, vad=None, vad_column=0, vad_energy_threshold=5.0, vad_energy_mean_scale=0.5,
                  vad_frames_context=0, vad_proportion_threshold=0.6, win_length=None, mel="notebook", fmin=0.0,
-                 fmax=None, pcen=None, sample_format="s16"):
+                 fmax=None, pcen=None, sample_format="s16", input_rate=None):
         if width != 16:
             raise ValueError("only width=16 (int16 PCM) is supported, like every reference target")
         fmt_name, fmt_code, _ = _sample_args(sample_format)
@@ -525,6 +534,8 @@ class MFCC(_Owner):
         self._h = h
         if fmt_code != _lib.SAMPLE_S16:
             self.set_sample_format(fmt_name)
+        if input_rate is not None:
+            self.set_input_rate(input_rate)
         self.pcen = None
         if pcen is not None and pcen is not False:
             self.set_pcen(pcen)
@@ -550,6 +561,24 @@ class MFCC(_Owner):
         name, code, _ = _sample_args(sample_format)
         _lib.check(self._lib.mfcc_hip_set_sample_format(self._h, code), "set_sample_format")
         self.sample_format = name
+
+    def _own_rate(self):
+        """``samplerate`` as the integer the resampler needs, or ``INVALID_PARAM``."""
+        if float(self.samplerate) != int(self.samplerate):
+            raise MfccHipError(_lib.ERROR_INVALID_PARAM, "a sample-rate conversion needs an integer samplerate, not %r"
+                               % (self.samplerate,))
+        return int(self.samplerate)
+
+    def set_input_rate(self, input_rate):
+        """The rate the sample arrays of every call after this one are at (``None``, 0 or ``samplerate``: the handle's own,
+        no conversion); ``BUSY`` while sessions, banks or gates of this handle live, ``UNSUPPORTED`` for a ratio
+        :func:`resample` refuses."""
+        rate = 0 if input_rate is None else input_rate
+        if rate != 0:
+            rate = _rate(rate, "input_rate")
+            self._own_rate()
+        _lib.check(self._lib.mfcc_hip_set_input_rate(self._h, rate), "set_input_rate")
+        self.input_rate = int(self._lib.mfcc_hip_input_rate(self._h)) or None
 
     def set_vad(self, mode, column=0, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0,
                 proportion_threshold=0.6):
@@ -701,6 +730,9 @@ class MFCC(_Owner):
         return self.nceptrums if fixed else self.num_features
 
     def num_frames(self, n_samples) -> int:
+        """Frames of ``n_samples`` samples of one channel or utterance (at ``input_rate`` where one is set)."""
+        if self.input_rate:
+            n_samples = resample_count(n_samples, self.input_rate, int(self.samplerate))
         out = C.c_size_t(0)
         _lib.check(self._lib.mfcc_hip_num_frames_framed(C.byref(self._params), self.win_length, int(n_samples),
                                                         C.byref(out)))
@@ -1029,6 +1061,13 @@ class MFCC(_Owner):
         :meth:`stream_bank` returns."""
         return MfccPowerGate(self, n_lines, self.nceptrums if n_cep is None else n_cep, n_frames, stride, threshold)
 
+    def resampler(self, n_lines, in_rate, sample_format="s16") -> "MfccResampler":
+        """A sample-rate converter for ``n_lines`` live lines from ``in_rate`` to this handle's ``samplerate``: chunks in
+        ``sample_format`` in, int16 at ``samplerate`` out, ready for ``stream_bank(n_lines).push_packed`` of an ``"s16"``
+        handle.  This handle only lends its device, stream and scratch areas: its own ``sample_format`` and
+        ``input_rate`` are not read."""
+        return MfccResampler(self, n_lines, in_rate, sample_format)
+
     # -- file level: mfcc_convert(sess, path_in, path_out), software/main.c:100-177 -----
     def convert_many(self, paths_in, paths_out, fixed=True):
         """``mfcc_convert`` for many files in one ragged launch; returns the frame count of each file."""
@@ -1321,6 +1360,102 @@ class MfccPowerGate(_Owner):
         return out
 
 
+class MfccResampler(_Owner):
+    """The streaming form of :func:`resample` for ``n_lines`` live lines, state on the device.  A line emits its outputs
+    ``H`` input samples late (``H = K / 2``); :meth:`flush` emits the rest on zeros beyond the end and restarts the
+    line.  The pushes plus the flush of a line, concatenated, are :func:`resample` of its concatenated chunks, bit for
+    bit, whatever the chunking."""
+
+    _ptr, _destroy = "_r", "mfcc_hip_resampler_destroy"
+
+    def __init__(self, mfcc: MFCC, n_lines, in_rate, sample_format="s16"):
+        self._m = mfcc
+        self._lib = mfcc._lib
+        self.n_lines = int(n_lines)
+        if self.n_lines < 1:
+            raise ValueError("a resampler needs at least one line")
+        self.sample_format, code, self._dtype = _sample_args(sample_format)
+        self.in_rate, self.out_rate = _rate(in_rate, "in_rate"), mfcc._own_rate()
+        r = _lib.Handle()
+        _lib.check(self._lib.mfcc_hip_resampler_create(mfcc._h, self.n_lines, code, self.in_rate, self.out_rate, C.byref(r)),
+                   "resampler_create")
+        self._r = r
+
+    def __len__(self):
+        return self.n_lines
+
+    @property
+    def seen(self) -> np.ndarray:
+        """Samples every line has received since create / reset / flush: uint64 ``(n_lines,)`` (a host mirror)."""
+        p = np.zeros(self.n_lines, dtype=np.uint64)
+        _lib.check(self._lib.mfcc_hip_resampler_seen(self._r, ptr(p)), "resampler_seen")
+        return p
+
+    def plan(self, offsets=None, flush=False) -> np.ndarray:
+        """``out_offsets`` a :meth:`push_packed` with these ``offsets`` would give now, or (``flush=True``) a flush of
+        every line behind it (host only: ``mfcc_hip_resampler_plan``)."""
+        off = None if offsets is None else _offsets(offsets, "offsets", "flat", n=self.n_lines)
+        oo = np.zeros(self.n_lines + 1, dtype=np.uint64)
+        seen = self.seen
+        _lib.check(self._lib.mfcc_hip_resampler_plan(self.in_rate, self.out_rate, ptr(seen), ptr(off), self.n_lines, int(flush),
+                                                     ptr(oo)), "resampler_plan")
+        return oo
+
+    def push_packed(self, flat, offsets):
+        """One chunk per line, line ``u`` = ``flat[offsets[u]:offsets[u + 1]]`` (a contiguous 1-D CUDA tensor of the
+        format's dtype; a chunk may be empty).  One launch, asynchronous on the current torch stream.  Returns ``(out,
+        out_offsets)``: a CUDA int16 tensor and the range of every line in it."""
+        import torch
+        if not flat.is_cuda or flat.dtype != getattr(torch, self._dtype.name) or flat.dim() != 1 or not flat.is_contiguous():
+            raise TypeError("flat must be a contiguous 1-D CUDA(HIP) %s tensor" % self._dtype.name)
+        off = _offsets(offsets, "offsets", "flat", n=self.n_lines, limit=flat.numel())
+        self._m._check_device(flat)
+        n = int(self.plan(off)[-1])
+        out = torch.empty(n, device=flat.device, dtype=torch.int16)
+        oo = np.zeros(self.n_lines + 1, dtype=np.uint64)
+        self._m._call(flat.device, "resampler_push_dev", self._r, ptr(flat), ptr(off), ptr(out), n, ptr(oo))
+        assert int(oo[-1]) == n
+        return out, oo
+
+    def push(self, chunks) -> list:
+        """``chunks``: one NumPy array per line (``None`` or empty: nothing for that line).  One copy in, one launch, one
+        copy out; returns every line's new int16 samples."""
+        import torch
+        if len(chunks) != self.n_lines:
+            raise ValueError("one chunk per line (%d), not %d" % (self.n_lines, len(chunks)))
+        arrs = [np.zeros(0, self._dtype) if c is None else _host_samples(c, self.sample_format, "chunk", ndim=1) for c in chunks]
+        off = _length_offsets([a.size for a in arrs])
+        flat = torch.from_numpy(np.concatenate(arrs) if arrs else np.zeros(0, self._dtype)).to(self._m._device())
+        out, oo = self.push_packed(flat, off)
+        out = out.cpu().numpy()
+        return [out[int(oo[u]):int(oo[u + 1])] for u in range(self.n_lines)]
+
+    def flush_packed(self, lines=None):
+        """The end of the listed lines (``None``: all): ``(out, out_offsets)`` like :meth:`push_packed`, entry ``i`` for
+        ``lines[i]``; the lines start again at sample 0.  Asynchronous on the current torch stream."""
+        import torch
+        s, n = _indices(lines, self.n_lines)
+        seen = self.seen if s is None else self.seen[s.astype(np.int64)]
+        oo = np.zeros(n + 1, dtype=np.uint64)
+        _lib.check(self._lib.mfcc_hip_resampler_plan(self.in_rate, self.out_rate, ptr(seen), None, n, 1, ptr(oo)),
+                   "resampler_plan")
+        dev = self._m._device()
+        out = torch.empty(int(oo[-1]), device=dev, dtype=torch.int16)
+        self._m._call(dev, "resampler_flush_dev", self._r, ptr(s), n, ptr(out), out.numel(), ptr(oo))
+        return out, oo
+
+    def flush(self, lines=None) -> list:
+        """:meth:`flush_packed` to the host: the last int16 samples of every listed line."""
+        out, oo = self.flush_packed(lines)
+        out = out.cpu().numpy()
+        return [out[int(oo[i]):int(oo[i + 1])] for i in range(len(oo) - 1)]
+
+    def reset(self, lines=None):
+        """The listed lines (``None``: all) start again at sample 0, without output."""
+        s, n = _indices(lines, self.n_lines)
+        _lib.check(self._lib.mfcc_hip_resampler_reset(self._r, ptr(s), n), "resampler_reset")
+
+
 _decode_handles = {}          # device index -> the handle decode() launches on (mfcc_hip_decode_dev takes any)
 
 
@@ -1347,6 +1482,59 @@ def decode(x, sample_format, mfcc=None):
     mfcc._check_device(x)
     out = torch.empty(x.shape, device=x.device, dtype=torch.int16)
     mfcc._call(x.device, "decode_dev", mfcc._h, code, ptr(x), x.numel(), ptr(out))
+    return out
+
+
+def _rate(v, what):
+    """``v`` as an int that fits the C ABI's ``int``, or TypeError / ValueError."""
+    if not _is_int(v):
+        raise TypeError("%s must be an integer number of samples per second, not %r" % (what, v))
+    if not 0 < int(v) < 2 ** 31:
+        raise ValueError("%s must be positive and below 2**31, not %r" % (what, v))
+    return int(v)
+
+
+def resample_count(n, in_rate, out_rate) -> int:
+    """Samples :func:`resample` returns for ``n`` input samples: ``ceil(n * L / M)`` (include/mfcc_hip.h)."""
+    out = C.c_size_t(0)
+    _lib.check(_lib.load().mfcc_hip_resample_count(_rate(in_rate, "in_rate"), _rate(out_rate, "out_rate"), int(n), C.byref(out)),
+               "resample_count")
+    return int(out.value)
+
+
+def resample_taps(in_rate, out_rate):
+    """The Q14 tap table of a ratio, ``(L, K)`` int16: row ``p`` is phase ``p`` (include/mfcc_hip.h has the design)."""
+    lib, i, o = _lib.load(), _rate(in_rate, "in_rate"), _rate(out_rate, "out_rate")
+    L, K = C.c_int(0), C.c_int(0)
+    _lib.check(lib.mfcc_hip_resample_geometry(i, o, C.byref(L), None, C.byref(K)), "resample_geometry")
+    t = np.empty((L.value, K.value), dtype=np.int16)
+    _lib.check(lib.mfcc_hip_resample_taps(i, o, ptr(t), t.size, None), "resample_taps")
+    return t
+
+
+def resample(x, in_rate, out_rate, mfcc=None):
+    """``x`` (1-D int16 at ``in_rate`` samples per second) at ``out_rate``: the integer polyphase rule of
+    include/mfcc_hip.h, the same bits on both routes.  A NumPy array goes through ``mfcc_hip_resample_host`` (no GPU
+    needed); a CUDA tensor through ``mfcc_hip_resample_dev``, asynchronous on the current torch stream, on ``mfcc``
+    (any handle of that device) or on a handle this function keeps per device."""
+    i, o = _rate(in_rate, "in_rate"), _rate(out_rate, "out_rate")
+    lib = _lib.load()
+    if not _is_torch(x):
+        x = _host_samples(x, "s16", "x", ndim=1)
+        out = np.empty(resample_count(x.size, i, o), dtype=np.int16)
+        _lib.check(lib.mfcc_hip_resample_host(i, o, ptr(x), x.size, ptr(out), out.size), "resample_host")
+        return out
+    import torch
+    if not x.is_cuda or x.dtype != torch.int16 or x.dim() != 1:
+        raise TypeError("x must be a 1-D CUDA(HIP) int16 tensor")
+    x = x.contiguous()
+    if mfcc is None:
+        mfcc = _decode_handles.get(x.device.index)
+        if mfcc is None:
+            mfcc = _decode_handles[x.device.index] = MFCC(nfft=512, nfilters=32, nceptrums=13, device=x.device.index)
+    mfcc._check_device(x)
+    out = torch.empty(resample_count(x.numel(), i, o), device=x.device, dtype=torch.int16)
+    mfcc._call(x.device, "resample_dev", mfcc._h, i, o, ptr(x), x.numel(), ptr(out), out.numel())
     return out
 
 

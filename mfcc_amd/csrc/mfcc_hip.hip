@@ -38,6 +38,7 @@
 #include "kernel_stream_bank_online.hpp"
 #include "kernel_gate.hpp"
 #include "kernel_decode.hpp"
+#include "kernel_resample.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -289,6 +290,13 @@ struct mfcc_hip_handle {
     // (d_dec) and the raw bytes of a session's push on their way to the decode (d_raw)
     int sample_fmt = MFCC_HIP_SAMPLE_S16;
     DevBuf d_dec, d_raw;
+    // sample rates (mfcc_hip_resample_dev, mfcc_hip_set_input_rate): the tap table of the last ratio on the device
+    // (d_rs_tab; rs_in / rs_out name the ratio, 0: none yet), the rate every sample pointer is read at (0: the handle's
+    // own, no pass) and the resampled int16 samples of a call (d_rs)
+    int rs_in = 0, rs_out = 0;
+    mfcc_rs::Geometry rs_geom;
+    DevBuf d_rs_tab, d_rs;
+    int input_rate = 0;
 };
 
 namespace {
@@ -420,6 +428,66 @@ int decode_to_scratch(mfcc_hip_handle *h, const void *d_in, size_t n, size_t row
     *out_stride = stride;
     return decode_rows(h, d_in, n, rows, rows <= 1 ? n : in_stride, static_cast<int16_t *>(h->d_dec.p), stride);
 }
+
+// ---- sample rates (include/mfcc_hip.h: "sample rates"; resample_plan.hpp, kernel_resample.hpp)
+int rs_geometry(int in_rate, int out_rate, mfcc_rs::Geometry &g) {
+    const int bad = mfcc_rs::geometry(in_rate, out_rate, g);
+    return bad == 1 ? MFCC_HIP_ERROR_INVALID_PARAM : bad ? MFCC_HIP_ERROR_UNSUPPORTED : MFCC_HIP_SUCCESS;
+}
+
+int rs_table(int in_rate, int out_rate, mfcc_rs::Geometry &g, std::vector<int16_t> &t) {
+    const int rc = rs_geometry(in_rate, out_rate, g);
+    if (rc) return rc;
+    return mfcc_rs::build_taps(g, t) ? MFCC_HIP_SUCCESS : MFCC_HIP_ERROR_UNSUPPORTED;
+}
+
+// the ratio's table on the handle's device.  Another ratio than the last one's: the stream drains first, since
+// kernels in flight may still read the old table
+int rs_bind(mfcc_hip_handle *h, int in_rate, int out_rate, mfcc_rs::Taps &a) {
+    if (h->rs_in != in_rate || h->rs_out != out_rate) {
+        mfcc_rs::Geometry g;
+        std::vector<int16_t> t;
+        int rc = rs_table(in_rate, out_rate, g, t);
+        if (rc) return rc;
+        if (h->rs_in) HIP_TRY(h, hipStreamSynchronize(h->stream));
+        h->rs_in = h->rs_out = 0;
+        if ((rc = ensure(h, h->d_rs_tab, t.size() * sizeof(int16_t)))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->d_rs_tab.p, t.data(), t.size() * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));          // t goes out of scope
+        h->rs_geom = g;
+        h->rs_in = in_rate;
+        h->rs_out = out_rate;
+    }
+    a = mfcc_rs::Taps{static_cast<const int16_t *>(h->d_rs_tab.p), h->rs_geom.L, h->rs_geom.M, h->rs_geom.H, h->rs_geom.K};
+    return MFCC_HIP_SUCCESS;
+}
+
+// a handle with an input rate (mfcc_hip_set_input_rate): every sample pointer is resampled to the handle's own rate
+// behind the decode and in front of the route
+inline bool rated(const mfcc_hip_handle *h) { return h && h->input_rate != 0; }
+
+// n of a call's samples, at the handle's own rate (the WAV readers size their buffers by it)
+inline size_t own_rate_len(const mfcc_hip_handle *h, size_t n) {
+    mfcc_rs::Geometry g;
+    if (!rated(h) || mfcc_rs::geometry(h->input_rate, h->r.sample_rate, g)) return n;
+    return size_t(mfcc_rs::count(n, g.L, g.M));
+}
+
+// the handle as a plain int16 handle at its own rate for the scope: the resampled samples take the routes of int16 input
+struct PlainInputGuard {
+    mfcc_hip_handle *h;
+    int fmt, rate;
+    explicit PlainInputGuard(mfcc_hip_handle *hh) : h(hh), fmt(hh->sample_fmt), rate(hh->input_rate) {
+        h->sample_fmt = MFCC_HIP_SAMPLE_S16;
+        h->input_rate = 0;
+    }
+    ~PlainInputGuard() {
+        h->sample_fmt = fmt;
+        h->input_rate = rate;
+    }
+    PlainInputGuard(const PlainInputGuard &) = delete;
+    PlainInputGuard &operator=(const PlainInputGuard &) = delete;
+};
 
 struct Arena {
     std::vector<char> host;
@@ -1112,8 +1180,12 @@ int launch_float_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t str
 
 // The dense device entries on a handle with a sample format: the samples the call reads -- n + halo of every channel --
 // decoded into the scratch area, then the route of int16 input on it.  MFCC_HIP_SAMPLE_S16: that route and nothing else
+int rated_dense_dev(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo,
+                    void *d_out, size_t *n_frames);
+
 int dense_dev(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo, void *d_out,
               size_t *n_frames) {
+    if (rated(h)) return rated_dense_dev(h, fixed, d_pcm, n, stride, nch, halo, d_out, n_frames);
     auto route = [&](const void *p, size_t st) {
         return fixed ? launch(h, true, p, n, st, nch, halo, d_out, n_frames)
                      : launch_float_dev(h, p, n, st, nch, halo, d_out, n_frames);
@@ -1314,8 +1386,13 @@ inline size_t host_chunk_bytes() {
 }
 
 template <typename OutT>
+int rated_process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, size_t nch, OutT *out, size_t cap,
+                       size_t *n_frames);
+
+template <typename OutT>
 int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, size_t nch, OutT *out,
                  size_t cap, size_t *n_frames) {
+    if (rated(h)) return rated_process_host<OutT>(h, fixed, pcm, n, nch, out, cap, n_frames);
     if (!h || (!pcm && n * nch)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     const size_t nf = count_frames(h->r, n);
@@ -1542,9 +1619,14 @@ int ragged_scanned(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const s
 
 // the device entry: the one scan of the call, then the above.  The order of the refusals is the entry's own
 template <typename OutT>
+int rated_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt, OutT *d_out,
+                     size_t cap, size_t *frame_offsets);
+
+template <typename OutT>
 int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
                        OutT *d_out, size_t cap, size_t *frame_offsets) {
     if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (rated(h)) return rated_ragged_dev<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
     const bool dec = decodes(h) && n_utt;                 // a sample format looks at the offsets and the pointer first
     if (!dec && fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     const mfcc_batch::Scan sc = ragged_scan(h, offsets, n_utt, frame_offsets);
@@ -1557,9 +1639,14 @@ int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, con
 // kernels, pack and gather for the rest -- and its rows come back in one copy.  (Round 1 copied utterance by
 // utterance into a zeroed packed stream: n_utt memcpy calls, 50 ms of call overhead for 10 000 utterances.)
 template <typename OutT>
+int rated_process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const size_t *offsets, size_t n_utt, OutT *out,
+                         size_t cap, size_t *frame_offsets);
+
+template <typename OutT>
 int process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const size_t *offsets, size_t n_utt,
                    OutT *out, size_t cap, size_t *frame_offsets) {
     if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (rated(h)) return rated_process_ragged<OutT>(h, fixed, pcm, offsets, n_utt, out, cap, frame_offsets);
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     const size_t ncep = fixed ? row_width(h->r) : out_width(h);          // elements per row
     const mfcc_batch::Scan sc = ragged_scan(h, offsets, n_utt, frame_offsets);
@@ -1606,6 +1693,161 @@ int process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const siz
         }
         return rc;
     });
+}
+
+// ---- a handle with an input rate: decode -> resample -> route.  The resampled samples live in h->d_rs (obtained like
+// d_dec); behind them every call is the call of a plain int16 handle on them, so its refusals, its frame counts and
+// its bits are that handle's on mfcc_hip_resample_host of the decoded input
+int rated_dense_dev(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo,
+                    void *d_out, size_t *n_frames) {
+    if ((!d_pcm && n * nch) || halo < 0 || halo > 1 || !sample_aligned(h, d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (nch > 1 && stride < n + size_t(halo)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (halo) return MFCC_HIP_ERROR_UNSUPPORTED;              // a shard's edge would need the neighbour's samples
+    if (n >= mfcc_rs::kMaxLen) return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    mfcc_rs::Taps a;
+    int rc = rs_bind(h, h->input_rate, h->r.sample_rate, a);
+    if (rc) return rc;
+    const size_t n2 = size_t(mfcc_rs::count(n, a.L, a.M)), stride2 = nch <= 1 ? n2 : (n2 + 7) & ~size_t(7);
+    if (count_frames(h->r, n2) == 0 || nch == 0 || !d_out) {                   // no sample is read
+        PlainInputGuard plain(h);
+        return dense_dev(h, fixed, d_pcm, n2, stride2, nch, 0, d_out, n_frames);
+    }
+    const int16_t *src = static_cast<const int16_t *>(d_pcm);
+    size_t src_stride = nch <= 1 ? n : stride;
+    if (decodes(h) && (rc = decode_to_scratch(h, d_pcm, n, nch, stride, &src, &src_stride))) return rc;
+    if ((rc = ensure(h, h->d_rs, nch * stride2 * sizeof(int16_t) + 64)) || (rc = scratch_acquire(h))) return rc;
+    mfcc_rs::launch(a, src, (long long)n, static_cast<int16_t *>(h->d_rs.p), (long long)n2, (long long)nch, (long long)src_stride,
+                    (long long)stride2, nullptr, 0, h->n_cu, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    {
+        PlainInputGuard plain(h);
+        rc = dense_dev(h, fixed, h->d_rs.p, n2, stride2, nch, 0, d_out, n_frames);
+    }
+    return rc ? rc : scratch_release(h);
+}
+
+// the offsets of the resampled utterances, back to back from 0.  false: decreasing offsets or a length over the limit
+bool rated_offsets(const mfcc_rs::Geometry &g, const size_t *offsets, size_t n_utt, std::vector<size_t> &off2) {
+    off2.assign(n_utt + 1, 0);
+    for (size_t u = 0; u < n_utt; ++u) {
+        if (offsets[u + 1] < offsets[u] || offsets[u + 1] - offsets[u] >= mfcc_rs::kMaxLen) return false;
+        off2[u + 1] = off2[u] + size_t(mfcc_rs::count(offsets[u + 1] - offsets[u], g.L, g.M));
+    }
+    return true;
+}
+
+// ragged: every utterance resampled on its own (zeros outside it) by one launch over a tile list, the new offsets from
+// the lengths alone; then the plain handle's call on them
+template <typename OutT>
+int rated_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt, OutT *d_out,
+                     size_t cap, size_t *frame_offsets) {
+    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
+    mfcc_rs::Geometry g;
+    int rc = rs_geometry(h->input_rate, h->r.sample_rate, g);
+    if (rc) return rc;
+    std::vector<size_t> off2;
+    if (!rated_offsets(g, offsets, n_utt, off2) || !sample_aligned(h, d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const mfcc_batch::Scan sc = ragged_scan(h, off2.data(), n_utt, frame_offsets);
+    if (sc.rc || (off2[n_utt] && !d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (sc.total == 0) return MFCC_HIP_SUCCESS;
+    const bool post = !fixed && has_post(h);
+    if (!d_out || cap < sc.total * (post ? out_width(h) : row_width(h->r))) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    DeviceGuard guard(h->device);
+    mfcc_rs::Taps a;
+    if ((rc = rs_bind(h, h->input_rate, h->r.sample_rate, a))) return rc;
+    // the decoded span (a sample format), else the caller's samples
+    const int16_t *src = d_pcm + offsets[0];
+    if (decodes(h)) {
+        size_t st = 0;
+        const size_t span = offsets[n_utt] - offsets[0];
+        if (span && (rc = decode_to_scratch(h, sample_at(h, d_pcm, offsets[0]), span, 1, span, &src, &st))) return rc;
+    }
+    // d_rs: the samples, then the records (their count does not depend on where the samples lie: 7 slots of lead at most)
+    size_t max_tiles = 0;
+    for (size_t u = 0; u < n_utt; ++u) max_tiles += mfcc_rs::max_tiles(off2[u + 1] - off2[u], false);
+    const size_t rec_off = (off2[n_utt] * sizeof(int16_t) + 255) & ~size_t(255);
+    const size_t rec_cap_ll = n_utt * mfcc_rs::kSegLL + max_tiles * mfcc_rs::kTileLL;
+    if ((rc = ensure(h, h->d_rs, rec_off + rec_cap_ll * sizeof(long long) + 64))) return rc;
+    int16_t *d_rs = static_cast<int16_t *>(h->d_rs.p);
+    std::vector<mfcc_rs::SegIn> segs(n_utt);
+    for (size_t u = 0; u < n_utt; ++u)
+        segs[u] = mfcc_rs::one_shot(g, reinterpret_cast<uintptr_t>(src + (offsets[u] - offsets[0])), offsets[u + 1] - offsets[u],
+                                    reinterpret_cast<uintptr_t>(d_rs + off2[u]));
+    mfcc_rs::CallPlan pl;
+    if (!mfcc_rs::plan_call(segs.data(), n_utt, pl) || pl.total_ll > rec_cap_ll) return MFCC_HIP_ERROR_INVALID_PARAM;
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    if ((rc = desc_acquire(h, pl.total_ll, &pd))) return rc;
+    mfcc_rs::fill_call(segs.data(), n_utt, pl, pd->p);
+    if ((rc = desc_stage(h, h->d_rs, 0, pd, pl.total_ll, rec_off))) return rc;
+    if (pl.n_tiles) {
+        mfcc_rs::launch(a, nullptr, 0, nullptr, 0, (long long)n_utt, 0, 0,
+                        reinterpret_cast<const long long *>(reinterpret_cast<const char *>(d_rs) + rec_off), (long long)pl.n_tiles,
+                        h->n_cu, h->stream);
+        HIP_TRY(h, hipGetLastError());
+    }
+    {
+        PlainInputGuard plain(h);
+        rc = ragged_scanned<OutT>(h, fixed, d_rs, off2.data(), n_utt, d_out, cap, frame_offsets, sc);
+    }
+    return rc ? rc : scratch_release(h);
+}
+
+// host buffers: the unchunked route -- one copy in, the device route, one copy back
+template <typename OutT>
+int rated_process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, size_t nch, OutT *out, size_t cap,
+                       size_t *n_frames) {
+    if (!pcm && n * nch) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
+    mfcc_rs::Geometry g;
+    int rc = rs_geometry(h->input_rate, h->r.sample_rate, g);
+    if (rc) return rc;
+    if (n >= mfcc_rs::kMaxLen) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const size_t nf = count_frames(h->r, size_t(mfcc_rs::count(n, g.L, g.M)));
+    if (n_frames) *n_frames = nf;
+    if (nf == 0 || nch == 0) return MFCC_HIP_SUCCESS;
+    const size_t n_out = nf * nch * (fixed ? row_width(h->r) : out_width(h));
+    if (!out || cap < n_out) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    DeviceGuard guard(h->device);
+    const size_t in_bytes = n * nch * sample_bytes(h);
+    if ((rc = ensure(h, h->d_raw, in_bytes + 64)) || (rc = ensure(h, h->d_full, n_out * sizeof(OutT) + 64)) ||
+        (rc = scratch_acquire(h)))
+        return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->d_raw.p, pcm, in_bytes, hipMemcpyHostToDevice, h->stream));
+    if ((rc = rated_dense_dev(h, fixed, h->d_raw.p, n, n, nch, 0, h->d_full.p, nullptr))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_full.p, n_out * sizeof(OutT), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MFCC_HIP_SUCCESS;
+}
+
+template <typename OutT>
+int rated_process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const size_t *offsets, size_t n_utt, OutT *out,
+                         size_t cap, size_t *frame_offsets) {
+    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
+    mfcc_rs::Geometry g;
+    int rc = rs_geometry(h->input_rate, h->r.sample_rate, g);
+    if (rc) return rc;
+    std::vector<size_t> off2, loc(n_utt + 1);
+    if (!rated_offsets(g, offsets, n_utt, off2)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const mfcc_batch::Scan sc = ragged_scan(h, off2.data(), n_utt, frame_offsets);
+    if (sc.rc || (off2[n_utt] && !pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (sc.total == 0) return MFCC_HIP_SUCCESS;
+    const size_t W = fixed ? row_width(h->r) : out_width(h), n_out = sc.total * W;
+    if (!out || cap < n_out) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    DeviceGuard guard(h->device);
+    for (size_t u = 0; u <= n_utt; ++u) loc[u] = offsets[u] - offsets[0];
+    const size_t in_bytes = loc[n_utt] * sample_bytes(h);
+    if ((rc = ensure(h, h->d_raw, in_bytes + 64)) || (rc = ensure(h, h->d_full, n_out * sizeof(OutT) + 64)) ||
+        (rc = scratch_acquire(h)))
+        return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->d_raw.p, sample_at(h, pcm, offsets[0]), in_bytes, hipMemcpyHostToDevice, h->stream));
+    if ((rc = rated_ragged_dev<OutT>(h, fixed, static_cast<const int16_t *>(h->d_raw.p), loc.data(), n_utt,
+                                     static_cast<OutT *>(h->d_full.p), n_out, frame_offsets)))
+        return rc;
+    // MFCC_HIP_VAD_SELECT: frame_offsets now counts the voiced rows (the call above has synchronized)
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_full.p, frame_offsets[n_utt] * W * sizeof(OutT), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MFCC_HIP_SUCCESS;
 }
 
 // ---- minimal RIFF/WAVE reader (the reference uses the un-vendored libwav, main.c:58-98)
@@ -1868,7 +2110,7 @@ void mfcc_hip_destroy(mfcc_hip_handle *h) {
     if (h->s_out) (void)hipStreamDestroy(h->s_out);
     if (h->arena) (void)hipFree(h->arena);
     for (DevBuf *b : {&h->d_in, &h->d_out, &h->d_norm, &h->d_pcen, &h->d_full, &h->d_stat, &h->d_dtab, &h->d_slide, &h->d_stab,
-                      &h->d_vad, &h->d_voiced, &h->d_sel, &h->d_final, &h->d_dec, &h->d_raw})
+                      &h->d_vad, &h->d_voiced, &h->d_sel, &h->d_final, &h->d_dec, &h->d_raw, &h->d_rs_tab, &h->d_rs})
         if (b->p) (void)hipFree(b->p);
     delete h;
 }
@@ -2186,6 +2428,89 @@ int mfcc_hip_set_sample_format(mfcc_hip_handle *h, int format) {
 
 int mfcc_hip_sample_format(const mfcc_hip_handle *h) { return h ? h->sample_fmt : MFCC_HIP_SAMPLE_S16; }
 
+// ---- sample rates (include/mfcc_hip.h: "sample rates"): the direct entries
+int mfcc_hip_resample_geometry(int in_rate, int out_rate, int *L, int *M, int *K) {
+    mfcc_rs::Geometry g;
+    const int rc = rs_geometry(in_rate, out_rate, g);
+    if (rc) return rc;
+    if (L) *L = g.L;
+    if (M) *M = g.M;
+    if (K) *K = g.K;
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_resample_count(int in_rate, int out_rate, size_t n, size_t *n_out) {
+    mfcc_rs::Geometry g;
+    const int rc = rs_geometry(in_rate, out_rate, g);
+    if (rc) return rc;
+    if (!n_out || n >= mfcc_rs::kMaxLen) return MFCC_HIP_ERROR_INVALID_PARAM;
+    *n_out = size_t(mfcc_rs::count(n, g.L, g.M));
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_resample_taps(int in_rate, int out_rate, int16_t *buf, size_t cap, size_t *n) {
+    mfcc_rs::Geometry g;
+    std::vector<int16_t> t;
+    const int rc = rs_table(in_rate, out_rate, g, t);
+    if (rc) return rc;
+    if (n) *n = t.size();
+    if (cap < t.size()) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    if (!buf) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::memcpy(buf, t.data(), t.size() * sizeof(int16_t));
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_resample_host(int in_rate, int out_rate, const int16_t *in, size_t n, int16_t *out, size_t cap) {
+    mfcc_rs::Geometry g;
+    std::vector<int16_t> t;
+    const int rc = rs_table(in_rate, out_rate, g, t);
+    if (rc) return rc;
+    if (n >= mfcc_rs::kMaxLen) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const size_t n_out = size_t(mfcc_rs::count(n, g.L, g.M));
+    if (cap < n_out) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    if (n && (!in || !out)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (n) mfcc_rs::resample_host(g, t.data(), in, (long long)n, 0, (long long)n_out, out);
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_resample_dev(mfcc_hip_handle *h, int in_rate, int out_rate, const void *d_in, size_t n, void *d_out, size_t cap) {
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    mfcc_rs::Geometry g;
+    int rc = rs_geometry(in_rate, out_rate, g);
+    if (rc) return rc;
+    if (n >= mfcc_rs::kMaxLen) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const size_t n_out = size_t(mfcc_rs::count(n, g.L, g.M));
+    if (cap < n_out) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    if (!n) return MFCC_HIP_SUCCESS;
+    const uintptr_t i_lo = reinterpret_cast<uintptr_t>(d_in), o_lo = reinterpret_cast<uintptr_t>(d_out);
+    if (!d_in || !d_out || (i_lo & 1) || (o_lo & 1)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (ranges_overlap(i_lo, i_lo + n * sizeof(int16_t), o_lo, o_lo + n_out * sizeof(int16_t))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    mfcc_rs::Taps a;
+    if ((rc = rs_bind(h, in_rate, out_rate, a))) return rc;
+    mfcc_rs::launch(a, static_cast<const int16_t *>(d_in), (long long)n, static_cast<int16_t *>(d_out), (long long)n_out, 1, 0, 0,
+                    nullptr, 0, h->n_cu, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_set_input_rate(mfcc_hip_handle *h, int in_rate) {
+    if (!h || in_rate < 0) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
+    if (in_rate == 0 || in_rate == h->r.sample_rate) {
+        h->input_rate = 0;
+        return MFCC_HIP_SUCCESS;
+    }
+    DeviceGuard guard(h->device);
+    mfcc_rs::Taps a;
+    const int rc = rs_bind(h, in_rate, h->r.sample_rate, a);          // the ratio's refusals; the table is on the device
+    if (rc) return rc;
+    h->input_rate = in_rate;
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_input_rate(const mfcc_hip_handle *h) { return h ? h->input_rate : 0; }
+
 // the WAV readers hand 16-bit PCM to the host entry points whatever the handle's format: S16 for the scope
 struct PcmFormatGuard {
     mfcc_hip_handle *h;
@@ -2212,9 +2537,9 @@ int mfcc_hip_convert_wav(mfcc_hip_handle *h, const char *wav_in, const char *mfc
     if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... n_cep wide
     if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                            // ... of every frame
     std::vector<int16_t> pcm;
-    int rc = read_wav_i16(wav_in, h->r.sample_rate, pcm);
+    int rc = read_wav_i16(wav_in, rated(h) ? h->input_rate : h->r.sample_rate, pcm);
     if (rc) return rc;
-    const size_t nf = count_frames(h->r, pcm.size());
+    const size_t nf = count_frames(h->r, own_rate_len(h, pcm.size()));
     std::vector<int16_t> cep(nf * size_t(h->r.n_cep));
     PcmFormatGuard pcm16(h);
     if (fixed) {
@@ -2247,13 +2572,13 @@ int mfcc_hip_convert_wavs(mfcc_hip_handle *h, const char *const *wav_in, const c
     for (size_t i = 0; i < n_files; ++i) {
         if (!wav_in[i] || !mfcc_out[i]) return MFCC_HIP_ERROR_INVALID_PARAM;
         std::vector<int16_t> one;
-        int rc = read_wav_i16(wav_in[i], h->r.sample_rate, one);
+        int rc = read_wav_i16(wav_in[i], rated(h) ? h->input_rate : h->r.sample_rate, one);
         if (rc) return rc;
         pcm.insert(pcm.end(), one.begin(), one.end());
         off[i + 1] = pcm.size();
     }
     size_t total = 0;
-    for (size_t i = 0; i < n_files; ++i) total += count_frames(h->r, off[i + 1] - off[i]);
+    for (size_t i = 0; i < n_files; ++i) total += count_frames(h->r, own_rate_len(h, off[i + 1] - off[i]));
     const size_t ncep = size_t(h->r.n_cep);
     std::vector<int16_t> cep(total * ncep);
     int rc;
@@ -2352,6 +2677,7 @@ int mfcc_hip_stream_create(mfcc_hip_handle *h, int fixed, mfcc_hip_stream **out)
     if (h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;                           // ... and a per-call smoother
     if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;     // deltas need 2 K N frames of lookahead
     if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;        // the threshold's mean is a whole-segment statistic
+    if (rated(h)) return MFCC_HIP_ERROR_UNSUPPORTED;           // a line's rate conversion keeps state between pushes
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     mfcc_hip_stream *s = new (std::nothrow) mfcc_hip_stream();
     if (!s) return MFCC_HIP_ERROR_NO_MEM;
@@ -2719,6 +3045,7 @@ int bank_create_checked(mfcc_hip_handle *h, int fixed, bool online, size_t n_str
     *out = nullptr;
     if (h->destroy_pending || !n_streams || (p && !pcen_ok(p))) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (rated(h)) return MFCC_HIP_ERROR_UNSUPPORTED;           // a line's rate conversion keeps state between pushes
     if (p && !is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (online && h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel)) return MFCC_HIP_ERROR_UNSUPPORTED;
@@ -3198,6 +3525,218 @@ int mfcc_hip_gate_window_dev(mfcc_hip_gate *g, const size_t *lines, size_t n, vo
                        geo, g->D, static_cast<int16_t *>(d_out));
     HIP_TRY(h, hipGetLastError());
     return scratch_release(h);
+}
+
+// ---- live lines (include/mfcc_hip.h: mfcc_hip_resampler): the streaming form of the rule.  A line keeps the count of
+// its samples on the host and its last K - 1 samples on the device, in two buffers used in turn
+struct mfcc_hip_resampler {
+    mfcc_hip_handle *h = nullptr;
+    size_t n = 0;                        // lines
+    int fmt = MFCC_HIP_SAMPLE_S16, in_rate = 0, out_rate = 0;
+    mfcc_rs::Geometry g;
+    int16_t *d_taps = nullptr;           // the ratio's table
+    int16_t *d_hist = nullptr;           // [n][2][hist_stride]
+    size_t hist_stride = 0;              // K - 1 rounded up to 8
+    std::vector<size_t> seen;            // samples since create / reset / flush: depends on chunk lengths only
+    std::vector<unsigned char> cur;      // which of a line's two buffers holds its history
+};
+
+namespace {
+
+// out_offsets of a push (flush = 0: every line's chunk offsets[u] .. offsets[u + 1] on top of seen[u]) or of a flush behind
+// it (flush != 0; offsets NULL: no chunks).  INVALID_PARAM where the offsets decrease or a line grows over the limit
+int rs_stream_plan(const mfcc_rs::Geometry &g, const size_t *seen, const size_t *offsets, size_t n_lines, int flush,
+                   size_t *out_offsets) {
+    out_offsets[0] = 0;
+    for (size_t u = 0; u < n_lines; ++u) {
+        if (offsets && offsets[u + 1] < offsets[u]) return MFCC_HIP_ERROR_INVALID_PARAM;
+        const size_t len = offsets ? offsets[u + 1] - offsets[u] : 0;
+        if (seen[u] >= mfcc_rs::kMaxLen || len >= mfcc_rs::kMaxLen - seen[u]) return MFCC_HIP_ERROR_INVALID_PARAM;
+        const size_t c = seen[u] + len;
+        const size_t k = flush ? size_t(mfcc_rs::count(c, g.L, g.M) - mfcc_rs::emitted(c, g.L, g.M, g.H))
+                               : size_t(mfcc_rs::emitted(c, g.L, g.M, g.H) - mfcc_rs::emitted(seen[u], g.L, g.M, g.H));
+        out_offsets[u + 1] = out_offsets[u] + k;
+    }
+    return MFCC_HIP_SUCCESS;
+}
+
+// the segments of a push or a flush in one launch: the records through the pinned pool into h->d_rs
+int rs_stream_launch(mfcc_hip_resampler *r, const std::vector<mfcc_rs::SegIn> &segs) {
+    mfcc_hip_handle *h = r->h;
+    mfcc_rs::CallPlan pl;
+    if (!mfcc_rs::plan_call(segs.data(), segs.size(), pl)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!pl.n_tiles) return MFCC_HIP_SUCCESS;
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    int rc = desc_acquire(h, pl.total_ll, &pd);
+    if (rc) return rc;
+    mfcc_rs::fill_call(segs.data(), segs.size(), pl, pd->p);
+    if ((rc = desc_stage(h, h->d_rs, pl.bytes, pd, pl.total_ll))) return rc;
+    const mfcc_rs::Taps a{r->d_taps, r->g.L, r->g.M, r->g.H, r->g.K};
+    mfcc_rs::launch(a, nullptr, 0, nullptr, 0, (long long)segs.size(), 0, 0, static_cast<const long long *>(h->d_rs.p),
+                    (long long)pl.n_tiles, h->n_cu, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    return MFCC_HIP_SUCCESS;
+}
+
+inline int16_t *rs_hist(const mfcc_hip_resampler *r, size_t line, int which) {
+    return r->d_hist + (2 * line + size_t(which)) * r->hist_stride;
+}
+
+}  // namespace
+
+int mfcc_hip_resampler_plan(int in_rate, int out_rate, const size_t *seen, const size_t *offsets, size_t n_lines, int flush,
+                            size_t *out_offsets) {
+    mfcc_rs::Geometry g;
+    const int rc = rs_geometry(in_rate, out_rate, g);
+    if (rc) return rc;
+    if (!out_offsets || (n_lines && !seen) || (!flush && n_lines && !offsets)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    return rs_stream_plan(g, seen, offsets, n_lines, flush, out_offsets);
+}
+
+int mfcc_hip_resampler_create(mfcc_hip_handle *h, size_t n_lines, int sample_format, int in_rate, int out_rate,
+                              mfcc_hip_resampler **out) {
+    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
+    *out = nullptr;
+    if (h->destroy_pending || !n_lines || !mfcc_decode::known(sample_format)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    mfcc_rs::Geometry g;
+    std::vector<int16_t> t;
+    const int rc = rs_table(in_rate, out_rate, g, t);
+    if (rc) return rc;
+    mfcc_hip_resampler *r = new (std::nothrow) mfcc_hip_resampler();
+    if (!r) return MFCC_HIP_ERROR_NO_MEM;
+    r->h = h;
+    r->n = n_lines;
+    r->fmt = sample_format;
+    r->in_rate = in_rate;
+    r->out_rate = out_rate;
+    r->g = g;
+    r->hist_stride = (size_t(g.K) - 1 + 7) & ~size_t(7);
+    r->seen.assign(n_lines, 0);
+    r->cur.assign(n_lines, 0);
+    ++h->n_sessions;
+    DeviceGuard guard(h->device);
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&r->d_taps), t.size() * sizeof(int16_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_hist), 2 * n_lines * r->hist_stride * sizeof(int16_t));
+    if (e == hipSuccess) e = hipMemcpy(r->d_taps, t.data(), t.size() * sizeof(int16_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        h->last_hip = int(e);
+        mfcc_hip_resampler_destroy(r);
+        return e == hipErrorOutOfMemory ? MFCC_HIP_ERROR_NO_MEM : MFCC_HIP_ERROR_OTHER;
+    }
+    *out = r;
+    return MFCC_HIP_SUCCESS;
+}
+
+void mfcc_hip_resampler_destroy(mfcc_hip_resampler *r) {
+    if (!r) return;
+    mfcc_hip_handle *h = r->h;
+    {
+        DeviceGuard guard(h->device);
+        if (h->scratch_used) (void)hipEventSynchronize(h->scratch_done);    // a push may be in flight on a caller's stream
+        (void)hipStreamSynchronize(h->stream);
+        if (r->d_taps) (void)hipFree(r->d_taps);
+        if (r->d_hist) (void)hipFree(r->d_hist);
+        delete r;
+    }
+    if (--h->n_sessions == 0 && h->destroy_pending) mfcc_hip_destroy(h);
+}
+
+int mfcc_hip_resampler_seen(const mfcc_hip_resampler *r, size_t *seen) {
+    if (!r || !seen) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::copy(r->seen.begin(), r->seen.end(), seen);
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_resampler_reset(mfcc_hip_resampler *r, const size_t *lines, size_t n) {
+    if (!r) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::vector<size_t> list;                           // lines == NULL: every line
+    const int rc = bank_list(r->n, lines, n, list);
+    if (rc) return rc;
+    // the counts travel with every launch's records: a line whose count is 0 reads nothing of its history
+    for (size_t u : list) r->seen[u] = 0;
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_resampler_push_dev(mfcc_hip_resampler *r, const void *d_in, const size_t *offsets, void *d_out, size_t cap,
+                                size_t *out_offsets) {
+    if (!r || !offsets || !out_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    mfcc_hip_handle *h = r->h;
+    const mfcc_rs::Geometry &g = r->g;
+    int rc = rs_stream_plan(g, r->seen.data(), offsets, r->n, 0, out_offsets);
+    if (rc) return rc;
+    const size_t span = offsets[r->n] - offsets[0], ssz = mfcc_decode::sample_size(r->fmt);
+    if (cap < out_offsets[r->n]) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    if (!span) return MFCC_HIP_SUCCESS;
+    if (!d_in || (reinterpret_cast<uintptr_t>(d_in) & (ssz - 1))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (out_offsets[r->n] && (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 1))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    // the chunks as int16: decoded in front, like a bank's push
+    const int16_t *src = static_cast<const int16_t *>(d_in) + offsets[0];
+    if (r->fmt != MFCC_HIP_SAMPLE_S16) {
+        if ((rc = ensure(h, h->d_dec, span * sizeof(int16_t) + 64)) || (rc = scratch_acquire(h))) return rc;
+        if (!mfcc_decode::launch(r->fmt, static_cast<const char *>(d_in) + offsets[0] * ssz, static_cast<int16_t *>(h->d_dec.p), span,
+                                 1, span, span, h->n_cu, h->stream))
+            return MFCC_HIP_ERROR_INVALID_PARAM;
+        HIP_TRY(h, hipGetLastError());
+        src = static_cast<const int16_t *>(h->d_dec.p);
+    }
+    std::vector<mfcc_rs::SegIn> segs;
+    segs.reserve(r->n);
+    for (size_t u = 0; u < r->n; ++u) {
+        const size_t len = offsets[u + 1] - offsets[u];
+        if (!len) continue;
+        mfcc_rs::SegIn s;
+        s.in = reinterpret_cast<uintptr_t>(src + (offsets[u] - offsets[0]));
+        s.n = len;
+        s.out = reinterpret_cast<uintptr_t>(static_cast<int16_t *>(d_out) + out_offsets[u]);
+        s.c0 = r->seen[u];
+        s.m0 = mfcc_rs::emitted(r->seen[u], g.L, g.M, g.H);
+        s.m1 = mfcc_rs::emitted(r->seen[u] + len, g.L, g.M, g.H);
+        s.hist = r->seen[u] ? reinterpret_cast<uintptr_t>(rs_hist(r, u, r->cur[u])) : 0;      // a fresh line: zeros
+        s.hist_new = reinterpret_cast<uintptr_t>(rs_hist(r, u, r->cur[u] ^ 1));
+        segs.push_back(s);
+    }
+    if ((rc = rs_stream_launch(r, segs)) || (rc = scratch_release(h))) return rc;
+    for (size_t u = 0; u < r->n; ++u) {
+        const size_t len = offsets[u + 1] - offsets[u];
+        if (!len) continue;
+        r->seen[u] += len;
+        r->cur[u] ^= 1;
+    }
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_resampler_flush_dev(mfcc_hip_resampler *r, const size_t *lines, size_t n, void *d_out, size_t cap,
+                                 size_t *out_offsets) {
+    if (!r || !out_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    mfcc_hip_handle *h = r->h;
+    const mfcc_rs::Geometry &g = r->g;
+    std::vector<size_t> list;                           // lines == NULL: every line
+    int rc = bank_list(r->n, lines, n, list);
+    if (rc) return rc;
+    std::vector<size_t> seen(list.size());
+    for (size_t i = 0; i < list.size(); ++i) seen[i] = r->seen[list[i]];
+    if ((rc = rs_stream_plan(g, seen.data(), nullptr, list.size(), 1, out_offsets))) return rc;
+    const size_t total = out_offsets[list.size()];
+    if (cap < total) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    if (total && (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 1))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (total) {
+        DeviceGuard guard(h->device);
+        std::vector<mfcc_rs::SegIn> segs;
+        for (size_t i = 0; i < list.size(); ++i) {
+            if (out_offsets[i + 1] == out_offsets[i]) continue;
+            mfcc_rs::SegIn s;                                           // no chunk: the history, then zeros
+            s.out = reinterpret_cast<uintptr_t>(static_cast<int16_t *>(d_out) + out_offsets[i]);
+            s.c0 = seen[i];
+            s.m0 = mfcc_rs::emitted(seen[i], g.L, g.M, g.H);
+            s.m1 = mfcc_rs::count(seen[i], g.L, g.M);
+            s.hist = reinterpret_cast<uintptr_t>(rs_hist(r, list[i], r->cur[list[i]]));
+            segs.push_back(s);
+        }
+        if ((rc = rs_stream_launch(r, segs)) || (rc = scratch_release(h))) return rc;
+    }
+    for (size_t u : list) r->seen[u] = 0;
+    return MFCC_HIP_SUCCESS;
 }
 
 int mfcc_hip_lift_file(const char *mfcc_in, const char *lift_out, int n_cep, double L, size_t *n_frames_out) {
