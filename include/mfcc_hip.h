@@ -306,6 +306,49 @@ int  mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t 
                        size_t ch_stride_samples, size_t n_channels, void *d_out,
                        int warmup, int iters, float *avg_ms);
 
+/* ---- power spectrum ----------------------------------------------------------------------------------------------
+ * The intermediate every float output starts from (the notebook's audio_power, MFCC.ipynb cell 22), as rows of
+ * bins = nfft / 2 + 1 float32 values.  Element k of row f of a channel is
+ *
+ *     | FFT_nfft(w . y_f)[k] / power_scale |^2          k = 0 .. nfft / 2
+ *
+ * y: the pre-emphasised stream, y[i] = x[i] - 31/32 x[i - 1] (x[-1] = 0, or the halo sample); y_f: its nfft samples from
+ * sample f * hop on; w: the handle's window -- periodic Hamming over the handle's frame length, then zeros up to nfft
+ * (mfcc_hip_create_framed).  Framing, padding and frame counts are the handle's (hop, pad_mode, frame length), exactly
+ * those of mfcc_hip_process_i16*.  A frame whose samples (and history sample) are all zero gives +0.0 in every bin; every
+ * value is finite and >= 0 for any int16 input.  With a mel matrix W [n][bins] the band energies of the float path are
+ * W . row -- for any n, not only the 64 rows the fused kernels hold.
+ *
+ * The handle's sample format and input rate apply (they say what a sample pointer holds: the decode and the resampler
+ * run in front, as for mfcc_hip_process_*).  The handle's n_mel, n_cep, output, lifter, mel bank, normalization, delta,
+ * PCEN and VAD settings do NOT apply: they are ignored, and a handle with any of them returns the rows of a plain one.
+ * float_impl = MFCC_HIP_IMPL_GENERIC selects the generic spectrum kernel.  There is no fixed-point form, and streaming
+ * sessions and stream banks have no spectrum output.  The parameter block and the ABI version are unchanged.           */
+
+/* bins of a row for this parameter block: nfft / 2 + 1.  Host only.  Invalid block or NULL bins:
+ * MFCC_HIP_ERROR_INVALID_PARAM. */
+int  mfcc_hip_spectrum_bins(const mfcc_hip_params *p, size_t *bins);
+/* Device-resident buffers: the arguments, frame counts, halo rule, stream behaviour and refusals of
+ * mfcc_hip_process_i16_dev.  d_out: float32 [n_channels][n_frames][bins], 4-byte aligned. */
+int  mfcc_hip_spectrum_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n_samples_per_ch,
+                               size_t ch_stride_samples, size_t n_channels, int halo, void *d_out, size_t *n_frames);
+/* Ragged batch on the device: the arguments and refusals of mfcc_hip_process_ragged_i16_dev, MFCC_HIP_ERROR_BUFFER_SMALL
+ * with frame_offsets filled included.  d_out: [sum frames][bins]; out_capacity counts floats.  Rows are bit-identical to
+ * one mfcc_hip_spectrum_i16_dev call per utterance. */
+int  mfcc_hip_spectrum_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const size_t *offsets, size_t n_utterances,
+                                      void *d_out, size_t out_capacity, size_t *frame_offsets);
+/* Host buffers, synchronous: the arguments and refusals of mfcc_hip_process_i16.  out: [n_channels][n_frames][bins];
+ * out_capacity counts floats. */
+int  mfcc_hip_spectrum_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n_samples_per_ch, size_t n_channels,
+                           float *out, size_t out_capacity, size_t *n_frames);
+/* the kernel the handle's spectrum calls run: "mfcc_spectrum512_kernel" or "mfcc_spectrum_generic_kernel".  As with the
+ * MFCC kernels, a single call whose tile count does not fit the fused kernel's 32-bit arithmetic (2^31 tiles of 16 frames,
+ * or 2^26 tiles in one channel) runs the generic spectrum kernel instead, without an error; this name does not change.
+ * The ragged entry packs utterances of different lengths into one stream, runs the kernel on it and gathers the rows
+ * (equal lengths run as channels of one dense launch): its rows cross HBM twice and the handle holds scratch for
+ * every packed frame x bins floats. */
+const char *mfcc_hip_spectrum_kernel_name(const mfcc_hip_handle *h);
+
 /* ---- per-segment normalization (enum mfcc_hip_normalize) -------------------------------------------------------
  * The handle's mode applies to every float call enqueued after it: mfcc_hip_process_i16, mfcc_hip_process_i16_dev,
  * both float mfcc_hip_process_ragged_* entry points and mfcc_hip_time_dev (which then times the launch AND the

@@ -259,6 +259,13 @@ SYMBOLS = {
     "mfcc_hip_resampler_plan": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, _SZ, C.c_int, C.c_void_p]),
     "mfcc_hip_resampler_push_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, _SZ, C.c_void_p]),
     "mfcc_hip_resampler_flush_dev": (C.c_int, [_H, C.c_void_p, _SZ, C.c_void_p, _SZ, C.c_void_p]),
+    # the power-spectrum output: the host-only helper, the three compute entries and the kernel's name
+    "mfcc_hip_spectrum_bins": (C.c_int, [C.POINTER(Params), _PSZ]),
+    "mfcc_hip_spectrum_i16_dev": (C.c_int, [_H, C.c_void_p, _SZ, _SZ, _SZ, C.c_int, C.c_void_p, _PSZ]),
+    "mfcc_hip_spectrum_ragged_i16_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                   C.c_void_p]),
+    "mfcc_hip_spectrum_i16": (C.c_int, [_H, C.c_void_p, _SZ, _SZ, C.c_void_p, _SZ, _PSZ]),
+    "mfcc_hip_spectrum_kernel_name": (C.c_char_p, [_H]),
 }
 
 _lib = None

@@ -280,6 +280,14 @@ def num_frames(n_samples, win_length=None, **kw) -> int:
     return int(out.value)
 
 
+def spectrum_bins(**kw) -> int:
+    """Width of a ``MFCC.power_spectrum`` row for ``make_params(**kw)``: ``nfft // 2 + 1`` (host-only)."""
+    p = make_params(**kw)
+    out = C.c_size_t(0)
+    _lib.check(_lib.load().mfcc_hip_spectrum_bins(C.byref(p), C.byref(out)), "spectrum_bins")
+    return int(out.value)
+
+
 _TABLE_DTYPES = {
     _lib.TABLE_WINDOW_F32: np.float32, _lib.TABLE_MEL_POINTS_I32: np.int32,
     _lib.TABLE_MEL_DENSE_F32: np.float32, _lib.TABLE_DCT_F32: np.float32,
@@ -726,8 +734,13 @@ class MFCC(_Owner):
         ``1 + deltas``."""
         return (self.nfilters if self.output == "logmel" else self.nceptrums) * (1 + self.deltas)
 
-    def _row(self, fixed):
-        return self.nceptrums if fixed else self.num_features
+    @property
+    def num_bins(self) -> int:
+        """Width of a ``power_spectrum`` row: ``nfft // 2 + 1``."""
+        return int(self.nfft) // 2 + 1
+
+    def _row(self, fixed, spectrum=False):
+        return self.num_bins if spectrum else self.nceptrums if fixed else self.num_features
 
     def num_frames(self, n_samples) -> int:
         """Frames of ``n_samples`` samples of one channel or utterance (at ``input_rate`` where one is set)."""
@@ -740,6 +753,10 @@ class MFCC(_Owner):
 
     def kernel_name(self, fixed=False) -> str:
         return self._lib.mfcc_hip_kernel_name(self._h, int(fixed)).decode()
+
+    def spectrum_kernel_name(self) -> str:
+        """The kernel ``power_spectrum`` runs: ``mfcc_spectrum512_kernel`` or ``mfcc_spectrum_generic_kernel``."""
+        return self._lib.mfcc_hip_spectrum_kernel_name(self._h).decode()
 
     def is_fallback(self, fixed=False) -> bool:
         """True when this parameter set runs on a generic kernel (one frame per wave, 3-6 x slower than the fused kernels
@@ -759,7 +776,7 @@ class MFCC(_Owner):
         _lib.check(self._lib.mfcc_hip_synchronize(self._h))
 
     # -- the hot path ---------------------------------------------------------------
-    def _host(self, pcm, fixed):
+    def _host(self, pcm, fixed, spectrum=False):
         pcm = _host_samples(pcm, self.sample_format, "pcm")
         squeeze = pcm.ndim == 1
         if squeeze:
@@ -768,15 +785,16 @@ class MFCC(_Owner):
             raise ValueError("pcm must be (n,) or (channels, n)")
         nch, n = pcm.shape
         nf = self.num_frames(n)
-        out = np.empty((nch, nf, self._row(fixed)), dtype=np.int16 if fixed else np.float32)
+        out = np.empty((nch, nf, self._row(fixed, spectrum)), dtype=np.int16 if fixed else np.float32)
         got = C.c_size_t(0)
-        fn = self._lib.mfcc_hip_process_fixed_i16 if fixed else self._lib.mfcc_hip_process_i16
+        fn = (self._lib.mfcc_hip_spectrum_i16 if spectrum else
+              self._lib.mfcc_hip_process_fixed_i16 if fixed else self._lib.mfcc_hip_process_i16)
         _lib.check(fn(self._h, ptr(pcm), n, nch, ptr(out), out.size, C.byref(got)),
-                   "process" if not self.vad else self._DENSE_VAD)
+                   "spectrum" if spectrum else "process" if not self.vad else self._DENSE_VAD)
         assert got.value == nf
         return out[0] if squeeze else out
 
-    def _dev(self, pcm, fixed, halo, out):
+    def _dev(self, pcm, fixed, halo, out, spectrum=False):
         import torch
         if not self._samples_dev_ok(pcm):
             raise TypeError("device path needs a %s tensor" % self._dev_what())
@@ -792,13 +810,13 @@ class MFCC(_Owner):
         nf = self.num_frames(n)
         self._check_device(pcm)
         odt = torch.int16 if fixed else torch.float32
-        row = self._row(fixed)
+        row = self._row(fixed, spectrum)
         want = (nf, row) if squeeze and out is not None and out.dim() == 2 else (nch, nf, row)
         out = _out(pcm, out, want, odt, lambda: torch.empty(want, device=pcm.device, dtype=odt))
         got = C.c_size_t(0)
-        self._call(pcm.device, "process_fixed_i16_dev" if fixed else "process_i16_dev", self._h, ptr(pcm), n,
-                   pcm.stride(0), nch, int(halo), ptr(out), C.byref(got),
-                   what="process_dev" if not self.vad else self._DENSE_VAD)
+        self._call(pcm.device, "spectrum_i16_dev" if spectrum else "process_fixed_i16_dev" if fixed else "process_i16_dev",
+                   self._h, ptr(pcm), n, pcm.stride(0), nch, int(halo), ptr(out), C.byref(got),
+                   what="spectrum_dev" if spectrum else "process_dev" if not self.vad else self._DENSE_VAD)
         if squeeze and out.dim() == 3:
             return out[0]
         return out
@@ -853,6 +871,26 @@ class MFCC(_Owner):
         if halo:
             raise ValueError("halo is only available on the device path")
         return self._host(pcm, False)
+
+    def power_spectrum(self, pcm, halo=0, out=None):
+        """The power spectrum every float output starts from: PCM ``(n,)`` / ``(channels, n)`` in the handle's sample
+        format and rate -> float32 ``(.., frames, nfft // 2 + 1)``, row ``f`` = ``|FFT(window * preemph(frame f)) /
+        power_scale|**2`` with the handle's framing and window.  NumPy in -> NumPy out; torch CUDA tensor in -> torch
+        tensor out, asynchronous on the current stream, ``halo`` and ``out`` as for ``process``.  The handle's filterbank,
+        output kind, normalization, deltas, PCEN and VAD do not apply: ``torch.matmul(rows, W.T)`` with any mel matrix
+        ``W`` gives the band energies."""
+        if _is_torch(pcm):
+            return self._dev(pcm, False, halo, out, spectrum=True)
+        if halo:
+            raise ValueError("halo is only available on the device path")
+        if out is not None:
+            raise ValueError("out is only available on the device path")
+        return self._host(pcm, False, spectrum=True)
+
+    def power_spectrum_packed(self, flat, offsets, out=None):
+        """``power_spectrum`` of a corpus that lies in HBM, as ``process_packed`` takes it: ``(rows, frame_offsets)`` with
+        ``rows`` the dense ``(sum frames, nfft // 2 + 1)`` tensor, bit-identical to one ``power_spectrum`` per utterance."""
+        return self._packed(flat, offsets, False, out, True)
 
     def process_fixed(self, pcm, halo=0, out=None):
         """Fixed contract (RTL arithmetic): int16 PCM -> int16 coefficients, bit-exact."""
@@ -911,6 +949,10 @@ class MFCC(_Owner):
         result tensor and the row range of every utterance (``out[fo[u]:fo[u + 1]]``).  Equal-length utterances run
         as channels of one multi-channel launch (no packing copy); the bits are the same.  On a ``vad="select"`` handle
         ``out`` still needs room for every frame; what is returned is ``(out[:fo[-1]], fo)``, the voiced rows."""
+        return self._packed(flat, offsets, fixed, out, False)
+
+    def _packed(self, flat, offsets, fixed, out, _spectrum):
+        """``process_packed`` and ``power_spectrum_packed``: the checks, the output and the ragged device entry."""
         import torch
         if not self._samples_dev_ok(flat) or flat.dim() != 1 or not flat.is_contiguous():
             raise TypeError("flat must be a contiguous 1-D %s tensor" % self._dev_what())
@@ -929,11 +971,12 @@ class MFCC(_Owner):
             uniq, counts = np.unique(lens, return_counts=True)
             nf = int(sum(self.num_frames(int(v)) * int(c) for v, c in zip(uniq, counts)))
         odt = torch.int16 if fixed else torch.float32
-        row = self._row(fixed)
+        row = self._row(fixed, _spectrum)
         out = _out(flat, out, (nf, row), odt, lambda: torch.empty((nf, row), device=flat.device, dtype=odt))
-        self._call(flat.device, "process_ragged_fixed_i16_dev" if fixed else "process_ragged_i16_dev", self._h, ptr(flat),
-                   ptr(offsets), n, ptr(out), out.numel(), ptr(fo), what="process_ragged_dev")
-        if self.vad and not fixed:
+        name = "spectrum_ragged_i16_dev" if _spectrum else "process_ragged_fixed_i16_dev" if fixed else "process_ragged_i16_dev"
+        self._call(flat.device, name, self._h, ptr(flat), ptr(offsets), n, ptr(out), out.numel(), ptr(fo),
+                   what="spectrum_ragged_dev" if _spectrum else "process_ragged_dev")
+        if self.vad and not fixed and not _spectrum:
             return out[:int(fo[-1])], fo                 # the voiced rows; the entry point has waited for the stream
         assert int(fo[-1]) == nf
         return out, fo

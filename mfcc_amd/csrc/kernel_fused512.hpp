@@ -701,6 +701,9 @@ __device__ __forceinline__ void mel_bf_blocks(const f32x4 (&acc)[SetsBf<DENSE>::
 // values instead of running the DCT; lds: lds_words(kQWords, DCX) floats.  The arguments are taken by value, as a kernel
 // takes them: with references the compiler allocates other registers and the instantiations' rates move by up to 4 %
 // either way.
+// kernel_spectrum.hpp: mfcc_spectrum512_kernel restates this loop's fetch / park order, pass 1, the transpose, pass 2 and
+// the column-16 MFMAs without the mel, log and DCT phases (a copy, so that this loop keeps its registers and its rate): a
+// fix to any of those here belongs there too.
 template <int HOP, bool DENSE, bool DCX, bool LOGMEL>
 __device__ __forceinline__ void tile_loop_w4(const mfcc_k::StreamDesc s, const FusedTables t, const LaunchGeom g,
                                              float *__restrict__ out, float *lds) {

@@ -70,6 +70,77 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// ---- the three stages every generic float kernel shares (mfcc_float_generic_kernel below, mfcc_spectrum_generic_kernel
+// in kernel_spectrum.hpp).  One wave, one frame; the caller puts a wave_sync() where a stage's LDS writes are read.
+
+// pre-emphasis (MFCC.ipynb cell 7) + Hamming (cell 18) of the frame at sample n0 into za: z[m] = y[2m] + i y[2m+1]
+template <int NFFT>
+__device__ __forceinline__ void gen_stage_frame(const StreamDesc &s, const int16_t *base, long long n0, const float *win_p,
+                                                float *za, int lane) {
+    for (int i = lane; i < NFFT; i += 64) {
+        float x0 = sample_at(s, base, n0 + i);
+        float x1 = sample_at(s, base, n0 + i - 1);
+        // y[0] = x[0] for the very first sample of a stream: history is 0 there
+        float y = x0 - 0.96875f * x1;
+        za[i] = y * win_p[i];
+    }
+}
+
+// Stockham autosort FFT of length M: radix-4 passes, one radix-2 pass if needed.  src and dst are the wave's ping-pong
+// buffers; on return src holds the transform and dst is free
+template <int M>
+__device__ __forceinline__ void gen_stockham(float2 *&src, float2 *&dst, const float2 *tw_p, int lane) {
+    int Ns = 1;
+    for (; Ns * 4 <= M; Ns *= 4) {
+        const int tstride = M / (Ns * 4);
+        for (int j = lane; j < M / 4; j += 64) {
+            const int k = j & (Ns - 1);
+            float2 v0 = src[j];
+            float2 v1 = cmul(src[j + M / 4], tw_p[k * tstride]);
+            float2 v2 = cmul(src[j + 2 * (M / 4)], tw_p[2 * k * tstride]);
+            float2 v3 = cmul(src[j + 3 * (M / 4)], tw_p[3 * k * tstride]);
+            float2 a0 = make_float2(v0.x + v2.x, v0.y + v2.y);
+            float2 a1 = make_float2(v0.x - v2.x, v0.y - v2.y);
+            float2 a2 = make_float2(v1.x + v3.x, v1.y + v3.y);
+            float2 a3 = make_float2(v1.y - v3.y, v3.x - v1.x);      // -i * (v1 - v3)
+            const int j0 = ((j - k) << 2) + k;
+            dst[j0] = make_float2(a0.x + a2.x, a0.y + a2.y);
+            dst[j0 + Ns] = make_float2(a1.x + a3.x, a1.y + a3.y);
+            dst[j0 + 2 * Ns] = make_float2(a0.x - a2.x, a0.y - a2.y);
+            dst[j0 + 3 * Ns] = make_float2(a1.x - a3.x, a1.y - a3.y);
+        }
+        wave_sync();
+        float2 *tmp = src; src = dst; dst = tmp;
+    }
+    if (Ns < M) {                       // remaining radix-2 pass (M = 2 * 4^n)
+        const int tstride = M / (Ns * 2);
+        for (int j = lane; j < M / 2; j += 64) {
+            const int k = j & (Ns - 1);
+            float2 v0 = src[j];
+            float2 v1 = cmul(src[j + M / 2], tw_p[k * tstride]);
+            const int j0 = ((j - k) << 1) + k;
+            dst[j0] = make_float2(v0.x + v1.x, v0.y + v1.y);
+            dst[j0 + Ns] = make_float2(v0.x - v1.x, v0.y - v1.y);
+        }
+        wave_sync();
+        float2 *tmp = src; src = dst; dst = tmp;
+    }
+}
+
+// real-FFT split (cell 20) of bin k, k = 0..M, out of the M-point transform, and its power xr^2 + xi^2 (cell 22)
+template <int M>
+__device__ __forceinline__ float gen_split_power(const float2 *src, const float2 *tws_p, int k) {
+    float2 a = src[k & (M - 1)];
+    float2 b = src[(M - k) & (M - 1)];
+    float er = 0.5f * (a.x + b.x), ei = 0.5f * (a.y - b.y);      // E = (a + conj b)/2
+    float dr = a.x - b.x, di = a.y + b.y;                         // a - conj b
+    float orr = 0.5f * di, oi = -0.5f * dr;                       // O = -i/2 (a - conj b)
+    float2 w = tws_p[k];
+    float xr = er + (w.x * orr - w.y * oi);
+    float xi = ei + (w.x * oi + w.y * orr);
+    return xr * xr + xi * xi;
+}
+
 // LOGMEL: the log-mel form -- rows of n_mel log2 band energies instead of n_cep DCT-II coefficients
 template <int NFFT, bool LOGMEL>
 __global__ __launch_bounds__(kBlock) void mfcc_float_generic_kernel(StreamDesc s, FloatTables t,
@@ -121,14 +192,7 @@ __global__ __launch_bounds__(kBlock) void mfcc_float_generic_kernel(StreamDesc s
         const long long n0 = f * (long long)s.hop;
 
         // pre-emphasis (MFCC.ipynb cell 7) + Hamming (cell 18); z[m] = y[2m] + i y[2m+1]
-        float *za = reinterpret_cast<float *>(bufA[wave]);
-        for (int i = lane; i < NFFT; i += 64) {
-            float x0 = valid ? sample_at(s, base, n0 + i) : 0.0f;
-            float x1 = valid ? sample_at(s, base, n0 + i - 1) : 0.0f;
-            // y[0] = x[0] for the very first sample of a stream: history is 0 there
-            float y = x0 - 0.96875f * x1;
-            za[i] = y * win_p[i];
-        }
+        gen_stage_frame<NFFT>(s, base, n0, win_p, reinterpret_cast<float *>(bufA[wave]), lane);
         double dc = 0.0;
         if (t.window_d) {                       // uniform: X[0] = sum w y in double (y is exact)
             for (int i = lane; i < NFFT; i += 64) {
@@ -140,57 +204,15 @@ __global__ __launch_bounds__(kBlock) void mfcc_float_generic_kernel(StreamDesc s
         }
         wave_sync();
 
-        // Stockham autosort FFT of length M: radix-4 passes, one radix-2 pass if needed
         float2 *src = bufA[wave];
         float2 *dst = bufB[wave];
-        int Ns = 1;
-        for (; Ns * 4 <= M; Ns *= 4) {
-            const int tstride = M / (Ns * 4);
-            for (int j = lane; j < M / 4; j += 64) {
-                const int k = j & (Ns - 1);
-                float2 v0 = src[j];
-                float2 v1 = cmul(src[j + M / 4], tw_p[k * tstride]);
-                float2 v2 = cmul(src[j + 2 * (M / 4)], tw_p[2 * k * tstride]);
-                float2 v3 = cmul(src[j + 3 * (M / 4)], tw_p[3 * k * tstride]);
-                float2 a0 = make_float2(v0.x + v2.x, v0.y + v2.y);
-                float2 a1 = make_float2(v0.x - v2.x, v0.y - v2.y);
-                float2 a2 = make_float2(v1.x + v3.x, v1.y + v3.y);
-                float2 a3 = make_float2(v1.y - v3.y, v3.x - v1.x);      // -i * (v1 - v3)
-                const int j0 = ((j - k) << 2) + k;
-                dst[j0] = make_float2(a0.x + a2.x, a0.y + a2.y);
-                dst[j0 + Ns] = make_float2(a1.x + a3.x, a1.y + a3.y);
-                dst[j0 + 2 * Ns] = make_float2(a0.x - a2.x, a0.y - a2.y);
-                dst[j0 + 3 * Ns] = make_float2(a1.x - a3.x, a1.y - a3.y);
-            }
-            wave_sync();
-            float2 *tmp = src; src = dst; dst = tmp;
-        }
-        if (Ns < M) {                       // remaining radix-2 pass (M = 2 * 4^n)
-            const int tstride = M / (Ns * 2);
-            for (int j = lane; j < M / 2; j += 64) {
-                const int k = j & (Ns - 1);
-                float2 v0 = src[j];
-                float2 v1 = cmul(src[j + M / 2], tw_p[k * tstride]);
-                const int j0 = ((j - k) << 1) + k;
-                dst[j0] = make_float2(v0.x + v1.x, v0.y + v1.y);
-                dst[j0 + Ns] = make_float2(v0.x - v1.x, v0.y - v1.y);
-            }
-            wave_sync();
-            float2 *tmp = src; src = dst; dst = tmp;
-        }
+        gen_stockham<M>(src, dst, tw_p, lane);
 
         // real-FFT split + power spectrum (cells 20, 22): P[k], k = 0..M, into dst (as floats)
         float *P = reinterpret_cast<float *>(dst);
         for (int k = lane; k <= M; k += 64) {
-            float2 a = src[k & (M - 1)];
-            float2 b = src[(M - k) & (M - 1)];
-            float er = 0.5f * (a.x + b.x), ei = 0.5f * (a.y - b.y);      // E = (a + conj b)/2
-            float dr = a.x - b.x, di = a.y + b.y;                         // a - conj b
-            float orr = 0.5f * di, oi = -0.5f * dr;                       // O = -i/2 (a - conj b)
-            float2 w = tws_p[k];
-            float xr = er + (w.x * orr - w.y * oi);
-            float xi = ei + (w.x * oi + w.y * orr);
-            P[k] = (k == 0 && t.window_d) ? (float)(dc * dc) : xr * xr + xi * xi;
+            const float p = gen_split_power<M>(src, tws_p, k);
+            P[k] = (k == 0 && t.window_d) ? (float)(dc * dc) : p;
         }
         wave_sync();
 

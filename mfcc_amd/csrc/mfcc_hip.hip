@@ -39,6 +39,7 @@
 #include "kernel_gate.hpp"
 #include "kernel_decode.hpp"
 #include "kernel_resample.hpp"
+#include "kernel_spectrum.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -53,10 +54,15 @@ struct Resolved {
     int frame_len;             // samples of a frame (hop <= frame_len <= nfft); the window's length.  nfft: a plain handle
     int mel_kind;              // enum mfcc_hip_mel_kind (mfcc_hip_create_banked); NOTEBOOK: the reference's bank
     double mel_lo, mel_hi;     // HTK: the band edges in Hz, mel_hi effective (never 0); NOTEBOOK: both 0
+    bool spectrum = false;     // set for the scope of a mfcc_hip_spectrum_* call (SpectrumGuard): the float routes write
+                               // power-spectrum rows
 };
 
-// width of an output row: n_mel log-mel values or n_cep coefficients
-inline size_t row_width(const Resolved &r) { return size_t(r.output == MFCC_HIP_OUTPUT_LOGMEL ? r.n_mel : r.n_cep); }
+// width of an output row: n_mel log-mel values or n_cep coefficients; nfft / 2 + 1 bins inside a spectrum call
+inline size_t row_width(const Resolved &r) {
+    if (r.spectrum) return size_t(mfcc_spec::bins(r.nfft));
+    return size_t(r.output == MFCC_HIP_OUTPUT_LOGMEL ? r.n_mel : r.n_cep);
+}
 inline bool is_logmel(const Resolved &r) { return r.output == MFCC_HIP_OUTPUT_LOGMEL; }
 
 // The kernel a handle's float calls run; build_tables decides it when the handle is made.
@@ -228,6 +234,10 @@ struct mfcc_hip_handle {
     mfcc_fused::FusedTables fu{};
     mfcc_fused160mb::Tables fmb{};
     mfcc_fixed512::Tables x5{};
+    // the power-spectrum output (mfcc_hip_spectrum_*): the kernel of every such call (spectrum_plan.hpp: choose) and the
+    // tables of the fused one
+    mfcc_spec::Kernel spec_kernel = mfcc_spec::Kernel::kGeneric;
+    mfcc_spec::FusedTables sf{};
     // the 1024 forms: one of the two is bound, the one float_kernel names
     mfcc_fused1024::Tables f1k{};          // bf16-split contraction, set lists for every rate (kernel_fused1024.hpp)
     mfcc_fused1024_f32::Tables f1k_f32{};  // fp32 contraction, one MFMA list per rate (kernel_fused1024_f32.hpp)
@@ -489,6 +499,35 @@ struct PlainInputGuard {
     PlainInputGuard &operator=(const PlainInputGuard &) = delete;
 };
 
+// The handle as a spectrum handle for the scope of a mfcc_hip_spectrum_* call: rows of nfft / 2 + 1 power values out of
+// the float routes (launch() runs the spectrum kernel, row_width() is the bin count), and nothing behind the kernel --
+// the output kind, normalization, deltas, PCEN and the VAD do not apply to the spectrum and are put back afterwards.
+// The sample format and the input rate stay: they say what a sample pointer holds
+struct SpectrumGuard {
+    mfcc_hip_handle *h;
+    int output, norm, delta_order, vad_mode;
+    bool pcen_on;
+    explicit SpectrumGuard(mfcc_hip_handle *hh)
+        : h(hh), output(hh->r.output), norm(hh->norm), delta_order(hh->delta_order), vad_mode(hh->vad_mode), pcen_on(hh->pcen_on) {
+        h->r.spectrum = true;
+        h->r.output = MFCC_HIP_OUTPUT_CEPSTRA;
+        h->norm = MFCC_HIP_NORMALIZE_NONE;
+        h->delta_order = 0;
+        h->vad_mode = MFCC_HIP_VAD_OFF;
+        h->pcen_on = false;
+    }
+    ~SpectrumGuard() {
+        h->r.spectrum = false;
+        h->r.output = output;
+        h->norm = norm;
+        h->delta_order = delta_order;
+        h->vad_mode = vad_mode;
+        h->pcen_on = pcen_on;
+    }
+    SpectrumGuard(const SpectrumGuard &) = delete;
+    SpectrumGuard &operator=(const SpectrumGuard &) = delete;
+};
+
 struct Arena {
     std::vector<char> host;
     template <typename T>
@@ -632,6 +671,14 @@ int build_tables(mfcc_hip_handle *h) {
     }
     size_t o_f1k = 0;
     if (have_1k) o_f1k = a.put(f1k_blob);
+    // ---- the power-spectrum kernels: the generic one reads the float tables above; the fused one has a blob of its own
+    h->spec_kernel = mfcc_spec::choose(r.nfft, r.hop, r.frame_len, r.float_impl == MFCC_HIP_IMPL_GENERIC);
+    std::vector<char> spec_blob;
+    size_t o_spec = 0;
+    if (h->spec_kernel == mfcc_spec::Kernel::kFused512) {
+        mfcc_spec::build_tables(wd, spec_blob);
+        o_spec = a.put(spec_blob);
+    }
 
     HIP_TRY(h, hipMalloc(&h->arena, a.host.size() + 256));
     HIP_TRY(h, hipMemcpy(h->arena, a.host.data(), a.host.size(), hipMemcpyHostToDevice));
@@ -671,6 +718,7 @@ int build_tables(mfcc_hip_handle *h) {
         if (f1k_fp32) mfcc_fused1024_f32::bind_tables(b + o_f1k, r.n_cep, f1k_var, h->f1k_f32);
         else mfcc_fused1024::bind_tables(b + o_f1k, r.n_cep, f1k_var, h->f1k);
     }
+    if (h->spec_kernel == mfcc_spec::Kernel::kFused512) mfcc_spec::bind_tables(b + o_spec, r.power_scale, h->sf);
     if (have_fixed512) {
         mfcc_fixed512::bind_tables(b + o_x5, h->x5);
         h->x5.tw64a = x5_tw[0]; h->x5.tw64b = x5_tw[1]; h->x5.tw192a = x5_tw[2]; h->x5.tw192b = x5_tw[3];
@@ -751,7 +799,16 @@ int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t s
     DeviceGuard guard(h->device);
     const long long total = s.total_frames;
     const bool logmel = is_logmel(h->r);
-    if (fixed && h->fixed_kernel == FixedKernel::kFixed512) {
+    if (!fixed && h->r.spectrum) {
+        // a spectrum call (SpectrumGuard): the fused kernel, or the generic one where the problem does not fit its tiles
+        float *o = static_cast<float *>(d_out);
+        if (reinterpret_cast<uintptr_t>(o) & 3) return MFCC_HIP_ERROR_INVALID_PARAM;
+        if (h->spec_kernel != mfcc_spec::Kernel::kFused512 || !mfcc_spec::launch_fused(s, h->sf, o, h->n_cu, h->stream)) {
+            const mfcc_spec::GenericTables gt{h->ft.window, h->ft.tw_fft, h->ft.tw_split,
+                                              float(1.0 / (h->r.power_scale * h->r.power_scale))};
+            if (!mfcc_spec::launch_generic(s, gt, h->r.nfft, o, h->n_cu, h->stream)) return MFCC_HIP_ERROR_UNSUPPORTED;
+        }
+    } else if (fixed && h->fixed_kernel == FixedKernel::kFixed512) {
         mfcc_fixed512::launch(s, h->x5, static_cast<int16_t *>(d_out), h->n_cu, h->stream);
     } else if (fixed) {
         long long blocks = (total + mfcc_k::kWavesPerBlock - 1) / mfcc_k::kWavesPerBlock;
@@ -1522,7 +1579,8 @@ int ragged_launch(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const si
     using mfcc_batch::Records;
     using mfcc_batch::Route;
     Records kernel = Records::kNone;        // what the kernel of this call reads utterances from
-    if (!fixed && h->float_kernel == FloatKernel::kFused512W12 && std::is_same<OutT, float>::value) kernel = Records::kTiles;
+    if (!fixed && !h->r.spectrum && h->float_kernel == FloatKernel::kFused512W12 && std::is_same<OutT, float>::value)
+        kernel = Records::kTiles;                 // (a spectrum call packs: its kernels take no tile records)
     if (fixed && h->fixed_kernel == FixedKernel::kFixed512 && std::is_same<OutT, int16_t>::value) kernel = Records::kFrames;
     const Route route = mfcc_batch::route(kernel, fixed, sc, n_utt);
     // Checked first: this is the per-step host work of a sharded corpus (BASELINE config 5: 10 000 x 10 s; bench.py
@@ -2215,6 +2273,44 @@ int mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n
     *avg_ms = ms / float(iters);
     return MFCC_HIP_SUCCESS;
 }
+
+// ---- the power-spectrum output (include/mfcc_hip.h: "power spectrum"; kernel_spectrum.hpp, spectrum_plan.hpp; DESIGN.md
+// section 4.18): the float entry points' own routes with the handle as a spectrum handle for the call (SpectrumGuard)
+int mfcc_hip_spectrum_bins(const mfcc_hip_params *p, size_t *bins) {
+    Resolved r;
+    const int rc = resolve(p, r);
+    if (rc || !bins) return rc ? rc : MFCC_HIP_ERROR_INVALID_PARAM;
+    *bins = size_t(mfcc_spec::bins(r.nfft));
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_spectrum_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo,
+                              void *d_out, size_t *n_frames) {
+    if (!h || !mfcc_spec::call_fits(n, nch, size_t(mfcc_spec::bins(h->r.nfft)))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    SpectrumGuard spectrum(h);
+    return dense_dev(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
+}
+
+int mfcc_hip_spectrum_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const size_t *offsets, size_t n_utt, void *d_out,
+                                     size_t cap, size_t *frame_offsets) {
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    // the row count times the bins must fit (decreasing offsets are the route's to refuse)
+    if (offsets && n_utt && offsets[n_utt] >= offsets[0] &&
+        !mfcc_spec::ragged_fits(offsets[n_utt] - offsets[0], n_utt, size_t(mfcc_spec::bins(h->r.nfft))))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    SpectrumGuard spectrum(h);
+    return process_ragged_dev<float>(h, false, static_cast<const int16_t *>(d_pcm), offsets, n_utt, static_cast<float *>(d_out),
+                                     cap, frame_offsets);
+}
+
+int mfcc_hip_spectrum_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_t nch, float *out, size_t cap,
+                          size_t *n_frames) {
+    if (!h || !mfcc_spec::call_fits(n, nch, size_t(mfcc_spec::bins(h->r.nfft)))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    SpectrumGuard spectrum(h);
+    return process_host<float>(h, false, pcm, n, nch, out, cap, n_frames);
+}
+
+const char *mfcc_hip_spectrum_kernel_name(const mfcc_hip_handle *h) { return h ? mfcc_spec::name_of(h->spec_kernel) : ""; }
 
 int mfcc_hip_set_normalize(mfcc_hip_handle *h, int mode) {
     if (!h || mode < MFCC_HIP_NORMALIZE_NONE || mode > MFCC_HIP_NORMALIZE_MEAN_VAR) return MFCC_HIP_ERROR_INVALID_PARAM;
