@@ -349,6 +349,84 @@ int  mfcc_hip_spectrum_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n_samp
  * every packed frame x bins floats. */
 const char *mfcc_hip_spectrum_kernel_name(const mfcc_hip_handle *h);
 
+/* ---- filterbank -------------------------------------------------------------------------------------------------
+ * A handle may carry a FILTER MATRIX W [n_bands][bins]: float32, given by the caller from host memory, with
+ * bins = nfft / 2 + 1 and 1 <= n_bands <= MFCC_HIP_MAX_FBANK_BANDS = 128.  Every weight is finite and not negative
+ * (-0.0 counts as 0); anything else is MFCC_HIP_ERROR_INVALID_PARAM.  Row f of a channel, element j:
+ *
+ *     E[f][j] = sum_k W[j][k] * P[f][k]        P: the power-spectrum row of section "power spectrum", exactly that contract
+ *     y[f][j] = E                               scale ENERGY
+ *               c * log2(max(E, floor))         scale LOG2 (c = 1), LN (c = (float)ln 2), LOG10 (c = (float)log10 2)
+ *
+ * log2 is v_log_f32, the log the mel kernels use, and there is one fp32 multiply by c.  floor is fp32, finite and >= 0;
+ * with floor = 0, E = 0 gives -inf, as the log-mel output does.  Framing, window, pre-emphasis, padding, halo, sample
+ * format and input rate are the handle's, as for mfcc_hip_spectrum_*.  The handle's n_mel, n_cep, output, lifter, mel
+ * bank, normalization, deltas, PCEN and VAD do NOT apply.  Weight on bin 0 and on bin nfft / 2 is allowed.
+ *
+ * Two results are bit-exact: a band whose row of W is all zero gives E = +0.0 in every frame, and a frame whose samples
+ * (and history sample) are all zero gives E = +0.0 in every band.  Every other value is finite and >= 0 in ENERGY scale
+ * (as long as the sum itself stays inside fp32).
+ *
+ * The rows of a segment are the same bits from the dense, ragged and host-buffer entries, and from any chunking of the
+ * copy pipeline.  The two kernels agree within the error bound, not bit for bit.  E is the
+ * fp32 chain fmaf(W[j][k], P[k], acc) over k from the band's first to its last non-zero bin, ascending, with one
+ * exception: at the shapes of "mfcc_fbank512_kernel", a matrix whose bands' first-to-last-non-zero ranges add up to more
+ * than 3072 bins (a dense or learned matrix, filters with long tails) is contracted on the matrix cores, weights and
+ * power each split into two bfloat16 terms and summed in fp32, about 2^-16 relative per band instead of 2^-24 per bin.
+ * Where that is not wanted, MFCC_HIP_IMPL_GENERIC keeps the fp32 chain at about a third of the rate.
+ *
+ * There is no fixed-point form and there are no sessions or banks.  The post-pass direct entries (mfcc_hip_normalize_dev,
+ * mfcc_hip_deltas_dev, mfcc_hip_pcen_dev, mfcc_hip_vad_dev) keep their width limit of 64: rows of up to 64 bands may be
+ * fed to them by the caller; wider post-passes do not exist.  The parameter block, ABI version 2, n_mel 1..64 and every
+ * limit of 64 are unchanged. */
+#define MFCC_HIP_MAX_FBANK_BANDS 128
+
+enum mfcc_hip_fbank_scale {
+    MFCC_HIP_FBANK_ENERGY = 0,
+    MFCC_HIP_FBANK_LOG2 = 1,
+    MFCC_HIP_FBANK_LN = 2,
+    MFCC_HIP_FBANK_LOG10 = 3
+};
+
+typedef struct mfcc_hip_fbank {
+    uint32_t struct_size;      /* sizeof(mfcc_hip_fbank) */
+    int32_t  n_bands;          /* 1 .. MFCC_HIP_MAX_FBANK_BANDS */
+    int32_t  scale;            /* enum mfcc_hip_fbank_scale */
+    float    floor;            /* the log scales' floor: finite, >= 0 */
+    int32_t  reserved[4];      /* must be 0 */
+} mfcc_hip_fbank;
+
+/* Sets (replaces) the handle's filter matrix: validates, builds the kernels' tables on the host and uploads them.
+ * weights: [p->n_bands][nfft / 2 + 1] float32 in host memory, read before the call returns.  p == NULL removes the
+ * matrix (weights is ignored).  A wrong struct_size, non-zero reserved words, n_bands out of range, an unknown scale, a
+ * bad floor, a bad weight or weights == NULL: MFCC_HIP_ERROR_INVALID_PARAM, and the handle keeps what it had.  Calls
+ * enqueued earlier, on any stream the handle had, keep their matrix: replacing or removing a matrix that a call has
+ * used SYNCHRONIZES THE DEVICE (hipDeviceSynchronize) before the old tables are freed; its error is returned as
+ * MFCC_HIP_ERROR_OTHER and the handle keeps what it had. */
+int  mfcc_hip_set_fbank(mfcc_hip_handle *h, const mfcc_hip_fbank *p, const float *weights);
+/* bands of the handle's matrix; 0 when none is set */
+int  mfcc_hip_fbank_bands(const mfcc_hip_handle *h, size_t *n_bands);
+/* The three compute entries: arguments, frame counts, halo rule, MFCC_HIP_ERROR_BUFFER_SMALL with frame_offsets filled,
+ * stream behaviour and refusals of mfcc_hip_spectrum_i16_dev, mfcc_hip_spectrum_ragged_i16_dev and mfcc_hip_spectrum_i16;
+ * rows are n_bands wide.  A handle without a matrix: MFCC_HIP_ERROR_UNSUPPORTED. */
+int  mfcc_hip_fbank_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n_samples_per_ch, size_t ch_stride_samples,
+                            size_t n_channels, int halo, void *d_out, size_t *n_frames);
+int  mfcc_hip_fbank_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const size_t *offsets, size_t n_utterances,
+                                   void *d_out, size_t out_capacity, size_t *frame_offsets);
+int  mfcc_hip_fbank_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n_samples_per_ch, size_t n_channels, float *out,
+                        size_t out_capacity, size_t *n_frames);
+/* the kernel the handle's filterbank calls run: "mfcc_fbank512_kernel" (nfft 512 at hop 170 with the full frame, or at
+ * hop 160 with any frame of 160 .. 512 samples), "mfcc_fbank_generic_kernel", or "" when no matrix is set.  float_impl =
+ * MFCC_HIP_IMPL_GENERIC selects the generic kernel; a call that does not fit the fused kernel's 32-bit tile arithmetic
+ * runs the generic kernel without an error, as for the spectrum. */
+const char *mfcc_hip_fbank_kernel_name(const mfcc_hip_handle *h);
+/* Host only: the matrix of the MFCC_HIP_MEL_HTK contract (mfcc_hip_create_banked) for 1 .. 128 bands, [n_bands][nfft / 2
+ * + 1] float32; high_hz 0 means sample_rate / 2.  For n_bands <= 64 these are the bits of MFCC_HIP_TABLE_MEL_DENSE_F32 of
+ * an HTK handle.  n_floats (optional) receives the count; out may be NULL to ask for it; cap_floats too small:
+ * MFCC_HIP_ERROR_BUFFER_SMALL. */
+int  mfcc_hip_htk_weights(int nfft, int sample_rate, int n_bands, float low_hz, float high_hz, float *out,
+                          size_t cap_floats, size_t *n_floats);
+
 /* ---- per-segment normalization (enum mfcc_hip_normalize) -------------------------------------------------------
  * The handle's mode applies to every float call enqueued after it: mfcc_hip_process_i16, mfcc_hip_process_i16_dev,
  * both float mfcc_hip_process_ragged_* entry points and mfcc_hip_time_dev (which then times the launch AND the

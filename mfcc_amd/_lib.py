@@ -114,6 +114,20 @@ class Pcen(C.Structure):
     ]
 
 
+class Fbank(C.Structure):
+    """struct mfcc_hip_fbank"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_bands", C.c_int32),
+        ("scale", C.c_int32),
+        ("floor", C.c_float),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
+MAX_FBANK_BANDS = 128
+FBANK_ENERGY, FBANK_LOG2, FBANK_LN, FBANK_LOG10 = 0, 1, 2, 3
+
 PCEN_TILE = 128
 
 Handle = C.c_void_p           # what a create call fills in: Handle(), passed with byref
@@ -266,6 +280,15 @@ SYMBOLS = {
                                                    C.c_void_p]),
     "mfcc_hip_spectrum_i16": (C.c_int, [_H, C.c_void_p, _SZ, _SZ, C.c_void_p, _SZ, _PSZ]),
     "mfcc_hip_spectrum_kernel_name": (C.c_char_p, [_H]),
+    # the filterbank output: the matrix, the three compute entries, the kernel's name and the host-only HTK matrix
+    "mfcc_hip_set_fbank": (C.c_int, [_H, C.POINTER(Fbank), C.c_void_p]),
+    "mfcc_hip_fbank_bands": (C.c_int, [_H, _PSZ]),
+    "mfcc_hip_fbank_i16_dev": (C.c_int, [_H, C.c_void_p, _SZ, _SZ, _SZ, C.c_int, C.c_void_p, _PSZ]),
+    "mfcc_hip_fbank_ragged_i16_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                C.c_void_p]),
+    "mfcc_hip_fbank_i16": (C.c_int, [_H, C.c_void_p, _SZ, _SZ, C.c_void_p, _SZ, _PSZ]),
+    "mfcc_hip_fbank_kernel_name": (C.c_char_p, [_H]),
+    "mfcc_hip_htk_weights": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, _SZ, _PSZ]),
 }
 
 _lib = None

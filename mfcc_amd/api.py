@@ -288,6 +288,51 @@ def spectrum_bins(**kw) -> int:
     return int(out.value)
 
 
+_FBANK_SCALES = {"energy": _lib.FBANK_ENERGY, "log2": _lib.FBANK_LOG2, "ln": _lib.FBANK_LN, "log10": _lib.FBANK_LOG10}
+
+
+def htk_filterbank(n_bands, nfft=512, samplerate=16000, fmin=0.0, fmax=None) -> np.ndarray:
+    """The HTK-style mel matrix of ``MFCC(mel="htk")`` for 1..128 bands: float32 ``(n_bands, nfft // 2 + 1)``, triangles
+    on the mel axis ``1127 ln(1 + f / 700)`` between ``fmin`` and ``fmax`` (default: ``samplerate / 2``), no area
+    normalisation (host-only).  What ``MFCC.set_filterbank`` takes; up to 64 bands it is ``get_table`` of an HTK handle
+    bit for bit."""
+    if float(samplerate) != int(samplerate):
+        raise ValueError("samplerate must be an integer, not %r" % (samplerate,))
+    lib = _lib.load()
+    n = C.c_size_t(0)
+    args = (int(nfft), int(samplerate), int(n_bands), float(fmin), 0.0 if fmax is None else float(fmax))
+    _lib.check(lib.mfcc_hip_htk_weights(*args, None, 0, C.byref(n)), "htk_filterbank")
+    out = np.empty(n.value, dtype=np.float32)
+    _lib.check(lib.mfcc_hip_htk_weights(*args, ptr(out), out.size, C.byref(n)), "htk_filterbank")
+    return out.reshape(int(n_bands), int(nfft) // 2 + 1)
+
+
+def _fbank_args(weights, scale, floor, bins):
+    """``(struct mfcc_hip_fbank, contiguous float32 (n_bands, bins) host array)`` of ``MFCC.set_filterbank``'s arguments,
+    or ValueError / TypeError: the checks the library makes too, with words."""
+    if _is_torch(weights):
+        weights = weights.detach().cpu().numpy()
+    w = np.asarray(weights)
+    if w.dtype.kind not in "fiu":
+        raise TypeError("weights must be a real array, not %s" % w.dtype)
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    if w.ndim != 2 or w.shape[1] != bins:
+        raise ValueError("weights must have shape (n_bands, %d), not %s" % (bins, w.shape))
+    if not 1 <= w.shape[0] <= _lib.MAX_FBANK_BANDS:
+        raise ValueError("n_bands must be 1..%d, not %d" % (_lib.MAX_FBANK_BANDS, w.shape[0]))
+    if not np.isfinite(w).all() or bool((w < 0).any()):
+        raise ValueError("every weight must be finite and not negative")
+    if scale not in _FBANK_SCALES:
+        raise ValueError("scale must be one of %s, not %r" % (sorted(_FBANK_SCALES), scale))
+    floor = float(floor)
+    if not 0.0 <= floor <= float(np.finfo(np.float32).max):
+        raise ValueError("floor must be finite and >= 0, not %r" % (floor,))
+    p = _lib.Fbank()
+    p.struct_size = C.sizeof(_lib.Fbank)
+    p.n_bands, p.scale, p.floor = w.shape[0], _FBANK_SCALES[scale], floor
+    return p, w
+
+
 _TABLE_DTYPES = {
     _lib.TABLE_WINDOW_F32: np.float32, _lib.TABLE_MEL_POINTS_I32: np.int32,
     _lib.TABLE_MEL_DENSE_F32: np.float32, _lib.TABLE_DCT_F32: np.float32,
@@ -739,8 +784,26 @@ class MFCC(_Owner):
         """Width of a ``power_spectrum`` row: ``nfft // 2 + 1``."""
         return int(self.nfft) // 2 + 1
 
-    def _row(self, fixed, spectrum=False):
-        return self.num_bins if spectrum else self.nceptrums if fixed else self.num_features
+    @property
+    def num_bands(self) -> int:
+        """Width of a ``filterbank`` row: the bands of the matrix ``set_filterbank`` gave, 0 without one."""
+        n = C.c_size_t(0)
+        _lib.check(self._lib.mfcc_hip_fbank_bands(self._h, C.byref(n)), "fbank_bands")
+        return int(n.value)
+
+    _ENTRIES = (None, "spectrum", "fbank")
+
+    def _row(self, fixed, entry=None):
+        """Width of a row.  ``entry`` names the family of entry points a call goes to, here and in ``_host``, ``_dev``
+        and ``_packed``: None (``process``), ``"spectrum"`` (``power_spectrum``) or ``"fbank"`` (``filterbank``) -- the
+        word between ``mfcc_hip_`` and ``_i16`` in the C names."""
+        if entry not in self._ENTRIES:
+            raise ValueError("unknown entry %r" % (entry,))
+        if entry == "fbank":
+            return self.num_bands
+        if entry == "spectrum":
+            return self.num_bins
+        return self.nceptrums if fixed else self.num_features
 
     def num_frames(self, n_samples) -> int:
         """Frames of ``n_samples`` samples of one channel or utterance (at ``input_rate`` where one is set)."""
@@ -776,7 +839,7 @@ class MFCC(_Owner):
         _lib.check(self._lib.mfcc_hip_synchronize(self._h))
 
     # -- the hot path ---------------------------------------------------------------
-    def _host(self, pcm, fixed, spectrum=False):
+    def _host(self, pcm, fixed, entry=None):
         pcm = _host_samples(pcm, self.sample_format, "pcm")
         squeeze = pcm.ndim == 1
         if squeeze:
@@ -785,16 +848,16 @@ class MFCC(_Owner):
             raise ValueError("pcm must be (n,) or (channels, n)")
         nch, n = pcm.shape
         nf = self.num_frames(n)
-        out = np.empty((nch, nf, self._row(fixed, spectrum)), dtype=np.int16 if fixed else np.float32)
+        out = np.empty((nch, nf, self._row(fixed, entry)), dtype=np.int16 if fixed else np.float32)
         got = C.c_size_t(0)
-        fn = (self._lib.mfcc_hip_spectrum_i16 if spectrum else
+        fn = (getattr(self._lib, "mfcc_hip_%s_i16" % entry) if entry else
               self._lib.mfcc_hip_process_fixed_i16 if fixed else self._lib.mfcc_hip_process_i16)
         _lib.check(fn(self._h, ptr(pcm), n, nch, ptr(out), out.size, C.byref(got)),
-                   "spectrum" if spectrum else "process" if not self.vad else self._DENSE_VAD)
+                   entry if entry else "process" if not self.vad else self._DENSE_VAD)
         assert got.value == nf
         return out[0] if squeeze else out
 
-    def _dev(self, pcm, fixed, halo, out, spectrum=False):
+    def _dev(self, pcm, fixed, halo, out, entry=None):
         import torch
         if not self._samples_dev_ok(pcm):
             raise TypeError("device path needs a %s tensor" % self._dev_what())
@@ -810,13 +873,14 @@ class MFCC(_Owner):
         nf = self.num_frames(n)
         self._check_device(pcm)
         odt = torch.int16 if fixed else torch.float32
-        row = self._row(fixed, spectrum)
+        row = self._row(fixed, entry)
         want = (nf, row) if squeeze and out is not None and out.dim() == 2 else (nch, nf, row)
         out = _out(pcm, out, want, odt, lambda: torch.empty(want, device=pcm.device, dtype=odt))
         got = C.c_size_t(0)
-        self._call(pcm.device, "spectrum_i16_dev" if spectrum else "process_fixed_i16_dev" if fixed else "process_i16_dev",
+        self._call(pcm.device, entry + "_i16_dev" if entry else
+                   "process_fixed_i16_dev" if fixed else "process_i16_dev",
                    self._h, ptr(pcm), n, pcm.stride(0), nch, int(halo), ptr(out), C.byref(got),
-                   what="spectrum_dev" if spectrum else "process_dev" if not self.vad else self._DENSE_VAD)
+                   what=entry + "_dev" if entry else "process_dev" if not self.vad else self._DENSE_VAD)
         if squeeze and out.dim() == 3:
             return out[0]
         return out
@@ -880,17 +944,52 @@ class MFCC(_Owner):
         output kind, normalization, deltas, PCEN and VAD do not apply: ``torch.matmul(rows, W.T)`` with any mel matrix
         ``W`` gives the band energies."""
         if _is_torch(pcm):
-            return self._dev(pcm, False, halo, out, spectrum=True)
+            return self._dev(pcm, False, halo, out, entry="spectrum")
         if halo:
             raise ValueError("halo is only available on the device path")
         if out is not None:
             raise ValueError("out is only available on the device path")
-        return self._host(pcm, False, spectrum=True)
+        return self._host(pcm, False, entry="spectrum")
 
     def power_spectrum_packed(self, flat, offsets, out=None):
         """``power_spectrum`` of a corpus that lies in HBM, as ``process_packed`` takes it: ``(rows, frame_offsets)`` with
         ``rows`` the dense ``(sum frames, nfft // 2 + 1)`` tensor, bit-identical to one ``power_spectrum`` per utterance."""
-        return self._packed(flat, offsets, False, out, True)
+        return self._packed(flat, offsets, False, out, "spectrum")
+
+    def set_filterbank(self, weights, scale="log2", floor=0.0):
+        """Give the handle a filter matrix for ``filterbank``: ``weights`` a NumPy array or a torch tensor of shape
+        ``(n_bands, nfft // 2 + 1)``, 1..128 bands, every weight finite and not negative (copied to the host once, as
+        float32); ``scale`` one of ``"energy"``, ``"log2"``, ``"ln"``, ``"log10"``; ``floor`` the log scales' floor
+        (finite, >= 0; with 0 an empty band gives ``-inf``).  ``None`` removes the matrix.  Calls enqueued before keep the
+        matrix they were enqueued with."""
+        if weights is None:
+            _lib.check(self._lib.mfcc_hip_set_fbank(self._h, None, None), "set_fbank")
+            return
+        p, w = _fbank_args(weights, scale, floor, self.num_bins)
+        _lib.check(self._lib.mfcc_hip_set_fbank(self._h, C.byref(p), ptr(w)), "set_fbank")
+
+    def filterbank_kernel_name(self) -> str:
+        """The kernel ``filterbank`` runs: ``mfcc_fbank512_kernel``, ``mfcc_fbank_generic_kernel``, or ``""`` without a
+        matrix."""
+        return self._lib.mfcc_hip_fbank_kernel_name(self._h).decode()
+
+    def filterbank(self, pcm, halo=0, out=None):
+        """Band energies under the matrix of ``set_filterbank``: PCM ``(n,)`` / ``(channels, n)`` in the handle's sample
+        format and rate -> float32 ``(.., frames, num_bands)``, row ``f`` = ``W @ power_spectrum row f`` in the matrix's
+        scale, contracted on the chip.  Arguments, device checks, streams and ``out`` as for ``power_spectrum``.  The
+        handle's own filterbank, output kind, normalization, deltas, PCEN and VAD do not apply."""
+        if _is_torch(pcm):
+            return self._dev(pcm, False, halo, out, entry="fbank")
+        if halo:
+            raise ValueError("halo is only available on the device path")
+        if out is not None:
+            raise ValueError("out is only available on the device path")
+        return self._host(pcm, False, entry="fbank")
+
+    def filterbank_packed(self, flat, offsets, out=None):
+        """``filterbank`` of a corpus that lies in HBM, as ``power_spectrum_packed`` takes it: ``(rows, frame_offsets)``
+        with ``rows`` the dense ``(sum frames, num_bands)`` tensor, bit-identical to one ``filterbank`` per utterance."""
+        return self._packed(flat, offsets, False, out, "fbank")
 
     def process_fixed(self, pcm, halo=0, out=None):
         """Fixed contract (RTL arithmetic): int16 PCM -> int16 coefficients, bit-exact."""
@@ -949,9 +1048,9 @@ class MFCC(_Owner):
         result tensor and the row range of every utterance (``out[fo[u]:fo[u + 1]]``).  Equal-length utterances run
         as channels of one multi-channel launch (no packing copy); the bits are the same.  On a ``vad="select"`` handle
         ``out`` still needs room for every frame; what is returned is ``(out[:fo[-1]], fo)``, the voiced rows."""
-        return self._packed(flat, offsets, fixed, out, False)
+        return self._packed(flat, offsets, fixed, out, None)
 
-    def _packed(self, flat, offsets, fixed, out, _spectrum):
+    def _packed(self, flat, offsets, fixed, out, entry):
         """``process_packed`` and ``power_spectrum_packed``: the checks, the output and the ragged device entry."""
         import torch
         if not self._samples_dev_ok(flat) or flat.dim() != 1 or not flat.is_contiguous():
@@ -971,12 +1070,13 @@ class MFCC(_Owner):
             uniq, counts = np.unique(lens, return_counts=True)
             nf = int(sum(self.num_frames(int(v)) * int(c) for v, c in zip(uniq, counts)))
         odt = torch.int16 if fixed else torch.float32
-        row = self._row(fixed, _spectrum)
+        row = self._row(fixed, entry)
         out = _out(flat, out, (nf, row), odt, lambda: torch.empty((nf, row), device=flat.device, dtype=odt))
-        name = "spectrum_ragged_i16_dev" if _spectrum else "process_ragged_fixed_i16_dev" if fixed else "process_ragged_i16_dev"
+        name = (entry + "_ragged_i16_dev" if entry else
+                "process_ragged_fixed_i16_dev" if fixed else "process_ragged_i16_dev")
         self._call(flat.device, name, self._h, ptr(flat), ptr(offsets), n, ptr(out), out.numel(), ptr(fo),
-                   what="spectrum_ragged_dev" if _spectrum else "process_ragged_dev")
-        if self.vad and not fixed and not _spectrum:
+                   what=entry + "_ragged_dev" if entry else "process_ragged_dev")
+        if self.vad and not fixed and not entry:
             return out[:int(fo[-1])], fo                 # the voiced rows; the entry point has waited for the stream
         assert int(fo[-1]) == nf
         return out, fo

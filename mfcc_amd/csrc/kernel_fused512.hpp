@@ -970,7 +970,10 @@ void mfcc_fused512_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, flo
 
 inline const char *kernel_name() { return "mfcc_fused512_kernel"; }
 
-// returns false when the problem does not fit the kernel's 32-bit tile arithmetic
+// returns false when the problem does not fit the kernel's 32-bit tile arithmetic.  A translation unit that wants this
+// header's device helpers and tables but not its kernels (fbank.hip) defines MFCC_NO_LAUNCHERS: a launcher names its
+// kernels, and that alone instantiates them into the unit's code object
+#ifndef MFCC_NO_LAUNCHERS
 inline bool launch(const mfcc_k::StreamDesc &s, const FusedTables &t, bool dense, float *out, int n_cu,
                    hipStream_t stream) {
     const bool dcx = t.win_dc != nullptr;        // only ever set together with the dense schedule
@@ -985,5 +988,6 @@ inline bool launch(const mfcc_k::StreamDesc &s, const FusedTables &t, bool dense
         hipLaunchKernelGGL((mfcc_fused512_kernel<false, false>), dim3(grid), dim3(64 * kWaves), 0, stream, s, t, g, out);
     return true;
 }
+#endif  // MFCC_NO_LAUNCHERS
 
 }  // namespace mfcc_fused

@@ -108,6 +108,7 @@ __global__ __launch_bounds__(mfcc_k::kBlock) void mfcc_spectrum_generic_kernel(m
 inline const char *generic_name() { return name_of(Kernel::kGeneric); }
 
 // false: an nfft the library does not take
+#ifndef MFCC_NO_LAUNCHERS          // kernel_fused512.hpp: launch
 inline bool launch_generic(const mfcc_k::StreamDesc &s, const GenericTables &t, int nfft, float *out, int n_cu,
                            hipStream_t stream) {
     long long blocks = (s.total_frames + mfcc_k::kWavesPerBlock - 1) / mfcc_k::kWavesPerBlock;
@@ -130,6 +131,7 @@ inline bool launch_generic(const mfcc_k::StreamDesc &s, const GenericTables &t, 
     }
     return true;
 }
+#endif
 
 // ------------------------------------------------------------------------------ fused 512
 
@@ -333,6 +335,7 @@ void mfcc_spectrum512_kernel(const mfcc_k::StreamDesc s, const FusedTables t, co
 inline const char *fused_name() { return name_of(Kernel::kFused512); }
 
 // false: the problem does not fit the kernel's 32-bit tile arithmetic (the caller runs the generic kernel)
+#ifndef MFCC_NO_LAUNCHERS
 inline bool launch_fused(const mfcc_k::StreamDesc &s, const FusedTables &t, float *out, int n_cu, hipStream_t stream) {
     LaunchGeom g;
     unsigned grid;
@@ -345,5 +348,6 @@ inline bool launch_fused(const mfcc_k::StreamDesc &s, const FusedTables &t, floa
         return false;
     return true;
 }
+#endif
 
 }  // namespace mfcc_spec

@@ -40,6 +40,7 @@
 #include "kernel_decode.hpp"
 #include "kernel_resample.hpp"
 #include "kernel_spectrum.hpp"
+#include "kernel_fbank.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -56,10 +57,13 @@ struct Resolved {
     double mel_lo, mel_hi;     // HTK: the band edges in Hz, mel_hi effective (never 0); NOTEBOOK: both 0
     bool spectrum = false;     // set for the scope of a mfcc_hip_spectrum_* call (SpectrumGuard): the float routes write
                                // power-spectrum rows
+    int fbank = 0;             // the band count for the scope of a mfcc_hip_fbank_* call (FbankGuard), else 0: the float
+                               // routes write filterbank rows
 };
 
 // width of an output row: n_mel log-mel values or n_cep coefficients; nfft / 2 + 1 bins inside a spectrum call
 inline size_t row_width(const Resolved &r) {
+    if (r.fbank) return size_t(r.fbank);
     if (r.spectrum) return size_t(mfcc_spec::bins(r.nfft));
     return size_t(r.output == MFCC_HIP_OUTPUT_LOGMEL ? r.n_mel : r.n_cep);
 }
@@ -238,6 +242,14 @@ struct mfcc_hip_handle {
     // tables of the fused one
     mfcc_spec::Kernel spec_kernel = mfcc_spec::Kernel::kGeneric;
     mfcc_spec::FusedTables sf{};
+    // the filterbank output (mfcc_hip_set_fbank, mfcc_hip_fbank_*): the kernel of every such call (fbank_plan.hpp:
+    // choose; the fused one reads sf too), the matrix's tables in a device allocation of their own (fb_dev; NULL: no
+    // matrix) and the scale.  fb_used: a call has read the tables, so a new matrix synchronizes the device first
+    mfcc_fbank::Kernel fb_kernel = mfcc_fbank::Kernel::kGeneric;
+    void *fb_dev = nullptr;
+    mfcc_fbank::Tables fb{};
+    int fb_scale = MFCC_HIP_FBANK_ENERGY;
+    bool fb_used = false;
     // the 1024 forms: one of the two is bound, the one float_kernel names
     mfcc_fused1024::Tables f1k{};          // bf16-split contraction, set lists for every rate (kernel_fused1024.hpp)
     mfcc_fused1024_f32::Tables f1k_f32{};  // fp32 contraction, one MFMA list per rate (kernel_fused1024_f32.hpp)
@@ -528,6 +540,14 @@ struct SpectrumGuard {
     SpectrumGuard &operator=(const SpectrumGuard &) = delete;
 };
 
+// The handle as a filterbank handle for the scope of a mfcc_hip_fbank_* call: the spectrum handle above with rows of
+// n_bands values (launch() runs a filterbank kernel)
+struct FbankGuard {
+    SpectrumGuard spectrum;
+    explicit FbankGuard(mfcc_hip_handle *hh) : spectrum(hh) { hh->r.fbank = hh->fb.n_bands; }
+    ~FbankGuard() { spectrum.h->r.fbank = 0; }
+};
+
 struct Arena {
     std::vector<char> host;
     template <typename T>
@@ -673,6 +693,7 @@ int build_tables(mfcc_hip_handle *h) {
     if (have_1k) o_f1k = a.put(f1k_blob);
     // ---- the power-spectrum kernels: the generic one reads the float tables above; the fused one has a blob of its own
     h->spec_kernel = mfcc_spec::choose(r.nfft, r.hop, r.frame_len, r.float_impl == MFCC_HIP_IMPL_GENERIC);
+    h->fb_kernel = mfcc_fbank::choose(r.nfft, r.hop, r.frame_len, r.float_impl == MFCC_HIP_IMPL_GENERIC);
     std::vector<char> spec_blob;
     size_t o_spec = 0;
     if (h->spec_kernel == mfcc_spec::Kernel::kFused512) {
@@ -799,7 +820,18 @@ int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t s
     DeviceGuard guard(h->device);
     const long long total = s.total_frames;
     const bool logmel = is_logmel(h->r);
-    if (!fixed && h->r.spectrum) {
+    if (!fixed && h->r.fbank) {
+        // a filterbank call (FbankGuard): the fused kernel, or the generic one where the problem does not fit its tiles
+        float *o = static_cast<float *>(d_out);
+        if (reinterpret_cast<uintptr_t>(o) & 3) return MFCC_HIP_ERROR_INVALID_PARAM;
+        const bool log = h->fb_scale != MFCC_HIP_FBANK_ENERGY;
+        if (h->fb_kernel != mfcc_fbank::Kernel::kFused512 || !mfcc_fbank::launch_fused(s, h->sf, h->fb, log, o, h->n_cu, h->stream)) {
+            const mfcc_spec::GenericTables gt{h->ft.window, h->ft.tw_fft, h->ft.tw_split,
+                                              float(1.0 / (h->r.power_scale * h->r.power_scale))};
+            if (!mfcc_fbank::launch_generic(s, gt, h->fb, log, h->r.nfft, o, h->n_cu, h->stream)) return MFCC_HIP_ERROR_UNSUPPORTED;
+        }
+        h->fb_used = true;
+    } else if (!fixed && h->r.spectrum) {
         // a spectrum call (SpectrumGuard): the fused kernel, or the generic one where the problem does not fit its tiles
         float *o = static_cast<float *>(d_out);
         if (reinterpret_cast<uintptr_t>(o) & 3) return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -1579,7 +1611,7 @@ int ragged_launch(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const si
     using mfcc_batch::Records;
     using mfcc_batch::Route;
     Records kernel = Records::kNone;        // what the kernel of this call reads utterances from
-    if (!fixed && !h->r.spectrum && h->float_kernel == FloatKernel::kFused512W12 && std::is_same<OutT, float>::value)
+    if (!fixed && !h->r.spectrum && !h->r.fbank && h->float_kernel == FloatKernel::kFused512W12 && std::is_same<OutT, float>::value)
         kernel = Records::kTiles;                 // (a spectrum call packs: its kernels take no tile records)
     if (fixed && h->fixed_kernel == FixedKernel::kFixed512 && std::is_same<OutT, int16_t>::value) kernel = Records::kFrames;
     const Route route = mfcc_batch::route(kernel, fixed, sc, n_utt);
@@ -2167,6 +2199,7 @@ void mfcc_hip_destroy(mfcc_hip_handle *h) {
     if (h->s_in) (void)hipStreamDestroy(h->s_in);
     if (h->s_out) (void)hipStreamDestroy(h->s_out);
     if (h->arena) (void)hipFree(h->arena);
+    if (h->fb_dev) (void)hipFree(h->fb_dev);
     for (DevBuf *b : {&h->d_in, &h->d_out, &h->d_norm, &h->d_pcen, &h->d_full, &h->d_stat, &h->d_dtab, &h->d_slide, &h->d_stab,
                       &h->d_vad, &h->d_voiced, &h->d_sel, &h->d_final, &h->d_dec, &h->d_raw, &h->d_rs_tab, &h->d_rs})
         if (b->p) (void)hipFree(b->p);
@@ -2311,6 +2344,126 @@ int mfcc_hip_spectrum_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size
 }
 
 const char *mfcc_hip_spectrum_kernel_name(const mfcc_hip_handle *h) { return h ? mfcc_spec::name_of(h->spec_kernel) : ""; }
+
+// ---- the filterbank output (include/mfcc_hip.h: "filterbank"; kernel_fbank.hpp, fbank_plan.hpp; DESIGN.md section
+// 4.19): the spectrum entries' routes with the handle as a filterbank handle for the call (FbankGuard)
+int mfcc_hip_set_fbank(mfcc_hip_handle *h, const mfcc_hip_fbank *p, const float *weights) {
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const int bins = mfcc_spec::bins(h->r.nfft);
+    mfcc_fbank::Table t;
+    mfcc_fbank::Sets sets;
+    bool mfma = false;           // the fused kernel's MFMA form: the packed weights do not fit its LDS (fbank_plan.hpp)
+    if (p) {
+        if (p->struct_size != sizeof(mfcc_hip_fbank) || !weights) return MFCC_HIP_ERROR_INVALID_PARAM;
+        for (int v : p->reserved)
+            if (v != 0) return MFCC_HIP_ERROR_INVALID_PARAM;
+        if (!mfcc_fbank::valid_bands(p->n_bands) || !mfcc_fbank::valid_scale(p->scale) || !mfcc_fbank::valid_floor(p->floor))
+            return MFCC_HIP_ERROR_INVALID_PARAM;
+        if (mfcc_fbank::first_bad_weight(weights, p->n_bands, bins) >= 0) return MFCC_HIP_ERROR_INVALID_PARAM;
+        t = mfcc_fbank::build_table(weights, p->n_bands, bins);
+        mfma = h->fb_kernel == mfcc_fbank::Kernel::kFused512 && !mfcc_fbank::weights_in_lds(t.packed.size());
+        if (mfma && !mfcc_fbank::build_sets(weights, p->n_bands, bins, sets)) return MFCC_HIP_ERROR_OTHER;
+    }
+    DeviceGuard guard(h->device);
+    void *dev = nullptr;
+    if (p) {
+        const std::vector<char> blob = mfma ? mfcc_fbank::build_blob(t, sets) : mfcc_fbank::build_blob(t);
+        HIP_TRY(h, hipMalloc(&dev, blob.size()));
+        const hipError_t e = hipMemcpy(dev, blob.data(), blob.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(dev);
+            HIP_TRY(h, e);
+        }
+    }
+    // calls enqueued earlier, on whichever streams the handle had then, still read the old tables: the device is
+    // synchronized before they are freed (include/mfcc_hip.h says so).  The new tables are a fresh allocation, so no
+    // kernel in flight sees them
+    if (h->fb_dev) {
+        if (h->fb_used) {
+            const hipError_t e = hipDeviceSynchronize();
+            if (e != hipSuccess) {
+                if (dev) (void)hipFree(dev);
+                HIP_TRY(h, e);
+            }
+        }
+        (void)hipFree(h->fb_dev);
+    }
+    h->fb_dev = dev;
+    h->fb = mfcc_fbank::Tables{};
+    h->fb_used = false;
+    if (p) {
+        const char *b = static_cast<const char *>(dev);
+        h->fb.w = reinterpret_cast<const float *>(b);
+        h->fb.band = reinterpret_cast<const int4 *>(b + mfcc_fbank::blob_bands(t.packed.size()));
+        h->fb.n_bands = p->n_bands;
+        h->fb.w_total = int(t.packed.size());
+        h->fb.c = mfcc_fbank::scale_factor(p->scale);
+        h->fb.floor = p->floor == 0.0f ? 0.0f : p->floor;          // -0.0 -> +0.0
+        h->fb_scale = p->scale;
+        if (mfma) {
+            h->fb.a_bf = reinterpret_cast<const uint4 *>(b + mfcc_fbank::blob_bytes(t.packed.size(), p->n_bands));
+            for (int i = 0; i < mfcc_fbank::kMaxBlocks; ++i) h->fb.mask[i] = sets.mask[i], h->fb.set_first[i] = sets.first[i];
+        }
+    }
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_fbank_bands(const mfcc_hip_handle *h, size_t *n_bands) {
+    if (!h || !n_bands) return MFCC_HIP_ERROR_INVALID_PARAM;
+    *n_bands = size_t(h->fb.n_bands);
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_fbank_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo, void *d_out,
+                           size_t *n_frames) {
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!h->fb_dev) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (!mfcc_fbank::call_fits(n, nch, size_t(h->fb.n_bands))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    FbankGuard fbank(h);
+    return dense_dev(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
+}
+
+int mfcc_hip_fbank_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const size_t *offsets, size_t n_utt, void *d_out,
+                                  size_t cap, size_t *frame_offsets) {
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!h->fb_dev) return MFCC_HIP_ERROR_UNSUPPORTED;
+    // the row count times the bands must fit (decreasing offsets are the route's to refuse)
+    if (offsets && n_utt && offsets[n_utt] >= offsets[0] &&
+        !mfcc_fbank::ragged_fits(offsets[n_utt] - offsets[0], n_utt, size_t(h->fb.n_bands)))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    FbankGuard fbank(h);
+    return process_ragged_dev<float>(h, false, static_cast<const int16_t *>(d_pcm), offsets, n_utt, static_cast<float *>(d_out),
+                                     cap, frame_offsets);
+}
+
+int mfcc_hip_fbank_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_t nch, float *out, size_t cap, size_t *n_frames) {
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!h->fb_dev) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (!mfcc_fbank::call_fits(n, nch, size_t(h->fb.n_bands))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    FbankGuard fbank(h);
+    return process_host<float>(h, false, pcm, n, nch, out, cap, n_frames);
+}
+
+const char *mfcc_hip_fbank_kernel_name(const mfcc_hip_handle *h) {
+    return h && h->fb_dev ? mfcc_fbank::name_of(h->fb_kernel) : "";
+}
+
+int mfcc_hip_htk_weights(int nfft, int sample_rate, int n_bands, float low_hz, float high_hz, float *out, size_t cap_floats,
+                         size_t *n_floats) {
+    if (!is_pow2(nfft) || nfft < 64 || nfft > 1024 || sample_rate <= 0 || !mfcc_fbank::valid_bands(n_bands))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    // the band edges as resolve_banked takes them
+    const double lo = double(low_hz), hi = double(high_hz), nyq = double(sample_rate) / 2.0, top = hi == 0.0 ? nyq : hi;
+    if (!(lo >= 0.0) || !(lo < top) || !(top <= nyq)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const size_t n = size_t(n_bands) * size_t(mfcc_spec::bins(nfft));
+    if (n_floats) *n_floats = n;
+    if (out) {
+        if (cap_floats < n) return MFCC_HIP_ERROR_BUFFER_SMALL;
+        const std::vector<double> w = mel_dense_htk(nfft, n_bands, double(sample_rate), lo, top);
+        for (size_t i = 0; i < n; ++i) out[i] = float(w[i]);
+    }
+    return MFCC_HIP_SUCCESS;
+}
 
 int mfcc_hip_set_normalize(mfcc_hip_handle *h, int mode) {
     if (!h || mode < MFCC_HIP_NORMALIZE_NONE || mode > MFCC_HIP_NORMALIZE_MEAN_VAR) return MFCC_HIP_ERROR_INVALID_PARAM;
