@@ -55,19 +55,47 @@ struct Resolved {
     int frame_len;             // samples of a frame (hop <= frame_len <= nfft); the window's length.  nfft: a plain handle
     int mel_kind;              // enum mfcc_hip_mel_kind (mfcc_hip_create_banked); NOTEBOOK: the reference's bank
     double mel_lo, mel_hi;     // HTK: the band edges in Hz, mel_hi effective (never 0); NOTEBOOK: both 0
-    bool spectrum = false;     // set for the scope of a mfcc_hip_spectrum_* call (SpectrumGuard): the float routes write
-                               // power-spectrum rows
-    int fbank = 0;             // the band count for the scope of a mfcc_hip_fbank_* call (FbankGuard), else 0: the float
-                               // routes write filterbank rows
 };
 
-// width of an output row: n_mel log-mel values or n_cep coefficients; nfft / 2 + 1 bins inside a spectrum call
-inline size_t row_width(const Resolved &r) {
-    if (r.fbank) return size_t(r.fbank);
-    if (r.spectrum) return size_t(mfcc_spec::bins(r.nfft));
-    return size_t(r.output == MFCC_HIP_OUTPUT_LOGMEL ? r.n_mel : r.n_cep);
-}
+// width of a row of the handle's own output: n_mel log-mel values or n_cep coefficients
+inline size_t row_width(const Resolved &r) { return size_t(r.output == MFCC_HIP_OUTPUT_LOGMEL ? r.n_mel : r.n_cep); }
 inline bool is_logmel(const Resolved &r) { return r.output == MFCC_HIP_OUTPUT_LOGMEL; }
+
+// The passes behind the float kernels as a handle is set up for them (mfcc_hip_set_normalize, _normalize_window, _deltas,
+// _pcen, _vad); default-constructed: none of them
+struct Post {
+    int norm = MFCC_HIP_NORMALIZE_NONE;
+    int norm_window = 0;       // 0: the per-segment form; else the sliding one, with the minimum window of its causal form
+    int norm_min_window = 1;   // and centered / causal
+    int norm_center = 1;
+    int delta_order = 0;       // 0 (off), 1 or 2
+    int delta_window = 2;
+    bool pcen_on = false;
+    mfcc_pcen::Prm pcen{};     // the parameters as the kernels take them
+    int vad_mode = MFCC_HIP_VAD_OFF;
+    int vad_column = 0;
+    int vad_context = 0;
+    float vad_threshold = 5.0f, vad_scale = 0.5f, vad_proportion = 0.6f;
+};
+const Post kNoPost{};
+
+// What the sample pointer in hand holds: the format and the rate (0: the handle's own).  It travels with the pointer as
+// far as the input stage of its route (dense_input, ragged_input); behind that stage every pointer is int16 at the handle's
+// own rate
+struct Samples {
+    int fmt, rate;
+};
+
+// What a call computes.  Every entry point builds one (call_of) and passes it down; the routes read it, never the handle's
+// settings
+enum class Kind { kFeatures, kSpectrum, kFbank };     // the handle's own output, power-spectrum rows, filterbank rows
+struct Call {
+    Kind kind;
+    bool fixed;
+    size_t width;              // floats (fixed: int16) of a row as the kernel writes it
+    size_t out_width;          // ... and as the call returns it: width times 1 + the delta order
+    const Post &post;          // the handle's for a float features call, else kNoPost
+};
 
 // The kernel a handle's float calls run; build_tables decides it when the handle is made.
 enum class FloatKernel {
@@ -279,34 +307,21 @@ struct mfcc_hip_handle {
     // the handle; the last mfcc_hip_stream_destroy then tears it down (include/mfcc_hip.h: lifetime)
     int n_sessions = 0;
     bool destroy_pending = false;
-    // per-segment normalization (mfcc_hip_set_normalize): the mode, the stats / coefficient / tile-table scratch and,
-    // for host-buffer calls whose chunks cut a channel, the whole result on the device (run_host_pipeline)
-    int norm = MFCC_HIP_NORMALIZE_NONE;
+    // the passes behind the float kernels: their settings, written by the mfcc_hip_set_* functions and nowhere else
+    Post post;
+    // per-segment normalization: the stats / coefficient / tile-table scratch and, for host-buffer calls whose chunks cut
+    // a channel, the whole result on the device (run_host_pipeline)
     DevBuf d_norm, d_full;
-    // delta coefficients (mfcc_hip_set_deltas): order 0 (off), 1 or 2 and the window; the static rows the delta pass
-    // reads (d_stat) and its tile table (d_dtab)
-    int delta_order = 0;
-    int delta_window = 2;
+    // delta coefficients: the static rows the delta pass reads (d_stat) and its tile table (d_dtab)
     DevBuf d_stat, d_dtab;
-    // sliding-window normalization (mfcc_hip_set_normalize_window): window 0 (off: the per-segment form), the minimum
-    // window of the causal form and centered / causal; the raw rows the sliding pass reads (d_slide: it cannot run
-    // in place) and its tile table (d_stab)
-    int norm_window = 0;
-    int norm_min_window = 1;
-    int norm_center = 1;
+    // sliding-window normalization: the raw rows the sliding pass reads (d_slide: it cannot run in place) and its tile
+    // table (d_stab)
     DevBuf d_slide, d_stab;
-    // energy VAD (mfcc_hip_set_vad): the mode and the rule's parameters; the decision's scratch (d_vad: tile partials,
-    // thresholds, tile table), the mask (d_voiced), the selection's scratch (d_sel: tile counts, prefixes, segment
-    // offsets, tile table) and the final rows of a SELECT call before the gather moves them to the caller (d_final)
-    int vad_mode = MFCC_HIP_VAD_OFF;
-    int vad_column = 0;
-    int vad_context = 0;
-    float vad_threshold = 5.0f, vad_scale = 0.5f, vad_proportion = 0.6f;
+    // energy VAD: the decision's scratch (d_vad: tile partials, thresholds, tile table), the mask (d_voiced), the
+    // selection's scratch (d_sel: tile counts, prefixes, segment offsets, tile table) and the final rows of a SELECT call
+    // before the gather moves them to the caller (d_final)
     DevBuf d_vad, d_voiced, d_sel, d_final;
-    // PCEN (mfcc_hip_set_pcen): on / off and the parameters as the kernels take them; the pass's scratch (d_pcen: tile
-    // ends, carries, tile table)
-    bool pcen_on = false;
-    mfcc_pcen::Prm pcen{};
+    // PCEN: the pass's scratch (d_pcen: tile ends, carries, tile table)
     DevBuf d_pcen;
     // sample format (mfcc_hip_set_sample_format): what every sample pointer holds; the decoded int16 samples of a call
     // (d_dec) and the raw bytes of a session's push on their way to the decode (d_raw)
@@ -414,26 +429,22 @@ int desc_stage(mfcc_hip_handle *h, DevBuf &b, size_t want, mfcc_hip_handle::Pinn
 
 // ---- sample formats (kernel_decode.hpp): one streaming pass in front of the kernels turns the
 // samples of a call into int16 in h->d_dec, and the call goes on from there as it does on int16 input
-inline bool decodes(const mfcc_hip_handle *h) { return h->sample_fmt != MFCC_HIP_SAMPLE_S16; }
-inline size_t sample_bytes(const mfcc_hip_handle *h) { return mfcc_decode::sample_size(h->sample_fmt); }
-inline bool sample_aligned(const mfcc_hip_handle *h, const void *p) {
-    return (reinterpret_cast<uintptr_t>(p) & (sample_bytes(h) - 1)) == 0;
-}
-// sample i behind p, in the handle's format
-inline const void *sample_at(const mfcc_hip_handle *h, const void *p, size_t i) {
-    return static_cast<const char *>(p) + i * sample_bytes(h);
-}
+inline bool decodes(int fmt) { return fmt != MFCC_HIP_SAMPLE_S16; }
+inline size_t sample_bytes(int fmt) { return mfcc_decode::sample_size(fmt); }
+inline bool sample_aligned(int fmt, const void *p) { return (reinterpret_cast<uintptr_t>(p) & (sample_bytes(fmt) - 1)) == 0; }
+// sample i behind p
+inline const void *sample_at(int fmt, const void *p, size_t i) { return static_cast<const char *>(p) + i * sample_bytes(fmt); }
 
-// rows of n samples in the handle's format (row r at sample r * in_stride of d_in) -> int16 rows of out_stride samples
-// at d_out, on the handle's stream.  More than one row: out_stride is a multiple of 8, or the rows lie back to back
-int decode_rows(mfcc_hip_handle *h, const void *d_in, size_t n, size_t rows, size_t in_stride, int16_t *d_out,
+// rows of n samples in format fmt (row r at sample r * in_stride of d_in) -> int16 rows of out_stride samples at d_out,
+// on the handle's stream.  More than one row: out_stride is a multiple of 8, or the rows lie back to back
+int decode_rows(mfcc_hip_handle *h, int fmt, const void *d_in, size_t n, size_t rows, size_t in_stride, int16_t *d_out,
                 size_t out_stride) {
     if (!n || !rows) return MFCC_HIP_SUCCESS;
     if (rows > 1 && in_stride == n && out_stride == n) {         // back to back on both sides: one row
         n *= rows;
         rows = 1;
     }
-    if (!mfcc_decode::launch(h->sample_fmt, d_in, d_out, n, rows, in_stride, out_stride, h->n_cu, h->stream))
+    if (!mfcc_decode::launch(fmt, d_in, d_out, n, rows, in_stride, out_stride, h->n_cu, h->stream))
         return MFCC_HIP_ERROR_INVALID_PARAM;
     HIP_TRY(h, hipGetLastError());
     return MFCC_HIP_SUCCESS;
@@ -441,14 +452,14 @@ int decode_rows(mfcc_hip_handle *h, const void *d_in, size_t n, size_t rows, siz
 
 // ... into the handle's scratch area, grown and taken (the caller releases it behind the kernels that read it): rows
 // back to back where the input's are, else every row rounded up to 8 samples
-int decode_to_scratch(mfcc_hip_handle *h, const void *d_in, size_t n, size_t rows, size_t in_stride, const int16_t **out,
-                      size_t *out_stride) {
+int decode_to_scratch(mfcc_hip_handle *h, int fmt, const void *d_in, size_t n, size_t rows, size_t in_stride,
+                      const int16_t **out, size_t *out_stride) {
     const size_t stride = rows <= 1 || in_stride == n ? n : (n + 7) & ~size_t(7);
     int rc = ensure(h, h->d_dec, rows * stride * sizeof(int16_t) + 64);
     if (rc || (rc = scratch_acquire(h))) return rc;
     *out = static_cast<const int16_t *>(h->d_dec.p);
     *out_stride = stride;
-    return decode_rows(h, d_in, n, rows, rows <= 1 ? n : in_stride, static_cast<int16_t *>(h->d_dec.p), stride);
+    return decode_rows(h, fmt, d_in, n, rows, rows <= 1 ? n : in_stride, static_cast<int16_t *>(h->d_dec.p), stride);
 }
 
 // ---- sample rates (include/mfcc_hip.h: "sample rates"; resample_plan.hpp, kernel_resample.hpp)
@@ -495,58 +506,18 @@ inline size_t own_rate_len(const mfcc_hip_handle *h, size_t n) {
     return size_t(mfcc_rs::count(n, g.L, g.M));
 }
 
-// the handle as a plain int16 handle at its own rate for the scope: the resampled samples take the routes of int16 input
-struct PlainInputGuard {
-    mfcc_hip_handle *h;
-    int fmt, rate;
-    explicit PlainInputGuard(mfcc_hip_handle *hh) : h(hh), fmt(hh->sample_fmt), rate(hh->input_rate) {
-        h->sample_fmt = MFCC_HIP_SAMPLE_S16;
-        h->input_rate = 0;
-    }
-    ~PlainInputGuard() {
-        h->sample_fmt = fmt;
-        h->input_rate = rate;
-    }
-    PlainInputGuard(const PlainInputGuard &) = delete;
-    PlainInputGuard &operator=(const PlainInputGuard &) = delete;
-};
+// what a sample pointer handed to an entry point holds: the handle's format, at its input rate
+inline Samples samples_of(const mfcc_hip_handle *h) { return Samples{h->sample_fmt, h->input_rate}; }
 
-// The handle as a spectrum handle for the scope of a mfcc_hip_spectrum_* call: rows of nfft / 2 + 1 power values out of
-// the float routes (launch() runs the spectrum kernel, row_width() is the bin count), and nothing behind the kernel --
-// the output kind, normalization, deltas, PCEN and the VAD do not apply to the spectrum and are put back afterwards.
-// The sample format and the input rate stay: they say what a sample pointer holds
-struct SpectrumGuard {
-    mfcc_hip_handle *h;
-    int output, norm, delta_order, vad_mode;
-    bool pcen_on;
-    explicit SpectrumGuard(mfcc_hip_handle *hh)
-        : h(hh), output(hh->r.output), norm(hh->norm), delta_order(hh->delta_order), vad_mode(hh->vad_mode), pcen_on(hh->pcen_on) {
-        h->r.spectrum = true;
-        h->r.output = MFCC_HIP_OUTPUT_CEPSTRA;
-        h->norm = MFCC_HIP_NORMALIZE_NONE;
-        h->delta_order = 0;
-        h->vad_mode = MFCC_HIP_VAD_OFF;
-        h->pcen_on = false;
-    }
-    ~SpectrumGuard() {
-        h->r.spectrum = false;
-        h->r.output = output;
-        h->norm = norm;
-        h->delta_order = delta_order;
-        h->vad_mode = vad_mode;
-        h->pcen_on = pcen_on;
-    }
-    SpectrumGuard(const SpectrumGuard &) = delete;
-    SpectrumGuard &operator=(const SpectrumGuard &) = delete;
-};
-
-// The handle as a filterbank handle for the scope of a mfcc_hip_fbank_* call: the spectrum handle above with rows of
-// n_bands values (launch() runs a filterbank kernel)
-struct FbankGuard {
-    SpectrumGuard spectrum;
-    explicit FbankGuard(mfcc_hip_handle *hh) : spectrum(hh) { hh->r.fbank = hh->fb.n_bands; }
-    ~FbankGuard() { spectrum.h->r.fbank = 0; }
-};
+// The descriptor of a call on h.  The passes behind the kernels belong to the handle's own float output: a spectrum, a
+// filterbank and a fixed-point call run none, whatever the handle is set up for
+inline Call call_of(const mfcc_hip_handle *h, Kind kind, bool fixed) {
+    const Post &post = kind == Kind::kFeatures && !fixed ? h->post : kNoPost;
+    const size_t w = kind == Kind::kFbank      ? size_t(h->fb.n_bands)
+                     : kind == Kind::kSpectrum ? size_t(mfcc_spec::bins(h->r.nfft))
+                                               : row_width(h->r);
+    return Call{kind, fixed, w, w * size_t(1 + post.delta_order), post};
+}
 
 struct Arena {
     std::vector<char> host;
@@ -795,9 +766,11 @@ int launch_generic(mfcc_hip_handle *h, const mfcc_k::StreamDesc &s, unsigned blo
     return MFCC_HIP_SUCCESS;
 }
 
-int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t stride, size_t nch,
+// The kernel of a call over int16 samples: the spectrum's, the filterbank's or the handle's own, as c says
+int launch(mfcc_hip_handle *h, const Call &c, const void *d_pcm, size_t n, size_t stride, size_t nch,
            int halo, void *d_out, size_t *n_frames, size_t force_frames = 0) {
-    if (!h || (!d_pcm && n * nch) || halo < 0 || halo > 1) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const bool fixed = c.fixed;
+    if ((!d_pcm && n * nch) || halo < 0 || halo > 1) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (!fixed && h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel))
         return MFCC_HIP_ERROR_UNSUPPORTED;
@@ -820,8 +793,8 @@ int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t s
     DeviceGuard guard(h->device);
     const long long total = s.total_frames;
     const bool logmel = is_logmel(h->r);
-    if (!fixed && h->r.fbank) {
-        // a filterbank call (FbankGuard): the fused kernel, or the generic one where the problem does not fit its tiles
+    if (c.kind == Kind::kFbank) {
+        // the fused kernel, or the generic one where the problem does not fit its tiles
         float *o = static_cast<float *>(d_out);
         if (reinterpret_cast<uintptr_t>(o) & 3) return MFCC_HIP_ERROR_INVALID_PARAM;
         const bool log = h->fb_scale != MFCC_HIP_FBANK_ENERGY;
@@ -831,8 +804,7 @@ int launch(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t s
             if (!mfcc_fbank::launch_generic(s, gt, h->fb, log, h->r.nfft, o, h->n_cu, h->stream)) return MFCC_HIP_ERROR_UNSUPPORTED;
         }
         h->fb_used = true;
-    } else if (!fixed && h->r.spectrum) {
-        // a spectrum call (SpectrumGuard): the fused kernel, or the generic one where the problem does not fit its tiles
+    } else if (c.kind == Kind::kSpectrum) {
         float *o = static_cast<float *>(d_out);
         if (reinterpret_cast<uintptr_t>(o) & 3) return MFCC_HIP_ERROR_INVALID_PARAM;
         if (h->spec_kernel != mfcc_spec::Kernel::kFused512 || !mfcc_spec::launch_fused(s, h->sf, o, h->n_cu, h->stream)) {
@@ -1049,10 +1021,8 @@ struct SlideArgs {
     int mode, window, min_window, center;
 };
 
-inline bool sliding(const mfcc_hip_handle *h) { return h->norm != MFCC_HIP_NORMALIZE_NONE && h->norm_window > 0; }
-inline SlideArgs slide_args(const mfcc_hip_handle *h) {
-    return SlideArgs{h->norm, h->norm_window, h->norm_min_window, h->norm_center};
-}
+inline bool sliding(const Post &p) { return p.norm != MFCC_HIP_NORMALIZE_NONE && p.norm_window > 0; }
+inline SlideArgs slide_args(const Post &p) { return SlideArgs{p.norm, p.norm_window, p.norm_min_window, p.norm_center}; }
 
 int sliding_pass(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, const SegSpan &sp, SlideArgs a) {
     if (span_empty(sp)) return MFCC_HIP_SUCCESS;
@@ -1076,8 +1046,8 @@ struct VadArgs {
     float proportion;
 };
 
-inline VadArgs vad_args(const mfcc_hip_handle *h) {
-    return VadArgs{h->vad_column, h->vad_threshold, h->vad_scale, h->vad_context, h->vad_proportion};
+inline VadArgs vad_args(const Post &p) {
+    return VadArgs{p.vad_column, p.vad_threshold, p.vad_scale, p.vad_context, p.vad_proportion};
 }
 
 inline bool vad_args_ok(int width, int column, float threshold, float scale, int context, float proportion) {
@@ -1181,22 +1151,17 @@ int select_segments(mfcc_hip_handle *h, const float *d_in, int Wp, const unsigne
     return select_run(h, d_in, Wp, d_voiced, pl, false, d_out, out_offsets);
 }
 
-// width of a float output row of this handle: the static row, times 1 + the delta order
-inline size_t out_width(const mfcc_hip_handle *h) { return row_width(h->r) * size_t(1 + h->delta_order); }
-
 // ---- the passes behind the float kernels.  Every float entry point of a handle runs them in
 // ONE order, enqueued by post_chain and nowhere else: the VAD decision on the raw rows, PCEN, the normalization (sliding or
 // per segment), deltas; the voiced-row selection (select_run) follows where the handle selects.
 // A handle with any of them is refused (UNSUPPORTED) by every fixed-point entry point and by the entry points that see
 // part of a stream: there is no fixed-point normalization, PCEN, delta or frame selection, and the float ones are
 // whole-segment passes.
-inline bool has_post(const mfcc_hip_handle *h) {
-    return h->norm != MFCC_HIP_NORMALIZE_NONE || h->pcen_on || h->delta_order || h->vad_mode;
-}
+inline bool has_post(const Post &p) { return p.norm != MFCC_HIP_NORMALIZE_NONE || p.pcen_on || p.delta_order || p.vad_mode; }
 
 // Where the rows of a call go.  The kernels write `raw`; PCEN works on it in place; the sliding normalization moves it to
 // `stat`, the per-segment one works on `stat` (= raw) in place; deltas expand `stat` into `out`.  So `stat` is h->d_stat
-// iff the handle has a delta order (else out), and `raw` is h->d_slide iff its normalization slides (else stat).
+// iff the call has a delta order (else out), and `raw` is h->d_slide iff its normalization slides (else stat).
 struct PostRoute {
     float *raw, *stat, *out;
     unsigned char *voiced;      // the decision's byte per row (selection only)
@@ -1205,90 +1170,120 @@ struct PostRoute {
 };
 
 // the rule, at `at` floats into h->d_stat / h->d_slide (already grown)
-inline PostRoute route_to(const mfcc_hip_handle *h, float *out, size_t at = 0) {
+inline PostRoute route_to(const mfcc_hip_handle *h, const Post &p, float *out, size_t at = 0) {
     PostRoute rt{};
     rt.out = out;
-    rt.stat = h->delta_order ? static_cast<float *>(h->d_stat.p) + at : out;
-    rt.raw = sliding(h) ? static_cast<float *>(h->d_slide.p) + at : rt.stat;
-    rt.staged = h->delta_order || sliding(h);
+    rt.stat = p.delta_order ? static_cast<float *>(h->d_stat.p) + at : out;
+    rt.raw = sliding(p) ? static_cast<float *>(h->d_slide.p) + at : rt.stat;
+    rt.staged = p.delta_order || sliding(p);
     return rt;
 }
 
 // grows h->d_stat / h->d_slide for `rows` static rows where the rule needs them
-int stage_rows(mfcc_hip_handle *h, size_t rows) {
-    const size_t bytes = rows * row_width(h->r) * sizeof(float) + 64;
-    int rc = h->delta_order ? ensure(h, h->d_stat, bytes) : MFCC_HIP_SUCCESS;
-    if (!rc && sliding(h)) rc = ensure(h, h->d_slide, bytes);
+int stage_rows(mfcc_hip_handle *h, const Call &c, size_t rows) {
+    const size_t bytes = rows * c.width * sizeof(float) + 64;
+    int rc = c.post.delta_order ? ensure(h, h->d_stat, bytes) : MFCC_HIP_SUCCESS;
+    if (!rc && sliding(c.post)) rc = ensure(h, h->d_slide, bytes);
     return rc;
 }
 
 // the route of a device call of `rows` frames into d_out; select: every frame goes to h->d_final first and its byte to
 // h->d_voiced, select_run then moves the voiced rows to d_out
-int post_route(mfcc_hip_handle *h, size_t rows, float *d_out, bool select, PostRoute &rt) {
+int post_route(mfcc_hip_handle *h, const Call &c, size_t rows, float *d_out, bool select, PostRoute &rt) {
     int rc = MFCC_HIP_SUCCESS;
     if (select) {
-        rc = ensure(h, h->d_final, rows * out_width(h) * sizeof(float) + 64);
+        rc = ensure(h, h->d_final, rows * c.out_width * sizeof(float) + 64);
         if (!rc) rc = ensure(h, h->d_voiced, rows + 64);
     }
-    if (rc || (rc = stage_rows(h, rows))) return rc;
-    rt = route_to(h, select ? static_cast<float *>(h->d_final.p) : d_out);
+    if (rc || (rc = stage_rows(h, c, rows))) return rc;
+    rt = route_to(h, c.post, select ? static_cast<float *>(h->d_final.p) : d_out);
     rt.voiced = select ? static_cast<unsigned char *>(h->d_voiced.p) : nullptr;
     rt.staged = rt.staged || select;
     return rt.staged ? scratch_acquire(h) : MFCC_HIP_SUCCESS;
 }
 
 // the chain over the segments of sp; sel: the tiles of the selection that follows, whose counts the decision fills
-int post_chain(mfcc_hip_handle *h, const SegSpan &sp, const PostRoute &rt, const SelPlan *sel) {
-    const int W = int(row_width(h->r));
+int post_chain(mfcc_hip_handle *h, const Call &c, const SegSpan &sp, const PostRoute &rt, const SelPlan *sel) {
+    const Post &p = c.post;
+    const int W = int(c.width);
     int rc;
-    if (sel && (rc = vad_decide(h, rt.raw, W, sp, vad_args(h), rt.voiced, *sel))) return rc;
-    if (h->pcen_on && (rc = pcen_pass(h, rt.raw, W, sp, h->pcen))) return rc;
-    if ((rc = sliding(h) ? sliding_pass(h, rt.raw, rt.stat, W, sp, slide_args(h))
-                         : normalize_pass(h, rt.stat, W, sp, h->norm)))
+    if (sel && (rc = vad_decide(h, rt.raw, W, sp, vad_args(p), rt.voiced, *sel))) return rc;
+    if (p.pcen_on && (rc = pcen_pass(h, rt.raw, W, sp, p.pcen))) return rc;
+    if ((rc = sliding(p) ? sliding_pass(h, rt.raw, rt.stat, W, sp, slide_args(p))
+                         : normalize_pass(h, rt.stat, W, sp, p.norm)))
         return rc;
-    if (h->delta_order && (rc = deltas_pass(h, rt.stat, rt.out, W, sp, h->delta_order, h->delta_window))) return rc;
+    if (p.delta_order && (rc = deltas_pass(h, rt.stat, rt.out, W, sp, p.delta_order, p.delta_window))) return rc;
     return MFCC_HIP_SUCCESS;
 }
 
 // the dense float device path: the launch, then the chain with one segment per channel
-int launch_float_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo, void *d_out,
-                     size_t *n_frames) {
+int launch_float_dev(mfcc_hip_handle *h, const Call &c, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo,
+                     void *d_out, size_t *n_frames) {
     // nothing behind the kernels (the headline of bench.py): the launch and nothing else
-    if (!h || !has_post(h))
-        return launch(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
+    if (!has_post(c.post)) return launch(h, c, d_pcm, n, stride, nch, halo, d_out, n_frames);
     if (halo) return MFCC_HIP_ERROR_UNSUPPORTED;                                 // a shard of a longer stream
     const size_t nf = count_frames(h->r, n);
-    if (nf == 0 || nch == 0 || !d_out) return launch(h, false, d_pcm, n, stride, nch, 0, d_out, n_frames);
+    if (nf == 0 || nch == 0 || !d_out) return launch(h, c, d_pcm, n, stride, nch, 0, d_out, n_frames);
     DeviceGuard guard(h->device);
     PostRoute rt;
-    int rc = post_route(h, nf * nch, static_cast<float *>(d_out), false, rt);
-    if (rc || (rc = launch(h, false, d_pcm, n, stride, nch, 0, rt.raw, n_frames))) return rc;
-    if ((rc = post_chain(h, span_uniform(0, nch, nf), rt, nullptr)) || !rt.staged) return rc;
+    int rc = post_route(h, c, nf * nch, static_cast<float *>(d_out), false, rt);
+    if (rc || (rc = launch(h, c, d_pcm, n, stride, nch, 0, rt.raw, n_frames))) return rc;
+    if ((rc = post_chain(h, c, span_uniform(0, nch, nf), rt, nullptr)) || !rt.staged) return rc;
     return scratch_release(h);
 }
 
-// The dense device entries on a handle with a sample format: the samples the call reads -- n + halo of every channel --
-// decoded into the scratch area, then the route of int16 input on it.  MFCC_HIP_SAMPLE_S16: that route and nothing else
-int rated_dense_dev(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo,
-                    void *d_out, size_t *n_frames);
+// ---- the input stage of a dense call (DESIGN.md sections 4.15, 4.17): nch rows of n samples as `in` describes them
+// (n + halo are read; a rate takes no halo) -> int16 rows at the handle's own rate: decoded into h->d_dec, then resampled
+// into h->d_rs by the taps of a (rs_bind) to n2 samples a row.  p / stride: where the rows now lie; the scratch area is
+// taken, the caller releases it behind the kernels that read them
+struct DenseIn {
+    const int16_t *p;
+    size_t stride;
+};
+// the stride of `rows` resampled rows of n samples: rounded up to 8 samples where there is more than one
+inline size_t rs_stride(size_t n, size_t rows) { return rows <= 1 ? n : (n + 7) & ~size_t(7); }
 
-int dense_dev(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo, void *d_out,
-              size_t *n_frames) {
-    if (rated(h)) return rated_dense_dev(h, fixed, d_pcm, n, stride, nch, halo, d_out, n_frames);
-    auto route = [&](const void *p, size_t st) {
-        return fixed ? launch(h, true, p, n, st, nch, halo, d_out, n_frames)
-                     : launch_float_dev(h, p, n, st, nch, halo, d_out, n_frames);
+int dense_input(mfcc_hip_handle *h, Samples in, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo,
+                const mfcc_rs::Taps &a, size_t n2, DenseIn &o) {
+    o = DenseIn{static_cast<const int16_t *>(d_pcm), nch <= 1 ? n : stride};
+    int rc;
+    if (decodes(in.fmt) && (rc = decode_to_scratch(h, in.fmt, d_pcm, n + size_t(halo), nch, stride, &o.p, &o.stride))) return rc;
+    if (!in.rate) return MFCC_HIP_SUCCESS;
+    const size_t stride2 = rs_stride(n2, nch);
+    if ((rc = ensure(h, h->d_rs, nch * stride2 * sizeof(int16_t) + 64)) || (rc = scratch_acquire(h))) return rc;
+    mfcc_rs::launch(a, o.p, (long long)n, static_cast<int16_t *>(h->d_rs.p), (long long)n2, (long long)nch, (long long)o.stride,
+                    (long long)stride2, nullptr, 0, h->n_cu, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    o = DenseIn{static_cast<const int16_t *>(h->d_rs.p), stride2};
+    return MFCC_HIP_SUCCESS;
+}
+
+// The dense device entries: int16 at the handle's own rate goes straight to the kernels; anything else through the input
+// stage first, and from there on as int16 at the handle's own rate
+int dense_dev(mfcc_hip_handle *h, const Call &c, Samples in, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo,
+              void *d_out, size_t *n_frames) {
+    auto route = [&](const void *p, size_t len, size_t st) {
+        return c.fixed ? launch(h, c, p, len, st, nch, halo, d_out, n_frames)
+                       : launch_float_dev(h, c, p, len, st, nch, halo, d_out, n_frames);
     };
-    if (!h || !decodes(h)) return route(d_pcm, stride);
+    if (!decodes(in.fmt) && !in.rate) return route(d_pcm, n, stride);
     // what launch() refuses, before anything is read
-    if ((!d_pcm && n * nch) || halo < 0 || halo > 1 || !sample_aligned(h, d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if ((!d_pcm && n * nch) || halo < 0 || halo > 1 || !sample_aligned(in.fmt, d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (nch > 1 && stride < n + size_t(halo)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (count_frames(h->r, n) == 0 || nch == 0 || !d_out) return route(d_pcm, stride);      // no sample is read
     DeviceGuard guard(h->device);
-    const int16_t *dec = nullptr;
-    size_t dec_stride = 0;
-    int rc = decode_to_scratch(h, d_pcm, n + size_t(halo), nch, stride, &dec, &dec_stride);
-    if (rc || (rc = route(dec, dec_stride))) return rc;
+    mfcc_rs::Taps a{};
+    size_t n2 = n;
+    int rc;
+    if (in.rate) {
+        if (halo) return MFCC_HIP_ERROR_UNSUPPORTED;              // a shard's edge would need the neighbour's samples
+        if (n >= mfcc_rs::kMaxLen) return MFCC_HIP_ERROR_INVALID_PARAM;
+        if ((rc = rs_bind(h, in.rate, h->r.sample_rate, a))) return rc;
+        n2 = size_t(mfcc_rs::count(n, a.L, a.M));
+    }
+    if (count_frames(h->r, n2) == 0 || nch == 0 || !d_out)       // no sample is read
+        return route(d_pcm, n2, in.rate ? rs_stride(n2, nch) : stride);
+    DenseIn src;
+    if ((rc = dense_input(h, in, d_pcm, n, stride, nch, halo, a, n2, src)) || (rc = route(src.p, n2, src.stride))) return rc;
     return scratch_release(h);
 }
 
@@ -1475,29 +1470,45 @@ inline size_t host_chunk_bytes() {
 }
 
 template <typename OutT>
-int rated_process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, size_t nch, OutT *out, size_t cap,
-                       size_t *n_frames);
-
-template <typename OutT>
-int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, size_t nch, OutT *out,
+int process_host(mfcc_hip_handle *h, const Call &c, Samples in, const void *pcm, size_t n, size_t nch, OutT *out,
                  size_t cap, size_t *n_frames) {
-    if (rated(h)) return rated_process_host<OutT>(h, fixed, pcm, n, nch, out, cap, n_frames);
-    if (!h || (!pcm && n * nch)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const bool fixed = c.fixed;
+    if (!pcm && n * nch) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
-    const size_t nf = count_frames(h->r, n);
+    size_t n2 = n;                              // samples of a channel at the handle's own rate
+    if (in.rate) {
+        mfcc_rs::Geometry g;
+        const int rc = rs_geometry(in.rate, h->r.sample_rate, g);
+        if (rc) return rc;
+        if (n >= mfcc_rs::kMaxLen) return MFCC_HIP_ERROR_INVALID_PARAM;
+        n2 = size_t(mfcc_rs::count(n, g.L, g.M));
+    }
+    const size_t nf = count_frames(h->r, n2);
     if (n_frames) *n_frames = nf;
     if (nf == 0 || nch == 0) return MFCC_HIP_SUCCESS;
-    const size_t ncep = fixed ? row_width(h->r) : out_width(h);   // elements per row
+    const size_t ncep = c.out_width;            // elements per row
     const size_t n_out = nf * nch * ncep;
     if (!out || cap < n_out) return MFCC_HIP_ERROR_BUFFER_SMALL;
     DeviceGuard guard(h->device);
+    const size_t ssz = sample_bytes(in.fmt);
+    if (in.rate) {
+        // an input rate: the unchunked route -- one copy in, the device route, one copy back
+        int rc;
+        if ((rc = ensure(h, h->d_raw, n * nch * ssz + 64)) || (rc = ensure(h, h->d_full, n_out * sizeof(OutT) + 64)) ||
+            (rc = scratch_acquire(h)))
+            return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->d_raw.p, pcm, n * nch * ssz, hipMemcpyHostToDevice, h->stream));
+        if ((rc = dense_dev(h, c, in, h->d_raw.p, n, n, nch, 0, h->d_full.p, nullptr))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(out, h->d_full.p, n_out * sizeof(OutT), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return MFCC_HIP_SUCCESS;
+    }
     const size_t kChunkBytes = host_chunk_bytes();
     // deltas: the static rows are 1 + K times narrower than the output rows
-    const int K = fixed ? 0 : h->delta_order;
+    const int K = c.post.delta_order;
     // a sample format: the chunks are cut by sample count exactly as for int16, their raw bytes cross the wire and every
     // chunk is decoded on the device in front of its kernel
-    const bool dec = decodes(h);
-    const size_t ssz = sample_bytes(h);
+    const bool dec = decodes(in.fmt);
 
     const std::vector<HostChunk> chunks = mfcc_batch::cut_dense(n, nch, nf, ncep, framing(h->r), kChunkBytes);
     // The chain (post_chain) works on whole channels: no row may leave the device before its channel's statistics exist,
@@ -1505,7 +1516,7 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
     // Chunks of whole channels run the chain on their own rows before the copy back; frame-range chunks of long channels
     // write into one device buffer of the whole result (and its staging), which goes through the chain and is copied
     // back after the pipeline
-    const bool post = !fixed && has_post(h);
+    const bool post = has_post(c.post);
     const bool whole = post && mfcc_batch::dense_cuts_channels(n, kChunkBytes);
     OutT *d_full = nullptr;
     if (whole) {
@@ -1514,39 +1525,34 @@ int process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, s
         d_full = static_cast<OutT *>(h->d_full.p);
     }
     // the staging of the chain (route_to's rule) holds the rows of one chunk, or of the whole result
-    const bool staged = post && (K || sliding(h));
+    const bool staged = post && (K || sliding(c.post));
     if (staged) {
-        int rc = stage_rows(h, whole ? nch * nf : mfcc_batch::max_chunk_rows(chunks));
+        int rc = stage_rows(h, c, whole ? nch * nf : mfcc_batch::max_chunk_rows(chunks));
         if (rc || (rc = scratch_acquire(h))) return rc;
     }
     std::vector<PipeChunk> pc;
     pc.reserve(chunks.size());
-    for (const HostChunk &c : chunks)
-        pc.push_back({sample_at(h, pcm, c.in_off), c.in_samples * ssz, out + c.out_off,
-                      whole ? 0 : c.out_elems * sizeof(OutT)});
+    for (const HostChunk &k : chunks)
+        pc.push_back({sample_at(in.fmt, pcm, k.in_off), k.in_samples * ssz, out + k.out_off,
+                      whole ? 0 : k.out_elems * sizeof(OutT)});
     int rc = run_host_pipeline(h, pc, pcm, nch * n * ssz, out, whole ? 0 : n_out * sizeof(OutT), [&](size_t i, void *d_raw, void *d_out) {
-        const HostChunk &c = chunks[i];
-        const void *d_in = d_raw;
-        size_t in_stride = c.stride;
-        if (dec) {
-            const int16_t *p = nullptr;
-            const int drc = decode_to_scratch(h, d_raw, c.n + size_t(c.halo), c.nch, c.stride, &p, &in_stride);
-            if (drc) return drc;
-            d_in = p;
-        }
-        void *rows = whole ? static_cast<void *>(d_full + c.out_off) : d_out;
+        const HostChunk &k = chunks[i];
+        DenseIn src{static_cast<const int16_t *>(d_raw), k.stride};
+        int crc;
+        if (dec && (crc = dense_input(h, in, d_raw, k.n, k.stride, k.nch, k.halo, mfcc_rs::Taps{}, k.n, src))) return crc;
+        void *rows = whole ? static_cast<void *>(d_full + k.out_off) : d_out;
         PostRoute rt{};
         if (post) {
             // a frame-range chunk writes its rows of the whole result, W wide where they are statics
-            rt = route_to(h, static_cast<float *>(rows), whole ? c.out_off / size_t(1 + K) : 0);
+            rt = route_to(h, c.post, static_cast<float *>(rows), whole ? k.out_off / size_t(1 + K) : 0);
             rows = rt.raw;
         }
-        const int lrc = launch(h, fixed, d_in, c.n, in_stride, c.nch, c.halo, rows, nullptr, c.halo || c.frames != nf ? c.frames : 0);
-        if (lrc || whole || !post) return lrc;
-        return post_chain(h, span_uniform(0, c.nch, nf), rt, nullptr);
+        crc = launch(h, c, src.p, k.n, src.stride, k.nch, k.halo, rows, nullptr, k.halo || k.frames != nf ? k.frames : 0);
+        if (crc || whole || !post) return crc;
+        return post_chain(h, c, span_uniform(0, k.nch, nf), rt, nullptr);
     });
     if (rc || !whole) return rc ? rc : (staged || dec ? scratch_release(h) : MFCC_HIP_SUCCESS);
-    if ((rc = post_chain(h, span_uniform(0, nch, nf), route_to(h, reinterpret_cast<float *>(d_full)), nullptr))) return rc;
+    if ((rc = post_chain(h, c, span_uniform(0, nch, nf), route_to(h, c.post, reinterpret_cast<float *>(d_full)), nullptr))) return rc;
     if ((staged || dec) && (rc = scratch_release(h))) return rc;
     HIP_TRY(h, hipMemcpyAsync(out, d_full, n_out * sizeof(OutT), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1606,19 +1612,20 @@ inline mfcc_batch::Scan ragged_scan(const mfcc_hip_handle *h, const size_t *offs
 // The launch of a scanned corpus with at least one frame, d_out large enough: route -> fill -> desc_stage -> launch
 // (batch_plan.hpp).  d_pcm is int16; fo: the scan's frame offsets
 template <typename OutT>
-int ragged_launch(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt, OutT *d_out,
+int ragged_launch(mfcc_hip_handle *h, const Call &c, const int16_t *d_pcm, const size_t *offsets, size_t n_utt, OutT *d_out,
                   const size_t *fo, const mfcc_batch::Scan &sc) {
     using mfcc_batch::Records;
     using mfcc_batch::Route;
+    const bool fixed = c.fixed;
     Records kernel = Records::kNone;        // what the kernel of this call reads utterances from
-    if (!fixed && !h->r.spectrum && !h->r.fbank && h->float_kernel == FloatKernel::kFused512W12 && std::is_same<OutT, float>::value)
-        kernel = Records::kTiles;                 // (a spectrum call packs: its kernels take no tile records)
+    if (!fixed && c.kind == Kind::kFeatures && h->float_kernel == FloatKernel::kFused512W12 && std::is_same<OutT, float>::value)
+        kernel = Records::kTiles;                 // (a spectrum or filterbank call packs: its kernels take no tile records)
     if (fixed && h->fixed_kernel == FixedKernel::kFixed512 && std::is_same<OutT, int16_t>::value) kernel = Records::kFrames;
     const Route route = mfcc_batch::route(kernel, fixed, sc, n_utt);
     // Checked first: this is the per-step host work of a sharded corpus (BASELINE config 5: 10 000 x 10 s; bench.py
     // `enqueue_us_per_step`) -- no packing copy, no row gather, no descriptors, the same bits (every channel of the
     // plain call starts from reset, its frames are the utterance's frames and the rows come out dense)
-    if (route == Route::kUniform) return launch(h, fixed, d_pcm + offsets[0], sc.len0, sc.len0, n_utt, 0, d_out, nullptr);
+    if (route == Route::kUniform) return launch(h, c, d_pcm + offsets[0], sc.len0, sc.len0, n_utt, 0, d_out, nullptr);
     // the table in pinned memory: its H2D copy is asynchronous
     mfcc_hip_handle::PinnedDesc *pd = nullptr;
     int rc = desc_acquire(h, mfcc_batch::table_ll(route, n_utt), &pd);
@@ -1646,7 +1653,7 @@ int ragged_launch(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const si
         mfcc_fixed512::launch_ragged(d_pcm, static_cast<const mfcc_fixed512::RaggedRec *>(h->d_in.p), (int)p.n_recs,
                                      (long long)sc.total, h->r.hop, h->x5, reinterpret_cast<int16_t *>(d_out), h->n_cu, h->stream);
     } else {
-        const size_t ncep = row_width(h->r);
+        const size_t ncep = c.width;
         const mfcc_batch::PackPlan p = mfcc_batch::fill_pack(offsets, fo, n_utt, framing(h->r), ncep * sizeof(OutT), pd->p);
         if ((rc = ensure(h, h->d_in, p.in_bytes))) return rc;
         if ((rc = desc_stage(h, h->d_out, p.out_bytes, pd, p.desc_ll, p.desc_off))) return rc;
@@ -1655,166 +1662,12 @@ int ragged_launch(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const si
         const unsigned blocks = (unsigned)std::min<size_t>(n_utt, size_t(h->n_cu) * 8);
         hipLaunchKernelGGL(pack_utterances_kernel, dim3(blocks), dim3(256), 0, h->stream, d_pcm,
                            static_cast<int16_t *>(h->d_in.p), d_desc, (long long)n_utt);
-        if ((rc = launch(h, fixed, h->d_in.p, p.len, p.len, 1, 0, d_all, nullptr, p.F))) return rc;
+        if ((rc = launch(h, c, h->d_in.p, p.len, p.len, 1, 0, d_all, nullptr, p.F))) return rc;
         hipLaunchKernelGGL(gather_rows_kernel<OutT>, dim3(blocks), dim3(256), 0, h->stream, d_all, d_out,
                            d_desc + p.gather_ll, (long long)n_utt, (int)ncep);
     }
     HIP_TRY(h, hipGetLastError());
     return scratch_release(h);
-}
-
-// A scanned corpus on the device, in the handle's sample format: what is left to refuse, the decode of the span
-// offsets[0] .. offsets[n_utt] into the scratch area (MFCC_HIP_SAMPLE_S16: none), the launch, and the chain over the result,
-// one segment per utterance (float contract only: the public fixed-point entry points refuse a handle with a pass).  A
-// handle that stages (deltas, a normalization window, MFCC_HIP_VAD_SELECT) has its kernels write into the staging.  With
-// MFCC_HIP_VAD_SELECT every frame goes through the chain into h->d_final, then only the voiced rows to d_out;
-// frame_offsets describes those, and the call synchronizes (select_run)
-template <typename OutT>
-int ragged_scanned(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt, OutT *d_out,
-                   size_t cap, size_t *frame_offsets, const mfcc_batch::Scan &sc) {
-    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (sc.max_len && !d_pcm) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (sc.total == 0) return MFCC_HIP_SUCCESS;
-    const bool post = !fixed && has_post(h), sel = post && h->vad_mode != MFCC_HIP_VAD_OFF;
-    const size_t WO = post ? out_width(h) : row_width(h->r);
-    if (!d_out || cap < sc.total * WO) return MFCC_HIP_ERROR_BUFFER_SMALL;    // frame_offsets: the counts, to size d_out by
-    DeviceGuard guard(h->device);
-    int rc;
-    std::vector<size_t> loc;
-    const bool dec = decodes(h);
-    if (dec) {
-        loc.resize(n_utt + 1);
-        for (size_t u = 0; u <= n_utt; ++u) loc[u] = offsets[u] - offsets[0];
-        const size_t span = loc[n_utt];
-        size_t stride = 0;
-        if ((rc = decode_to_scratch(h, sample_at(h, d_pcm, offsets[0]), span, 1, span, &d_pcm, &stride))) return rc;
-        offsets = loc.data();
-    }
-    if (!post) {
-        rc = ragged_launch<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, frame_offsets, sc);
-    } else {
-        PostRoute rt;
-        if ((rc = post_route(h, sc.total, reinterpret_cast<float *>(d_out), sel, rt)) ||
-            (rc = ragged_launch<float>(h, false, d_pcm, offsets, n_utt, rt.raw, frame_offsets, sc)))
-            return rc;
-        const SegSpan sp = span_offsets(frame_offsets, n_utt);
-        SelPlan pl;
-        if (sel && (rc = select_plan(h, sp, int(WO), pl))) return rc;
-        if ((rc = post_chain(h, sp, rt, sel ? &pl : nullptr))) return rc;
-        if (sel) rc = select_run(h, rt.out, int(WO), rt.voiced, pl, true, reinterpret_cast<float *>(d_out), frame_offsets);
-        else if (rt.staged) rc = scratch_release(h);
-    }
-    return rc || !dec ? rc : scratch_release(h);
-}
-
-// the device entry: the one scan of the call, then the above.  The order of the refusals is the entry's own
-template <typename OutT>
-int rated_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt, OutT *d_out,
-                     size_t cap, size_t *frame_offsets);
-
-template <typename OutT>
-int process_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt,
-                       OutT *d_out, size_t cap, size_t *frame_offsets) {
-    if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (rated(h)) return rated_ragged_dev<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets);
-    const bool dec = decodes(h) && n_utt;                 // a sample format looks at the offsets and the pointer first
-    if (!dec && fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
-    const mfcc_batch::Scan sc = ragged_scan(h, offsets, n_utt, frame_offsets);
-    if (sc.rc || (dec && !sample_aligned(h, d_pcm))) return MFCC_HIP_ERROR_INVALID_PARAM;
-    return ragged_scanned<OutT>(h, fixed, d_pcm, offsets, n_utt, d_out, cap, frame_offsets, sc);
-}
-
-// Host buffers: the corpus goes to the device in ONE copy (the span offsets[0] .. offsets[n_utt] as it lies), runs through
-// the device-resident path above -- no copy at all for equal lengths, per-tile / per-utterance records for the fused
-// kernels, pack and gather for the rest -- and its rows come back in one copy.  (Round 1 copied utterance by
-// utterance into a zeroed packed stream: n_utt memcpy calls, 50 ms of call overhead for 10 000 utterances.)
-template <typename OutT>
-int rated_process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const size_t *offsets, size_t n_utt, OutT *out,
-                         size_t cap, size_t *frame_offsets);
-
-template <typename OutT>
-int process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const size_t *offsets, size_t n_utt,
-                   OutT *out, size_t cap, size_t *frame_offsets) {
-    if (!h || !offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (rated(h)) return rated_process_ragged<OutT>(h, fixed, pcm, offsets, n_utt, out, cap, frame_offsets);
-    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
-    const size_t ncep = fixed ? row_width(h->r) : out_width(h);          // elements per row
-    const mfcc_batch::Scan sc = ragged_scan(h, offsets, n_utt, frame_offsets);
-    if (sc.rc || (sc.max_len && !pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (sc.total == 0) return MFCC_HIP_SUCCESS;                          // frame_offsets: all zero
-    if (!out || cap < sc.total * ncep) return MFCC_HIP_ERROR_BUFFER_SMALL;      // the counts, so that the caller can size `out`
-    DeviceGuard guard(h->device);
-    // the same copy pipeline as process_host: chunks of whole utterances, ~64 MB each; every chunk is one call of the
-    // device-resident ragged path on its own offsets, its rows land behind those of the chunk before it.  A sample format:
-    // the chunks are cut by sample count as for int16, their raw bytes cross the wire and the ragged path decodes them
-    const size_t ssz = sample_bytes(h);
-    const std::vector<mfcc_batch::UttRange> ranges =
-        mfcc_batch::cut_ragged(offsets, frame_offsets, n_utt, host_chunk_bytes());
-    std::vector<PipeChunk> pc;
-    pc.reserve(ranges.size());
-    for (const mfcc_batch::UttRange &r : ranges)
-        pc.push_back({sample_at(h, pcm, offsets[r.u0]), (offsets[r.u1] - offsets[r.u0]) * ssz, out + r.rows0 * ncep,
-                      (r.rows1 - r.rows0) * ncep * sizeof(OutT)});
-    // the frame counts of the scan, chunk by chunk (a chunk's call does not count them again)
-    const std::vector<size_t> counts(frame_offsets, frame_offsets + n_utt + 1);
-    std::vector<size_t> loc, fo;
-    // MFCC_HIP_VAD_SELECT: every chunk returns its voiced rows only (the call below synchronizes and reports them), so its
-    // copy back shrinks and lands behind the voiced rows of the chunks before it
-    const bool sel_mode = !fixed && h->vad_mode;
-    size_t sel_rows = 0;
-    return run_host_pipeline(h, pc, sample_at(h, pcm, offsets[0]), (offsets[n_utt] - offsets[0]) * ssz, out,
-                             sc.total * ncep * sizeof(OutT), [&](size_t i, void *d_in, void *d_out) {
-        const mfcc_batch::UttRange &r = ranges[i];
-        const size_t k = r.u1 - r.u0;
-        loc.assign(k + 1, 0);
-        fo.assign(k + 1, 0);
-        for (size_t j = 0; j <= k; ++j) loc[j] = offsets[r.u0 + j] - offsets[r.u0];
-        const mfcc_batch::Scan csc =
-            mfcc_batch::scan_with(loc.data(), k, size_t(kRaggedTiles.tile),
-                                  [&](size_t u, size_t) { return counts[r.u0 + u + 1] - counts[r.u0 + u]; }, fo.data());
-        const int rc = ragged_scanned<OutT>(h, fixed, static_cast<const int16_t *>(d_in), loc.data(), k,
-                                            static_cast<OutT *>(d_out), pc[i].out_bytes / sizeof(OutT), fo.data(), csc);
-        const size_t rows0 = sel_mode ? sel_rows : r.rows0;
-        for (size_t j = 1; j <= k; ++j) frame_offsets[r.u0 + j] = rows0 + fo[j];
-        if (sel_mode && !rc) {
-            pc[i].out = out + rows0 * ncep;
-            pc[i].out_bytes = fo[k] * ncep * sizeof(OutT);
-            sel_rows += fo[k];
-        }
-        return rc;
-    });
-}
-
-// ---- a handle with an input rate: decode -> resample -> route.  The resampled samples live in h->d_rs (obtained like
-// d_dec); behind them every call is the call of a plain int16 handle on them, so its refusals, its frame counts and
-// its bits are that handle's on mfcc_hip_resample_host of the decoded input
-int rated_dense_dev(mfcc_hip_handle *h, bool fixed, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo,
-                    void *d_out, size_t *n_frames) {
-    if ((!d_pcm && n * nch) || halo < 0 || halo > 1 || !sample_aligned(h, d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (nch > 1 && stride < n + size_t(halo)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (halo) return MFCC_HIP_ERROR_UNSUPPORTED;              // a shard's edge would need the neighbour's samples
-    if (n >= mfcc_rs::kMaxLen) return MFCC_HIP_ERROR_INVALID_PARAM;
-    DeviceGuard guard(h->device);
-    mfcc_rs::Taps a;
-    int rc = rs_bind(h, h->input_rate, h->r.sample_rate, a);
-    if (rc) return rc;
-    const size_t n2 = size_t(mfcc_rs::count(n, a.L, a.M)), stride2 = nch <= 1 ? n2 : (n2 + 7) & ~size_t(7);
-    if (count_frames(h->r, n2) == 0 || nch == 0 || !d_out) {                   // no sample is read
-        PlainInputGuard plain(h);
-        return dense_dev(h, fixed, d_pcm, n2, stride2, nch, 0, d_out, n_frames);
-    }
-    const int16_t *src = static_cast<const int16_t *>(d_pcm);
-    size_t src_stride = nch <= 1 ? n : stride;
-    if (decodes(h) && (rc = decode_to_scratch(h, d_pcm, n, nch, stride, &src, &src_stride))) return rc;
-    if ((rc = ensure(h, h->d_rs, nch * stride2 * sizeof(int16_t) + 64)) || (rc = scratch_acquire(h))) return rc;
-    mfcc_rs::launch(a, src, (long long)n, static_cast<int16_t *>(h->d_rs.p), (long long)n2, (long long)nch, (long long)src_stride,
-                    (long long)stride2, nullptr, 0, h->n_cu, h->stream);
-    HIP_TRY(h, hipGetLastError());
-    {
-        PlainInputGuard plain(h);
-        rc = dense_dev(h, fixed, h->d_rs.p, n2, stride2, nch, 0, d_out, n_frames);
-    }
-    return rc ? rc : scratch_release(h);
 }
 
 // the offsets of the resampled utterances, back to back from 0.  false: decreasing offsets or a length over the limit
@@ -1827,43 +1680,51 @@ bool rated_offsets(const mfcc_rs::Geometry &g, const size_t *offsets, size_t n_u
     return true;
 }
 
-// ragged: every utterance resampled on its own (zeros outside it) by one launch over a tile list, the new offsets from
-// the lengths alone; then the plain handle's call on them
-template <typename OutT>
-int rated_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const size_t *offsets, size_t n_utt, OutT *d_out,
-                     size_t cap, size_t *frame_offsets) {
-    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
-    mfcc_rs::Geometry g;
-    int rc = rs_geometry(h->input_rate, h->r.sample_rate, g);
-    if (rc) return rc;
-    std::vector<size_t> off2;
-    if (!rated_offsets(g, offsets, n_utt, off2) || !sample_aligned(h, d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    const mfcc_batch::Scan sc = ragged_scan(h, off2.data(), n_utt, frame_offsets);
-    if (sc.rc || (off2[n_utt] && !d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (sc.total == 0) return MFCC_HIP_SUCCESS;
-    const bool post = !fixed && has_post(h);
-    if (!d_out || cap < sc.total * (post ? out_width(h) : row_width(h->r))) return MFCC_HIP_ERROR_BUFFER_SMALL;
-    DeviceGuard guard(h->device);
+// ---- the input stage of a ragged call (DESIGN.md sections 4.15, 4.17): the utterances at `offsets` of d_pcm, as `in`
+// describes them -> int16 utterances at the handle's own rate.  The span offsets[0] .. offsets[n_utt] is decoded into
+// h->d_dec; every utterance is then resampled on its own (zeros outside it) by one launch over a tile list into h->d_rs, at
+// `own` (rated_offsets).  p / offsets: where the utterances now lie.  scratch: the area is taken, the caller releases it
+// behind the kernels that read them (int16 at the handle's own rate: nothing is done, nothing taken)
+struct RaggedIn {
+    const int16_t *p;
+    const size_t *offsets;
+    bool scratch;
+    std::vector<size_t> loc;                // the offsets of a decoded span, from its start
+};
+
+int ragged_input(mfcc_hip_handle *h, Samples in, const void *d_pcm, const size_t *offsets, const size_t *own, size_t n_utt,
+                 RaggedIn &o) {
+    o.p = static_cast<const int16_t *>(d_pcm);
+    o.offsets = offsets;
+    o.scratch = decodes(in.fmt) || in.rate;
+    if (!o.scratch) return MFCC_HIP_SUCCESS;
+    int rc;
     mfcc_rs::Taps a;
-    if ((rc = rs_bind(h, h->input_rate, h->r.sample_rate, a))) return rc;
-    // the decoded span (a sample format), else the caller's samples
-    const int16_t *src = d_pcm + offsets[0];
-    if (decodes(h)) {
+    if (in.rate && (rc = rs_bind(h, in.rate, h->r.sample_rate, a))) return rc;
+    const int16_t *src = o.p + offsets[0];
+    if (decodes(in.fmt)) {
         size_t st = 0;
         const size_t span = offsets[n_utt] - offsets[0];
-        if (span && (rc = decode_to_scratch(h, sample_at(h, d_pcm, offsets[0]), span, 1, span, &src, &st))) return rc;
+        if ((rc = decode_to_scratch(h, in.fmt, sample_at(in.fmt, d_pcm, offsets[0]), span, 1, span, &src, &st))) return rc;
+    }
+    if (!in.rate) {
+        o.loc.resize(n_utt + 1);
+        for (size_t u = 0; u <= n_utt; ++u) o.loc[u] = offsets[u] - offsets[0];
+        o.p = src;
+        o.offsets = o.loc.data();
+        return MFCC_HIP_SUCCESS;
     }
     // d_rs: the samples, then the records (their count does not depend on where the samples lie: 7 slots of lead at most)
     size_t max_tiles = 0;
-    for (size_t u = 0; u < n_utt; ++u) max_tiles += mfcc_rs::max_tiles(off2[u + 1] - off2[u], false);
-    const size_t rec_off = (off2[n_utt] * sizeof(int16_t) + 255) & ~size_t(255);
+    for (size_t u = 0; u < n_utt; ++u) max_tiles += mfcc_rs::max_tiles(own[u + 1] - own[u], false);
+    const size_t rec_off = (own[n_utt] * sizeof(int16_t) + 255) & ~size_t(255);
     const size_t rec_cap_ll = n_utt * mfcc_rs::kSegLL + max_tiles * mfcc_rs::kTileLL;
     if ((rc = ensure(h, h->d_rs, rec_off + rec_cap_ll * sizeof(long long) + 64))) return rc;
     int16_t *d_rs = static_cast<int16_t *>(h->d_rs.p);
     std::vector<mfcc_rs::SegIn> segs(n_utt);
     for (size_t u = 0; u < n_utt; ++u)
-        segs[u] = mfcc_rs::one_shot(g, reinterpret_cast<uintptr_t>(src + (offsets[u] - offsets[0])), offsets[u + 1] - offsets[u],
-                                    reinterpret_cast<uintptr_t>(d_rs + off2[u]));
+        segs[u] = mfcc_rs::one_shot(h->rs_geom, reinterpret_cast<uintptr_t>(src + (offsets[u] - offsets[0])),
+                                    offsets[u + 1] - offsets[u], reinterpret_cast<uintptr_t>(d_rs + own[u]));
     mfcc_rs::CallPlan pl;
     if (!mfcc_rs::plan_call(segs.data(), n_utt, pl) || pl.total_ll > rec_cap_ll) return MFCC_HIP_ERROR_INVALID_PARAM;
     mfcc_hip_handle::PinnedDesc *pd = nullptr;
@@ -1876,68 +1737,147 @@ int rated_ragged_dev(mfcc_hip_handle *h, bool fixed, const int16_t *d_pcm, const
                         h->n_cu, h->stream);
         HIP_TRY(h, hipGetLastError());
     }
-    {
-        PlainInputGuard plain(h);
-        rc = ragged_scanned<OutT>(h, fixed, d_rs, off2.data(), n_utt, d_out, cap, frame_offsets, sc);
-    }
-    return rc ? rc : scratch_release(h);
-}
-
-// host buffers: the unchunked route -- one copy in, the device route, one copy back
-template <typename OutT>
-int rated_process_host(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, size_t n, size_t nch, OutT *out, size_t cap,
-                       size_t *n_frames) {
-    if (!pcm && n * nch) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
-    mfcc_rs::Geometry g;
-    int rc = rs_geometry(h->input_rate, h->r.sample_rate, g);
-    if (rc) return rc;
-    if (n >= mfcc_rs::kMaxLen) return MFCC_HIP_ERROR_INVALID_PARAM;
-    const size_t nf = count_frames(h->r, size_t(mfcc_rs::count(n, g.L, g.M)));
-    if (n_frames) *n_frames = nf;
-    if (nf == 0 || nch == 0) return MFCC_HIP_SUCCESS;
-    const size_t n_out = nf * nch * (fixed ? row_width(h->r) : out_width(h));
-    if (!out || cap < n_out) return MFCC_HIP_ERROR_BUFFER_SMALL;
-    DeviceGuard guard(h->device);
-    const size_t in_bytes = n * nch * sample_bytes(h);
-    if ((rc = ensure(h, h->d_raw, in_bytes + 64)) || (rc = ensure(h, h->d_full, n_out * sizeof(OutT) + 64)) ||
-        (rc = scratch_acquire(h)))
-        return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->d_raw.p, pcm, in_bytes, hipMemcpyHostToDevice, h->stream));
-    if ((rc = rated_dense_dev(h, fixed, h->d_raw.p, n, n, nch, 0, h->d_full.p, nullptr))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(out, h->d_full.p, n_out * sizeof(OutT), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    o.p = d_rs;
+    o.offsets = own;
     return MFCC_HIP_SUCCESS;
 }
 
+// A scanned corpus on the device, as `in` describes it (own: the offsets at the handle's own rate, which sc has scanned --
+// `offsets` itself without an input rate): what is left to refuse, the input stage, the launch, and the chain over the
+// result, one segment per utterance.  A call that stages (deltas, a normalization window, MFCC_HIP_VAD_SELECT) has its
+// kernels write into the staging.  With MFCC_HIP_VAD_SELECT every frame goes through the chain into h->d_final, then only
+// the voiced rows to d_out; frame_offsets describes those, and the call synchronizes (select_run)
 template <typename OutT>
-int rated_process_ragged(mfcc_hip_handle *h, bool fixed, const int16_t *pcm, const size_t *offsets, size_t n_utt, OutT *out,
-                         size_t cap, size_t *frame_offsets) {
-    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
-    mfcc_rs::Geometry g;
-    int rc = rs_geometry(h->input_rate, h->r.sample_rate, g);
-    if (rc) return rc;
-    std::vector<size_t> off2, loc(n_utt + 1);
-    if (!rated_offsets(g, offsets, n_utt, off2)) return MFCC_HIP_ERROR_INVALID_PARAM;
-    const mfcc_batch::Scan sc = ragged_scan(h, off2.data(), n_utt, frame_offsets);
-    if (sc.rc || (off2[n_utt] && !pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
+int ragged_scanned(mfcc_hip_handle *h, const Call &c, Samples in, const void *d_pcm, const size_t *offsets, const size_t *own,
+                   size_t n_utt, OutT *d_out, size_t cap, size_t *frame_offsets, const mfcc_batch::Scan &sc) {
+    if (c.fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (sc.max_len && !d_pcm) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (sc.total == 0) return MFCC_HIP_SUCCESS;
-    const size_t W = fixed ? row_width(h->r) : out_width(h), n_out = sc.total * W;
-    if (!out || cap < n_out) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    const bool post = has_post(c.post), sel = c.post.vad_mode != MFCC_HIP_VAD_OFF;
+    const size_t WO = c.out_width;
+    if (!d_out || cap < sc.total * WO) return MFCC_HIP_ERROR_BUFFER_SMALL;    // frame_offsets: the counts, to size d_out by
     DeviceGuard guard(h->device);
-    for (size_t u = 0; u <= n_utt; ++u) loc[u] = offsets[u] - offsets[0];
-    const size_t in_bytes = loc[n_utt] * sample_bytes(h);
-    if ((rc = ensure(h, h->d_raw, in_bytes + 64)) || (rc = ensure(h, h->d_full, n_out * sizeof(OutT) + 64)) ||
-        (rc = scratch_acquire(h)))
+    RaggedIn src;
+    int rc = ragged_input(h, in, d_pcm, offsets, own, n_utt, src);
+    if (rc) return rc;
+    if (!post) {
+        rc = ragged_launch<OutT>(h, c, src.p, src.offsets, n_utt, d_out, frame_offsets, sc);
+    } else {
+        PostRoute rt;
+        if ((rc = post_route(h, c, sc.total, reinterpret_cast<float *>(d_out), sel, rt)) ||
+            (rc = ragged_launch<float>(h, c, src.p, src.offsets, n_utt, rt.raw, frame_offsets, sc)))
+            return rc;
+        const SegSpan sp = span_offsets(frame_offsets, n_utt);
+        SelPlan pl;
+        if (sel && (rc = select_plan(h, sp, int(WO), pl))) return rc;
+        if ((rc = post_chain(h, c, sp, rt, sel ? &pl : nullptr))) return rc;
+        if (sel) rc = select_run(h, rt.out, int(WO), rt.voiced, pl, true, reinterpret_cast<float *>(d_out), frame_offsets);
+        else if (rt.staged) rc = scratch_release(h);
+    }
+    return rc || !src.scratch ? rc : scratch_release(h);
+}
+
+// the device entry: the one scan of the call, then the above.  The order of the refusals is the entry's own: a sample format
+// looks at the offsets and the pointer before the fixed-point kernel, an input rate after it
+template <typename OutT>
+int process_ragged_dev(mfcc_hip_handle *h, const Call &c, Samples in, const void *d_pcm, const size_t *offsets, size_t n_utt,
+                       OutT *d_out, size_t cap, size_t *frame_offsets) {
+    if (!offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const bool dec = decodes(in.fmt) && n_utt;
+    if ((!dec || in.rate) && c.fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
+    std::vector<size_t> off2;
+    if (in.rate) {
+        mfcc_rs::Geometry g;
+        const int rc = rs_geometry(in.rate, h->r.sample_rate, g);
+        if (rc) return rc;
+        if (!rated_offsets(g, offsets, n_utt, off2) || !sample_aligned(in.fmt, d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    }
+    const size_t *own = in.rate ? off2.data() : offsets;
+    const mfcc_batch::Scan sc = ragged_scan(h, own, n_utt, frame_offsets);
+    if (sc.rc || (dec && !sample_aligned(in.fmt, d_pcm))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    return ragged_scanned<OutT>(h, c, in, d_pcm, offsets, own, n_utt, d_out, cap, frame_offsets, sc);
+}
+
+// Host buffers: the corpus goes to the device in ONE copy (the span offsets[0] .. offsets[n_utt] as it lies), runs through
+// the device-resident path above -- no copy at all for equal lengths, per-tile / per-utterance records for the fused
+// kernels, pack and gather for the rest -- and its rows come back in one copy.  (Round 1 copied utterance by
+// utterance into a zeroed packed stream: n_utt memcpy calls, 50 ms of call overhead for 10 000 utterances.)
+template <typename OutT>
+int process_ragged(mfcc_hip_handle *h, const Call &c, Samples in, const void *pcm, const size_t *offsets, size_t n_utt,
+                   OutT *out, size_t cap, size_t *frame_offsets) {
+    const bool fixed = c.fixed;
+    if (!offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
+    const size_t ncep = c.out_width;                                     // elements per row
+    std::vector<size_t> off2;                                            // an input rate: the offsets at the handle's own
+    if (in.rate) {
+        mfcc_rs::Geometry g;
+        const int rc = rs_geometry(in.rate, h->r.sample_rate, g);
+        if (rc) return rc;
+        if (!rated_offsets(g, offsets, n_utt, off2)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    }
+    const mfcc_batch::Scan sc = ragged_scan(h, in.rate ? off2.data() : offsets, n_utt, frame_offsets);
+    if (sc.rc || (sc.max_len && !pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (sc.total == 0) return MFCC_HIP_SUCCESS;                          // frame_offsets: all zero
+    if (!out || cap < sc.total * ncep) return MFCC_HIP_ERROR_BUFFER_SMALL;      // the counts, so that the caller can size `out`
+    DeviceGuard guard(h->device);
+    const size_t ssz = sample_bytes(in.fmt);
+    std::vector<size_t> loc, fo;
+    if (in.rate) {
+        // an input rate: the unchunked route -- one copy in, the device route, one copy back
+        loc.resize(n_utt + 1);
+        for (size_t u = 0; u <= n_utt; ++u) loc[u] = offsets[u] - offsets[0];
+        const size_t in_bytes = loc[n_utt] * ssz, n_out = sc.total * ncep;
+        int rc;
+        if ((rc = ensure(h, h->d_raw, in_bytes + 64)) || (rc = ensure(h, h->d_full, n_out * sizeof(OutT) + 64)) ||
+            (rc = scratch_acquire(h)))
+            return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->d_raw.p, sample_at(in.fmt, pcm, offsets[0]), in_bytes, hipMemcpyHostToDevice, h->stream));
+        if ((rc = ragged_scanned<OutT>(h, c, in, h->d_raw.p, loc.data(), off2.data(), n_utt, static_cast<OutT *>(h->d_full.p),
+                                       n_out, frame_offsets, sc)))
+            return rc;
+        // MFCC_HIP_VAD_SELECT: frame_offsets now counts the voiced rows (the call above has synchronized)
+        HIP_TRY(h, hipMemcpyAsync(out, h->d_full.p, frame_offsets[n_utt] * ncep * sizeof(OutT), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return MFCC_HIP_SUCCESS;
+    }
+    // the same copy pipeline as process_host: chunks of whole utterances, ~64 MB each; every chunk is one call of the
+    // device-resident ragged path on its own offsets, its rows land behind those of the chunk before it.  A sample format:
+    // the chunks are cut by sample count as for int16, their raw bytes cross the wire and the ragged path decodes them
+    const std::vector<mfcc_batch::UttRange> ranges =
+        mfcc_batch::cut_ragged(offsets, frame_offsets, n_utt, host_chunk_bytes());
+    std::vector<PipeChunk> pc;
+    pc.reserve(ranges.size());
+    for (const mfcc_batch::UttRange &r : ranges)
+        pc.push_back({sample_at(in.fmt, pcm, offsets[r.u0]), (offsets[r.u1] - offsets[r.u0]) * ssz, out + r.rows0 * ncep,
+                      (r.rows1 - r.rows0) * ncep * sizeof(OutT)});
+    // the frame counts of the scan, chunk by chunk (a chunk's call does not count them again)
+    const std::vector<size_t> counts(frame_offsets, frame_offsets + n_utt + 1);
+    // MFCC_HIP_VAD_SELECT: every chunk returns its voiced rows only (the call below synchronizes and reports them), so its
+    // copy back shrinks and lands behind the voiced rows of the chunks before it
+    const bool sel_mode = c.post.vad_mode;
+    size_t sel_rows = 0;
+    return run_host_pipeline(h, pc, sample_at(in.fmt, pcm, offsets[0]), (offsets[n_utt] - offsets[0]) * ssz, out,
+                             sc.total * ncep * sizeof(OutT), [&](size_t i, void *d_in, void *d_out) {
+        const mfcc_batch::UttRange &r = ranges[i];
+        const size_t k = r.u1 - r.u0;
+        loc.assign(k + 1, 0);
+        fo.assign(k + 1, 0);
+        for (size_t j = 0; j <= k; ++j) loc[j] = offsets[r.u0 + j] - offsets[r.u0];
+        const mfcc_batch::Scan csc =
+            mfcc_batch::scan_with(loc.data(), k, size_t(kRaggedTiles.tile),
+                                  [&](size_t u, size_t) { return counts[r.u0 + u + 1] - counts[r.u0 + u]; }, fo.data());
+        const int rc = ragged_scanned<OutT>(h, c, in, d_in, loc.data(), loc.data(), k, static_cast<OutT *>(d_out),
+                                            pc[i].out_bytes / sizeof(OutT), fo.data(), csc);
+        const size_t rows0 = sel_mode ? sel_rows : r.rows0;
+        for (size_t j = 1; j <= k; ++j) frame_offsets[r.u0 + j] = rows0 + fo[j];
+        if (sel_mode && !rc) {
+            pc[i].out = out + rows0 * ncep;
+            pc[i].out_bytes = fo[k] * ncep * sizeof(OutT);
+            sel_rows += fo[k];
+        }
         return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->d_raw.p, sample_at(h, pcm, offsets[0]), in_bytes, hipMemcpyHostToDevice, h->stream));
-    if ((rc = rated_ragged_dev<OutT>(h, fixed, static_cast<const int16_t *>(h->d_raw.p), loc.data(), n_utt,
-                                     static_cast<OutT *>(h->d_full.p), n_out, frame_offsets)))
-        return rc;
-    // MFCC_HIP_VAD_SELECT: frame_offsets now counts the voiced rows (the call above has synchronized)
-    HIP_TRY(h, hipMemcpyAsync(out, h->d_full.p, frame_offsets[n_utt] * W * sizeof(OutT), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return MFCC_HIP_SUCCESS;
+    });
 }
 
 // ---- minimal RIFF/WAVE reader (the reference uses the un-vendored libwav, main.c:58-98)
@@ -2226,61 +2166,70 @@ int mfcc_hip_synchronize(mfcc_hip_handle *h) {
 
 int mfcc_hip_process_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_t nch, float *out,
                          size_t cap, size_t *n_frames) {
-    if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;   // a dense result cannot hold rows of different counts
-    return process_host<float>(h, false, pcm, n, nch, out, cap, n_frames);
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (h->post.vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;   // a dense result cannot hold rows of different counts
+    return process_host<float>(h, call_of(h, Kind::kFeatures, false), samples_of(h), pcm, n, nch, out, cap, n_frames);
 }
 
 int mfcc_hip_process_fixed_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_t nch,
                                int16_t *out, size_t cap, size_t *n_frames) {
-    if (h && has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
-    return process_host<int16_t>(h, true, pcm, n, nch, out, cap, n_frames);
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    return process_host<int16_t>(h, call_of(h, Kind::kFeatures, true), samples_of(h), pcm, n, nch, out, cap, n_frames);
 }
 
 int mfcc_hip_process_ragged_i16(mfcc_hip_handle *h, const int16_t *pcm, const size_t *offsets, size_t n_utt,
                                 float *out, size_t cap, size_t *frame_offsets) {
-    return process_ragged<float>(h, false, pcm, offsets, n_utt, out, cap, frame_offsets);
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    return process_ragged<float>(h, call_of(h, Kind::kFeatures, false), samples_of(h), pcm, offsets, n_utt, out, cap, frame_offsets);
 }
 
 int mfcc_hip_process_ragged_fixed_i16(mfcc_hip_handle *h, const int16_t *pcm, const size_t *offsets, size_t n_utt,
                                       int16_t *out, size_t cap, size_t *frame_offsets) {
-    if (h && has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
-    return process_ragged<int16_t>(h, true, pcm, offsets, n_utt, out, cap, frame_offsets);
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    return process_ragged<int16_t>(h, call_of(h, Kind::kFeatures, true), samples_of(h), pcm, offsets, n_utt, out, cap, frame_offsets);
 }
 
 int mfcc_hip_process_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const size_t *offsets, size_t n_utt,
                                     void *d_out, size_t cap, size_t *frame_offsets) {
-    return process_ragged_dev<float>(h, false, static_cast<const int16_t *>(d_pcm), offsets, n_utt,
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    return process_ragged_dev<float>(h, call_of(h, Kind::kFeatures, false), samples_of(h), d_pcm, offsets, n_utt,
                                      static_cast<float *>(d_out), cap, frame_offsets);
 }
 
 int mfcc_hip_process_ragged_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const size_t *offsets, size_t n_utt,
                                           void *d_out, size_t cap, size_t *frame_offsets) {
-    if (h && has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
-    return process_ragged_dev<int16_t>(h, true, static_cast<const int16_t *>(d_pcm), offsets, n_utt,
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    return process_ragged_dev<int16_t>(h, call_of(h, Kind::kFeatures, true), samples_of(h), d_pcm, offsets, n_utt,
                                        static_cast<int16_t *>(d_out), cap, frame_offsets);
 }
 
 int mfcc_hip_process_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch,
                              int halo, void *d_out, size_t *n_frames) {
-    if (h && h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;   // a dense result cannot hold rows of different counts
-    return dense_dev(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (h->post.vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;   // a dense result cannot hold rows of different counts
+    return dense_dev(h, call_of(h, Kind::kFeatures, false), samples_of(h), d_pcm, n, stride, nch, halo, d_out, n_frames);
 }
 
 int mfcc_hip_process_fixed_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride,
                                    size_t nch, int halo, void *d_out, size_t *n_frames) {
-    if (h && has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
-    return dense_dev(h, true, d_pcm, n, stride, nch, halo, d_out, n_frames);
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    return dense_dev(h, call_of(h, Kind::kFeatures, true), samples_of(h), d_pcm, n, stride, nch, halo, d_out, n_frames);
 }
 
 int mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n, size_t stride,
                       size_t nch, void *d_out, int warmup, int iters, float *avg_ms) {
     if (!h || iters < 1 || warmup < 0 || !avg_ms) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (fixed && has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;        // a dense result cannot hold rows of different counts
+    if (fixed && has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (h->post.vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;   // a dense result cannot hold rows of different counts
     DeviceGuard guard(h->device);
     // what process_*_dev enqueues: with a sample format the decode, with normalization or deltas on the passes behind
     // the float launch
-    auto once = [&]() { return dense_dev(h, fixed != 0, d_pcm, n, stride, nch, 0, d_out, nullptr); };
+    const Call c = call_of(h, Kind::kFeatures, fixed != 0);
+    auto once = [&]() { return dense_dev(h, c, samples_of(h), d_pcm, n, stride, nch, 0, d_out, nullptr); };
     for (int i = 0; i < warmup; ++i) {
         int rc = once();
         if (rc) return rc;
@@ -2308,7 +2257,7 @@ int mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t n
 }
 
 // ---- the power-spectrum output (include/mfcc_hip.h: "power spectrum"; kernel_spectrum.hpp, spectrum_plan.hpp; DESIGN.md
-// section 4.18): the float entry points' own routes with the handle as a spectrum handle for the call (SpectrumGuard)
+// section 4.18): the float entry points' own routes on a Kind::kSpectrum call
 int mfcc_hip_spectrum_bins(const mfcc_hip_params *p, size_t *bins) {
     Resolved r;
     const int rc = resolve(p, r);
@@ -2320,8 +2269,7 @@ int mfcc_hip_spectrum_bins(const mfcc_hip_params *p, size_t *bins) {
 int mfcc_hip_spectrum_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo,
                               void *d_out, size_t *n_frames) {
     if (!h || !mfcc_spec::call_fits(n, nch, size_t(mfcc_spec::bins(h->r.nfft)))) return MFCC_HIP_ERROR_INVALID_PARAM;
-    SpectrumGuard spectrum(h);
-    return dense_dev(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
+    return dense_dev(h, call_of(h, Kind::kSpectrum, false), samples_of(h), d_pcm, n, stride, nch, halo, d_out, n_frames);
 }
 
 int mfcc_hip_spectrum_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const size_t *offsets, size_t n_utt, void *d_out,
@@ -2331,22 +2279,20 @@ int mfcc_hip_spectrum_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, cons
     if (offsets && n_utt && offsets[n_utt] >= offsets[0] &&
         !mfcc_spec::ragged_fits(offsets[n_utt] - offsets[0], n_utt, size_t(mfcc_spec::bins(h->r.nfft))))
         return MFCC_HIP_ERROR_INVALID_PARAM;
-    SpectrumGuard spectrum(h);
-    return process_ragged_dev<float>(h, false, static_cast<const int16_t *>(d_pcm), offsets, n_utt, static_cast<float *>(d_out),
-                                     cap, frame_offsets);
+    return process_ragged_dev<float>(h, call_of(h, Kind::kSpectrum, false), samples_of(h), d_pcm, offsets, n_utt,
+                                     static_cast<float *>(d_out), cap, frame_offsets);
 }
 
 int mfcc_hip_spectrum_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_t nch, float *out, size_t cap,
                           size_t *n_frames) {
     if (!h || !mfcc_spec::call_fits(n, nch, size_t(mfcc_spec::bins(h->r.nfft)))) return MFCC_HIP_ERROR_INVALID_PARAM;
-    SpectrumGuard spectrum(h);
-    return process_host<float>(h, false, pcm, n, nch, out, cap, n_frames);
+    return process_host<float>(h, call_of(h, Kind::kSpectrum, false), samples_of(h), pcm, n, nch, out, cap, n_frames);
 }
 
 const char *mfcc_hip_spectrum_kernel_name(const mfcc_hip_handle *h) { return h ? mfcc_spec::name_of(h->spec_kernel) : ""; }
 
 // ---- the filterbank output (include/mfcc_hip.h: "filterbank"; kernel_fbank.hpp, fbank_plan.hpp; DESIGN.md section
-// 4.19): the spectrum entries' routes with the handle as a filterbank handle for the call (FbankGuard)
+// 4.19): the spectrum entries' routes on a Kind::kFbank call
 int mfcc_hip_set_fbank(mfcc_hip_handle *h, const mfcc_hip_fbank *p, const float *weights) {
     if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
     const int bins = mfcc_spec::bins(h->r.nfft);
@@ -2419,8 +2365,7 @@ int mfcc_hip_fbank_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size
     if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (!h->fb_dev) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (!mfcc_fbank::call_fits(n, nch, size_t(h->fb.n_bands))) return MFCC_HIP_ERROR_INVALID_PARAM;
-    FbankGuard fbank(h);
-    return dense_dev(h, false, d_pcm, n, stride, nch, halo, d_out, n_frames);
+    return dense_dev(h, call_of(h, Kind::kFbank, false), samples_of(h), d_pcm, n, stride, nch, halo, d_out, n_frames);
 }
 
 int mfcc_hip_fbank_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const size_t *offsets, size_t n_utt, void *d_out,
@@ -2431,17 +2376,15 @@ int mfcc_hip_fbank_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const s
     if (offsets && n_utt && offsets[n_utt] >= offsets[0] &&
         !mfcc_fbank::ragged_fits(offsets[n_utt] - offsets[0], n_utt, size_t(h->fb.n_bands)))
         return MFCC_HIP_ERROR_INVALID_PARAM;
-    FbankGuard fbank(h);
-    return process_ragged_dev<float>(h, false, static_cast<const int16_t *>(d_pcm), offsets, n_utt, static_cast<float *>(d_out),
-                                     cap, frame_offsets);
+    return process_ragged_dev<float>(h, call_of(h, Kind::kFbank, false), samples_of(h), d_pcm, offsets, n_utt,
+                                     static_cast<float *>(d_out), cap, frame_offsets);
 }
 
 int mfcc_hip_fbank_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_t nch, float *out, size_t cap, size_t *n_frames) {
     if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (!h->fb_dev) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (!mfcc_fbank::call_fits(n, nch, size_t(h->fb.n_bands))) return MFCC_HIP_ERROR_INVALID_PARAM;
-    FbankGuard fbank(h);
-    return process_host<float>(h, false, pcm, n, nch, out, cap, n_frames);
+    return process_host<float>(h, call_of(h, Kind::kFbank, false), samples_of(h), pcm, n, nch, out, cap, n_frames);
 }
 
 const char *mfcc_hip_fbank_kernel_name(const mfcc_hip_handle *h) {
@@ -2468,7 +2411,7 @@ int mfcc_hip_htk_weights(int nfft, int sample_rate, int n_bands, float low_hz, f
 int mfcc_hip_set_normalize(mfcc_hip_handle *h, int mode) {
     if (!h || mode < MFCC_HIP_NORMALIZE_NONE || mode > MFCC_HIP_NORMALIZE_MEAN_VAR) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
-    h->norm = mode;
+    h->post.norm = mode;
     return MFCC_HIP_SUCCESS;
 }
 
@@ -2507,8 +2450,8 @@ int mfcc_hip_set_pcen(mfcc_hip_handle *h, const mfcc_hip_pcen *p) {
     if (!h || (p && !pcen_ok(p))) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (p && !is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;      // PCEN reads log2 band energies
     if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
-    h->pcen_on = p != nullptr;
-    if (p) h->pcen = pcen_prm(*p);
+    h->post.pcen_on = p != nullptr;
+    if (p) h->post.pcen = pcen_prm(*p);
     return MFCC_HIP_SUCCESS;
 }
 
@@ -2527,9 +2470,9 @@ int mfcc_hip_set_normalize_window(mfcc_hip_handle *h, int window, int min_window
         return MFCC_HIP_ERROR_INVALID_PARAM;
     if (window && (min_window < 1 || min_window > window)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
-    h->norm_window = window;
-    h->norm_min_window = window ? min_window : 1;
-    h->norm_center = center;
+    h->post.norm_window = window;
+    h->post.norm_min_window = window ? min_window : 1;
+    h->post.norm_center = center;
     return MFCC_HIP_SUCCESS;
 }
 
@@ -2557,8 +2500,8 @@ int mfcc_hip_set_deltas(mfcc_hip_handle *h, int order, int window) {
     if (!h || order < 0 || order > 2 || window < 1 || window > MFCC_HIP_MAX_DELTA_WINDOW)
         return MFCC_HIP_ERROR_INVALID_PARAM;
     if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
-    h->delta_order = order;
-    h->delta_window = window;
+    h->post.delta_order = order;
+    h->post.delta_window = window;
     return MFCC_HIP_SUCCESS;
 }
 
@@ -2583,12 +2526,12 @@ int mfcc_hip_set_vad(mfcc_hip_handle *h, int mode, int column, float energy_thre
     if (!vad_args_ok(int(row_width(h->r)), column, energy_threshold, energy_mean_scale, frames_context, proportion_threshold))
         return MFCC_HIP_ERROR_INVALID_PARAM;
     if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
-    h->vad_mode = mode;
-    h->vad_column = column;
-    h->vad_threshold = energy_threshold;
-    h->vad_scale = energy_mean_scale;
-    h->vad_context = frames_context;
-    h->vad_proportion = proportion_threshold;
+    h->post.vad_mode = mode;
+    h->post.vad_column = column;
+    h->post.vad_threshold = energy_threshold;
+    h->post.vad_scale = energy_mean_scale;
+    h->post.vad_context = frames_context;
+    h->post.vad_proportion = proportion_threshold;
     return MFCC_HIP_SUCCESS;
 }
 
@@ -2760,16 +2703,6 @@ int mfcc_hip_set_input_rate(mfcc_hip_handle *h, int in_rate) {
 
 int mfcc_hip_input_rate(const mfcc_hip_handle *h) { return h ? h->input_rate : 0; }
 
-// the WAV readers hand 16-bit PCM to the host entry points whatever the handle's format: S16 for the scope
-struct PcmFormatGuard {
-    mfcc_hip_handle *h;
-    int fmt;
-    explicit PcmFormatGuard(mfcc_hip_handle *hh) : h(hh), fmt(hh->sample_fmt) { h->sample_fmt = MFCC_HIP_SAMPLE_S16; }
-    ~PcmFormatGuard() { h->sample_fmt = fmt; }
-    PcmFormatGuard(const PcmFormatGuard &) = delete;
-    PcmFormatGuard &operator=(const PcmFormatGuard &) = delete;
-};
-
 // float coefficients -> the int16 a `.mfcc` file holds: astype(np.int16) of software/lift.py:39 (truncate)
 static inline int16_t to_mfcc_i16(float v) {
     if (!(v == v)) v = 0.0f;
@@ -2782,21 +2715,20 @@ int mfcc_hip_convert_wav(mfcc_hip_handle *h, const char *wav_in, const char *mfc
                          size_t *n_frames_out) {
     if (!h || !wav_in || !mfcc_out) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
-    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;     // ... raw ones
-    if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... n_cep wide
-    if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                            // ... of every frame
+    if (has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;   // ... raw ones, n_cep wide, of every frame
     std::vector<int16_t> pcm;
     int rc = read_wav_i16(wav_in, rated(h) ? h->input_rate : h->r.sample_rate, pcm);
     if (rc) return rc;
     const size_t nf = count_frames(h->r, own_rate_len(h, pcm.size()));
     std::vector<int16_t> cep(nf * size_t(h->r.n_cep));
-    PcmFormatGuard pcm16(h);
+    // the file's 16-bit PCM, whatever the handle's sample format, at the rate the handle reads
+    const Samples pcm16{MFCC_HIP_SAMPLE_S16, h->input_rate};
     if (fixed) {
-        rc = mfcc_hip_process_fixed_i16(h, pcm.data(), pcm.size(), 1, cep.data(), cep.size(), nullptr);
+        rc = process_host<int16_t>(h, call_of(h, Kind::kFeatures, true), pcm16, pcm.data(), pcm.size(), 1, cep.data(), cep.size(), nullptr);
         if (rc) return rc;
     } else {
         std::vector<float> f(cep.size());
-        rc = mfcc_hip_process_i16(h, pcm.data(), pcm.size(), 1, f.data(), f.size(), nullptr);
+        rc = process_host<float>(h, call_of(h, Kind::kFeatures, false), pcm16, pcm.data(), pcm.size(), 1, f.data(), f.size(), nullptr);
         if (rc) return rc;
         for (size_t i = 0; i < f.size(); ++i) cep[i] = to_mfcc_i16(f[i]);
     }
@@ -2813,9 +2745,7 @@ int mfcc_hip_convert_wavs(mfcc_hip_handle *h, const char *const *wav_in, const c
                           int fixed, size_t *n_frames_each) {
     if (!h || (n_files && (!wav_in || !mfcc_out))) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
-    if (h->norm != MFCC_HIP_NORMALIZE_NONE || h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;     // ... raw ones
-    if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;                         // ... n_cep wide
-    if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;                            // ... of every frame
+    if (has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;   // ... raw ones, n_cep wide, of every frame
     std::vector<int16_t> pcm;
     std::vector<size_t> off(n_files + 1, 0), fo(n_files + 1, 0);
     for (size_t i = 0; i < n_files; ++i) {
@@ -2831,13 +2761,15 @@ int mfcc_hip_convert_wavs(mfcc_hip_handle *h, const char *const *wav_in, const c
     const size_t ncep = size_t(h->r.n_cep);
     std::vector<int16_t> cep(total * ncep);
     int rc;
-    PcmFormatGuard pcm16(h);
+    const Samples pcm16{MFCC_HIP_SAMPLE_S16, h->input_rate};
     if (fixed) {
-        rc = mfcc_hip_process_ragged_fixed_i16(h, pcm.data(), off.data(), n_files, cep.data(), cep.size(), fo.data());
+        rc = process_ragged<int16_t>(h, call_of(h, Kind::kFeatures, true), pcm16, pcm.data(), off.data(), n_files, cep.data(),
+                                     cep.size(), fo.data());
         if (rc) return rc;
     } else {
         std::vector<float> f(cep.size());
-        rc = mfcc_hip_process_ragged_i16(h, pcm.data(), off.data(), n_files, f.data(), f.size(), fo.data());
+        rc = process_ragged<float>(h, call_of(h, Kind::kFeatures, false), pcm16, pcm.data(), off.data(), n_files, f.data(),
+                                   f.size(), fo.data());
         if (rc) return rc;
         for (size_t i = 0; i < f.size(); ++i) cep[i] = to_mfcc_i16(f[i]);
     }
@@ -2908,7 +2840,7 @@ int stream_emit(mfcc_hip_stream *s, size_t total, size_t nf, void *out) {
     mfcc_hip_handle *h = s->h;
     const size_t esz = s->fixed ? sizeof(int16_t) : sizeof(float);
     const size_t bytes = nf * row_width(h->r) * esz;
-    int rc = launch(h, s->fixed, s->buf[s->cur], total, total + 1, 1, /*halo=*/1, s->d_out, nullptr, nf);
+    int rc = launch(h, call_of(h, Kind::kFeatures, s->fixed), s->buf[s->cur], total, total + 1, 1, /*halo=*/1, s->d_out, nullptr, nf);
     if (rc) return rc;
     HIP_TRY(h, hipMemcpyAsync(out, s->d_out, bytes, hipMemcpyDeviceToHost, h->stream));
     return MFCC_HIP_SUCCESS;
@@ -2922,10 +2854,10 @@ int mfcc_hip_stream_create(mfcc_hip_handle *h, int fixed, mfcc_hip_stream **out)
     if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
     *out = nullptr;
     if (h->destroy_pending) return MFCC_HIP_ERROR_INVALID_PARAM;        // the handle was already given back
-    if (h->norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // per-call statistics of a stream
-    if (h->pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;                           // ... and a per-call smoother
-    if (h->delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;     // deltas need 2 K N frames of lookahead
-    if (h->vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;        // the threshold's mean is a whole-segment statistic
+    if (h->post.norm != MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_ERROR_UNSUPPORTED;   // per-call statistics of a stream
+    if (h->post.pcen_on) return MFCC_HIP_ERROR_UNSUPPORTED;                           // ... and a per-call smoother
+    if (h->post.delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;     // deltas need 2 K N frames of lookahead
+    if (h->post.vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;        // the threshold's mean is a whole-segment statistic
     if (rated(h)) return MFCC_HIP_ERROR_UNSUPPORTED;           // a line's rate conversion keeps state between pushes
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     mfcc_hip_stream *s = new (std::nothrow) mfcc_hip_stream();
@@ -2984,12 +2916,12 @@ int mfcc_hip_stream_push(mfcc_hip_stream *s, const int16_t *samples, size_t n, v
     DeviceGuard guard(h->device);
     int rc = stream_reserve(s, total, nf * ncep * sizeof(float));
     if (rc) return rc;
-    if (n && decodes(h)) {
+    if (n && decodes(h->sample_fmt)) {
         // the raw bytes to the device, decoded straight to their place behind the pending samples
-        const size_t raw = n * sample_bytes(h);
+        const size_t raw = n * sample_bytes(h->sample_fmt);
         if ((rc = ensure(h, h->d_raw, raw + 64)) || (rc = scratch_acquire(h))) return rc;
         HIP_TRY(h, hipMemcpyAsync(h->d_raw.p, samples, raw, hipMemcpyHostToDevice, h->stream));
-        if ((rc = decode_rows(h, h->d_raw.p, n, 1, n, s->buf[s->cur] + 1 + s->pending, n)) || (rc = scratch_release(h)))
+        if ((rc = decode_rows(h, h->sample_fmt, h->d_raw.p, n, 1, n, s->buf[s->cur] + 1 + s->pending, n)) || (rc = scratch_release(h)))
             return rc;
     } else if (n) {
         HIP_TRY(h, hipMemcpyAsync(s->buf[s->cur] + 1 + s->pending, samples, n * sizeof(int16_t), hipMemcpyHostToDevice,
@@ -3134,10 +3066,11 @@ int bank_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const
     if (rc || !l.n_rec) return rc;
     // a sample format: the span offsets[0] .. offsets[n] of the chunks is decoded into the handle's scratch area in front
     // of the parking kernel, which then reads its chunks there, counted from the span's start
-    const bool dec = decodes(h);
+    const int fmt = h->sample_fmt;
+    const bool dec = decodes(fmt);
     const size_t span = offsets[b->n] - offsets[0];
-    const void *d_span = dec ? sample_at(h, d_samples, offsets[0] - shift) : nullptr;
-    if (dec && !sample_aligned(h, d_samples)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const void *d_span = dec ? sample_at(fmt, d_samples, offsets[0] - shift) : nullptr;
+    if (dec && !sample_aligned(fmt, d_samples)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (dec) shift = offsets[0];
     DeviceGuard guard(h->device);
     mfcc_hip_handle::PinnedDesc *pd = nullptr;
@@ -3147,7 +3080,7 @@ int bank_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const
     if (dec && (rc = ensure(h, h->d_dec, span * sizeof(int16_t) + 64))) return rc;
     if ((rc = desc_stage(h, h->d_out, l.out_bytes, pd, l.desc_ll))) return rc;
     if (dec) {
-        if ((rc = decode_rows(h, d_span, span, 1, span, static_cast<int16_t *>(h->d_dec.p), span))) return rc;
+        if ((rc = decode_rows(h, fmt, d_span, span, 1, span, static_cast<int16_t *>(h->d_dec.p), span))) return rc;
         d_samples = static_cast<const int16_t *>(h->d_dec.p);
     }
     int16_t *d_w = static_cast<int16_t *>(h->d_in.p);
@@ -3157,7 +3090,7 @@ int bank_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const
                        (long long)l.stride, h->r.frame_len, h->r.hop);
     if (l.n_active) {
         void *d_rows = l.direct ? d_out : static_cast<char *>(h->d_out.p) + l.raw_off;
-        if ((rc = launch(h, b->fixed, d_w, l.stride - 1, l.stride, l.n_active, /*halo=*/1, d_rows, nullptr, l.nfmax))) return rc;
+        if ((rc = launch(h, call_of(h, Kind::kFeatures, b->fixed), d_w, l.stride - 1, l.stride, l.n_active, /*halo=*/1, d_rows, nullptr, l.nfmax))) return rc;
         bank_passes(b, l, d_out);
     }
     HIP_TRY(h, hipGetLastError());
@@ -3211,7 +3144,7 @@ int bank_end(mfcc_hip_bank *b, const std::vector<size_t> &list, bool give, void 
                        desc_table<mfcc_bank::Rec>(h, l.bank), (long long)l.n_rec, (long long)l.stride, h->r.frame_len);
     if (emit) {
         void *d_rows = l.direct ? b->st_out.p : static_cast<char *>(h->d_out.p) + l.raw_off;
-        if ((rc = launch(h, b->fixed, d_w, l.stride - 1, l.stride, l.n_active, /*halo=*/1, d_rows, nullptr, 1))) return rc;
+        if ((rc = launch(h, call_of(h, Kind::kFeatures, b->fixed), d_w, l.stride - 1, l.stride, l.n_active, /*halo=*/1, d_rows, nullptr, 1))) return rc;
     }
     bank_passes(b, l, b->st_out.p);
     if (result_bytes) HIP_TRY(h, hipMemcpyAsync(out, b->st_out.p, result_bytes, hipMemcpyDeviceToHost, h->stream));
@@ -3293,7 +3226,7 @@ int bank_create_checked(mfcc_hip_handle *h, int fixed, bool online, size_t n_str
     if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
     *out = nullptr;
     if (h->destroy_pending || !n_streams || (p && !pcen_ok(p))) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (has_post(h)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (rated(h)) return MFCC_HIP_ERROR_UNSUPPORTED;           // a line's rate conversion keeps state between pushes
     if (p && !is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
@@ -3425,10 +3358,10 @@ int mfcc_hip_bank_push(mfcc_hip_bank *b, const int16_t *samples, const size_t *o
     if (!span) return MFCC_HIP_SUCCESS;
     if (!samples) return MFCC_HIP_ERROR_INVALID_PARAM;
     DeviceGuard guard(h->device);
-    const size_t raw = span * sample_bytes(h);              // the chunks as they are: the device push decodes them
+    const size_t raw = span * sample_bytes(h->sample_fmt);              // the chunks as they are: the device push decodes them
     if ((rc = ensure(h, b->st_in, raw + 64))) return rc;
     if ((rc = ensure(h, b->st_out, total * W * esz + 64))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(b->st_in.p, sample_at(h, samples, offsets[0]), raw, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(b->st_in.p, sample_at(h->sample_fmt, samples, offsets[0]), raw, hipMemcpyHostToDevice, h->stream));
     rc = bank_advance(b, static_cast<const int16_t *>(b->st_in.p), offsets[0], offsets, b->st_out.p, total * W, frame_offsets);
     if (!rc && total) HIP_TRY(h, hipMemcpyAsync(out, b->st_out.p, total * W * esz, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));        // `samples` and `out` belong to the caller again
