@@ -695,15 +695,83 @@ __device__ __forceinline__ void mel_bf_blocks(const f32x4 (&acc)[SetsBf<DENSE>::
     }
 }
 
+// ---- straight-line pieces of a four-wave tile.  The power tile of the spectrum and filterbank kernels
+// (kernel_spectrum.hpp: power_tile_loop) is made of them.  tile_loop_w4 below and the bank kernel
+// (kernel_fused512_h160_mb.hpp) call one only where every instantiation still compiles to the instructions it had with
+// its own lines, and restate the others; each loop's header says which and why (DESIGN.md section 4.1 has the diffs).  A
+// fix to one of these pieces belongs in the helper and in the loops that restate it.
+
+// The workgroup's first tile: the cursor's start, the tile's span fetched and parked by the fetchers, and the barrier
+// behind which every wave reads it (and whatever the kernel staged in LDS before the call).  TILE_HOP: samples between
+// consecutive tiles; shift: the span's alignment shift (0 when the workgroup has no tile)
+template <int TILE_HOP>
+__device__ __forceinline__ Cursor first_tile(const mfcc_k::StreamDesc s, const LaunchGeom g, float *Sf, int fetcher,
+                                             bool fetches, Fetch &fx, int &shift) {
+    Cursor cur;
+    cur.ch = (int)(blockIdx.x / (unsigned)g.tiles_per_ch);
+    cur.t_in = (int)(blockIdx.x - (unsigned)cur.ch * (unsigned)g.tiles_per_ch);
+    cur.ptr = s.pcm + (long long)cur.ch * s.ch_stride + (long long)cur.t_in * TILE_HOP;
+    shift = 0;
+    if (cur.ch < g.n_ch) {
+        const Window w0 = window_of(cur, g);
+        shift = w0.shift;
+        if (fetches) {
+            fetch_window<TILE_HOP>(s, w0, fetcher, fx);
+            park_window(Sf, fetcher, fx);
+        }
+    }
+    __syncthreads();
+    return cur;
+}
+
+// pass 2's input: a column of a frame out of the transpose tile T (trow: T + frame * kTFrame + k1 * kTRow), 16 complex
+// values on 8 ds_read_b128.  The caller forms the address: with it formed in here tile_loop_w4's prologue is scheduled
+// in another order
+__device__ __forceinline__ void t_column(const f32x4 *trow, mfcc_codelets::v2f (&x)[16]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const f32x4 a = trow[i];
+        x[2 * i] = (mfcc_codelets::v2f){a[0], a[1]};
+        x[2 * i + 1] = (mfcc_codelets::v2f){a[2], a[3]};
+    }
+}
+
+// pass 2: the complex FFT-16 over n2 of that column with the power in its last layer, pp[k2] = (|z[k2]|^2, |z[k2 + 8]|^2)
+// (the codelet's last layer is transposed): bins k1 + 32 k2 in .x, 32 (8 - k2) - k1 in .y
+__device__ __forceinline__ void pass2_power(const float *Tt, int lo, int k1, mfcc_codelets::v2f (&pp)[8]) {
+    mfcc_codelets::v2f x[16];
+    t_column(reinterpret_cast<const f32x4 *>(Tt + lo * kTFrame + k1 * kTRow), x);
+    mfcc_codelets::cfft16_pow(x, pp);
+}
+
+// column 16 of frame lo -> bins 16 + 32 j: a 16 x 16 real DFT matrix on four fp32 MFMAs (ax[0 .. 3]: col16_dft_rows);
+// lane (lo, q) ends with the power of bins 16 + 64 q (s0) and 48 + 64 q (s1)
+template <int N>
+__device__ __forceinline__ void col16_power(const float *Vt, const float (&ax)[N], int lo, int q, float &s0, float &s1) {
+    const float v0 = Vt[lo * kVStride + 0 + q], v1 = Vt[lo * kVStride + 4 + q];
+    const float v2 = Vt[lo * kVStride + 8 + q], v3 = Vt[lo * kVStride + 12 + q];
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 sp = zero, sp2 = zero;
+    sp = MFCC_MFMA(ax[0], v0, sp);
+    sp2 = MFCC_MFMA(ax[1], v1, sp2);
+    sp = MFCC_MFMA(ax[2], v2, sp);
+    sp2 = MFCC_MFMA(ax[3], v3, sp2);
+    sp += sp2;
+    s0 = fmaf(sp[0], sp[0], sp[1] * sp[1]);
+    s1 = fmaf(sp[2], sp[2], sp[3] * sp[3]);
+}
+
 // ---- the tile loop of mfcc_fused512_kernel (HOP = 170, LOGMEL = false) and of mfcc_fused512_h160_kernel (HOP = 160:
 // kernel_fused512_h160.hpp): the header's tile, written once.  HOP: samples between consecutive frames -- the lane's slot
 // in the parked span, the cursor's start, the tile step of the fetch's edge path; LOGMEL: the tail stores the n_mel log2
 // values instead of running the DCT; lds: lds_words(kQWords, DCX) floats.  The arguments are taken by value, as a kernel
 // takes them: with references the compiler allocates other registers and the instantiations' rates move by up to 4 %
 // either way.
-// kernel_spectrum.hpp: mfcc_spectrum512_kernel restates this loop's fetch / park order, pass 1, the transpose, pass 2 and
-// the column-16 MFMAs without the mel, log and DCT phases (a copy, so that this loop keeps its registers and its rate): a
-// fix to any of those here belongs there too.
+// Of the helpers above it calls t_column: pass 2 here is t_column, the MFCC_STAMP of the diagnostic build and the
+// codelet, which is pass2_power with a stamp in the middle.  It restates first_tile (the cursor's start, the first
+// fetch and park, the barrier): as a call, every instantiation gets another loop structure (2 more VALU instructions,
+// in the DCT forms also 7 v_mov_b32 and 7 s_branch).  Role 1 restates col16_power's four MFMAs because it issues them
+// between its mel MFMAs (mel_bf_all's After), where the helper's straight line cannot go.
 template <int HOP, bool DENSE, bool DCX, bool LOGMEL>
 __device__ __forceinline__ void tile_loop_w4(const mfcc_k::StreamDesc s, const FusedTables t, const LaunchGeom g,
                                              float *__restrict__ out, float *lds) {
@@ -842,13 +910,7 @@ __device__ __forceinline__ void tile_loop_w4(const mfcc_k::StreamDesc s, const F
         float pw[16];                            // |X|^2 at bin(wave, q, k2)
         {
             v2f x[16];
-            const f32x4 *trow = reinterpret_cast<const f32x4 *>(Tt + lo * kTFrame + (4 * wave + q) * kTRow);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const f32x4 a = trow[i];
-                x[2 * i] = (v2f){a[0], a[1]};
-                x[2 * i + 1] = (v2f){a[2], a[3]};
-            }
+            t_column(reinterpret_cast<const f32x4 *>(Tt + lo * kTFrame + (4 * wave + q) * kTRow), x);
             MFCC_STAMP(1);
             v2f pp[8];                               // (|z[k2]|^2, |z[k2 + 8]|^2): the codelet's last layer is transposed
             mfcc_codelets::cfft16_pow(x, pp);

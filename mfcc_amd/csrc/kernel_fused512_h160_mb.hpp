@@ -6,6 +6,11 @@
 // -- without the DC path and with the mel contraction driven by the handle's matrix instead of a compile-time list.
 // fetch_window<TILE_HOP>, parking, split_power and the host table helpers are mfcc_fused's; the loop itself is repeated
 // here (DESIGN.md section 4.1 says why), so a change to the passes, the barriers or the parking belongs in both.
+// It restates all three of kernel_fused512.hpp's tile helpers -- first_tile (the cursor's start up to __syncthreads()),
+// pass2_power (the T column and cfft16_pow) and col16_power (role 1's four fp32 MFMAs, issued here in front of mel_sets
+// and summed behind it) -- because on each of them this kernel compiles to other instructions than on its own lines:
+// 2 to 4 instructions more with first_tile, commuted v_pk_add_f32 operands with pass2_power, 310 reordered lines with
+// t_column alone, 3 instructions fewer and another LDS read pattern with col16_power.
 //
 //  sets     the host walks the matrix with the bin <-> (wave, quarter, k2) map of mfcc_fused::build_tables and lists the
 //           (filter block, K group) pairs that carry a non-zero weight (build_tables below; 4 to 6 of the 8 possible for

@@ -12,7 +12,10 @@
 // transpose tile T and the column-16 tile V; barrier B1; pass 2 is the complex FFT-16 over n2 with the power in its last
 // layer (cfft16_pow), which leaves lane (frame lo, k1 = 4 wave + q) with the 16 bins k1 + 32 k2 (k2 < 8) and
 // 32 (16 - k2) - k1 (k2 >= 8); wave 1 also turns column 16 into the bins 16 + 32 j with the 16 x 16 real DFT matrix on
-// four fp32 MFMAs.
+// four fp32 MFMAs.  That tile, up to the barrier B2 behind which the power lies in the LDS image R, is power_tile_loop
+// below, written once for this kernel and for mfcc_fbank512_kernel (kernel_fbank.hpp) out of the helpers of
+// kernel_fused512.hpp (first_tile, pass2_power, col16_power); a kernel adds where the image starts and what happens
+// to it behind B2.  The generic kernel is the front end of kernels_generic.hpp with the output row as its target.
 //
 // What is new is where the power goes.  The fused MFCC kernels contract it out of registers; here all 257 bins of all 16
 // frames leave the chip: 16 448 bytes per tile against 5 440 bytes of samples in.  The rows of a tile are ONE contiguous
@@ -49,58 +52,24 @@ namespace mfcc_spec {
 
 // ------------------------------------------------------------------------------ generic
 
-struct GenericTables {
-    const float  *window;     // [NFFT]       the handle's window: periodic Hamming over the frame, zeros up to NFFT
-    const float2 *tw_fft;     // [NFFT/2]     W_M^m, M = NFFT/2
-    const float2 *tw_split;   // [NFFT/2 + 1] W_NFFT^k
-    float inv_scale2;         // 1 / power_scale^2
-};
-
-// One frame per wave, four waves per workgroup: mfcc_float_generic_kernel's frame staging, Stockham FFT and real split
-// (kernels_generic.hpp: gen_stage_frame, gen_stockham, gen_split_power), then P[k] / power_scale^2 straight to the row --
-// lane l stores bins l, l + 64, ...: 256 contiguous bytes per store instruction.
+// One frame per wave, four waves per workgroup: the generic front end of kernels_generic.hpp (gen_stage_tables,
+// FrameCursor, gen_power_row), with P[k] / power_scale^2 straight to the row -- lane l stores bins l, l + 64, ...: 256
+// contiguous bytes per store instruction.
 template <int NFFT>
-__global__ __launch_bounds__(mfcc_k::kBlock) void mfcc_spectrum_generic_kernel(mfcc_k::StreamDesc s, GenericTables t,
+__global__ __launch_bounds__(mfcc_k::kBlock) void mfcc_spectrum_generic_kernel(mfcc_k::StreamDesc s, mfcc_k::PowerTables t,
                                                                              float *__restrict__ out) {
     using namespace mfcc_k;
     constexpr int M = NFFT / 2;
     __shared__ float2 bufA[kWavesPerBlock][M];
     __shared__ float2 bufB[kWavesPerBlock][M + 1];
-    // the window and both twiddle tables in LDS up to 512 points, in global memory at 1024 (kernels_generic.hpp says why)
-    constexpr bool kStage = NFFT <= 512;
-    __shared__ float  winl[kStage ? NFFT : 1];
-    __shared__ float2 twl[kStage ? M : 1];
-    __shared__ float2 twsl[kStage ? M + 1 : 1];
-    if constexpr (kStage) {
-        for (int i = threadIdx.x; i < NFFT; i += kBlock) winl[i] = t.window[i];
-        for (int i = threadIdx.x; i < M; i += kBlock) twl[i] = t.tw_fft[i];
-        for (int i = threadIdx.x; i <= M; i += kBlock) twsl[i] = t.tw_split[i];
-    }
-    const float *const win_p = kStage ? winl : t.window;
-    const float2 *const tw_p = kStage ? twl : t.tw_fft;
-    const float2 *const tws_p = kStage ? twsl : t.tw_split;
+    const GenTables p = gen_stage_tables<NFFT>(t.window, t.tw_fft, t.tw_split);
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const long long waves_total = (long long)gridDim.x * kWavesPerBlock;
-    const long long step_ch = waves_total / s.frames_per_ch, step_f = waves_total % s.frames_per_ch;
-    long long fid = (long long)blockIdx.x * kWavesPerBlock + wave;
-    long long ch = fid / s.frames_per_ch, f = fid % s.frames_per_ch;
-
-    for (; fid < s.total_frames; fid += waves_total, ch += step_ch, f += step_f) {
-        if (f >= s.frames_per_ch) {
-            f -= s.frames_per_ch;
-            ++ch;
-        }
-        const int16_t *base = s.pcm + ch * s.ch_stride;
-        gen_stage_frame<NFFT>(s, base, f * (long long)s.hop, win_p, reinterpret_cast<float *>(bufA[wave]), lane);
-        wave_sync();
-        float2 *src = bufA[wave];
-        float2 *dst = bufB[wave];
-        gen_stockham<M>(src, dst, tw_p, lane);
-        float *row = out + fid * (M + 1);
-        for (int k = lane; k <= M; k += 64) row[k] = gen_split_power<M>(src, tws_p, k) * t.inv_scale2;
+    for (FrameCursor c(s, wave); c.fid < s.total_frames; c.next()) {
+        c.carry(s);
+        gen_power_row<NFFT>(s, c, p, t.inv_scale2, bufA[wave], bufB[wave], lane, [&](float *) { return out + c.fid * (M + 1); });
         wave_sync();                             // the next frame's staging overwrites what the split read
     }
 }
@@ -109,16 +78,13 @@ inline const char *generic_name() { return name_of(Kernel::kGeneric); }
 
 // false: an nfft the library does not take
 #ifndef MFCC_NO_LAUNCHERS          // kernel_fused512.hpp: launch
-inline bool launch_generic(const mfcc_k::StreamDesc &s, const GenericTables &t, int nfft, float *out, int n_cu,
+inline bool launch_generic(const mfcc_k::StreamDesc &s, const mfcc_k::PowerTables &t, int nfft, float *out, int n_cu,
                            hipStream_t stream) {
-    long long blocks = (s.total_frames + mfcc_k::kWavesPerBlock - 1) / mfcc_k::kWavesPerBlock;
-    const long long cap = (long long)n_cu * 128;         // the generic float kernel's grid (mfcc_hip.hip: launch)
-    if (blocks > cap) blocks = cap;
+    const dim3 grid(mfcc_k::generic_grid(s, n_cu));
     switch (nfft) {
 #define MFCC_SPEC_CASE(N)                                                                                              \
     case N:                                                                                                            \
-        hipLaunchKernelGGL((mfcc_spectrum_generic_kernel<N>), dim3((unsigned)blocks), dim3(mfcc_k::kBlock), 0, stream, \
-                           s, t, out);                                                                                 \
+        hipLaunchKernelGGL((mfcc_spectrum_generic_kernel<N>), grid, dim3(mfcc_k::kBlock), 0, stream, s, t, out);       \
         break;
         MFCC_SPEC_CASE(64)
         MFCC_SPEC_CASE(128)
@@ -141,7 +107,6 @@ using mfcc_fused::kTFrame;
 using mfcc_fused::kTRow;
 using mfcc_fused::kVStride;
 using mfcc_fused::kWaves;
-using mfcc_fused::kFetchers;
 using mfcc_fc::f32x4;
 using mfcc_fc::Cursor;
 using mfcc_fc::LaunchGeom;
@@ -150,7 +115,8 @@ using mfcc_fc::Window;
 static_assert(kTile == mfcc_fused::kTile && kFusedNfft == kNfft, "spectrum_plan.hpp restates the fused tile");
 
 // LDS of the kernel: T | V | S | R
-constexpr int kLdsWords = kTile * kTFrame + kTile * kVStride + kSUsed + kRWords;
+constexpr int kTileWords = kTile * kTFrame + kTile * kVStride + kSUsed;       // T | V | S: where the image R starts
+constexpr int kLdsWords = kTileWords + kRWords;
 
 struct FusedTables {
     const float *win;     // [16 n2][32 n1]  window[16 n1 + n2] / 64 (pre-emphasis x32, real-FFT split x2)
@@ -192,12 +158,25 @@ __device__ __forceinline__ void store_tile(const float *R, float *__restrict__ o
     if (tid < g.tail) o[t0 + tid] = R[lds_word(g, t0 + tid)];
 }
 
-template <int HOP>
-__global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void mfcc_spectrum512_kernel(const mfcc_k::StreamDesc s, const FusedTables t, const LaunchGeom g, float *__restrict__ out) {
+// first row of tile `me` among the output's rows (uniform)
+__device__ __forceinline__ long long tile_row0(const mfcc_k::StreamDesc &s, const Cursor &me) {
+    return (long long)me.ch * s.frames_per_ch + (long long)me.t_in * kTile;
+}
+
+// The power tile of mfcc_spectrum512_kernel and mfcc_fbank512_kernel (kernel_fbank.hpp), written once: the header's
+// tile up to barrier B2, behind which the power of the tile's 16 frames x 257 bins lies in the LDS image R.  lds: T | V
+// | S | R, and behind them whatever the kernel keeps of its own.  The two kernels give their difference as callables,
+// the way mfcc_fused::mel_bf_all takes its After:
+//   image_base(me, rows) -> the word of R at which the tile's row 0 starts (uniform; called between B1 and pass 2)
+//   tail(me, rows, tid, lo, q, wave, R)  what happens to the image behind B2; nothing waits for its stores, and the
+//                                        next tile's B1 is what lets R be rewritten
+// me: the tile's cursor; rows: its frames inside the channel (16, fewer in a channel's last tile).  Plain template
+// parameters and the arguments by value, as mfcc_fused::tile_loop_w4 takes them.
+template <int HOP, typename ImageBase, typename Tail>
+__device__ __forceinline__ void power_tile_loop(const mfcc_k::StreamDesc s, const FusedTables t, const LaunchGeom g,
+                                                float *lds, ImageBase image_base, Tail tail) {
     using mfcc_codelets::v2f;
     using mfcc_fused::Fetch;
-    __shared__ __attribute__((aligned(16))) float lds[kLdsWords];
     constexpr int kTileHopT = kTile * HOP;           // samples between consecutive tiles
     static_assert(7 + (kTile - 1) * HOP + kNfft <= kSUsed, "a tile's frames must lie inside the parked span");
     const int tid = threadIdx.x;
@@ -210,7 +189,7 @@ void mfcc_spectrum512_kernel(const mfcc_k::StreamDesc s, const FusedTables t, co
     float *const Tt = lds;                                         // [16 frames][584]
     float *const Vt = Tt + kTile * kTFrame;                        // [16 frames][18]
     float *const Sf = Vt + kTile * kVStride;                       // pre-emphasised sample span, fp32
-    float *const Rt = Sf + kSUsed;                                 // pad + [16 frames][257]: the tile's rows
+    float *const Rt = Sf + kSUsed;                                 // image_base + [16 frames][257]: the tile's rows
 
     // per-lane constants, resident for the whole kernel
     v2f wp[16], tw[16];
@@ -225,31 +204,16 @@ void mfcc_spectrum512_kernel(const mfcc_k::StreamDesc s, const FusedTables t, co
 
     const int lane_slot = fr_id * HOP + lo;
     // three waves fetch and park the span, as in the MFCC kernel (its 192 fetchers cover the 3072 slots); wave 0 does
-    // not, and has the head and the tail of the store in exchange
+    // not, and has the head and the tail of the spectrum's store in exchange
     const int fetcher = (wave - 1) * 64 + lane;
     const bool fetches = wave != 0;
     // the lane's 16 bins of frame lo in pass 2, as words of a row: k1 + 32 k2 going up, 32 (16 - k2) - k1 going down
     const int k1 = 4 * wave + q;
 
-    Cursor cur;
-    cur.ch = (int)(blockIdx.x / (unsigned)g.tiles_per_ch);
-    cur.t_in = (int)(blockIdx.x - (unsigned)cur.ch * (unsigned)g.tiles_per_ch);
-    cur.ptr = s.pcm + (long long)cur.ch * s.ch_stride + (long long)cur.t_in * kTileHopT;
-
     Fetch fx;
-    int shift = 0;
-    if (cur.ch < g.n_ch) {
-        const Window w0 = mfcc_fc::window_of(cur, g);
-        shift = w0.shift;
-        if (fetches) {
-            mfcc_fused::fetch_window<kTileHopT>(s, w0, fetcher, fx);
-            mfcc_fused::park_window(Sf, fetcher, fx);
-        }
-    }
-    __syncthreads();
+    int shift;
+    Cursor cur = mfcc_fused::first_tile<kTileHopT>(s, g, Sf, fetcher, fetches, fx, shift);
 
-    const unsigned long long out_word = reinterpret_cast<uintptr_t>(out) >> 2;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     while (cur.ch < g.n_ch) {
         // ---------------- pass 1: windowed real FFT-32 over n1 of the pre-emphasised samples
         v2f ep[16];
@@ -275,28 +239,17 @@ void mfcc_spectrum512_kernel(const mfcc_k::StreamDesc s, const FusedTables t, co
         for (int c = 0; c < 16; ++c) tcol0[c * (kTRow / 2)] = ty[c];
         Vt[fr_id * kVStride + lo] = y16;
         mfcc_fc::lds_barrier();                // B1: T and V of all 16 frames are in LDS; S is consumed, and so is R: every
-                                               // wave has read its part of the previous tile's image on its way here
+                                               // wave has run its part of the previous tile's tail on its way here
 
-        // the tile's span of the output (uniform)
-        const long long fr0 = (long long)me.t_in * kTile;
-        const long long rows_left = s.frames_per_ch - fr0;
+        // the tile's rows (uniform)
+        const long long rows_left = s.frames_per_ch - (long long)me.t_in * kTile;
         const int rows = rows_left < kTile ? (int)rows_left : kTile;
-        const long long first = ((long long)me.ch * s.frames_per_ch + fr0) * kFusedBins;
-        const StoreGeom sg = store_geom(out_word + (unsigned long long)first, rows, kFusedBins);
+        float *const row = Rt + image_base(me, rows) + lo * kFusedBins;
 
         // ---------------- pass 2: complex FFT-16 over n2 for frame lo, column k1; the power goes to row lo of R
         {
-            v2f x[16];
-            const f32x4 *trow = reinterpret_cast<const f32x4 *>(Tt + lo * kTFrame + k1 * kTRow);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const f32x4 a = trow[i];
-                x[2 * i] = (v2f){a[0], a[1]};
-                x[2 * i + 1] = (v2f){a[2], a[3]};
-            }
-            v2f pp[8];                               // (|z[k2]|^2, |z[k2 + 8]|^2)
-            mfcc_codelets::cfft16_pow(x, pp);
-            float *row = Rt + sg.pad + lo * kFusedBins;
+            v2f pp[8];
+            mfcc_fused::pass2_power(Tt, lo, k1, pp);
 #pragma unroll
             for (int k2 = 0; k2 < 8; ++k2) row[k1 + 32 * k2] = pp[k2].x * inv;
             // k2 = 8 .. 15: bins 32 (16 - k2) - k1.  Column 0 is real-input symmetric there: bin 256 (k2 = 8) is its
@@ -308,28 +261,34 @@ void mfcc_spectrum512_kernel(const mfcc_k::StreamDesc s, const FusedTables t, co
             }
         }
         if (wave == 1) {
-            // column 16 -> bins 16 + 32 j: a 16 x 16 real DFT matrix on four fp32 MFMAs; lane (lo, q) ends with
-            // (Re, Im) of bins 16 + 64 q and 48 + 64 q of frame lo
-            const float v0 = Vt[lo * kVStride + 0 + q], v1 = Vt[lo * kVStride + 4 + q];
-            const float v2 = Vt[lo * kVStride + 8 + q], v3 = Vt[lo * kVStride + 12 + q];
-            f32x4 sp = zero, sp2 = zero;
-            sp = MFCC_MFMA(ax[0], v0, sp);
-            sp2 = MFCC_MFMA(ax[1], v1, sp2);
-            sp = MFCC_MFMA(ax[2], v2, sp);
-            sp2 = MFCC_MFMA(ax[3], v3, sp2);
-            sp += sp2;
-            float *row = Rt + sg.pad + lo * kFusedBins;
-            row[16 + 64 * q] = fmaf(sp[0], sp[0], sp[1] * sp[1]) * inv;
-            row[48 + 64 * q] = fmaf(sp[2], sp[2], sp[3] * sp[3]) * inv;
+            float s0, s1;
+            mfcc_fused::col16_power(Vt, ax, lo, q, s0, s1);
+            row[16 + 64 * q] = s0 * inv;
+            row[48 + 64 * q] = s1 * inv;
         }
         // park the next tile's sample span (every read of the current one happened before B1)
         if (more && fetches) mfcc_fused::park_window(Sf, fetcher, fx);
         shift = next_shift;
         mfcc_fc::lds_barrier();                // B2: R and S are in LDS, T and V may be overwritten
 
-        // ---------------- store: the image -> HBM.  Nothing waits for the stores: the next barrier orders LDS only
-        store_tile(Rt, out + first, sg, tid);
+        tail(me, rows, tid, lo, q, wave, Rt);
     }
+}
+
+template <int HOP>
+__global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void mfcc_spectrum512_kernel(const mfcc_k::StreamDesc s, const FusedTables t, const LaunchGeom g, float *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float lds[kLdsWords];
+    // the tile's span of the output starts at float first(me); its store geometry (uniform)
+    const unsigned long long out_word = reinterpret_cast<uintptr_t>(out) >> 2;
+    auto first = [&](const Cursor &me) { return tile_row0(s, me) * kFusedBins; };
+    auto geom = [&](const Cursor &me, int rows) { return store_geom(out_word + (unsigned long long)first(me), rows, kFusedBins); };
+    // the image starts behind the geometry's pad; behind B2 it goes to HBM.  Nothing waits for the stores: the next
+    // barrier orders LDS only
+    power_tile_loop<HOP>(s, t, g, lds, [&](const Cursor &me, int rows) { return geom(me, rows).pad; },
+                         [&](const Cursor &me, int rows, int tid, int, int, int, const float *R) {
+                             store_tile(R, out + first(me), geom(me, rows), tid);
+                         });
 }
 
 inline const char *fused_name() { return name_of(Kernel::kFused512); }

@@ -70,8 +70,64 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// ---- the three stages every generic float kernel shares (mfcc_float_generic_kernel below, mfcc_spectrum_generic_kernel
-// in kernel_spectrum.hpp).  One wave, one frame; the caller puts a wave_sync() where a stage's LDS writes are read.
+// ---- the front end every generic float kernel shares (mfcc_float_generic_kernel below, mfcc_spectrum_generic_kernel in
+// kernel_spectrum.hpp, mfcc_fbank_generic_kernel in kernel_fbank.hpp): the tables, the frame cursor, the three stages.
+
+// The grid of those kernels: a workgroup per four frames, at most 128 per CU (measured: 8 per CU 3.55 ms, 32 3.24,
+// 128 3.06 at nfft 256)
+inline unsigned generic_grid(const StreamDesc &s, int n_cu) {
+    const long long blocks = (s.total_frames + kWavesPerBlock - 1) / kWavesPerBlock, cap = (long long)n_cu * 128;
+    return (unsigned)(blocks < cap ? blocks : cap);
+}
+
+// Up to 512 points the window and both twiddle tables are staged in LDS, in global memory at 1024
+// (mfcc_float_generic_kernel says why)
+constexpr bool gen_staged(int nfft) { return nfft <= 512; }
+
+// where the frame loop reads them
+struct GenTables {
+    const float *win;
+    const float2 *tw, *tws;
+};
+
+// Stages the three tables (all 256 threads; the caller's __syncthreads() publishes them) or passes the global ones on
+template <int NFFT>
+__device__ __forceinline__ GenTables gen_stage_tables(const float *window, const float2 *tw_fft, const float2 *tw_split) {
+    constexpr int M = NFFT / 2;
+    constexpr bool kStage = gen_staged(NFFT);
+    __shared__ float  winl[kStage ? NFFT : 1];
+    __shared__ float2 twl[kStage ? M : 1];
+    __shared__ float2 twsl[kStage ? M + 1 : 1];
+    if constexpr (kStage) {
+        for (int i = threadIdx.x; i < NFFT; i += kBlock) winl[i] = window[i];
+        for (int i = threadIdx.x; i < M; i += kBlock) twl[i] = tw_fft[i];
+        for (int i = threadIdx.x; i <= M; i += kBlock) twsl[i] = tw_split[i];
+    }
+    return GenTables{kStage ? winl : window, kStage ? twl : tw_fft, kStage ? twsl : tw_split};
+}
+
+// Frame cursor of a wave: frame fid = frame f of channel ch, advanced by the number of waves in the grid without a
+// division (a 64-bit division per frame cost as many instructions as a 256-point FFT).
+//   for (FrameCursor c(s, wave); c.fid < s.total_frames; c.next()) { c.carry(s); ... }
+struct FrameCursor {
+    long long fid, ch, f, waves_total, step_ch, step_f;
+    __device__ __forceinline__ FrameCursor(const StreamDesc &s, int wave) {
+        waves_total = (long long)gridDim.x * kWavesPerBlock;
+        step_ch = waves_total / s.frames_per_ch, step_f = waves_total % s.frames_per_ch;
+        fid = (long long)blockIdx.x * kWavesPerBlock + wave;
+        ch = fid / s.frames_per_ch, f = fid % s.frames_per_ch;
+    }
+    // next() lets f run past the channel's frames; carry() at the top of the loop body takes it into ch
+    __device__ __forceinline__ void carry(const StreamDesc &s) {
+        if (f >= s.frames_per_ch) {
+            f -= s.frames_per_ch;
+            ++ch;
+        }
+    }
+    __device__ __forceinline__ void next() { fid += waves_total, ch += step_ch, f += step_f; }
+};
+
+// One wave, one frame; the caller puts a wave_sync() where a stage's LDS writes are read.
 
 // pre-emphasis (MFCC.ipynb cell 7) + Hamming (cell 18) of the frame at sample n0 into za: z[m] = y[2m] + i y[2m+1]
 template <int NFFT>
@@ -141,6 +197,30 @@ __device__ __forceinline__ float gen_split_power(const float2 *src, const float2
     return xr * xr + xi * xi;
 }
 
+// what the power kernels (spectrum, filterbank) read: the float kernel's window and twiddles, and the scale
+struct PowerTables {
+    const float  *window;     // [NFFT]       the handle's window: periodic Hamming over the frame, zeros up to NFFT
+    const float2 *tw_fft;     // [NFFT/2]     W_M^m, M = NFFT/2
+    const float2 *tw_split;   // [NFFT/2 + 1] W_NFFT^k
+    float inv_scale2;         // 1 / power_scale^2
+};
+
+// The cursor's frame -> its power row P[k] / power_scale^2, k = 0 .. NFFT/2: stage, Stockham, split.  src, dst: the
+// wave's ping-pong buffers; row_of(free): where the row goes, given the buffer the split does not read (2 M floats
+// >= M + 1) -- the output for the spectrum, that buffer for the filterbank.  Returns the row; the caller puts a
+// wave_sync() before the buffers are touched again
+template <int NFFT, typename RowOf>
+__device__ __forceinline__ float *gen_power_row(const StreamDesc &s, const FrameCursor &c, const GenTables &p, float inv_scale2,
+                                                float2 *src, float2 *dst, int lane, RowOf row_of) {
+    constexpr int M = NFFT / 2;
+    gen_stage_frame<NFFT>(s, s.pcm + c.ch * s.ch_stride, c.f * (long long)s.hop, p.win, reinterpret_cast<float *>(src), lane);
+    wave_sync();
+    gen_stockham<M>(src, dst, p.tw, lane);
+    float *row = row_of(reinterpret_cast<float *>(dst));
+    for (int k = lane; k <= M; k += 64) row[k] = gen_split_power<M>(src, p.tws, k) * inv_scale2;
+    return row;
+}
+
 // LOGMEL: the log-mel form -- rows of n_mel log2 band energies instead of n_cep DCT-II coefficients
 template <int NFFT, bool LOGMEL>
 __global__ __launch_bounds__(kBlock) void mfcc_float_generic_kernel(StreamDesc s, FloatTables t,
@@ -155,44 +235,26 @@ __global__ __launch_bounds__(kBlock) void mfcc_float_generic_kernel(StreamDesc s
     // enough) the DCT rows are staged too -- what round 2 found on the fixed-point twin of this kernel (SQ_WAIT_ANY 59 %
     // on flat loads): 512 points 10.2 -> 7.2 ms.  At 1024 points the tables would take the LDS that keeps a second and
     // third workgroup on the CU (2.28 -> 3.38 ms, measured): there they stay in global memory.
-    constexpr bool kStage = NFFT <= 512;
+    constexpr bool kStage = gen_staged(NFFT);
     constexpr int kDctLds = kStage ? 1024 : 1;
-    __shared__ float  winl[kStage ? NFFT : 1];
-    __shared__ float2 twl[kStage ? M : 1];
-    __shared__ float2 twsl[kStage ? M + 1 : 1];
     __shared__ float  dctl[kDctLds];
     const bool dct_in_lds = kStage && t.n_cep * t.n_mel <= kDctLds;
-    if constexpr (kStage) {
-        for (int i = threadIdx.x; i < NFFT; i += kBlock) winl[i] = t.window[i];
-        for (int i = threadIdx.x; i < M; i += kBlock) twl[i] = t.tw_fft[i];
-        for (int i = threadIdx.x; i <= M; i += kBlock) twsl[i] = t.tw_split[i];
-        if (dct_in_lds)
-            for (int i = threadIdx.x; i < t.n_cep * t.n_mel; i += kBlock) dctl[i] = t.dct[i];
-    }
-    const float *const win_p = kStage ? winl : t.window;
-    const float2 *const tw_p = kStage ? twl : t.tw_fft;
-    const float2 *const tws_p = kStage ? twsl : t.tw_split;
+    const GenTables p = gen_stage_tables<NFFT>(t.window, t.tw_fft, t.tw_split);
+    if (dct_in_lds)
+        for (int i = threadIdx.x; i < t.n_cep * t.n_mel; i += kBlock) dctl[i] = t.dct[i];
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    // frame cursor of this wave: (ch, f), advanced by the number of waves in the grid without a division
-    const long long waves_total = (long long)gridDim.x * kWavesPerBlock;
-    const long long step_ch = waves_total / s.frames_per_ch, step_f = waves_total % s.frames_per_ch;
-    long long fid = (long long)blockIdx.x * kWavesPerBlock + wave;
-    long long ch = fid / s.frames_per_ch, f = fid % s.frames_per_ch;
-
-    for (; fid < s.total_frames; fid += waves_total, ch += step_ch, f += step_f) {
-        if (f >= s.frames_per_ch) {
-            f -= s.frames_per_ch;
-            ++ch;
-        }
+    for (FrameCursor c(s, wave); c.fid < s.total_frames; c.next()) {
+        c.carry(s);
+        const long long fid = c.fid;
         const bool valid = true;
-        const int16_t *base = s.pcm + ch * s.ch_stride;
-        const long long n0 = f * (long long)s.hop;
+        const int16_t *base = s.pcm + c.ch * s.ch_stride;
+        const long long n0 = c.f * (long long)s.hop;
 
         // pre-emphasis (MFCC.ipynb cell 7) + Hamming (cell 18); z[m] = y[2m] + i y[2m+1]
-        gen_stage_frame<NFFT>(s, base, n0, win_p, reinterpret_cast<float *>(bufA[wave]), lane);
+        gen_stage_frame<NFFT>(s, base, n0, p.win, reinterpret_cast<float *>(bufA[wave]), lane);
         double dc = 0.0;
         if (t.window_d) {                       // uniform: X[0] = sum w y in double (y is exact)
             for (int i = lane; i < NFFT; i += 64) {
@@ -206,13 +268,13 @@ __global__ __launch_bounds__(kBlock) void mfcc_float_generic_kernel(StreamDesc s
 
         float2 *src = bufA[wave];
         float2 *dst = bufB[wave];
-        gen_stockham<M>(src, dst, tw_p, lane);
+        gen_stockham<M>(src, dst, p.tw, lane);
 
         // real-FFT split + power spectrum (cells 20, 22): P[k], k = 0..M, into dst (as floats)
         float *P = reinterpret_cast<float *>(dst);
         for (int k = lane; k <= M; k += 64) {
-            const float p = gen_split_power<M>(src, tws_p, k);
-            P[k] = (k == 0 && t.window_d) ? (float)(dc * dc) : p;
+            const float pk = gen_split_power<M>(src, p.tws, k);
+            P[k] = (k == 0 && t.window_d) ? (float)(dc * dc) : pk;
         }
         wave_sync();
 
@@ -475,22 +537,13 @@ __global__ __launch_bounds__(kBlock) void mfcc_fixed_kernel(StreamDesc s, FixedT
     for (int i = threadIdx.x; i < 2 * t.n_mel; i += kBlock) tw2[i] = t.tw_dct[i];
     __syncthreads();
 
-    // frame cursor of this wave: (ch, f), advanced by the number of waves in the grid without a division (a 64-bit
-    // division per frame cost as many instructions as a 256-point FFT)
-    const long long waves_total = (long long)gridDim.x * kWavesPerBlock;
-    const long long step_ch = waves_total / s.frames_per_ch, step_f = waves_total % s.frames_per_ch;
     constexpr int L = __builtin_ctz(NFFT);
-    long long fid = (long long)blockIdx.x * kWavesPerBlock + wave;
-    long long ch = fid / s.frames_per_ch, f = fid % s.frames_per_ch;
-
-    for (; fid < s.total_frames; fid += waves_total, ch += step_ch, f += step_f) {
-        if (f >= s.frames_per_ch) {
-            f -= s.frames_per_ch;
-            ++ch;
-        }
+    for (FrameCursor c(s, wave); c.fid < s.total_frames; c.next()) {
+        c.carry(s);
+        const long long fid = c.fid;
         const bool valid = true;
-        const int16_t *base = s.pcm + ch * s.ch_stride;
-        const long long n0 = f * (long long)s.hop;
+        const int16_t *base = s.pcm + c.ch * s.ch_stride;
+        const long long n0 = c.f * (long long)s.hop;
 
         // preemph.py:24  y = wrap16(x + (o >> 5) - o);  window.py:84  (y * curve) >> 9;
         // fft.py:413-424 bit-reversed load, imag = 0

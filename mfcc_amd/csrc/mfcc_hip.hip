@@ -766,6 +766,11 @@ int launch_generic(mfcc_hip_handle *h, const mfcc_k::StreamDesc &s, unsigned blo
     return MFCC_HIP_SUCCESS;
 }
 
+// what the generic spectrum and filterbank kernels read of the handle's float tables
+mfcc_k::PowerTables power_tables(const mfcc_hip_handle *h) {
+    return {h->ft.window, h->ft.tw_fft, h->ft.tw_split, float(1.0 / (h->r.power_scale * h->r.power_scale))};
+}
+
 // The kernel of a call over int16 samples: the spectrum's, the filterbank's or the handle's own, as c says
 int launch(mfcc_hip_handle *h, const Call &c, const void *d_pcm, size_t n, size_t stride, size_t nch,
            int halo, void *d_out, size_t *n_frames, size_t force_frames = 0) {
@@ -799,18 +804,14 @@ int launch(mfcc_hip_handle *h, const Call &c, const void *d_pcm, size_t n, size_
         if (reinterpret_cast<uintptr_t>(o) & 3) return MFCC_HIP_ERROR_INVALID_PARAM;
         const bool log = h->fb_scale != MFCC_HIP_FBANK_ENERGY;
         if (h->fb_kernel != mfcc_fbank::Kernel::kFused512 || !mfcc_fbank::launch_fused(s, h->sf, h->fb, log, o, h->n_cu, h->stream)) {
-            const mfcc_spec::GenericTables gt{h->ft.window, h->ft.tw_fft, h->ft.tw_split,
-                                              float(1.0 / (h->r.power_scale * h->r.power_scale))};
-            if (!mfcc_fbank::launch_generic(s, gt, h->fb, log, h->r.nfft, o, h->n_cu, h->stream)) return MFCC_HIP_ERROR_UNSUPPORTED;
+            if (!mfcc_fbank::launch_generic(s, power_tables(h), h->fb, log, h->r.nfft, o, h->n_cu, h->stream)) return MFCC_HIP_ERROR_UNSUPPORTED;
         }
         h->fb_used = true;
     } else if (c.kind == Kind::kSpectrum) {
         float *o = static_cast<float *>(d_out);
         if (reinterpret_cast<uintptr_t>(o) & 3) return MFCC_HIP_ERROR_INVALID_PARAM;
         if (h->spec_kernel != mfcc_spec::Kernel::kFused512 || !mfcc_spec::launch_fused(s, h->sf, o, h->n_cu, h->stream)) {
-            const mfcc_spec::GenericTables gt{h->ft.window, h->ft.tw_fft, h->ft.tw_split,
-                                              float(1.0 / (h->r.power_scale * h->r.power_scale))};
-            if (!mfcc_spec::launch_generic(s, gt, h->r.nfft, o, h->n_cu, h->stream)) return MFCC_HIP_ERROR_UNSUPPORTED;
+            if (!mfcc_spec::launch_generic(s, power_tables(h), h->r.nfft, o, h->n_cu, h->stream)) return MFCC_HIP_ERROR_UNSUPPORTED;
         }
     } else if (fixed && h->fixed_kernel == FixedKernel::kFixed512) {
         mfcc_fixed512::launch(s, h->x5, static_cast<int16_t *>(d_out), h->n_cu, h->stream);
@@ -885,10 +886,8 @@ int launch(mfcc_hip_handle *h, const Call &c, const void *d_pcm, size_t n, size_
             break;
         }
         if (generic) {
-            long long blocks = (total + mfcc_k::kWavesPerBlock - 1) / mfcc_k::kWavesPerBlock;
-            long long cap = (long long)n_cu * 128;       // measured: 8 per CU 3.55 ms, 32 3.24, 128 3.06 (nfft 256)
-            if (blocks > cap) blocks = cap;
-            const int rc = logmel ? launch_generic<true>(h, s, (unsigned)blocks, o) : launch_generic<false>(h, s, (unsigned)blocks, o);
+            const unsigned blocks = mfcc_k::generic_grid(s, n_cu);
+            const int rc = logmel ? launch_generic<true>(h, s, blocks, o) : launch_generic<false>(h, s, blocks, o);
             if (rc) return rc;
         }
     }

@@ -356,28 +356,57 @@ def test_ragged_is_bit_identical_to_dense_calls(mfcc_amd, wav_pcm, cfg, pad_mode
 
 
 # ---------------------------------------------------------------------------------------------------- steady state
-@pytest.mark.parametrize("cfg", FUSED_CFGS, ids=_id)
-def test_steady_state_of_the_tile_loop(mfcc_amd, wav_pcm, cfg):
-    """The batch of ``spectrum_ref.steady_shape``: workgroups run a first, a middle and a last tile; bit-identical to slices
-    where no workgroup gets a second tile, and within bound, at 80 bands."""
+_STEADY = {}
+
+
+def _steady_inputs(cfg, cu, wav_pcm):
+    """The batch of ``spectrum_ref.steady_shape`` with its float64 power and all-zero frames: computed once per
+    configuration and shared by both contraction forms, read-only."""
+    if cfg not in _STEADY:
+        nfft, hop, flen = cfg
+        tpc, frames, nch = sr.steady_shape(cu)
+        x = sr.batch_inputs(nfft, hop, flen, wav_pcm, nch, frames)
+        p_ref, zero = sr.reference(x, nfft, hop, flen), sr.zero_frames(x, nfft, hop, flen, "notebook", 0)
+        for a in (x, p_ref, zero):
+            a.setflags(write=False)
+        _STEADY[cfg] = (x, p_ref, zero)
+    return _STEADY[cfg]
+
+
+def _steady_state(mfcc_amd, wav_pcm, cfg, W, what):
     import torch
-    nfft, hop, flen = cfg
     cu = torch.cuda.get_device_properties(0).multi_processor_count
     tpc, frames, nch = sr.steady_shape(cu)
     per_slice = max(1, (cu // 2) // tpc)
-    x = sr.batch_inputs(nfft, hop, flen, wav_pcm, nch, frames)
+    x, p_ref, zero = _steady_inputs(cfg, cu, wav_pcm)
     view = _strided(x)
-    W = fr.htk_weights(80)
     with _open(mfcc_amd, cfg, FUSED, W, "energy") as m:
         assert m.num_frames(x.shape[1]) == frames
         whole = m.filterbank(view)
-        assert tuple(whole.shape) == (nch, frames, 80)
+        assert tuple(whole.shape) == (nch, frames, len(W))
         parts = [m.filterbank(view[a:a + per_slice]) for a in range(0, nch, per_slice)]
         torch.cuda.synchronize()
     assert same(whole, torch.cat(parts)), "%s: the batch differs from its slices" % (cfg,)
-    worst = _check(whole, sr.reference(x, nfft, hop, flen), sr.zero_frames(x, nfft, hop, flen, "notebook", 0), W, "energy", 0.0,
-                   "steady state %s" % (cfg,))
-    print("steady state %s: %d channels, worst error / bound %.3f" % (cfg, nch, worst))
+    worst = _check(whole, p_ref, zero, W, "energy", 0.0, "steady state %s %s" % (what, cfg), FUSED)
+    print("steady state %s %s: %d channels, worst error / bound %.3f" % (what, cfg, nch, worst))
+
+
+@pytest.mark.parametrize("cfg", FUSED_CFGS, ids=_id)
+def test_steady_state_of_the_tile_loop(mfcc_amd, wav_pcm, cfg):
+    """The batch of ``spectrum_ref.steady_shape``: workgroups run a first, a middle and a last tile; bit-identical to slices
+    where no workgroup gets a second tile, and within bound, at 80 bands (weights in LDS: the fp32 contraction)."""
+    W = fr.htk_weights(80)
+    assert fr.form_of(W, FUSED) == "f32"
+    _steady_state(mfcc_amd, wav_pcm, cfg, W, "htk80")
+
+
+@pytest.mark.parametrize("cfg", FUSED_CFGS, ids=_id)
+def test_steady_state_of_the_tile_loop_on_the_mfma_form(mfcc_amd, wav_pcm, cfg):
+    """The same batch through the other tail of the shared tile loop: a dense 128 x 257 matrix, whose weights do not fit
+    the LDS, so the MFMA contraction runs behind every first, middle and last tile."""
+    W = fr.dense_random(128)
+    assert fr.form_of(W, FUSED) != "f32"
+    _steady_state(mfcc_amd, wav_pcm, cfg, W, "dense128")
 
 
 # ---------------------------------------------------------------------------------------------------- entry points
