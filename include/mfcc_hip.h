@@ -132,7 +132,8 @@ int  mfcc_hip_create(const mfcc_hip_params *p, mfcc_hip_handle **out);
  *   - hop <= L <= nfft and L >= 2, else MFCC_HIP_ERROR_INVALID_PARAM (p->hop == 0 still means nfft / 3 and is refused
  *     when that exceeds L);
  *   - frame f is samples [f * hop, f * hop + L) of the pre-emphasised stream, multiplied by the periodic Hamming window
- *     of length L, w[i] = 0.54 - 0.46 cos(2 pi i / L), and zero-padded at the end to nfft;
+ *     of length L, w[i] = 0.54 - 0.46 cos(2 pi i / L) (or the window of the handle's front, mfcc_hip_create_fronted), and
+ *     zero-padded at the end to nfft;
  *   - from the FFT on nothing changes: mel points, power_scale (0 -> nfft), DCT and lifter depend on nfft as before;
  *   - frame counts: NOTEBOOK (n - L) / hop + 1 (0 if n < L), STREAM (n - L) / hop + 2 (1 if n < L).
  * frame_length 0 or p->nfft IS mfcc_hip_create: the same kernels, the same bits.  The frame length is not part of
@@ -190,6 +191,57 @@ int  mfcc_hip_create_banked(const mfcc_hip_params *p, int frame_length, const mf
                             mfcc_hip_handle **out);
 /* the bank of a handle: kind, low_hz and the effective high_hz (both 0 for a notebook bank) */
 int  mfcc_hip_mel_bank_of(const mfcc_hip_handle *h, mfcc_hip_mel_bank *out);
+/*
+ * The front of a handle (float path): the window function over the frame and the pre-emphasis coefficient -- the two
+ * constants between the samples and the spectrum.  front = (window kind, symmetric flag, preemph_num, preemph_den).
+ * Windows, for frame length L (mfcc_hip_create_framed; nfft on a plain handle), with D = L for the periodic form
+ * (symmetric = 0) and D = L - 1 for the symmetric one (symmetric = 1), evaluated in float64 on the host for i = 0 .. L - 1
+ * and zero-padded to nfft:
+ *   MFCC_HIP_WINDOW_HAMMING      0.54 - 0.46 cos(2 pi i / D)                          scipy get_window("hamming", L, fftbins)
+ *   MFCC_HIP_WINDOW_HANN         0.5 - 0.5 cos(2 pi i / D)                            "hann" (librosa, torchaudio, Whisper)
+ *   MFCC_HIP_WINDOW_POVEY        (0.5 - 0.5 cos(2 pi i / D)) ^ 0.85                   Kaldi's (symmetric there)
+ *   MFCC_HIP_WINDOW_BLACKMAN     0.42 - 0.5 cos(2 pi i / D) + 0.08 cos(4 pi i / D)    "blackman"
+ *   MFCC_HIP_WINDOW_RECTANGULAR  1
+ * Pre-emphasis: y[i] = x[i] - (num / den) x[i-1], x[-1] the history sample (0 at a stream's start, or the halo sample).
+ *   - 0 <= num <= den, den >= 1, num + den <= 255, else MFCC_HIP_ERROR_INVALID_PARAM; the pair is reduced by its gcd, so
+ *     (62, 64) is (31, 32) and mfcc_hip_front_of returns the reduced pair;
+ *   - the kernels form the exact integer e[i] = den x[i] - num x[i-1] (|e| < 2^23: exact in int32 and in fp32) and 1 / den
+ *     is folded into the window table in float64 before its one rounding to fp32;
+ *   - num = 0 switches pre-emphasis off: the history sample then has no influence on any bit.
+ * The default is HAMMING, periodic, (31, 32): the reference's.  front == NULL, or the default front written out (in any
+ * unreduced form), IS mfcc_hip_create_banked: the same kernel, the same bits.  An unknown kind, symmetric not 0 or 1, a
+ * pair outside the constraints, a wrong struct_size or a non-zero reserved word is INVALID_PARAM.  The front is not part
+ * of mfcc_hip_params (whose size, reserved words and ABI version stay as they are).
+ * Everything behind the window is unchanged: FFT, power_scale, mel banks, log, DCT, lifter, frame counts, post-passes,
+ * PCEN, VAD, sample formats, input rate; every float entry point, power spectrum, filterbank, session and stream bank
+ * works on such a handle.  On a non-default front:
+ *   - the fixed-point path refuses exactly as on a framed handle: every fixed entry point, fixed session, fixed bank and
+ *     the fixed .mfcc writers return MFCC_HIP_ERROR_UNSUPPORTED (and so does MFCC_HIP_TABLE_FX_MEL_DENSE_U32);
+ *   - with num + den <= 127 (0, 31/32, 15/16, 19/20, 32/33, 63/64 ...) the four-wave 512 kernels serve it where they
+ *     serve the shape: mfcc_fused512_h160_kernel, mfcc_fused512_h160_mb_kernel, mfcc_fused512_kernel for cepstra at 512 /
+ *     170 (log-mel rows there, and every 1024 shape, run the generic kernel), mfcc_spectrum512_kernel, mfcc_fbank512_kernel;
+ *   - with num + den > 127 (97/100, the exact 0.97) every output runs the generic kernels, and float_impl FUSED512 is
+ *     MFCC_HIP_ERROR_UNSUPPORTED.  (32, 33) is the fused stand-in for 0.97: the coefficient differs by 3.0e-4.
+ */
+enum mfcc_hip_window {
+    MFCC_HIP_WINDOW_HAMMING = 0,
+    MFCC_HIP_WINDOW_HANN = 1,
+    MFCC_HIP_WINDOW_POVEY = 2,
+    MFCC_HIP_WINDOW_BLACKMAN = 3,
+    MFCC_HIP_WINDOW_RECTANGULAR = 4
+};
+typedef struct mfcc_hip_front {
+    uint32_t struct_size;   /* sizeof(mfcc_hip_front) */
+    int32_t  window;        /* enum mfcc_hip_window */
+    int32_t  symmetric;     /* 0: periodic (D = L), 1: symmetric (D = L - 1) */
+    int32_t  preemph_num;   /* 0 .. preemph_den; 0: no pre-emphasis */
+    int32_t  preemph_den;   /* >= 1, preemph_num + preemph_den <= 255 */
+    int32_t  reserved[3];   /* must be zero */
+} mfcc_hip_front;
+int  mfcc_hip_create_fronted(const mfcc_hip_params *p, int frame_length, const mfcc_hip_mel_bank *bank,
+                             const mfcc_hip_front *front, mfcc_hip_handle **out);
+/* the front of a handle, the pair reduced (HAMMING, 0, 31, 32 for a handle made without one) */
+int  mfcc_hip_front_of(const mfcc_hip_handle *h, mfcc_hip_front *out);
 /* Lifetime rule: a handle that still has streaming sessions (mfcc_hip_stream_create below) is only MARKED
  * by mfcc_hip_destroy -- its stream, tables and scratch stay valid for those sessions, no new session can be
  * opened on it and no other call may be made with it -- and is freed by the mfcc_hip_stream_destroy of its
@@ -216,7 +268,7 @@ int  mfcc_hip_last_hip_error(const mfcc_hip_handle *h);
 /* The constant tables the kernels use, as built on the host (no GPU needed) -- lets the
  * CPU test-suite check the table builders against the oracle.  `which`: */
 enum mfcc_hip_table {
-    MFCC_HIP_TABLE_WINDOW_F32      = 0,  /* float[nfft]            periodic Hamming       */
+    MFCC_HIP_TABLE_WINDOW_F32      = 0,  /* float[nfft]            periodic Hamming, or the front's */
     MFCC_HIP_TABLE_MEL_POINTS_I32  = 1,  /* int32[n_mel + 2]       filter points          */
     MFCC_HIP_TABLE_MEL_DENSE_F32   = 2,  /* float[n_mel][nfft/2+1] weights (unscaled)     */
     MFCC_HIP_TABLE_DCT_F32         = 3,  /* float[n_cep][n_mel]    ortho DCT-II (x lifter)*/
@@ -237,6 +289,11 @@ int  mfcc_hip_get_table_framed(const mfcc_hip_params *p, int frame_length, int w
  * MFCC_HIP_TABLE_FX_MEL_DENSE_U32 are UNSUPPORTED; the other tables do not depend on the bank */
 int  mfcc_hip_get_table_banked(const mfcc_hip_params *p, int frame_length, const mfcc_hip_mel_bank *bank, int which,
                                void *buf, size_t cap_bytes, size_t *n_bytes);
+/* ... of a handle with a front (mfcc_hip_create_fronted; front NULL: the call above).  Only MFCC_HIP_TABLE_WINDOW_F32
+ * differs: the front's window over the frame length, WITHOUT the 1 / den the kernels' own tables carry, zeros up to nfft;
+ * on a non-default front MFCC_HIP_TABLE_FX_MEL_DENSE_U32 is UNSUPPORTED */
+int  mfcc_hip_get_table_fronted(const mfcc_hip_params *p, int frame_length, const mfcc_hip_mel_bank *bank,
+                                const mfcc_hip_front *front, int which, void *buf, size_t cap_bytes, size_t *n_bytes);
 
 /* ---- the hot path: replaces the per-frame ft601_write / ft601_read loop of
  *      mfcc_convert (software/main.c:128-166) ------------------------------------------ */
@@ -312,8 +369,9 @@ int  mfcc_hip_time_dev(mfcc_hip_handle *h, int fixed, const void *d_pcm, size_t 
  *
  *     | FFT_nfft(w . y_f)[k] / power_scale |^2          k = 0 .. nfft / 2
  *
- * y: the pre-emphasised stream, y[i] = x[i] - 31/32 x[i - 1] (x[-1] = 0, or the halo sample); y_f: its nfft samples from
- * sample f * hop on; w: the handle's window -- periodic Hamming over the handle's frame length, then zeros up to nfft
+ * y: the pre-emphasised stream, y[i] = x[i] - 31/32 x[i - 1] (x[-1] = 0, or the halo sample; num / den of the handle's
+ * front in place of 31/32, mfcc_hip_create_fronted); y_f: its nfft samples from sample f * hop on; w: the handle's window --
+ * periodic Hamming (or the front's window function) over the handle's frame length, then zeros up to nfft
  * (mfcc_hip_create_framed).  Framing, padding and frame counts are the handle's (hop, pad_mode, frame length), exactly
  * those of mfcc_hip_process_i16*.  A frame whose samples (and history sample) are all zero gives +0.0 in every bin; every
  * value is finite and >= 0 for any int16 input.  With a mel matrix W [n][bins] the band energies of the float path are

@@ -101,6 +101,23 @@ class MelBank(C.Structure):
     ]
 
 
+# enum mfcc_hip_window
+WINDOW_HAMMING, WINDOW_HANN, WINDOW_POVEY, WINDOW_BLACKMAN, WINDOW_RECTANGULAR = 0, 1, 2, 3, 4
+MAX_PREEMPH_SUM = 255
+
+
+class Front(C.Structure):
+    """struct mfcc_hip_front"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("window", C.c_int32),
+        ("symmetric", C.c_int32),
+        ("preemph_num", C.c_int32),
+        ("preemph_den", C.c_int32),
+        ("reserved", C.c_int32 * 3),
+    ]
+
+
 class Pcen(C.Structure):
     """struct mfcc_hip_pcen"""
     _fields_ = [
@@ -244,6 +261,12 @@ SYMBOLS = {
     "mfcc_hip_get_table_banked": (C.c_int, [C.POINTER(Params), C.c_int, C.POINTER(MelBank), C.c_int, C.c_void_p, _SZ,
                                             _PSZ]),
     "mfcc_hip_mel_bank_of": (C.c_int, [_H, C.POINTER(MelBank)]),
+    # the front of a handle (window function, pre-emphasis pair): mfcc_hip_create_fronted and the table helper's twin
+    "mfcc_hip_create_fronted": (C.c_int, [C.POINTER(Params), C.c_int, C.POINTER(MelBank), C.POINTER(Front),
+                                          C.POINTER(_H)]),
+    "mfcc_hip_get_table_fronted": (C.c_int, [C.POINTER(Params), C.c_int, C.POINTER(MelBank), C.POINTER(Front), C.c_int,
+                                             C.c_void_p, _SZ, _PSZ]),
+    "mfcc_hip_front_of": (C.c_int, [_H, C.POINTER(Front)]),
     # PCEN: the host-only helpers, the handle's setting and the kernels' direct entry
     "mfcc_hip_pcen_defaults": (C.c_int, [C.POINTER(Pcen)]),
     "mfcc_hip_pcen_constants": (C.c_int, [C.POINTER(Pcen), C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -194,12 +194,70 @@ def _window_args(window, min_window=_MIN_WINDOW, center=True):
     return window, min_window, center
 
 
+_WINDOWS = {"hamming": _lib.WINDOW_HAMMING, "hann": _lib.WINDOW_HANN, "povey": _lib.WINDOW_POVEY,
+            "blackman": _lib.WINDOW_BLACKMAN, "rectangular": _lib.WINDOW_RECTANGULAR}
+_WINDOW_NAMES = {v: k for k, v in _WINDOWS.items()}
+
+
+def _preemph_pair(preemph):
+    """``(num, den)`` of a pre-emphasis coefficient: a ``(num, den)`` tuple of integers as it is, a float ``x`` as
+    ``Fraction(x).limit_denominator(128)`` -- ``ValueError`` when that fraction is further than 1e-9 from ``x`` or when
+    ``num + den > 255``, asking for a tuple.  The range itself (``0 <= num <= den``, ``den >= 1``) is checked here too,
+    with words; the library reduces the pair by its gcd."""
+    if isinstance(preemph, (tuple, list)):
+        if len(preemph) != 2 or not all(_is_int(v) for v in preemph):
+            raise ValueError("preemph must be a number or a (num, den) pair of integers, not %r" % (preemph,))
+        num, den = int(preemph[0]), int(preemph[1])
+    else:
+        if isinstance(preemph, bool) or not isinstance(preemph, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(preemph):
+            raise ValueError("preemph must be a number or a (num, den) pair of integers, not %r" % (preemph,))
+        from fractions import Fraction
+        x = float(preemph)
+        fr = Fraction(x).limit_denominator(128)
+        if abs(float(fr) - x) > 1e-9 or fr.numerator + fr.denominator > _lib.MAX_PREEMPH_SUM:
+            raise ValueError("preemph=%r is no fraction num / den with den <= 128 and num + den <= %d: give the "
+                             "(num, den) pair to use, e.g. (32, 33) or (97, 100)" % (preemph, _lib.MAX_PREEMPH_SUM))
+        num, den = fr.numerator, fr.denominator
+    if den < 1 or num < 0 or num > den or num + den > _lib.MAX_PREEMPH_SUM:
+        raise ValueError("preemph (%d, %d): need 0 <= num <= den, den >= 1 and num + den <= %d"
+                         % (num, den, _lib.MAX_PREEMPH_SUM))
+    return num, den
+
+
+def make_front(window="hamming", window_periodic=True, preemph=31 / 32) -> _lib.Front:
+    """``struct mfcc_hip_front`` of the front arguments of :class:`MFCC`: the window function (``"hamming"``, ``"hann"``,
+    ``"povey"``, ``"blackman"``, ``"rectangular"``, or the integer of ``enum mfcc_hip_window``), its periodic
+    (``True``) or symmetric form, and the pre-emphasis coefficient as a float or a ``(num, den)`` pair.  The defaults
+    are the reference's front."""
+    if isinstance(window, str):
+        if window not in _WINDOWS:
+            raise ValueError("window must be one of %s, not %r" % (sorted(_WINDOWS), window))
+        kind = _WINDOWS[window]
+    elif _is_int(window) and int(window) in _WINDOW_NAMES:
+        kind = int(window)
+    else:
+        raise ValueError("window must be one of %s, not %r" % (sorted(_WINDOWS), window))
+    if not isinstance(window_periodic, (bool, np.bool_)):
+        raise ValueError("window_periodic must be True or False, not %r" % (window_periodic,))
+    num, den = _preemph_pair(preemph)
+    f = _lib.Front()
+    f.struct_size = C.sizeof(_lib.Front)
+    f.window, f.symmetric, f.preemph_num, f.preemph_den = kind, 0 if window_periodic else 1, num, den
+    return f
+
+
 def make_params(nfft=512, hop=None, nfilters=32, nceptrums=13, samplerate=16000, pad_mode="notebook",
-                power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra") -> Params:
+                power_scale=512.0, lifter=0.0, device=-1, impl="auto", output="cepstra", window="hamming",
+                window_periodic=True, preemph=31 / 32) -> Params:
     """``output``: ``"cepstra"`` (rows of ``nceptrums`` DCT-II coefficients) or ``"logmel"`` (rows of ``nfilters``
-    log2 mel band energies, the stage before the DCT; float path only, no lifter)."""
+    log2 mel band energies, the stage before the DCT; float path only, no lifter).  ``window``, ``window_periodic``,
+    ``preemph``: the front (:func:`make_front`), which the C parameter block does not hold: it travels as the
+    ``front`` attribute of the result, for the ``_fronted`` calls."""
     lib = _lib.load()
+    front = make_front(window, window_periodic, preemph)
     p = Params()
+    p.front = front
     _lib.check(lib.mfcc_hip_default_params(C.byref(p)))
     p.nfft = int(nfft)
     p.hop = 0 if hop is None else int(hop)          # 0 -> nfft // 3 (mfcc/core/mfcc.py:43)
@@ -343,7 +401,8 @@ _TABLE_DTYPES = {
 
 def get_table(which, win_length=None, mel="notebook", fmin=0.0, fmax=None, **kw) -> np.ndarray:
     """The constant tables as the library's host code builds them (works without a GPU).  ``win_length``: the frame
-    length of a framed handle; only the window table depends on it (``nfft`` floats, zeros from ``win_length`` on).
+    length of a framed handle; only the window table depends on it (``nfft`` floats, zeros from ``win_length`` on) and
+    on the front (``window``, ``window_periodic``; ``preemph`` is validated and does not enter the table).
     ``mel``, ``fmin``, ``fmax``: the bank of the handle (``MFCC(mel=...)``); the dense mel table depends on it, and an
     ``"htk"`` bank has neither filter points nor a fixed-point table (``UNSUPPORTED``)."""
     L = _win_length(win_length, kw.get("nfft", 512), kw.get("hop"))
@@ -351,10 +410,26 @@ def get_table(which, win_length=None, mel="notebook", fmin=0.0, fmax=None, **kw)
     lib = _lib.load()
     p = make_params(**kw)
     n = C.c_size_t(0)
-    _lib.check(lib.mfcc_hip_get_table_banked(C.byref(p), L, C.byref(bank), which, None, 0, C.byref(n)), "get_table")
+    front = C.byref(p.front)
+    _lib.check(lib.mfcc_hip_get_table_fronted(C.byref(p), L, C.byref(bank), front, which, None, 0, C.byref(n)), "get_table")
     buf = np.empty(n.value, dtype=np.uint8)
-    _lib.check(lib.mfcc_hip_get_table_banked(C.byref(p), L, C.byref(bank), which, ptr(buf), buf.nbytes, C.byref(n)))
+    _lib.check(lib.mfcc_hip_get_table_fronted(C.byref(p), L, C.byref(bank), front, which, ptr(buf), buf.nbytes, C.byref(n)))
     return buf.view(_TABLE_DTYPES[which])
+
+
+def window(kind, length, periodic=True) -> np.ndarray:
+    """The window function ``kind`` (``"hamming"``, ``"hann"``, ``"povey"``, ``"blackman"``, ``"rectangular"``) over
+    ``length`` samples (2..1024) as the library builds it: float32 ``(length,)``, periodic or symmetric (host-only).  What
+    ``MFCC(window=kind, window_periodic=periodic, win_length=length)`` multiplies a frame by."""
+    if not _is_int(length) or not 2 <= int(length) <= 1024:
+        raise ValueError("length must be an integer 2..1024, not %r" % (length,))
+    length = int(length)
+    nfft = 64
+    while nfft < length:
+        nfft *= 2
+    # hop 1: any frame length up to nfft is a valid framing
+    return get_table(_lib.TABLE_WINDOW_F32, win_length=length, nfft=nfft, hop=1, window=kind,
+                     window_periodic=periodic)[:length].copy()
 
 
 def _is_torch(x):
@@ -524,6 +599,17 @@ class MFCC(_Owner):
     every utterance on its own.  ``None``, 0 or ``samplerate`` itself: off.  ``process(..., halo=1)``, :meth:`stream` and
     :meth:`stream_bank` raise ``UNSUPPORTED`` on such a handle (live lines go through :meth:`resampler`); ``convert*``
     expect WAV files of that rate.
+
+    ``window`` (``"hamming"``, ``"hann"``, ``"povey"``, ``"blackman"``, ``"rectangular"``), ``window_periodic`` and
+    ``preemph`` are the handle's front: the window function over the frame, in its periodic (``True``: denominator
+    ``win_length``) or symmetric (``win_length - 1``) form, and the pre-emphasis ``y[i] = x[i] - preemph x[i-1]``.
+    ``preemph`` is a float or an exact ``(num, den)`` pair of integers with ``0 <= num <= den`` and ``num + den <= 255``
+    (a float becomes ``Fraction(x).limit_denominator(128)`` and must be that fraction to 1e-9); 0 switches it off.  The
+    defaults are the reference's, Hamming / periodic / 31/32, and give today's bits.  torchaudio / librosa style:
+    ``window="hann", preemph=0``; Kaldi style: ``window="povey", window_periodic=False, preemph=(32, 33)`` -- (32, 33) is
+    the pair next to 0.97 that the fused kernels serve (``num + den <= 127``); the exact ``(97, 100)`` runs the generic
+    kernels.  :attr:`front` reads the effective front back.  Float path only: the fixed-point entries raise
+    ``UNSUPPORTED`` on any other front than the default.
     """
 
     deltas, delta_window = 0, 2                 # the state after mfcc_hip_create
@@ -549,7 +635,8 @@ class MFCC(_Owner):
                  normalize=None, deltas=0, delta_window=2, normalize_window=None, normalize_min_window=_MIN_WINDOW,
                  normalize_center=True, vad=None, vad_column=0, vad_energy_threshold=5.0, vad_energy_mean_scale=0.5,
                  vad_frames_context=0, vad_proportion_threshold=0.6, win_length=None, mel="notebook", fmin=0.0,
-                 fmax=None, pcen=None, sample_format="s16", input_rate=None):
+                 fmax=None, pcen=None, sample_format="s16", input_rate=None, window="hamming", window_periodic=True,
+                 preemph=31 / 32):
         if width != 16:
             raise ValueError("only width=16 (int16 PCM) is supported, like every reference target")
         fmt_name, fmt_code, _ = _sample_args(sample_format)
@@ -558,7 +645,7 @@ class MFCC(_Owner):
         self.mel, self.fmin, self.fmax, bank = _mel_bank(mel, fmin, fmax, samplerate, nfilters)
         norm = normalize_mode(normalize)
         _window_args(normalize_window, normalize_min_window, normalize_center)
-        order, window = _delta_args(deltas, delta_window)
+        order, dwindow = _delta_args(deltas, delta_window)
         vad_args = _vad_args(vad, vad_column, vad_energy_threshold, vad_energy_mean_scale, vad_frames_context,
                              vad_proportion_threshold)
         self.width = width
@@ -569,7 +656,8 @@ class MFCC(_Owner):
         self._lib = _lib.load()
         self._params = make_params(nfft=nfft, hop=hop, nfilters=nfilters, nceptrums=nceptrums,
                                    samplerate=int(samplerate), pad_mode=pad_mode, power_scale=power_scale,
-                                   lifter=lifter, device=device, impl=impl, output=output)
+                                   lifter=lifter, device=device, impl=impl, output=output, window=window,
+                                   window_periodic=window_periodic, preemph=preemph)
         self.hop = self._params.hop or self.nfft // 3
         self.output = "logmel" if self._params.output == _lib.OUTPUT_LOGMEL else "cepstra"
         h = _lib.Handle()
@@ -582,8 +670,8 @@ class MFCC(_Owner):
                     self._device_index = torch.cuda.current_device()
             except ImportError:
                 pass
-        _lib.check(self._lib.mfcc_hip_create_banked(C.byref(self._params), self.win_length, C.byref(bank), C.byref(h)),
-                   "mfcc_hip_create")
+        _lib.check(self._lib.mfcc_hip_create_fronted(C.byref(self._params), self.win_length, C.byref(bank),
+                                                     C.byref(self._params.front), C.byref(h)), "mfcc_hip_create")
         self._h = h
         if fmt_code != _lib.SAMPLE_S16:
             self.set_sample_format(fmt_name)
@@ -595,9 +683,9 @@ class MFCC(_Owner):
         self.normalize = None
         if norm != _lib.NORMALIZE_NONE:
             self.set_normalize(normalize)
-        self.deltas, self.delta_window = 0, window
+        self.deltas, self.delta_window = 0, dwindow
         if order:
-            self.set_deltas(order, window)
+            self.set_deltas(order, dwindow)
         self.normalize_window, self.normalize_min_window, self.normalize_center = None, _MIN_WINDOW, True
         if normalize_window is not None:
             self.set_normalize_window(normalize_window, normalize_min_window, normalize_center)
@@ -607,6 +695,13 @@ class MFCC(_Owner):
         if vad_args[0] != _lib.VAD_OFF:
             self.set_vad(vad, vad_column, vad_energy_threshold, vad_energy_mean_scale, vad_frames_context,
                          vad_proportion_threshold)
+
+    @property
+    def front(self):
+        """``(window, window_periodic, (num, den))`` as the handle holds them (``mfcc_hip_front_of``): the pair reduced."""
+        f = _lib.Front()
+        _lib.check(self._lib.mfcc_hip_front_of(self._h, C.byref(f)), "front_of")
+        return _WINDOW_NAMES[f.window], not f.symmetric, (int(f.preemph_num), int(f.preemph_den))
 
     def set_sample_format(self, sample_format):
         """What the sample arrays of every call after this one hold (``"s16"``, ``"ulaw"``, ``"alaw"``, ``"u8"``,

@@ -66,15 +66,20 @@ __device__ __forceinline__ Window window_of(const Cursor &c, const LaunchGeom &g
     return w;
 }
 
-// e[k] = 32 x[k] - 31 x[k-1] for the 8 samples packed in v, x[-1] = high half of prev.  One
-// v_dot2_i32_i16 per sample (the three-operand form: for the builtin hipcc picks v_dot2c, which costs
-// an extra v_mov 0 per sample); the 1/32 is in the window table.
+// e[k] = den x[k] - num x[k-1] for the 8 samples packed in v, x[-1] = high half of prev; pair = (int16 -num, int16 den),
+// by default the reference's 32 x[k] - 31 x[k-1].  One v_dot2_i32_i16 per sample (the three-operand form: for the builtin
+// hipcc picks v_dot2c, which costs an extra v_mov 0 per sample); the 1 / den is in the window table.
 // No int -> float conversion: the dot product's addend is 0x4B400000, the bits of the float 1.5 * 2^23, whose ulp is 1 --
-// so for |e| < 2^22 (here |e| <= 63 * 32768 < 2^21) the integer sum IS the float 12582912 + e, and ONE packed subtraction
-// per pair of samples takes the bias off again, exactly: 4 instructions per pair of samples instead of 5.
+// so for |e| < 2^22 the integer sum IS the float 12582912 + e, and ONE packed subtraction per pair of samples takes the
+// bias off again, exactly: 4 instructions per pair of samples instead of 5.
+// Range: |x| <= 2^15, so |e| <= (num + den) 2^15.  The default pair gives 63 * 2^15 < 2^21; a pair from the tables struct
+// (the four-wave 512 kernels and the power tile) has num + den <= 127 (tables.hpp: kMaxFusedPreemphSum), so
+// |e| <= 127 * 2^15 < 2^22 and 12582912 + e stays inside [2^23, 2^24), where the float's ulp is 1.  The host refuses to build
+// those kernels' tables for a larger pair (num + den <= 255 keeps |e| < 2^23, exact in fp32, but not under this bias).
+// The kernels that do not pass a pair (twelve-wave 512, the 1024 forms) keep the constant at compile time.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void preemph8(int prev, const i32x4 &v, float *__restrict__ dst) {
-    const int c3132 = 0x0020ffe1;                  // (int16 -31, int16 32)
+__device__ __forceinline__ void preemph8(int prev, const i32x4 &v, float *__restrict__ dst, const int pair = 0x0020ffe1) {
+    const int c3132 = pair;                        // default: (int16 -31, int16 32)
     const int bias_bits = 0x4B400000;              // 12582912.0f (a VGPR: VOP3 takes one scalar operand on gfx9)
     const f32x2 bias = {12582912.0f, 12582912.0f};
     f32x2 e[4];

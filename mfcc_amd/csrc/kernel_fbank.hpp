@@ -86,7 +86,7 @@ __global__ __launch_bounds__(mfcc_k::kBlock) void mfcc_fbank_generic_kernel(mfcc
     constexpr int M = NFFT / 2;
     __shared__ float2 bufA[kWavesPerBlock][M];
     __shared__ float2 bufB[kWavesPerBlock][M + 1];
-    const GenTables p = gen_stage_tables<NFFT>(t.window, t.tw_fft, t.tw_split);
+    const GenTables p = gen_stage_tables<NFFT>(t.window, t.tw_fft, t.tw_split, t.pe_num, t.pe_den);
     __syncthreads();
 
     const int lane = threadIdx.x & 63;

@@ -7,12 +7,12 @@
 //
 //  input   the tile's contiguous sample span (16 frames = 3062 samples, ~6 KB) is fetched by the
 //          whole workgroup with 16-byte loads -- each sample crosses HBM/L2 once per tile -- one tile
-//          ahead; pre-emphasis 32 x[i] - 31 x[i-1] (one v_dot2_i32_i16, exact) is applied once per
-//          sample when the window is parked in LDS as fp32, just before the second barrier of the
-//          previous tile.
+//          ahead; pre-emphasis den x[i] - num x[i-1] (32 and 31 unless the handle's front says otherwise; one
+//          v_dot2_i32_i16, exact) is applied once per sample when the window is parked in LDS as fp32, just
+//          before the second barrier of the previous tile.
 //  pass 1  wave w, lane (q = lane>>4, n2 = lane&15) owns frame w + 8 (q&1) + 4 (q>>1) and reads its
 //          32 samples i = 16 n1 + n2 from the window (ds_read_b32, conflict free).  A register-resident
-//          REAL 32-point FFT over n1 with the Hamming window folded into its first butterfly layer
+//          REAL 32-point FFT over n1 with the window (Hamming, or the front's) folded into its first butterfly layer
 //          (packed fp32, codelets_gen.hpp) gives Y[k1, n2], k1 = 0..16.  Columns 0..15 are multiplied
 //          by W512^(n2 k1) and written to the LDS transpose tile T[frame][n2][k1]; column 16 (real)
 //          goes to the LDS tile V.
@@ -124,13 +124,14 @@ typedef short s16x2 __attribute__((ext_vector_type(2)));
 constexpr int kDcDigits = 7;
 
 struct FusedTables {
-    const float *win;     // [16 n2][32 n1]   hamming[16 n1 + n2] / 64 (pre-emphasis x32, real-FFT split x2)
+    const float *win;     // [16 n2][32 n1]   window[16 n1 + n2] / (2 den): the pre-emphasis pair's den (x32 by default),
+                          // real-FFT split x2
     const float2 *tw;     // [16 n2][16 k1]   W512^(n2 k1)
     const float *a_mel;   // [4 waves][17][64] mel weights of the bins wave w transforms, in Sched<> order (fp32: no kernel
                           // reads them any more; they keep their place in the blob and in this kernel argument)
     const uint32_t *a_mel_bf; // [4 waves][sets][hi, lo][4 dwords][64] the same weights as bf16 pairs
     const float *a_extra; // [4 roles][8][64]  role 0: DCT rows; role 1: column-16 DFT + its mel weights
-    const double *win_dc; // [16 n2][32 n1]   hamming[16 n1 + n2] / 32 in double -- or nullptr.  Set when a mel filter has
+    const double *win_dc; // [16 n2][32 n1]   window[16 n1 + n2] / den in double -- or nullptr.  Set when a mel filter has
                           // weight on bin 0 (any sample rate whose first two filter points are both 0: 44.1 kHz, 48 kHz ...).
                           // X[0] = sum w e is REAL: it comes arbitrarily close to 0 by cancellation, the log turns its
                           // relative error into an absolute one, and an fp32 sum is then off by 1e-6 rms / |X[0]|
@@ -153,6 +154,11 @@ struct FusedTables {
     const uint32_t *a_dct_bf;
     int n_cep;
     int n_mel;            // 32, or 16: block 1 does not exist (its zero sums must not reach the DCT as -inf * 0)
+};
+// ... as the four-wave kernels take them: with the handle's pre-emphasis pair (int16 -num, int16 den), num + den <= 127
+// (fused_common.hpp: preemph8).  The twelve-wave kernel takes the base: its kernel arguments stay where they were.
+struct W4Tables : FusedTables {
+    int preemph;
 };
 
 // ---- the mel contraction.  After pass 2, lane (j, g) of wave w holds |X|^2 of frame j at the 16
@@ -281,14 +287,16 @@ inline BlobOffsets blob_offsets(bool dense) {
     return o;
 }
 
+// w: the window over kNfft samples (zeros from the frame length on); num / den: the pre-emphasis pair, reduced.  false
+// also for a pair the fused kernels do not serve (num + den > 127)
 template <bool DENSE>
 inline bool build_tables(int sample_rate, double power_scale, double lifter, int n_cep, int n_mel,
-                         std::vector<char> &blob) {
+                         const std::vector<double> &w, int num, int den, std::vector<char> &blob) {
     constexpr int kAmel = Sched<DENSE>::N;
     if (n_mel != kMel && !DENSE) return false;
     using namespace mfcc_tables;
+    if (w.size() != size_t(kNfft) || num < 0 || den < 1 || num > den || num + den > kMaxFusedPreemphSum) return false;
     std::vector<float> amel(size_t(kWaves) * kAmel * 64, 0.0f), aext(size_t(kWaves) * kAextra * 64, 0.0f);
-    const std::vector<double> w = hamming_periodic(kNfft);
     std::vector<double> md(size_t(kMel) * 257, 0.0);                          // [32][257], rows >= n_mel stay 0
     {
         std::vector<double> m0 = mel_dense(kNfft, n_mel, double(sample_rate));
@@ -373,16 +381,17 @@ inline bool build_tables(int sample_rate, double power_scale, double lifter, int
     // the window in sample order for the twelve-wave form of the DC path (n = 0 .. 256, padded to 264), bin 0's weight
     // per filter
     std::vector<double> wl(264, 0.0);
-    for (int n = 0; n <= 256; ++n) wl[n] = w[n] / 32.0;
+    for (int n = 0; n <= 256; ++n) wl[n] = w[n] / double(den);
     std::vector<float> wdc(32, 0.0f);
     for (int f = 0; f < kMel; ++f) wdc[f] = float(md[size_t(f) * 257] * inv);
-    // bin 0 on the raw samples: e[n] = 32 x[n] - 31 x[n-1], X[0] = sum_n (w[n] / 32) e[n] = sum_{m=-1}^{511} c[m] x[m]
+    // bin 0 on the raw samples: e[n] = den x[n] - num x[n-1], X[0] = sum_n (w[n] / den) e[n] = sum_{m=-1}^{511} c[m] x[m]
+    // (read by the twelve-wave kernel, which only the default front reaches)
     std::vector<uint32_t> adc(size_t(17) * 64 * 4, 0u);
     double consts[3];
     {
         double c[513], maxc = 0.0;
         for (int m = -1; m <= 511; ++m) {
-            c[m + 1] = (m >= 0 ? w[m] : 0.0) - (m <= 510 ? 31.0 / 32.0 * w[m + 1] : 0.0);
+            c[m + 1] = (m >= 0 ? w[m] : 0.0) - (m <= 510 ? double(num) / double(den) * w[m + 1] : 0.0);
             if (std::fabs(c[m + 1]) > maxc) maxc = std::fabs(c[m + 1]);
         }
         // seven digits in [-64, 63]: |C| <= 64 (128^7 - 1) / 127 = 2.8e14 -- 48 bits, what the double sum resolved
@@ -436,8 +445,8 @@ inline bool build_tables(int sample_rate, double power_scale, double lifter, int
         if (off + bytes == end) std::memcpy(blob.data() + off, p, bytes);
         else fits = false;
     };
-    const std::vector<float> win = window_rows<float>(w, 64.0), tw = twiddle_rows();
-    const std::vector<double> wd = window_rows<double>(w, 32.0);             // the DC bin's rows (kernel_fused512.hpp: DCX)
+    const std::vector<float> win = window_rows<float>(w, 2.0 * double(den)), tw = twiddle_rows();
+    const std::vector<double> wd = window_rows<double>(w, double(den));      // the DC bin's rows (kernel_fused512.hpp: DCX)
     place(o.win, o.tw, win.data(), win.size() * 4);
     place(o.tw, o.a_mel, tw.data(), tw.size() * 4);
     place(o.a_mel, o.a_extra, amel.data(), amel.size() * 4);
@@ -453,16 +462,29 @@ inline bool build_tables(int sample_rate, double power_scale, double lifter, int
     return fits;
 }
 
-// Puts the window of a frame of L samples (L <= kNfft, zero-padded) into a blob made by build_tables: the fp32 rows the
-// kernel keeps in registers and the double rows of the DC path, both [16 n2][32 n1] with zeros from sample L on.
-inline void set_window(std::vector<char> &blob, bool dense, int L) {
-    std::vector<double> w = mfcc_tables::hamming_periodic(L);
-    w.resize(kNfft, 0.0);
-    const std::vector<float> win = window_rows<float>(w, 64.0);
-    const std::vector<double> wd = window_rows<double>(w, 32.0);
+// the reference's front: the periodic Hamming window over kNfft samples and 31/32
+template <bool DENSE>
+inline bool build_tables(int sample_rate, double power_scale, double lifter, int n_cep, int n_mel,
+                         std::vector<char> &blob) {
+    return build_tables<DENSE>(sample_rate, power_scale, lifter, n_cep, n_mel, mfcc_tables::hamming_periodic(kNfft), 31, 32,
+                               blob);
+}
+
+// Puts the window of a frame of L samples (L <= kNfft; w: kNfft values, zeros from sample L on) into a blob made by
+// build_tables with the same den: the fp32 rows the kernel keeps in registers and the double rows of the DC path, both
+// [16 n2][32 n1].
+inline void set_window(std::vector<char> &blob, bool dense, const std::vector<double> &w, int den) {
+    const std::vector<float> win = window_rows<float>(w, 2.0 * double(den));
+    const std::vector<double> wd = window_rows<double>(w, double(den));
     const BlobOffsets o = blob_offsets(dense);
     std::memcpy(blob.data() + o.win, win.data(), win.size() * sizeof(float));
     std::memcpy(blob.data() + o.win_dc, wd.data(), wd.size() * sizeof(double));
+}
+// ... the reference's: periodic Hamming over L samples, den 32
+inline void set_window(std::vector<char> &blob, bool dense, int L) {
+    std::vector<double> w = mfcc_tables::hamming_periodic(L);
+    w.resize(kNfft, 0.0);
+    set_window(blob, dense, w, 32);
 }
 
 // device pointer arithmetic only
@@ -517,8 +539,8 @@ __device__ unsigned long long g_stamps[4 * 12 + 16];   // [wave][12 phases], the
 // j = 0..3071, where shift = 0..7 makes the 16-byte global loads aligned.  Fetcher u (0..191: the
 // lanes of roles 1..3; role 0 spends that time on the previous tile's tail) fetches the pieces
 // [8 u, 8 u + 8) and [1536 + 8 u, ...), plus the dword holding the sample in front of each piece.
-// What is parked in LDS is the pre-emphasised sample e[i] = 32 x[i] - 31 x[i-1] as fp32 (exact:
-// |e| < 2^21) -- computed once per sample here instead of once per (frame, sample) in pass 1, where
+// What is parked in LDS is the pre-emphasised sample e[i] = den x[i] - num x[i-1] as fp32 (exact:
+// |e| < 2^22, fused_common.hpp: preemph8) -- computed once per sample here instead of once per (frame, sample) in pass 1, where
 // three overlapping frames would each redo it.  Windows that stick out of the channel (stream start
 // without history, zero-padded tail) are filled sample by sample with the stream's edge rules;
 // TILE_HOP, the samples between consecutive tiles, places the tile in the channel there.
@@ -552,9 +574,9 @@ __device__ __forceinline__ void fetch_window(const mfcc_k::StreamDesc &s, const 
     }
 }
 
-__device__ __forceinline__ void park_window(float *Sf, int u, const Fetch &f) {
-    preemph8(f.p0, f.v0, Sf + 8 * u);
-    preemph8(f.p1, f.v1, Sf + 8 * (kFetchers + u));
+__device__ __forceinline__ void park_window(float *Sf, int u, const Fetch &f, int pair) {
+    preemph8(f.p0, f.v0, Sf + 8 * u, pair);
+    preemph8(f.p1, f.v1, Sf + 8 * (kFetchers + u), pair);
 }
 
 // The summed mel energies of a finished tile, then log2 (MFCC.ipynb cell 36): register r of block b
@@ -703,10 +725,10 @@ __device__ __forceinline__ void mel_bf_blocks(const f32x4 (&acc)[SetsBf<DENSE>::
 
 // The workgroup's first tile: the cursor's start, the tile's span fetched and parked by the fetchers, and the barrier
 // behind which every wave reads it (and whatever the kernel staged in LDS before the call).  TILE_HOP: samples between
-// consecutive tiles; shift: the span's alignment shift (0 when the workgroup has no tile)
+// consecutive tiles; shift: the span's alignment shift (0 when the workgroup has no tile); pair: the pre-emphasis pair
 template <int TILE_HOP>
 __device__ __forceinline__ Cursor first_tile(const mfcc_k::StreamDesc s, const LaunchGeom g, float *Sf, int fetcher,
-                                             bool fetches, Fetch &fx, int &shift) {
+                                             bool fetches, Fetch &fx, int &shift, int pair) {
     Cursor cur;
     cur.ch = (int)(blockIdx.x / (unsigned)g.tiles_per_ch);
     cur.t_in = (int)(blockIdx.x - (unsigned)cur.ch * (unsigned)g.tiles_per_ch);
@@ -717,7 +739,7 @@ __device__ __forceinline__ Cursor first_tile(const mfcc_k::StreamDesc s, const L
         shift = w0.shift;
         if (fetches) {
             fetch_window<TILE_HOP>(s, w0, fetcher, fx);
-            park_window(Sf, fetcher, fx);
+            park_window(Sf, fetcher, fx, pair);
         }
     }
     __syncthreads();
@@ -773,7 +795,7 @@ __device__ __forceinline__ void col16_power(const float *Vt, const float (&ax)[N
 // in the DCT forms also 7 v_mov_b32 and 7 s_branch).  Role 1 restates col16_power's four MFMAs because it issues them
 // between its mel MFMAs (mel_bf_all's After), where the helper's straight line cannot go.
 template <int HOP, bool DENSE, bool DCX, bool LOGMEL>
-__device__ __forceinline__ void tile_loop_w4(const mfcc_k::StreamDesc s, const FusedTables t, const LaunchGeom g,
+__device__ __forceinline__ void tile_loop_w4(const mfcc_k::StreamDesc s, const W4Tables t, const LaunchGeom g,
                                              float *__restrict__ out, float *lds) {
     constexpr int kTileHopT = kTile * HOP;           // samples between consecutive tiles
     static_assert(7 + (kTile - 1) * HOP + kNfft <= kSUsed, "a tile's frames must lie inside the parked span");
@@ -838,7 +860,7 @@ __device__ __forceinline__ void tile_loop_w4(const mfcc_k::StreamDesc s, const F
         shift = w0.shift;
         if (fetches) {
             fetch_window<kTileHopT>(s, w0, fetcher, fx);
-            park_window(Sf, fetcher, fx);
+            park_window(Sf, fetcher, fx, t.preemph);
         }
     }
     __syncthreads();
@@ -994,7 +1016,7 @@ __device__ __forceinline__ void tile_loop_w4(const mfcc_k::StreamDesc s, const F
         have_prev = true;
         MFCC_STAMP(10);
         // park the next tile's sample span (every read of the current one happened before B1)
-        if (more && fetches) park_window(Sf, fetcher, fx);
+        if (more && fetches) park_window(Sf, fetcher, fx, t.preemph);
         shift = next_shift;
         MFCC_STAMP(4);
         lds_barrier();                         // B2: partial sums and S are in LDS, T/V may be overwritten
@@ -1025,7 +1047,7 @@ __device__ __forceinline__ void tile_loop_w4(const mfcc_k::StreamDesc s, const F
 
 template <bool DENSE, bool DCX>
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void mfcc_fused512_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, float *__restrict__ out) {
+void mfcc_fused512_kernel(mfcc_k::StreamDesc s, W4Tables t, LaunchGeom g, float *__restrict__ out) {
     __shared__ __attribute__((aligned(16))) float lds[lds_words(kQWords, DCX)];
     tile_loop_w4<kHop, DENSE, DCX, false>(s, t, g, out, lds);
 }
@@ -1036,7 +1058,7 @@ inline const char *kernel_name() { return "mfcc_fused512_kernel"; }
 // header's device helpers and tables but not its kernels (fbank.hip) defines MFCC_NO_LAUNCHERS: a launcher names its
 // kernels, and that alone instantiates them into the unit's code object
 #ifndef MFCC_NO_LAUNCHERS
-inline bool launch(const mfcc_k::StreamDesc &s, const FusedTables &t, bool dense, float *out, int n_cu,
+inline bool launch(const mfcc_k::StreamDesc &s, const W4Tables &t, bool dense, float *out, int n_cu,
                    hipStream_t stream) {
     const bool dcx = t.win_dc != nullptr;        // only ever set together with the dense schedule
     LaunchGeom g;

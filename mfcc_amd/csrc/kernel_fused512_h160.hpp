@@ -7,8 +7,8 @@
 //
 //  hop     consecutive tiles are 16 * 160 = 2560 samples apart and frame fr of a tile starts at slot 160 fr of the
 //          parked span.  A tile reads slots up to 7 + 15 * 160 + 511 = 2918 of the 3072 it parks.
-//  window  a frame owns L samples (160 <= L <= 511) and is zero-padded to 512: FusedTables::win holds the periodic
-//          Hamming window of length L in its first L entries and zeros behind them (mfcc_fused::set_window).  The kernel
+//  window  a frame owns L samples (160 <= L <= 511) and is zero-padded to 512: FusedTables::win holds the handle's
+//          window (periodic Hamming by default) of length L in its first L entries and zeros behind them (mfcc_fused::set_window).  The kernel
 //          still reads 512 slots per frame; slots L .. 511 are finite (pre-emphasised int16, or the zeros the edge path
 //          supplies beyond the channel) and meet a zero weight, so whatever follows the frame -- the next frame, the next
 //          utterance of a packed batch, the padding -- does not reach its result.
@@ -41,7 +41,7 @@ inline bool supported(int nfft, int hop, int frame_len, int n_mel, int n_cep) {
 
 template <bool DENSE, bool DCX, bool LOGMEL>
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void mfcc_fused512_h160_kernel(mfcc_k::StreamDesc s, FusedTables t, LaunchGeom g, float *__restrict__ out) {
+void mfcc_fused512_h160_kernel(mfcc_k::StreamDesc s, W4Tables t, LaunchGeom g, float *__restrict__ out) {
     __shared__ __attribute__((aligned(16))) float lds[lds_words(kQWords, DCX)];
     tile_loop_w4<kHop160, DENSE, DCX, LOGMEL>(s, t, g, out, lds);
 }
@@ -50,7 +50,7 @@ inline const char *kernel_name() { return "mfcc_fused512_h160_kernel"; }
 
 // returns false when the problem does not fit the kernel's 32-bit tile arithmetic
 template <bool LOGMEL>
-inline bool launch(const mfcc_k::StreamDesc &s, const FusedTables &t, bool dense, float *out, int n_cu,
+inline bool launch(const mfcc_k::StreamDesc &s, const W4Tables &t, bool dense, float *out, int n_cu,
                    hipStream_t stream) {
     const bool dcx = t.win_dc != nullptr;        // only ever set together with the dense schedule
     LaunchGeom g;

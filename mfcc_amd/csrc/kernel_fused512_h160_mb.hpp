@@ -48,7 +48,7 @@ inline bool supported(int nfft, int hop, int frame_len, int n_mel, int n_cep, bo
 }
 
 struct Tables {
-    const float *win;          // [16 n2][32 n1]  window of the frame length / 64, zeros from sample L on
+    const float *win;          // [16 n2][32 n1]  window of the frame length / (2 den), zeros from sample L on
     const float2 *tw;          // [16 n2][16 k1]  W512^(n2 k1)
     const u32x4 *a_bf;         // [4 waves][n_sets][hi, lo][64 lanes] bf16 pairs of the listed sets, in pair order
     const float *a_extra;      // [4 roles][16][64]  role 0: DCT rows, index 4 block + r; role 1: column-16 DFT (0..3)
@@ -58,25 +58,27 @@ struct Tables {
     int n_blocks;              // (n_mel + 15) / 16
     int n_cep;
     int n_mel;
+    int preemph;               // the pre-emphasis pair (int16 -num, int16 den), num + den <= 127 (fused_common.hpp: preemph8)
 };
 
 // ---- host.  md: the handle's matrix [n_mel][257] (float64 holding the weights as the contract rounds them), before the
 // power scale.  Returns false when a filter has weight on bin 0 or (never, by construction) a weight is not covered.
 // blob layout: win | tw | a_extra | a_bf; sets: the listed pairs in order (for the record in DESIGN.md and the tests).
-inline bool build_tables(const std::vector<double> &md, int n_mel, int n_cep, int frame_len, double power_scale,
-                         double lifter, std::vector<char> &blob, uint32_t &set_mask) {
+// w: the handle's window over kNfft samples (zeros from the frame length on); den: of the pre-emphasis pair, folded into
+// the window rows (the pair itself goes through bind_tables).
+inline bool build_tables(const std::vector<double> &md, int n_mel, int n_cep, const std::vector<double> &w, int den,
+                         double power_scale, double lifter, std::vector<char> &blob, uint32_t &set_mask) {
     using namespace mfcc_tables;
     const int nb = (n_mel + 15) / 16;
     if (n_mel < 1 || nb > kMaxBlocks || md.size() != size_t(n_mel) * 257) return false;
+    if (w.size() != size_t(kNfft) || den < 1 || den > kMaxFusedPreemphSum) return false;
     for (int f = 0; f < n_mel; ++f)
         if (md[size_t(f) * 257] != 0.0) return false;                 // bin 0 is real-valued: no DC path here
     const double inv = 1.0 / (power_scale * power_scale);
     auto W = [&](int filt, int bin) -> float { return filt < n_mel ? float(md[size_t(filt) * 257 + bin] * inv) : 0.0f; };
     auto bin_of = [](int k1, int k2) { return k2 < 8 ? k1 + 32 * k2 : 32 * (16 - k2) - k1; };
 
-    std::vector<double> w = hamming_periodic(frame_len);
-    w.resize(kNfft, 0.0);
-    const std::vector<float> win = window_rows<float>(w, 64.0), tw = twiddle_rows();
+    const std::vector<float> win = window_rows<float>(w, 2.0 * double(den)), tw = twiddle_rows();
     std::vector<float> aext(size_t(kWaves) * kAextra * 64, 0.0f);
     // the set list: pair (block, group) is needed when any wave has a non-zero weight in it
     set_mask = 0;
@@ -154,8 +156,17 @@ inline bool build_tables(const std::vector<double> &md, int n_mel, int n_cep, in
     return true;
 }
 
-// device pointer arithmetic only; b must be 16-byte aligned
-inline void bind_tables(const char *b, int n_cep, int n_mel, uint32_t set_mask, Tables &t) {
+// the reference's front: the periodic Hamming window over frame_len samples and 31/32
+inline bool build_tables(const std::vector<double> &md, int n_mel, int n_cep, int frame_len, double power_scale,
+                         double lifter, std::vector<char> &blob, uint32_t &set_mask) {
+    std::vector<double> w = mfcc_tables::hamming_periodic(frame_len);
+    w.resize(kNfft, 0.0);
+    return build_tables(md, n_mel, n_cep, w, 32, power_scale, lifter, blob, set_mask);
+}
+
+// device pointer arithmetic only; b must be 16-byte aligned.  pair: mfcc_tables::packed_preemph of the handle's pair
+inline void bind_tables(const char *b, int n_cep, int n_mel, uint32_t set_mask, Tables &t,
+                        int pair = mfcc_tables::packed_preemph(31, 32)) {
     const float *f = reinterpret_cast<const float *>(b);
     t.win = f;                                  f += 16 * 32;
     t.tw = reinterpret_cast<const float2 *>(f); f += 16 * 16 * 2;
@@ -167,6 +178,7 @@ inline void bind_tables(const char *b, int n_cep, int n_mel, uint32_t set_mask, 
     t.n_blocks = (n_mel + 15) / 16;
     t.n_cep = n_cep;
     t.n_mel = n_mel;
+    t.preemph = pair;
 }
 
 // ---- device
@@ -294,7 +306,7 @@ void mfcc_fused512_h160_mb_kernel(mfcc_k::StreamDesc s, Tables t, LaunchGeom g, 
         shift = w0.shift;
         if (fetches) {
             fetch_window<kTileHop160>(s, w0, fetcher, fx);
-            park_window(Sf, fetcher, fx);
+            park_window(Sf, fetcher, fx, t.preemph);
         }
     }
     __syncthreads();
@@ -391,7 +403,7 @@ void mfcc_fused512_h160_mb_kernel(mfcc_k::StreamDesc s, Tables t, LaunchGeom g, 
         prev = me;
         have_prev = true;
         // park the next tile's sample span (every read of the current one happened before B1)
-        if (more && fetches) park_window(Sf, fetcher, fx);
+        if (more && fetches) park_window(Sf, fetcher, fx, t.preemph);
         shift = next_shift;
         lds_barrier();                         // B2: partial sums and S are in LDS, T/V may be overwritten
     }

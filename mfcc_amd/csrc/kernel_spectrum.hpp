@@ -62,7 +62,7 @@ __global__ __launch_bounds__(mfcc_k::kBlock) void mfcc_spectrum_generic_kernel(m
     constexpr int M = NFFT / 2;
     __shared__ float2 bufA[kWavesPerBlock][M];
     __shared__ float2 bufB[kWavesPerBlock][M + 1];
-    const GenTables p = gen_stage_tables<NFFT>(t.window, t.tw_fft, t.tw_split);
+    const GenTables p = gen_stage_tables<NFFT>(t.window, t.tw_fft, t.tw_split, t.pe_num, t.pe_den);
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
@@ -119,18 +119,20 @@ constexpr int kTileWords = kTile * kTFrame + kTile * kVStride + kSUsed;       //
 constexpr int kLdsWords = kTileWords + kRWords;
 
 struct FusedTables {
-    const float *win;     // [16 n2][32 n1]  window[16 n1 + n2] / 64 (pre-emphasis x32, real-FFT split x2)
+    const float *win;     // [16 n2][32 n1]  window[16 n1 + n2] / (2 den) (pre-emphasis x den, real-FFT split x2)
     const float2 *tw;     // [16 n2][16 k1]  W512^(n2 k1)
     const float *a_col16; // [4][64 lanes]   the column-16 DFT matrix as MFMA A operands (mfcc_fused::col16_dft_rows)
     float inv_scale2;     // 1 / power_scale^2
+    int preemph;          // the pre-emphasis pair (int16 -num, int16 den), num + den <= 127 (fused_common.hpp: preemph8)
 };
 
 constexpr size_t kBlobWin = 0, kBlobTw = kBlobWin + 4 * 16 * 32, kBlobCol16 = kBlobTw + 4 * 16 * 16 * 2,
                  kBlobBytes = kBlobCol16 + 4 * 4 * 64;
 
-// host: the tables of a handle whose window is `window` (nfft doubles: zeros from the frame length on)
-inline void build_tables(const std::vector<double> &window, std::vector<char> &blob) {
-    const std::vector<float> win = mfcc_fused::window_rows<float>(window, 64.0), tw = mfcc_fused::twiddle_rows();
+// host: the tables of a handle whose window is `window` (nfft doubles: zeros from the frame length on) and whose
+// pre-emphasis pair has the denominator den
+inline void build_tables(const std::vector<double> &window, std::vector<char> &blob, int den = 32) {
+    const std::vector<float> win = mfcc_fused::window_rows<float>(window, 2.0 * double(den)), tw = mfcc_fused::twiddle_rows();
     float col16[4 * 64];
     mfcc_fused::col16_dft_rows(col16);
     blob.assign(kBlobBytes, 0);
@@ -140,7 +142,8 @@ inline void build_tables(const std::vector<double> &window, std::vector<char> &b
 }
 
 // device pointer arithmetic only
-inline void bind_tables(const char *b, double power_scale, FusedTables &t) {
+inline void bind_tables(const char *b, double power_scale, FusedTables &t, int pair = mfcc_tables::packed_preemph(31, 32)) {
+    t.preemph = pair;
     t.win = reinterpret_cast<const float *>(b + kBlobWin);
     t.tw = reinterpret_cast<const float2 *>(b + kBlobTw);
     t.a_col16 = reinterpret_cast<const float *>(b + kBlobCol16);
@@ -212,7 +215,7 @@ __device__ __forceinline__ void power_tile_loop(const mfcc_k::StreamDesc s, cons
 
     Fetch fx;
     int shift;
-    Cursor cur = mfcc_fused::first_tile<kTileHopT>(s, g, Sf, fetcher, fetches, fx, shift);
+    Cursor cur = mfcc_fused::first_tile<kTileHopT>(s, g, Sf, fetcher, fetches, fx, shift, t.preemph);
 
     while (cur.ch < g.n_ch) {
         // ---------------- pass 1: windowed real FFT-32 over n1 of the pre-emphasised samples
@@ -267,7 +270,7 @@ __device__ __forceinline__ void power_tile_loop(const mfcc_k::StreamDesc s, cons
             row[48 + 64 * q] = s1 * inv;
         }
         // park the next tile's sample span (every read of the current one happened before B1)
-        if (more && fetches) mfcc_fused::park_window(Sf, fetcher, fx);
+        if (more && fetches) mfcc_fused::park_window(Sf, fetcher, fx, t.preemph);
         shift = next_shift;
         mfcc_fc::lds_barrier();                // B2: R and S are in LDS, T and V may be overwritten
 

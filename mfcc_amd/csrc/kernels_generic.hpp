@@ -43,7 +43,7 @@ __device__ __forceinline__ int sample_at_i(const StreamDesc &s, const int16_t *b
 // ------------------------------------------------------------------------------ float
 
 struct FloatTables {
-    const float  *window;     // [NFFT]
+    const float  *window;     // [NFFT]       the handle's window / den (the pre-emphasis pair's, below)
     const float2 *tw_fft;     // [NFFT/2]     W_M^m, M = NFFT/2 (complex FFT length)
     const float2 *tw_split;   // [NFFT/2 + 1] W_NFFT^k
     const int    *mel_start;  // [n_mel]
@@ -52,9 +52,13 @@ struct FloatTables {
     const float  *mel_w;      // packed weights, 1/power_scale^2 folded in
     int mel_w_total;          // entries of mel_w: at most 2 per bin (staged in LDS by the kernel)
     const float  *dct;        // [n_cep][n_mel] (lifter folded in)
-    const double *window_d;   // [NFFT] the window in double, or nullptr: set when a mel filter has weight on bin 0 --
+    const double *window_d;   // [NFFT] the window / den in double, or nullptr: set when a mel filter has weight on bin 0 --
                               // that bin is then accumulated in double (kernel_fused512.hpp, FusedTables::win_dc)
     int n_mel, n_cep;
+    float pe_num, pe_den;     // pre-emphasis y[i] = x[i] - (num / den) x[i-1], reduced, num + den <= 255 (31, 32 by default);
+                              // as floats: the kernels multiply samples by them, and a conversion in the kernel would hold
+                              // two vector registers for its whole frame loop
+    int pe_num_i, pe_den_i;   // ... and as integers, for the DC sum in double
 };
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
@@ -88,11 +92,13 @@ constexpr bool gen_staged(int nfft) { return nfft <= 512; }
 struct GenTables {
     const float *win;
     const float2 *tw, *tws;
+    float pe_num, pe_den;     // the pre-emphasis pair (gen_stage_frame)
 };
 
 // Stages the three tables (all 256 threads; the caller's __syncthreads() publishes them) or passes the global ones on
 template <int NFFT>
-__device__ __forceinline__ GenTables gen_stage_tables(const float *window, const float2 *tw_fft, const float2 *tw_split) {
+__device__ __forceinline__ GenTables gen_stage_tables(const float *window, const float2 *tw_fft, const float2 *tw_split,
+                                                      float pe_num, float pe_den) {
     constexpr int M = NFFT / 2;
     constexpr bool kStage = gen_staged(NFFT);
     __shared__ float  winl[kStage ? NFFT : 1];
@@ -103,7 +109,7 @@ __device__ __forceinline__ GenTables gen_stage_tables(const float *window, const
         for (int i = threadIdx.x; i < M; i += kBlock) twl[i] = tw_fft[i];
         for (int i = threadIdx.x; i <= M; i += kBlock) twsl[i] = tw_split[i];
     }
-    return GenTables{kStage ? winl : window, kStage ? twl : tw_fft, kStage ? twsl : tw_split};
+    return GenTables{kStage ? winl : window, kStage ? twl : tw_fft, kStage ? twsl : tw_split, pe_num, pe_den};
 }
 
 // Frame cursor of a wave: frame fid = frame f of channel ch, advanced by the number of waves in the grid without a
@@ -129,16 +135,20 @@ struct FrameCursor {
 
 // One wave, one frame; the caller puts a wave_sync() where a stage's LDS writes are read.
 
-// pre-emphasis (MFCC.ipynb cell 7) + Hamming (cell 18) of the frame at sample n0 into za: z[m] = y[2m] + i y[2m+1]
+// pre-emphasis (MFCC.ipynb cell 7) + window (cell 18) of the frame at sample n0 into za: z[m] = y[2m] + i y[2m+1].
+// What is formed is the integer e = den x[i] - num x[i-1], exact in fp32 (|e| <= 255 * 2^15 < 2^23: both products and
+// the fused sum are integers below 2^24), times the table, which carries 1 / den.  With the default pair this is the
+// value x[i] - 0.96875 x[i-1] times the window to the bit: e is 32 times that difference (itself exact) and the table
+// the window's fp32 value over 32, so the one rounding of the product sees the same real number.
 template <int NFFT>
-__device__ __forceinline__ void gen_stage_frame(const StreamDesc &s, const int16_t *base, long long n0, const float *win_p,
+__device__ __forceinline__ void gen_stage_frame(const StreamDesc &s, const int16_t *base, long long n0, const GenTables &p,
                                                 float *za, int lane) {
     for (int i = lane; i < NFFT; i += 64) {
         float x0 = sample_at(s, base, n0 + i);
         float x1 = sample_at(s, base, n0 + i - 1);
-        // y[0] = x[0] for the very first sample of a stream: history is 0 there
-        float y = x0 - 0.96875f * x1;
-        za[i] = y * win_p[i];
+        // e[0] = den x[0] for the very first sample of a stream: history is 0 there
+        float e = fmaf(-p.pe_num, x1, p.pe_den * x0);
+        za[i] = e * p.win[i];
     }
 }
 
@@ -199,10 +209,11 @@ __device__ __forceinline__ float gen_split_power(const float2 *src, const float2
 
 // what the power kernels (spectrum, filterbank) read: the float kernel's window and twiddles, and the scale
 struct PowerTables {
-    const float  *window;     // [NFFT]       the handle's window: periodic Hamming over the frame, zeros up to NFFT
+    const float  *window;     // [NFFT]       the handle's window over the frame / den, zeros up to NFFT
     const float2 *tw_fft;     // [NFFT/2]     W_M^m, M = NFFT/2
     const float2 *tw_split;   // [NFFT/2 + 1] W_NFFT^k
     float inv_scale2;         // 1 / power_scale^2
+    float pe_num, pe_den;     // the pre-emphasis pair (FloatTables)
 };
 
 // The cursor's frame -> its power row P[k] / power_scale^2, k = 0 .. NFFT/2: stage, Stockham, split.  src, dst: the
@@ -213,7 +224,7 @@ template <int NFFT, typename RowOf>
 __device__ __forceinline__ float *gen_power_row(const StreamDesc &s, const FrameCursor &c, const GenTables &p, float inv_scale2,
                                                 float2 *src, float2 *dst, int lane, RowOf row_of) {
     constexpr int M = NFFT / 2;
-    gen_stage_frame<NFFT>(s, s.pcm + c.ch * s.ch_stride, c.f * (long long)s.hop, p.win, reinterpret_cast<float *>(src), lane);
+    gen_stage_frame<NFFT>(s, s.pcm + c.ch * s.ch_stride, c.f * (long long)s.hop, p, reinterpret_cast<float *>(src), lane);
     wave_sync();
     gen_stockham<M>(src, dst, p.tw, lane);
     float *row = row_of(reinterpret_cast<float *>(dst));
@@ -239,7 +250,7 @@ __global__ __launch_bounds__(kBlock) void mfcc_float_generic_kernel(StreamDesc s
     constexpr int kDctLds = kStage ? 1024 : 1;
     __shared__ float  dctl[kDctLds];
     const bool dct_in_lds = kStage && t.n_cep * t.n_mel <= kDctLds;
-    const GenTables p = gen_stage_tables<NFFT>(t.window, t.tw_fft, t.tw_split);
+    const GenTables p = gen_stage_tables<NFFT>(t.window, t.tw_fft, t.tw_split, t.pe_num, t.pe_den);
     if (dct_in_lds)
         for (int i = threadIdx.x; i < t.n_cep * t.n_mel; i += kBlock) dctl[i] = t.dct[i];
     __syncthreads();
@@ -253,13 +264,13 @@ __global__ __launch_bounds__(kBlock) void mfcc_float_generic_kernel(StreamDesc s
         const int16_t *base = s.pcm + c.ch * s.ch_stride;
         const long long n0 = c.f * (long long)s.hop;
 
-        // pre-emphasis (MFCC.ipynb cell 7) + Hamming (cell 18); z[m] = y[2m] + i y[2m+1]
-        gen_stage_frame<NFFT>(s, base, n0, p.win, reinterpret_cast<float *>(bufA[wave]), lane);
+        // pre-emphasis (MFCC.ipynb cell 7) + window (cell 18); z[m] = y[2m] + i y[2m+1]
+        gen_stage_frame<NFFT>(s, base, n0, p, reinterpret_cast<float *>(bufA[wave]), lane);
         double dc = 0.0;
-        if (t.window_d) {                       // uniform: X[0] = sum w y in double (y is exact)
+        if (t.window_d) {                       // uniform: X[0] = sum (w / den) e in double (e is an exact integer)
             for (int i = lane; i < NFFT; i += 64) {
-                const double yd = (double)sample_at_i(s, base, n0 + i) - 0.96875 * (double)sample_at_i(s, base, n0 + i - 1);
-                dc = __builtin_fma(t.window_d[i], yd, dc);
+                const int e = t.pe_den_i * sample_at_i(s, base, n0 + i) - t.pe_num_i * sample_at_i(s, base, n0 + i - 1);
+                dc = __builtin_fma(t.window_d[i], (double)e, dc);
             }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) dc += __shfl_xor(dc, o, 64);

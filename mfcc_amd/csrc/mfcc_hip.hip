@@ -55,6 +55,7 @@ struct Resolved {
     int frame_len;             // samples of a frame (hop <= frame_len <= nfft); the window's length.  nfft: a plain handle
     int mel_kind;              // enum mfcc_hip_mel_kind (mfcc_hip_create_banked); NOTEBOOK: the reference's bank
     double mel_lo, mel_hi;     // HTK: the band edges in Hz, mel_hi effective (never 0); NOTEBOOK: both 0
+    Front front;               // window function and pre-emphasis pair (mfcc_hip_create_fronted); default: the reference's
 };
 
 // width of a row of the handle's own output: n_mel log-mel values or n_cep coefficients
@@ -136,6 +137,7 @@ int resolve(const mfcc_hip_params *p, Resolved &r) {
     r.frame_len = p->nfft;
     r.mel_kind = MFCC_HIP_MEL_NOTEBOOK;
     r.mel_lo = r.mel_hi = 0.0;
+    r.front = Front{};
     if (!is_pow2(r.nfft) || r.nfft < 64 || r.nfft > 1024) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (r.hop < 1 || r.hop > r.nfft) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (r.n_mel < 1 || r.n_mel > mfcc_k::kMaxMel) return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -184,6 +186,28 @@ int resolve_banked(const mfcc_hip_params *p, int frame_length, const mfcc_hip_me
 
 inline bool is_htk(const Resolved &r) { return r.mel_kind == MFCC_HIP_MEL_HTK; }
 
+// ... and a front (mfcc_hip_create_fronted): NULL means the handle above.  The pair is reduced by its gcd, so the default
+// front written out in any form IS the default front
+int resolve_fronted(const mfcc_hip_params *p, int frame_length, const mfcc_hip_mel_bank *bank, const mfcc_hip_front *front,
+                    Resolved &r) {
+    const int rc = resolve_banked(p, frame_length, bank, r);
+    if (rc || !front) return rc;
+    if (front->struct_size != sizeof(mfcc_hip_front)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    for (int v : front->reserved)
+        if (v != 0) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (front->window < 0 || front->window >= kFrontWindows) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (front->symmetric != 0 && front->symmetric != 1) return MFCC_HIP_ERROR_INVALID_PARAM;
+    int num = front->preemph_num, den = front->preemph_den;
+    if (!reduce_preemph(num, den)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    r.front.window = front->window;
+    r.front.symmetric = front->symmetric;
+    r.front.num = num;
+    r.front.den = den;
+    return MFCC_HIP_SUCCESS;
+}
+
+inline bool is_fronted(const Resolved &r) { return !front_is_default(r.front); }
+
 // the mel matrix of a handle, [n_mel][nfft / 2 + 1], before the power scale: every float table is built from this
 std::vector<double> handle_mel(const Resolved &r) {
     if (is_htk(r)) return mel_dense_htk(r.nfft, r.n_mel, double(r.sample_rate), r.mel_lo, r.mel_hi);
@@ -196,9 +220,10 @@ inline mfcc_batch::Framing framing(const Resolved &r) {
 
 size_t count_frames(const Resolved &r, size_t n) { return mfcc_batch::frames_of(framing(r), n); }
 
-// the float window of a handle: periodic Hamming over the frame, zeros up to nfft (the frame is zero-padded at the end)
+// the float window of a handle: its front's window function (periodic Hamming by default) over the frame, zeros up to
+// nfft (the frame is zero-padded at the end).  Every float table is built from this vector and the front's pair
 std::vector<double> frame_window(const Resolved &r) {
-    std::vector<double> w = hamming_periodic(r.frame_len);
+    std::vector<double> w = front_window(r.front, r.frame_len);
     w.resize(size_t(r.nfft), 0.0);
     return w;
 }
@@ -206,8 +231,9 @@ std::vector<double> frame_window(const Resolved &r) {
 bool fixed_supported(const Resolved &r) {
     // RTL constraints: FFT sizes are powers of two (mfcc/misc/fft.py:351-353) for both the
     // nfft-point FFT and the (4 * nfilters)-point DCT FFT; hop = nfft // 3 (mfcc/core/mfcc.py:43); the window is the
-    // RTL's ROM curve over nfft samples: no frame length below nfft; its filterbank is the notebook's: no HTK bank
-    if (is_framed(r) || is_htk(r)) return false;
+    // RTL's ROM curve over nfft samples: no frame length below nfft and no other front; its filterbank is the notebook's:
+    // no HTK bank
+    if (is_framed(r) || is_htk(r) || is_fronted(r)) return false;
     if (!(is_pow2(4 * r.n_mel) && 4 * r.n_mel <= r.nfft && r.n_mel >= 4 && r.hop == r.nfft / 3 && r.nfft >= 64))
         return false;
     // filter points too dense for the streaming filterbank's ramp logic (filterbank.py:22-34, 88-142): the RTL then
@@ -263,7 +289,7 @@ struct mfcc_hip_handle {
     void *arena = nullptr;
     mfcc_k::FloatTables ft{};
     mfcc_k::FixedTables xt{};
-    mfcc_fused::FusedTables fu{};
+    mfcc_fused::W4Tables fu{};             // the twelve-wave kernel takes its base
     mfcc_fused160mb::Tables fmb{};
     mfcc_fixed512::Tables x5{};
     // the power-spectrum output (mfcc_hip_spectrum_*): the kernel of every such call (spectrum_plan.hpp: choose) and the
@@ -534,7 +560,12 @@ int build_tables(mfcc_hip_handle *h) {
     const Resolved &r = h->r;
     Arena a;
     // ---- float
-    std::vector<double> wd = frame_window(r);
+    // the window in double; the kernels' tables carry it over den (they form the integer den x[i] - num x[i-1]): one
+    // rounding of w / den to fp32
+    const std::vector<double> wfull = frame_window(r);
+    const int pe_num = r.front.num, pe_den = r.front.den;
+    std::vector<double> wd(wfull.size());
+    for (size_t i = 0; i < wd.size(); ++i) wd[i] = wfull[i] / double(pe_den);
     std::vector<float> win(wd.begin(), wd.end());
     const int M = r.nfft / 2;
     std::vector<float2> twf(M), tws(M + 1);
@@ -613,32 +644,43 @@ int build_tables(mfcc_hip_handle *h) {
     // a framed handle (frame_len < nfft) runs none of the fused forms below: their windows span nfft samples
     // ... and an HTK-bank handle runs the matrix-driven hop-160 form or the generic kernel, nothing else: the band
     // schedules and DC paths of the other forms are built around the notebook bank
-    const bool framed = is_framed(r), htk = is_htk(r);
+    // ... and another front than the reference's runs the four-wave 512 forms (pair up to num + den = 127) or the generic
+    // kernel: the twelve-wave 512 kernel's DC path folds 31/32 and a window symmetric about sample 256 into its digits, and
+    // the 1024 forms keep the pair at compile time.  The choice refuses; it never mis-computes
+    const bool framed = is_framed(r), htk = is_htk(r), fronted = is_fronted(r), pair_fused = front_fused(r.front);
     std::vector<char> fmb_blob;
     uint32_t fmb_mask = 0;
-    const bool have_h160mb = htk && mfcc_fused160mb::supported(r.nfft, r.hop, r.frame_len, r.n_mel, r.n_cep, is_logmel(r)) &&
-                             mfcc_fused160mb::build_tables(md, r.n_mel, r.n_cep, r.frame_len, r.power_scale, r.lifter, fmb_blob,
+    const bool have_h160mb = htk && pair_fused &&
+                             mfcc_fused160mb::supported(r.nfft, r.hop, r.frame_len, r.n_mel, r.n_cep, is_logmel(r)) &&
+                             mfcc_fused160mb::build_tables(md, r.n_mel, r.n_cep, wfull, pe_den, r.power_scale, r.lifter, fmb_blob,
                                                            fmb_mask);
     const size_t o_fmb = have_h160mb ? a.put(fmb_blob) : 0;
     bool have_h160 = false;
-    if (!htk && framed && mfcc_fused160::supported(r.nfft, r.hop, r.frame_len, r.n_mel, r.n_cep)) {
+    // the window the hop-170 tables are built with: the front's over all 512 samples (a framed handle's goes in behind)
+    const std::vector<double> w512 = r.nfft == mfcc_fused::kNfft ? front_window(r.front, mfcc_fused::kNfft) : std::vector<double>();
+    auto fused_tables = [&](bool dense) {
+        return dense ? mfcc_fused::build_tables<true>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, w512, pe_num,
+                                                      pe_den, fused_blob)
+                     : mfcc_fused::build_tables<false>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, w512, pe_num,
+                                                       pe_den, fused_blob);
+    };
+    if (!htk && framed && pair_fused && mfcc_fused160::supported(r.nfft, r.hop, r.frame_len, r.n_mel, r.n_cep)) {
         // the tables of the hop-170 form (none of them depends on the hop) with the frame's window in place of theirs
         fused_dcx = mfcc_fused::needs_dc_exact(r.sample_rate, r.n_mel);
-        have_h160 = !fused_dcx &&
-                    mfcc_fused::build_tables<false>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
+        have_h160 = !fused_dcx && fused_tables(false);
         if (!have_h160) {
             h->fused_dense = true;
-            have_h160 = mfcc_fused::build_tables<true>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
+            have_h160 = fused_tables(true);
         }
-        if (have_h160) mfcc_fused160::set_window(fused_blob, h->fused_dense, r.frame_len);
+        if (have_h160) mfcc_fused160::set_window(fused_blob, h->fused_dense, wfull, pe_den);
     }
-    if (!htk && !framed && mfcc_fused::supported(r.nfft, r.hop, r.n_mel, r.n_cep)) {
+    // a fronted handle has the four-wave form here, which has no log-mel tail: its log-mel rows come from the generic kernel
+    if (!htk && !framed && pair_fused && !(fronted && is_logmel(r)) && mfcc_fused::supported(r.nfft, r.hop, r.n_mel, r.n_cep)) {
         fused_dcx = mfcc_fused::needs_dc_exact(r.sample_rate, r.n_mel);    // only the dense instantiation has the DC path
-        have_fused = !fused_dcx &&
-                     mfcc_fused::build_tables<false>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
+        have_fused = !fused_dcx && fused_tables(false);
         if (!have_fused) {
             h->fused_dense = true;
-            have_fused = mfcc_fused::build_tables<true>(r.sample_rate, r.power_scale, r.lifter, r.n_cep, r.n_mel, fused_blob);
+            have_fused = fused_tables(true);
         }
     }
     size_t o_fu = 0;
@@ -646,7 +688,7 @@ int build_tables(mfcc_hip_handle *h) {
     std::vector<char> f1k_blob;
     int f1k_var = 0;
     bool f1k_fp32 = false, f1k_twelve = false;
-    bool have_1k = !htk && !framed && mfcc_fused1024::supported(r.nfft, r.hop, r.n_mel, r.n_cep);
+    bool have_1k = !htk && !framed && !fronted && mfcc_fused1024::supported(r.nfft, r.hop, r.n_mel, r.n_cep);
     if (have_1k) {
         // Default: the twelve-wave staging with the bf16-split contraction (kernel_fused1024_w12.hpp), every rate.
         // MFCC_HIP_FUSED1024 is a diagnostic override for A/B runs -- f32 / bf16: the eight-wave lockstep staging of
@@ -663,12 +705,13 @@ int build_tables(mfcc_hip_handle *h) {
     size_t o_f1k = 0;
     if (have_1k) o_f1k = a.put(f1k_blob);
     // ---- the power-spectrum kernels: the generic one reads the float tables above; the fused one has a blob of its own
-    h->spec_kernel = mfcc_spec::choose(r.nfft, r.hop, r.frame_len, r.float_impl == MFCC_HIP_IMPL_GENERIC);
-    h->fb_kernel = mfcc_fbank::choose(r.nfft, r.hop, r.frame_len, r.float_impl == MFCC_HIP_IMPL_GENERIC);
+    const bool power_generic = r.float_impl == MFCC_HIP_IMPL_GENERIC || !pair_fused;   // the power tile parks with preemph8
+    h->spec_kernel = mfcc_spec::choose(r.nfft, r.hop, r.frame_len, power_generic);
+    h->fb_kernel = mfcc_fbank::choose(r.nfft, r.hop, r.frame_len, power_generic);
     std::vector<char> spec_blob;
     size_t o_spec = 0;
     if (h->spec_kernel == mfcc_spec::Kernel::kFused512) {
-        mfcc_spec::build_tables(wd, spec_blob);
+        mfcc_spec::build_tables(wfull, spec_blob, pe_den);
         o_spec = a.put(spec_blob);
     }
 
@@ -687,6 +730,11 @@ int build_tables(mfcc_hip_handle *h) {
     h->ft.window_d = dc_exact ? reinterpret_cast<const double *>(b + o_wd) : nullptr;
     h->ft.n_mel = r.n_mel;
     h->ft.n_cep = r.n_cep;
+    h->ft.pe_num = float(pe_num);
+    h->ft.pe_den = float(pe_den);
+    h->ft.pe_num_i = pe_num;
+    h->ft.pe_den_i = pe_den;
+    const int pair = packed_preemph(pe_num, pe_den);
     if (have_fixed) {
         h->xt.curve = reinterpret_cast<const int *>(b + o_cv);
         h->xt.tw_fft = reinterpret_cast<const uint2 *>(b + o_xt);
@@ -704,13 +752,16 @@ int build_tables(mfcc_hip_handle *h) {
         h->xt.log2_dct = ilog2(4 * r.n_mel);
         h->xt.n_cep = r.n_cep;
     }
-    if (have_fused || have_h160) mfcc_fused::bind_tables(b + o_fu, r.n_cep, r.n_mel, h->fused_dense, fused_dcx, h->fu);
-    if (have_h160mb) mfcc_fused160mb::bind_tables(b + o_fmb, r.n_cep, r.n_mel, fmb_mask, h->fmb);
+    if (have_fused || have_h160) {
+        mfcc_fused::bind_tables(b + o_fu, r.n_cep, r.n_mel, h->fused_dense, fused_dcx, h->fu);
+        h->fu.preemph = pair;
+    }
+    if (have_h160mb) mfcc_fused160mb::bind_tables(b + o_fmb, r.n_cep, r.n_mel, fmb_mask, h->fmb, pair);
     if (have_1k) {
         if (f1k_fp32) mfcc_fused1024_f32::bind_tables(b + o_f1k, r.n_cep, f1k_var, h->f1k_f32);
         else mfcc_fused1024::bind_tables(b + o_f1k, r.n_cep, f1k_var, h->f1k);
     }
-    if (h->spec_kernel == mfcc_spec::Kernel::kFused512) mfcc_spec::bind_tables(b + o_spec, r.power_scale, h->sf);
+    if (h->spec_kernel == mfcc_spec::Kernel::kFused512) mfcc_spec::bind_tables(b + o_spec, r.power_scale, h->sf, pair);
     if (have_fixed512) {
         mfcc_fixed512::bind_tables(b + o_x5, h->x5);
         h->x5.tw64a = x5_tw[0]; h->x5.tw64b = x5_tw[1]; h->x5.tw192a = x5_tw[2]; h->x5.tw192b = x5_tw[3];
@@ -728,7 +779,7 @@ int build_tables(mfcc_hip_handle *h) {
     // diagnostic override for A/B runs: MFCC_HIP_FUSED512=w4 keeps the four-wave form (not on a log-mel handle: the
     // four-wave form has no log-mel tail)
     const char *e512 = is_logmel(r) ? nullptr : std::getenv("MFCC_HIP_FUSED512");
-    const bool w4 = e512 && std::strcmp(e512, "w4") == 0;
+    const bool w4 = fronted || (e512 && std::strcmp(e512, "w4") == 0);
     h->float_kernel = FloatKernel::kGeneric;
     if (r.float_impl == MFCC_HIP_IMPL_GENERIC) {
         // the tables above stay allocated and unused
@@ -768,7 +819,8 @@ int launch_generic(mfcc_hip_handle *h, const mfcc_k::StreamDesc &s, unsigned blo
 
 // what the generic spectrum and filterbank kernels read of the handle's float tables
 mfcc_k::PowerTables power_tables(const mfcc_hip_handle *h) {
-    return {h->ft.window, h->ft.tw_fft, h->ft.tw_split, float(1.0 / (h->r.power_scale * h->r.power_scale))};
+    return {h->ft.window, h->ft.tw_fft, h->ft.tw_split, float(1.0 / (h->r.power_scale * h->r.power_scale)), h->ft.pe_num,
+            h->ft.pe_den};
 }
 
 // The kernel of a call over int16 samples: the spectrum's, the filterbank's or the handle's own, as c says
@@ -1984,8 +2036,13 @@ int mfcc_hip_get_table_framed(const mfcc_hip_params *p, int frame_length, int wh
 
 int mfcc_hip_get_table_banked(const mfcc_hip_params *p, int frame_length, const mfcc_hip_mel_bank *bank, int which,
                               void *buf, size_t cap, size_t *n_bytes) {
+    return mfcc_hip_get_table_fronted(p, frame_length, bank, nullptr, which, buf, cap, n_bytes);
+}
+
+int mfcc_hip_get_table_fronted(const mfcc_hip_params *p, int frame_length, const mfcc_hip_mel_bank *bank,
+                               const mfcc_hip_front *front, int which, void *buf, size_t cap, size_t *n_bytes) {
     Resolved r;
-    int rc = resolve_banked(p, frame_length, bank, r);
+    int rc = resolve_fronted(p, frame_length, bank, front, r);
     if (rc) return rc;
     std::vector<char> blob;
     auto put = [&](const void *d, size_t n) { blob.assign((const char *)d, (const char *)d + n); };
@@ -2067,10 +2124,26 @@ int mfcc_hip_mel_bank_of(const mfcc_hip_handle *h, mfcc_hip_mel_bank *out) {
 
 int mfcc_hip_create_banked(const mfcc_hip_params *p, int frame_length, const mfcc_hip_mel_bank *bank,
                            mfcc_hip_handle **out) {
+    return mfcc_hip_create_fronted(p, frame_length, bank, nullptr, out);
+}
+
+int mfcc_hip_front_of(const mfcc_hip_handle *h, mfcc_hip_front *out) {
+    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::memset(out, 0, sizeof *out);
+    out->struct_size = sizeof *out;
+    out->window = h->r.front.window;
+    out->symmetric = h->r.front.symmetric;
+    out->preemph_num = h->r.front.num;
+    out->preemph_den = h->r.front.den;
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_create_fronted(const mfcc_hip_params *p, int frame_length, const mfcc_hip_mel_bank *bank,
+                            const mfcc_hip_front *front, mfcc_hip_handle **out) {
     if (!out) return MFCC_HIP_ERROR_INVALID_PARAM;
     *out = nullptr;
     Resolved r;
-    int rc = resolve_banked(p, frame_length, bank, r);
+    int rc = resolve_fronted(p, frame_length, bank, front, r);
     if (rc) return rc;
     int ndev = 0;
     g_create_hip_error = int(hipGetDeviceCount(&ndev));

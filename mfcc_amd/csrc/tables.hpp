@@ -40,6 +40,64 @@ inline std::vector<double> hamming_periodic(int n) {
     return w;
 }
 
+// ---- the front of a handle (include/mfcc_hip.h: mfcc_hip_create_fronted): the window function over the frame and the
+// pre-emphasis y[i] = x[i] - (num / den) x[i-1] as a reduced integer pair.  Default-constructed: the reference's, the
+// periodic Hamming window and 31/32.  The kinds are enum mfcc_hip_window's values.
+struct Front {
+    int window = 0;        // 0 Hamming, 1 Hann, 2 Povey, 3 Blackman, 4 rectangular
+    int symmetric = 0;     // 0: periodic (denominator L), 1: symmetric (L - 1)
+    int num = 31, den = 32;
+};
+constexpr int kFrontWindows = 5;
+// What the kernels form is the integer e[i] = den x[i] - num x[i-1]; 1 / den is folded into the window tables.  With
+// int16 samples |e| <= (num + den) 2^15: below 2^23 for num + den <= 255 (exact in int32 and in fp32: every kernel), below
+// 2^22 for num + den <= 127 (the fused kernels' biased dot product, fused_common.hpp: preemph8).
+constexpr int kMaxPreemphSum = 255, kMaxFusedPreemphSum = 127;
+
+inline int gcd_of(int a, int b) {
+    while (b) {
+        const int t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+// validates and reduces the pair; false: outside 0 <= num <= den, den >= 1, num + den <= 255
+inline bool reduce_preemph(int &num, int &den) {
+    if (num < 0 || den < 1 || num > den || (long long)num + den > kMaxPreemphSum) return false;
+    const int g = gcd_of(den, num);
+    num /= g;
+    den /= g;
+    return true;
+}
+inline bool front_is_default(const Front &f) { return f.window == 0 && f.symmetric == 0 && f.num == 31 && f.den == 32; }
+inline bool front_fused(const Front &f) { return f.num + f.den <= kMaxFusedPreemphSum; }
+// the pair as the fused kernels' dot-product operand: (int16 -num, int16 den), -num in the low half
+inline int packed_preemph(int num, int den) { return int((uint32_t(den) << 16) | (uint32_t(-num) & 0xffffu)); }
+
+// The window of `n` samples in double.  The default front's is hamming_periodic above, value for value; every other one
+// is the closed form over i / D, D = n (periodic) or n - 1 (symmetric).
+inline std::vector<double> front_window(const Front &f, int n) {
+    if (f.window == 0 && !f.symmetric) return hamming_periodic(n);
+    std::vector<double> w(n);
+    const double D = double(f.symmetric ? n - 1 : n);
+    for (int i = 0; i < n; ++i) {
+        const double c1 = std::cos(2.0 * kPi * double(i) / D);
+        switch (f.window) {
+            case 0: w[i] = 0.54 - 0.46 * c1; break;
+            case 1: w[i] = 0.5 - 0.5 * c1; break;
+            case 2: {
+                const double h = 0.5 - 0.5 * c1;
+                w[i] = h > 0.0 ? std::pow(h, 0.85) : 0.0;
+                break;
+            }
+            case 3: w[i] = 0.42 - 0.5 * c1 + 0.08 * std::cos(4.0 * kPi * double(i) / D); break;
+            default: w[i] = 1.0; break;
+        }
+    }
+    return w;
+}
+
 // MFCC.ipynb cells 26-27 == mfcc/core/filterbank.py:9-20
 inline std::vector<int> mel_points(int nfft, int n_mel, double sample_rate) {
     double fmin = 0.0, fmax = sample_rate / 2.0;
