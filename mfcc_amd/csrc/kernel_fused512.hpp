@@ -886,8 +886,9 @@ __device__ __forceinline__ void tile_loop_w4(const mfcc_k::StreamDesc s, const W
             for (int n1 = 0; n1 < 32; ++n1) ep[n1 >> 1][n1 & 1] = sp[16 * n1];
         }
         if constexpr (DCX) {
-            // bin 0 of this lane's 32 samples in double: sum_n1 w[16 n1 + n2] e[16 n1 + n2] (the products of a
-            // 24-bit window value and a 22-bit integer are exact in double; so is their sum to 2^-53)
+            // bin 0 of this lane's 32 samples in double: sum_n1 (w[16 n1 + n2] / den) e[16 n1 + n2].  The row is w / den
+            // in full double precision and e an integer below 2^22 in magnitude: each fused multiply-add rounds once,
+            // at 2^-53 of the running sum
             const double *wr = Wd + lo * kWdRow;
             double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
 #pragma unroll

@@ -75,11 +75,51 @@ static const char *check_case(int window, int symmetric, int num, int den, int L
     return nullptr;
 }
 
+// A line with seven fields, "window symmetric num den frame_len rate n_mel": the dense four-wave tables at that sample
+// rate and filter count (32 or 16) under the front.  Checks
+//   win_dc   [16 n2][32 n1] == w[16 n1 + n2] / den in double, behind set_window when frame_len < 512
+//   every mel operand -- the fp32 and bf16 set lists, with and without bin 0, bin 0's weights, the column-16 rows and the
+//   DCT rows -- is the default front's byte for byte: the bank does not depend on the front
+// and prints "ok <needs_dc_exact> <entries checked>".
+static const char *check_rate(int window, int symmetric, int num, int den, int L, int rate, int n_mel, long &checked) {
+    using namespace mfcc_tables;
+    Front f;
+    f.window = window, f.symmetric = symmetric, f.num = num, f.den = den;
+    std::vector<double> w = front_window(f, L);
+    w.resize(mfcc_fused::kNfft, 0.0);
+    const std::vector<double> w512 = front_window(f, mfcc_fused::kNfft);
+    const int n_cep = n_mel < 13 ? n_mel : 13;
+    std::vector<char> blob, plain;
+    if (!mfcc_fused::build_tables<true>(rate, 512.0, 0.0, n_cep, n_mel, w512, num, den, blob)) return "dense builder refused";
+    if (!mfcc_fused::build_tables<true>(rate, 512.0, 0.0, n_cep, n_mel, plain)) return "dense builder refused the default front";
+    if (L < mfcc_fused::kNfft) mfcc_fused160::set_window(blob, true, w, den);
+    const mfcc_fused::BlobOffsets o = mfcc_fused::blob_offsets(true);
+    if (blob.size() != o.total || plain.size() != o.total) return "blob size";
+    const double *wdc = reinterpret_cast<const double *>(blob.data() + o.win_dc);
+    for (int n2 = 0; n2 < 16; ++n2)
+        for (int n1 = 0; n1 < 32; ++n1, ++checked)
+            if (wdc[n2 * 32 + n1] != w[16 * n1 + n2] / double(den)) return "win_dc row";
+    const size_t same[][2] = {{o.tw, o.win_dc}, {o.a_mel_bf_nodc, o.a_dc_i8}, {o.a_dct_bf, o.total}};
+    for (const auto &r : same) {
+        if (memcmp(blob.data() + r[0], plain.data() + r[0], r[1] - r[0]) != 0) return "a mel operand differs from the default front's";
+        checked += long(r[1] - r[0]) / 4;
+    }
+    return nullptr;
+}
+
 int main() {
     char line[256];
     while (fgets(line, sizeof line, stdin)) {
-        int window, symmetric, num, den, L;
-        if (sscanf(line, "%d %d %d %d %d", &window, &symmetric, &num, &den, &L) != 5) continue;
+        int window, symmetric, num, den, L, rate, n_mel;
+        const int fields = sscanf(line, "%d %d %d %d %d %d %d", &window, &symmetric, &num, &den, &L, &rate, &n_mel);
+        if (fields == 7) {
+            long checked = 0;
+            const char *bad = check_rate(window, symmetric, num, den, L, rate, n_mel, checked);
+            if (bad) printf("FAIL %s\n", bad);
+            else printf("ok %d %ld\n", int(mfcc_fused::needs_dc_exact(rate, n_mel)), checked);
+            continue;
+        }
+        if (fields != 5) continue;
         long checked = 0;
         const char *bad = check_case(window, symmetric, num, den, L, checked);
         if (bad) printf("FAIL %s\n", bad);
