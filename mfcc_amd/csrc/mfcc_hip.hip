@@ -3032,6 +3032,109 @@ int mfcc_hip_stream_flush(mfcc_hip_stream *s, void *out, size_t cap, size_t *n_f
     return mfcc_hip_stream_reset(s);
 }
 
+// ---- live objects: what a stream bank, a gate tracker and a resampler share (the session above keeps buffers of its own
+// and is timed against the bank in profiles/session_bank_of_one.txt).  Each keeps a
+// handle `h`, `n` lines, device allocations of its own and per-line counts on the host, and counts as a session of its
+// handle (include/mfcc_hip.h: the lifetime rule at mfcc_hip_destroy)
+
+}  // extern "C"
+
+namespace {
+
+// The first checks of every create: INVALID_PARAM for a missing handle or out pointer, then -- *out cleared -- for a
+// handle already given back or no lines.  The object's own checks follow
+template <class T>
+int live_check(const mfcc_hip_handle *h, size_t n_lines, T **out) {
+    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
+    *out = nullptr;
+    return h->destroy_pending || !n_lines ? MFCC_HIP_ERROR_INVALID_PARAM : MFCC_HIP_SUCCESS;
+}
+
+// a new object of n_lines lines that counts as a session of h from here on; NULL: no memory
+template <class T>
+T *live_new(mfcc_hip_handle *h, size_t n_lines) {
+    T *o = new (std::nothrow) T();
+    if (!o) return nullptr;
+    o->h = h;
+    o->n = n_lines;
+    ++h->n_sessions;
+    return o;
+}
+
+// The object's work drained -- a push may be in flight on a caller's stream --, its device memory (T::owned) freed, the
+// object deleted and its handle released: the last one frees a handle that was already given back
+template <class T>
+void live_destroy(T *o) {
+    if (!o) return;
+    mfcc_hip_handle *h = o->h;
+    {
+        DeviceGuard guard(h->device);
+        if (h->scratch_used) (void)hipEventSynchronize(h->scratch_done);
+        (void)hipStreamSynchronize(h->stream);
+        for (void *p : o->owned())
+            if (p) (void)hipFree(p);
+        delete o;
+    }
+    if (--h->n_sessions == 0 && h->destroy_pending) mfcc_hip_destroy(h);
+}
+
+// the end of a create: e is what its allocations and copies answered
+template <class T>
+int live_created(T *o, hipError_t e, T **out) {
+    if (e == hipSuccess) {
+        *out = o;
+        return MFCC_HIP_SUCCESS;
+    }
+    o->h->last_hip = int(e);
+    live_destroy(o);
+    return e == hipErrorOutOfMemory ? MFCC_HIP_ERROR_NO_MEM : MFCC_HIP_ERROR_OTHER;
+}
+
+// a count per line, copied to the caller
+template <class T>
+int live_counts(const T *o, std::vector<size_t> T::*count, size_t *dst) {
+    if (!o || !dst) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::copy((o->*count).begin(), (o->*count).end(), dst);
+    return MFCC_HIP_SUCCESS;
+}
+
+// `idx` of a flush / reset / window request as a list: NULL = every index below `size`, else n distinct ones below it
+int live_lines(size_t size, const size_t *idx, size_t n, std::vector<size_t> &list) {
+    list.clear();
+    if (!idx) {
+        for (size_t u = 0; u < size; ++u) list.push_back(u);
+        return MFCC_HIP_SUCCESS;
+    }
+    std::vector<char> hit(size, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (idx[i] >= size || hit[idx[i]]) return MFCC_HIP_ERROR_INVALID_PARAM;
+        hit[idx[i]] = 1;
+        list.push_back(idx[i]);
+    }
+    return MFCC_HIP_SUCCESS;
+}
+
+// The listed lines back in the reset state: these counts of theirs are 0.  The counts travel with the records of every
+// launch, and a line whose count is 0 reads nothing of what it has on the device
+void live_zero(const std::vector<size_t> &list, std::initializer_list<std::vector<size_t> *> counts) {
+    for (std::vector<size_t> *c : counts)
+        for (size_t u : list) (*c)[u] = 0;
+}
+
+// a reset that is nothing more: `lines` as a list (NULL: every line), then that count of theirs to 0
+template <class T>
+int live_reset(T *o, const size_t *lines, size_t n, std::vector<size_t> T::*count) {
+    if (!o) return MFCC_HIP_ERROR_INVALID_PARAM;
+    std::vector<size_t> list;
+    const int rc = live_lines(o->n, lines, n, list);
+    if (!rc) live_zero(list, {&(o->*count)});
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
 // ---- stream bank (include/mfcc_hip.h: mfcc_hip_bank_*; kernel_stream_bank.hpp) -------------
 // N sessions whose state rows ([history | pending], frame_len int16 each) lie in one device allocation.  A push is planned on
 // the host from lengths alone, described by one record per stream in the pinned descriptor pool and carried out by ONE
@@ -3063,6 +3166,7 @@ struct mfcc_hip_bank {
     // the device, [n][2][W] carry and local smoother per (stream, column), then the decay table A_k
     mfcc_pcen::Prm pcen_prm{};
     float *d_pcen = nullptr;
+    std::vector<void *> owned() const { return {d_state, d_ring, d_tail, d_pcen, st_in.p, st_out.p}; }
 };
 
 namespace {
@@ -3173,22 +3277,6 @@ int bank_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const
     return MFCC_HIP_SUCCESS;
 }
 
-// `idx` of a flush / reset / window request as a list: NULL = every index below `size`, else n distinct ones below it
-int bank_list(size_t size, const size_t *idx, size_t n, std::vector<size_t> &list) {
-    list.clear();
-    if (!idx) {
-        for (size_t u = 0; u < size; ++u) list.push_back(u);
-        return MFCC_HIP_SUCCESS;
-    }
-    std::vector<char> hit(size, 0);
-    for (size_t i = 0; i < n; ++i) {
-        if (idx[i] >= size || hit[idx[i]]) return MFCC_HIP_ERROR_INVALID_PARAM;
-        hit[idx[i]] = 1;
-        list.push_back(idx[i]);
-    }
-    return MFCC_HIP_SUCCESS;
-}
-
 // The end of the listed streams.  give: a flush, to host memory (synchronous): with the handle's pad mode STREAM the
 // zero-padded tail frame (main.c:134-144: one frame over history | pending | zeros) joins each stream as its last row,
 // the held rows and that one are returned with the end clamped -- fo[i + 1] - fo[i] rows of stream list[i] (fo NULL:
@@ -3222,7 +3310,7 @@ int bank_end(mfcc_hip_bank *b, const std::vector<size_t> &list, bool give, void 
     if (result_bytes) HIP_TRY(h, hipMemcpyAsync(out, b->st_out.p, result_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipGetLastError());
     if ((rc = scratch_release(h))) return rc;
-    for (size_t u : list) b->pending[u] = b->seen[u] = b->held[u] = 0;
+    live_zero(list, {&b->pending, &b->seen, &b->held});
     // as it has been: a plain bank waits for its tail frames, an online one after every flush
     if (emit || (give && b->s.online())) HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MFCC_HIP_SUCCESS;
@@ -3231,11 +3319,9 @@ int bank_end(mfcc_hip_bank *b, const std::vector<size_t> &list, bool give, void 
 // a bank on a checked handle; norm / order as validated by the caller (NONE and 0: a plain bank)
 int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int window, int order, int dwin,
                 mfcc_hip_bank **out, const mfcc_pcen::Prm *pcen = nullptr) {
-    mfcc_hip_bank *b = new (std::nothrow) mfcc_hip_bank();
+    mfcc_hip_bank *b = live_new<mfcc_hip_bank>(h, n_streams);
     if (!b) return MFCC_HIP_ERROR_NO_MEM;
-    b->h = h;
     b->fixed = fixed != 0;
-    b->n = n_streams;
     b->pending.assign(n_streams, 0);
     b->after.assign(n_streams, 0);
     b->seen.assign(n_streams, 0);
@@ -3263,16 +3349,10 @@ int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int w
         s.g = size_t(mfcc_online::tile_rows(int(W), order, dwin));
         b->dwin = dwin;
     }
-    ++h->n_sessions;
     DeviceGuard guard(h->device);
     const size_t bytes = n_streams * s.flen * sizeof(int16_t);
     const size_t ring_bytes = n_streams * size_t(b->depth) * W * sizeof(float);
     const size_t tail_bytes = n_streams * 2 * s.L * W * sizeof(float);
-    auto fail = [&](hipError_t e) {
-        h->last_hip = int(e);
-        mfcc_hip_bank_destroy(b);
-        return e == hipErrorOutOfMemory ? MFCC_HIP_ERROR_NO_MEM : MFCC_HIP_ERROR_OTHER;
-    };
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_state), bytes + 64);
     if (e == hipSuccess && ring_bytes) e = hipMalloc(reinterpret_cast<void **>(&b->d_ring), ring_bytes + 64);
     if (e == hipSuccess && tail_bytes) e = hipMalloc(reinterpret_cast<void **>(&b->d_tail), tail_bytes + 64);
@@ -3285,9 +3365,7 @@ int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int w
     }
     if (e == hipSuccess) e = hipMemsetAsync(b->d_state, 0, bytes, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(e);
-    *out = b;
-    return MFCC_HIP_SUCCESS;
+    return live_created(b, e, out);
 }
 
 // The checks the three create entries share, then the bank.  The bank's settings are its own: the handle must be a raw
@@ -3295,9 +3373,7 @@ int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int w
 // that can run the path asked for; an online bank (float) takes log-mel rows where it has PCEN
 int bank_create_checked(mfcc_hip_handle *h, int fixed, bool online, size_t n_streams, const mfcc_hip_pcen *p, int normalize,
                         int normalize_window, int delta_order, int delta_window, mfcc_hip_bank **out) {
-    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
-    *out = nullptr;
-    if (h->destroy_pending || !n_streams || (p && !pcen_ok(p))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (live_check(h, n_streams, out) || (p && !pcen_ok(p))) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (rated(h)) return MFCC_HIP_ERROR_UNSUPPORTED;           // a line's rate conversion keeps state between pushes
     if (p && !is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;
@@ -3337,11 +3413,7 @@ size_t mfcc_hip_bank_row_width(const mfcc_hip_bank *b) { return b ? b->s.out_wid
 
 int mfcc_hip_bank_lag(const mfcc_hip_bank *b) { return b ? int(b->s.L) : 0; }
 
-int mfcc_hip_bank_held(const mfcc_hip_bank *b, size_t *held) {
-    if (!b || !held) return MFCC_HIP_ERROR_INVALID_PARAM;
-    std::copy(b->held.begin(), b->held.end(), held);
-    return MFCC_HIP_SUCCESS;
-}
+int mfcc_hip_bank_held(const mfcc_hip_bank *b, size_t *held) { return live_counts(b, &mfcc_hip_bank::held, held); }
 
 int mfcc_hip_bank_plan_online(const mfcc_hip_params *p, int lag, const size_t *pending, const size_t *held,
                               const size_t *offsets, size_t n_streams, size_t *frame_offsets, size_t *pending_after,
@@ -3365,35 +3437,15 @@ int mfcc_hip_bank_flush_ragged(mfcc_hip_bank *b, const size_t *streams, size_t n
                                size_t *frame_offsets) {
     if (!b || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
     std::vector<size_t> list;
-    const int rc = bank_list(b->n, streams, n, list);
+    const int rc = live_lines(b->n, streams, n, list);
     return rc ? rc : bank_end(b, list, true, out, out_capacity, frame_offsets);
 }
 
-void mfcc_hip_bank_destroy(mfcc_hip_bank *b) {
-    if (!b) return;
-    mfcc_hip_handle *h = b->h;
-    {
-        DeviceGuard guard(h->device);
-        if (h->scratch_used) (void)hipEventSynchronize(h->scratch_done);    // a push may be in flight on a caller's stream
-        (void)hipStreamSynchronize(h->stream);
-        if (b->d_state) (void)hipFree(b->d_state);
-        if (b->d_ring) (void)hipFree(b->d_ring);
-        if (b->d_tail) (void)hipFree(b->d_tail);
-        if (b->d_pcen) (void)hipFree(b->d_pcen);
-        if (b->st_in.p) (void)hipFree(b->st_in.p);
-        if (b->st_out.p) (void)hipFree(b->st_out.p);
-        delete b;
-    }
-    if (--h->n_sessions == 0 && h->destroy_pending) mfcc_hip_destroy(h);
-}
+void mfcc_hip_bank_destroy(mfcc_hip_bank *b) { live_destroy(b); }
 
 size_t mfcc_hip_bank_size(const mfcc_hip_bank *b) { return b ? b->n : 0; }
 
-int mfcc_hip_bank_pending(const mfcc_hip_bank *b, size_t *pending) {
-    if (!b || !pending) return MFCC_HIP_ERROR_INVALID_PARAM;
-    std::copy(b->pending.begin(), b->pending.end(), pending);
-    return MFCC_HIP_SUCCESS;
-}
+int mfcc_hip_bank_pending(const mfcc_hip_bank *b, size_t *pending) { return live_counts(b, &mfcc_hip_bank::pending, pending); }
 
 int mfcc_hip_bank_plan(const mfcc_hip_params *p, const size_t *pending, const size_t *offsets, size_t n_streams,
                        size_t *frame_offsets, size_t *pending_after) {
@@ -3444,7 +3496,7 @@ int mfcc_hip_bank_flush(mfcc_hip_bank *b, const size_t *streams, size_t n, void 
                         size_t *n_frames_out) {
     if (!b) return MFCC_HIP_ERROR_INVALID_PARAM;
     std::vector<size_t> list;
-    const int rc = bank_list(b->n, streams, n, list);
+    const int rc = live_lines(b->n, streams, n, list);
     if (rc) return rc;
     if (b->s.L > 0) return MFCC_HIP_ERROR_UNSUPPORTED;      // ragged output: mfcc_hip_bank_flush_ragged
     if (n_frames_out) *n_frames_out = b->h->r.pad_mode == MFCC_HIP_PAD_STREAM ? list.size() : 0;
@@ -3454,7 +3506,7 @@ int mfcc_hip_bank_flush(mfcc_hip_bank *b, const size_t *streams, size_t n, void 
 int mfcc_hip_bank_reset(mfcc_hip_bank *b, const size_t *streams, size_t n) {
     if (!b) return MFCC_HIP_ERROR_INVALID_PARAM;
     std::vector<size_t> list;
-    const int rc = bank_list(b->n, streams, n, list);
+    const int rc = live_lines(b->n, streams, n, list);
     return rc ? rc : bank_end(b, list, false, nullptr, 0, nullptr);
 }
 
@@ -3471,6 +3523,7 @@ struct mfcc_hip_gate {
     long long threshold = 0;
     int16_t *d_ring = nullptr;           // [n][D][n_cep]
     std::vector<size_t> seen;            // frames since create / reset: depends on chunk lengths only
+    std::vector<void *> owned() const { return {d_ring}; }
 };
 
 namespace {
@@ -3648,48 +3701,20 @@ int mfcc_hip_gate_plan(int n_frames, int stride, const size_t *seen, const size_
 
 int mfcc_hip_gate_create(mfcc_hip_handle *h, size_t n_lines, int n_cep, int n_frames, int stride, long long threshold,
                          mfcc_hip_gate **out) {
-    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
-    *out = nullptr;
-    if (h->destroy_pending || !n_lines || !gate_shape_ok(n_cep, n_frames, stride) || threshold < 0)
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    mfcc_hip_gate *g = new (std::nothrow) mfcc_hip_gate();
+    if (live_check(h, n_lines, out) || !gate_shape_ok(n_cep, n_frames, stride) || threshold < 0) return MFCC_HIP_ERROR_INVALID_PARAM;
+    mfcc_hip_gate *g = live_new<mfcc_hip_gate>(h, n_lines);
     if (!g) return MFCC_HIP_ERROR_NO_MEM;
-    g->h = h;
-    g->n = n_lines;
     g->g = mfcc_gate::geometry(n_cep, n_frames, stride);
     g->D = n_frames + stride - 1;
     g->threshold = threshold;
     g->seen.assign(n_lines, 0);
-    ++h->n_sessions;
     DeviceGuard guard(h->device);
-    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&g->d_ring), n_lines * size_t(g->D) * size_t(n_cep) * sizeof(int16_t) + 64);
-    if (e != hipSuccess) {
-        h->last_hip = int(e);
-        mfcc_hip_gate_destroy(g);
-        return e == hipErrorOutOfMemory ? MFCC_HIP_ERROR_NO_MEM : MFCC_HIP_ERROR_OTHER;
-    }
-    *out = g;
-    return MFCC_HIP_SUCCESS;
+    return live_created(g, hipMalloc(reinterpret_cast<void **>(&g->d_ring), n_lines * size_t(g->D) * size_t(n_cep) * sizeof(int16_t) + 64), out);
 }
 
-void mfcc_hip_gate_destroy(mfcc_hip_gate *g) {
-    if (!g) return;
-    mfcc_hip_handle *h = g->h;
-    {
-        DeviceGuard guard(h->device);
-        if (h->scratch_used) (void)hipEventSynchronize(h->scratch_done);    // a push may be in flight on a caller's stream
-        (void)hipStreamSynchronize(h->stream);
-        if (g->d_ring) (void)hipFree(g->d_ring);
-        delete g;
-    }
-    if (--h->n_sessions == 0 && h->destroy_pending) mfcc_hip_destroy(h);
-}
+void mfcc_hip_gate_destroy(mfcc_hip_gate *g) { live_destroy(g); }
 
-int mfcc_hip_gate_seen(const mfcc_hip_gate *g, size_t *seen) {
-    if (!g || !seen) return MFCC_HIP_ERROR_INVALID_PARAM;
-    std::copy(g->seen.begin(), g->seen.end(), seen);
-    return MFCC_HIP_SUCCESS;
-}
+int mfcc_hip_gate_seen(const mfcc_hip_gate *g, size_t *seen) { return live_counts(g, &mfcc_hip_gate::seen, seen); }
 
 int mfcc_hip_gate_push_dev(mfcc_hip_gate *g, const void *d_rows, const size_t *frame_offsets, void *d_power, void *d_gate,
                            void *d_gate_ref, size_t capacity_windows, size_t *win_offsets) {
@@ -3743,15 +3768,7 @@ int mfcc_hip_gate_push_dev(mfcc_hip_gate *g, const void *d_rows, const size_t *f
     return MFCC_HIP_SUCCESS;
 }
 
-int mfcc_hip_gate_reset(mfcc_hip_gate *g, const size_t *lines, size_t n) {
-    if (!g) return MFCC_HIP_ERROR_INVALID_PARAM;
-    std::vector<size_t> list;                           // lines == NULL: every line
-    const int rc = bank_list(g->n, lines, n, list);
-    if (rc) return rc;
-    // the frame counts travel with every push's records: a line whose count is 0 reads nothing of its ring
-    for (size_t u : list) g->seen[u] = 0;
-    return MFCC_HIP_SUCCESS;
-}
+int mfcc_hip_gate_reset(mfcc_hip_gate *g, const size_t *lines, size_t n) { return live_reset(g, lines, n, &mfcc_hip_gate::seen); }
 
 int mfcc_hip_gate_window_dev(mfcc_hip_gate *g, const size_t *lines, size_t n, void *d_out) {
     if (!g || (n && !lines)) return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -3759,7 +3776,7 @@ int mfcc_hip_gate_window_dev(mfcc_hip_gate *g, const size_t *lines, size_t n, vo
     const mfcc_gate::Geo &geo = g->g;
     if (!n) return MFCC_HIP_SUCCESS;
     std::vector<size_t> list;
-    if (bank_list(g->n, lines, n, list)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (live_lines(g->n, lines, n, list)) return MFCC_HIP_ERROR_INVALID_PARAM;
     for (size_t u : list)
         if (g->seen[u] < size_t(geo.n_frames)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 1)) return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -3793,6 +3810,7 @@ struct mfcc_hip_resampler {
     size_t hist_stride = 0;              // K - 1 rounded up to 8
     std::vector<size_t> seen;            // samples since create / reset / flush: depends on chunk lengths only
     std::vector<unsigned char> cur;      // which of a line's two buffers holds its history
+    std::vector<void *> owned() const { return {d_taps, d_hist}; }
 };
 
 namespace {
@@ -3849,17 +3867,13 @@ int mfcc_hip_resampler_plan(int in_rate, int out_rate, const size_t *seen, const
 
 int mfcc_hip_resampler_create(mfcc_hip_handle *h, size_t n_lines, int sample_format, int in_rate, int out_rate,
                               mfcc_hip_resampler **out) {
-    if (!h || !out) return MFCC_HIP_ERROR_INVALID_PARAM;
-    *out = nullptr;
-    if (h->destroy_pending || !n_lines || !mfcc_decode::known(sample_format)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (live_check(h, n_lines, out) || !mfcc_decode::known(sample_format)) return MFCC_HIP_ERROR_INVALID_PARAM;
     mfcc_rs::Geometry g;
     std::vector<int16_t> t;
     const int rc = rs_table(in_rate, out_rate, g, t);
     if (rc) return rc;
-    mfcc_hip_resampler *r = new (std::nothrow) mfcc_hip_resampler();
+    mfcc_hip_resampler *r = live_new<mfcc_hip_resampler>(h, n_lines);
     if (!r) return MFCC_HIP_ERROR_NO_MEM;
-    r->h = h;
-    r->n = n_lines;
     r->fmt = sample_format;
     r->in_rate = in_rate;
     r->out_rate = out_rate;
@@ -3867,48 +3881,19 @@ int mfcc_hip_resampler_create(mfcc_hip_handle *h, size_t n_lines, int sample_for
     r->hist_stride = (size_t(g.K) - 1 + 7) & ~size_t(7);
     r->seen.assign(n_lines, 0);
     r->cur.assign(n_lines, 0);
-    ++h->n_sessions;
     DeviceGuard guard(h->device);
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&r->d_taps), t.size() * sizeof(int16_t));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_hist), 2 * n_lines * r->hist_stride * sizeof(int16_t));
     if (e == hipSuccess) e = hipMemcpy(r->d_taps, t.data(), t.size() * sizeof(int16_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        h->last_hip = int(e);
-        mfcc_hip_resampler_destroy(r);
-        return e == hipErrorOutOfMemory ? MFCC_HIP_ERROR_NO_MEM : MFCC_HIP_ERROR_OTHER;
-    }
-    *out = r;
-    return MFCC_HIP_SUCCESS;
+    return live_created(r, e, out);
 }
 
-void mfcc_hip_resampler_destroy(mfcc_hip_resampler *r) {
-    if (!r) return;
-    mfcc_hip_handle *h = r->h;
-    {
-        DeviceGuard guard(h->device);
-        if (h->scratch_used) (void)hipEventSynchronize(h->scratch_done);    // a push may be in flight on a caller's stream
-        (void)hipStreamSynchronize(h->stream);
-        if (r->d_taps) (void)hipFree(r->d_taps);
-        if (r->d_hist) (void)hipFree(r->d_hist);
-        delete r;
-    }
-    if (--h->n_sessions == 0 && h->destroy_pending) mfcc_hip_destroy(h);
-}
+void mfcc_hip_resampler_destroy(mfcc_hip_resampler *r) { live_destroy(r); }
 
-int mfcc_hip_resampler_seen(const mfcc_hip_resampler *r, size_t *seen) {
-    if (!r || !seen) return MFCC_HIP_ERROR_INVALID_PARAM;
-    std::copy(r->seen.begin(), r->seen.end(), seen);
-    return MFCC_HIP_SUCCESS;
-}
+int mfcc_hip_resampler_seen(const mfcc_hip_resampler *r, size_t *seen) { return live_counts(r, &mfcc_hip_resampler::seen, seen); }
 
 int mfcc_hip_resampler_reset(mfcc_hip_resampler *r, const size_t *lines, size_t n) {
-    if (!r) return MFCC_HIP_ERROR_INVALID_PARAM;
-    std::vector<size_t> list;                           // lines == NULL: every line
-    const int rc = bank_list(r->n, lines, n, list);
-    if (rc) return rc;
-    // the counts travel with every launch's records: a line whose count is 0 reads nothing of its history
-    for (size_t u : list) r->seen[u] = 0;
-    return MFCC_HIP_SUCCESS;
+    return live_reset(r, lines, n, &mfcc_hip_resampler::seen);
 }
 
 int mfcc_hip_resampler_push_dev(mfcc_hip_resampler *r, const void *d_in, const size_t *offsets, void *d_out, size_t cap,
@@ -3966,7 +3951,7 @@ int mfcc_hip_resampler_flush_dev(mfcc_hip_resampler *r, const size_t *lines, siz
     mfcc_hip_handle *h = r->h;
     const mfcc_rs::Geometry &g = r->g;
     std::vector<size_t> list;                           // lines == NULL: every line
-    int rc = bank_list(r->n, lines, n, list);
+    int rc = live_lines(r->n, lines, n, list);
     if (rc) return rc;
     std::vector<size_t> seen(list.size());
     for (size_t i = 0; i < list.size(); ++i) seen[i] = r->seen[list[i]];
@@ -3989,7 +3974,7 @@ int mfcc_hip_resampler_flush_dev(mfcc_hip_resampler *r, const size_t *lines, siz
         }
         if ((rc = rs_stream_launch(r, segs)) || (rc = scratch_release(h))) return rc;
     }
-    for (size_t u : list) r->seen[u] = 0;
+    live_zero(list, {&r->seen});
     return MFCC_HIP_SUCCESS;
 }
 

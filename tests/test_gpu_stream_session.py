@@ -4,6 +4,7 @@ bit for bit, both contracts, both framing modes -- the core's sink/source/reset 
 import numpy as np
 import pytest
 
+from kernel_families import same
 from oracle import mfcc_fixed as mx
 from oracle import mfcc_float as mf
 
@@ -107,3 +108,137 @@ def test_push_with_a_small_buffer_leaves_the_session_untouched(mfcc_amd, wav_pcm
         rc = lib.mfcc_hip_stream_push(s._s, x.ctypes.data, x.size, out.ctypes.data, out.size, C.byref(nf))
         assert rc == -106 and nf.value == 9 and s.pending == 0           # BUFFER_SMALL, nothing consumed
         assert np.array_equal(s.push(x), m.process(x))
+
+
+# ---- what the C entry points answer at their edges (include/mfcc_hip.h: mfcc_hip_stream_*), through ctypes.  The one-shot
+# call is the witness wherever rows come out; 3000 samples of the golden wav: 15 frames at 512 / 170, 450 pending
+
+N_EDGE = 3000
+
+
+def _open(mfcc_amd, fixed, pad_mode="stream", **kw):
+    return mfcc_amd.MFCC(nfft=512, nfilters=32, nceptrums=16 if fixed else 13, pad_mode=pad_mode, **kw)
+
+
+def _one_shot(m, fixed, x):
+    return m.process_fixed(x) if fixed else m.process(x)
+
+
+def _c_push(s, x, n, out, cap, want_nf=True):
+    """mfcc_hip_stream_push with any argument NULL (None); returns (rc, *n_frames_out or None)."""
+    import ctypes as C
+    nf = C.c_size_t(12345)
+    rc = s._lib.mfcc_hip_stream_push(s._s, None if x is None else x.ctypes.data, n, None if out is None else out.ctypes.data,
+                                     cap, C.byref(nf) if want_nf else None)
+    return rc, (int(nf.value) if want_nf else None)
+
+
+def _c_flush(s, out, cap, want_nf=True):
+    import ctypes as C
+    nf = C.c_size_t(12345)
+    rc = s._lib.mfcc_hip_stream_flush(s._s, None if out is None else out.ctypes.data, cap, C.byref(nf) if want_nf else None)
+    return rc, (int(nf.value) if want_nf else None)
+
+
+@pytest.mark.parametrize("fixed", [False, True])
+def test_push_refusals_consume_nothing_and_empty_pushes_succeed(mfcc_amd, wav_pcm, fixed):
+    from mfcc_amd import _lib as L
+    x = np.ascontiguousarray(wav_pcm[:N_EDGE])
+    with _open(mfcc_amd, fixed) as m, m.stream(fixed=fixed) as s:
+        one = _one_shot(m, fixed, x)
+        W = one.shape[1]
+        out = np.empty((16, W), one.dtype)
+        head = s.push(x[:1000])
+        assert head.shape == (3, W) and s.pending == 490
+        # NULL samples with n > 0: INVALID_PARAM, whatever the output buffer is like
+        for o, cap in ((out, out.size), (out, 1), (None, 0), (None, out.size)):
+            assert _c_push(s, None, 2000, o, cap)[0] == L.ERROR_INVALID_PARAM and s.pending == 490
+        assert _c_push(s, None, 2000, None, 0, want_nf=False)[0] == L.ERROR_INVALID_PARAM and s.pending == 490
+        # BUFFER_SMALL: the count is written all the same, a NULL count is accepted, nothing is consumed
+        rest = x[1000:]
+        for o, cap in ((out, 11 * W), (out, 12 * W - 1), (None, out.size)):
+            assert _c_push(s, rest, rest.size, o, cap) == (L.ERROR_BUFFER_SMALL, 12) and s.pending == 490
+            assert _c_push(s, rest, rest.size, o, cap, want_nf=False)[0] == L.ERROR_BUFFER_SMALL and s.pending == 490
+        # n = 0: success with 0 frames, with and without pointers
+        assert _c_push(s, None, 0, None, 0) == (0, 0) and s.pending == 490
+        assert _c_push(s, rest, 0, out, out.size) == (0, 0) and s.pending == 490
+        assert _c_push(s, None, 0, None, 0, want_nf=False)[0] == 0 and s.pending == 490
+        # a push that completes no frame needs no output buffer; one that does may leave the count out
+        assert _c_push(s, rest, 21, None, 0) == (0, 0) and s.pending == 511
+        assert _c_push(s, rest[21:], rest.size - 21, out, 12 * W, want_nf=False)[0] == 0 and s.pending == 450
+        assert same(np.concatenate([head, out[:12], s.flush()]), one)
+
+
+@pytest.mark.parametrize("fixed", [False, True])
+def test_flush_with_a_small_buffer_keeps_the_pending_samples(mfcc_amd, wav_pcm, fixed):
+    from mfcc_amd import _lib as L
+    x = np.ascontiguousarray(wav_pcm[:N_EDGE])
+    with _open(mfcc_amd, fixed) as m, m.stream(fixed=fixed) as s:
+        one = _one_shot(m, fixed, x)
+        W = one.shape[1]
+        assert same(s.push(x), one[:-1]) and s.pending == 450
+        row = np.empty((1, W), one.dtype)
+        for o, cap in ((None, 0), (None, W), (row, W - 1), (row, 0)):
+            assert _c_flush(s, o, cap) == (L.ERROR_BUFFER_SMALL, 1) and s.pending == 450
+            assert _c_flush(s, o, cap, want_nf=False)[0] == L.ERROR_BUFFER_SMALL and s.pending == 450
+        assert _c_flush(s, row, W) == (0, 1) and s.pending == 0
+        assert same(row, one[-1:])
+        # the flush left a reset session: its next flush is the one of a fresh one (below), a NULL count is accepted
+        assert _c_flush(s, row, W, want_nf=False)[0] == 0
+        assert same(row, _one_shot(m, fixed, x[:0]))
+
+
+@pytest.mark.parametrize("fixed", [False, True])
+def test_flush_of_a_fresh_session_is_the_tail_frame_of_no_samples(mfcc_amd, wav_pcm, fixed):
+    with _open(mfcc_amd, fixed) as m:
+        empty = _one_shot(m, fixed, wav_pcm[:0])
+        assert empty.shape[0] == 1
+        with m.stream(fixed=fixed) as s:
+            for _ in range(2):                                           # ... and again: every flush leaves a reset session
+                got = s.flush()
+                assert got.dtype == empty.dtype and same(got, empty) and s.pending == 0
+
+
+@pytest.mark.parametrize("fixed", [False, True])
+def test_notebook_flush_gives_no_row_and_resets(mfcc_amd, wav_pcm, fixed):
+    x = np.ascontiguousarray(wav_pcm[:N_EDGE])
+    with _open(mfcc_amd, fixed, pad_mode="notebook") as m, m.stream(fixed=fixed) as s:
+        one = _one_shot(m, fixed, x)
+        assert len(one) == 15
+        assert _c_flush(s, None, 0) == (0, 0) and s.pending == 0         # fresh: nothing, and no buffer is needed
+        assert len(s.push(x[:700])) == 2 and s.pending == 360
+        assert _c_flush(s, None, 0) == (0, 0) and s.pending == 0
+        assert len(s.push(x[:100])) == 0 and s.pending == 100
+        assert s.flush().shape == (0, one.shape[1]) and s.pending == 0
+        assert same(s.push(x), one) and s.flush().shape[0] == 0   # history and pending samples are gone
+
+
+@pytest.mark.parametrize("fixed", [False, True])
+def test_a_used_session_after_flush_or_reset_equals_a_fresh_one(mfcc_amd, wav_pcm, fixed):
+    x = np.ascontiguousarray(wav_pcm[:N_EDGE])
+    with _open(mfcc_amd, fixed) as m, m.stream(fixed=fixed) as s:
+        one = _one_shot(m, fixed, x)
+        fresh = _run(s, x, 700)
+        assert same(fresh, one)
+        assert same(_run(s, x, 700), one)                      # behind a flush
+        s.reset()
+        assert same(_run(s, x, 171), one)                      # behind a flush and a reset
+        s.push(wav_pcm[5000:5900])
+        s.reset()
+        assert s.pending == 0 and same(_run(s, x, 700), one)   # behind a reset mid-stream
+
+
+@pytest.mark.parametrize("fixed,fmt", [(False, "s16"), (True, "s16"), (False, "alaw")])
+def test_a_session_is_a_bank_of_one(mfcc_amd, wav_pcm, fixed, fmt):
+    import decode_ref as dr
+    x = dr.encode_like(wav_pcm[:N_EDGE], fmt, np.random.default_rng(5))
+    cuts = [0, 1, 171, 512, 513, 513, 1200, 1370, N_EDGE]                # no frame, one, several; an empty chunk
+    with _open(mfcc_amd, fixed, sample_format=fmt) as m, m.stream(fixed=fixed) as s, m.stream_bank(1, fixed=fixed) as bank:
+        for a, b in zip(cuts, cuts[1:]):
+            rows, = bank.push([x[a:b]])
+            got = s.push(x[a:b])
+            assert got.dtype == rows.dtype and same(got, rows), (a, b)
+            assert s.pending == int(bank.pending[0])
+        tail, = bank.flush()
+        assert same(s.flush(), tail) and tail.shape[0] == 1
+        assert s.pending == 0 and int(bank.pending[0]) == 0
