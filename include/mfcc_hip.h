@@ -433,7 +433,8 @@ const char *mfcc_hip_spectrum_kernel_name(const mfcc_hip_handle *h);
  * power each split into two bfloat16 terms and summed in fp32, about 2^-16 relative per band instead of 2^-24 per bin.
  * Where that is not wanted, MFCC_HIP_IMPL_GENERIC keeps the fp32 chain at about a third of the rate.
  *
- * There is no fixed-point form and there are no sessions or banks.  The post-pass direct entries (mfcc_hip_normalize_dev,
+ * There is no fixed-point form.  Live lines take these rows through mfcc_hip_bank_create_filterbank (a stream bank, with
+ * causal CMVN, deltas and PCEN of its own; a bank of one line is the session).  The post-pass direct entries (mfcc_hip_normalize_dev,
  * mfcc_hip_deltas_dev, mfcc_hip_pcen_dev, mfcc_hip_vad_dev) keep their width limit of 64: rows of up to 64 bands may be
  * fed to them by the caller; wider post-passes do not exist.  The parameter block, ABI version 2, n_mel 1..64 and every
  * limit of 64 are unchanged. */
@@ -997,6 +998,38 @@ int    mfcc_hip_bank_create_online(mfcc_hip_handle *h, size_t n_streams, int nor
  * normalize_window, min_window 1, center 0, delta_order, delta_window.                                            */
 int    mfcc_hip_bank_create_online_pcen(mfcc_hip_handle *h, size_t n_streams, const mfcc_hip_pcen *p, int normalize,
                                         int normalize_window, int delta_order, int delta_window, mfcc_hip_bank **out);
+/* ---- filterbank bank: live lines whose rows are the handle's filterbank rows ----------
+ * A float bank whose frame launch is the one of mfcc_hip_fbank_i16_dev: rows of W = n_bands floats, 1 .. 128, of the
+ * matrix the handle carries when the bank is created, in that matrix's scale and with its floor (mfcc_hip_set_fbank).
+ * Framing, window, pre-emphasis, pad mode and sample format are the handle's.  The handle's own n_mel, output kind,
+ * normalization, deltas, PCEN and VAD settings do NOT apply and are not refused, as on every filterbank call.  There is
+ * no fixed-point form.
+ *   p, normalize, normalize_window, delta_order, delta_window
+ *                     exactly those of mfcc_hip_bank_create_online_pcen / mfcc_hip_bank_create_online, with the same
+ *                     validation and the same MFCC_HIP_ERROR_INVALID_PARAM cases; p may be NULL.  With p = NULL,
+ *                     MFCC_HIP_NORMALIZE_NONE and order 0 it is a plain bank: lockstep pushes write straight into the
+ *                     caller's buffer, mixed pushes gather.
+ * Contract: any pushes followed by a flush give, per stream and bit for bit, the rows of mfcc_hip_fbank_i16_dev on the
+ * stream's whole signal with the handle's pad mode (MFCC_HIP_PAD_STREAM: one zero-padded tail row from the flush;
+ * MFCC_HIP_PAD_NOTEBOOK: none), on the generic kernel and on both forms of the fused one -- an element's bits depend on
+ * its power row alone.  With online settings: those rows taken column by column through PCEN, the causal sliding
+ * normalization (window = normalize_window, min_window 1, center 0) and the delta regression of the direct entries
+ * mfcc_hip_pcen_dev, mfcc_hip_normalize_sliding_dev and mfcc_hip_deltas_dev, whose arithmetic is per column and does not
+ * depend on the row width (those entries themselves keep their limit of 64 columns).  Rows are [s | D | DD],
+ * n_bands (1 + delta_order) floats: mfcc_hip_bank_row_width.
+ * Refused before anything is allocated, MFCC_HIP_ERROR_UNSUPPORTED: a handle without a matrix (as the mfcc_hip_fbank_*
+ * calls answer); a handle with an input rate (as every bank answers); p on a matrix whose scale is not
+ * MFCC_HIP_FBANK_LOG2 (PCEN reads log2 energies).
+ * Lifetime: the bank counts as a session of the handle like any bank (MFCC_HIP_ERROR_BUSY of the mfcc_hip_set_* calls,
+ * either destroy order).  While at least one filterbank bank of a handle lives, mfcc_hip_set_fbank on that handle answers
+ * MFCC_HIP_ERROR_BUSY and leaves the matrix untouched: the bank's width and state are the matrix's.  With only other
+ * banks or sessions alive mfcc_hip_set_fbank succeeds as before.
+ * mfcc_hip_bank_push / _push_dev / _flush / _flush_ragged / _reset / _pending / _held / _lag / _row_width / _size /
+ * _destroy take the bank unchanged; mfcc_hip_bank_push_dev stays asynchronous (no synchronize, no device-to-host copy).
+ * Device memory: that of the online banks with W = n_bands. */
+int    mfcc_hip_bank_create_filterbank(mfcc_hip_handle *h, size_t n_streams, const mfcc_hip_pcen *p /* may be NULL */,
+                                  int normalize, int normalize_window, int delta_order, int delta_window,
+                                  mfcc_hip_bank **out);
 /* floats per row: W (1 + delta_order); W for a plain bank (int16 elements for a fixed one); 0 for NULL */
 size_t mfcc_hip_bank_row_width(const mfcc_hip_bank *b);
 /* delta_order * delta_window; 0 for a plain bank or NULL */

@@ -311,6 +311,8 @@ SYMBOLS = {
                                                 C.c_void_p]),
     "mfcc_hip_fbank_i16": (C.c_int, [_H, C.c_void_p, _SZ, _SZ, C.c_void_p, _SZ, _PSZ]),
     "mfcc_hip_fbank_kernel_name": (C.c_char_p, [_H]),
+    # ... and the bank of live lines on those rows (p may be NULL)
+    "mfcc_hip_bank_create_filterbank": (C.c_int, [_H, _SZ, C.POINTER(Pcen), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
     "mfcc_hip_htk_weights": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, _SZ, _PSZ]),
 }
 

@@ -1191,7 +1191,7 @@ class MFCC(_Owner):
         """A streaming session on this handle: feed chunks, get the frames they complete."""
         return MfccStream(self, fixed)
 
-    def stream_bank(self, n_streams, fixed=False, *, normalize=None, normalize_window=None, deltas=0,
+    def stream_bank(self, n_streams, fixed=False, *, filterbank=False, normalize=None, normalize_window=None, deltas=0,
                     delta_window=2, pcen=None) -> "MfccStreamBank":
         """``n_streams`` streaming sessions on this handle that advance together: one launch per push.
 
@@ -1204,9 +1204,17 @@ class MFCC(_Owner):
 
         ``pcen`` (``True`` or a dict, see :meth:`set_pcen`; a raw ``output="logmel"`` handle) runs PCEN on every
         stream's rows before that, the smoother carried from push to push: two floats per stream and band.  The
-        one-shot call it equals then has ``pcen=`` the same parameters."""
-        return MfccStreamBank(self, n_streams, fixed, normalize=normalize, normalize_window=normalize_window,
-                              deltas=deltas, delta_window=delta_window, pcen=pcen)
+        one-shot call it equals then has ``pcen=`` the same parameters.
+
+        ``filterbank=True`` makes the rows those of :meth:`filterbank` under the matrix the handle carries now
+        (``set_filterbank``; ``UNSUPPORTED`` without one): up to 128 bands, ``num_features = num_bands * (1 + deltas)``.
+        Pushes followed by a flush equal ``filterbank`` of the whole signal, bit for bit; ``normalize`` / ``deltas`` /
+        ``pcen`` (a ``"log2"`` matrix) are the bank's own and work column by column as on the narrow banks, while the
+        handle's own output kind, normalization, deltas, PCEN and VAD do not apply.  Float only: with ``fixed=True`` it
+        raises ``ValueError``.  While such a bank lives ``set_filterbank`` raises ``BUSY``.  There is no separate session
+        class: ``stream_bank(1, filterbank=True)`` is the streaming session on filterbank rows."""
+        return MfccStreamBank(self, n_streams, fixed, filterbank=filterbank, normalize=normalize,
+                              normalize_window=normalize_window, deltas=deltas, delta_window=delta_window, pcen=pcen)
 
     # -- the receiver's power gate on fixed-point rows (software/cepstrum.c:93-183; include/mfcc_hip.h) -----
     def _int16_rows_in(self, rows):
@@ -1378,11 +1386,14 @@ class MfccStreamBank(_Owner):
 
     _ptr, _destroy = "_b", "mfcc_hip_bank_destroy"
 
-    def __init__(self, mfcc: MFCC, n_streams, fixed=False, *, normalize=None, normalize_window=None, deltas=0,
-                 delta_window=2, pcen=None):
+    def __init__(self, mfcc: MFCC, n_streams, fixed=False, *, filterbank=False, normalize=None, normalize_window=None,
+                 deltas=0, delta_window=2, pcen=None):
         self._m = mfcc
         self._lib = mfcc._lib
         self.fixed = bool(fixed)
+        self.filterbank = bool(filterbank)
+        if self.filterbank and self.fixed:
+            raise ValueError("a filterbank bank is float only: fixed=True does not go with filterbank=True")
         self.n_streams = int(n_streams)
         if self.n_streams < 1:
             raise ValueError("a bank needs at least one stream")
@@ -1404,7 +1415,10 @@ class MfccStreamBank(_Owner):
         self.normalize, self.normalize_window = (normalize if mode != _lib.NORMALIZE_NONE else None), (window or None)
         self.deltas, self.delta_window = order, dwin
         b = _lib.Handle()
-        if p is not None:
+        if self.filterbank:
+            _lib.check(self._lib.mfcc_hip_bank_create_filterbank(mfcc._h, self.n_streams, None if p is None else C.byref(p), mode,
+                                                            window, order, dwin, C.byref(b)), "bank_create_filterbank")
+        elif p is not None:
             _lib.check(self._lib.mfcc_hip_bank_create_online_pcen(mfcc._h, self.n_streams, C.byref(p), mode, window, order,
                                                                   dwin, C.byref(b)), "bank_create_online_pcen")
         elif self.online:
@@ -1427,7 +1441,7 @@ class MfccStreamBank(_Owner):
 
     @property
     def num_features(self) -> int:
-        """Elements per row: the handle's row width times ``1 + deltas``."""
+        """Elements per row: the handle's row width (a filterbank bank: ``num_bands``) times ``1 + deltas``."""
         return int(self._lib.mfcc_hip_bank_row_width(self._b))
 
     @property

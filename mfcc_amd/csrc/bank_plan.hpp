@@ -41,6 +41,26 @@ struct Rec {
 constexpr int kRecLL = 8;                                  // a record as long longs in the pinned descriptor pool
 static_assert(sizeof(Rec) == kRecLL * sizeof(long long), "record layout");
 
+// The delta kernels' tiles (kernel_stream_bank_online.hpp).  A tile of g emitted rows holds (g + 2L) W static floats,
+// L = order * window, and at order 2 (g + 2 window) W delta floats as well.  Rows of up to kNarrowWidth floats -- every
+// MFCC bank -- have 16 KB of LDS, as kernel_deltas.hpp: g >= 8 for every W <= 64, window <= 8.  The rows of 65 .. 128
+// floats of a filterbank bank have 32 KB: g >= 8 for every W <= 128, order <= 2, window <= 8 (exactly 8 at 128 x 2 x 8),
+// and five workgroups of a CU's 160 KB still run side by side
+constexpr int kLdsFloats = 4096;
+constexpr int kWideLdsFloats = 8192;
+constexpr int kNarrowWidth = 64;
+constexpr int tile_rows_of(int lds_floats, int width, int order, int window) {
+    return order == 1 ? lds_floats / width - 2 * order * window
+                      : (lds_floats / width - 2 * order * window - 2 * window) / 2;
+}
+constexpr int tile_rows(int width, int order, int window) { return tile_rows_of(kLdsFloats, width, order, window); }
+constexpr int wide_tile_rows(int width, int order, int window) { return tile_rows_of(kWideLdsFloats, width, order, window); }
+// ... of a bank whose rows are `width` floats: which kernel runs is decided by the width alone
+constexpr bool wide_rows(size_t width) { return width > size_t(kNarrowWidth); }
+constexpr int delta_tile_rows(int width, int order, int window) {
+    return wide_rows(size_t(width)) ? wide_tile_rows(width, order, window) : tile_rows(width, order, window);
+}
+
 // The runs of the causal CMVN that cover the fresh rows [seen, seen + nf) of a stream: S rows each, counted from frame 0
 inline size_t online_runs(size_t seen, size_t nf, size_t S) { return nf ? (seen + nf - 1) / S - seen / S + 1 : 0; }
 

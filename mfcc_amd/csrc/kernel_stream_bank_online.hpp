@@ -29,26 +29,33 @@
 //   kernel_deltas.hpp (acc = fma(n, a_n - b_n, acc), n ascending, then acc * r32, nothing contracted).
 // online_carry_kernel: one workgroup per stream that got fresh rows, behind the two above in stream order: the last
 //   min(nf, D) fresh raw rows into the ring, the last min(nf, 2L) fresh statics into the tail.
+// online_deltas_wide_kernel: the same lines over kWideLdsFloats of LDS, for the rows of 65 .. 128 floats of a filterbank
+//   bank (mfcc_hip_bank_create_filterbank).  It is the kernel of bank_wide.hip, a code object
+//   of its own (MFCC_ONLINE_WIDE_UNIT: this header then gives that kernel and its launcher only); everywhere else the
+//   header declares the launcher, launch_deltas_wide.
 // Wave64, 256 threads; no atomics; every store is a plain vector store.
+//
+// What each unit sees of this header:
+//   mfcc_hip.hip (MFCC_ONLINE_WIDE_UNIT not defined): Rows .. online_cmvn_kernel, delta_at, the delta kernel's lines as
+//     online_deltas_kernel, online_carry_kernel, and the DECLARATION of launch_deltas_wide;
+//   bank_wide.hip (MFCC_ONLINE_WIDE_UNIT defined): delta_at, the delta kernel's lines as online_deltas_wide_kernel, and
+//     the declaration AND definition of launch_deltas_wide -- nothing of the CMVN or carry kernels, whose host stubs
+//     would otherwise be defined twice in the library.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "bank_plan.hpp"                                   // Rec (one struct for the three passes), kNoEdge
+#include "bank_plan.hpp"                                   // Rec (one struct for the three passes), kNoEdge, the tile sizes
+#ifndef MFCC_ONLINE_WIDE_UNIT
 #include "kernel_normalize_sliding.hpp"
+#endif
 
 namespace mfcc_online {
 
 constexpr int kThreads = 256;
-constexpr int kLdsFloats = 4096;                           // 16 KB of LDS per workgroup, as kernel_deltas.hpp
 
-// emitted rows per tile of the delta kernel: K = 1: (g + 2L) W static floats; K = 2: (g + 2L) W static and
-// (g + 2Nd) W delta floats.  At least 8 for every W <= 64, Nd <= 8
-__host__ __device__ inline int tile_rows(int width, int order, int window) {
-    const int per = kLdsFloats / width, L = order * window;
-    return order == 1 ? per - 2 * L : (per - 2 * L - 2 * window) / 2;
-}
+#ifndef MFCC_ONLINE_WIDE_UNIT
 
 // column c of a stream's raw rows: the ring below `seen`, the fresh rows from there on
 struct Rows {
@@ -153,6 +160,8 @@ __global__ __launch_bounds__(kThreads) void online_cmvn_kernel(const float *__re
     }
 }
 
+#endif  // MFCC_ONLINE_WIDE_UNIT
+
 // the delta of column c of the row at src (rows W floats apart; the rows N above and below are there, already clamped)
 __device__ __forceinline__ float delta_at(const float *src, int W, int N, float r32) {
 #pragma clang fp contract(off)
@@ -161,11 +170,23 @@ __device__ __forceinline__ float delta_at(const float *src, int W, int N, float 
     return acc * r32;
 }
 
-__global__ __launch_bounds__(kThreads) void online_deltas_kernel(const float *__restrict__ tail,
-                                                                  const float *__restrict__ fresh, float *__restrict__ y,
-                                                                  const Rec *__restrict__ rec, long long n_rec, int W, int K,
-                                                                  int N, float r32) {
-    __shared__ float lds[kLdsFloats];
+// The delta kernel: these lines are compiled once per unit -- as online_deltas_kernel over kLdsFloats in the MFCC
+// kernels' unit, as online_deltas_wide_kernel over kWideLdsFloats in bank_wide.hip.  (As a function that two kernels
+// inline -- the tile its own as a template on the size, or handed to it -- the same lines gave the narrow kernel other
+// gfx950 code: instruction order and register numbers.  This way its code is what it was.)  Every record fits its
+// kernel's LDS: bank_plan.hpp, tile_rows / wide_tile_rows
+#ifdef MFCC_ONLINE_WIDE_UNIT
+#define MFCC_ONLINE_DELTAS_KERNEL online_deltas_wide_kernel
+#define MFCC_ONLINE_DELTAS_LDS kWideLdsFloats
+#else
+#define MFCC_ONLINE_DELTAS_KERNEL online_deltas_kernel
+#define MFCC_ONLINE_DELTAS_LDS kLdsFloats
+#endif
+__global__ __launch_bounds__(kThreads) void MFCC_ONLINE_DELTAS_KERNEL(const float *__restrict__ tail,
+                                                                       const float *__restrict__ fresh, float *__restrict__ y,
+                                                                       const Rec *__restrict__ rec, long long n_rec, int W,
+                                                                       int K, int N, float r32) {
+    __shared__ float lds[MFCC_ONLINE_DELTAS_LDS];
     const int L = K * N, L2 = 2 * L, WO = W * (1 + K), t = threadIdx.x;
     for (long long b = blockIdx.x; b < n_rec; b += gridDim.x) {
         const Rec q = rec[b];
@@ -211,6 +232,11 @@ __global__ __launch_bounds__(kThreads) void online_deltas_kernel(const float *__
     }
 }
 
+#undef MFCC_ONLINE_DELTAS_KERNEL
+#undef MFCC_ONLINE_DELTAS_LDS
+
+#ifndef MFCC_ONLINE_WIDE_UNIT
+
 // ring / tail may be null (no normalization / no deltas); stat = the fresh static rows (raw without normalization)
 __global__ __launch_bounds__(kThreads) void online_carry_kernel(float *ring, float *tail, const float *__restrict__ raw,
                                                                  const float *__restrict__ stat, const Rec *__restrict__ rec,
@@ -237,5 +263,21 @@ __global__ __launch_bounds__(kThreads) void online_carry_kernel(float *ring, flo
         }
     }
 }
+
+#endif  // MFCC_ONLINE_WIDE_UNIT
+
+// online_deltas_wide_kernel over `blocks` workgroups on `stream`; the arguments are online_deltas_kernel's
+void launch_deltas_wide(const float *tail, const float *fresh, float *y, const Rec *rec, long long n_rec, int W, int K, int N,
+                        float r32, unsigned blocks, hipStream_t stream);
+
+#ifdef MFCC_ONLINE_WIDE_UNIT
+
+void launch_deltas_wide(const float *tail, const float *fresh, float *y, const Rec *rec, long long n_rec, int W, int K, int N,
+                        float r32, unsigned blocks, hipStream_t stream) {
+    hipLaunchKernelGGL(online_deltas_wide_kernel, dim3(blocks), dim3(kThreads), 0, stream, tail, fresh, y, rec, n_rec, W, K, N,
+                       r32);
+}
+
+#endif  // MFCC_ONLINE_WIDE_UNIT
 
 }  // namespace mfcc_online

@@ -333,6 +333,9 @@ struct mfcc_hip_handle {
     // the handle; the last mfcc_hip_stream_destroy then tears it down (include/mfcc_hip.h: lifetime)
     int n_sessions = 0;
     bool destroy_pending = false;
+    // ... and the filterbank banks among them (mfcc_hip_bank_create_filterbank): their width and state are the matrix's,
+    // so mfcc_hip_set_fbank answers BUSY while one lives
+    int n_fbank_banks = 0;
     // the passes behind the float kernels: their settings, written by the mfcc_hip_set_* functions and nowhere else
     Post post;
     // per-segment normalization: the stats / coefficient / tile-table scratch and, for host-buffer calls whose chunks cut
@@ -2367,6 +2370,7 @@ const char *mfcc_hip_spectrum_kernel_name(const mfcc_hip_handle *h) { return h ?
 // 4.19): the spectrum entries' routes on a Kind::kFbank call
 int mfcc_hip_set_fbank(mfcc_hip_handle *h, const mfcc_hip_fbank *p, const float *weights) {
     if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (h->n_fbank_banks > 0) return MFCC_HIP_ERROR_BUSY;      // a filterbank bank's width and state are this matrix's
     const int bins = mfcc_spec::bins(h->r.nfft);
     mfcc_fbank::Table t;
     mfcc_fbank::Sets sets;
@@ -3148,6 +3152,7 @@ extern "C" {
 
 struct mfcc_hip_bank {
     mfcc_hip_handle *h = nullptr;
+    Kind kind = Kind::kFeatures;         // what its frame launch computes: the handle's own rows, or its filterbank rows
     bool fixed = false;
     size_t n = 0;                        // streams
     mfcc_bank::Settings s{};             // what the plans of a push, flush or reset read (bank_plan.hpp)
@@ -3167,6 +3172,9 @@ struct mfcc_hip_bank {
     mfcc_pcen::Prm pcen_prm{};
     float *d_pcen = nullptr;
     std::vector<void *> owned() const { return {d_state, d_ring, d_tail, d_pcen, st_in.p, st_out.p}; }
+    ~mfcc_hip_bank() {                   // in front of the handle's release (live_destroy)
+        if (kind == Kind::kFbank) --h->n_fbank_banks;
+    }
 };
 
 namespace {
@@ -3216,7 +3224,11 @@ void bank_passes(mfcc_hip_bank *b, const mfcc_bank::Layout &l, void *y) {
                            (long long)l.cmvn.n, W, b->window, b->depth, b->norm);
     }
     const float *stat = s.norm ? d_stat : d_raw;
-    if (l.delta.n)
+    if (l.delta.n && mfcc_online::wide_rows(s.W))          // s.g is the wide tile's (bank_create)
+        mfcc_online::launch_deltas_wide(b->d_tail, stat, out, desc_table<mfcc_online::Rec>(h, l.delta), (long long)l.delta.n, W,
+                                        s.order, b->dwin, mfcc_delta::delta_scale(b->dwin),
+                                        (unsigned)std::min(l.delta.n, cap), h->stream);
+    else if (l.delta.n)
         hipLaunchKernelGGL(mfcc_online::online_deltas_kernel, dim3((unsigned)std::min(l.delta.n, cap)),
                            dim3(mfcc_online::kThreads), 0, h->stream, b->d_tail, stat, out,
                            desc_table<mfcc_online::Rec>(h, l.delta), (long long)l.delta.n, W, s.order, b->dwin,
@@ -3266,7 +3278,7 @@ int bank_advance(mfcc_hip_bank *b, const int16_t *d_samples, size_t shift, const
                        (long long)l.stride, h->r.frame_len, h->r.hop);
     if (l.n_active) {
         void *d_rows = l.direct ? d_out : static_cast<char *>(h->d_out.p) + l.raw_off;
-        if ((rc = launch(h, call_of(h, Kind::kFeatures, b->fixed), d_w, l.stride - 1, l.stride, l.n_active, /*halo=*/1, d_rows, nullptr, l.nfmax))) return rc;
+        if ((rc = launch(h, call_of(h, b->kind, b->fixed), d_w, l.stride - 1, l.stride, l.n_active, /*halo=*/1, d_rows, nullptr, l.nfmax))) return rc;
         bank_passes(b, l, d_out);
     }
     HIP_TRY(h, hipGetLastError());
@@ -3304,7 +3316,7 @@ int bank_end(mfcc_hip_bank *b, const std::vector<size_t> &list, bool give, void 
                        desc_table<mfcc_bank::Rec>(h, l.bank), (long long)l.n_rec, (long long)l.stride, h->r.frame_len);
     if (emit) {
         void *d_rows = l.direct ? b->st_out.p : static_cast<char *>(h->d_out.p) + l.raw_off;
-        if ((rc = launch(h, call_of(h, Kind::kFeatures, b->fixed), d_w, l.stride - 1, l.stride, l.n_active, /*halo=*/1, d_rows, nullptr, 1))) return rc;
+        if ((rc = launch(h, call_of(h, b->kind, b->fixed), d_w, l.stride - 1, l.stride, l.n_active, /*halo=*/1, d_rows, nullptr, 1))) return rc;
     }
     bank_passes(b, l, b->st_out.p);
     if (result_bytes) HIP_TRY(h, hipMemcpyAsync(out, b->st_out.p, result_bytes, hipMemcpyDeviceToHost, h->stream));
@@ -3316,12 +3328,15 @@ int bank_end(mfcc_hip_bank *b, const std::vector<size_t> &list, bool give, void 
     return MFCC_HIP_SUCCESS;
 }
 
-// a bank on a checked handle; norm / order as validated by the caller (NONE and 0: a plain bank)
-int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int window, int order, int dwin,
+// a bank on a checked handle whose frame launch is c; norm / order as validated by the caller (NONE and 0: a plain bank)
+int bank_create(mfcc_hip_handle *h, const Call &c, size_t n_streams, int norm, int window, int order, int dwin,
                 mfcc_hip_bank **out, const mfcc_pcen::Prm *pcen = nullptr) {
     mfcc_hip_bank *b = live_new<mfcc_hip_bank>(h, n_streams);
     if (!b) return MFCC_HIP_ERROR_NO_MEM;
-    b->fixed = fixed != 0;
+    const bool fixed = c.fixed;
+    b->kind = c.kind;
+    if (c.kind == Kind::kFbank) ++h->n_fbank_banks;
+    b->fixed = fixed;
     b->pending.assign(n_streams, 0);
     b->after.assign(n_streams, 0);
     b->seen.assign(n_streams, 0);
@@ -3329,7 +3344,7 @@ int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int w
     b->held_after.assign(n_streams, 0);
     b->raw_fo.assign(n_streams + 1, 0);
     mfcc_bank::Settings &s = b->s;
-    const size_t W = row_width(h->r);
+    const size_t W = c.width;
     s.flen = size_t(h->r.frame_len);
     s.hop = size_t(h->r.hop);
     s.W = W;
@@ -3346,7 +3361,7 @@ int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int w
     if (order) {
         s.order = order;
         s.L = size_t(order * dwin);
-        s.g = size_t(mfcc_online::tile_rows(int(W), order, dwin));
+        s.g = size_t(mfcc_online::delta_tile_rows(int(W), order, dwin));
         b->dwin = dwin;
     }
     DeviceGuard guard(h->device);
@@ -3368,15 +3383,18 @@ int bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, int norm, int w
     return live_created(b, e, out);
 }
 
-// The checks the three create entries share, then the bank.  The bank's settings are its own: the handle must be a raw
+// The checks the create entries share, then the bank.  The bank's settings are its own: the handle must be a raw
 // one (what mfcc_hip_stream_create refuses: per-call statistics, lookahead and whole-segment thresholds of a stream)
-// that can run the path asked for; an online bank (float) takes log-mel rows where it has PCEN
-int bank_create_checked(mfcc_hip_handle *h, int fixed, bool online, size_t n_streams, const mfcc_hip_pcen *p, int normalize,
-                        int normalize_window, int delta_order, int delta_window, mfcc_hip_bank **out) {
+// that can run the path asked for; an online bank (float) takes log-mel rows where it has PCEN.  A filterbank bank
+// (kind kFbank, float) wants the handle's matrix instead -- in log2 where it has PCEN, which reads log2 energies --
+// and the handle's own post settings do not apply to it, as on every filterbank call
+int bank_create_checked(mfcc_hip_handle *h, Kind kind, int fixed, bool online, size_t n_streams, const mfcc_hip_pcen *p,
+                        int normalize, int normalize_window, int delta_order, int delta_window, mfcc_hip_bank **out) {
     if (live_check(h, n_streams, out) || (p && !pcen_ok(p))) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    const bool fb = kind == Kind::kFbank;
+    if (fb ? !h->fb_dev : has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (rated(h)) return MFCC_HIP_ERROR_UNSUPPORTED;           // a line's rate conversion keeps state between pushes
-    if (p && !is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (p && !(fb ? h->fb_scale == MFCC_HIP_FBANK_LOG2 : is_logmel(h->r))) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (online && h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (normalize != MFCC_HIP_NORMALIZE_NONE && normalize != MFCC_HIP_NORMALIZE_MEAN && normalize != MFCC_HIP_NORMALIZE_MEAN_VAR)
@@ -3387,7 +3405,8 @@ int bank_create_checked(mfcc_hip_handle *h, int fixed, bool online, size_t n_str
         return MFCC_HIP_ERROR_INVALID_PARAM;
     mfcc_pcen::Prm prm{};
     if (p) prm = pcen_prm(*p);
-    return bank_create(h, fixed, n_streams, normalize, normalize_window, delta_order, delta_window, out, p ? &prm : nullptr);
+    return bank_create(h, call_of(h, kind, fixed != 0), n_streams, normalize, normalize_window, delta_order, delta_window, out,
+                       p ? &prm : nullptr);
 }
 
 }  // namespace
@@ -3395,18 +3414,27 @@ int bank_create_checked(mfcc_hip_handle *h, int fixed, bool online, size_t n_str
 extern "C" {
 
 int mfcc_hip_bank_create(mfcc_hip_handle *h, int fixed, size_t n_streams, mfcc_hip_bank **out) {
-    return bank_create_checked(h, fixed, false, n_streams, nullptr, MFCC_HIP_NORMALIZE_NONE, 0, 0, 1, out);
+    return bank_create_checked(h, Kind::kFeatures, fixed, false, n_streams, nullptr, MFCC_HIP_NORMALIZE_NONE, 0, 0, 1, out);
 }
 
 int mfcc_hip_bank_create_online(mfcc_hip_handle *h, size_t n_streams, int normalize, int normalize_window, int delta_order,
                                 int delta_window, mfcc_hip_bank **out) {
-    return bank_create_checked(h, 0, true, n_streams, nullptr, normalize, normalize_window, delta_order, delta_window, out);
+    return bank_create_checked(h, Kind::kFeatures, 0, true, n_streams, nullptr, normalize, normalize_window, delta_order,
+                               delta_window, out);
 }
 
 // p == NULL: no PCEN, mfcc_hip_bank_create_online
 int mfcc_hip_bank_create_online_pcen(mfcc_hip_handle *h, size_t n_streams, const mfcc_hip_pcen *p, int normalize,
                                      int normalize_window, int delta_order, int delta_window, mfcc_hip_bank **out) {
-    return bank_create_checked(h, 0, true, n_streams, p, normalize, normalize_window, delta_order, delta_window, out);
+    return bank_create_checked(h, Kind::kFeatures, 0, true, n_streams, p, normalize, normalize_window, delta_order, delta_window,
+                               out);
+}
+
+// the rows are the handle's filterbank rows; p == NULL: no PCEN
+int mfcc_hip_bank_create_filterbank(mfcc_hip_handle *h, size_t n_streams, const mfcc_hip_pcen *p, int normalize, int normalize_window,
+                               int delta_order, int delta_window, mfcc_hip_bank **out) {
+    return bank_create_checked(h, Kind::kFbank, 0, true, n_streams, p, normalize, normalize_window, delta_order, delta_window,
+                               out);
 }
 
 size_t mfcc_hip_bank_row_width(const mfcc_hip_bank *b) { return b ? b->s.out_width() : 0; }
