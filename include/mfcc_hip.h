@@ -831,6 +831,64 @@ int  mfcc_hip_resampler_push_dev(mfcc_hip_resampler *r, const void *d_in, const 
 int  mfcc_hip_resampler_flush_dev(mfcc_hip_resampler *r, const size_t *lines, size_t n, void *d_out, size_t cap,
                                   size_t *out_offsets);
 
+/* ---- centring ---------------------------------------------------------------------------
+ * The framing of librosa.stft / torch.stft / torchaudio / Whisper (center=True): frame t is centred on sample t hop,
+ * the signal's edges are reflected (or zero-padded), and n samples give 1 + n div hop frames.
+ * L: the handle's frame length (nfft, or frame_length of a framed handle), hop: its hop, n: the samples of one channel
+ * or utterance at the handle's own rate (after decode and resample).  All divisions are integer divisions.
+ *     PL    = nfft / 2 - (nfft - L) / 2                         (= ceil(L / 2); torch.stft's placement of a short window)
+ *     F(n)  = 0               if n <= PL (REFLECT)  or  n == 0 (ZEROS)
+ *           = 1 + n / hop     otherwise
+ *     N'(n) = (F - 1) hop + L                                   (0 when F = 0)
+ *     p[i], 0 <= i < N':   j = i - PL
+ *           REFLECT:  j < 0 -> -j;  j >= n -> 2 (n - 1) - j     (the edge sample is not repeated: numpy / torch "reflect")
+ *           ZEROS:    0 where j < 0 or j >= n
+ *           else      x[j]
+ * With n > PL one reflection suffices on both sides.  The rows of a centred handle are the rows the same handle gives
+ * uncentred (MFCC_HIP_PAD_NOTEBOOK) on p, bit for bit, F of them.  Pre-emphasis runs over p with p[-1] = 0. */
+enum mfcc_hip_center { MFCC_HIP_CENTER_OFF = 0, MFCC_HIP_CENTER_REFLECT = 1, MFCC_HIP_CENTER_ZEROS = 2 };
+/* The geometry: *n_frames = F(n), *left = PL, *padded = N'(n) (any may be NULL).  frame_length as in
+ * mfcc_hip_create_framed (0: nfft); mode REFLECT or ZEROS.  Bad params, frame length or mode:
+ * MFCC_HIP_ERROR_INVALID_PARAM.  Host only, no GPU. */
+int  mfcc_hip_center_geometry(const mfcc_hip_params *p, int frame_length, int mode, size_t n, size_t *n_frames, size_t *left,
+                              size_t *padded);
+/* The rule on int16: the n samples at `in` -> out[N'].  *n_out (may be NULL) = N', also on MFCC_HIP_ERROR_BUFFER_SMALL
+ * (cap < N', nothing written).  N' = 0 looks at no pointer; else a NULL in or out: MFCC_HIP_ERROR_INVALID_PARAM.  Host
+ * only, no GPU, no handle. */
+int  mfcc_hip_center_host(const mfcc_hip_params *p, int frame_length, int mode, const int16_t *in, size_t n, int16_t *out,
+                          size_t cap, size_t *n_out);
+/* The kernel's direct entry on one row, with the handle's L and hop: n samples in `format` (any of enum
+ * mfcc_hip_sample_format; the decode rule is applied while padding) at d_in, aligned to the format's sample size -> N'
+ * int16 at d_out, 2-byte aligned at any int16 offset.  *n_out (may be NULL) = N', also on MFCC_HIP_ERROR_BUFFER_SMALL
+ * (cap < N', nothing enqueued).  A NULL or misaligned pointer that is needed, an overlap of the two byte ranges, an
+ * unknown format, a mode other than REFLECT or ZEROS: MFCC_HIP_ERROR_INVALID_PARAM.  Asynchronous on the handle's stream;
+ * N' = 0 is a no-op.  The handle's own mode, format and rate are not read. */
+int  mfcc_hip_center_dev(mfcc_hip_handle *h, int mode, int format, const void *d_in, size_t n, void *d_out, size_t cap,
+                         size_t *n_out);
+/* The handle's mode, applied to every call enqueued after it: every one-shot float entry point (mfcc_hip_process_i16,
+ * _i16_dev, _ragged_i16, _ragged_i16_dev, mfcc_hip_spectrum_*, mfcc_hip_fbank_*, mfcc_hip_time_dev, mfcc_hip_convert_wav(s)
+ * in float) returns, bit for bit, what the same handle with MFCC_HIP_CENTER_OFF returns on p of every channel or
+ * utterance.  The order is decode -> resample -> centre -> route: a handle with a sample format and no input rate runs
+ * ONE pass in front (decode and centre together), a plain int16 handle one, a handle with an input rate three.  The
+ * padded samples go to a scratch area of the handle that grows on demand and is never shrunk (2 bytes per padded sample,
+ * a dense call of several channels rounds every channel up to 8 samples; MFCC_HIP_ERROR_NO_MEM if it cannot be had).
+ * Sample counts, strides and `offsets` keep counting the CALLER's samples; frame counts and frame_offsets count F.
+ *   - ragged calls: an utterance with F = 0 (REFLECT: up to PL samples) gives no rows and the call succeeds;
+ *   - normalization, sliding normalization, deltas, PCEN and VAD run behind the kernels on the F rows as they do on any;
+ *   - the host-buffer entry points take the unchunked route: one copy in, the device route, one copy back
+ *     (MFCC_HIP_ERROR_NO_MEM where that does not fit).
+ * MFCC_HIP_CENTER_OFF: the state after mfcc_hip_create -- no pass is enqueued, every entry point is the code it was.
+ * MFCC_HIP_ERROR_UNSUPPORTED, before anything is read or allocated, on a centred handle: dense calls with halo = 1 (a
+ * shard of a longer stream has no edges), every fixed-point entry point (the RTL's framing is its contract),
+ * mfcc_hip_stream_create, every mfcc_hip_bank_create* and mfcc_hip_resampler_create (a centred line must hold back its
+ * first PL + 1 samples and flushes several frames).  mfcc_hip_set_center itself: MFCC_HIP_ERROR_UNSUPPORTED for a mode
+ * other than OFF on a MFCC_HIP_PAD_STREAM handle; MFCC_HIP_ERROR_BUSY while sessions, banks or gates live; another value
+ * or a NULL handle: MFCC_HIP_ERROR_INVALID_PARAM.  A refused call leaves the handle as it was.  The parameter block and
+ * the ABI version are unchanged. */
+int  mfcc_hip_set_center(mfcc_hip_handle *h, int mode);
+/* the handle's mode, MFCC_HIP_CENTER_OFF for NULL */
+int  mfcc_hip_center(const mfcc_hip_handle *h);
+
 /* name of the kernel symbol process_*_dev launches for this handle (to match rocprofv3 rows).  A log-mel handle runs
  * the log-mel instantiation of the kernel named (the default form: MFCC_HIP_FUSED512 / MFCC_HIP_FUSED1024 do not
  * apply to it) */

@@ -62,6 +62,11 @@ SAMPLE_I2S32 = 4
 SAMPLE_S32 = 5
 SAMPLE_F32 = 6
 
+# enum mfcc_hip_center
+CENTER_OFF = 0
+CENTER_REFLECT = 1
+CENTER_ZEROS = 2
+
 TABLE_WINDOW_F32 = 0
 TABLE_MEL_POINTS_I32 = 1
 TABLE_MEL_DENSE_F32 = 2
@@ -288,6 +293,12 @@ SYMBOLS = {
     "mfcc_hip_resample_dev": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, _SZ, C.c_void_p, _SZ]),
     "mfcc_hip_set_input_rate": (C.c_int, [_H, C.c_int]),
     "mfcc_hip_input_rate": (C.c_int, [_H]),
+    "mfcc_hip_center_geometry": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
+                                           C.POINTER(_SZ)]),
+    "mfcc_hip_center_host": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_void_p, _SZ, C.c_void_p, _SZ, C.POINTER(_SZ)]),
+    "mfcc_hip_center_dev": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, _SZ, C.c_void_p, _SZ, C.POINTER(_SZ)]),
+    "mfcc_hip_set_center": (C.c_int, [_H, C.c_int]),
+    "mfcc_hip_center": (C.c_int, [_H]),
     # live lines: the streaming resampler
     "mfcc_hip_resampler_create": (C.c_int, [_H, _SZ, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
     "mfcc_hip_resampler_destroy": (None, [_H]),

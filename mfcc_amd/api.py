@@ -327,12 +327,35 @@ def _mel_bank(mel, fmin, fmax, samplerate, nfilters):
     return mel, fmin, top, bank
 
 
-def num_frames(n_samples, win_length=None, **kw) -> int:
+_CENTER = {None: _lib.CENTER_OFF, False: _lib.CENTER_OFF, "off": _lib.CENTER_OFF, True: _lib.CENTER_REFLECT,
+           "reflect": _lib.CENTER_REFLECT, "zeros": _lib.CENTER_ZEROS}
+_CENTER_NAMES = {_lib.CENTER_OFF: None, _lib.CENTER_REFLECT: "reflect", _lib.CENTER_ZEROS: "zeros"}
+
+
+def center_mode(center) -> int:
+    """``None`` / ``False`` / ``True`` / ``"reflect"`` / ``"zeros"`` -> ``enum mfcc_hip_center``, or ValueError."""
+    if isinstance(center, (bool, str, type(None))) and center in _CENTER:
+        return _CENTER[center]
+    raise ValueError("center must be None, False, True, 'reflect' or 'zeros', not %r" % (center,))
+
+
+def center_geometry(n_samples, mode, params, win_length) -> tuple:
+    """``(frames, left pad, padded samples)`` of ``n_samples`` under centring (include/mfcc_hip.h; host only)."""
+    f, left, padded = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    _lib.check(_lib.load().mfcc_hip_center_geometry(C.byref(params), int(win_length), center_mode(mode), int(n_samples),
+                                                    C.byref(f), C.byref(left), C.byref(padded)), "center_geometry")
+    return int(f.value), int(left.value), int(padded.value)
+
+
+def num_frames(n_samples, win_length=None, center=None, **kw) -> int:
     """Frames a stream of ``n_samples`` yields (host-only; `nframes`, software/main.c:95); ``win_length``: the frame
-    length of a framed handle (``MFCC(win_length=...)``), ``None`` = ``nfft``."""
+    length of a framed handle (``MFCC(win_length=...)``), ``None`` = ``nfft``; ``center``: as for :class:`MFCC`
+    (``1 + n_samples // hop`` frames, none for a signal too short to reflect)."""
     lib = _lib.load()
     L = _win_length(win_length, kw.get("nfft", 512), kw.get("hop"))
     p = make_params(**kw)
+    if center_mode(center) != _lib.CENTER_OFF:
+        return center_geometry(n_samples, center, p, L)[0]
     out = C.c_size_t(0)
     _lib.check(lib.mfcc_hip_num_frames_framed(C.byref(p), L, int(n_samples), C.byref(out)), "num_frames")
     return int(out.value)
@@ -600,6 +623,16 @@ class MFCC(_Owner):
     :meth:`stream_bank` raise ``UNSUPPORTED`` on such a handle (live lines go through :meth:`resampler`); ``convert*``
     expect WAV files of that rate.
 
+    ``center`` (``None`` / ``False``: off; ``True`` / ``"reflect"``; ``"zeros"``) is the framing of ``librosa.stft``,
+    ``torch.stft``, ``torchaudio.transforms.MelSpectrogram`` and Whisper's log-mel (``center=True``): frame ``t`` is
+    centred on sample ``t * hop``, the edges of every channel / utterance are reflected (or zero-padded) and ``n``
+    samples give ``1 + n // hop`` frames.  The padding is done on the device, behind decode and resample and in front of
+    the kernels (include/mfcc_hip.h has the rule, :func:`center_pad` applies it alone), and every one-shot float method
+    returns, bit for bit, what the handle without it returns on the padded samples.  A signal of at most
+    ``ceil(win_length / 2)`` samples cannot be reflected and gives no frames.  :meth:`stream`, :meth:`stream_bank`,
+    :meth:`resampler`, ``process_fixed`` and ``halo=1`` raise ``UNSUPPORTED`` on such a handle, and so does
+    ``pad_mode="stream"`` with ``center``.
+
     ``window`` (``"hamming"``, ``"hann"``, ``"povey"``, ``"blackman"``, ``"rectangular"``), ``window_periodic`` and
     ``preemph`` are the handle's front: the window function over the frame, in its periodic (``True``: denominator
     ``win_length``) or symmetric (``win_length - 1``) form, and the pre-emphasis ``y[i] = x[i] - preemph x[i-1]``.
@@ -616,6 +649,7 @@ class MFCC(_Owner):
     vad = None
     sample_format = "s16"
     input_rate = None
+    center = None
     _ptr, _destroy = "_h", "mfcc_hip_destroy"
 
     def _sample_np(self):
@@ -636,9 +670,10 @@ class MFCC(_Owner):
                  normalize_center=True, vad=None, vad_column=0, vad_energy_threshold=5.0, vad_energy_mean_scale=0.5,
                  vad_frames_context=0, vad_proportion_threshold=0.6, win_length=None, mel="notebook", fmin=0.0,
                  fmax=None, pcen=None, sample_format="s16", input_rate=None, window="hamming", window_periodic=True,
-                 preemph=31 / 32):
+                 preemph=31 / 32, center=None):
         if width != 16:
             raise ValueError("only width=16 (int16 PCM) is supported, like every reference target")
+        center_mode(center)
         fmt_name, fmt_code, _ = _sample_args(sample_format)
         _pcen_args(pcen, samplerate, hop or int(nfft) // 3)
         self.win_length = _win_length(win_length, nfft, hop)
@@ -677,6 +712,8 @@ class MFCC(_Owner):
             self.set_sample_format(fmt_name)
         if input_rate is not None:
             self.set_input_rate(input_rate)
+        if center_mode(center) != _lib.CENTER_OFF:
+            self.set_center(center)
         self.pcen = None
         if pcen is not None and pcen is not False:
             self.set_pcen(pcen)
@@ -727,6 +764,13 @@ class MFCC(_Owner):
             self._own_rate()
         _lib.check(self._lib.mfcc_hip_set_input_rate(self._h, rate), "set_input_rate")
         self.input_rate = int(self._lib.mfcc_hip_input_rate(self._h)) or None
+
+    def set_center(self, center):
+        """The framing of every one-shot float call after this one: ``None`` / ``False`` (frame ``t`` starts at sample
+        ``t * hop``), ``True`` / ``"reflect"`` or ``"zeros"`` (frame ``t`` is centred on it, the edges padded);
+        ``BUSY`` while sessions, banks or gates of this handle live, ``UNSUPPORTED`` on a ``pad_mode="stream"`` handle."""
+        _lib.check(self._lib.mfcc_hip_set_center(self._h, center_mode(center)), "set_center")
+        self.center = _CENTER_NAMES[int(self._lib.mfcc_hip_center(self._h))]
 
     def set_vad(self, mode, column=0, energy_threshold=5.0, energy_mean_scale=0.5, frames_context=0,
                 proportion_threshold=0.6):
@@ -901,9 +945,12 @@ class MFCC(_Owner):
         return self.nceptrums if fixed else self.num_features
 
     def num_frames(self, n_samples) -> int:
-        """Frames of ``n_samples`` samples of one channel or utterance (at ``input_rate`` where one is set)."""
+        """Frames of ``n_samples`` samples of one channel or utterance (at ``input_rate`` where one is set; centred
+        where ``center`` is)."""
         if self.input_rate:
             n_samples = resample_count(n_samples, self.input_rate, int(self.samplerate))
+        if self.center:
+            return center_geometry(n_samples, self.center, self._params, self.win_length)[0]
         out = C.c_size_t(0)
         _lib.check(self._lib.mfcc_hip_num_frames_framed(C.byref(self._params), self.win_length, int(n_samples),
                                                         C.byref(out)))
@@ -1787,6 +1834,38 @@ def resample(x, in_rate, out_rate, mfcc=None):
     mfcc._check_device(x)
     out = torch.empty(resample_count(x.numel(), i, o), device=x.device, dtype=torch.int16)
     mfcc._call(x.device, "resample_dev", mfcc._h, i, o, ptr(x), x.numel(), ptr(out), out.numel())
+    return out
+
+
+def center_pad(x, mode="reflect", nfft=512, hop=None, win_length=None, mfcc=None):
+    """The padded signal a ``center=mode`` handle frames (include/mfcc_hip.h, "centring"): ``ceil(L / 2)`` samples in
+    front and up to the end of frame ``n // hop`` behind, reflected (``"reflect"`` / ``True``) or zero (``"zeros"``);
+    empty where the signal gives no frame.  A 1-D int16 NumPy array goes through ``mfcc_hip_center_host`` (no GPU needed)
+    with ``nfft``, ``hop`` (``None``: ``nfft // 3``) and ``win_length``; a 1-D CUDA tensor through
+    ``mfcc_hip_center_dev`` on ``mfcc``, asynchronous on the current torch stream, with that handle's framing and in
+    that handle's ``sample_format`` (decoded while it is padded): int16 comes back on both routes."""
+    code = center_mode(mode)
+    if code == _lib.CENTER_OFF:
+        raise ValueError("mode must be True, 'reflect' or 'zeros'")
+    lib = _lib.load()
+    if not _is_torch(x):
+        x = _host_samples(x, "s16", "x", ndim=1)
+        L = _win_length(win_length, nfft, hop)
+        p = make_params(nfft=nfft, hop=hop)
+        out = np.empty(center_geometry(x.size, mode, p, L)[2], dtype=np.int16)
+        _lib.check(lib.mfcc_hip_center_host(C.byref(p), L, code, ptr(x), x.size, ptr(out), out.size, None), "center_host")
+        return out
+    import torch
+    if mfcc is None:
+        raise ValueError("center_pad of a device tensor needs mfcc=: the handle whose framing and device it uses")
+    if not mfcc._samples_dev_ok(x) or x.dim() != 1:
+        raise TypeError("x must be a 1-D %s tensor" % mfcc._dev_what())
+    x = x.contiguous()
+    mfcc._check_device(x)
+    np_ = center_geometry(x.numel(), mode, mfcc._params, mfcc.win_length)[2]
+    out = torch.empty(np_, device=x.device, dtype=torch.int16)
+    mfcc._call(x.device, "center_dev", mfcc._h, code, _sample_args(mfcc.sample_format)[1], ptr(x), x.numel(), ptr(out),
+               out.numel(), None)
     return out
 
 

@@ -39,6 +39,7 @@
 #include "kernel_gate.hpp"
 #include "kernel_decode.hpp"
 #include "kernel_resample.hpp"
+#include "kernel_center.hpp"
 #include "kernel_spectrum.hpp"
 #include "kernel_fbank.hpp"
 #include "tables.hpp"
@@ -80,11 +81,11 @@ struct Post {
 };
 const Post kNoPost{};
 
-// What the sample pointer in hand holds: the format and the rate (0: the handle's own).  It travels with the pointer as
-// far as the input stage of its route (dense_input, ragged_input); behind that stage every pointer is int16 at the handle's
-// own rate
+// What the sample pointer in hand holds: the format, the rate (0: the handle's own) and whether the signal is still to be
+// centred (enum mfcc_hip_center).  It travels with the pointer as far as the input stage of its route (dense_input,
+// ragged_input); behind that stage every pointer is int16 at the handle's own rate, padded where it had to be
 struct Samples {
-    int fmt, rate;
+    int fmt, rate, center;
 };
 
 // What a call computes.  Every entry point builds one (call_of) and passes it down; the routes read it, never the handle's
@@ -363,6 +364,10 @@ struct mfcc_hip_handle {
     mfcc_rs::Geometry rs_geom;
     DevBuf d_rs_tab, d_rs;
     int input_rate = 0;
+    // centring (mfcc_hip_set_center): the mode every one-shot float call frames by, and the padded int16 samples of a call
+    // (d_ctr; behind them the records of a ragged one)
+    int center = MFCC_HIP_CENTER_OFF;
+    DevBuf d_ctr;
 };
 
 namespace {
@@ -536,7 +541,17 @@ inline size_t own_rate_len(const mfcc_hip_handle *h, size_t n) {
 }
 
 // what a sample pointer handed to an entry point holds: the handle's format, at its input rate
-inline Samples samples_of(const mfcc_hip_handle *h) { return Samples{h->sample_fmt, h->input_rate}; }
+inline Samples samples_of(const mfcc_hip_handle *h) { return Samples{h->sample_fmt, h->input_rate, h->center}; }
+
+// ---- centring (include/mfcc_hip.h: "centring"; center_plan.hpp, kernel_center.hpp)
+inline bool centred(Samples in) { return in.center != MFCC_HIP_CENTER_OFF; }
+inline mfcc_center::Geom center_geom(const Resolved &r, int mode) {
+    return mfcc_center::geometry(r.nfft, r.frame_len, r.hop, mode);
+}
+// n of a call's samples at the handle's own rate -> the samples the kernels frame: N'(n) of a centred call
+inline size_t framed_len(const mfcc_hip_handle *h, Samples in, size_t n) {
+    return centred(in) ? mfcc_center::padded(center_geom(h->r, in.center), n) : n;
+}
 
 // The descriptor of a call on h.  The passes behind the kernels belong to the handle's own float output: a spectrum, a
 // filterbank and a fixed-point call run none, whatever the handle is set up for
@@ -1286,10 +1301,11 @@ int launch_float_dev(mfcc_hip_handle *h, const Call &c, const void *d_pcm, size_
     return scratch_release(h);
 }
 
-// ---- the input stage of a dense call (DESIGN.md sections 4.15, 4.17): nch rows of n samples as `in` describes them
-// (n + halo are read; a rate takes no halo) -> int16 rows at the handle's own rate: decoded into h->d_dec, then resampled
-// into h->d_rs by the taps of a (rs_bind) to n2 samples a row.  p / stride: where the rows now lie; the scratch area is
-// taken, the caller releases it behind the kernels that read them
+// ---- the input stage of a dense call (DESIGN.md sections 4.15, 4.17, 4.21): nch rows of n samples as `in` describes them
+// (n + halo are read; a rate and centring take no halo) -> int16 rows at the handle's own rate: decoded into h->d_dec, then
+// resampled into h->d_rs by the taps of a (rs_bind) to n2 samples a row, then centred into h->d_ctr to n3 samples a row.
+// The centring kernel decodes while it pads, so a centred call without a rate runs no decode pass of its own.  p / stride:
+// where the rows now lie; the scratch area is taken, the caller releases it behind the kernels that read them
 struct DenseIn {
     const int16_t *p;
     size_t stride;
@@ -1298,17 +1314,29 @@ struct DenseIn {
 inline size_t rs_stride(size_t n, size_t rows) { return rows <= 1 ? n : (n + 7) & ~size_t(7); }
 
 int dense_input(mfcc_hip_handle *h, Samples in, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo,
-                const mfcc_rs::Taps &a, size_t n2, DenseIn &o) {
+                const mfcc_rs::Taps &a, size_t n2, size_t n3, DenseIn &o) {
     o = DenseIn{static_cast<const int16_t *>(d_pcm), nch <= 1 ? n : stride};
-    int rc;
-    if (decodes(in.fmt) && (rc = decode_to_scratch(h, in.fmt, d_pcm, n + size_t(halo), nch, stride, &o.p, &o.stride))) return rc;
-    if (!in.rate) return MFCC_HIP_SUCCESS;
-    const size_t stride2 = rs_stride(n2, nch);
-    if ((rc = ensure(h, h->d_rs, nch * stride2 * sizeof(int16_t) + 64)) || (rc = scratch_acquire(h))) return rc;
-    mfcc_rs::launch(a, o.p, (long long)n, static_cast<int16_t *>(h->d_rs.p), (long long)n2, (long long)nch, (long long)o.stride,
-                    (long long)stride2, nullptr, 0, h->n_cu, h->stream);
+    int rc, fmt = in.fmt;                   // fmt: the format of the rows at o.p
+    if (decodes(fmt) && (in.rate || !centred(in))) {
+        if ((rc = decode_to_scratch(h, fmt, d_pcm, n + size_t(halo), nch, stride, &o.p, &o.stride))) return rc;
+        fmt = MFCC_HIP_SAMPLE_S16;
+    }
+    if (in.rate) {
+        const size_t stride2 = rs_stride(n2, nch);
+        if ((rc = ensure(h, h->d_rs, nch * stride2 * sizeof(int16_t) + 64)) || (rc = scratch_acquire(h))) return rc;
+        mfcc_rs::launch(a, o.p, (long long)n, static_cast<int16_t *>(h->d_rs.p), (long long)n2, (long long)nch, (long long)o.stride,
+                        (long long)stride2, nullptr, 0, h->n_cu, h->stream);
+        HIP_TRY(h, hipGetLastError());
+        o = DenseIn{static_cast<const int16_t *>(h->d_rs.p), stride2};
+    }
+    if (!centred(in)) return MFCC_HIP_SUCCESS;
+    const size_t stride3 = mfcc_center::dense_stride(n3, nch);
+    if ((rc = ensure(h, h->d_ctr, nch * stride3 * sizeof(int16_t) + 64)) || (rc = scratch_acquire(h))) return rc;
+    if (!mfcc_center::launch_dense(fmt, o.p, static_cast<int16_t *>(h->d_ctr.p), n2, n3, nch, o.stride, stride3,
+                                   center_geom(h->r, in.center), h->n_cu, h->stream))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
     HIP_TRY(h, hipGetLastError());
-    o = DenseIn{static_cast<const int16_t *>(h->d_rs.p), stride2};
+    o = DenseIn{static_cast<const int16_t *>(h->d_ctr.p), stride3};
     return MFCC_HIP_SUCCESS;
 }
 
@@ -1320,7 +1348,9 @@ int dense_dev(mfcc_hip_handle *h, const Call &c, Samples in, const void *d_pcm, 
         return c.fixed ? launch(h, c, p, len, st, nch, halo, d_out, n_frames)
                        : launch_float_dev(h, c, p, len, st, nch, halo, d_out, n_frames);
     };
-    if (!decodes(in.fmt) && !in.rate) return route(d_pcm, n, stride);
+    if (!decodes(in.fmt) && !in.rate && !centred(in)) return route(d_pcm, n, stride);
+    // centring: the fixed-point framing is the RTL's, and a shard of a longer stream has no edges
+    if (centred(in) && (c.fixed || halo == 1)) return MFCC_HIP_ERROR_UNSUPPORTED;
     // what launch() refuses, before anything is read
     if ((!d_pcm && n * nch) || halo < 0 || halo > 1 || !sample_aligned(in.fmt, d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (nch > 1 && stride < n + size_t(halo)) return MFCC_HIP_ERROR_INVALID_PARAM;
@@ -1334,10 +1364,11 @@ int dense_dev(mfcc_hip_handle *h, const Call &c, Samples in, const void *d_pcm, 
         if ((rc = rs_bind(h, in.rate, h->r.sample_rate, a))) return rc;
         n2 = size_t(mfcc_rs::count(n, a.L, a.M));
     }
-    if (count_frames(h->r, n2) == 0 || nch == 0 || !d_out)       // no sample is read
-        return route(d_pcm, n2, in.rate ? rs_stride(n2, nch) : stride);
+    const size_t n3 = framed_len(h, in, n2);                     // the samples of a channel as the kernels frame them
+    if (count_frames(h->r, n3) == 0 || nch == 0 || !d_out)       // no sample is read
+        return route(d_pcm, n3, centred(in) ? mfcc_center::dense_stride(n3, nch) : in.rate ? rs_stride(n2, nch) : stride);
     DenseIn src;
-    if ((rc = dense_input(h, in, d_pcm, n, stride, nch, halo, a, n2, src)) || (rc = route(src.p, n2, src.stride))) return rc;
+    if ((rc = dense_input(h, in, d_pcm, n, stride, nch, halo, a, n2, n3, src)) || (rc = route(src.p, n3, src.stride))) return rc;
     return scratch_release(h);
 }
 
@@ -1528,7 +1559,7 @@ int process_host(mfcc_hip_handle *h, const Call &c, Samples in, const void *pcm,
                  size_t cap, size_t *n_frames) {
     const bool fixed = c.fixed;
     if (!pcm && n * nch) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (fixed && (h->fixed_kernel == FixedKernel::kNone || centred(in))) return MFCC_HIP_ERROR_UNSUPPORTED;
     size_t n2 = n;                              // samples of a channel at the handle's own rate
     if (in.rate) {
         mfcc_rs::Geometry g;
@@ -1537,7 +1568,7 @@ int process_host(mfcc_hip_handle *h, const Call &c, Samples in, const void *pcm,
         if (n >= mfcc_rs::kMaxLen) return MFCC_HIP_ERROR_INVALID_PARAM;
         n2 = size_t(mfcc_rs::count(n, g.L, g.M));
     }
-    const size_t nf = count_frames(h->r, n2);
+    const size_t nf = count_frames(h->r, framed_len(h, in, n2));
     if (n_frames) *n_frames = nf;
     if (nf == 0 || nch == 0) return MFCC_HIP_SUCCESS;
     const size_t ncep = c.out_width;            // elements per row
@@ -1545,8 +1576,8 @@ int process_host(mfcc_hip_handle *h, const Call &c, Samples in, const void *pcm,
     if (!out || cap < n_out) return MFCC_HIP_ERROR_BUFFER_SMALL;
     DeviceGuard guard(h->device);
     const size_t ssz = sample_bytes(in.fmt);
-    if (in.rate) {
-        // an input rate: the unchunked route -- one copy in, the device route, one copy back
+    if (in.rate || centred(in)) {
+        // an input rate, centring: the unchunked route -- one copy in, the device route, one copy back
         int rc;
         if ((rc = ensure(h, h->d_raw, n * nch * ssz + 64)) || (rc = ensure(h, h->d_full, n_out * sizeof(OutT) + 64)) ||
             (rc = scratch_acquire(h)))
@@ -1593,7 +1624,7 @@ int process_host(mfcc_hip_handle *h, const Call &c, Samples in, const void *pcm,
         const HostChunk &k = chunks[i];
         DenseIn src{static_cast<const int16_t *>(d_raw), k.stride};
         int crc;
-        if (dec && (crc = dense_input(h, in, d_raw, k.n, k.stride, k.nch, k.halo, mfcc_rs::Taps{}, k.n, src))) return crc;
+        if (dec && (crc = dense_input(h, in, d_raw, k.n, k.stride, k.nch, k.halo, mfcc_rs::Taps{}, k.n, k.n, src))) return crc;
         void *rows = whole ? static_cast<void *>(d_full + k.out_off) : d_out;
         PostRoute rt{};
         if (post) {
@@ -1734,11 +1765,23 @@ bool rated_offsets(const mfcc_rs::Geometry &g, const size_t *offsets, size_t n_u
     return true;
 }
 
-// ---- the input stage of a ragged call (DESIGN.md sections 4.15, 4.17): the utterances at `offsets` of d_pcm, as `in`
+// the offsets of the centred utterances (center_plan.hpp: fill_table): they abut from 0, F = 0 takes no room.  false:
+// decreasing offsets
+bool centred_offsets(const mfcc_hip_handle *h, int mode, const size_t *own, size_t n_utt, std::vector<size_t> &off3) {
+    off3.assign(n_utt + 1, 0);
+    for (size_t u = 0; u < n_utt; ++u)
+        if (own[u + 1] < own[u]) return false;
+    mfcc_center::fill_table(center_geom(h->r, mode), own, n_utt, 0, off3.data(), nullptr);
+    return true;
+}
+
+// ---- the input stage of a ragged call (DESIGN.md sections 4.15, 4.17, 4.21): the utterances at `offsets` of d_pcm, as `in`
 // describes them -> int16 utterances at the handle's own rate.  The span offsets[0] .. offsets[n_utt] is decoded into
 // h->d_dec; every utterance is then resampled on its own (zeros outside it) by one launch over a tile list into h->d_rs, at
-// `own` (rated_offsets).  p / offsets: where the utterances now lie.  scratch: the area is taken, the caller releases it
-// behind the kernels that read them (int16 at the handle's own rate: nothing is done, nothing taken)
+// `own` (rated_offsets); every utterance is then centred on its own by one launch over a record list into h->d_ctr, at
+// `ctr` (centred_offsets; NULL where the call is not centred).  The centring kernel decodes while it pads, so a centred
+// call without a rate runs no decode pass.  p / offsets: where the utterances now lie.  scratch: the area is taken, the
+// caller releases it behind the kernels that read them (plain int16 at the handle's own rate: nothing is done or taken)
 struct RaggedIn {
     const int16_t *p;
     const size_t *offsets;
@@ -1746,13 +1789,42 @@ struct RaggedIn {
     std::vector<size_t> loc;                // the offsets of a decoded span, from its start
 };
 
-int ragged_input(mfcc_hip_handle *h, Samples in, const void *d_pcm, const size_t *offsets, const size_t *own, size_t n_utt,
-                 RaggedIn &o) {
+// the centring of a ragged call: the utterances at src_off of d_src, in format fmt -> h->d_ctr at ctr, one launch.  d_ctr:
+// the samples, then the records
+int ragged_center(mfcc_hip_handle *h, int mode, int fmt, const void *d_src, const size_t *src_off, const size_t *ctr,
+                  size_t n_utt) {
+    const mfcc_center::Geom g = center_geom(h->r, mode);
+    const size_t rec_off = (ctr[n_utt] * sizeof(int16_t) + 255) & ~size_t(255), rec_ll = n_utt * mfcc_center::kRecLL;
+    int rc;
+    if ((rc = ensure(h, h->d_ctr, rec_off + rec_ll * sizeof(long long) + 64))) return rc;
+    mfcc_hip_handle::PinnedDesc *pd = nullptr;
+    if ((rc = desc_acquire(h, rec_ll, &pd))) return rc;
+    std::vector<size_t> off3(n_utt + 1);
+    const mfcc_center::Table t = mfcc_center::fill_table(g, src_off, n_utt, 0, off3.data(), pd->p);
+    if ((rc = desc_stage(h, h->d_ctr, 0, pd, rec_ll, rec_off))) return rc;
+    if (!t.total) return MFCC_HIP_SUCCESS;
+    if (!mfcc_center::launch_ragged(fmt, d_src, static_cast<int16_t *>(h->d_ctr.p),
+                                    reinterpret_cast<const long long *>(static_cast<const char *>(h->d_ctr.p) + rec_off), n_utt,
+                                    t.max_padded, g, h->n_cu, h->stream))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    HIP_TRY(h, hipGetLastError());
+    return MFCC_HIP_SUCCESS;
+}
+
+int ragged_input(mfcc_hip_handle *h, Samples in, const void *d_pcm, const size_t *offsets, const size_t *own, const size_t *ctr,
+                 size_t n_utt, RaggedIn &o) {
     o.p = static_cast<const int16_t *>(d_pcm);
     o.offsets = offsets;
-    o.scratch = decodes(in.fmt) || in.rate;
+    o.scratch = decodes(in.fmt) || in.rate || centred(in);
     if (!o.scratch) return MFCC_HIP_SUCCESS;
     int rc;
+    if (centred(in) && !in.rate) {
+        // one pass: the kernel reads the caller's samples where they lie and decodes them while it pads
+        if ((rc = ragged_center(h, in.center, in.fmt, d_pcm, offsets, ctr, n_utt))) return rc;
+        o.p = static_cast<const int16_t *>(h->d_ctr.p);
+        o.offsets = ctr;
+        return MFCC_HIP_SUCCESS;
+    }
     mfcc_rs::Taps a;
     if (in.rate && (rc = rs_bind(h, in.rate, h->r.sample_rate, a))) return rc;
     const int16_t *src = o.p + offsets[0];
@@ -1793,17 +1865,22 @@ int ragged_input(mfcc_hip_handle *h, Samples in, const void *d_pcm, const size_t
     }
     o.p = d_rs;
     o.offsets = own;
+    if (!centred(in)) return MFCC_HIP_SUCCESS;
+    if ((rc = ragged_center(h, in.center, MFCC_HIP_SAMPLE_S16, d_rs, own, ctr, n_utt))) return rc;
+    o.p = static_cast<const int16_t *>(h->d_ctr.p);
+    o.offsets = ctr;
     return MFCC_HIP_SUCCESS;
 }
 
-// A scanned corpus on the device, as `in` describes it (own: the offsets at the handle's own rate, which sc has scanned --
-// `offsets` itself without an input rate): what is left to refuse, the input stage, the launch, and the chain over the
+// A scanned corpus on the device, as `in` describes it (own: the offsets at the handle's own rate -- `offsets` itself
+// without an input rate; ctr: those of the centred utterances, NULL where the call is not centred; sc has scanned the last
+// of the three that exists): what is left to refuse, the input stage, the launch, and the chain over the
 // result, one segment per utterance.  A call that stages (deltas, a normalization window, MFCC_HIP_VAD_SELECT) has its
 // kernels write into the staging.  With MFCC_HIP_VAD_SELECT every frame goes through the chain into h->d_final, then only
 // the voiced rows to d_out; frame_offsets describes those, and the call synchronizes (select_run)
 template <typename OutT>
 int ragged_scanned(mfcc_hip_handle *h, const Call &c, Samples in, const void *d_pcm, const size_t *offsets, const size_t *own,
-                   size_t n_utt, OutT *d_out, size_t cap, size_t *frame_offsets, const mfcc_batch::Scan &sc) {
+                   const size_t *ctr, size_t n_utt, OutT *d_out, size_t cap, size_t *frame_offsets, const mfcc_batch::Scan &sc) {
     if (c.fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (sc.max_len && !d_pcm) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (sc.total == 0) return MFCC_HIP_SUCCESS;
@@ -1812,7 +1889,7 @@ int ragged_scanned(mfcc_hip_handle *h, const Call &c, Samples in, const void *d_
     if (!d_out || cap < sc.total * WO) return MFCC_HIP_ERROR_BUFFER_SMALL;    // frame_offsets: the counts, to size d_out by
     DeviceGuard guard(h->device);
     RaggedIn src;
-    int rc = ragged_input(h, in, d_pcm, offsets, own, n_utt, src);
+    int rc = ragged_input(h, in, d_pcm, offsets, own, ctr, n_utt, src);
     if (rc) return rc;
     if (!post) {
         rc = ragged_launch<OutT>(h, c, src.p, src.offsets, n_utt, d_out, frame_offsets, sc);
@@ -1837,9 +1914,10 @@ template <typename OutT>
 int process_ragged_dev(mfcc_hip_handle *h, const Call &c, Samples in, const void *d_pcm, const size_t *offsets, size_t n_utt,
                        OutT *d_out, size_t cap, size_t *frame_offsets) {
     if (!offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (centred(in) && c.fixed) return MFCC_HIP_ERROR_UNSUPPORTED;          // the fixed-point framing is the RTL's
     const bool dec = decodes(in.fmt) && n_utt;
     if ((!dec || in.rate) && c.fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
-    std::vector<size_t> off2;
+    std::vector<size_t> off2, off3;
     if (in.rate) {
         mfcc_rs::Geometry g;
         const int rc = rs_geometry(in.rate, h->r.sample_rate, g);
@@ -1847,9 +1925,11 @@ int process_ragged_dev(mfcc_hip_handle *h, const Call &c, Samples in, const void
         if (!rated_offsets(g, offsets, n_utt, off2) || !sample_aligned(in.fmt, d_pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
     }
     const size_t *own = in.rate ? off2.data() : offsets;
-    const mfcc_batch::Scan sc = ragged_scan(h, own, n_utt, frame_offsets);
+    if (centred(in) && !centred_offsets(h, in.center, own, n_utt, off3)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    const size_t *ctr = centred(in) ? off3.data() : nullptr;
+    const mfcc_batch::Scan sc = ragged_scan(h, ctr ? ctr : own, n_utt, frame_offsets);
     if (sc.rc || (dec && !sample_aligned(in.fmt, d_pcm))) return MFCC_HIP_ERROR_INVALID_PARAM;
-    return ragged_scanned<OutT>(h, c, in, d_pcm, offsets, own, n_utt, d_out, cap, frame_offsets, sc);
+    return ragged_scanned<OutT>(h, c, in, d_pcm, offsets, own, ctr, n_utt, d_out, cap, frame_offsets, sc);
 }
 
 // Host buffers: the corpus goes to the device in ONE copy (the span offsets[0] .. offsets[n_utt] as it lies), runs through
@@ -1861,24 +1941,27 @@ int process_ragged(mfcc_hip_handle *h, const Call &c, Samples in, const void *pc
                    OutT *out, size_t cap, size_t *frame_offsets) {
     const bool fixed = c.fixed;
     if (!offsets || !frame_offsets) return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (fixed && (h->fixed_kernel == FixedKernel::kNone || centred(in))) return MFCC_HIP_ERROR_UNSUPPORTED;
     const size_t ncep = c.out_width;                                     // elements per row
-    std::vector<size_t> off2;                                            // an input rate: the offsets at the handle's own
+    std::vector<size_t> off2, off3;                                      // an input rate: the offsets at the handle's own;
+                                                                         // centring: those of the padded utterances
     if (in.rate) {
         mfcc_rs::Geometry g;
         const int rc = rs_geometry(in.rate, h->r.sample_rate, g);
         if (rc) return rc;
         if (!rated_offsets(g, offsets, n_utt, off2)) return MFCC_HIP_ERROR_INVALID_PARAM;
     }
-    const mfcc_batch::Scan sc = ragged_scan(h, in.rate ? off2.data() : offsets, n_utt, frame_offsets);
+    if (centred(in) && !centred_offsets(h, in.center, in.rate ? off2.data() : offsets, n_utt, off3))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    const mfcc_batch::Scan sc = ragged_scan(h, centred(in) ? off3.data() : in.rate ? off2.data() : offsets, n_utt, frame_offsets);
     if (sc.rc || (sc.max_len && !pcm)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (sc.total == 0) return MFCC_HIP_SUCCESS;                          // frame_offsets: all zero
     if (!out || cap < sc.total * ncep) return MFCC_HIP_ERROR_BUFFER_SMALL;      // the counts, so that the caller can size `out`
     DeviceGuard guard(h->device);
     const size_t ssz = sample_bytes(in.fmt);
     std::vector<size_t> loc, fo;
-    if (in.rate) {
-        // an input rate: the unchunked route -- one copy in, the device route, one copy back
+    if (in.rate || centred(in)) {
+        // an input rate, centring: the unchunked route -- one copy in, the device route, one copy back
         loc.resize(n_utt + 1);
         for (size_t u = 0; u <= n_utt; ++u) loc[u] = offsets[u] - offsets[0];
         const size_t in_bytes = loc[n_utt] * ssz, n_out = sc.total * ncep;
@@ -1887,8 +1970,9 @@ int process_ragged(mfcc_hip_handle *h, const Call &c, Samples in, const void *pc
             (rc = scratch_acquire(h)))
             return rc;
         HIP_TRY(h, hipMemcpyAsync(h->d_raw.p, sample_at(in.fmt, pcm, offsets[0]), in_bytes, hipMemcpyHostToDevice, h->stream));
-        if ((rc = ragged_scanned<OutT>(h, c, in, h->d_raw.p, loc.data(), off2.data(), n_utt, static_cast<OutT *>(h->d_full.p),
-                                       n_out, frame_offsets, sc)))
+        if ((rc = ragged_scanned<OutT>(h, c, in, h->d_raw.p, loc.data(), in.rate ? off2.data() : loc.data(),
+                                       centred(in) ? off3.data() : nullptr, n_utt, static_cast<OutT *>(h->d_full.p), n_out,
+                                       frame_offsets, sc)))
             return rc;
         // MFCC_HIP_VAD_SELECT: frame_offsets now counts the voiced rows (the call above has synchronized)
         HIP_TRY(h, hipMemcpyAsync(out, h->d_full.p, frame_offsets[n_utt] * ncep * sizeof(OutT), hipMemcpyDeviceToHost, h->stream));
@@ -1921,7 +2005,7 @@ int process_ragged(mfcc_hip_handle *h, const Call &c, Samples in, const void *pc
         const mfcc_batch::Scan csc =
             mfcc_batch::scan_with(loc.data(), k, size_t(kRaggedTiles.tile),
                                   [&](size_t u, size_t) { return counts[r.u0 + u + 1] - counts[r.u0 + u]; }, fo.data());
-        const int rc = ragged_scanned<OutT>(h, c, in, d_in, loc.data(), loc.data(), k, static_cast<OutT *>(d_out),
+        const int rc = ragged_scanned<OutT>(h, c, in, d_in, loc.data(), loc.data(), nullptr, k, static_cast<OutT *>(d_out),
                                             pc[i].out_bytes / sizeof(OutT), fo.data(), csc);
         const size_t rows0 = sel_mode ? sel_rows : r.rows0;
         for (size_t j = 1; j <= k; ++j) frame_offsets[r.u0 + j] = rows0 + fo[j];
@@ -2216,7 +2300,7 @@ void mfcc_hip_destroy(mfcc_hip_handle *h) {
     if (h->arena) (void)hipFree(h->arena);
     if (h->fb_dev) (void)hipFree(h->fb_dev);
     for (DevBuf *b : {&h->d_in, &h->d_out, &h->d_norm, &h->d_pcen, &h->d_full, &h->d_stat, &h->d_dtab, &h->d_slide, &h->d_stab,
-                      &h->d_vad, &h->d_voiced, &h->d_sel, &h->d_final, &h->d_dec, &h->d_raw, &h->d_rs_tab, &h->d_rs})
+                      &h->d_vad, &h->d_voiced, &h->d_sel, &h->d_final, &h->d_dec, &h->d_raw, &h->d_rs_tab, &h->d_rs, &h->d_ctr})
         if (b->p) (void)hipFree(b->p);
     delete h;
 }
@@ -2779,6 +2863,70 @@ int mfcc_hip_set_input_rate(mfcc_hip_handle *h, int in_rate) {
 
 int mfcc_hip_input_rate(const mfcc_hip_handle *h) { return h ? h->input_rate : 0; }
 
+// ---- centring (include/mfcc_hip.h: "centring"): the geometry, the host rule, the direct entry
+static int center_resolve(const mfcc_hip_params *p, int frame_length, int mode, mfcc_center::Geom &g) {
+    Resolved r;
+    const int rc = resolve_framed(p, frame_length, r);
+    if (rc) return rc;
+    if (mode != MFCC_HIP_CENTER_REFLECT && mode != MFCC_HIP_CENTER_ZEROS) return MFCC_HIP_ERROR_INVALID_PARAM;
+    g = center_geom(r, mode);
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_center_geometry(const mfcc_hip_params *p, int frame_length, int mode, size_t n, size_t *n_frames, size_t *left,
+                             size_t *padded) {
+    mfcc_center::Geom g;
+    const int rc = center_resolve(p, frame_length, mode, g);
+    if (rc) return rc;
+    if (n_frames) *n_frames = mfcc_center::frames(g, n);
+    if (left) *left = size_t(g.left);
+    if (padded) *padded = mfcc_center::padded(g, n);
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_center_host(const mfcc_hip_params *p, int frame_length, int mode, const int16_t *in, size_t n, int16_t *out,
+                         size_t cap, size_t *n_out) {
+    mfcc_center::Geom g;
+    const int rc = center_resolve(p, frame_length, mode, g);
+    if (rc) return rc;
+    const size_t np = mfcc_center::padded(g, n);
+    if (n_out) *n_out = np;
+    if (cap < np) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    if (np && (!in || !out)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (np) mfcc_center::center_host(g, in, n, out);
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_center_dev(mfcc_hip_handle *h, int mode, int format, const void *d_in, size_t n, void *d_out, size_t cap,
+                        size_t *n_out) {
+    if (!h || !mfcc_decode::known(format) || (mode != MFCC_HIP_CENTER_REFLECT && mode != MFCC_HIP_CENTER_ZEROS))
+        return MFCC_HIP_ERROR_INVALID_PARAM;
+    const mfcc_center::Geom g = center_geom(h->r, mode);
+    const size_t np = mfcc_center::padded(g, n);
+    if (n_out) *n_out = np;
+    if (cap < np) return MFCC_HIP_ERROR_BUFFER_SMALL;
+    if (!np) return MFCC_HIP_SUCCESS;
+    const size_t size = mfcc_decode::sample_size(format);
+    const uintptr_t i_lo = reinterpret_cast<uintptr_t>(d_in), o_lo = reinterpret_cast<uintptr_t>(d_out);
+    if (!d_in || !d_out || (i_lo & (size - 1)) || (o_lo & 1)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (ranges_overlap(i_lo, i_lo + n * size, o_lo, o_lo + np * sizeof(int16_t))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    DeviceGuard guard(h->device);
+    mfcc_center::launch_dense(format, d_in, static_cast<int16_t *>(d_out), n, np, 1, n, np, g, h->n_cu, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_set_center(mfcc_hip_handle *h, int mode) {
+    if (!h || !mfcc_center::known(mode)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
+    // the padded signal is framed by MFCC_HIP_PAD_NOTEBOOK: the stream rule would add a zero-padded frame behind it
+    if (mode != MFCC_HIP_CENTER_OFF && h->r.pad_mode != MFCC_HIP_PAD_NOTEBOOK) return MFCC_HIP_ERROR_UNSUPPORTED;
+    h->center = mode;
+    return MFCC_HIP_SUCCESS;
+}
+
+int mfcc_hip_center(const mfcc_hip_handle *h) { return h ? h->center : MFCC_HIP_CENTER_OFF; }
+
 // float coefficients -> the int16 a `.mfcc` file holds: astype(np.int16) of software/lift.py:39 (truncate)
 static inline int16_t to_mfcc_i16(float v) {
     if (!(v == v)) v = 0.0f;
@@ -2792,13 +2940,14 @@ int mfcc_hip_convert_wav(mfcc_hip_handle *h, const char *wav_in, const char *mfc
     if (!h || !wav_in || !mfcc_out) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
     if (has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;   // ... raw ones, n_cep wide, of every frame
+    if (fixed && h->center) return MFCC_HIP_ERROR_UNSUPPORTED;  // the fixed-point framing is the RTL's
     std::vector<int16_t> pcm;
     int rc = read_wav_i16(wav_in, rated(h) ? h->input_rate : h->r.sample_rate, pcm);
     if (rc) return rc;
-    const size_t nf = count_frames(h->r, own_rate_len(h, pcm.size()));
+    const size_t nf = count_frames(h->r, framed_len(h, samples_of(h), own_rate_len(h, pcm.size())));
     std::vector<int16_t> cep(nf * size_t(h->r.n_cep));
     // the file's 16-bit PCM, whatever the handle's sample format, at the rate the handle reads
-    const Samples pcm16{MFCC_HIP_SAMPLE_S16, h->input_rate};
+    const Samples pcm16{MFCC_HIP_SAMPLE_S16, h->input_rate, h->center};
     if (fixed) {
         rc = process_host<int16_t>(h, call_of(h, Kind::kFeatures, true), pcm16, pcm.data(), pcm.size(), 1, cep.data(), cep.size(), nullptr);
         if (rc) return rc;
@@ -2822,6 +2971,7 @@ int mfcc_hip_convert_wavs(mfcc_hip_handle *h, const char *const *wav_in, const c
     if (!h || (n_files && (!wav_in || !mfcc_out))) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (is_logmel(h->r)) return MFCC_HIP_ERROR_UNSUPPORTED;     // a .mfcc file holds cepstra
     if (has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;   // ... raw ones, n_cep wide, of every frame
+    if (fixed && h->center) return MFCC_HIP_ERROR_UNSUPPORTED;  // the fixed-point framing is the RTL's
     std::vector<int16_t> pcm;
     std::vector<size_t> off(n_files + 1, 0), fo(n_files + 1, 0);
     for (size_t i = 0; i < n_files; ++i) {
@@ -2833,11 +2983,11 @@ int mfcc_hip_convert_wavs(mfcc_hip_handle *h, const char *const *wav_in, const c
         off[i + 1] = pcm.size();
     }
     size_t total = 0;
-    for (size_t i = 0; i < n_files; ++i) total += count_frames(h->r, own_rate_len(h, off[i + 1] - off[i]));
+    for (size_t i = 0; i < n_files; ++i) total += count_frames(h->r, framed_len(h, samples_of(h), own_rate_len(h, off[i + 1] - off[i])));
     const size_t ncep = size_t(h->r.n_cep);
     std::vector<int16_t> cep(total * ncep);
     int rc;
-    const Samples pcm16{MFCC_HIP_SAMPLE_S16, h->input_rate};
+    const Samples pcm16{MFCC_HIP_SAMPLE_S16, h->input_rate, h->center};
     if (fixed) {
         rc = process_ragged<int16_t>(h, call_of(h, Kind::kFeatures, true), pcm16, pcm.data(), off.data(), n_files, cep.data(),
                                      cep.size(), fo.data());
@@ -2935,6 +3085,7 @@ int mfcc_hip_stream_create(mfcc_hip_handle *h, int fixed, mfcc_hip_stream **out)
     if (h->post.delta_order) return MFCC_HIP_ERROR_UNSUPPORTED;     // deltas need 2 K N frames of lookahead
     if (h->post.vad_mode) return MFCC_HIP_ERROR_UNSUPPORTED;        // the threshold's mean is a whole-segment statistic
     if (rated(h)) return MFCC_HIP_ERROR_UNSUPPORTED;           // a line's rate conversion keeps state between pushes
+    if (h->center) return MFCC_HIP_ERROR_UNSUPPORTED;          // a centred line holds back PL + 1 samples, flushes several frames
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     mfcc_hip_stream *s = new (std::nothrow) mfcc_hip_stream();
     if (!s) return MFCC_HIP_ERROR_NO_MEM;
@@ -3394,6 +3545,7 @@ int bank_create_checked(mfcc_hip_handle *h, Kind kind, int fixed, bool online, s
     const bool fb = kind == Kind::kFbank;
     if (fb ? !h->fb_dev : has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (rated(h)) return MFCC_HIP_ERROR_UNSUPPORTED;           // a line's rate conversion keeps state between pushes
+    if (h->center) return MFCC_HIP_ERROR_UNSUPPORTED;          // a centred line holds back PL + 1 samples, flushes several frames
     if (p && !(fb ? h->fb_scale == MFCC_HIP_FBANK_LOG2 : is_logmel(h->r))) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (fixed && h->fixed_kernel == FixedKernel::kNone) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (online && h->r.float_impl == MFCC_HIP_IMPL_FUSED512 && !is_fused512(h->float_kernel)) return MFCC_HIP_ERROR_UNSUPPORTED;
@@ -3896,6 +4048,7 @@ int mfcc_hip_resampler_plan(int in_rate, int out_rate, const size_t *seen, const
 int mfcc_hip_resampler_create(mfcc_hip_handle *h, size_t n_lines, int sample_format, int in_rate, int out_rate,
                               mfcc_hip_resampler **out) {
     if (live_check(h, n_lines, out) || !mfcc_decode::known(sample_format)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (h->center) return MFCC_HIP_ERROR_UNSUPPORTED;          // its lines feed a bank, and a centred handle has none
     mfcc_rs::Geometry g;
     std::vector<int16_t> t;
     const int rc = rs_table(in_rate, out_rate, g, t);
