@@ -436,8 +436,9 @@ const char *mfcc_hip_spectrum_kernel_name(const mfcc_hip_handle *h);
  * There is no fixed-point form.  Live lines take these rows through mfcc_hip_bank_create_filterbank (a stream bank, with
  * causal CMVN, deltas and PCEN of its own; a bank of one line is the session).  The post-pass direct entries (mfcc_hip_normalize_dev,
  * mfcc_hip_deltas_dev, mfcc_hip_pcen_dev, mfcc_hip_vad_dev) keep their width limit of 64: rows of up to 64 bands may be
- * fed to them by the caller; wider post-passes do not exist.  The parameter block, ABI version 2, n_mel 1..64 and every
- * limit of 64 are unchanged. */
+ * fed to them by the caller; wider rows get their post-passes behind the three compute entries below, from the settings
+ * of section "filterbank post-passes".  The parameter block, ABI version 2, n_mel 1..64 and every limit of 64 are
+ * unchanged. */
 #define MFCC_HIP_MAX_FBANK_BANDS 128
 
 enum mfcc_hip_fbank_scale {
@@ -485,6 +486,39 @@ const char *mfcc_hip_fbank_kernel_name(const mfcc_hip_handle *h);
  * MFCC_HIP_ERROR_BUFFER_SMALL. */
 int  mfcc_hip_htk_weights(int nfft, int sample_rate, int n_bands, float low_hz, float high_hz, float *out,
                           size_t cap_floats, size_t *n_floats);
+
+/* ---- filterbank post-passes ----------------------------------------------------------------
+ * The matrix may carry post-pass settings OF ITS OWN: PCEN, per-segment or sliding normalization and deltas behind
+ * mfcc_hip_fbank_i16_dev, mfcc_hip_fbank_ragged_i16_dev and mfcc_hip_fbank_i16, on rows of up to 128 bands, one segment
+ * per channel or utterance.  They are the passes of the sections "per-segment normalization", "sliding-window
+ * normalization", "PCEN" and "deltas" below, in that chain's order -- PCEN in place on the raw rows, then the
+ * normalization, then deltas -- with those sections' arithmetic: a column of a row of 65 .. 128 floats gets the bits the
+ * direct entries give the same column of a slice of at most 64 columns (sliding normalization, PCEN, deltas), and a
+ * segment's per-segment statistics depend on the row width and the segment's rows alone.  The rows of a segment are the
+ * same bits from the three entries and from any chunking of the copy pipeline.
+ *
+ * The handle's own settings (mfcc_hip_set_normalize, _set_normalize_window, _set_deltas, _set_pcen, _set_vad) still do
+ * NOT apply to a filterbank call, and these do not apply to any other call.  There is no VAD and no selection here: the
+ * energy VAD decides on C0 or one named band and a filterbank has no C0; rows of up to 64 bands can still go to
+ * mfcc_hip_vad_dev.
+ *
+ * normalize: enum mfcc_hip_normalize; normalize_window 0 (per segment) or 1 .. MFCC_HIP_MAX_NORMALIZE_WINDOW with
+ * 1 <= normalize_min_window <= normalize_window and normalize_center 0 / 1 (the rules of mfcc_hip_set_normalize_window);
+ * delta_order 0 .. 2 and delta_window 1 .. MFCC_HIP_MAX_DELTA_WINDOW (those of mfcc_hip_set_deltas; the window is checked
+ * at order 0 too); pcen_on 0 / 1, pcen as mfcc_hip_set_pcen takes it (looked at only with pcen_on).  Anything else, a
+ * wrong struct_size or a non-zero reserved word: MFCC_HIP_ERROR_INVALID_PARAM.  p == NULL: none.  On a handle without
+ * a matrix (p == NULL included), and with pcen_on unless the matrix's scale is MFCC_HIP_FBANK_LOG2 (PCEN reads log2
+ * energies): MFCC_HIP_ERROR_UNSUPPORTED.  While a filterbank bank of the handle lives: MFCC_HIP_ERROR_BUSY.  A refused
+ * call leaves the settings as they were.  mfcc_hip_set_fbank -- a new matrix or NULL -- RESETS them to none: they were
+ * checked against the old matrix's scale and width.  mfcc_hip_bank_create_filterbank on a handle that has such settings:
+ * MFCC_HIP_ERROR_UNSUPPORTED (a bank takes its settings at creation and its frame launch is the raw kernel).
+ *
+ * With settings, rows are mfcc_hip_filterbank_row_width(h) = n_bands * (1 + delta_order) floats wide, [ s | D | DD ]:
+ * size buffers and out_capacity by it.  A call with halo = 1 and settings: MFCC_HIP_ERROR_UNSUPPORTED, as
+ * mfcc_hip_process_i16_dev answers.  Sample format, input rate and centring in front compose as before.
+ *
+ * The struct embeds a mfcc_hip_pcen, so it and the two functions are declared behind section "PCEN":
+ * mfcc_hip_filterbank_post, mfcc_hip_set_filterbank_post, mfcc_hip_filterbank_row_width. */
 
 /* ---- per-segment normalization (enum mfcc_hip_normalize) -------------------------------------------------------
  * The handle's mode applies to every float call enqueued after it: mfcc_hip_process_i16, mfcc_hip_process_i16_dev,
@@ -677,6 +711,24 @@ int  mfcc_hip_set_pcen(mfcc_hip_handle *h, const mfcc_hip_pcen *p);
  * the handle's stream; n_segs = 0 is a no-op.  E.g. the gathered rows of a frame-range-sharded stream.            */
 int  mfcc_hip_pcen_dev(mfcc_hip_handle *h, void *d_rows, int row_width, const size_t *seg_offsets, size_t n_segs,
                        const mfcc_hip_pcen *p);
+
+/* the settings of section "filterbank post-passes" */
+typedef struct mfcc_hip_filterbank_post {
+    uint32_t struct_size;          /* sizeof(mfcc_hip_filterbank_post) */
+    int32_t  normalize;            /* enum mfcc_hip_normalize */
+    int32_t  normalize_window;     /* 0: per segment */
+    int32_t  normalize_min_window;
+    int32_t  normalize_center;
+    int32_t  delta_order;          /* 0 .. 2 */
+    int32_t  delta_window;         /* 1 .. MFCC_HIP_MAX_DELTA_WINDOW */
+    int32_t  pcen_on;              /* 0 / 1 */
+    mfcc_hip_pcen pcen;
+    int32_t  reserved[4];          /* must be 0 */
+} mfcc_hip_filterbank_post;
+
+int    mfcc_hip_set_filterbank_post(mfcc_hip_handle *h, const mfcc_hip_filterbank_post *p /* NULL: none */);
+/* floats of a row of the three filterbank compute entries: n_bands * (1 + delta_order); 0 without a matrix or handle */
+size_t mfcc_hip_filterbank_row_width(const mfcc_hip_handle *h);
 
 /* ---- sample formats ----------------------------------------------------------------------
  * What a sample pointer holds is a property of the handle.  Every format is decoded to int16 on the device by one

@@ -147,6 +147,22 @@ class Fbank(C.Structure):
     ]
 
 
+class FilterbankPost(C.Structure):
+    """struct mfcc_hip_filterbank_post"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("normalize", C.c_int32),
+        ("normalize_window", C.c_int32),
+        ("normalize_min_window", C.c_int32),
+        ("normalize_center", C.c_int32),
+        ("delta_order", C.c_int32),
+        ("delta_window", C.c_int32),
+        ("pcen_on", C.c_int32),
+        ("pcen", Pcen),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 MAX_FBANK_BANDS = 128
 FBANK_ENERGY, FBANK_LOG2, FBANK_LN, FBANK_LOG10 = 0, 1, 2, 3
 
@@ -325,6 +341,9 @@ SYMBOLS = {
     # ... and the bank of live lines on those rows (p may be NULL)
     "mfcc_hip_bank_create_filterbank": (C.c_int, [_H, _SZ, C.POINTER(Pcen), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
     "mfcc_hip_htk_weights": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, _SZ, _PSZ]),
+    # the post-passes behind the three compute entries (p may be NULL) and the row width they give
+    "mfcc_hip_set_filterbank_post": (C.c_int, [_H, C.POINTER(FilterbankPost)]),
+    "mfcc_hip_filterbank_row_width": (C.c_size_t, [_H]),
 }
 
 _lib = None

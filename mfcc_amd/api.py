@@ -939,7 +939,7 @@ class MFCC(_Owner):
         if entry not in self._ENTRIES:
             raise ValueError("unknown entry %r" % (entry,))
         if entry == "fbank":
-            return self.num_bands
+            return self.num_filterbank_columns
         if entry == "spectrum":
             return self.num_bins
         return self.nceptrums if fixed else self.num_features
@@ -1098,17 +1098,50 @@ class MFCC(_Owner):
         ``rows`` the dense ``(sum frames, nfft // 2 + 1)`` tensor, bit-identical to one ``power_spectrum`` per utterance."""
         return self._packed(flat, offsets, False, out, "spectrum")
 
-    def set_filterbank(self, weights, scale="log2", floor=0.0):
+    def set_filterbank(self, weights, scale="log2", floor=0.0, *, normalize=None, normalize_window=None,
+                       normalize_min_window=_MIN_WINDOW, normalize_center=True, deltas=0, delta_window=2, pcen=None):
         """Give the handle a filter matrix for ``filterbank``: ``weights`` a NumPy array or a torch tensor of shape
         ``(n_bands, nfft // 2 + 1)``, 1..128 bands, every weight finite and not negative (copied to the host once, as
         float32); ``scale`` one of ``"energy"``, ``"log2"``, ``"ln"``, ``"log10"``; ``floor`` the log scales' floor
         (finite, >= 0; with 0 an empty band gives ``-inf``).  ``None`` removes the matrix.  Calls enqueued before keep the
-        matrix they were enqueued with."""
+        matrix they were enqueued with.
+
+        The keywords are the matrix's own post-passes behind ``filterbank`` / ``filterbank_packed``, with the meaning and
+        defaults of the handle's keywords of the same names (which still do not apply to filterbank rows): PCEN
+        (``pcen``: ``True`` or a dict, ``"log2"`` only), then utterance or sliding CMVN (``normalize``,
+        ``normalize_window`` ...), then deltas -- on up to 128 bands, one segment per channel or utterance, rows
+        ``num_filterbank_columns = num_bands * (1 + deltas)`` wide.  Every ``set_filterbank`` replaces them (``None`` and
+        a call without keywords: none).  With them ``halo=1`` and ``stream_bank(filterbank=True)`` raise
+        ``UNSUPPORTED``."""
+        mode = normalize_mode(normalize)
+        w_, m_, c_ = _window_args(normalize_window, normalize_min_window, normalize_center)
+        order, dwin = _delta_args(deltas, delta_window)
+        pc = _pcen_args(pcen, self.samplerate, self.hop)
+        post = mode != _lib.NORMALIZE_NONE or w_ or order or pc is not None
         if weights is None:
+            if post:
+                raise ValueError("filterbank post-passes need a matrix: weights=None takes no keywords")
             _lib.check(self._lib.mfcc_hip_set_fbank(self._h, None, None), "set_fbank")
             return
+        if pc is not None and scale != "log2":
+            raise ValueError("pcen reads log2 band energies: scale must be 'log2', not %r" % (scale,))
         p, w = _fbank_args(weights, scale, floor, self.num_bins)
         _lib.check(self._lib.mfcc_hip_set_fbank(self._h, C.byref(p), ptr(w)), "set_fbank")
+        if not post:
+            return                  # mfcc_hip_set_fbank has reset them
+        q = _lib.FilterbankPost()
+        q.struct_size = C.sizeof(_lib.FilterbankPost)
+        q.normalize, q.normalize_window, q.normalize_min_window, q.normalize_center = mode, w_, m_, c_
+        q.delta_order, q.delta_window = order, dwin
+        if pc is not None:
+            q.pcen_on, q.pcen = 1, pc
+        _lib.check(self._lib.mfcc_hip_set_filterbank_post(self._h, C.byref(q)), "set_filterbank_post")
+
+    @property
+    def num_filterbank_columns(self) -> int:
+        """Width of a ``filterbank`` row as the calls return it: ``num_bands * (1 + deltas)`` with the ``deltas`` of
+        ``set_filterbank``; 0 without a matrix."""
+        return int(self._lib.mfcc_hip_filterbank_row_width(self._h))
 
     def filterbank_kernel_name(self) -> str:
         """The kernel ``filterbank`` runs: ``mfcc_fbank512_kernel``, ``mfcc_fbank_generic_kernel``, or ``""`` without a
@@ -1119,7 +1152,8 @@ class MFCC(_Owner):
         """Band energies under the matrix of ``set_filterbank``: PCM ``(n,)`` / ``(channels, n)`` in the handle's sample
         format and rate -> float32 ``(.., frames, num_bands)``, row ``f`` = ``W @ power_spectrum row f`` in the matrix's
         scale, contracted on the chip.  Arguments, device checks, streams and ``out`` as for ``power_spectrum``.  The
-        handle's own filterbank, output kind, normalization, deltas, PCEN and VAD do not apply."""
+        handle's own filterbank, output kind, normalization, deltas, PCEN and VAD do not apply; the post-passes given to
+        ``set_filterbank`` do, one segment per channel, and make the rows ``num_filterbank_columns`` wide."""
         if _is_torch(pcm):
             return self._dev(pcm, False, halo, out, entry="fbank")
         if halo:
@@ -1130,7 +1164,8 @@ class MFCC(_Owner):
 
     def filterbank_packed(self, flat, offsets, out=None):
         """``filterbank`` of a corpus that lies in HBM, as ``power_spectrum_packed`` takes it: ``(rows, frame_offsets)``
-        with ``rows`` the dense ``(sum frames, num_bands)`` tensor, bit-identical to one ``filterbank`` per utterance."""
+        with ``rows`` the dense ``(sum frames, num_filterbank_columns)`` tensor, bit-identical to one ``filterbank`` per
+        utterance (``set_filterbank``'s post-passes included: every utterance is a segment)."""
         return self._packed(flat, offsets, False, out, "fbank")
 
     def process_fixed(self, pcm, halo=0, out=None):

@@ -17,17 +17,33 @@
 // and DD of every tile row into an LDS copy of the tile's output, in the output's own layout.  Last, the tile's
 // T * W * (1 + K) contiguous output floats leave with float4 stores (the copy is placed so that its 16-byte boundaries
 // are those of the output).  K and N are template parameters: the taps unroll.  No atomics.
+//
+// These lines are compiled twice, as kernel_normalize.hpp's are: as mfcc_delta::deltas_kernel over
+// 16 KB of LDS in mfcc_hip.hip, and as mfcc_delta_wide::deltas_wide_kernel over post_plan.hpp's kDeltaWideLdsFloats in
+// post_wide.hip (MFCC_POST_WIDE_UNIT), for rows of 65 .. 128 floats.  delta_at is the same lines in both: a column gets the
+// same bits from either.  At 128 x (1 + 2) the int products stay small: a tile's output is at most kLdsFloats floats.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "kernel_normalize.hpp"
+#include "post_plan.hpp"
 
-namespace mfcc_delta {
+#ifdef MFCC_POST_WIDE_UNIT
+#define MFCC_DELTA_NS mfcc_delta_wide
+#define MFCC_DELTA_LDS_FLOATS mfcc_post::kDeltaWideLdsFloats
+#define MFCC_DELTAS_KERNEL deltas_wide_kernel
+#else
+#define MFCC_DELTA_NS mfcc_delta
+#define MFCC_DELTA_LDS_FLOATS 4096
+#define MFCC_DELTAS_KERNEL deltas_kernel
+#endif
+
+namespace MFCC_DELTA_NS {
 
 constexpr int kThreads = 256;
-constexpr int kLdsFloats = 4096;       // 16 KB of LDS per workgroup (eight per CU): static rows, (K = 2) D rows, output tile
+constexpr int kLdsFloats = MFCC_DELTA_LDS_FLOATS;      // 16 KB of LDS per workgroup (eight per CU): static rows, (K = 2) D rows, output tile
 constexpr int kMaxWidth = mfcc_norm::kMaxWidth;
 constexpr int kMaxWindow = 8;
 
@@ -37,8 +53,7 @@ using mfcc_norm::f32x4;
 // (T + 4N) W static + (T + 2N) W delta + T 3W output floats; 8 floats of slack for the alignment of the output copy.
 // At least 3 rows for every W <= 64, N <= 8 (60 at W = 13, K = N = 2)
 __host__ __device__ inline int tile_rows(int width, int order, int window) {
-    const int per = (kLdsFloats - 8) / width;
-    return order == 1 ? (per - 2 * window) / 3 : (per - 6 * window) / 5;
+    return mfcc_post::delta_tile_rows_of(kLdsFloats, width, order, window);
 }
 
 // r32 = (float)(1 / (2 sum_{n=1..N} n^2))
@@ -58,8 +73,8 @@ __device__ __forceinline__ float delta_at(const float *src, int W, float r32) {
 }
 
 template <int K, int N>
-__global__ __launch_bounds__(kThreads) void deltas_kernel(const float *__restrict__ x, float *__restrict__ y,
-                                                          mfcc_norm::Segs s, float r32) {
+__global__ __launch_bounds__(kThreads) void MFCC_DELTAS_KERNEL(const float *__restrict__ x, float *__restrict__ y,
+                                                               mfcc_norm::Segs s, float r32) {
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
     constexpr int H = K * N;                                      // static rows staged on each side of the tile
     const int W = s.width, WO = W * (1 + K), t = threadIdx.x, T = s.tile_rows;
@@ -162,12 +177,12 @@ __global__ __launch_bounds__(kThreads) void deltas_kernel(const float *__restric
 typedef void (*DeltasKernel)(const float *__restrict__, float *__restrict__, mfcc_norm::Segs, float);
 inline DeltasKernel deltas_kernel_of(int order, int window) {
     static const DeltasKernel k[2][kMaxWindow] = {
-        {deltas_kernel<1, 1>, deltas_kernel<1, 2>, deltas_kernel<1, 3>, deltas_kernel<1, 4>, deltas_kernel<1, 5>,
-         deltas_kernel<1, 6>, deltas_kernel<1, 7>, deltas_kernel<1, 8>},
-        {deltas_kernel<2, 1>, deltas_kernel<2, 2>, deltas_kernel<2, 3>, deltas_kernel<2, 4>, deltas_kernel<2, 5>,
-         deltas_kernel<2, 6>, deltas_kernel<2, 7>, deltas_kernel<2, 8>}};
+#define MFCC_DK MFCC_DELTAS_KERNEL
+        {MFCC_DK<1, 1>, MFCC_DK<1, 2>, MFCC_DK<1, 3>, MFCC_DK<1, 4>, MFCC_DK<1, 5>, MFCC_DK<1, 6>, MFCC_DK<1, 7>, MFCC_DK<1, 8>},
+        {MFCC_DK<2, 1>, MFCC_DK<2, 2>, MFCC_DK<2, 3>, MFCC_DK<2, 4>, MFCC_DK<2, 5>, MFCC_DK<2, 6>, MFCC_DK<2, 7>, MFCC_DK<2, 8>}};
+#undef MFCC_DK
     if (order < 1 || order > 2 || window < 1 || window > kMaxWindow) return nullptr;
     return k[order - 1][window - 1];
 }
 
-}  // namespace mfcc_delta
+}  // namespace mfcc_delta / mfcc_delta_wide

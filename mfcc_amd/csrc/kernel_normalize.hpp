@@ -13,6 +13,12 @@
 // Every order of summation is a function of W and of the segment's rows alone (the 16-byte-aligned float4 body of
 // a tile only decides how the bytes reach LDS or registers): a segment gives the same bits wherever it lies, in
 // whatever call.  No atomics.
+//
+// These lines are compiled twice.  In the MFCC kernels' unit, mfcc_hip.hip, they are namespace
+// mfcc_norm with width-sized LDS arrays of 64 columns, as they always were.  In post_wide.hip (MFCC_POST_WIDE_UNIT) they
+// are namespace mfcc_norm_wide with arrays of 128 columns and kernels named *_wide_kernel: the filterbank post-passes'
+// rows of 65 .. 128 floats.  Nothing else differs: the tile is kTileFloats in both, G = 256 / W is 3 for 65 .. 85 and 2
+// for 86 .. 128, and a thread with g >= G reads mean_s[c] with c = t % W < W like any other.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -20,11 +26,31 @@
 
 #include "seg_plan.hpp"      // Segs, BlockRec, tile_of: shared with the host planner
 
-namespace mfcc_norm {
+#ifdef MFCC_POST_WIDE_UNIT
+#define MFCC_NORM_NS mfcc_norm_wide
+#define MFCC_NORM_MAX_WIDTH 128
+#define MFCC_NORM_STATS_KERNEL normalize_stats_wide_kernel
+#define MFCC_NORM_FINALIZE_KERNEL normalize_finalize_wide_kernel
+#define MFCC_NORM_APPLY_KERNEL normalize_apply_wide_kernel
+#else
+#define MFCC_NORM_NS mfcc_norm
+#define MFCC_NORM_MAX_WIDTH 64
+#define MFCC_NORM_STATS_KERNEL normalize_stats_kernel
+#define MFCC_NORM_FINALIZE_KERNEL normalize_finalize_kernel
+#define MFCC_NORM_APPLY_KERNEL normalize_apply_kernel
+#endif
+
+namespace MFCC_NORM_NS {
+
+#ifdef MFCC_POST_WIDE_UNIT
+using mfcc_norm::Segs;
+using mfcc_norm::BlockRec;
+using mfcc_norm::tile_of;
+#endif
 
 constexpr int kThreads = 256;
 constexpr int kTileFloats = 8192;      // 32 KB of LDS per stats workgroup
-constexpr int kMaxWidth = 64;
+constexpr int kMaxWidth = MFCC_NORM_MAX_WIDTH;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -46,7 +72,7 @@ __device__ __forceinline__ int head_of(long long e0, int n, unsigned mis) {
     return head < n ? head : n;
 }
 
-__global__ __launch_bounds__(kThreads) void normalize_stats_kernel(const float *__restrict__ x, Segs s,
+__global__ __launch_bounds__(kThreads) void MFCC_NORM_STATS_KERNEL(const float *__restrict__ x, Segs s,
                                                                    Part *__restrict__ part) {
     __shared__ float tile[kTileFloats];
     __shared__ double red[kThreads];
@@ -135,7 +161,7 @@ __device__ __forceinline__ void chan(double &n, double &m, double &q, double nb,
 }
 
 // mode: 1 = mean only (r = 1), 2 = mean and variance.  coef[seg][col] = (mu, r), fp32
-__global__ __launch_bounds__(kThreads) void normalize_finalize_kernel(Segs s, const Part *__restrict__ part,
+__global__ __launch_bounds__(kThreads) void MFCC_NORM_FINALIZE_KERNEL(Segs s, const Part *__restrict__ part,
                                                                       float2 *__restrict__ coef, int mode) {
     __shared__ double sn[kThreads], sm[kThreads], sq[kThreads];
     const int W = s.width, G = kThreads / W, t = threadIdx.x, c = t % W, g = t / W;
@@ -179,7 +205,7 @@ __global__ __launch_bounds__(kThreads) void normalize_finalize_kernel(Segs s, co
 
 __device__ __forceinline__ float apply1(float v, float2 cf) { return finite(v) ? (v - cf.x) * cf.y : v; }
 
-__global__ __launch_bounds__(kThreads) void normalize_apply_kernel(float *__restrict__ x, Segs s,
+__global__ __launch_bounds__(kThreads) void MFCC_NORM_APPLY_KERNEL(float *__restrict__ x, Segs s,
                                                                    const float2 *__restrict__ coef) {
     __shared__ float2 cf[kMaxWidth];
     const int W = s.width, t = threadIdx.x;
@@ -216,4 +242,13 @@ __global__ __launch_bounds__(kThreads) void normalize_apply_kernel(float *__rest
     }
 }
 
+}  // namespace mfcc_norm / mfcc_norm_wide
+
+#ifdef MFCC_POST_WIDE_UNIT
+// what kernel_deltas.hpp takes from mfcc_norm by name: in this unit, the wide unit's
+namespace mfcc_norm {
+using mfcc_norm_wide::f32x4;
+using mfcc_norm_wide::head_of;
+using mfcc_norm_wide::kMaxWidth;
 }  // namespace mfcc_norm
+#endif

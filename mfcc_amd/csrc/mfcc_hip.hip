@@ -42,6 +42,7 @@
 #include "kernel_center.hpp"
 #include "kernel_spectrum.hpp"
 #include "kernel_fbank.hpp"
+#include "post_wide.hpp"
 #include "tables.hpp"
 
 namespace {
@@ -96,7 +97,7 @@ struct Call {
     bool fixed;
     size_t width;              // floats (fixed: int16) of a row as the kernel writes it
     size_t out_width;          // ... and as the call returns it: width times 1 + the delta order
-    const Post &post;          // the handle's for a float features call, else kNoPost
+    const Post &post;          // the handle's for a float features call, its fb_post for a filterbank call, else kNoPost
 };
 
 // The kernel a handle's float calls run; build_tables decides it when the handle is made.
@@ -305,6 +306,9 @@ struct mfcc_hip_handle {
     mfcc_fbank::Tables fb{};
     int fb_scale = MFCC_HIP_FBANK_ENERGY;
     bool fb_used = false;
+    // the passes behind the one-shot filterbank calls (mfcc_hip_set_filterbank_post): the matrix's, so mfcc_hip_set_fbank
+    // resets them; never a VAD.  `post` below does not apply to a filterbank call, and this does not apply to any other
+    Post fb_post;
     // the 1024 forms: one of the two is bound, the one float_kernel names
     mfcc_fused1024::Tables f1k{};          // bf16-split contraction, set lists for every rate (kernel_fused1024.hpp)
     mfcc_fused1024_f32::Tables f1k_f32{};  // fp32 contraction, one MFMA list per rate (kernel_fused1024_f32.hpp)
@@ -553,10 +557,12 @@ inline size_t framed_len(const mfcc_hip_handle *h, Samples in, size_t n) {
     return centred(in) ? mfcc_center::padded(center_geom(h->r, in.center), n) : n;
 }
 
-// The descriptor of a call on h.  The passes behind the kernels belong to the handle's own float output: a spectrum, a
-// filterbank and a fixed-point call run none, whatever the handle is set up for
+// The descriptor of a call on h.  The handle's own passes behind the kernels belong to its own float output: a spectrum
+// and a fixed-point call run none, whatever the handle is set up for, and a filterbank call runs the matrix's
+// (h->fb_post, mfcc_hip_set_filterbank_post).  A filterbank bank's frame launch gets kNoPost through this too: a bank
+// cannot exist together with those settings (bank_create_checked, mfcc_hip_set_filterbank_post)
 inline Call call_of(const mfcc_hip_handle *h, Kind kind, bool fixed) {
-    const Post &post = kind == Kind::kFeatures && !fixed ? h->post : kNoPost;
+    const Post &post = kind == Kind::kFeatures && !fixed ? h->post : kind == Kind::kFbank ? h->fb_post : kNoPost;
     const size_t w = kind == Kind::kFbank      ? size_t(h->fb.n_bands)
                      : kind == Kind::kSpectrum ? size_t(mfcc_spec::bins(h->r.nfft))
                                                : row_width(h->r);
@@ -1001,13 +1007,21 @@ inline unsigned tile_grid(long long n) { return unsigned(std::min<long long>(n, 
 
 // ---- per-segment mean / variance normalization (kernel_normalize.hpp): in place.
 // Scratch (h->d_norm): [tile partials: n_blocks * W * 24 B][coefficients: n_segs * W * 8 B][tile table]
+// Rows of more than 64 floats (a filterbank call's; the direct entry refuses them) go to the wide kernels of post_wide.hip:
+// the same tiles, the same scratch
 int normalize_pass(mfcc_hip_handle *h, float *d_rows, int width, const SegSpan &sp, int mode) {
     if (span_empty(sp) || mode == MFCC_HIP_NORMALIZE_NONE) return MFCC_HIP_SUCCESS;
+    static_assert(mfcc_norm::kTileFloats == mfcc_post::kNormTileFloats && mfcc_norm::kMaxWidth == mfcc_post::kNarrowWidth, "post_plan.hpp");
     const size_t W = size_t(width);
     const Area areas[] = {{W * sizeof(mfcc_norm::Part), 0, 0}, {0, W * sizeof(float2), 0}};
     Staged st;
     const int rc = seg_stage(h, sp, width, mfcc_norm::tile_rows(width), nullptr, h->d_norm, areas, 2, st);
     if (rc) return rc;
+    if (mfcc_post::wide_rows(width)) {
+        mfcc_post_wide::launch_normalize(d_rows, st.s, st.area[0], st.area[1], mode, h->n_cu, h->stream);
+        HIP_TRY(h, hipGetLastError());
+        return scratch_release(h);
+    }
     auto *part = reinterpret_cast<mfcc_norm::Part *>(st.area[0]);
     auto *coef = reinterpret_cast<float2 *>(st.area[1]);
     const mfcc_norm::Segs &s = st.s;
@@ -1032,6 +1046,14 @@ bool pcen_ok(const mfcc_hip_pcen *p) {
     return p->s > 0.0f && p->s <= 1.0f && p->alpha >= 0.0f && p->alpha <= 1.0f && p->delta >= 0.0f && p->r > 0.0f &&
            p->r <= 1.0f && p->eps > 0.0f;
 }
+
+// what mfcc_hip_set_normalize, _set_normalize_window and _set_deltas take, and mfcc_hip_set_filterbank_post with them
+inline bool normalize_mode_ok(int mode) { return mode >= MFCC_HIP_NORMALIZE_NONE && mode <= MFCC_HIP_NORMALIZE_MEAN_VAR; }
+inline bool normalize_window_ok(int window, int min_window, int center) {
+    if (center < 0 || center > 1 || window < 0 || window > MFCC_HIP_MAX_NORMALIZE_WINDOW) return false;
+    return !window || (min_window >= 1 && min_window <= window);
+}
+inline bool deltas_ok(int order, int window) { return order >= 0 && order <= 2 && window >= 1 && window <= MFCC_HIP_MAX_DELTA_WINDOW; }
 
 // the constants of the tile form: float64 on the host, rounded once
 mfcc_pcen::Prm pcen_prm(const mfcc_hip_pcen &p) {
@@ -1070,12 +1092,21 @@ int pcen_pass(mfcc_hip_handle *h, float *d_rows, int width, const SegSpan &sp, c
 }
 
 // ---- delta coefficients (kernel_deltas.hpp): out of place, the last step of post_chain.  The
-// tile table of a ragged call goes to h->d_dtab
+// tile table of a ragged call goes to h->d_dtab.  Rows of more than 64 floats (a filterbank call's; the direct entry refuses
+// them) go to the wide kernel of post_wide.hip, on its larger tiles
 int deltas_pass(mfcc_hip_handle *h, const float *d_in, float *d_out, int width, const SegSpan &sp, int order, int window) {
     if (span_empty(sp)) return MFCC_HIP_SUCCESS;
+    static_assert(mfcc_delta::kLdsFloats == mfcc_post::kDeltaLdsFloats && mfcc_delta::kMaxWidth == mfcc_post::kNarrowWidth, "post_plan.hpp");
+    const bool wide = mfcc_post::wide_rows(width);
+    const int tile = wide ? mfcc_post::delta_wide_tile_rows(width, order, window) : mfcc_delta::tile_rows(width, order, window);
     Staged st;
-    const int rc = seg_stage(h, sp, width, mfcc_delta::tile_rows(width, order, window), nullptr, h->d_dtab, nullptr, 0, st);
+    const int rc = seg_stage(h, sp, width, tile, nullptr, h->d_dtab, nullptr, 0, st);
     if (rc) return rc;
+    if (wide) {
+        if (!mfcc_post_wide::launch_deltas(d_in, d_out, st.s, order, window, h->n_cu, h->stream)) return MFCC_HIP_ERROR_INVALID_PARAM;
+        HIP_TRY(h, hipGetLastError());
+        return scratch_release(h);
+    }
     const mfcc_delta::DeltasKernel kernel = mfcc_delta::deltas_kernel_of(order, window);
     if (!kernel) return MFCC_HIP_ERROR_INVALID_PARAM;
     hipLaunchKernelGGL(kernel, dim3(tile_grid(st.s.n_blocks)), dim3(mfcc_delta::kThreads), 0, h->stream, d_in, d_out, st.s,
@@ -2497,6 +2528,7 @@ int mfcc_hip_set_fbank(mfcc_hip_handle *h, const mfcc_hip_fbank *p, const float 
     h->fb_dev = dev;
     h->fb = mfcc_fbank::Tables{};
     h->fb_used = false;
+    h->fb_post = Post{};        // the settings were the old matrix's: checked against its scale, sized by its width
     if (p) {
         const char *b = static_cast<const char *>(dev);
         h->fb.w = reinterpret_cast<const float *>(b);
@@ -2520,11 +2552,43 @@ int mfcc_hip_fbank_bands(const mfcc_hip_handle *h, size_t *n_bands) {
     return MFCC_HIP_SUCCESS;
 }
 
+// ---- the filterbank post-passes (include/mfcc_hip.h: "filterbank post-passes"): a Post of the
+// matrix's own, which call_of hands to every Kind::kFbank call; the routes and the chain are the MFCC calls'
+int mfcc_hip_set_filterbank_post(mfcc_hip_handle *h, const mfcc_hip_filterbank_post *p) {
+    if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
+    Post q{};
+    if (p) {
+        if (p->struct_size != sizeof(mfcc_hip_filterbank_post)) return MFCC_HIP_ERROR_INVALID_PARAM;
+        for (int v : p->reserved)
+            if (v != 0) return MFCC_HIP_ERROR_INVALID_PARAM;
+        if (!normalize_mode_ok(p->normalize) || !normalize_window_ok(p->normalize_window, p->normalize_min_window, p->normalize_center) ||
+            !deltas_ok(p->delta_order, p->delta_window) || p->pcen_on < 0 || p->pcen_on > 1 || (p->pcen_on && !pcen_ok(&p->pcen)))
+            return MFCC_HIP_ERROR_INVALID_PARAM;
+        q.norm = p->normalize;
+        q.norm_window = p->normalize_window;
+        q.norm_min_window = p->normalize_window ? p->normalize_min_window : 1;
+        q.norm_center = p->normalize_center;
+        q.delta_order = p->delta_order;
+        q.delta_window = p->delta_window;
+        q.pcen_on = p->pcen_on != 0;
+        if (q.pcen_on) q.pcen = pcen_prm(p->pcen);
+    }
+    if (!h->fb_dev) return MFCC_HIP_ERROR_UNSUPPORTED;
+    if (q.pcen_on && h->fb_scale != MFCC_HIP_FBANK_LOG2) return MFCC_HIP_ERROR_UNSUPPORTED;      // PCEN reads log2 energies
+    if (h->n_fbank_banks > 0) return MFCC_HIP_ERROR_BUSY;      // a bank's frame launch is the raw kernel of this handle
+    h->fb_post = q;
+    return MFCC_HIP_SUCCESS;
+}
+
+size_t mfcc_hip_filterbank_row_width(const mfcc_hip_handle *h) {
+    return h ? size_t(h->fb.n_bands) * size_t(1 + h->fb_post.delta_order) : 0;
+}
+
 int mfcc_hip_fbank_i16_dev(mfcc_hip_handle *h, const void *d_pcm, size_t n, size_t stride, size_t nch, int halo, void *d_out,
                            size_t *n_frames) {
     if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (!h->fb_dev) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (!mfcc_fbank::call_fits(n, nch, size_t(h->fb.n_bands))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!mfcc_fbank::call_fits(n, nch, mfcc_hip_filterbank_row_width(h))) return MFCC_HIP_ERROR_INVALID_PARAM;
     return dense_dev(h, call_of(h, Kind::kFbank, false), samples_of(h), d_pcm, n, stride, nch, halo, d_out, n_frames);
 }
 
@@ -2534,7 +2598,7 @@ int mfcc_hip_fbank_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const s
     if (!h->fb_dev) return MFCC_HIP_ERROR_UNSUPPORTED;
     // the row count times the bands must fit (decreasing offsets are the route's to refuse)
     if (offsets && n_utt && offsets[n_utt] >= offsets[0] &&
-        !mfcc_fbank::ragged_fits(offsets[n_utt] - offsets[0], n_utt, size_t(h->fb.n_bands)))
+        !mfcc_fbank::ragged_fits(offsets[n_utt] - offsets[0], n_utt, mfcc_hip_filterbank_row_width(h)))
         return MFCC_HIP_ERROR_INVALID_PARAM;
     return process_ragged_dev<float>(h, call_of(h, Kind::kFbank, false), samples_of(h), d_pcm, offsets, n_utt,
                                      static_cast<float *>(d_out), cap, frame_offsets);
@@ -2543,7 +2607,7 @@ int mfcc_hip_fbank_ragged_i16_dev(mfcc_hip_handle *h, const void *d_pcm, const s
 int mfcc_hip_fbank_i16(mfcc_hip_handle *h, const int16_t *pcm, size_t n, size_t nch, float *out, size_t cap, size_t *n_frames) {
     if (!h) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (!h->fb_dev) return MFCC_HIP_ERROR_UNSUPPORTED;
-    if (!mfcc_fbank::call_fits(n, nch, size_t(h->fb.n_bands))) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!mfcc_fbank::call_fits(n, nch, mfcc_hip_filterbank_row_width(h))) return MFCC_HIP_ERROR_INVALID_PARAM;
     return process_host<float>(h, call_of(h, Kind::kFbank, false), samples_of(h), pcm, n, nch, out, cap, n_frames);
 }
 
@@ -2569,7 +2633,7 @@ int mfcc_hip_htk_weights(int nfft, int sample_rate, int n_bands, float low_hz, f
 }
 
 int mfcc_hip_set_normalize(mfcc_hip_handle *h, int mode) {
-    if (!h || mode < MFCC_HIP_NORMALIZE_NONE || mode > MFCC_HIP_NORMALIZE_MEAN_VAR) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!h || !normalize_mode_ok(mode)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
     h->post.norm = mode;
     return MFCC_HIP_SUCCESS;
@@ -2626,9 +2690,7 @@ int mfcc_hip_pcen_dev(mfcc_hip_handle *h, void *d_rows, int row_width, const siz
 }
 
 int mfcc_hip_set_normalize_window(mfcc_hip_handle *h, int window, int min_window, int center) {
-    if (!h || center < 0 || center > 1 || window < 0 || window > MFCC_HIP_MAX_NORMALIZE_WINDOW)
-        return MFCC_HIP_ERROR_INVALID_PARAM;
-    if (window && (min_window < 1 || min_window > window)) return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!h || !normalize_window_ok(window, min_window, center)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
     h->post.norm_window = window;
     h->post.norm_min_window = window ? min_window : 1;
@@ -2657,8 +2719,7 @@ int mfcc_hip_normalize_sliding_dev(mfcc_hip_handle *h, const void *d_in, int row
 }
 
 int mfcc_hip_set_deltas(mfcc_hip_handle *h, int order, int window) {
-    if (!h || order < 0 || order > 2 || window < 1 || window > MFCC_HIP_MAX_DELTA_WINDOW)
-        return MFCC_HIP_ERROR_INVALID_PARAM;
+    if (!h || !deltas_ok(order, window)) return MFCC_HIP_ERROR_INVALID_PARAM;
     if (h->n_sessions > 0) return MFCC_HIP_ERROR_BUSY;
     h->post.delta_order = order;
     h->post.delta_window = window;
@@ -3543,7 +3604,8 @@ int bank_create_checked(mfcc_hip_handle *h, Kind kind, int fixed, bool online, s
                         int normalize, int normalize_window, int delta_order, int delta_window, mfcc_hip_bank **out) {
     if (live_check(h, n_streams, out) || (p && !pcen_ok(p))) return MFCC_HIP_ERROR_INVALID_PARAM;
     const bool fb = kind == Kind::kFbank;
-    if (fb ? !h->fb_dev : has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;
+    // a bank takes its settings at creation and its frame launch is the raw kernel: no settings of the handle's behind it
+    if (fb ? !h->fb_dev || has_post(h->fb_post) : has_post(h->post)) return MFCC_HIP_ERROR_UNSUPPORTED;
     if (rated(h)) return MFCC_HIP_ERROR_UNSUPPORTED;           // a line's rate conversion keeps state between pushes
     if (h->center) return MFCC_HIP_ERROR_UNSUPPORTED;          // a centred line holds back PL + 1 samples, flushes several frames
     if (p && !(fb ? h->fb_scale == MFCC_HIP_FBANK_LOG2 : is_logmel(h->r))) return MFCC_HIP_ERROR_UNSUPPORTED;
